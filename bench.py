@@ -5,11 +5,16 @@ One "step" = one SyncDDIMSampler.denoise_apply (reference morphable_diffusion.py
 views of one sample with classifier-free guidance (UNet batch 2N), full-width UNet, 5023-vertex FLAME-sized
 synthetic mesh, 256x256 images (32x32 latents).  Inputs are resident in HBM before the timed region.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (views sharded)
 
 Prints ONE JSON line (rank 0).  With N GPUs the 16 views are partitioned over the ranks (strong scaling:
 total work fixed) and the only per-step exchange is one RCCL all-reduce of the [Nv,16] fused vertex features.
+
+A plain run sets up, warms up, times K steps and prints the line.  --full adds what the headline figure does not need:
+the per-family kernel survey and the roofline of the dominant family (event brackets inside the timed region), the
+50-step trajectory and VAE decode, and the CPU baseline.  --dump-outputs DIR writes what the last timed step returned
+(DIR/<name>.npy, float32): with the same arguments the inputs are identical from run to run.
 """
 import argparse
 import json
@@ -62,6 +67,36 @@ def rocprof_us_per_launch(family, config):
         return d["us_per_launch"].get(family)
     except (OSError, ValueError, KeyError):
         return None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """``--dump-outputs DIR``: each tensor of ``arrays`` as DIR/<name>.npy in float32.  An array that would take the total past
+    ``limit`` bytes is written as a fixed, seeded sample of its flattened elements instead (<name>.sample.npy)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    used = 0
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().contiguous()
+        if used + 4 * a.numel() > limit:
+            k = max(0, (limit - used) // 4)
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            a, name = a.flatten()[idx], name + ".sample"
+        np.save(os.path.join(out_dir, name + ".npy"), a.numpy().astype(np.float32))
+        used += 4 * a.numel()
+
+
+def gather_ranks(x, world):
+    """Every rank's ``x`` concatenated along dim 1 in rank order, on every rank: this rank's views [B, N_local, ...] ->
+    all views [B, N, ...] (a rank's views are one contiguous range, SyncDDIMSampler.view_range)."""
+    if world == 1:
+        return x
+    import torch.distributed as dist
+    parts = [None] * world
+    dist.all_gather_object(parts, x.cpu())
+    return torch.cat(parts, 1)
 
 
 def unet_kwargs(cfg):
@@ -320,6 +355,10 @@ def train_main(args):
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs:  # what training_step returned in the last timed step, one loss per rank
+        loss = gather_ranks(torch.as_tensor(losses[-1], dtype=torch.float32).reshape(1, 1), world)
+        if rank == 0:
+            write_outputs(args.dump_outputs, {"loss": loss.flatten()})
     lv = [float(l) for l in losses]
     assert all(v == v and abs(v) < 1e6 for v in lv), lv
     if rank == 0:
@@ -353,12 +392,17 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-family kernel survey and the roofline "
+                         "of the dominant family, the 50-step trajectory and VAE decode, and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-thread-point", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the 50-step trajectory and the VAE decode reported next to the headline (profiling runs: the "
-                         "process then executes only identical denoising steps)")
+                    help="with --full: skip the 50-step trajectory and the VAE decode reported next to the headline (profiling "
+                         "runs: the process then executes only identical denoising steps)")
     ap.add_argument("--batch-view-num", type=int, default=0, help="views per UNet pass (0 = all local views)")
     ap.add_argument("--train-batch", type=int, default=8, help="--config train: samples per GPU and step")
     ap.add_argument("--train-vertices", type=int, default=5023,
@@ -376,7 +420,8 @@ def main():
                          "64^2 latents, orthographic cameras, 4 views per UNet pass); train = configs[3]'s unit of work, one training step "
                          "(forward, loss, UNet backward, gradient all-reduce, AdamW, re-pack).  Only 'headline' is the headline value")
     ap.add_argument("--probe-stride", type=int, default=4,
-                    help="bracket 1 in N launches of the dominant kernel family with HIP events inside the timed region")
+                    help="with --full: bracket 1 in N launches of the dominant kernel family with HIP events inside the timed "
+                         "region")
     ap.add_argument("--simulate-gpus", type=int, default=0,
                     help="timing aid: run ONE rank's share of a G-way view sharding on one GPU (no collective); "
                          "reported as a per-rank step time, never as the headline value")
@@ -434,8 +479,9 @@ def main():
     ucfg = UNetConfig(image_size=CFG["size"] // 8)
     vcfg = VolumeConfig(num_views=N_VIEWS, projection=CFG["proj"], input_image_size=CFG["size"])
     W = seeded_state_dict(full_manifest(ucfg, vcfg), 7)  # random-init weights of the reference architecture
-    from morphablediffusion_amd.spec import VaeConfig, vae_decoder_manifest
-    W.update(seeded_state_dict(vae_decoder_manifest(VaeConfig()), 7))  # first-stage decoder (reported separately)
+    if args.full:
+        from morphablediffusion_amd.spec import VaeConfig, vae_decoder_manifest
+        W.update(seeded_state_dict(vae_decoder_manifest(VaeConfig()), 7))  # first-stage decoder (reported separately)
     model = SyncMultiviewDiffusion(
         unet_config={"target": "ldm.models.diffusion.attention.DepthWiseAttention", "params": unet_kwargs(ucfg)},
         projection=CFG["proj"], view_num=N_VIEWS, image_size=CFG["size"], cfg_scale=2.0, device=dev, workspace_gb=48.0)
@@ -453,47 +499,55 @@ def main():
     batch = {k: v.to(dev) for k, v in synthetic.make_batch(N_VIEWS, CFG["proj"], CFG["nverts"], mesh_seed=1,
                                                             image_size=CFG["size"], radii=CFG["radii"]).items()}
     x_T, x_in, clip = [t.to(dev) for t in synthetic.make_latents(N_VIEWS, lat, seed=6033)]
-    x = x_T[:, lo:hi].contiguous()
+    x = x_start = x_T[:, lo:hi].contiguous()
     info = {"x": x_in}
     g = torch.Generator(device=dev).manual_seed(123)
     noise = torch.randn(1, N_VIEWS, 4, lat, lat, device=dev, generator=g)[:, lo:hi].contiguous()
     nsteps = len(sampler.ddim_timesteps)
 
     def one_step(i, xx):
+        # step i of a sequence of DDIM trajectories: every nsteps steps a new one starts from x_T, as SyncDDIMSampler.sample
+        # does.  (Feeding a finished trajectory's output back in as the next one's noise grows x until it overflows to inf)
+        if i % nsteps == 0:
+            xx = x_start
         index = nsteps - 1 - (i % nsteps)
         step = int(sampler.ddim_timesteps[index])
         ts = sampler._time_steps(1, step, dev)  # as SyncDDIMSampler.sample does: one resident tensor per DDIM step value
         return sampler.denoise_apply(xx, info, clip, ts, index, 2.0, batch_view_num=bvn, is_step0=index == 0,
                                      batch=batch, noise=noise, host_steps=[step])
 
+    dominant = None
     with torch.no_grad():
         for i in range(args.warmup):
             x = one_step(i, x)
-        # survey pass (NOT timed): HIP events on the launch stream around EVERY launch of every kernel family for two
-        # steps -> per-family table (time, algorithmic FLOPs / bytes); the family with the largest summed time is the
-        # dominant kernel, and only that one is bracketed (a 1-in-stride sample of its launches) in the timed region
-        model.engine.probe_config(1)
-        for i in range(2):
-            x = one_step(args.warmup + i, x)
-        torch.cuda.synchronize()
-        families = model.engine.probe_report()
-        model.engine.probe_config(0)
-        # what an event bracket adds to a launch's own duration: pairs of events with nothing between them, recorded by the
-        # survey pass on the same stream after every 8th launch; subtracted per bracketed launch below (rocprofv3's kernel
-        # durations, which the roofline must agree with, do not contain it)
-        # ... measured two ways: an EMPTY bracket (event overhead alone) and a bracket around a NULL kernel (event overhead +
-        # the dispatch latency between the first event and the kernel's first wave).  The second is what separates an event
-        # bracket from rocprofv3's begin-to-end kernel duration (round 5 subtracted the first: 16 % high on a 45 us kernel)
-        empty = [f for f in families if f["family"] == "(empty bracket)"]
-        nullk = [f for f in families if f["family"] == "(null-kernel bracket)"]
-        families = [f for f in families if not f["family"].startswith("(")]
-        empty_ms = (empty[0]["ms"] / empty[0]["sampled"]) if empty and empty[0]["sampled"] else 0.0
-        null_ms = (nullk[0]["ms"] / nullk[0]["sampled"]) if nullk and nullk[0]["sampled"] else 0.0
-        bracket_ms = null_ms if null_ms > 0 else empty_ms
-        for f in families:
-            f["ms_raw"] = f["ms"]
-            f["ms"] = max(f["ms"] - f["sampled"] * bracket_ms, 0.5 * f["ms"])
-        dominant = max(families, key=lambda f: f["ms"])["family"] if families else None
+        first = args.warmup  # step counter of the first timed step
+        if args.full:
+            # survey pass (NOT timed): HIP events on the launch stream around EVERY launch of every kernel family for two
+            # steps -> per-family table (time, algorithmic FLOPs / bytes); the family with the largest summed time is the
+            # dominant kernel, and only that one is bracketed (a 1-in-stride sample of its launches) in the timed region
+            model.engine.probe_config(1)
+            for i in range(2):
+                x = one_step(args.warmup + i, x)
+            torch.cuda.synchronize()
+            families = model.engine.probe_report()
+            model.engine.probe_config(0)
+            # what an event bracket adds to a launch's own duration: pairs of events with nothing between them, recorded by the
+            # survey pass on the same stream after every 8th launch; subtracted per bracketed launch below (rocprofv3's kernel
+            # durations, which the roofline must agree with, do not contain it)
+            # ... measured two ways: an EMPTY bracket (event overhead alone) and a bracket around a NULL kernel (event overhead +
+            # the dispatch latency between the first event and the kernel's first wave).  The second is what separates an event
+            # bracket from rocprofv3's begin-to-end kernel duration (round 5 subtracted the first: 16 % high on a 45 us kernel)
+            empty = [f for f in families if f["family"] == "(empty bracket)"]
+            nullk = [f for f in families if f["family"] == "(null-kernel bracket)"]
+            families = [f for f in families if not f["family"].startswith("(")]
+            empty_ms = (empty[0]["ms"] / empty[0]["sampled"]) if empty and empty[0]["sampled"] else 0.0
+            null_ms = (nullk[0]["ms"] / nullk[0]["sampled"]) if nullk and nullk[0]["sampled"] else 0.0
+            bracket_ms = null_ms if null_ms > 0 else empty_ms
+            for f in families:
+                f["ms_raw"] = f["ms"]
+                f["ms"] = max(f["ms"] - f["sampled"] * bracket_ms, 0.5 * f["ms"])
+            dominant = max(families, key=lambda f: f["ms"])["family"] if families else None
+            first += 2
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
@@ -501,7 +555,7 @@ def main():
             model.engine.probe_config(2, dominant, args.probe_stride)
         t0 = time.perf_counter()
         for i in range(args.steps):
-            x = one_step(args.warmup + 2 + i, x)
+            x = one_step(first + i, x)
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -512,81 +566,75 @@ def main():
         dt = float(tt.item())
     assert torch.isfinite(x).all()
 
-    timed = {f["family"]: f for f in model.engine.probe_report()} if dominant else {}
-    model.engine.probe_config(0)
-    for f in timed.values():
-        f["ms_raw"] = f["ms"]
-        f["ms"] = max(f["ms"] - f["sampled"] * bracket_ms, 0.5 * f["ms"])
+    if args.dump_outputs:  # what denoise_apply returned in the last timed step: x_prev of every view
+        x_all = gather_ranks(x, world)
+        if rank == 0:
+            write_outputs(args.dump_outputs, {"x_prev": x_all})
 
-    # reported next to the headline value ("plus 50-step wall-time"): one full 50-step DDIM trajectory
-    # through SyncDDIMSampler.sample, and the first-stage decode of this rank's views
-    extras = {"ddim50_wall_s": None, "vae_decode_ms": None}
-    try:
-        if args.no_extras:
-            raise RuntimeError("skipped (--no-extras)")
-        gen = torch.Generator(device=dev).manual_seed(6033)
-        torch.cuda.synchronize()
-        if world > 1:
-            dist.barrier()
-        t1 = time.perf_counter()
-        import contextlib
-        with torch.no_grad(), contextlib.redirect_stdout(sys.stderr):  # sample() prints like the reference does
-            x50, _ = sampler.sample(info, clip, unconditional_scale=2.0, batch_view_num=bvn, batch=batch, generator=gen)
-        torch.cuda.synchronize()
-        extras["ddim50_wall_s"] = time.perf_counter() - t1
-        zl = x50[0, lo:hi].contiguous()
-        model.decode_first_stage(zl)
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        img = model.decode_first_stage(zl)
-        torch.cuda.synchronize()
-        extras["vae_decode_ms"] = 1e3 * (time.perf_counter() - t1)
-        assert torch.isfinite(img).all() and tuple(img.shape) == (nl, 3, CFG["size"], CFG["size"])
-    except Exception as exc:  # never lose the headline line to an extra
-        print(f"bench extras failed: {exc!r}", file=sys.stderr)
+    full = {}  # --full: what is measured beside the headline figure
+    if args.full:
+        timed = {f["family"]: f for f in model.engine.probe_report()} if dominant else {}
+        model.engine.probe_config(0)
+        for f in timed.values():
+            f["ms_raw"] = f["ms"]
+            f["ms"] = max(f["ms"] - f["sampled"] * bracket_ms, 0.5 * f["ms"])
 
-    # Roofline of the dominant kernel family (largest summed time in the survey pass).  For the bracketed launches of the
-    # timed region:  t_mfma = sum(flops) / peak,  t_hbm = sum(algorithmic bytes) / peak;  the larger one is the roof that
-    # bounds the family, `achieved` is the family's aggregate rate in that roof's unit, frac = achieved / peak.
-    def roof(f):
-        t = f["ms"] * 1e-3
-        if t <= 0 or f["sampled"] == 0:
-            return None
-        tf, tb = f["flops"] / (PEAK_F16_TFLOPS * 1e12), f["bytes"] / (PEAK_HBM_GBS * 1e9)
-        bound = "mfma" if tf >= tb else "hbm"
-        return {"bound": bound, "achieved": (f["flops"] / t / 1e12) if bound == "mfma" else (f["bytes"] / t / 1e9),
-                "peak": PEAK_F16_TFLOPS if bound == "mfma" else PEAK_HBM_GBS, "unit": "TFLOP/s" if bound == "mfma" else "GB/s",
-                "tflops": f["flops"] / t / 1e12, "gbs": f["bytes"] / t / 1e9, "us_per_launch": 1e6 * t / f["sampled"],
-                "us_per_launch_raw": 1e3 * f.get("ms_raw", f["ms"]) / f["sampled"],
-                "launches_bracketed": f["sampled"], "launches": f["launches"]}
+        # reported next to the headline value ("plus 50-step wall-time"): one full 50-step DDIM trajectory
+        # through SyncDDIMSampler.sample, and the first-stage decode of this rank's views
+        extras = {"ddim50_wall_s": None, "vae_decode_ms": None}
+        try:
+            if args.no_extras:
+                raise RuntimeError("skipped (--no-extras)")
+            gen = torch.Generator(device=dev).manual_seed(6033)
+            torch.cuda.synchronize()
+            if world > 1:
+                dist.barrier()
+            t1 = time.perf_counter()
+            import contextlib
+            with torch.no_grad(), contextlib.redirect_stdout(sys.stderr):  # sample() prints like the reference does
+                x50, _ = sampler.sample(info, clip, unconditional_scale=2.0, batch_view_num=bvn, batch=batch, generator=gen)
+            torch.cuda.synchronize()
+            extras["ddim50_wall_s"] = time.perf_counter() - t1
+            zl = x50[0, lo:hi].contiguous()
+            model.decode_first_stage(zl)
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            img = model.decode_first_stage(zl)
+            torch.cuda.synchronize()
+            extras["vae_decode_ms"] = 1e3 * (time.perf_counter() - t1)
+            assert torch.isfinite(img).all() and tuple(img.shape) == (nl, 3, CFG["size"], CFG["size"])
+        except Exception as exc:  # never lose the headline line to an extra
+            print(f"bench extras failed: {exc!r}", file=sys.stderr)
 
-    fam_rows = []
-    tot_ms = sum(f["ms"] for f in families) or 1.0
-    for f in sorted(families, key=lambda f: -f["ms"]):
-        r = roof(f) or {}
-        fam_rows.append({"family": f["family"], "launches_per_step": f["launches"] / 2.0, "ms_per_step": f["ms"] / 2.0,
-                         "share": f["ms"] / tot_ms, "tflops": r.get("tflops"), "gbs": r.get("gbs"), "bound": r.get("bound"),
-                         "frac": (r["achieved"] / r["peak"]) if r else None})
-    dom = roof(timed[dominant]) if dominant and dominant in timed else None
-    if dom is None and families:  # nothing bracketed in the timed region (stride too large for the step count)
-        dom = roof(max(families, key=lambda f: f["ms"]))
-    us_rp = rocprof_us_per_launch(dominant, args.config) if (dominant and world == 1 and not args.simulate_gpus) else None
-    if dom is not None:  # algorithmic work per launch in units of the bounding roof's peak-seconds: frac = this / launch duration
-        dom["frac_alg_per_launch"] = dom["achieved"] / dom["peak"] * dom["us_per_launch"] * 1e-6
-    if rank == 0:
-        out = {
-            "metric": "multi-view denoising steps/sec (N=16 views, 256x256, CFG 2.0, DDIM-50 step)" if args.config == "headline"
-                      else f"NOT the headline metric: denoising steps/sec of BASELINE config '{args.config}' "
-                           f"(N={N_VIEWS} views, {CFG['size']}x{CFG['size']}, CFG 2.0)",
-            "value": args.steps / dt, "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": args.dtype, "data": "synthetic",
-            "config": {"workload": f"synthetic sample ({'FaceScape-FLAME' if CFG['nverts'] == 5023 else 'SMPL-X'}-sized mesh, "
-                                   f"{CFG['nverts']} vertices before voxel de-duplication): N={N_VIEWS} target views, "
-                                   f"{CFG['size']}x{CFG['size']} (latent {lat}x{lat}), {CFG['proj']} cameras, full-width UNet "
-                                   f"(916.9M params, random init), CFG 2.0, one denoise_apply per step",
-                       "name": args.config, "views_per_gpu": nl, "batch_view_num": bvn,
-                       "parallelism": f"view-sharded x{world}" if world > 1 else "single GPU"},
+        # Roofline of the dominant kernel family (largest summed time in the survey pass).  For the bracketed launches of the
+        # timed region:  t_mfma = sum(flops) / peak,  t_hbm = sum(algorithmic bytes) / peak;  the larger one is the roof that
+        # bounds the family, `achieved` is the family's aggregate rate in that roof's unit, frac = achieved / peak.
+        def roof(f):
+            t = f["ms"] * 1e-3
+            if t <= 0 or f["sampled"] == 0:
+                return None
+            tf, tb = f["flops"] / (PEAK_F16_TFLOPS * 1e12), f["bytes"] / (PEAK_HBM_GBS * 1e9)
+            bound = "mfma" if tf >= tb else "hbm"
+            return {"bound": bound, "achieved": (f["flops"] / t / 1e12) if bound == "mfma" else (f["bytes"] / t / 1e9),
+                    "peak": PEAK_F16_TFLOPS if bound == "mfma" else PEAK_HBM_GBS, "unit": "TFLOP/s" if bound == "mfma" else "GB/s",
+                    "tflops": f["flops"] / t / 1e12, "gbs": f["bytes"] / t / 1e9, "us_per_launch": 1e6 * t / f["sampled"],
+                    "us_per_launch_raw": 1e3 * f.get("ms_raw", f["ms"]) / f["sampled"],
+                    "launches_bracketed": f["sampled"], "launches": f["launches"]}
+
+        fam_rows = []
+        tot_ms = sum(f["ms"] for f in families) or 1.0
+        for f in sorted(families, key=lambda f: -f["ms"]):
+            r = roof(f) or {}
+            fam_rows.append({"family": f["family"], "launches_per_step": f["launches"] / 2.0, "ms_per_step": f["ms"] / 2.0,
+                             "share": f["ms"] / tot_ms, "tflops": r.get("tflops"), "gbs": r.get("gbs"), "bound": r.get("bound"),
+                             "frac": (r["achieved"] / r["peak"]) if r else None})
+        dom = roof(timed[dominant]) if dominant and dominant in timed else None
+        if dom is None and families:  # nothing bracketed in the timed region (stride too large for the step count)
+            dom = roof(max(families, key=lambda f: f["ms"]))
+        us_rp = rocprof_us_per_launch(dominant, args.config) if (dominant and world == 1 and not args.simulate_gpus) else None
+        if dom is not None:  # algorithmic work per launch in units of the bounding roof's peak-seconds: frac = this / launch duration
+            dom["frac_alg_per_launch"] = dom["achieved"] / dom["peak"] * dom["us_per_launch"] * 1e-6
+        full = {
             "roofline": None if dom is None else {
                 "bound": dom["bound"], "achieved": dom["achieved"], "peak": dom["peak"], "unit": dom["unit"],
                 "frac": dom["achieved"] / dom["peak"],
@@ -615,18 +663,34 @@ def main():
                 "tflops": dom["tflops"], "gbs": dom["gbs"],
                 "mfma_frac": dom["tflops"] / PEAK_F16_TFLOPS, "hbm_frac": dom["gbs"] / PEAK_HBM_GBS},
             "families": fam_rows,
-            "rccl_ranks": dist.get_world_size() if world > 1 else 1,
-            "dist_backend": dist.get_backend() if world > 1 else None,
             # algorithmic FLOPs of one step as the engine books them launch by launch (survey pass, all families), not a
             # constant: the SURVEY figure 433.9 GFLOP x N holds for the 32 x 32 latents of the headline only
             "step_gflop": sum(f["flops"] for f in families) / 2.0 / 1e9,
             "step_tflops": sum(f["flops"] for f in families) / 2.0 / (dt / args.steps) / 1e12,
             "ddim50_wall_s": extras["ddim50_wall_s"], "vae_decode_ms_local_views": extras["vae_decode_ms"],
         }
+    if rank == 0:
+        out = {
+            "metric": "multi-view denoising steps/sec (N=16 views, 256x256, CFG 2.0, DDIM-50 step)" if args.config == "headline"
+                      else f"NOT the headline metric: denoising steps/sec of BASELINE config '{args.config}' "
+                           f"(N={N_VIEWS} views, {CFG['size']}x{CFG['size']}, CFG 2.0)",
+            "value": args.steps / dt, "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": args.dtype, "data": "synthetic",
+            "config": {"workload": f"synthetic sample ({'FaceScape-FLAME' if CFG['nverts'] == 5023 else 'SMPL-X'}-sized mesh, "
+                                   f"{CFG['nverts']} vertices before voxel de-duplication): N={N_VIEWS} target views, "
+                                   f"{CFG['size']}x{CFG['size']} (latent {lat}x{lat}), {CFG['proj']} cameras, full-width UNet "
+                                   f"(916.9M params, random init), CFG 2.0, one denoise_apply per step",
+                       "name": args.config, "views_per_gpu": nl, "batch_view_num": bvn,
+                       "parallelism": f"view-sharded x{world}" if world > 1 else "single GPU"},
+            "rccl_ranks": dist.get_world_size() if world > 1 else 1,
+            "dist_backend": dist.get_backend() if world > 1 else None,
+        }
+        out.update(full)
         if args.simulate_gpus:
             out["metric"] = f"SIMULATED per-rank step rate of a {args.simulate_gpus}-way view sharding (one rank, no collective)"
             out["n_gpus"] = 1
-        if not args.no_cpu_baseline and world == 1 and not args.simulate_gpus:
+        if args.full and not args.no_cpu_baseline and world == 1 and not args.simulate_gpus:
             print("[bench] GPU part done: " + json.dumps({k: out[k] for k in ("value", "ms_per_step", "roofline")}), file=sys.stderr)
             sys.stderr.flush()
             out["cpu_baseline"] = cpu_baseline()

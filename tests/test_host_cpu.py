@@ -537,6 +537,24 @@ def test_bench_reads_roofline_traffic_from_the_pmc_summary(tmp_path, monkeypatch
     assert committed["config"] == "headline" and "FETCH_SIZE" in committed["source"]
 
 
+def test_bench_dump_outputs_are_float32_and_sampled_past_the_byte_budget(tmp_path):
+    """bench.py --dump-outputs: every array as DIR/<name>.npy in float32; an array that would pass the byte budget is replaced
+    by the same seeded sample of its elements in every run."""
+    import importlib
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    small, big = torch.randn(2, 3, dtype=torch.float64), torch.arange(1000, dtype=torch.float16)
+    bench.write_outputs(str(tmp_path / "a"), {"x_prev": small, "big": big}, limit=4 * 6 + 4 * 100)
+    bench.write_outputs(str(tmp_path / "b"), {"x_prev": small, "big": big}, limit=4 * 6 + 4 * 100)
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.sample.npy", "x_prev.npy"]
+    x = np.load(tmp_path / "a" / "x_prev.npy")
+    assert x.dtype == np.float32 and x.shape == (2, 3) and np.array_equal(x, small.float().numpy())
+    s = np.load(tmp_path / "a" / "big.sample.npy")
+    assert s.dtype == np.float32 and s.shape == (100,) and len(set(s.tolist())) == 100 and np.all(np.diff(s) > 0)
+    assert np.array_equal(s, np.load(tmp_path / "b" / "big.sample.npy"))
+    assert bench.DUMP_LIMIT_BYTES == 64 << 20
+
+
 def test_lds_layouts_of_the_attention_and_conv3x_kernels_are_conflict_free_in_the_bank_model():
     """The two LDS layouts round 5 changed, pinned in the bank model of tools/lds_bank_model.py (the banking
     rules of the microarchitecture guide): the attention kernel's row-major V image at the row pitches k_attn.hip selects serves

@@ -2,7 +2,7 @@
 A=$1; B=$2; F=$3; R=${4:-3}; shift 4
 for i in $(seq 1 $R); do
   for L in $A $B; do
-    MVD_LIB_PATH=$PWD/$L timeout 300 python bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-extras "$@" 2>/dev/null | python -c "
+    MVD_LIB_PATH=$PWD/$L timeout 300 python bench.py --steps 30 --warmup 3 --full --no-cpu-baseline --no-extras "$@" 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 f=[x for x in d['families'] if x['family']=='$F']

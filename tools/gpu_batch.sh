@@ -11,14 +11,14 @@ if want tests; then
 fi
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 NC=""; if want nocpu; then NC="--no-cpu-baseline"; fi  # (the CPU-baseline leg is ~6 minutes of host time on the GPU box)
-timeout 700 python bench.py --steps 20 --warmup 3 $NC > $O/bench.json 2> $O/bench.err
-timeout 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras --simulate-gpus 8 > $O/bench_sim8.json 2>/dev/null
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o b -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $O/bench_prof.json 2> $O/prof.err
+timeout 700 python bench.py --steps 20 --warmup 3 --full $NC > $O/bench.json 2> $O/bench.err
+timeout 300 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-extras --simulate-gpus 8 > $O/bench_sim8.json 2>/dev/null
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o b -- python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-extras > $O/bench_prof.json 2> $O/prof.err
 f=$(find $O/prof -name "*kernel_stats.csv" | head -1); cp $f $O/kernel_stats.csv; rm -rf $O/prof
 python tools/prof_summary.py $O/kernel_stats.csv $O/bench_prof.json $O/kernel_durations.json > $O/family_table.txt
 MVD_LAYER_TIMING=1 timeout 300 python tools/layer_step.py 2> $O/layers.log > /dev/null; python tools/layer_agg.py $O/layers.log 40 > $O/layers_step.txt 2>/dev/null
 if want pmc; then
-  CMD="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras"
+  CMD="python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-extras"
   timeout 500 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/mfma -o m -- $CMD > $O/pmc_bench.json 2> $O/mfma.err
   f=$(find $O/mfma -name "*counter_collection.csv" | head -1); python tools/pmc_step.py $f > $O/pmc_mfma_busy.txt; rm -rf $O/mfma
   for C in FETCH_SIZE WRITE_SIZE; do

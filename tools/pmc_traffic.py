@@ -1,5 +1,5 @@
 """HBM-side traffic per kernel family from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE; counter CSVs) over
-`bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras` (5 identical steps), next to the algorithmic bytes the bench line
+`bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-extras` (5 identical steps), next to the algorithmic bytes the bench line
 books per family:  python tools/pmc_traffic.py counters_FETCH_SIZE.csv counters_WRITE_SIZE.csv bench_line.json [steps]
 FETCH_SIZE is doubled (gfx950: 128-byte requests tallied at 64 B, MI355X_MICROARCH.md 'HBM'); WRITE_SIZE is uncalibrated on
 gfx950 (same guide) and shown as reported.  Units: MB = 1e6 bytes per step on BOTH sides (the counters report KiB:
@@ -68,8 +68,8 @@ print(f"whole step: {tot_b / 1e9:.2f} GB HBM-side (2 x FETCH + WRITE, bytes) vs 
       f"= {tot_b / alg_b if alg_b else float('nan'):.2f} x")
 
 if json_out:
-    out = {"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over bench.py --steps 2 --warmup 1 --no-cpu-baseline "
-                     "--no-extras; bytes = (2 x FETCH_SIZE + WRITE_SIZE) KB x 1024 per launch, family average",
+    out = {"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) over bench.py --steps 2 --warmup 1 --full "
+                     "--no-cpu-baseline --no-extras; bytes = (2 x FETCH_SIZE + WRITE_SIZE) KB x 1024 per launch, family average",
            "config": line["config"].get("name"), "bytes_per_launch": {}}
     import os
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

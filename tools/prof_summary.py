@@ -6,7 +6,7 @@
 * algorithmic FLOPs / bytes per step and family come from the bench line's "families" (booked by the engine's probe at each
   launch: every operand and the result once);
 * TF/s, GB/s and the fraction of the binding roof (2.5 PFLOP/s dense fp16 MFMA, 8 TB/s HBM) follow.
-total_steps = identical denoising steps the profiled process executed (warmup + 2 survey + timed, with --no-extras)."""
+total_steps = identical denoising steps the profiled process executed (warmup + 2 survey + timed, with --full --no-extras)."""
 import csv
 import json
 import re
@@ -95,7 +95,7 @@ if json_out:
     import os
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from morphablediffusion_amd.lib import csrc_sha16
-    json.dump({"source": "rocprofv3 --kernel-trace --stats over bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras: TotalDurationNs / Calls "
+    json.dump({"source": "rocprofv3 --kernel-trace --stats over bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-extras: TotalDurationNs / Calls "
                          "per kernel family (kernel begin to end, no launch path)",
                "config": bench.get("config", {}).get("name"), "csrc_sha16": csrc_sha16(),
                "us_per_launch": {f: fam_t[f] / fam_n[f] / 1e3 for f in fam_t}, "launches_per_step": {f: fam_n[f] / steps for f in fam_t},
