@@ -378,6 +378,33 @@ int mvd_op_group_norm_bwd(mvd_ctx* ctx, const float* x, const float* dy, int B, 
                           const float* beta, float eps, int act, float* dx, float* dgamma, float* dbeta, void* stream);
 int mvd_op_layer_norm_bwd(mvd_ctx* ctx, const float* x, const float* dy, int rows, int C, const float* gamma, float* dx,
                           float* dgamma, float* dbeta, void* stream);
+/* Adjoints of the training step's convolutions, Linears and GEMMs (csrc/engine_train.hip), one layer at a time on the production
+ * code: the engine's forward pack of w (xp != 0: the extended-precision [w_hi | w_hi | w_lo] layout), the adjoint pack built as at
+ * finalize, then the backward functions the training step calls.  Activations are channels-last fp32 device buffers; an input
+ * width C is stored with a row stride of up8(C) (pad columns zero); x_f16 != 0: the production path reads x as fp16 (rounded
+ * here).  dx is written, or added to with accum != 0; dw / db (reference layouts; either may be NULL) are always ADDED to, as
+ * the gradient arena is.  poison != 0: the free workspace is filled with 0xFF bytes before the op runs.
+ * mvd_op_conv_bwd: kind 0 plain 3x3 / 1x1 (ksize), 1 Downsample (3x3 stride 2), 2 Upsample (nearest x2, then 3x3); x / dx
+ * [B,H,W,up8(Cin)], dy [B,Ho,Wo,Cout], w [Cout][Cin][k][k]; need_din == 0 skips dx (the first layer). */
+int mvd_op_conv_bwd(mvd_ctx* ctx, int kind, int ksize, int B, int Cin, int H, int W, int Cout, const float* x, int x_f16,
+                    const float* w, const float* dy, int xp, int accum, int need_din, int poison, float* dx, float* dw, float* db,
+                    void* stream);
+/* mvd_op_linear_bwd: x / dx [rows][up8(K)] (rows % B == 0, B = samples), w [N][K], dy [rows][N].  dx_f16: dx produced in fp16
+ * (as the attention output projection's), returned as fp32.  staged: dy's fp16 row image and transposed image come from one
+ * read (the SpatialTransformer's staging).  geglu: the FF1 GEGLU backward (bias [N] needed, N % 64 == 0): dy is dL/d(value *
+ * gelu(gate)) [rows][N/2], the pre-activations are re-computed from fp16 x. */
+int mvd_op_linear_bwd(mvd_ctx* ctx, int B, int rows, int K, int N, const float* x, int x_f16, const float* w, const float* bias,
+                      const float* dy, int geglu, int dx_f16, int staged, int xp, int accum, int poison, float* dx, float* dw,
+                      float* db, void* stream);
+/* mvd_op_conv3d_bwd: kind 0 Conv3d(k3, s1, p1), 1 Conv3d(k3, s2, p1) (even D, H, W), 2 ConvTranspose3d(k3, s2, p1, op1);
+ * x / dx [B,D,H,W,Cin] (Cin % 8 == 0), dy on the output grid [B,Do,Ho,Wo,Cout], w [Cout][Cin][27] (kind 2: [Cin][Cout][27]). */
+int mvd_op_conv3d_bwd(mvd_ctx* ctx, int kind, int B, int Cin, int D, int H, int W, int Cout, const float* x, int x_f16,
+                      const float* w, const float* dy, int accum, int poison, float* dx, float* dw, float* db, void* stream);
+/* mvd_op_tgemm: out[M][N] (ldc) (+)= op(A) op(B) through the training step's tgemm.  a_trans: A stored [K][M], else [M][K];
+ * b_trans: B stored [N][K], else [K][N]; lda / ldb the stored row strides; a_f16 / b_f16: the operand is passed to tgemm as
+ * fp16 (rounded here); xp: extended precision (fp32 operands only). */
+int mvd_op_tgemm(mvd_ctx* ctx, int M, int N, int K, const float* a, int a_f16, int a_trans, long lda, const float* b, int b_f16,
+                 int b_trans, long ldb, float* out, int ldc, int accum, int xp, int poison, void* stream);
 /* Row-chain kernel test / timing hook (csrc/k_rowchain.hip): the row-local tail of a SpatialTransformer block in ONE launch,
  *   t2 = ao @ w_ao^T + b_ao + rowbias[sample] + xin   (flags & 1; otherwise t2 = xin)     ldm/modules/attention.py:196-200, 266-267
  *   t3 = t2 + FF2(GEGLU(FF1(LayerNorm(t2))))                                              ldm/modules/attention.py:37-73, 268

@@ -343,6 +343,9 @@ struct mvd_ctx {
   };
   std::vector<ParamRec> params;
   std::map<std::string, size_t> param_index;
+  // gradient destinations that engine_grad consults before param_index: filled only for the duration of one backward-op test
+  // hook (engine_train.hip: GradOverride), empty otherwise
+  std::map<std::string, float*> grad_override;
   size_t arena_n = 0;
   float *arena_p = nullptr, *arena_g = nullptr, *arena_m = nullptr, *arena_v = nullptr;
   bool arena_owned[4] = {false, false, false, false};  // hipMalloc'ed here (true) or adopted from the caller (mvd_train_adopt_arena)

@@ -143,6 +143,10 @@ int engine_train_setup(mvd_ctx* c) {
 }
 
 float* engine_grad(mvd_ctx* c, const std::string& key) {
+  if (!c->grad_override.empty()) {
+    auto o = c->grad_override.find(key);
+    if (o != c->grad_override.end()) return o->second;
+  }
   auto it = c->param_index.find(key);
   return it == c->param_index.end() ? nullptr : c->arena_g + c->params[it->second].off;
 }
@@ -153,6 +157,9 @@ const float* engine_master(mvd_ctx* c, const std::string& key) {
 
 // adjoint weights of every GEMM of the UNet trunk (ResBlocks, SpatialTransformers, conv_in / down / up, the output conv)
 namespace {
+// tap flip of a 3x3x3 adjoint pack: a stride-1 conv's adjoint is the same conv on tap-flipped weights; a strided conv's adjoint is
+// launched as a transposed conv and vice versa (their tap tables carry the o = 2 i - 1 + k relation), so those packs keep their taps
+inline int adjoint_flip3d(int stride, bool transposed) { return stride == 1 && !transposed ? 1 : 0; }
 int make_wT(mvd_ctx* c, ConvW& w, int flip = 1) {
   if (!w.w) return 0;
   const int Cl = w.cin_l > 0 ? w.cin_l : w.Cin;
@@ -174,8 +181,7 @@ int engine_build_dgrad(mvd_ctx* c) {
   RET_IF(make_wT(c, c->out_conv));
   return 0;
 }
-// ... and of the conditioner's dense convolutions.  A strided conv's adjoint is launched as a transposed conv and vice versa
-// (their tap tables carry the o = 2 i - 1 + k relation), so those packs are transposed but not tap-flipped.
+// ... and of the conditioner's dense convolutions (tap flips: adjoint_flip3d)
 int engine_build_dgrad_cond(mvd_ctx* c) {
   for (int i = 0; i < 3; ++i) {
     RET_IF(make_wT(c, c->enc_blocks[i].c1));
@@ -183,8 +189,8 @@ int engine_build_dgrad_cond(mvd_ctx* c) {
   }
   RET_IF(make_wT(c, c->enc_final));
   RET_IF(make_wT(c, c->fr_conv0));
-  for (int i = 0; i < 6; ++i) RET_IF(make_wT(c, c->fr_blocks[i].conv, c->fr_blocks[i].stride == 1 ? 1 : 0));
-  for (int i = 0; i < 3; ++i) RET_IF(make_wT(c, c->fr_up[i].conv, 0));
+  for (int i = 0; i < 6; ++i) RET_IF(make_wT(c, c->fr_blocks[i].conv, adjoint_flip3d(c->fr_blocks[i].stride, false)));
+  for (int i = 0; i < 3; ++i) RET_IF(make_wT(c, c->fr_up[i].conv, adjoint_flip3d(2, true)));
   return 0;
 }
 
@@ -471,6 +477,42 @@ int bwd_res(Bwd& b, const ResW& r, const ResSaved& sv, View in, View dout, View 
   return 0;
 }
 
+// ---- FF1 + GEGLU of a BasicTransformerBlock (modules/attention.py:37-45, 59-73) ---------------------------------------
+// gg = GEGLU(x @ ff1^T + b), x [rows][K] fp16, ff1 packed in the GEGLU column order with N = 2 * (width of gg) rows, d_gg
+// [rows][N/2] fp32.  The pre-activations are re-computed into pre16 [rows][N] (packed column order), never stored by the
+// forward pass; dL/dx goes to dx [rows][K] fp32 (written or, with accum, added); the weight / bias gradients are computed in the
+// packed row order and un-permuted into the reference's [value | gate] rows.  Scratch: dpre16 [rows][N], tmpW [N][K], part
+// [B][N].
+int bwd_ff1_geglu(Bwd& b, const ConvW& ff1, const half_t* x, int K, const float* d_gg, int rows, half_t* pre16, half_t* dpre16, float* dx,
+                  bool accum, float* tmpW, float* part) {
+  mvd_ctx* c = b.c;
+  const int N = ff1.N, T = rows / b.B;
+  {
+    GemmArgs g;
+    g.a = x; g.lda = K; g.w = &ff1; g.out = pre16; g.out_f32 = 0; g.ldc = N;
+    RET_IF(run_linear(c, g, b.B, rows, b.s));
+  }
+  RET_IF(bwd_geglu(pre16, d_gg, N / 2, rows, N, dpre16, b.s));
+  RET_IF(dgrad_linear(b, ff1, dpre16, N, dx, K, 1, rows, accum));
+  WsScope sc2(c, WS_TEMP);
+  const int Rp = up64(rows);
+  half_t* dyT = ws_alloc<half_t>(c, (size_t)N * Rp);
+  half_t* xT = ws_alloc<half_t>(c, (size_t)K * Rp);
+  WS_CHECK(dyT && xT);
+  if (float* G = engine_grad(c, ff1.key)) {
+    RET_IF(bwd_tcast(dpre16, 0, N, rows, N, dyT, Rp, b.s));
+    RET_IF(bwd_tcast(x, 0, K, rows, K, xT, Rp, b.s));
+    RET_IF(wgrad_gemm(b, dyT, N, xT, K, Rp, tmpW, false));
+    RET_IF(bwd_geglu_unpermute_add(tmpW, N, K, G, b.s));
+  }
+  if (float* Gb = engine_grad(c, ff1.bkey)) {
+    RET_IF(bwd_colsum_samples(dpre16, 0, N, b.B, T, N, part, N, b.s));
+    RET_IF(bwd_sum_rows_add(part, b.B, N, N, tmpW, 0, b.s));
+    RET_IF(bwd_geglu_unpermute_add(tmpW, N, 1, Gb, b.s));
+  }
+  return 0;
+}
+
 // ---- SpatialTransformer (modules/attention.py:325-336, BasicTransformerBlock._forward :265-269) ----------------------
 int bwd_st(Bwd& b, const STW& t, const STSaved& sv, View in, View dout, View din, bool accum, int H, int W) {
   mvd_ctx* c = b.c;
@@ -498,32 +540,8 @@ int bwd_st(Bwd& b, const STW& t, const STSaved& sv, View in, View dout, View din
   RET_IF(grad16(c, d_t, C, rows, C, &g16, b.s, &gT));
   RET_IF(dgrad_linear(b, t.ff2, g16, C, d_gg, 4 * C, 1, rows, false));
   RET_IF(wgrad_linear(b, t.ff2, d_t, C, sv.gg, 0, 4 * C, rows, 4 * C, gT));
-  // gg = GEGLU(ff1(l3)): the pre-activations are re-computed (packed column order), never stored by the forward pass
-  {
-    GemmArgs g;
-    g.a = sv.l3; g.lda = C; g.w = &t.ff1; g.out = pre16; g.out_f32 = 0; g.ldc = 8 * C;
-    RET_IF(run_linear(c, g, b.B, rows, b.s));
-  }
-  RET_IF(bwd_geglu(pre16, d_gg, 4 * C, rows, 8 * C, dpre16, b.s));
-  RET_IF(dgrad_linear(b, t.ff1, dpre16, 8 * C, d_l, C, 1, rows, false));
-  {  // FF1 weight / bias gradient: computed in the packed row order, un-permuted into the reference's [value | gate] rows
-    WsScope sc2(c, WS_TEMP);
-    const int Rp = up64(rows);
-    half_t* dyT = ws_alloc<half_t>(c, (size_t)8 * C * Rp);
-    half_t* xT = ws_alloc<half_t>(c, (size_t)C * Rp);
-    WS_CHECK(dyT && xT);
-    if (float* G = engine_grad(c, t.ff1.key)) {
-      RET_IF(bwd_tcast(dpre16, 0, 8 * C, rows, 8 * C, dyT, Rp, b.s));
-      RET_IF(bwd_tcast(sv.l3, 0, C, rows, C, xT, Rp, b.s));
-      RET_IF(wgrad_gemm(b, dyT, 8 * C, xT, C, Rp, tmpW, false));
-      RET_IF(bwd_geglu_unpermute_add(tmpW, 8 * C, C, G, b.s));
-    }
-    if (float* Gb = engine_grad(c, t.ff1.bkey)) {
-      RET_IF(bwd_colsum_samples(dpre16, 0, 8 * C, b.B, T, 8 * C, part, 8 * C, b.s));
-      RET_IF(bwd_sum_rows_add(part, b.B, 8 * C, 8 * C, tmpW, 0, b.s));
-      RET_IF(bwd_geglu_unpermute_add(tmpW, 8 * C, 1, Gb, b.s));
-    }
-  }
+  // gg = GEGLU(ff1(l3))
+  RET_IF(bwd_ff1_geglu(b, t.ff1, sv.l3, C, d_gg, rows, pre16, dpre16, d_l, false, tmpW, part));
   // l3 = LN3(t2)
   RET_IF(ln_backward(b, t.ln3, sv.t2, C, d_l, C, rows, d_t, C, true));
   // t2 = t0 + to_out(ao) + b_o + attn2[b]
@@ -1601,4 +1619,220 @@ int engine_train_conditioner_backward(mvd_ctx* c, const float* x_noisy_nchw, int
   const int slot = c->cur_slot;
   return engine_train_conditioner_backward_batch(c, 1, &slot, x_noisy_nchw, &timestep, v_embed, n_views, &target_idx, dsrc, dbg_dvolume,
                                                  dbg_dfused, dbg_dfeats, dbg_dtembed, s);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// backward-op test hooks (include/mvd.h, tests/test_gpu_train_ops.py): the training step's own adjoint functions above, run on
+// one layer whose weights, input and output gradient the caller supplies.  The forward pack is the engine's (xp: repack_xp's
+// [w_hi | w_hi | w_lo] rows), the adjoint pack is built as make_wT / engine_build_dgrad_cond build it, and the weight / bias
+// gradients land in the caller's buffers through mvd_ctx::grad_override.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+const char* const kHookW = "hook.weight";
+const char* const kHookB = "hook.bias";
+
+struct GradOverride {  // the override table is empty again on every exit path
+  mvd_ctx* c;
+  GradOverride(mvd_ctx* c_, float* dw, float* db) : c(c_) {
+    c->grad_override.clear();
+    if (dw) c->grad_override[kHookW] = dw;
+    if (db) c->grad_override[kHookB] = db;
+  }
+  ~GradOverride() { c->grad_override.clear(); }
+  GradOverride(const GradOverride&) = delete;
+  GradOverride& operator=(const GradOverride&) = delete;
+};
+
+int hook_begin(mvd_ctx* c) {
+  if (!c) return mvd_fail("null context");
+  if (hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
+  return 0;
+}
+
+// the free part of the workspace -> 0xFF bytes (NaN as fp16, bf16 and fp32): a read of anything the op did not write shows
+// in its result
+int ws_poison(mvd_ctx* c, hipStream_t s) {
+  const size_t o = (c->ws.off + 255) & ~(size_t)255;
+  if (o < c->ws.size) HIP_CHECK_RET(hipMemsetAsync(c->ws.base + o, 0xFF, c->ws.size - o, s));
+  return 0;
+}
+
+// w fp32 in the reference layout ([N][cin][taps], transposed: [cin][N][taps]) -> the forward pack (Cl = up8(cin) columns, or
+// 3 Cl with xp) and its adjoint pack [taps][Cl][Np]
+int hook_pack(mvd_ctx* c, const float* w, int N, int cin, int taps, int transposed, int geglu, int xp, int flip, ConvW* o, hipStream_t s) {
+  const int Cl = up8(cin);
+  o->N = N;
+  o->taps = taps;
+  o->xp = xp ? 1 : 0;
+  o->cin_l = xp ? Cl : 0;
+  o->Cin = xp ? 3 * Cl : Cl;
+  o->Np = up8(N);
+  o->w = ws_alloc<half_t>(c, (size_t)taps * N * o->Cin);
+  o->wT = ws_alloc<half_t>(c, (size_t)taps * Cl * o->Np);
+  WS_CHECK(o->w && o->wT);
+  o->key = kHookW;
+  o->bkey = kHookB;
+  RET_IF(launch_pack_weight(w, N, o->Cin, taps, transposed, geglu, o->w, s, cin, o->xp));
+  return bwd_pack_dgrad(o->w, taps, N, o->Cin, Cl, o->Np, o->wT, s, flip);
+}
+
+// an fp32 operand the caller supplies as the fp16 image the production path reads
+int hook_f16(mvd_ctx* c, const float* src, size_t n, const half_t** out, hipStream_t s) {
+  half_t* d = ws_alloc<half_t>(c, n);
+  WS_CHECK(d);
+  RET_IF(launch_f32_to_f16(src, d, n, s));
+  *out = d;
+  return 0;
+}
+
+__global__ void hook_f16_to_f32_kernel(const half_t* in, float* out, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = (float)in[i];
+}
+}  // namespace
+
+int mvd_op_conv_bwd(mvd_ctx* c, int kind, int ksize, int B, int Cin, int H, int W, int Cout, const float* x, int x_f16, const float* w,
+                    const float* dy, int xp, int accum, int need_din, int poison, float* dx, float* dw, float* db, void* stream) {
+  RET_IF(hook_begin(c));
+  if (kind < 0 || kind > 2 || (ksize != 1 && ksize != 3) || (ksize == 1 && kind) || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0)
+    return mvd_fail("op_conv_bwd: bad argument");
+  if (!x || !w || !dy || (need_din && !dx)) return mvd_fail("op_conv_bwd: null operand");
+  hipStream_t s = (hipStream_t)stream;
+  WsScope ws_scope(c);
+  const int cp = up8(Cin), taps = ksize * ksize;
+  const int stride = kind == 1 ? 2 : 1, ups = kind == 2 ? 1 : 0;
+  const int Ho = ((H << ups) - 1) / stride + 1, Wo = ((W << ups) - 1) / stride + 1, rows = B * H * W, rows_o = B * Ho * Wo;
+  // the conv_in / Downsample / Upsample form (bwd_conv) reads an fp32 input of the layer's full width; the ResBlock / encoder
+  // form reads the fp16 saved activation, or an input narrower than its pack
+  const bool whole = ksize == 3 && !x_f16 && Cin % 8 == 0;
+  if (kind && !whole) return mvd_fail("op_conv_bwd: Downsample / Upsample layers take an fp32 input with Cin % 8 == 0");
+  ConvW cw;
+  RET_IF(hook_pack(c, w, Cout, Cin, taps, 0, 0, xp, 1, &cw, s));
+  const half_t* x16 = nullptr;
+  if (x_f16) RET_IF(hook_f16(c, x, (size_t)rows * cp, &x16, s));
+  const void* xs = x_f16 ? (const void*)x16 : (const void*)x;
+  if (poison) RET_IF(ws_poison(c, s));
+  GradOverride go(c, dw, db);
+  Bwd b{c, s, B, nullptr, nullptr};
+  if (whole) {
+    const int opk = kind == 1 ? OP_DOWN : (kind == 2 ? OP_UP : OP_CONV_IN);
+    View in, dout, din;
+    in.p = const_cast<float*>(x); in.ld = cp; in.C = Cin;
+    dout.p = const_cast<float*>(dy); dout.ld = Cout; dout.C = Cout;
+    din.p = dx; din.ld = cp; din.C = Cin;
+    return bwd_conv(b, opk, cw, in, dout, din, accum != 0, need_din != 0, H, W);
+  }
+  half_t *dy16, *dyT;
+  RET_IF(grad16(c, dy, Cout, rows_o, Cout, &dy16, s, &dyT));
+  if (ksize == 1) {  // the ResBlock skip connection's form
+    if (need_din) RET_IF(dgrad_linear(b, cw, dy16, up8(Cout), dx, cp, 1, rows, accum != 0));
+    return wgrad_linear(b, cw, dy, Cout, xs, x_f16 ? 0 : 1, cp, rows, Cin, dyT);
+  }
+  if (need_din) RET_IF(dgrad_conv3(b, cw, dy16, dx, cp, H, W, accum != 0));
+  return wgrad_conv3(b, cw, dy, Cout, xs, x_f16 ? 0 : 1, cp, H, W, Cin, 1, 0, dyT);
+}
+
+int mvd_op_linear_bwd(mvd_ctx* c, int B, int rows, int K, int N, const float* x, int x_f16, const float* w, const float* bias,
+                      const float* dy, int geglu, int dx_f16, int staged, int xp, int accum, int poison, float* dx, float* dw, float* db,
+                      void* stream) {
+  RET_IF(hook_begin(c));
+  if (B <= 0 || rows <= 0 || rows % B || K <= 0 || N <= 0) return mvd_fail("op_linear_bwd: bad argument");
+  if (!x || !w || !dy || !dx) return mvd_fail("op_linear_bwd: null operand");
+  if (geglu && (N % 64 || K % 8 || xp || dx_f16 || !bias)) return mvd_fail("op_linear_bwd: GEGLU takes N % 64 == 0, K % 8 == 0, a bias, fp32 dx, no xp");
+  hipStream_t s = (hipStream_t)stream;
+  WsScope ws_scope(c);
+  const int kp = up8(K);
+  ConvW cw;
+  RET_IF(hook_pack(c, w, N, K, 1, 0, geglu, xp, 1, &cw, s));
+  const half_t* x16 = nullptr;
+  if (x_f16 || geglu) RET_IF(hook_f16(c, x, (size_t)rows * kp, &x16, s));
+  const void* xs = x16 ? (const void*)x16 : (const void*)x;
+  half_t* dx16 = nullptr;
+  if (dx_f16) {
+    dx16 = ws_alloc<half_t>(c, (size_t)rows * kp);
+    WS_CHECK(dx16);
+    if (accum) RET_IF(launch_f32_to_f16(dx, dx16, (size_t)rows * kp, s));
+  }
+  half_t *pre16 = nullptr, *dpre16 = nullptr;
+  float *tmpW = nullptr, *part = nullptr;
+  if (geglu) {
+    float* bp = ws_alloc<float>(c, (size_t)N);
+    pre16 = ws_alloc<half_t>(c, (size_t)rows * N);
+    dpre16 = ws_alloc<half_t>(c, (size_t)rows * N);
+    tmpW = ws_alloc<float>(c, (size_t)N * K);
+    part = ws_alloc<float>(c, (size_t)B * N);
+    WS_CHECK(bp && pre16 && dpre16 && tmpW && part);
+    RET_IF(launch_permute_geglu_bias(bias, N, bp, s));
+    cw.bias = bp;
+  }
+  if (poison) RET_IF(ws_poison(c, s));
+  GradOverride go(c, dw, db);
+  Bwd b{c, s, B, nullptr, nullptr};
+  if (geglu) return bwd_ff1_geglu(b, cw, x16, K, dy, rows, pre16, dpre16, dx, accum != 0, tmpW, part);
+  half_t *dy16, *dyT = nullptr;
+  // staged: the row image and the transposed wgrad operand from one read of dy (grad16(..., &gT), as bwd_st / bwd_res stage it)
+  RET_IF(grad16(c, dy, N, rows, N, &dy16, s, staged ? &dyT : nullptr));
+  RET_IF(dgrad_linear(b, cw, dy16, up8(N), dx_f16 ? (void*)dx16 : (void*)dx, kp, dx_f16 ? 0 : 1, rows, accum != 0));
+  RET_IF(wgrad_linear(b, cw, dy, N, xs, x_f16 ? 0 : 1, kp, rows, K, dyT));
+  if (dx_f16) {
+    hipLaunchKernelGGL(hook_f16_to_f32_kernel, dim3(256), dim3(256), 0, s, dx16, dx, (size_t)rows * kp);
+    HIP_CHECK_RET(hipGetLastError());
+  }
+  return 0;
+}
+
+int mvd_op_conv3d_bwd(mvd_ctx* c, int kind, int B, int Cin, int D, int H, int W, int Cout, const float* x, int x_f16, const float* w,
+                      const float* dy, int accum, int poison, float* dx, float* dw, float* db, void* stream) {
+  RET_IF(hook_begin(c));
+  if (kind < 0 || kind > 2 || B <= 0 || Cin <= 0 || Cin % 8 || Cout <= 0 || D <= 0 || H <= 0 || W <= 0) return mvd_fail("op_conv3d_bwd: bad argument");
+  // the stride-2 adjoint is a transposed conv from the coarse grid: it covers 2 Do x 2 Ho x 2 Wo input voxels
+  if (kind == 1 && ((D | H | W) & 1)) return mvd_fail("op_conv3d_bwd: a stride-2 layer needs even D, H, W");
+  if (!x || !w || !dy || !dx) return mvd_fail("op_conv3d_bwd: null operand");
+  hipStream_t s = (hipStream_t)stream;
+  WsScope ws_scope(c);
+  const int Do = kind == 2 ? 2 * D : (kind == 1 ? D / 2 : D), Ho = kind == 2 ? 2 * H : (kind == 1 ? H / 2 : H),
+            Wo = kind == 2 ? 2 * W : (kind == 1 ? W / 2 : W);
+  const long rows = (long)B * D * H * W, rows_o = (long)B * Do * Ho * Wo;
+  ConvW cw;
+  RET_IF(hook_pack(c, w, Cout, Cin, 27, kind == 2 ? 1 : 0, 0, 0, adjoint_flip3d(kind == 0 ? 1 : 2, kind == 2), &cw, s));
+  const half_t* x16 = nullptr;
+  if (x_f16) RET_IF(hook_f16(c, x, (size_t)rows * Cin, &x16, s));
+  const void* xs = x_f16 ? (const void*)x16 : (const void*)x;
+  if (poison) RET_IF(ws_poison(c, s));
+  GradOverride go(c, dw, db);
+  Bwd b{c, s, B, nullptr, nullptr};
+  half_t* dy16;
+  RET_IF(grad16(c, dy, Cout, rows_o, Cout, &dy16, s));
+  const int xf = x_f16 ? 0 : 1;
+  if (kind == 0) {
+    RET_IF(dgrad_conv3d(b, cw, 0, dy16, dx, Cin, D, H, W, accum != 0));
+    return wgrad_conv3d(b, cw, dy, Cout, xs, xf, Cin, D, H, W, Cin, 1);
+  }
+  if (kind == 1) {
+    RET_IF(dgrad_conv3d(b, cw, 1, dy16, dx, Cin, Do, Ho, Wo, accum != 0));
+    return wgrad_conv3d(b, cw, dy, Cout, xs, xf, Cin, D, H, W, Cin, 2);
+  }
+  RET_IF(dgrad_conv3d(b, cw, 2, dy16, dx, Cin, Do, Ho, Wo, accum != 0));
+  return wgrad_convT3d(b, cw, dy, Cout, xs, xf, Cin, D, H, W);
+}
+
+int mvd_op_tgemm(mvd_ctx* c, int M, int N, int K, const float* a, int a_f16, int a_trans, long lda, const float* bm, int b_f16, int b_trans,
+                 long ldb, float* out, int ldc, int accum, int xp, int poison, void* stream) {
+  RET_IF(hook_begin(c));
+  if (M <= 0 || N <= 0 || K <= 0 || !a || !bm || !out) return mvd_fail("op_tgemm: bad argument");
+  if (lda < (a_trans ? M : K) || ldb < (b_trans ? K : N) || ldc < N) return mvd_fail("op_tgemm: leading dimension too small");
+  hipStream_t s = (hipStream_t)stream;
+  WsScope ws_scope(c);
+  Opnd A = F32(a, lda, a_trans), Bm = F32(bm, ldb, b_trans);
+  if (a_f16) {
+    const half_t* h;
+    RET_IF(hook_f16(c, a, (size_t)(a_trans ? K : M) * lda, &h, s));
+    A = F16(h, lda, a_trans);
+  }
+  if (b_f16) {
+    const half_t* h;
+    RET_IF(hook_f16(c, bm, (size_t)(b_trans ? N : K) * ldb, &h, s));
+    Bm = F16(h, ldb, b_trans);
+  }
+  if (poison) RET_IF(ws_poison(c, s));
+  return tgemm(c, A, Bm, out, ldc, M, N, K, accum != 0, s, xp != 0);
 }

@@ -740,6 +740,90 @@ class Engine:
                                                L.ptr(db), _stream()))
         return dx, dg, db
 
+    # ---- training-backward adjoints of one layer (mvd_op_*_bwd, mvd_op_tgemm): reference layouts in, reference layouts out.
+    # accum = (dx0, dW0, db0): the gradients start from these values (otherwise from zero: dx written, dW / db added to zero).
+    def _pad_last(self, t, n):
+        t = _f32(t, self.device)
+        return t if t.shape[-1] == n else torch.nn.functional.pad(t, (0, n - t.shape[-1])).contiguous()
+
+    def op_conv_bwd(self, x, w, dy, kind=0, x_half=False, xp=False, accum=None, need_din=True, poison=False):
+        """Conv2d k1 / k3 (kind 0), Downsample (1: stride 2), Upsample (2: nearest x2, then k3) adjoint.  x [B,Cin,H,W], w
+        [Cout,Cin,k,k], dy [B,Cout,Ho,Wo] -> (dx [B,Cin,H,W] or None, dW like w, db [Cout])."""
+        dev = self.device
+        B, Cin, H, W = x.shape
+        Cout, k = w.shape[0], w.shape[2]
+        cp = (Cin + 7) // 8 * 8
+        xn = self._pad_last(x.permute(0, 2, 3, 1), cp)
+        dyn = _f32(dy.permute(0, 2, 3, 1), dev)
+        ww = _f32(w, dev)
+        dx = torch.zeros(B, H, W, cp, device=dev)
+        dW = torch.zeros(Cout, Cin * k * k, device=dev)
+        db = torch.zeros(Cout, device=dev)
+        if accum is not None:
+            dx.copy_(self._pad_last(accum[0].permute(0, 2, 3, 1), cp))
+            dW.copy_(accum[1].reshape(Cout, -1))
+            db.copy_(accum[2])
+        L.check(self.lib.mvd_op_conv_bwd(self._ctx, int(kind), int(k), B, Cin, H, W, Cout, L.ptr(xn), 1 if x_half else 0, L.ptr(ww), L.ptr(dyn),
+                                         1 if xp else 0, 1 if accum is not None else 0, 1 if need_din else 0, 1 if poison else 0,
+                                         L.ptr(dx), L.ptr(dW), L.ptr(db), _stream()))
+        dxo = dx[..., :Cin].permute(0, 3, 1, 2).contiguous() if need_din else None
+        return dxo, dW.view_as(w), db
+
+    def op_linear_bwd(self, x, w, dy, B=1, bias=None, x_half=False, geglu=False, dx_half=False, staged=True, xp=False, accum=None,
+                      poison=False):
+        """Linear adjoint: x [rows,K], w [N,K], dy [rows,N] (geglu: dy = dL/d(value * gelu(gate)) [rows,N/2], bias needed)
+        -> (dx [rows,K], dW [N,K], db [N])."""
+        dev = self.device
+        rows, K = x.shape
+        N = w.shape[0]
+        kp = (K + 7) // 8 * 8
+        xn, dyn, ww = self._pad_last(x, kp), _f32(dy, dev), _f32(w, dev)
+        bb = None if bias is None else _f32(bias, dev)
+        dx = torch.zeros(rows, kp, device=dev)
+        dW = torch.zeros(N, K, device=dev)
+        db = torch.zeros(N, device=dev)
+        if accum is not None:
+            dx.copy_(self._pad_last(accum[0], kp))
+            dW.copy_(accum[1])
+            db.copy_(accum[2])
+        L.check(self.lib.mvd_op_linear_bwd(self._ctx, int(B), rows, K, N, L.ptr(xn), 1 if x_half else 0, L.ptr(ww), L.ptr(bb), L.ptr(dyn),
+                                           1 if geglu else 0, 1 if dx_half else 0, 1 if staged else 0, 1 if xp else 0,
+                                           1 if accum is not None else 0, 1 if poison else 0, L.ptr(dx), L.ptr(dW), L.ptr(db), _stream()))
+        return dx[:, :K].contiguous(), dW, db
+
+    def op_conv3d_bwd(self, x, w, dy, kind=0, x_half=False, accum=None, poison=False):
+        """Conv3d k3 p1 stride 1 (kind 0) / stride 2 (1), ConvTranspose3d(k3, s2, p1, op1) (2) adjoint.  x [B,Cin,D,H,W], w
+        [Cout,Cin,3,3,3] (kind 2: [Cin,Cout,3,3,3]), dy on the output grid -> (dx, dW like w, db [Cout])."""
+        dev = self.device
+        B, Cin, D, H, W = x.shape
+        Cout = w.shape[1] if kind == 2 else w.shape[0]
+        xn = _f32(x.permute(0, 2, 3, 4, 1), dev)
+        dyn = _f32(dy.permute(0, 2, 3, 4, 1), dev)
+        ww = _f32(w, dev)
+        dx = torch.zeros(B, D, H, W, Cin, device=dev)
+        dW = torch.zeros(w.shape, device=dev)
+        db = torch.zeros(Cout, device=dev)
+        if accum is not None:
+            dx.copy_(accum[0].permute(0, 2, 3, 4, 1))
+            dW.copy_(accum[1])
+            db.copy_(accum[2])
+        L.check(self.lib.mvd_op_conv3d_bwd(self._ctx, int(kind), B, Cin, D, H, W, Cout, L.ptr(xn), 1 if x_half else 0, L.ptr(ww), L.ptr(dyn),
+                                           1 if accum is not None else 0, 1 if poison else 0, L.ptr(dx), L.ptr(dW), L.ptr(db), _stream()))
+        return dx.permute(0, 4, 1, 2, 3).contiguous(), dW, db
+
+    def op_tgemm(self, a, b, a_trans=False, b_trans=False, a_half=False, b_half=False, xp=False, out=None, poison=False):
+        """op(A) op(B) through the training step's tgemm: a stored [M,K] ([K,M] with a_trans), b stored [K,N] ([N,K] with b_trans).
+        out (optional, [M,N]): accumulated into.  Returns the [M,N] result."""
+        dev = self.device
+        a, b = _f32(a, dev), _f32(b, dev)
+        M, K = (a.shape[1], a.shape[0]) if a_trans else a.shape
+        N = b.shape[0] if b_trans else b.shape[1]
+        o = torch.zeros(M, N, device=dev) if out is None else _f32(out, dev).clone()
+        L.check(self.lib.mvd_op_tgemm(self._ctx, M, N, K, L.ptr(a), 1 if a_half else 0, 1 if a_trans else 0, C.c_long(a.shape[1]),
+                                      L.ptr(b), 1 if b_half else 0, 1 if b_trans else 0, C.c_long(b.shape[1]), L.ptr(o), N,
+                                      1 if out is not None else 0, 1 if xp else 0, 1 if poison else 0, _stream()))
+        return o
+
     def bench_conv(self, B, Cc, H, W, Cout, iters=20):
         ms = C.c_float(0)
         L.check(self.lib.mvd_bench_conv(self._ctx, B, Cc, H, W, Cout, iters, C.byref(ms), _stream()))
