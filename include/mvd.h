@@ -350,7 +350,24 @@ int mvd_denoise_views_batch(mvd_ctx* ctx, int B, const int* slots, const float* 
                             float cfg_scale, const float* noise, float sqrt_one_minus_at, float sqrt_at, float sqrt_aprev,
                             float dir_coef, float sigma, float* eps_out, float* x_prev, void* stream);
 
+/* The same step with a DPM-Solver++ multistep update in place of DDIM's (SyncDPMSolverSampler, morphablediffusion_amd/schedule.py
+ * DPMSolverSchedule): the arguments of mvd_denoise_views_batch up to `noise`, then one step's coefficient row.  With the guided
+ * eps and x0 = (x_noisy - s1m eps) / sqrt_at (DDIM's x0 prediction):
+ *     x_next = c_x x_noisy + c_d x0 + c_c (x0 - x0_hist) + c_n noise,   then x0_hist <- x0.
+ * x0_hist [B,TN,4,h,w]: the previous step's x0, read and overwritten in place (required).  first != 0: the first step of a
+ * trajectory -- x0_hist is written but NOT read (its contents may be anything, NaN included).  noise may be NULL (no noise
+ * term); eps_out may be NULL; x_next is required.  B == 1 with slots == NULL is the single-sample step. */
+int mvd_denoise_views_ms(mvd_ctx* ctx, int B, const int* slots, const float* x_noisy, const float* x_input, const float* clip,
+                         const int64_t* timesteps, const float* t_embed, const float* v_embed, const int32_t* view_idx, int TN,
+                         float cfg_scale, const float* noise, float s1m, float sqrt_at, float c_x, float c_d, float c_c, float c_n,
+                         float* x0_hist, int first, float* eps_out, float* x_next, void* stream);
+
 /* ---- single-kernel hooks used by the parity tests (tests/test_gpu_ops.py) ---- */
+/* The update kernel of mvd_denoise_views_ms on its own, over n device floats: eps = eps_u + scale (eps_c - eps_u) (eps_u NULL:
+ * eps = eps_c), then the update above.  No context: runs on the current device. */
+int mvd_op_cfg_ms(const float* eps_c, const float* eps_u, float scale, const float* x, const float* noise, float s1m, float sqrt_at,
+                  float c_x, float c_d, float c_c, float c_n, float* x0_hist, int first, float* eps_out, float* x_next, size_t n,
+                  void* stream);
 int mvd_op_conv(mvd_ctx* ctx, const float* x_nchw, int B, int Cin, int H, int W, const float* w, const float* bias,
                 int Cout, int ksize, int stride, int upsample, const float* resid_nchw, float* out_nchw, int force_splitk,
                 void* stream);

@@ -786,13 +786,18 @@ int mvd_frustum_volumes_batch(mvd_ctx* c, int B, const int* slots, const float* 
   return 0;
 }
 
-int mvd_denoise_views_batch(mvd_ctx* c, int B, const int* slots, const float* x_noisy, const float* x_input, const float* clip,
-                            const int64_t* timesteps, const float* t_embed, const float* v_embed, const int32_t* view_idx, int TN,
-                            float cfg_scale, const float* noise, float sqrt_one_minus_at, float sqrt_at, float sqrt_aprev,
-                            float dir_coef, float sigma, float* eps_out, float* x_prev, void* stream) {
+// The final launch of a denoising step: (guided-eps inputs eps_c / eps_u (null without guidance), element count, stream) -> the
+// sampler's update kernel (cfg_ddim_kernel or cfg_dpm_kernel)
+typedef std::function<int(const float*, const float*, size_t, hipStream_t)> StepUpdate;
+
+// The body shared by mvd_denoise_views_batch (DDIM) and mvd_denoise_views_ms (DPM-Solver++): CFG input rows -> UNet -> NCHW eps;
+// only the update launch differs
+static int denoise_views_common(const char* name, mvd_ctx* c, int B, const int* slots, const float* x_noisy, const float* x_input,
+                                const float* clip, const int64_t* timesteps, const float* t_embed, const float* v_embed,
+                                const int32_t* view_idx, int TN, float cfg_scale, const StepUpdate& update, void* stream) {
   if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
   if (!c || !c->finalized) return mvd_fail("weights not finalized");
-  if (B < 1 || TN < 1 || (B > 1 && !slots) || !timesteps) return mvd_fail("mvd_denoise_views_batch: bad argument");
+  if (B < 1 || TN < 1 || (B > 1 && !slots) || !timesteps) return mvd_fail((std::string(name) + ": bad argument").c_str());
   hipStream_t s = S(stream);
   const mvd_unet_config& u = c->u;
   if (u.in_channels != 8 || u.out_channels != 4) return mvd_fail("denoise_views: expects the 8-in / 4-out latent UNet");
@@ -840,9 +845,39 @@ int mvd_denoise_views_batch(mvd_ctx* c, int B, const int* slots, const float* x_
   RET_IF(engine_unet(c, xin, 8, tt, ctx, Bv, B * TN, c->v.frustum_volume_depth, cl, eps, s, &produce));
   RET_IF(launch_nhwc_to_nchw(eps, 4, Bv, 4, HW, eps_nchw, s));
   const size_t n = (size_t)B * TN * 4 * HW;
-  RET_IF(launch_cfg_ddim(eps_nchw, cfg ? eps_nchw + n : nullptr, cfg_scale, x_noisy, noise, sqrt_one_minus_at, sqrt_at,
-                         sqrt_aprev, dir_coef, sigma, eps_out, x_prev, n, s));
-  return 0;
+  return update(eps_nchw, cfg ? eps_nchw + n : nullptr, n, s);
+}
+
+int mvd_denoise_views_batch(mvd_ctx* c, int B, const int* slots, const float* x_noisy, const float* x_input, const float* clip,
+                            const int64_t* timesteps, const float* t_embed, const float* v_embed, const int32_t* view_idx, int TN,
+                            float cfg_scale, const float* noise, float sqrt_one_minus_at, float sqrt_at, float sqrt_aprev,
+                            float dir_coef, float sigma, float* eps_out, float* x_prev, void* stream) {
+  const StepUpdate ddim = [&](const float* ec, const float* eu, size_t n, hipStream_t s) {
+    return launch_cfg_ddim(ec, eu, cfg_scale, x_noisy, noise, sqrt_one_minus_at, sqrt_at, sqrt_aprev, dir_coef, sigma, eps_out,
+                           x_prev, n, s);
+  };
+  return denoise_views_common("mvd_denoise_views_batch", c, B, slots, x_noisy, x_input, clip, timesteps, t_embed, v_embed, view_idx,
+                              TN, cfg_scale, ddim, stream);
+}
+
+int mvd_denoise_views_ms(mvd_ctx* c, int B, const int* slots, const float* x_noisy, const float* x_input, const float* clip,
+                         const int64_t* timesteps, const float* t_embed, const float* v_embed, const int32_t* view_idx, int TN,
+                         float cfg_scale, const float* noise, float s1m, float sqrt_at, float c_x, float c_d, float c_c, float c_n,
+                         float* x0_hist, int first, float* eps_out, float* x_next, void* stream) {
+  if (!x0_hist || !x_next) return mvd_fail("mvd_denoise_views_ms: x0_hist and x_next are required");
+  const DpmCoef k{s1m, sqrt_at, c_x, c_d, c_c, c_n};
+  const StepUpdate dpm = [&](const float* ec, const float* eu, size_t n, hipStream_t s) {
+    return launch_cfg_dpm(ec, eu, cfg_scale, x_noisy, noise, k, x0_hist, first ? 0 : 1, eps_out, x_next, n, s);
+  };
+  return denoise_views_common("mvd_denoise_views_ms", c, B, slots, x_noisy, x_input, clip, timesteps, t_embed, v_embed, view_idx, TN,
+                              cfg_scale, dpm, stream);
+}
+
+int mvd_op_cfg_ms(const float* eps_c, const float* eps_u, float scale, const float* x, const float* noise, float s1m, float sqrt_at,
+                  float c_x, float c_d, float c_c, float c_n, float* x0_hist, int first, float* eps_out, float* x_next, size_t n,
+                  void* stream) {
+  return launch_cfg_dpm(eps_c, eps_u, scale, x, noise, DpmCoef{s1m, sqrt_at, c_x, c_d, c_c, c_n}, x0_hist, first ? 0 : 1, eps_out,
+                        x_next, n, S(stream));
 }
 
 int mvd_denoise_views(mvd_ctx* c, const float* x_noisy, const float* x_input, const float* clip, int64_t timestep,

@@ -224,6 +224,14 @@ int launch_relu_beta_tile(const float* beta, int Cc, int heads, half_t* out, hip
 int launch_cfg_ddim(const float* eps_c, const float* eps_u, float scale, const float* x, const float* noise,
                     float sqrt_one_minus_at, float sqrt_at, float sqrt_aprev, float dir_coef, float sigma,
                     float* eps_out, float* x_prev, size_t n, hipStream_t s);
+// DPM-Solver++ multistep update coefficients of one step (schedule.py DPMSolverSchedule.rows)
+struct DpmCoef {
+  float s1m, sqrt_at, c_x, c_d, c_c, c_n;
+};
+// CFG combine + x0 prediction + x_next = c_x x + c_d x0 + c_c (x0 - x0_hist) + c_n noise, x0 -> x0_hist (in place);
+// x0_hist is not read when use_hist == 0; eps_u / noise / eps_out may be null
+int launch_cfg_dpm(const float* eps_c, const float* eps_u, float scale, const float* x, const float* noise, DpmCoef k,
+                   float* x0_hist, int use_hist, float* eps_out, float* x_next, size_t n, hipStream_t s);
 // conditioner
 struct ViewCam {
   float P[12];     // 3x4 projection into the size x size feature map (rows of the 4x4 minus the last)

@@ -417,6 +417,53 @@ __global__ void cfg_ddim_kernel(const float* __restrict__ ec, const float* __res
   }
 }
 
+// The same CFG combine and x0 prediction (same expressions, same order), then one DPM-Solver++ multistep update
+// (schedule.py DPMSolverSchedule):  x_next = c_x x + c_d x0 + c_c (x0 - x0_hist) + c_n noise,  x0_hist <- x0.
+// x0_hist is read, then overwritten, by the same thread (in place); it is not read when use_hist == 0 (the first step: its
+// contents are undefined there and 0 * NaN would not vanish).  eu, noise and eps_out may be null.
+__device__ __forceinline__ void dpm_elem(float ec, const float eu, bool has_eu, float scale, float x, float z, bool has_z, float h,
+                                         bool use_hist, const DpmCoef& k, float& e, float& pred_x0, float& xn) {
+  e = ec;
+  if (has_eu) e = eu + scale * (e - eu);
+  pred_x0 = (x - k.s1m * e) / k.sqrt_at;
+  xn = k.c_x * x + k.c_d * pred_x0;
+  if (use_hist) xn += k.c_c * (pred_x0 - h);
+  if (has_z) xn += k.c_n * z;
+}
+
+// vec != 0 (every pointer 16-byte aligned): elements [0, n & ~3) move as float4 (16-byte loads / stores), the scalar loop
+// takes the tail; vec == 0: the scalar loop takes everything
+__global__ void cfg_dpm_kernel(const float* __restrict__ ec, const float* __restrict__ eu, float scale, const float* __restrict__ x,
+                               const float* __restrict__ noise, DpmCoef k, float* x0_hist, int use_hist,
+                               float* __restrict__ eps_out, float* __restrict__ x_next, size_t n, int vec) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x, tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t n4 = vec ? n / 4 : 0;
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (size_t q = tid; q < n4; q += stride) {
+    const float4 c4 = reinterpret_cast<const float4*>(ec)[q];
+    const float4 u4 = eu ? reinterpret_cast<const float4*>(eu)[q] : zero4;
+    const float4 x4 = reinterpret_cast<const float4*>(x)[q];
+    const float4 z4 = noise ? reinterpret_cast<const float4*>(noise)[q] : zero4;
+    const float4 h4 = use_hist ? reinterpret_cast<const float4*>(x0_hist)[q] : zero4;
+    float4 e4, p4, n4v;
+    dpm_elem(c4.x, u4.x, eu, scale, x4.x, z4.x, noise, h4.x, use_hist, k, e4.x, p4.x, n4v.x);
+    dpm_elem(c4.y, u4.y, eu, scale, x4.y, z4.y, noise, h4.y, use_hist, k, e4.y, p4.y, n4v.y);
+    dpm_elem(c4.z, u4.z, eu, scale, x4.z, z4.z, noise, h4.z, use_hist, k, e4.z, p4.z, n4v.z);
+    dpm_elem(c4.w, u4.w, eu, scale, x4.w, z4.w, noise, h4.w, use_hist, k, e4.w, p4.w, n4v.w);
+    if (eps_out) reinterpret_cast<float4*>(eps_out)[q] = e4;
+    reinterpret_cast<float4*>(x0_hist)[q] = p4;
+    reinterpret_cast<float4*>(x_next)[q] = n4v;
+  }
+  for (size_t i = n4 * 4 + tid; i < n; i += stride) {
+    float e, p, xn;
+    dpm_elem(ec[i], eu ? eu[i] : 0.f, eu, scale, x[i], noise ? noise[i] : 0.f, noise, use_hist ? x0_hist[i] : 0.f, use_hist, k, e, p,
+             xn);
+    if (eps_out) eps_out[i] = e;
+    x0_hist[i] = p;
+    x_next[i] = xn;
+  }
+}
+
 __global__ void add_rows_kernel(float* __restrict__ dst, const float* __restrict__ a, const float* __restrict__ b, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
     dst[i] = a[i] + (b ? b[i] : 0.f);
@@ -559,6 +606,19 @@ int launch_cfg_ddim(const float* eps_c, const float* eps_u, float scale, const f
                     float* eps_out, float* x_prev, size_t n, hipStream_t s) {
   hipLaunchKernelGGL(cfg_ddim_kernel, dim3(grid_for(n)), dim3(256), 0, s, eps_c, eps_u, scale, x, noise,
                      sqrt_one_minus_at, sqrt_at, sqrt_aprev, dir_coef, sigma, eps_out, x_prev, n);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+
+int launch_cfg_dpm(const float* eps_c, const float* eps_u, float scale, const float* x, const float* noise, DpmCoef k,
+                   float* x0_hist, int use_hist, float* eps_out, float* x_next, size_t n, hipStream_t s) {
+  if (n == 0) return 0;
+  if (!eps_c || !x || !x0_hist || !x_next) return mvd_fail("launch_cfg_dpm: null argument");
+  const auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  const int vec = al(eps_c) && al(eps_u) && al(x) && al(noise) && al(x0_hist) && al(eps_out) && al(x_next);
+  const size_t work = vec ? n / 4 + (n & 3) : n;
+  hipLaunchKernelGGL(cfg_dpm_kernel, dim3(grid_for(work)), dim3(256), 0, s, eps_c, eps_u, scale, x, noise, k, x0_hist, use_hist ? 1 : 0,
+                     eps_out, x_next, n, vec);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }

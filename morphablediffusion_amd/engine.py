@@ -612,7 +612,56 @@ class Engine:
             L.ptr(eps), L.ptr(x_prev), _stream()))
         return (x_prev, eps) if want_eps else x_prev
 
+    def denoise_views_ms(self, slots, x_noisy, x_input, clip, timesteps, t_embed, v_embed, view_idx, cfg_scale, noise, coef,
+                         x0_hist, first, want_eps=False, out=None, eps_out=None):
+        """One denoising step with the DPM-Solver++ multistep update (mvd_denoise_views_ms).  slots None: one sample, shaped as for
+        denoise_views (x_noisy [TN,4,h,w], timesteps one int); else the shapes of denoise_views_batch.  coef = (s1m, sqrt_at, c_x,
+        c_d, c_c, c_n) python floats (DPMSolverSchedule.coefficients); x0_hist: contiguous float32 device tensor shaped like
+        x_noisy, read (unless ``first``) and overwritten with this step's x0.  ``out`` / ``eps_out`` as for denoise_views."""
+        dev = self.device
+        x = _f32(x_noisy, dev)
+        single = slots is None
+        B, TN = (1, x.shape[0]) if single else x.shape[:2]
+        vi = view_idx.to(device=dev, dtype=torch.int32).contiguous()
+        steps = [timesteps] if single else list(timesteps)
+        assert vi.shape[0] == TN and len(steps) == B and (single or len(slots) == B)
+        if not (x0_hist.is_contiguous() and x0_hist.dtype == torch.float32 and x0_hist.device == x.device and x0_hist.shape == x.shape):
+            raise ValueError("x0_hist must be a contiguous float32 tensor on the engine's device shaped like x_noisy")
+
+        def direct(t):
+            return t is not None and t.is_contiguous() and t.dtype == torch.float32 and t.device == x.device and t.shape == x.shape
+
+        x_next = out if direct(out) else torch.empty_like(x)
+        eps = (eps_out if direct(eps_out) else torch.empty_like(x)) if want_eps else None
+        nz = None if noise is None else _f32(noise, dev)
+        xi, cl, te, ve = _f32(x_input, dev), _f32(clip, dev), _f32(t_embed, dev), _f32(v_embed, dev)
+        sl = None if single else (C.c_int * B)(*[int(v) for v in slots])
+        ts = (C.c_int64 * B)(*[int(v) for v in steps])
+        L.check(self.lib.mvd_denoise_views_ms(
+            self._ctx, B, sl, L.ptr(x), L.ptr(xi), L.ptr(cl), ts, L.ptr(te), L.ptr(ve), L.ptr(vi), TN, C.c_float(cfg_scale),
+            L.ptr(nz), *[C.c_float(v) for v in coef], L.ptr(x0_hist), 1 if first else 0, L.ptr(eps), L.ptr(x_next), _stream()))
+        if out is not None and x_next is not out:
+            out.copy_(x_next)
+        if want_eps and eps_out is not None and eps is not eps_out:
+            eps_out.copy_(eps)
+        return (x_next, eps) if want_eps else x_next
+
     # ---- single-kernel hooks (parity tests) -------------------------------------------------------
+    def op_cfg_ms(self, eps_c, eps_u, scale, x, noise, coef, x0_hist, first, want_eps=False):
+        """The update kernel of denoise_views_ms alone (mvd_op_cfg_ms) over flat float32 device tensors: returns x_next (and the
+        guided eps); x0_hist is updated in place.  eps_u / noise may be None."""
+        dev = self.device
+        ec, x = _f32(eps_c, dev), _f32(x, dev)
+        eu = None if eps_u is None else _f32(eps_u, dev)
+        nz = None if noise is None else _f32(noise, dev)
+        assert x0_hist.is_contiguous() and x0_hist.dtype == torch.float32 and x0_hist.numel() == x.numel()
+        x_next = torch.empty_like(x)
+        eps = torch.empty_like(x) if want_eps else None
+        L.check(self.lib.mvd_op_cfg_ms(L.ptr(ec), L.ptr(eu), C.c_float(scale), L.ptr(x), L.ptr(nz), *[C.c_float(v) for v in coef],
+                                       L.ptr(x0_hist), 1 if first else 0, L.ptr(eps), L.ptr(x_next), C.c_size_t(x.numel()),
+                                       _stream()))
+        return (x_next, eps) if want_eps else x_next
+
     def op_conv(self, x, w, bias=None, stride=1, upsample=0, resid=None, force_splitk=0):
         dev = self.device
         x, w = _f32(x, dev), _f32(w, dev)

@@ -2,7 +2,7 @@
 MI355X engine: same flags, same batch construction, same outputs.
 
   --input_img IMG --exp_img IMG --mesh MESH.{ply,obj} --cfg configs/facescape.yaml --ckpt CKPT --output_dir DIR
-  [--cfg_scale 2.0] [--batch_view_num 8] [--seed 6033] [--sampler ddim] [--sample_steps 50]
+  [--cfg_scale 2.0] [--batch_view_num 8] [--seed 6033] [--sampler ddim|dpmpp_2m|dpmpp_2m_sde] [--sample_steps 50]
   [--camera_trajectory virtual|real] [--prepare_neus2_data]
 
 writes ``<output_dir>/<input>_<exp>.png`` (the input view followed by the 16 generated views, generate_face.py:244-253) and, with
@@ -122,7 +122,8 @@ def build_parser():
     p.add_argument("--cfg_scale", type=float, default=2.0)
     p.add_argument("--batch_view_num", type=int, default=8)
     p.add_argument("--seed", type=int, default=6033)
-    p.add_argument("--sampler", type=str, default="ddim")
+    p.add_argument("--sampler", type=str, default="ddim", choices=["ddim", "dpmpp_2m", "dpmpp_2m_sde"],
+                   help="ddim: the reference's sampler; dpmpp_2m / dpmpp_2m_sde: DPM-Solver++(2M) on the logSNR grid (not reference)")
     p.add_argument("--sample_steps", type=int, default=50)
     p.add_argument("--camera_trajectory", type=str, default="virtual", choices=["real", "virtual"])
     p.add_argument("--prepare_neus2_data", action="store_true")
@@ -136,7 +137,7 @@ def run(flags, model=None):
     """The body of generate_face.py:main (:107-262).  ``model``: an already loaded SyncMultiviewDiffusion (tests); default:
     batch.load_model(flags.cfg, flags.ckpt).  Returns (strip uint8 [256, 17*256, 3], output path)."""
     from PIL import Image
-    from .model import SyncDDIMSampler, SyncMultiviewDiffusion
+    from .model import SyncDDIMSampler, SyncDPMSolverSampler, SyncMultiviewDiffusion
     img_name = flags.input_img.split("/")[-1].split(".")[0]
     exp_name = flags.exp_img.split("/")[-1].split(".")[0]
     torch.random.manual_seed(flags.seed)
@@ -145,9 +146,12 @@ def run(flags, model=None):
         model = B.load_model(flags.cfg, flags.ckpt, device=flags.device)
     assert isinstance(model, SyncMultiviewDiffusion)
     Path(flags.output_dir).mkdir(exist_ok=True, parents=True)
-    if flags.sampler != "ddim":
-        raise NotImplementedError
-    sampler = SyncDDIMSampler(model, flags.sample_steps, latent_size=model.image_size // 8)
+    if flags.sampler == "ddim":
+        sampler = SyncDDIMSampler(model, flags.sample_steps, latent_size=model.image_size // 8)
+    elif flags.sampler in ("dpmpp_2m", "dpmpp_2m_sde"):
+        sampler = SyncDPMSolverSampler(model, flags.sample_steps, flags.sampler, latent_size=model.image_size // 8)
+    else:
+        raise NotImplementedError(flags.sampler)
     if flags.camera_trajectory == "real":
         cams = B.cameras_from_dict(load_camera_dict(flags.camera_file), NUM_VIEWS)
     else:

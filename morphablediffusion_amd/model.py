@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from .engine import Engine
-from .schedule import DDIMSchedule
+from .schedule import SOLVERS, DDIMSchedule, DPMSolverSchedule
 from .spec import UNetConfig, VolumeConfig
 
 
@@ -364,9 +364,12 @@ class SyncMultiviewDiffusion(nn.Module):
         self.model.diffusion_model.bind(self.engine)
         self.spatial_volume.bind(self.engine)
         self._device = torch.device(device)
-        if sample_type != "ddim":
-            raise NotImplementedError  # morphable_diffusion.py:359
-        self.sampler = SyncDDIMSampler(self, sample_steps, "uniform", 1.0, latent_size=image_size // 8)
+        if sample_type == "ddim":
+            self.sampler = SyncDDIMSampler(self, sample_steps, "uniform", 1.0, latent_size=image_size // 8)
+        elif sample_type in SOLVERS:  # DPM-Solver++(2M), not a reference sampler
+            self.sampler = SyncDPMSolverSampler(self, sample_steps, sample_type, latent_size=image_size // 8)
+        else:
+            raise NotImplementedError(sample_type)  # morphable_diffusion.py:359
 
     @property
     def device(self):
@@ -946,7 +949,6 @@ class SyncDDIMSampler:
                  shard_views=False, exchange="all_gather", overlap=True):
         self.model = model
         self.ddpm_num_timesteps = model.num_timesteps
-        self.latent_size = latent_size
         self.schedule = DDIMSchedule(ddim_num_steps, ddim_eta, self.ddpm_num_timesteps)
         if ddim_discretize != "uniform":
             raise NotImplementedError(f'There is no ddim discretization method called "{ddim_discretize}"')
@@ -955,6 +957,11 @@ class SyncDDIMSampler:
         self.ddim_sigmas = self.schedule.ddim_sigmas
         self.ddim_sqrt_one_minus_alphas = self.schedule.ddim_sqrt_one_minus_alphas
         self.eta = ddim_eta
+        self._init_runtime(latent_size, shard_views, exchange, overlap)
+
+    def _init_runtime(self, latent_size, shard_views, exchange, overlap):
+        """What every sampler over this engine shares: view sharding, the exchange, batching of B > 1, persistent buffers."""
+        self.latent_size = latent_size
         self.shard_views = shard_views
         if exchange not in ("all_gather", "all_reduce"):
             raise ValueError(f"unknown exchange {exchange!r}")
@@ -1011,7 +1018,7 @@ class SyncDDIMSampler:
             raise ValueError("x_target_noisy must hold all views when the sampler is not sharded")
         v_embed = self._v_embed(batch, x_target_noisy.device)
         t_embed = m.embed_time(time_steps)
-        coef = self.schedule.coefficients(index)
+        coef = self._coefficients(index)
         if noise is None and not is_step0:
             noise = torch.randn_like(x_target_noisy)
         out = torch.empty_like(x_target_noisy, memory_format=torch.contiguous_format)
@@ -1030,7 +1037,7 @@ class SyncDDIMSampler:
             try:
                 return self._denoise_apply_batched(x_target_noisy, x_input, clip_embed, host_steps, t_embed, v_embed, local_idx, lo, NL,
                                                    rank, world, N, unconditional_scale, batch_view_num, is_step0, batch, noise, coef,
-                                                   out, eps_out, return_eps)
+                                                   out, eps_out, return_eps, index)
             except Exception as e:  # MvdError from the library
                 if "workspace" not in str(e):
                     raise
@@ -1050,8 +1057,8 @@ class SyncDDIMSampler:
                 # x_prev / eps land in the caller-visible tensors straight from the C call (contiguous slices of `out`), and the
                 # view embeddings are a slice, not a gather: no torch kernel on the step path
                 o_v, e_v = out[bi, sl], (eps_out[bi, sl] if return_eps else None)
-                r = eng.denoise_views(
-                    x_target_noisy[bi, sl], x_input[bi], clip_embed[bi].reshape(-1), host_steps[bi], t_embed[bi],
+                r = self._views_step(
+                    eng, index, bi, sl, x_target_noisy[bi, sl], x_input[bi], clip_embed[bi].reshape(-1), host_steps[bi], t_embed[bi],
                     v_embed[bi, lo + sl.start:lo + sl.stop], idx, float(unconditional_scale),
                     None if is_step0 else noise[bi, sl], coef, want_eps=return_eps, out=o_v, eps_out=e_v)
                 xp, ep = r if return_eps else (r, None)
@@ -1062,7 +1069,7 @@ class SyncDDIMSampler:
         return (out, eps_out) if return_eps else out
 
     def _denoise_apply_batched(self, x_target_noisy, x_input, clip_embed, host_steps, t_embed, v_embed, local_idx, lo, NL, rank, world,
-                               N, unconditional_scale, batch_view_num, is_step0, batch, noise, coef, out, eps_out, return_eps):
+                               N, unconditional_scale, batch_view_num, is_step0, batch, noise, coef, out, eps_out, return_eps, index=None):
         from .engine import MAX_SAMPLE_SLOTS
         m, eng = self.model, self.model.engine
         B = x_target_noisy.shape[0]
@@ -1076,8 +1083,8 @@ class SyncDDIMSampler:
         for ni in range(0, NL, batch_view_num):
             sl = slice(ni, min(NL, ni + batch_view_num))
             idx = local_idx[sl]
-            r = eng.denoise_views_batch(
-                slots, x_target_noisy[:, sl], x_input, clip_embed.reshape(B, -1), host_steps, t_embed,
+            r = self._views_step_batch(
+                eng, index, sl, slots, x_target_noisy[:, sl], x_input, clip_embed.reshape(B, -1), host_steps, t_embed,
                 v_embed[:, lo + sl.start:lo + sl.stop], idx, float(unconditional_scale),
                 None if is_step0 else noise[:, sl], coef, want_eps=return_eps)
             if return_eps:
@@ -1085,6 +1092,19 @@ class SyncDDIMSampler:
             else:
                 out[:, sl] = r
         return (out, eps_out) if return_eps else out
+
+    # -- the sampler's update (SyncDPMSolverSampler overrides these four) --------------------------------------------------
+    def _coefficients(self, index):
+        return self.schedule.coefficients(index)
+
+    def _begin_sample(self, B, NL, device):
+        pass
+
+    def _views_step(self, eng, index, bi, sl, *args, **kw):
+        return eng.denoise_views(*args, **kw)
+
+    def _views_step_batch(self, eng, index, sl, *args, **kw):
+        return eng.denoise_views_batch(*args, **kw)
 
     def _v_embed(self, batch, device):
         """get_viewpoint_embedding(batch) on `device`, cached on the CONTENT identity of the four angle tensors (storage address,
@@ -1121,7 +1141,12 @@ class SyncDDIMSampler:
         # (construct_spatial_volume, morphable_diffusion.py:253-254); callers that sample call .eval() (generate_face.py:77)
         bn_train = bool(getattr(self.model.spatial_volume, "training", False))
         if side and self._comm is None:
-            self._comm = (torch.cuda.Stream(device=dev), torch.cuda.Event(), torch.cuda.Event())
+            # one set per engine, shared by every sampler of the model: the engine keeps the volume event registered after the
+            # sampler that recorded it is gone, and the next table upload (mvd_set_samples_async) waits on it -- an event owned by
+            # a collected sampler would be destroyed under that wait
+            self._comm = getattr(eng, "_volume_comm", None)
+            if self._comm is None:
+                self._comm = eng._volume_comm = (torch.cuda.Stream(device=dev), torch.cuda.Event(), torch.cuda.Event())
         NL = x_local.shape[0]
         if self.exchange == "all_gather":
             Nv = eng.num_vertices
@@ -1205,6 +1230,7 @@ class SyncDDIMSampler:
             return torch.randn([B, N, C, H, W], device=device, generator=generator)[:, lo:hi].contiguous()
 
         x = draw()
+        self._begin_sample(B, hi - lo, device)
         intermediates = {"x_inter": []}
         if return_eps:
             intermediates["eps"] = []
@@ -1240,3 +1266,57 @@ class SyncDDIMSampler:
         parts = [torch.empty_like(x) for _ in range(world)]
         dist.all_gather(parts, x.contiguous())
         return torch.cat(parts, 1)
+
+
+class SyncDPMSolverSampler(SyncDDIMSampler):
+    """DPM-Solver++(2M) (Lu et al. 2022, "DPM-Solver++", Alg. 2) over the same engine: everything but the update is
+    SyncDDIMSampler's -- volume building, view sharding, batched B > 1 and its loop fallback, the sample() loop, its RNG order
+    (x_T first, then one N(0,1) draw per step except the last) and its return value.  The update is fused into the step's last
+    kernel (mvd_denoise_views_ms), which also keeps the previous step's x0 in a device buffer the sampler owns.
+
+    solver: "dpmpp_2m" (the ODE solver; its draws are made but unused) or "dpmpp_2m_sde" (eta = 1).  order 1 is the first-order
+    solver -- DDIM at eta = 0 for "dpmpp_2m".  spacing: "logsnr" (uniform in lambda = log(alpha / sigma), integer timesteps
+    999 -> 0; the grid on which the solver is second order) or "uniform" (the reference's DDIM grid).
+    ``ddim_timesteps`` holds the S model-evaluation timesteps in increasing order, as the DDIM sampler's does."""
+
+    def __init__(self, model, steps, solver="dpmpp_2m", order=2, spacing="logsnr", latent_size=32, shard_views=False,
+                 exchange="all_gather", overlap=True):
+        self.model = model
+        self.ddpm_num_timesteps = model.num_timesteps
+        self.schedule = DPMSolverSchedule(steps, solver, order, spacing, self.ddpm_num_timesteps)
+        self.solver, self.order, self.spacing = solver, order, spacing
+        self.ddim_timesteps = np.flip(self.schedule.timesteps[:-1]).copy()
+        self._x0_hist = None
+        self._init_runtime(latent_size, shard_views, exchange, overlap)
+
+    # sample() counts index down from S - 1 (the first step) to 0 (the last): step i = S - 1 - index
+    def _coefficients(self, index):
+        return self.schedule.coefficients(self.schedule.steps - 1 - index)
+
+    def _begin_sample(self, B, NL, device):
+        """The x0 history [B, N_local, 4, h, w], allocated once per sample() call.  Stored chunk-major: the views [lo, hi) of one
+        engine call are one contiguous [B, hi - lo, 4, h, w] block, so that the batched call reads and writes it in place."""
+        self._x0_hist = torch.empty((B, NL, 4, self.latent_size, self.latent_size), device=device, dtype=torch.float32)
+
+    def denoise_apply(self, x_target_noisy, *args, **kwargs):
+        h = self._x0_hist
+        if h is None or h.shape != x_target_noisy.shape or h.device != x_target_noisy.device:
+            self._begin_sample(x_target_noisy.shape[0], x_target_noisy.shape[1], x_target_noisy.device)
+        return super().denoise_apply(x_target_noisy, *args, **kwargs)
+
+    def _hist(self, sl):
+        B, NL = self._x0_hist.shape[:2]
+        E = self._x0_hist[0, 0].numel()
+        flat = self._x0_hist.view(-1)
+        return flat[B * sl.start * E:B * sl.stop * E].view(B, sl.stop - sl.start, *self._x0_hist.shape[2:])
+
+    def _noise(self, noise):
+        return noise if self.solver == "dpmpp_2m_sde" else None  # c_n = 0: skip the read
+
+    def _views_step(self, eng, index, bi, sl, x, x_input, clip, step, t_embed, v_embed, idx, scale, noise, coef, **kw):
+        return eng.denoise_views_ms(None, x, x_input, clip, step, t_embed, v_embed, idx, scale, self._noise(noise), coef,
+                                    self._hist(sl)[bi], index == self.schedule.steps - 1, **kw)
+
+    def _views_step_batch(self, eng, index, sl, slots, x, x_input, clip, steps, t_embed, v_embed, idx, scale, noise, coef, **kw):
+        return eng.denoise_views_ms(slots, x, x_input, clip, steps, t_embed, v_embed, idx, scale, self._noise(noise), coef,
+                                    self._hist(sl), index == self.schedule.steps - 1, **kw)
