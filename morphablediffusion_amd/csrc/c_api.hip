@@ -125,7 +125,7 @@ int mvd_create(const mvd_unet_config* ucfg, const mvd_volume_config* vcfg, int d
   c->u = *ucfg;
   c->v = *vcfg;
   c->device = device;
-  c->use_halo = getenv("MVD_NO_HALO") == nullptr;
+  c->use_halo = mvd_env_engine().halo;
   if (workspace_bytes == 0) workspace_bytes = (size_t)8 << 30;
   hipError_t e = hipMalloc((void**)&c->ws.base, workspace_bytes);
   if (e != hipSuccess) {
@@ -1091,7 +1091,7 @@ int mvd_op_conv(mvd_ctx* c, const float* x_nchw, int B, int Cin, int H, int W, c
     g.a = xh;
     g.a_f32 = 0;
     const int bnx = Cout % 160 == 0 ? 160 : (Cout % 128 == 0 ? 128 : 0);
-    if (taps == 9 && bnx && !getenv("MVD_NO_CONV3X")) {  // ... and the conv3x form of the weights (k_conv3x.hip), as build_conv3x_streams does
+    if (taps == 9 && bnx && mvd_env_call::conv3x()) {  // ... and the conv3x form of the weights (k_conv3x.hip), as build_conv3x_streams does
       cw.wx = ws_alloc<half_t>(c, conv3x_stream_halfs(Cout, cpad, bnx));
       WS_CHECK(cw.wx);
       RET_IF(conv3x_pack(wp, Cout, cpad, bnx, cw.wx, s));
@@ -1261,7 +1261,7 @@ int mvd_op_group_norm_bwd(mvd_ctx* c, const float* x, const float* dy, int B, in
   hipStream_t s = S(stream);
   WsScope ws_scope(c);
   // the slabbed form the training step uses; MVD_GN_BWD_ONE_BLOCK=1: the one-workgroup-per-(sample, group) kernel
-  static const bool one_block = getenv("MVD_GN_BWD_ONE_BLOCK") != nullptr;
+  const bool one_block = mvd_env().gn_bwd_one_block;
   const int S = one_block ? 1 : bwd_gn_slabs(B, groups, rows);
   float* dg = ws_alloc<float>(c, (size_t)B * S * C);
   float* db = ws_alloc<float>(c, (size_t)B * S * C);
@@ -1304,7 +1304,7 @@ int mvd_bench_conv(mvd_ctx* c, int B, int C, int H, int W, int Cout, int iters, 
   ConvW cw;
   cw.w = w; cw.N = Cout; cw.Cin = C; cw.taps = 9;
   const int bnx = Cout % 160 == 0 ? 160 : (Cout % 128 == 0 ? 128 : 0);
-  if (C % 64 == 0 && bnx && !getenv("MVD_NO_CONV3X")) {
+  if (C % 64 == 0 && bnx && mvd_env_call::conv3x()) {
     cw.wx = ws_alloc<half_t>(c, conv3x_stream_halfs(Cout, C, bnx));
     WS_CHECK(cw.wx);
     RET_IF(conv3x_pack(w, Cout, C, bnx, cw.wx, s));

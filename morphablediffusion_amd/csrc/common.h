@@ -4,6 +4,8 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 
+#include "env.h"
+
 // The 16-bit MFMA operand type of the whole library.  Default build: IEEE fp16 (11-bit significand: what the inference parity
 // bounds are stated for).  -DMVD_BF16 (make bf16 -> libmvd_hip_bf16.so, selected with MVD_DTYPE=bf16): bfloat16 operands and
 // storage, fp32 accumulation and master weights -- BASELINE configs[3]'s training dtype (fp32 range: no loss scaling needed;

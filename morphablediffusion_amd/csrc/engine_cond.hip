@@ -380,7 +380,7 @@ int mesh_commit(mvd_ctx* c, HostMesh& h, const float* vertices, const int32_t* o
 // allocation failure) leaves it exactly as it was.
 int engine_set_mesh(mvd_ctx* c, const float* vertices, const int32_t* coord, const int32_t* out_sh, const float* bounds, int Nv,
                     hipStream_t s) {
-  static const bool timing = getenv("MVD_MESH_TIMING") != nullptr;  // development aid: host phases of this call on stderr
+  const bool timing = mvd_env().mesh_timing;  // development aid: host phases of this call on stderr
   const auto t0 = std::chrono::steady_clock::now();
   static thread_local HostMesh h;
   RET_IF(host_mesh_build(coord, out_sh, Nv, h));
@@ -419,7 +419,7 @@ int engine_select_sample(mvd_ctx* c, int slot);
 int engine_set_samples(mvd_ctx* c, int B, const int* slots, const float* const* vertices, const int32_t* const* coord,
                        const int32_t* const* out_sh, const float* const* bounds, const int* Nv, const float* const* K,
                        const float* const* RT, int N, hipStream_t s) {
-  static const bool timing = getenv("MVD_MESH_TIMING") != nullptr;
+  const bool timing = mvd_env().mesh_timing;
   const auto t0 = std::chrono::steady_clock::now();
   static thread_local std::vector<HostMesh> hs;  // scratch kept between steps
   if ((int)hs.size() < B) hs.resize(B);
@@ -488,8 +488,7 @@ int engine_select_sample(mvd_ctx* c, int slot) {
 // rank's share of the view mean (morphable_diffusion.py:203-231).
 // the whole 2-D encoder as one launch (k_enc.hip) applies: 32 x 32 latents, the reference's 8 -> 16 -> ... -> 16 channel plan
 bool engine_encoder_is_fused(const mvd_ctx* c) {
-  static const bool no_fused_enc = getenv("MVD_NO_FUSED_ENC") != nullptr;
-  bool fused_enc = !no_fused_enc && c->has_cond && c->u.image_size == 32 && c->enc_init.Cin == 8 && c->enc_init.N == 16 &&
+  bool fused_enc = mvd_env().fused_enc && c->has_cond && c->u.image_size == 32 && c->enc_init.Cin == 8 && c->enc_init.N == 16 &&
                    c->enc_init.taps == 9 && !c->enc_init.xp && c->enc_final.N == 16 && c->enc_final.Cin == 16 && !c->enc_final.xp;
   for (int i = 0; i < 3 && fused_enc; ++i)
     fused_enc = c->enc_blocks[i].c1.Cin == 16 && c->enc_blocks[i].c1.N == 16 && !c->enc_blocks[i].c1.xp &&
@@ -695,8 +694,7 @@ static int frustum_net(mvd_ctx* c, int TN, FrustumOut* out, hipStream_t s, bool 
   float* up = ws_alloc<float>(c, vox(0) * fd[0]);
   WS_CHECK(gath && tmp && a && pre && up);
   RET_IF(gather(gath));
-  static const bool dbg_sum = getenv("MVD_DEBUG_SUM") != nullptr;
-  if (dbg_sum) {
+  if (mvd_env().debug_sum) {
     const int V = c->v.spatial_volume_size;
     c->dbg.push_back({"volume", c->volume, (size_t)V * V * V * 64 * 4});
     c->dbg.push_back({"gath", gath, vox(0) * 64 * 2});

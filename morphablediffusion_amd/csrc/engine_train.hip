@@ -1182,7 +1182,7 @@ int engine_train_conditioner_backward_batch(mvd_ctx* c, int B, const int* slots,
     if (!dsrc[l]) return mvd_fail("conditioner backward: dL/d(frustum volume) of every level is required");
   WsScope scope(c);
   // MVD_COND_BWD_TIMING=1: host-side enqueue time of each phase on stderr (development aid)
-  static const bool host_timing = getenv("MVD_COND_BWD_TIMING") != nullptr;
+  const bool host_timing = mvd_env().cond_bwd_timing;
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_last = now();
   auto mark = [&](const char* what) {

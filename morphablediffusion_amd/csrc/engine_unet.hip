@@ -53,187 +53,32 @@ void igemm_fill(IGemm& g, const GemmArgs& ga) {
   g.out_split = ga.out_split;
 }
 
-int igemm_go(mvd_ctx* c, IGemm& g, int force_splitk, hipStream_t s, const GemmArgs* defer = nullptr) {
-  const int M = g.B * g.Z * g.Y * g.X;
-  g.bn = igemm_pick_bn(g.N, g.geglu);
-  // (fp32 sources keep the 160-wide tile too: 32768 x 960 x 320 runs 48 us as 3 x 128 columns -- 768 workgroups, one and
-  //  a half rounds, A read three times -- and 37 us as 2 x 160; MVD_IGEMM_F32_BN128=1 restores the old choice)
-  static const bool f32_bn128 = getenv("MVD_IGEMM_F32_BN128") != nullptr;
-  if (g.a_f32 && g.bn == 160 && f32_bn128) g.bn = 128;
-  static const bool no_cx = getenv("MVD_NO_CONV3X") != nullptr;
-  if (!no_cx && c->use_halo && g.wx && conv3x_eligible(g, g.wx_bn)) {
-    // conv3x (k_conv3x.hip): one workgroup per CU and 16 x 16 pixel tile x wx_bn columns; split over 64-channel chunks when the
-    // tiles do not fill the chip (microseconds, as for the halo kernel below)
-    const int ncc = g.Cin / 64;
-    const int tiles = (g.X == 8 ? cdiv(g.B, 4) : g.B * (g.Y / 16) * (g.X / 16)) * (g.N / g.wx_bn);  // 8 x 8 images: four per tile
-    double best = 1e30;
-    int sk = 1;
-    for (int s2 = 1; s2 <= 8 && s2 <= ncc; ++s2) {
-      const int rounds = cdiv(tiles * s2, 256), steps = cdiv(ncc, s2) * 9;
-      double t = rounds * (steps * (g.wx_bn == 160 ? 0.75 : 0.62) + 8.0);
-      if (s2 > 1) t += 3.0 + (s2 + 1) * (double)M * g.N * 4.0 / 3.5e6;
-      if (t < best) {
-        best = t;
-        sk = s2;
-      }
+// Split of a one-workgroup-per-CU 3x3 kernel (conv3x, LDS-halo) over its 64-channel chunks: the split that minimises
+//   rounds * (steps * step_us + fill) + reduce pass   (microseconds, fitted to conv_bench3 sweeps); *us: that minimum
+int pick_chunk_split(int tiles, int ncc, double step_us, int M, int N, double* us) {
+  int sk = 1;
+  *us = 1e30;
+  for (int s2 = 1; s2 <= 8 && s2 <= ncc; ++s2) {
+    const int rounds = cdiv(tiles * s2, 256), steps = cdiv(ncc, s2) * 9;
+    double t = rounds * (steps * step_us + 8.0);
+    if (s2 > 1) t += 3.0 + (s2 + 1) * (double)M * N * 4.0 / 3.5e6;
+    if (t < *us) {
+      *us = t;
+      sk = s2;
     }
-    if (force_splitk > 0) sk = force_splitk < ncc ? force_splitk : ncc;
-    if (sk > 1) sk = cdiv(ncc, cdiv(ncc, sk));
-    WsScope ws_scope(c, WS_TEMP);
-    g.splitk = sk;
-    g.partial = nullptr;
-    g.bn = g.wx_bn;
-    bool deferred = false;
-    if (sk > 1) {
-      static const int defer_max = getenv("MVD_DEFER_MAX") ? atoi(getenv("MVD_DEFER_MAX")) : 16;
-      if (defer && defer->slabs && defer->sk_used && sk <= defer_max && (size_t)sk * M * g.N <= defer->slabs_cap &&
-          (!g.resid || (defer->defer_epilogue && g.resid_f32))) {
-        g.partial = defer->slabs;
-        deferred = true;
-      } else {
-        g.partial = ws_alloc<float>(c, (size_t)sk * M * g.N);
-        if (!g.partial) g.splitk = 1;
-      }
-    }
-    if (defer && defer->sk_used) *defer->sk_used = deferred ? sk : 1;
-    const double kalg = (double)(g.cin_alg ? g.cin_alg : g.Cin);
-    const double flops = 2.0 * M * g.N * kalg * 9.0;
-    double bytes = (double)M * kalg * 2 + 9.0 * g.N * kalg * 2 + (g.splitk > 1 ? 0.0 : (double)M * g.N * 4);
-    if (g.resid && g.splitk <= 1) bytes += (double)M * g.N * 4;
-    int r;
-    {
-      ProbeScope ps(c, s, g.wx_bn == 160 ? "conv3x_kernel<5>" : "conv3x_kernel<4>", flops, bytes);
-      r = launch_conv3x(g, g.wx, g.wx_bn, s);
-    }
-    if (!r && g.splitk > 1 && !deferred) {
-      ProbeScope ps(c, s, "splitk_reduce_kernel", 0.0, (double)M * g.N * 4.0 * (g.splitk + 1));
-      r = launch_splitk_reduce(g, s);
-    }
-    return r;
   }
-  const bool halo = c->use_halo && conv3_halo_eligible(g);
-  static const bool use_dense = getenv("MVD_NO_GEMM_DMA") == nullptr;
-  static const int dense_min_m = getenv("MVD_DENSE_MIN_M") ? atoi(getenv("MVD_DENSE_MIN_M")) : 64;
-  // one 256-row workgroup per CU: wins for the Linear layers and wherever weights stream (small M, long K), down to one
-  // quarter-filled row tile (2-views-per-rank step: 7.08 ms with a 512-row threshold, 6.97 ms with 64);
-  // the big shallow 3-D convs keep the 128-row gather kernel (finer tiles, 2 workgroups per CU)
-  if (g.npar > 0) {  // parity-batched launch (run_convT3d / run_upconv2d): LDS-DMA kernel, no split-K
-    if (!gemm_dma_eligible(g)) return mvd_fail("igemm_go: parity batch needs the LDS-DMA kernel");
-    int kmax = 0;
-    for (int p = 0; p < g.npar; ++p) kmax = g.par_ntaps[p] > kmax ? g.par_ntaps[p] : kmax;
-    int nch = 1, sk2 = 1;
-    gemm_dma_plan(M * g.npar, g.N, kmax * cdiv(g.Cin, 64), g.bn, 1, &nch, &sk2);
-    g.nch = nch;
-    g.splitk = 1;
-    g.partial = nullptr;
-    // Parity walk (k_gemm.hip PWALK): every workgroup walks the parity classes of its tile instead of one workgroup per class --
-    // meant for the frustum network's level-0 ConvTranspose3d (384 tiles x 8 classes of 2 ... 16 k-steps each: 282 us at 154
-    // TFLOP/s).  MEASURED (profiles/r06_y_ab_pwalk.txt, threshold 192 tiles): 12.828 vs 12.811 ms per step, 6.169 vs 6.169 at 2
-    // views per rank -- nothing: the launch sits on the side stream beside the trunk.  Tested form, off unless
-    // MVD_PAR_WALK_MIN=<tiles> is set.
-    static const int pwalk_min = getenv("MVD_PAR_WALK_MIN") ? atoi(getenv("MVD_PAR_WALK_MIN")) : 0;
-    if (pwalk_min > 0 && cdiv(M, 256) * cdiv(g.N, g.bn) >= pwalk_min) {
-      g.par_walk = 1;
-      g.nch = 1;
-    }
-    double fl = 0.0;
-    for (int p = 0; p < g.npar; ++p) fl += 2.0 * M * g.N * (double)(g.cin_alg ? g.cin_alg : g.Cin) * g.par_ntaps[p];
-    const double by = (double)g.B * g.PZ * g.PY * g.PX * g.Cin * 2 + (double)g.npar * kmax * g.N * g.Cin * 2 +
-                      (double)M * g.npar * g.N * (g.out_f32 ? 4 : 2) + (g.resid ? (double)M * g.npar * g.N * (g.resid_f32 ? 4 : 2) : 0.0);
-    char fam[64];
-    snprintf(fam, sizeof fam, "gemm_dma_kernel<%d,0>", g.bn);
-    ProbeScope ps(c, s, fam, fl, by);
-    return launch_gemm_dma(g, s);
-  }
-  const bool dense = use_dense && !halo && M >= dense_min_m && (g.ntaps == 1 || M <= 16384) && gemm_dma_eligible(g);
-  if (g.gn_partial && !dense) return mvd_fail("igemm_go: the statistics-only pass needs the LDS-DMA kernel");
-  int sk;
-  if (halo) {
-    // LDS-halo 3x3 kernel, one workgroup per CU: pick the column width and the split over 64-channel chunks that
-    // minimise  rounds * (steps * step_cost + fill) + reduce pass  (microseconds, fitted to conv_bench3 sweeps)
-    const int ncc = g.Cin / 64;
-    double best = 1e30;
-    int best_bn = 128, best_sk = 1;
-    for (int bn = 128; bn <= 160; bn += 32) {
-      const int tiles = conv3_halo_tiles(g, bn);
-      for (int s2 = 1; s2 <= 8 && s2 <= ncc; ++s2) {
-        const int rounds = cdiv(tiles * s2, 256), steps = cdiv(ncc, s2) * 9;
-        double t = rounds * (steps * (bn == 160 ? 1.3 : 1.0) + 8.0);
-        if (s2 > 1) t += 3.0 + (s2 + 1) * (double)M * g.N * 4.0 / 3.5e6;
-        if (t < best) {
-          best = t;
-          best_bn = bn;
-          best_sk = s2;
-        }
-      }
-    }
-    g.bn = best_bn;
-    sk = force_splitk > 0 ? (force_splitk < ncc ? force_splitk : ncc) : best_sk;
-    static const int tune_bn = getenv("MVD_HALO_BN") ? atoi(getenv("MVD_HALO_BN")) : 0;  // tools/conv_bench3.py sweeps
-    static const int tune_sk = getenv("MVD_HALO_SK") ? atoi(getenv("MVD_HALO_SK")) : 0;
-    if (tune_bn) g.bn = tune_bn;
-    if (tune_sk) sk = tune_sk;
-    if (sk > ncc) sk = ncc;
-    if (sk > 1) sk = cdiv(ncc, cdiv(ncc, sk));  // no empty split (the kernels cut the chunk range in ceil(ncc/sk) pieces)
-  } else if (dense) {
-    int nch = 1, sk2 = 1;
-    const int ksteps = g.ntaps * cdiv(g.Cin, 64);
-    static const bool old_plan = getenv("MVD_OLD_PLAN") != nullptr;
-    const bool plain_gemm = !g.gn_partial && !g.rowscale && g.ntaps == 1;
-    if (plain_gemm && !old_plan) {
-      int bn = 0, bm = 256;
-      // (128-row tiles exist for the PLAIN instantiation only: one centre tap, linear rows)
-      gemm_dma_plan_us(M, g.N, ksteps, g.geglu, g.out_f32 ? 4 : (g.out_split ? 6 : 2), g.resid ? (g.resid_f32 ? 4 : 2) : 0, &bn,
-                       &nch, &sk2, gemm_dma_is_plain(g) ? &bm : nullptr);
-      g.bn = bn;
-      g.bm = bm;
-    } else {
-      gemm_dma_plan(M, g.N, ksteps, g.bn, g.geglu, &nch, &sk2);
-    }
-    if (g.gn_partial || g.rowscale) {  // folded-GroupNorm passes walk the whole tile grid: one round of workgroups
-      if (g.bn == 160) g.bn = 128;
-      const int tiles = cdiv(M, 256) * cdiv(g.N, g.bn);
-      nch = cdiv(tiles, 256);
-      if (nch > 64) nch = 64;
-      force_splitk = 1;
-    }
-    sk = g.geglu ? 1 : (force_splitk > 0 ? force_splitk : sk2);
-    {  // sweeps (tools/gemm_plan_sweep.py): column-tile width and split of the next dense launches
-      static const int tune_bn = getenv("MVD_DENSE_BN") ? atoi(getenv("MVD_DENSE_BN")) : 0;
-      static const int tune_sk = getenv("MVD_DENSE_SK") ? atoi(getenv("MVD_DENSE_SK")) : 0;
-      static const int tune_bm = getenv("MVD_DENSE_BM") ? atoi(getenv("MVD_DENSE_BM")) : 0;
-      if (tune_bn && !g.geglu && !g.gn_partial && !g.rowscale) {
-        g.bn = tune_bn;
-        g.bm = (tune_bm == 128 && gemm_dma_is_plain(g)) ? 128 : 256;
-        gemm_dma_plan(M, g.N, ksteps, g.bn, g.geglu, &nch, &sk2);
-        if (g.bm == 128) {  // no column walk with the swept 128-row tiles: one tile per workgroup
-          nch = 1;
-          sk2 = 1;
-        }
-        if (force_splitk <= 0) sk = sk2;
-      }
-      if (tune_sk && !g.geglu && force_splitk <= 0) sk = tune_sk;
-    }
-    if (sk > ksteps) sk = ksteps;
-    if (sk > 1) sk = cdiv(ksteps, cdiv(ksteps, sk));  // no empty split
-    g.nch = sk > 1 ? 1 : nch;
-    static const bool plan_debug = getenv("MVD_PLAN_DEBUG") != nullptr;
-    if (plan_debug) fprintf(stderr, "[plan] M=%d N=%d ksteps=%d -> bm=%d bn=%d nch=%d sk=%d\n", M, g.N, ksteps, g.bm ? g.bm : 256, g.bn, g.nch, sk);
-  } else {
-    const int ksteps = g.ntaps * cdiv(g.Cin, 64);
-    sk = force_splitk > 0 ? force_splitk : igemm_pick_splitk(M, g.N, ksteps, g.bn);
-    if (sk > ksteps) sk = ksteps;
-    if (sk > 1) sk = cdiv(ksteps, cdiv(ksteps, sk));  // no empty split
-  }
-  WsScope ws_scope(c, WS_TEMP);
+  return sk;
+}
+
+// Where a launch split sk ways writes its partial sums: into the slab buffer the caller offers (GemmArgs::slabs) when that takes
+// them and `form_ok` -- DEFERRED: the caller's consumer adds the slabs, no reduce pass -- else into scratch.  Returns: deferred?
+bool place_partials(mvd_ctx* c, IGemm& g, int M, int sk, const GemmArgs* defer, bool form_ok) {
   g.splitk = sk;
   g.partial = nullptr;
-  bool deferred = false;  // the caller's consumer adds the slabs (GemmArgs::slabs): no reduce pass
+  bool deferred = false;
   if (sk > 1) {
-    static const int defer_max = getenv("MVD_DEFER_MAX") ? atoi(getenv("MVD_DEFER_MAX")) : 16;  // A/B: 4 = the round-3 limit
-    if (defer && defer->slabs && defer->sk_used && sk <= defer_max && (size_t)sk * M * g.N <= defer->slabs_cap && !g.geglu &&
-        (!g.resid || (defer->defer_epilogue && g.resid_f32)) && g.act == 0 && g.alpha == 1.0f && g.out_linear && g.out_f32 &&
-        !g.out_split) {
+    if (defer && defer->slabs && defer->sk_used && sk <= mvd_env().defer_max && (size_t)sk * M * g.N <= defer->slabs_cap &&
+        (!g.resid || (defer->defer_epilogue && g.resid_f32)) && form_ok) {
       g.partial = defer->slabs;
       deferred = true;
     } else {
@@ -242,7 +87,151 @@ int igemm_go(mvd_ctx* c, IGemm& g, int force_splitk, hipStream_t s, const GemmAr
     }
   }
   if (defer && defer->sk_used) *defer->sk_used = deferred ? sk : 1;
-  static const bool timing = getenv("MVD_LAYER_TIMING") != nullptr;  // debugging aid: per-GEMM time on stderr
+  return deferred;
+}
+
+// the slabs are written once and read once: 2 x splitk x M x N x 4 bytes that no roofline needs
+int reduce_partials(mvd_ctx* c, IGemm& g, int M, hipStream_t s) {
+  ProbeScope ps(c, s, "splitk_reduce_kernel", 0.0, (double)M * g.N * 4.0 * (g.splitk + 1));
+  return launch_splitk_reduce(g, s);
+}
+
+// conv3x (k_conv3x.hip): one workgroup per CU and 16 x 16 pixel tile x wx_bn columns; split over 64-channel chunks
+int go_conv3x(mvd_ctx* c, IGemm& g, int M, int force_splitk, hipStream_t s, const GemmArgs* defer) {
+  const int ncc = g.Cin / 64;
+  const int tiles = (g.X == 8 ? cdiv(g.B, 4) : g.B * (g.Y / 16) * (g.X / 16)) * (g.N / g.wx_bn);  // 8 x 8 images: four per tile
+  double us;
+  int sk = pick_chunk_split(tiles, ncc, g.wx_bn == 160 ? 0.75 : 0.62, M, g.N, &us);
+  if (force_splitk > 0) sk = force_splitk < ncc ? force_splitk : ncc;
+  if (sk > 1) sk = cdiv(ncc, cdiv(ncc, sk));
+  g.bn = g.wx_bn;
+  WsScope ws_scope(c, WS_TEMP);
+  const bool deferred = place_partials(c, g, M, sk, defer, true);
+  const double kalg = (double)(g.cin_alg ? g.cin_alg : g.Cin);
+  const double flops = 2.0 * M * g.N * kalg * 9.0;
+  double bytes = (double)M * kalg * 2 + 9.0 * g.N * kalg * 2 + (g.splitk > 1 ? 0.0 : (double)M * g.N * 4);
+  if (g.resid && g.splitk <= 1) bytes += (double)M * g.N * 4;
+  int r;
+  {
+    ProbeScope ps(c, s, g.wx_bn == 160 ? "conv3x_kernel<5>" : "conv3x_kernel<4>", flops, bytes);
+    r = launch_conv3x(g, g.wx, g.wx_bn, s);
+  }
+  if (!r && g.splitk > 1 && !deferred) r = reduce_partials(c, g, M, s);
+  return r;
+}
+
+// parity-batched launch (run_convT3d / run_upconv2d): LDS-DMA kernel, no split-K
+int go_parity_batch(mvd_ctx* c, IGemm& g, int M, hipStream_t s) {
+  if (!gemm_dma_eligible(g)) return mvd_fail("igemm_go: parity batch needs the LDS-DMA kernel");
+  int kmax = 0;
+  for (int p = 0; p < g.npar; ++p) kmax = g.par_ntaps[p] > kmax ? g.par_ntaps[p] : kmax;
+  int nch = 1, sk2 = 1;
+  gemm_dma_plan(M * g.npar, g.N, kmax * cdiv(g.Cin, 64), g.bn, 1, &nch, &sk2);
+  g.nch = nch;
+  g.splitk = 1;
+  g.partial = nullptr;
+  // Parity walk (k_gemm.hip PWALK): every workgroup walks the parity classes of its tile instead of one workgroup per class --
+  // meant for the frustum network's level-0 ConvTranspose3d (384 tiles x 8 classes of 2 ... 16 k-steps each: 282 us at 154
+  // TFLOP/s).  MEASURED at a threshold of 192 tiles: 12.828 vs 12.811 ms per step -- nothing: the launch sits on the side stream.
+  const int pwalk_min = mvd_env().par_walk_min;
+  if (pwalk_min > 0 && cdiv(M, 256) * cdiv(g.N, g.bn) >= pwalk_min) {
+    g.par_walk = 1;
+    g.nch = 1;
+  }
+  double fl = 0.0;
+  for (int p = 0; p < g.npar; ++p) fl += 2.0 * M * g.N * (double)(g.cin_alg ? g.cin_alg : g.Cin) * g.par_ntaps[p];
+  const double by = (double)g.B * g.PZ * g.PY * g.PX * g.Cin * 2 + (double)g.npar * kmax * g.N * g.Cin * 2 +
+                    (double)M * g.npar * g.N * (g.out_f32 ? 4 : 2) + (g.resid ? (double)M * g.npar * g.N * (g.resid_f32 ? 4 : 2) : 0.0);
+  char fam[64];
+  snprintf(fam, sizeof fam, "gemm_dma_kernel<%d,0>", g.bn);
+  ProbeScope ps(c, s, fam, fl, by);
+  return launch_gemm_dma(g, s);
+}
+
+// The three plans set g.bn (g.bm, g.nch) and return the split.  LDS-halo 3x3 kernel: the column width and split of the least time
+int plan_halo(IGemm& g, int M, int force_splitk) {
+  const MvdEnv& env = mvd_env();
+  const int ncc = g.Cin / 64;
+  double best = 1e30;
+  int best_bn = 128, best_sk = 1;
+  for (int bn = 128; bn <= 160; bn += 32) {
+    double us;
+    const int s2 = pick_chunk_split(conv3_halo_tiles(g, bn), ncc, bn == 160 ? 1.3 : 1.0, M, g.N, &us);
+    if (us < best) {
+      best = us;
+      best_bn = bn;
+      best_sk = s2;
+    }
+  }
+  g.bn = best_bn;
+  int sk = force_splitk > 0 ? (force_splitk < ncc ? force_splitk : ncc) : best_sk;
+  if (env.halo_bn) g.bn = env.halo_bn;  // tools/conv_bench3.py sweeps
+  if (env.halo_sk) sk = env.halo_sk;
+  if (sk > ncc) sk = ncc;
+  if (sk > 1) sk = cdiv(ncc, cdiv(ncc, sk));  // no empty split (the kernels cut the chunk range in ceil(ncc/sk) pieces)
+  return sk;
+}
+
+// LDS-DMA kernel, one 256-row workgroup per CU
+int plan_dense(IGemm& g, int M, int force_splitk) {
+  const MvdEnv& env = mvd_env();
+  int nch = 1, sk2 = 1;
+  const int ksteps = g.ntaps * cdiv(g.Cin, 64);
+  const bool plain_gemm = !g.gn_partial && !g.rowscale && g.ntaps == 1;
+  if (plain_gemm && !env.old_plan) {
+    int bn = 0, bm = 256;
+    // (128-row tiles exist for the PLAIN instantiation only: one centre tap, linear rows)
+    gemm_dma_plan_us(M, g.N, ksteps, g.geglu, g.out_f32 ? 4 : (g.out_split ? 6 : 2), g.resid ? (g.resid_f32 ? 4 : 2) : 0, &bn,
+                     &nch, &sk2, gemm_dma_is_plain(g) ? &bm : nullptr);
+    g.bn = bn;
+    g.bm = bm;
+  } else {
+    gemm_dma_plan(M, g.N, ksteps, g.bn, g.geglu, &nch, &sk2);
+  }
+  if (g.gn_partial || g.rowscale) {  // folded-GroupNorm passes walk the whole tile grid: one round of workgroups
+    if (g.bn == 160) g.bn = 128;
+    const int tiles = cdiv(M, 256) * cdiv(g.N, g.bn);
+    nch = cdiv(tiles, 256);
+    if (nch > 64) nch = 64;
+    force_splitk = 1;
+  }
+  int sk = g.geglu ? 1 : (force_splitk > 0 ? force_splitk : sk2);
+  // sweeps (tools/gemm_plan_sweep.py): column-tile width and split of the next dense launches
+  if (env.dense_bn && !g.geglu && !g.gn_partial && !g.rowscale) {
+    g.bn = env.dense_bn;
+    g.bm = (env.dense_bm == 128 && gemm_dma_is_plain(g)) ? 128 : 256;
+    gemm_dma_plan(M, g.N, ksteps, g.bn, g.geglu, &nch, &sk2);
+    if (g.bm == 128) {  // no column walk with the swept 128-row tiles: one tile per workgroup
+      nch = 1;
+      sk2 = 1;
+    }
+    if (force_splitk <= 0) sk = sk2;
+  }
+  if (env.dense_sk && !g.geglu && force_splitk <= 0) sk = env.dense_sk;
+  if (sk > ksteps) sk = ksteps;
+  if (sk > 1) sk = cdiv(ksteps, cdiv(ksteps, sk));  // no empty split
+  g.nch = sk > 1 ? 1 : nch;
+  if (env.plan_debug) fprintf(stderr, "[plan] M=%d N=%d ksteps=%d -> bm=%d bn=%d nch=%d sk=%d\n", M, g.N, ksteps, g.bm ? g.bm : 256, g.bn, g.nch, sk);
+  return sk;
+}
+
+// register-staged gather kernel (k_igemm.hip), 128-row tiles
+int plan_gather(IGemm& g, int M, int force_splitk) {
+  const int ksteps = g.ntaps * cdiv(g.Cin, 64);
+  int sk = force_splitk > 0 ? force_splitk : igemm_pick_splitk(M, g.N, ksteps, g.bn);
+  if (sk > ksteps) sk = ksteps;
+  if (sk > 1) sk = cdiv(ksteps, cdiv(ksteps, sk));  // no empty split
+  return sk;
+}
+
+enum IGemmKernel { K_GATHER = 0, K_HALO = 1, K_DENSE = 2 };
+
+// the common tail: place the partial sums of a planned launch, launch it, reduce them, time it
+int launch_planned(mvd_ctx* c, IGemm& g, int M, int sk, IGemmKernel kernel, hipStream_t s, const GemmArgs* defer) {
+  WsScope ws_scope(c, WS_TEMP);
+  const bool deferred =
+      place_partials(c, g, M, sk, defer, !g.geglu && g.act == 0 && g.alpha == 1.0f && g.out_linear && g.out_f32 && !g.out_split);
+  const bool timing = mvd_env().layer_timing;  // debugging aid: per-GEMM time on stderr
   static hipEvent_t ev0 = nullptr, ev1 = nullptr;
   if (timing) {
     if (!ev0) {
@@ -252,8 +241,7 @@ int igemm_go(mvd_ctx* c, IGemm& g, int force_splitk, hipStream_t s, const GemmAr
     hipEventRecord(ev0, s);
   }
   int r;
-  // algorithmic work of this launch: every operand and the result once (gathered taps re-read the same input pixels)
-  // algorithmic FLOPs: the layer's own K (an extended-precision layer executes 3x that), every tap once
+  // algorithmic work: every operand and the result once; the layer's own K (extended precision executes 3x that), every tap once
   const double flops = 2.0 * M * g.N * (double)(g.cin_alg ? g.cin_alg : g.Cin) * g.ntaps;
   const double in_rows = (double)g.B * g.PZ * g.PY * g.PX;
   const double out_cols = g.geglu ? g.N / 2 : g.N;
@@ -262,13 +250,11 @@ int igemm_go(mvd_ctx* c, IGemm& g, int force_splitk, hipStream_t s, const GemmAr
                  (g.gn_partial ? 0.0 : (double)M * out_cols * (g.out_f32 ? 4 : 2));
   if (g.resid) bytes += (double)M * g.N * (g.resid_f32 ? 4 : 2);
   char fam[64];
-  if (halo) {
+  if (kernel == K_HALO) {
     snprintf(fam, sizeof fam, "conv3_dma_kernel<%d,%d,%d>", g.bn == 160 ? 160 : 128, g.X % 16 == 0 ? 16 : 8, g.X % 16 == 0 ? 16 : 8);
-    {
-      ProbeScope ps(c, s, fam, flops, g.splitk > 1 ? bytes - (double)M * out_cols * (g.out_f32 ? 4 : 2) : bytes);
-      r = launch_conv3_halo(g, s);
-    }
-  } else if (dense) {
+    ProbeScope ps(c, s, fam, flops, g.splitk > 1 ? bytes - (double)M * out_cols * (g.out_f32 ? 4 : 2) : bytes);
+    r = launch_conv3_halo(g, s);
+  } else if (kernel == K_DENSE) {
     if (g.bm == 128) snprintf(fam, sizeof fam, "gemm_dma_kernel<128x%d>", g.bn);  // four-wave row tiles (round 6)
     else snprintf(fam, sizeof fam, "gemm_dma_kernel<%d,%d>", g.bn, g.gn_partial ? 1 : (g.rowscale ? 2 : 0));
     ProbeScope ps(c, s, fam, flops, bytes);
@@ -279,10 +265,7 @@ int igemm_go(mvd_ctx* c, IGemm& g, int force_splitk, hipStream_t s, const GemmAr
     ProbeScope ps(c, s, fam, flops, bytes);
     r = launch_igemm(g, s);
   }
-  if (!r && g.splitk > 1 && !deferred) {  // the slabs are written once and read once: 2 x splitk x M x N x 4 bytes that no roofline needs
-    ProbeScope ps(c, s, "splitk_reduce_kernel", 0.0, (double)M * g.N * 4.0 * (g.splitk + 1));
-    r = launch_splitk_reduce(g, s);
-  }
+  if (!r && g.splitk > 1 && !deferred) r = reduce_partials(c, g, M, s);
   if (timing) {
     hipEventRecord(ev1, s);
     hipEventSynchronize(ev1);
@@ -290,9 +273,30 @@ int igemm_go(mvd_ctx* c, IGemm& g, int force_splitk, hipStream_t s, const GemmAr
     hipEventElapsedTime(&ms, ev0, ev1);
     const double fl = 2.0 * M * g.N * g.Cin * g.ntaps;
     fprintf(stderr, "[gemm] M=%d N=%d Cin=%d taps=%d f32=%d halo=%d bn=%d sk=%d geglu=%d  %.1f us  %.0f TF\n", M, g.N, g.Cin,
-            g.ntaps, g.a_f32, halo ? 1 : (dense ? 2 : 0), g.bn, g.splitk, g.geglu, ms * 1e3, fl / (ms * 1e-3) * 1e-12);
+            g.ntaps, g.a_f32, (int)kernel, g.bn, g.splitk, g.geglu, ms * 1e3, fl / (ms * 1e-3) * 1e-12);
   }
   return r;
+}
+
+// plans and launches one convolution or GEMM of the step
+int igemm_go(mvd_ctx* c, IGemm& g, int force_splitk, hipStream_t s, const GemmArgs* defer = nullptr) {
+  const MvdEnv& env = mvd_env();
+  const int M = g.B * g.Z * g.Y * g.X;
+  g.bn = igemm_pick_bn(g.N, g.geglu);
+  // (fp32 sources keep the 160-wide tile too: 32768 x 960 x 320 runs 48 us as 3 x 128 columns -- 768 workgroups, one and
+  //  a half rounds, A read three times -- and 37 us as 2 x 160; MVD_IGEMM_F32_BN128=1 restores the old choice)
+  if (g.a_f32 && g.bn == 160 && env.igemm_f32_bn128) g.bn = 128;
+  if (env.conv3x && c->use_halo && g.wx && conv3x_eligible(g, g.wx_bn)) return go_conv3x(c, g, M, force_splitk, s, defer);
+  if (g.npar > 0) return go_parity_batch(c, g, M, s);
+  const bool halo = c->use_halo && conv3_halo_eligible(g);
+  // one 256-row workgroup per CU: wins for the Linear layers and wherever weights stream (small M, long K), down to one
+  // quarter-filled row tile (2-views-per-rank step: 7.08 ms with a 512-row threshold, 6.97 ms with 64);
+  // the big shallow 3-D convs keep the 128-row gather kernel (finer tiles, 2 workgroups per CU)
+  const bool dense = env.gemm_dma && !halo && M >= env.dense_min_m && (g.ntaps == 1 || M <= 16384) && gemm_dma_eligible(g);
+  if (g.gn_partial && !dense) return mvd_fail("igemm_go: the statistics-only pass needs the LDS-DMA kernel");
+  if (halo) return launch_planned(c, g, M, plan_halo(g, M, force_splitk), K_HALO, s, defer);
+  if (dense) return launch_planned(c, g, M, plan_dense(g, M, force_splitk), K_DENSE, s, defer);
+  return launch_planned(c, g, M, plan_gather(g, M, force_splitk), K_GATHER, s, defer);
 }
 
 }  // namespace
@@ -349,7 +353,6 @@ int run_upconv2d(mvd_ctx* c, const GemmArgs& ga_in, int B, int H, int W, hipStre
     ga.a_f32 = 0;
     ga.lda = cw.Cin;
   }
-  static const bool no_batch = getenv("MVD_NO_PARITY_BATCH") != nullptr;
   IGemm gb;
   igemm_init(gb);
   igemm_fill(gb, ga);
@@ -362,7 +365,7 @@ int run_upconv2d(mvd_ctx* c, const GemmArgs& ga_in, int B, int H, int W, hipStre
   gb.OX = 2 * W;
   gb.ozm = 1;
   gb.oym = gb.oxm = 2;
-  const bool batched = !no_batch && ga.force_splitk <= 1 && gemm_dma_eligible(gb);
+  const bool batched = mvd_env().parity_batch && ga.force_splitk <= 1 && gemm_dma_eligible(gb);
   for (int par = 0; par < 4; ++par) {
     const int py = par >> 1, px = par & 1;
     int taps[4];
@@ -420,7 +423,6 @@ int run_conv3d(mvd_ctx* c, const GemmArgs& ga, int B, int D, int H, int W, int s
 // p = 0 -> k = 1, i = q ;  p = 1 -> (k = 0, i = q + 1), (k = 2, i = q)   where o = 2 q + p.
 int run_convT3d(mvd_ctx* c, const GemmArgs& ga, int B, int D, int H, int W, hipStream_t s) {
   if (ga.w->taps != 27) return mvd_fail("run_convT3d: expects a 3x3x3 kernel");
-  static const bool no_batch = getenv("MVD_NO_PARITY_BATCH") != nullptr;
   IGemm gb;  // all 8 parity classes in one launch when the LDS-DMA kernel applies
   igemm_init(gb);
   igemm_fill(gb, ga);
@@ -433,7 +435,7 @@ int run_convT3d(mvd_ctx* c, const GemmArgs& ga, int B, int D, int H, int W, hipS
   gb.OY = 2 * H;
   gb.OX = 2 * W;
   gb.ozm = gb.oym = gb.oxm = 2;
-  const bool batched = !no_batch && !ga.a_f32 && ga.force_splitk <= 1 && B * D * H * W >= 512 && gemm_dma_eligible(gb);
+  const bool batched = mvd_env().parity_batch && !ga.a_f32 && ga.force_splitk <= 1 && B * D * H * W >= 512 && gemm_dma_eligible(gb);
   for (int par = 0; par < 8; ++par) {
     const int pz = par >> 2, py = (par >> 1) & 1, px = par & 1;
     const int kz[2] = {pz ? 0 : 1, 2}, dzv[2] = {pz ? 1 : 0, 0}, nz = pz ? 2 : 1;
@@ -473,8 +475,7 @@ int run_group_norm(mvd_ctx* c, const float* x, int ld, int B, int rows_per_sampl
                    size_t slab_stride, const float* bias2, const float* resid, int ldr, float* mat, int ldm) {
   // algorithmic: x read once (fp32), fp16 result written once
   ProbeScope ps(c, s, "group_norm", 0.0, (double)B * rows_per_sample * n.C * 6.0);
-  static const bool two_pass = getenv("MVD_GN_TWO_PASS") != nullptr;
-  if (!two_pass && gn_group_eligible(ld, rows_per_sample, n.C, groups, preadd ? (preadd_ld ? preadd_ld : n.C) : 0, ldo))
+  if (!mvd_env().gn_two_pass && gn_group_eligible(ld, rows_per_sample, n.C, groups, preadd ? (preadd_ld ? preadd_ld : n.C) : 0, ldo))
     return launch_gn_group(x, ld, B, rows_per_sample, n.C, groups, preadd, preadd_ld ? preadd_ld : n.C, n.g, n.b, eps, act, out,
                            ldo, s, split, nslab, slab_stride, bias2, resid, ldr, mat, ldm);
   if (nslab > 1 || resid || mat) return mvd_fail("run_group_norm: slab input needs the single-pass form");
@@ -504,13 +505,11 @@ int unet_do_res(Fwd& f, const ResW& r, View in, View out, int H, int W, ResSaved
   half_t* a2 = ws_alloc<half_t>(c, (size_t)rows * r.cout * w2);
   WS_CHECK(a1 && h1 && a2);
   // The 1x1 skip convolution (openaimodel.py:273: skip_connection(x)) reads the block input only: on a helper stream it can run
-  // beside GroupNorm1 -> conv1 -> GroupNorm2 instead of in front of conv2.  MEASURED (profiles/r06_z_ab_skip_side.txt): 12.24 vs
-  // 12.245 ms per step, 6.11 vs 6.01 ms at 2 views per rank -- the chip gives two dependent-free kernels of one process no more
-  // than their sum (the same answer as the two half-batch chains).  Tested form, on with MVD_SKIP_SIDE=1 only.
+  // beside GroupNorm1 -> conv1 -> GroupNorm2 instead of in front of conv2.  MEASURED: 12.24 vs 12.245 ms per step -- the chip gives
+  // two dependent-free kernels of one process no more than their sum.  Tested form, on with MVD_SKIP_SIDE=1 only.
   // Its result buffer is allocated here (block scope, or the carry's storage); it takes no split-K scratch on the helper stream
   // (the workspace scopes are released in host order).
-  static const bool no_skip_side = getenv("MVD_SKIP_SIDE") == nullptr;
-  const bool skip_side = r.has_skip && !no_skip_side && !f.train && !sv;
+  const bool skip_side = r.has_skip && mvd_env().skip_side && !f.train && !sv;
   const bool sk_in_carry = r.has_skip && out_carry && out_carry->aux && out_carry->aux_cap >= (size_t)rows * r.cout;
   float* skbuf = nullptr;
   auto launch_skip = [&](hipStream_t ss, bool no_split) -> int {
@@ -554,10 +553,9 @@ int unet_do_res(Fwd& f, const ResW& r, View in, View out, int H, int W, ResSaved
   g1.rowbias = f.emb_all + r.emb_off; g1.rb_ld = c->emb_total;
   // conv1's result only feeds GroupNorm 2: when the conv splits K, the norm adds the slabs (+ bias + emb) itself and the
   // reduce pass (a launch, a write and a read of h1) disappears
-  static const bool no_defer = getenv("MVD_NO_DEFER_REDUCE") != nullptr || getenv("MVD_GN_TWO_PASS") != nullptr;
   int sk1 = 1;
   const size_t slab_elems = (size_t)rows * r.cout;
-  if (!no_defer && !f.train && gn_group_eligible(r.cout, H * W, r.cout, 32, c->emb_total, r.cout * w2)) {
+  if (mvd_env().defer_reduce && !f.train && gn_group_eligible(r.cout, H * W, r.cout, 32, c->emb_total, r.cout * w2)) {
     const size_t nsl = rows > 8192 ? 4 : 16;  // the 4 x 4 level's convolutions split K twelve ways; full resolution never splits
     g1.slabs = ws_alloc<float>(c, nsl * slab_elems);
     g1.slabs_cap = g1.slabs ? nsl * slab_elems : 0;
@@ -613,12 +611,10 @@ int unet_do_st(Fwd& f, const STW& t, View in, View out, int H, int W, STSaved* s
   // FF1, GEGLU, FF2, the residual, proj_out + the block input -- is ONE launch with the rows resident in registers; the
   // intermediates t2 / l3 / gg (and t3, unless an extended-precision proj_out wants its [hi | lo | hi] operand) do not exist.
   // Below ~128 workgroups of 128 rows the layered GEMMs fill the chip better than one wave per 32 rows does.
-  static const bool no_rc = getenv("MVD_NO_ROWCHAIN") != nullptr;
-  static const int rc_min_rows = getenv("MVD_ROWCHAIN_MIN_ROWS") ? atoi(getenv("MVD_ROWCHAIN_MIN_ROWS")) : 16384;
-  const bool rc = !no_rc && !f.train && !sv && t.rc_stream && rows >= rc_min_rows && rowchain_takes(C, rows, T) && !(in.ld & 3) && !(out.ld & 3);
-  static const bool no_xpf = getenv("MVD_NO_XP_FUSE") != nullptr;  // A/B: extended-precision proj_in / proj_out as separate GEMMs
+  const MvdEnv& env = mvd_env();
+  const bool rc = env.rowchain && !f.train && !sv && t.rc_stream && rows >= env.rowchain_min_rows && rowchain_takes(C, rows, T) && !(in.ld & 3) && !(out.ld & 3);
   // the stream was packed for this precision form of proj_out (rc_po 0: that form of the kernel does not exist at this width)
-  const bool rc_po = rc && t.rc_po != 0 && t.rc_po == (t.proj_out.xp ? 2 : 1) && !(no_xpf && t.proj_out.xp) &&
+  const bool rc_po = rc && t.rc_po != 0 && t.rc_po == (t.proj_out.xp ? 2 : 1) && !(!env.xp_fuse && t.proj_out.xp) &&
                      rowchain_form_instantiated(C, 1, t.rc_po);
   half_t* n0 = ws_alloc<half_t>(c, (size_t)rows * C * wi);
   float* t0 = ws_alloc<float>(c, (size_t)rows * C);
@@ -628,8 +624,7 @@ int unet_do_st(Fwd& f, const STW& t, View in, View out, int H, int W, STSaved* s
   float* t2 = rc ? nullptr : ws_alloc<float>(c, (size_t)rows * C);
   // Layered path, plain-precision proj_out, inference: FF2 and proj_out are ONE GEMM over [gg | t2] with K = 5C (STW::ffp); LayerNorm3
   // leaves the fp16 copy of t2 behind the 4C columns of gg, t3 does not exist (MVD_NO_FFP=1: the two layers)
-  static const bool ln_scalar = getenv("MVD_LN_SCALAR") != nullptr;
-  const bool ffp = !rc && t.ffp.w && !f.train && !sv && !t.proj_out.xp && !ln_scalar && layernorm_slabs_takes(C);
+  const bool ffp = !rc && t.ffp.w && !f.train && !sv && !t.proj_out.xp && !env.ln_scalar && layernorm_slabs_takes(C);
   const int ldg = ffp ? 5 * C : 4 * C;
   half_t* gg = rc ? nullptr : ws_alloc<half_t>(c, (size_t)rows * ldg);
   half_t* t3 = (rc_po || ffp) ? nullptr : ws_alloc<half_t>(c, (size_t)rows * C * wo);  // x + ff(x): only ever the proj_out operand -> fp16
@@ -645,22 +640,19 @@ int unet_do_st(Fwd& f, const STW& t, View in, View out, int H, int W, STSaved* s
   // that LayerNorm when the plan splits K: launch_layernorm_slabs sums them, adds what the reduce pass would have added, writes the
   // finished fp32 row (t0 / t2: the later residuals) and the normalised fp16 row -- no reduce launch (the low-resolution blocks and
   // the few-views-per-rank step, where K is split).  Inference only.
-  // MEASURED (profiles/r06_g_ab_ln_defer.txt): 2 launches fewer at the headline, 12 fewer at 2 views per rank, and no time gained
-  // (13.20 vs 13.17 ms, 6.49 vs 6.45 ms): a dependent 5 us reduce launch with a warm L2 costs what the wider LayerNorm costs.  Kept
-  // as a tested form behind MVD_LN_DEFER=1, off by default.
-  static const bool no_ln_defer = getenv("MVD_LN_DEFER") == nullptr || getenv("MVD_NO_DEFER_REDUCE") != nullptr;
+  // MEASURED: 2 launches fewer at the headline, 12 fewer at 2 views per rank, and no time gained: a dependent 5 us reduce launch
+  // with a warm L2 costs what the wider LayerNorm costs.  Kept as a tested form behind MVD_LN_DEFER=1, off by default.
   const size_t ln_slab_elems = (size_t)rows * C;
   int sk_ln = 1;
   auto offer_ln_slabs = [&](GemmArgs& ga, int* sk) {
     *sk = 1;
-    if (no_ln_defer || f.train || sv || !layernorm_slabs_takes(C) || (c->a2_total & 3) || (t.a2_off & 3)) return;
+    if (!env.ln_defer || f.train || sv || !layernorm_slabs_takes(C) || (c->a2_total & 3) || (t.a2_off & 3)) return;
     const size_t nsl = rows > 8192 ? 4 : 16;
     ga.slabs = ws_alloc<float>(c, nsl * ln_slab_elems);
     ga.slabs_cap = ga.slabs ? nsl * ln_slab_elems : 0;
     ga.sk_used = sk;
   };
-  static const bool no_rh = getenv("MVD_NO_ROWHEAD") != nullptr;
-  if (rc && !no_rh && t.rh_stream && t.rh_xp == (t.proj_in.xp ? 1 : 0) && !(no_xpf && t.proj_in.xp)) {
+  if (rc && env.rowhead && t.rh_stream && t.rh_xp == (t.proj_in.xp ? 1 : 0) && !(!env.xp_fuse && t.proj_in.xp)) {
     // row-head kernel: proj_in -> t0, LayerNorm1 and the q | k | v projection in one launch (k_rowchain.hip)
     RowHead hp;
     hp.stream = t.rh_stream; hp.rows = rows; hp.n0 = n0; hp.ld_n0 = C * wi; hp.b_pi = t.proj_in.bias; hp.t0 = t0; hp.ld_t0 = C;
@@ -774,9 +766,8 @@ namespace {
 // only (sum, sumsq) per group, pass 2 re-computes it and applies scale/shift + ReLU in the epilogue.  Depends on the context
 // volume and the weights only, so engine_unet issues it on the side stream for every DepthTransformer up front.
 bool ctx_fold_ok(const Fwd& f, const CondW& d, int HW, int D, int level) {
-  static const bool fold_off = getenv("MVD_NO_CTX_FOLD") != nullptr;
   const int rps = D * HW, cpg = d.Cc / 8;
-  return !fold_off && f.n_ctx > 0 && f.src16[level] && rps % 256 == 0 && (cpg == 8 || cpg == 16 || cpg == 32) &&
+  return mvd_env().ctx_fold && f.n_ctx > 0 && f.src16[level] && rps % 256 == 0 && (cpg == 8 || cpg == 16 || cpg == 32) &&
          (long)f.n_ctx * HW * D >= 512;
 }
 // the same for every DepthTransformer of one context level at once (mvd_ctx::CtxGroup): cn_all [n_ctx * HW * D][nblk * Cc]
@@ -824,9 +815,8 @@ int unet_do_cond(Fwd& f, const CondW& d, View in, View out, int H, int W, int le
   // Samples without context (CFG's unconditional half) get x + K (mvd_ctx::CondConst): the block below then runs on the Bx = n_ctx
   // samples WITH context only -- half the rows of proj_in, the three GroupNorms, the output projection and both 3x3 convolutions.
   // MVD_NO_COND_CONST=1: the round-5 form (every layer over all samples, the context-free rows' z filled with relu(beta)).
-  static const bool no_const = getenv("MVD_NO_COND_CONST") != nullptr;
   const int n_free = f.Bv - f.n_ctx;
-  const bool use_const = !no_const && !f.train && !c->train_mode && cond_idx >= 0 && n_free > 0 && f.n_ctx > 0 && !(d.dim & 3) &&
+  const bool use_const = mvd_env().cond_const && !f.train && !c->train_mode && cond_idx >= 0 && n_free > 0 && f.n_ctx > 0 && !(d.dim & 3) &&
                          !(in.ld & 3) && !(out.ld & 3);
   if (use_const) {
     if (c->cond_const.size() < c->conds.size()) c->cond_const.resize(c->conds.size());
@@ -866,12 +856,10 @@ int unet_do_cond(Fwd& f, const CondW& d, View in, View out, int H, int W, int le
   // conv1 -> gn_o2) leave their split-K slabs to that norm when the plan splits K (GemmArgs::slabs, as ResBlock conv1 does): the
   // reduce pass -- a launch, a write and a read of the tensor -- disappears (round 6: 24 of the headline step's 46 reduce launches
   // sat in front of a GroupNorm here; MVD_NO_COND_DEFER=1 restores them).  Inference only: the backward pass reads p / o / o2.
-  static const bool no_cdefer = getenv("MVD_NO_COND_DEFER") != nullptr || getenv("MVD_NO_DEFER_REDUCE") != nullptr ||
-                                getenv("MVD_GN_TWO_PASS") != nullptr;
   const size_t slab_elems = (size_t)rows * I;
   auto offer_slabs = [&](GemmArgs& ga, int* sk, int ldo) {
     *sk = 1;
-    if (no_cdefer || f.train || !gn_group_eligible(I, HW, I, 8, 0, ldo)) return;
+    if (!mvd_env().cond_defer || f.train || !gn_group_eligible(I, HW, I, 8, 0, ldo)) return;
     const size_t nsl = rows > 8192 ? 4 : 16;
     ga.slabs = ws_alloc<float>(c, nsl * slab_elems);
     ga.slabs_cap = ga.slabs ? nsl * slab_elems : 0;
@@ -965,8 +953,7 @@ int unet_do_op(Fwd& f, const UOp& op, View in, View out, int& H, int& W, StageRe
       if (can_defer) {
         g.slabs = out_carry->slabs; g.slabs_cap = out_carry->cap; g.sk_used = &skc; g.defer_epilogue = true;
       }
-      static const bool no_in32 = getenv("MVD_NO_CONV_IN_F32") != nullptr;
-      if (op.kind == OP_CONV_IN && !f.train && !no_in32 && c->convs[op.idx].w32) {
+      if (op.kind == OP_CONV_IN && !f.train && mvd_env().conv_in_f32 && c->convs[op.idx].w32) {
         // inference: the first convolution in exact fp32 on the vector ALU (K = 72 is all staging for the MFMA forms)
         const ConvW& cw = c->convs[op.idx];
         ProbeScope ps(c, f.s, "conv_in_f32_kernel", 2.0 * f.Bv * H * W * 72.0 * cw.N,
@@ -991,11 +978,10 @@ int unet_do_op(Fwd& f, const UOp& op, View in, View out, int& H, int& W, StageRe
         g.a = as; g.a_f32 = 0; g.lda = 3 * Cl;
       }
       // weight-streaming regime (few pixels): the 9-tap form moves 9 slabs instead of 16
-      static const bool no_up3x = getenv("MVD_NO_UP_CONV3X") != nullptr;
       const ConvW& cw = c->convs[op.idx];
       if (ups && cw.w_up && f.Bv * H * W >= 2048) {
         RET_IF(run_upconv2d(c, g, f.Bv, H, W, f.s));
-      } else if (ups && !no_up3x && !f.train && cw.wx && !cw.xp && 2 * H == cw.res_out && 2 * W == cw.res_out && c->use_halo && !(in.ld & 3) &&
+      } else if (ups && mvd_env().up_conv3x && !f.train && cw.wx && !cw.xp && 2 * H == cw.res_out && 2 * W == cw.res_out && c->use_halo && !(in.ld & 3) &&
                  !(op.cin & 3)) {
         // 4 x 4 -> 8 x 8: the nearest-upsampled image as fp16 (one small launch), then conv3x over whole 8 x 8 images (round 6: the
         // register-staged 9-tap GEMM on the fp32 source ran this layer at 476 TFLOP/s, 127 us of the step)
@@ -1102,9 +1088,8 @@ int engine_unet(mvd_ctx* c, const float* x_nhwc, int x_ld, const int64_t* t, con
   // the side stream back on every exit path, so the workspace these launches use is never handed out again while they may
   // still be running.
   SideJoin join(s);
-  static const bool side_off = getenv("MVD_NO_SIDE_STREAM") != nullptr;
   // (the training forward stays on one stream: its intermediates are the tape, ordered with the backward pass that follows)
-  const bool use_side = !side_off && !tape && n_ctx > 0 && src && c->conds.size() <= 16;
+  const bool use_side = mvd_env().side_stream && !tape && n_ctx > 0 && src && c->conds.size() <= 16;
   bool forked = false;
   // fork_ctx: everything that produces or only reads the context volumes.  With a producer (the frustum network of
   // mvd_denoise_views) it is called after the full-resolution input blocks, so the side stream shares the CUs with the
@@ -1119,10 +1104,9 @@ int engine_unet(mvd_ctx* c, const float* x_nhwc, int x_ld, const int64_t* t, con
       // was not bit-reproducible in ~5 % of runs)
       // MVD_ONE_WAY_FORK re-creates the round-1 non-determinism on demand (tools/det_fork.sh; the pad /
       // spin / host-sync variants of that investigation are in the history: commit 88b2973)
-      static const bool one_way = getenv("MVD_ONE_WAY_FORK") != nullptr;
       HIP_CHECK_RET(hipEventRecord(c->ev_fork, s));
       HIP_CHECK_RET(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-      if (!one_way) {
+      if (!mvd_env().one_way_fork) {
         HIP_CHECK_RET(hipEventRecord(c->ev_join2, c->side));
         HIP_CHECK_RET(hipStreamWaitEvent(s, c->ev_join2, 0));
       }
@@ -1169,10 +1153,9 @@ int engine_unet(mvd_ctx* c, const float* x_nhwc, int x_ld, const int64_t* t, con
       if (i >= 3 && 1 + (i - 3) < cH.size()) cH[1 + (i - 3)] = Hc;
     }
     // the blocks of one level together (mvd_ctx::CtxGroup: the volume is read once per pass and level); MVD_NO_CTX_GROUP=1: one by one
-    static const bool no_group = getenv("MVD_NO_CTX_GROUP") != nullptr;
     std::vector<char> grouped(c->conds.size(), 0);
     for (const mvd_ctx::CtxGroup& gp : c->ctx_groups) {
-      if (no_group) break;
+      if (!mvd_env().ctx_group) break;
       bool ok = gp.nblk >= 2;
       int Hk = 0;
       for (int j = 0; j < gp.nblk && ok; ++j) {
@@ -1215,8 +1198,7 @@ int engine_unet(mvd_ctx* c, const float* x_nhwc, int x_ld, const int64_t* t, con
   // stream waits for them behind the first input block).  Their split-K scratch is freed by host scopes while the side
   // stream may still use it: held, like the context producer's (Workspace::hold).
   float *e0 = nullptr, *e1 = nullptr, *e2 = nullptr, *ea = nullptr, *a2 = nullptr;
-  static const bool side_emb_off = getenv("MVD_NO_SIDE_EMB") != nullptr;
-  const bool side_emb = use_side && produce && !side_emb_off && c->in_blocks.size() > 1 && c->ws.hold == 0;  // (without a producer the side stream is already busy with the context folds)
+  const bool side_emb = use_side && produce && mvd_env().side_emb && c->in_blocks.size() > 1 && c->ws.hold == 0;  // (without a producer the side stream is already busy with the context folds)
   if (side_emb) {
     RET_IF(engine_side_init(c));
     HIP_CHECK_RET(hipEventRecord(c->ev_emb0, s));  // t / context were written on the caller's stream
@@ -1269,9 +1251,9 @@ int engine_unet(mvd_ctx* c, const float* x_nhwc, int x_ld, const int64_t* t, con
 
   // A block whose first layer is a single-pass GroupNorm over exactly the previous block's output can take that output as
   // split-K slabs (Carry): the previous block's reduce pass and this GroupNorm become one launch.
-  static const bool no_carry = getenv("MVD_NO_CARRY") != nullptr;
+  const bool carry = mvd_env().carry;
   auto takes_carry = [&](const UOp& nx, int Hn) -> bool {
-    if (no_carry || tape || (long)Bv * Hn * Hn > 8192) return false;  // (full resolution never splits K)
+    if (!carry || tape || (long)Bv * Hn * Hn > 8192) return false;  // (full resolution never splits K)
     const int C = nx.cin;
     if (nx.kind == OP_RES) return gn_group_eligible(C, Hn * Hn, C, 32, 0, C * (c->res[nx.idx].c1.xp ? 3 : 1));
     if (nx.kind == OP_ST) return gn_group_eligible(C, Hn * Hn, C, 32, 0, C * (c->st[nx.idx].proj_in.xp ? 3 : 1));
@@ -1366,7 +1348,7 @@ int engine_unet(mvd_ctx* c, const float* x_nhwc, int x_ld, const int64_t* t, con
     size_t emax = 0;
     for (int j = 0; j < nb; ++j)
       if ((long)Bv * in_res[j] * in_res[j] <= 8192) emax = std::max(emax, (size_t)Bv * in_res[j] * in_res[j] * in_ch[j]);
-    if (emax && !tape && !no_carry) {
+    if (emax && !tape && carry) {
       carry_storage(xcarry[0], emax);
       carry_storage(xcarry[1], emax);
     }
@@ -1414,8 +1396,7 @@ int engine_unet(mvd_ctx* c, const float* x_nhwc, int x_ld, const int64_t* t, con
   // out: GroupNorm32 + SiLU + zero-init conv (openaimodel.py:717-721)
   {
     const int rows = Bv * H * W;
-    static const bool no_head32 = getenv("MVD_NO_OUT_CONV_F32") != nullptr || getenv("MVD_GN_TWO_PASS") != nullptr;
-    if (!tape && !no_head32 && c->out_conv.w32 && !(W & 15) && gn_group_eligible(mc, H * W, mc, 32, 0, 2 * mc)) {
+    if (!tape && mvd_env().out_conv_f32 && c->out_conv.w32 && !(W & 15) && gn_group_eligible(mc, H * W, mc, 32, 0, 2 * mc)) {
       // inference: GroupNorm + SiLU written in fp32, the 3 x 3 convolution onto 4 channels in exact fp32 on the vector ALU
       float* a32 = ws_alloc<float>(c, (size_t)rows * mc);
       WS_CHECK(a32);
@@ -1436,8 +1417,7 @@ int engine_unet(mvd_ctx* c, const float* x_nhwc, int x_ld, const int64_t* t, con
     RET_IF(run_conv2d(c, g, Bv, H, W, 1, 0, s));
     }
   }
-  static const bool dbg_sum = getenv("MVD_DEBUG_SUM") != nullptr;  // investigation aid: which buffers differ between repeats?
-  if (dbg_sum) {
+  if (mvd_env().debug_sum) {  // investigation aid: which buffers differ between repeats?
     hipStreamSynchronize(s);
     if (c->side) hipStreamSynchronize(c->side);
     unsigned long long* d = ws_alloc<unsigned long long>(c, 1);

@@ -234,8 +234,7 @@ int build_sparse_layer(mvd_ctx* c, const std::string& p, const std::string& blk,
   RET_IF(launch_sparse_w_pack(w->d, cin, cout, layout, L->w, c->bs));                       // -> [27][cin][cout]
   // MVD_SPARSE_VALU=1 (A/B switch, read when the weights are built): the one-site-per-workgroup kernels and the scatter-form
   // data gradient instead -- tests/test_gpu_train.py holds the two forms against each other
-  const bool valu_only = getenv("MVD_SPARSE_VALU") != nullptr && getenv("MVD_SPARSE_VALU")[0] == '1';
-  if (sparse_mfma_takes(cin, cout) && !valu_only) {  // B fragments of the matrix-core kernel; the data-gradient's in a training context
+  if (sparse_mfma_takes(cin, cout) && !mvd_env_call::sparse_valu()) {  // B fragments of the matrix-core kernel; the data-gradient's in a training context
     RET_IF(dmalloc(c, (void**)&L->wp, w->numel * 4));
     RET_IF(launch_sparse_w_frag(L->w, cin, cout, 0, 0, L->wp, c->bs));
     if (c->train_mode) {
@@ -563,8 +562,7 @@ int xp_ops(mvd_ctx* c, const std::vector<UOp>& ops, bool convs3) {
 // (k_conv3x.hip); the level of a convolution is not recorded in ResW, its width is: levels 0 .. l16 have at most
 // model_channels * channel_mult[l16] output channels, where l16 is the last level whose resolution is a multiple of 16.
 int build_conv3x_streams(mvd_ctx* c) {
-  static const bool off = getenv("MVD_NO_CONV3X") != nullptr;
-  if (off || !c->has_unet) return 0;
+  if (!mvd_env().conv3x || !c->has_unet) return 0;
   // conv3x takes resolutions divisible by 16 and 8 x 8 images (conv3x_eligible): only convolutions that RUN at such a resolution
   // get a stream (the plan records it in ResW::res / CondW::res) -- with channel_mult (1, 2, 4, 4) the 4 x 4 level's 1280-wide
   // ResBlocks share their width with the 8 x 8 level's, and a stream for them would be ~29 MB each, packed (and re-packed every
@@ -653,8 +651,7 @@ int build_rowchain_streams(mvd_ctx* c) {
 // runs in extended precision keeps the two layers.  Inference contexts only (a training context re-packs every step and its
 // backward pass needs both layers).
 int build_ffp(mvd_ctx* c) {
-  static const bool off = getenv("MVD_NO_FFP") != nullptr;
-  if (off || !c->has_unet || c->train_mode) return 0;
+  if (!mvd_env().ffp || !c->has_unet || c->train_mode) return 0;
   for (STW& st : c->st) {
     if (st.proj_out.xp || (st.C & 7)) continue;
     const int C = st.C;
@@ -688,7 +685,7 @@ int build_ffp(mvd_ctx* c) {
 }
 
 int apply_xp_policy(mvd_ctx* c) {
-  const int lvl = getenv("MVD_XP") ? atoi(getenv("MVD_XP")) : c->precision_level;
+  const int lvl = mvd_env_call::xp(c->precision_level);
   if (lvl <= 0 || !c->has_unet) return 0;
   const std::string U = "model.diffusion_model.";
   RET_IF(repack_xp(c, U + "out.2.weight", &c->out_conv));
@@ -1069,7 +1066,7 @@ int engine_repack(mvd_ctx* c, hipStream_t after, bool have_stream) {
   if (!c->finalized || !c->train_mode) return mvd_fail("engine_repack: the context was not finalized in training mode");
   HIP_CHECK_RET(hipSetDevice(c->device));
   // ~600 pack / fold launches of 5-50 us that do not fill the chip: four streams (MVD_REPACK_STREAMS=1: one stream)
-  static const bool one_stream = getenv("MVD_REPACK_STREAMS") != nullptr && getenv("MVD_REPACK_STREAMS")[0] == '1';
+  const bool one_stream = mvd_env().repack_one_stream;
   if (!c->bstreams[0])
     for (int i = 0; i < 4; ++i) {
       HIP_CHECK_RET(hipStreamCreateWithFlags(&c->bstreams[i], hipStreamNonBlocking));

@@ -353,7 +353,7 @@ int launch_attention(const half_t* qk, int ldqk, const half_t* v, int ldv, half_
     return mvd_fail("attention: alignment (row strides and d multiples of 8, 16-byte aligned operands)");
   if ((long)cdiv(T, 128) * heads * B > 0x7FFFFFFFL) return mvd_fail("attention: grid too large");
   dim3 grid((unsigned)(cdiv(T, 128) * heads * B));
-  static const int xcd_remap = getenv("MVD_ATTN_NO_XCD") == nullptr;  // A/B switch: the pre-remap workgroup order
+  const int xcd_remap = mvd_env().attn_xcd;
   const float scale = 1.4426950408889634f / sqrtf((float)d);  // softmax scale * log2(e): the kernel uses exp2
 #define MVD_ATTN(DD) \
   case DD: hipLaunchKernelGGL(attn_kernel<DD>, grid, dim3(256), 0, s, qk, ldqk, v, ldv, out, ldo, T, heads, scale, Tstride, xcd_remap); break;

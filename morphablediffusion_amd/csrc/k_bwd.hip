@@ -1133,8 +1133,7 @@ int bwd_tcast(const void* src, int src_f32, long ld, int R, int C, half_t* dst, 
   if (split && !src_f32) return mvd_fail("bwd_tcast: the split layout needs an fp32 source");
   if (rows16 && (Cp < C || Cp > 64 * cdiv(C, 64))) return mvd_fail("bwd_tcast: bad row-image width");
   dim3 grid(cdiv(Rp, 64), cdiv(C, 64));
-  static const bool scalar_only = getenv("MVD_STAGE_SCALAR") != nullptr;  // A/B switch: the element-per-thread staging kernels
-  const bool vec = !scalar_only && !(C & 3) && !(ld & 3) && !(Rp & 63) && !((uintptr_t)src & 15) && !((uintptr_t)dst & 15) &&
+  const bool vec = !mvd_env().stage_scalar && !(C & 3) && !(ld & 3) && !(Rp & 63) && !((uintptr_t)src & 15) && !((uintptr_t)dst & 15) &&
                    (!rows16 || (!(Cp & 3) && !((uintptr_t)rows16 & 7)));
   if (vec) {
     if (src_f32) hipLaunchKernelGGL(tcast_vec_kernel<float>, grid, dim3(256), 0, s, (const float*)src, ld, R, C, dst, Rp, split, rows16, Cp);
@@ -1148,8 +1147,7 @@ int bwd_im2colT(const void* src, int src_f32, long ld, int B, int H, int W, int 
   const int Ho = ((H << ups) - 1) / stride + 1, Wo = ((W << ups) - 1) / stride + 1;
   if (Rp < B * Ho * Wo) return mvd_fail("bwd_im2colT: bad shape");
   dim3 grid(cdiv(Rp, 64), cdiv(C, 64), 9);
-  static const bool scalar_only = getenv("MVD_STAGE_SCALAR") != nullptr;
-  if (!scalar_only && !(C & 3) && !(ld & 3) && !(Rp & 63) && !((uintptr_t)src & 15) && !((uintptr_t)dst & 15)) {
+  if (!mvd_env().stage_scalar && !(C & 3) && !(ld & 3) && !(Rp & 63) && !((uintptr_t)src & 15) && !((uintptr_t)dst & 15)) {
     if (src_f32) hipLaunchKernelGGL(im2colT_vec_kernel<float>, grid, dim3(256), 0, s, (const float*)src, ld, B, H, W, C, stride, ups, Ho, Wo, dst, Rp);
     else hipLaunchKernelGGL(im2colT_vec_kernel<half_t>, grid, dim3(256), 0, s, (const half_t*)src, ld, B, H, W, C, stride, ups, Ho, Wo, dst, Rp);
   } else if (src_f32) hipLaunchKernelGGL(im2colT_kernel<float>, grid, dim3(256), 0, s, (const float*)src, ld, B, H, W, C, stride, ups, Ho, Wo, dst, Rp);
@@ -1158,8 +1156,7 @@ int bwd_im2colT(const void* src, int src_f32, long ld, int B, int H, int W, int 
   return 0;
 }
 int bwd_cast_rows(const float* src, long ld, long rows, int C, int Cp, half_t* dst, hipStream_t s, int split) {
-  static const bool scalar_only = getenv("MVD_STAGE_SCALAR") != nullptr;
-  if (!scalar_only && !(C & 3) && !(Cp & 3) && !(ld & 3) && !((uintptr_t)src & 15) && !((uintptr_t)dst & 7))
+  if (!mvd_env().stage_scalar && !(C & 3) && !(Cp & 3) && !(ld & 3) && !((uintptr_t)src & 15) && !((uintptr_t)dst & 7))
     hipLaunchKernelGGL(cast_rows_vec_kernel, dim3(gridn((size_t)rows * (Cp >> 2))), dim3(256), 0, s, src, ld, rows, C, Cp, dst, split);
   else
     hipLaunchKernelGGL(cast_rows_kernel, dim3(gridn((size_t)rows * Cp)), dim3(256), 0, s, src, ld, rows, C, Cp, dst, split);
@@ -1167,8 +1164,7 @@ int bwd_cast_rows(const float* src, long ld, long rows, int C, int Cp, half_t* d
   return 0;
 }
 int bwd_pack_dgrad(const half_t* w, int taps, int N, int ldw, int Cl, int Np, half_t* wT, hipStream_t s, int flip) {
-  static const bool scalar_only = getenv("MVD_STAGE_SCALAR") != nullptr;
-  if (!scalar_only && !(ldw & 7) && !(Np & 7) && !(Cl & 7) && !((uintptr_t)w & 15) && !((uintptr_t)wT & 15))
+  if (!mvd_env().stage_scalar && !(ldw & 7) && !(Np & 7) && !(Cl & 7) && !((uintptr_t)w & 15) && !((uintptr_t)wT & 15))
     hipLaunchKernelGGL(pack_dgrad_vec_kernel, dim3(cdiv(Np, 64), cdiv(Cl, 64), taps), dim3(256), 0, s, w, taps, N, ldw, Cl, Np, wT, flip);
   else
     hipLaunchKernelGGL(pack_dgrad_kernel, dim3(cdiv(Np, 64), cdiv(Cl, 64), taps), dim3(256), 0, s, w, taps, N, ldw, Cl, Np, wT, flip);

@@ -565,8 +565,7 @@ int launch_bn_fold(const float* gamma, const float* beta, const float* mean, con
 int launch_bn_rows_relu(const float* x, float* y, int n, int C, const float* gamma, const float* beta, float eps, float* stats_out,
                         hipStream_t s, float* rmean, float* rvar, float momentum) {
   if (n <= 0 || C <= 0) return 0;
-  const char* loop_env = getenv("MVD_BN_LOOP");  // A/B + the bit-identity test: the looped form
-  const bool loop = loop_env && loop_env[0] == '1';
+  const bool loop = mvd_env_call::bn_loop();  // A/B + the bit-identity test: the looped form
   if (n <= 256 * 24 && !loop)
     hipLaunchKernelGGL(bn_rows_relu_reg_kernel<24>, dim3(C), dim3(256), 0, s, x, y, n, C, gamma, beta, eps, stats_out, rmean, rvar, momentum);
   else if (n <= 256 * 48 && !loop)

@@ -676,8 +676,7 @@ int cbwd_im2colT3d(const void* src, int src_f32, long ld, int B, int D, int H, i
   const int Do = (D - 1) / stride + 1, Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
   if (Rp < B * Do * Ho * Wo) return mvd_fail("im2colT3d: bad shape");
   dim3 grid(cdiv(Rp, 64), cdiv(C, 64), 27);
-  static const bool scalar_only = getenv("MVD_STAGE_SCALAR") != nullptr;
-  if (!scalar_only && !(C & 3) && !(ld & 3) && !(Rp & 63) && !((uintptr_t)src & 15) && !((uintptr_t)dst & 15)) {
+  if (!mvd_env().stage_scalar && !(C & 3) && !(ld & 3) && !(Rp & 63) && !((uintptr_t)src & 15) && !((uintptr_t)dst & 15)) {
     if (src_f32) hipLaunchKernelGGL(im2colT3d_vec_kernel<float>, grid, dim3(256), 0, s, (const float*)src, ld, B, D, H, W, C, stride, Do, Ho, Wo, dst, Rp);
     else hipLaunchKernelGGL(im2colT3d_vec_kernel<half_t>, grid, dim3(256), 0, s, (const half_t*)src, ld, B, D, H, W, C, stride, Do, Ho, Wo, dst, Rp);
     HIP_CHECK_RET(hipGetLastError());

@@ -353,9 +353,8 @@ int launch_cx(const IGemm& g, const half_t* stream, hipStream_t s) {
   constexpr int NI = CxGeo<IW>::NI;
   dim3 grid(cdiv(g.B * (g.Y / IW) * (g.X / IW), NI) * (g.N / (32 * NF)), g.splitk > 1 ? g.splitk : 1);
   IGemm gl = g;
-  static const bool no_cols = getenv("MVD_NO_XCD_COLS") != nullptr;
   const int tiles_m = cdiv(g.B * (g.Y / IW) * (g.X / IW), NI);
-  gl.xcd_cols = !no_cols && xcd_prefers_cols(tiles_m, g.N / (32 * NF), (double)tiles_m * CxGeo<IW>::ROWS * g.Cin * 2, 9.0 * g.N * g.Cin * 2);
+  gl.xcd_cols = mvd_env().xcd_cols && xcd_prefers_cols(tiles_m, g.N / (32 * NF), (double)tiles_m * CxGeo<IW>::ROWS * g.Cin * 2, 9.0 * g.N * g.Cin * 2);
   hipLaunchKernelGGL((conv3x_kernel<NF, IW>), grid, dim3(256), LDS, s, gl, stream);
   HIP_CHECK_RET(hipGetLastError());
   return 0;

@@ -528,9 +528,8 @@ int launch_gd(const IGemm& g, int M, hipStream_t s) {
   IGemm gl = g;
   gl.xcd_cols = 0;
   if (MODE == 0) {
-    static const bool no_cols = getenv("MVD_NO_XCD_COLS") != nullptr;
     const int ntaps = g.npar > 0 ? g.par_ntaps[0] : g.ntaps;
-    gl.xcd_cols = !no_cols && xcd_prefers_cols(cdiv(M, BM), cdiv(cdiv(g.N, BN), nch),
+    gl.xcd_cols = mvd_env().xcd_cols && xcd_prefers_cols(cdiv(M, BM), cdiv(cdiv(g.N, BN), nch),
                                                (double)g.B * g.PZ * g.PY * g.PX * g.Cin * (g.a_f32 ? 4 : 2), (double)ntaps * g.N * g.Cin * 2);
   }
   hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, MODE, PLAIN>), grid, dim3(BM * 2), LDS, s, gl);
@@ -609,7 +608,6 @@ void gemm_dma_plan_us(int M, int N, int ksteps, int geglu, int out_b, int res_b,
   // wave per SIMD pays every DMA issue, LDS wait and barrier of the step itself, so what a k-step costs is its dependent chain, not
   // its MFMAs.  8192 x 640 x 640: 27.0 us as 256 tiles of 128 x 160 against 24.0 as 160 tiles of 256 x 128; no shape of the step won.
   // The planner therefore only offers these tiles when MVD_BM128=1 (A/B reproduction); with the measured step times it would not pick them.
-  static const bool no_bm128 = getenv("MVD_BM128") == nullptr || getenv("MVD_NO_BM128") != nullptr;
   struct Cand {
     int bm, bn;
     double t_step;
@@ -617,7 +615,7 @@ void gemm_dma_plan_us(int M, int N, int ksteps, int geglu, int out_b, int res_b,
   const Cand cand[6] = {{256, 64, 0.70}, {256, 128, 1.05}, {256, 160, 1.25}, {128, 96, 0.70}, {128, 128, 0.79}, {128, 160, 1.03}};
   for (int ci = 0; ci < 6; ++ci) {
     const int bm = cand[ci].bm, bn = cand[ci].bn;
-    if (bm == 128 && (!bm_out || no_bm128 || geglu)) continue;
+    if (bm == 128 && (!bm_out || !mvd_env().bm128 || geglu)) continue;
     if (bm == 256 && (geglu ? bn != 128 : (*bn_io < 0 && bn != -*bn_io))) continue;  // bn_io < 0: the caller fixes the width
     if (bm == 128 && *bn_io < 0) continue;
     const double t_step = cand[ci].t_step;
@@ -667,9 +665,8 @@ void gemm_dma_plan_us(int M, int N, int ksteps, int geglu, int out_b, int res_b,
 
 // one centre tap, unit strides, linear input and output rows: the PLAIN instantiations (every Linear layer and 1 x 1 conv)
 bool gemm_dma_is_plain(const IGemm& g) {
-  static const bool no_plain = getenv("MVD_NO_PLAIN") != nullptr;
   const long M = (long)g.B * g.Z * g.Y * g.X;
-  return !no_plain && g.npar == 0 && g.ntaps == 1 && g.tap[0] == igemm_tap(0, 0, 0, 0) && g.out_linear && g.ups == 0 && g.sz == 1 &&
+  return mvd_env().plain && g.npar == 0 && g.ntaps == 1 && g.tap[0] == igemm_tap(0, 0, 0, 0) && g.out_linear && g.ups == 0 && g.sz == 1 &&
          g.sy == 1 && g.sx == 1 && g.PZ == g.Z && g.PY == g.Y && g.PX == g.X && g.IZ == g.Z && g.IY == g.Y && g.IX == g.X &&
          M < (1 << 22) && !g.gn_partial && !g.rowscale;
 }

@@ -703,9 +703,8 @@ int launch_layernorm(const float* x, int rows, int C, const float* gamma, const 
   LnSlabs sl = LnSlabs();
   sl.raw = raw;
   sl.ld_raw = ld_raw;
-  static const bool no_vec = getenv("MVD_LN_SCALAR") != nullptr;
   const bool aligned = !(((uintptr_t)x | (uintptr_t)out | (uintptr_t)gamma | (uintptr_t)beta) & 15);
-  if (!no_vec && aligned && C % 40 == 0) {  // C = 8 * L * 5: the UNet's 320 / 640 / 1280 / 2560-wide rows
+  if (!mvd_env().ln_scalar && aligned && C % 40 == 0) {  // C = 8 * L * 5: the UNet's 320 / 640 / 1280 / 2560-wide rows
     const int L = C / 40;
 #define MVD_LNV(L_) \
   hipLaunchKernelGGL((layernorm_vec_kernel<L_, 5>), dim3(cdiv(rows, 4 * (64 / L_))), dim3(256), 0, s, x, rows, C, gamma, beta, eps, out, sl)

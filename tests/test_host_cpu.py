@@ -27,6 +27,55 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
     assert sorted(lib.SYMBOLS) == declared
 
 
+def _env_table():
+    """The rows of csrc/env.h: {name: (lifetime, kind, field, default)}."""
+    header = open(os.path.join(ROOT, "morphablediffusion_amd", "csrc", "env.h")).read()
+    rows = re.findall(r'^\s+(PROCESS|ENGINE|CALL|PROCESS_CALL)\((on|off|one|num), (\w+), "(MVD_[A-Z0-9_]+)", (\w+), ".+"\)', header, re.M)
+    assert len(rows) == len(re.findall(r'"MVD_[A-Z0-9_]+"', header)), "a row of env.h is not in the table's one-line form"
+    table = {name: (life, kind, field, default) for life, kind, field, name, default in rows}
+    assert len(table) == len(rows) and len({r[2] for r in rows}) == len(rows), "env.h declares a variable or a field twice"
+    return table
+
+
+def test_every_environment_switch_in_use_is_declared_in_the_table():
+    """A test, tool or A/B script that sets a misspelled or removed MVD_* variable runs the default path and passes: every such
+    name in tests/, tools/ and the Python package must be a row of csrc/env.h or be read by Python code of the tree (the
+    package, bench.py, __graft_entry__.py, or the very file that uses it).  The library reads its environment through that
+    table only, and DESIGN.md section 5 lists the same rows."""
+    table = _env_table()
+    assert len(table) >= 50 and table["MVD_BN_LOOP"][0] == "CALL" and table["MVD_SPARSE_VALU"][0] == "CALL"
+    csrc = os.path.join(ROOT, "morphablediffusion_amd", "csrc")
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h")) and f != "env.h":
+            assert "getenv(" not in open(os.path.join(csrc, f)).read(), f"csrc/{f} reads the environment past the table of env.h"
+
+    py_read = re.compile(r"""environ\.get\(\s*["'](MVD_\w+)|environ\[\s*["'](MVD_\w+)|getenv\(\s*["'](MVD_\w+)|["'](MVD_\w+)["']\s+(?:not\s+)?in\s+os\.environ""")
+    reads = lambda path: {n for m in py_read.findall(open(path).read()) for n in m if n}
+    pkg = os.path.join(ROOT, "morphablediffusion_amd")
+    python_side = set()
+    for path in [os.path.join(pkg, f) for f in sorted(os.listdir(pkg)) if f.endswith(".py")] + [os.path.join(ROOT, "bench.py"), os.path.join(ROOT, "__graft_entry__.py")]:
+        python_side |= reads(path)
+    assert {"MVD_DTYPE", "MVD_LIB_PATH", "MVD_HEAD_ON_MAIN"} <= python_side
+    not_environment = {"MVD_BF16", "MVD_TIMELINE", "MVD_API",  # compile-time macros
+                       "MVD_DUMMY"}  # the A/B scripts' deliberate no-op
+    users = [os.path.join(pkg, f) for f in sorted(os.listdir(pkg)) if f.endswith(".py")]
+    for d in ("tests", "tools"):
+        users += [os.path.join(ROOT, d, f) for f in sorted(os.listdir(os.path.join(ROOT, d))) if f.endswith((".py", ".sh"))]
+    unknown = {}
+    for path in users:
+        text = open(path).read()
+        own = reads(path) if path.endswith(".py") else set()
+        for name in set(re.findall(r"\bMVD_[A-Z0-9_]+\b", text)) - set(table) - python_side - own - not_environment:
+            unknown.setdefault(name, []).append(os.path.relpath(path, ROOT))
+    assert not unknown, f"MVD_* names that nothing reads: {unknown}"
+
+    design = open(os.path.join(ROOT, "DESIGN.md")).read()
+    listed = re.findall(r"^\| `(MVD_[A-Z0-9_]+)` \| (\w+) \| `(\w+)` = (\w+) \| (process|engine|call)", design, re.M)
+    lifetime = {"PROCESS": "process", "ENGINE": "engine", "CALL": "call", "PROCESS_CALL": "process"}
+    assert {n: (k, f, d, l) for n, k, f, d, l in listed} == {n: (k, f, d, lifetime[l]) for n, (l, k, f, d) in table.items()}, \
+        "DESIGN.md section 5 and csrc/env.h list different switches"
+
+
 def test_library_has_no_crossed_packed_f32_multiply(tmp_path):
     """ISA lint of the built library.  On MI355X a ``v_pk_mul_f32`` whose low result takes the HIGH half of a VGPR operand
     (``op_sel:[0,1]``; the SLP vectoriser emits it for 3x4 camera transforms) returns 0 in the low half of lanes 48-63
