@@ -171,6 +171,25 @@ int mvd_vertex_features_stream_safe(mvd_ctx* ctx);
 int mvd_stage_target_encoder(mvd_ctx* ctx, const float* x_noisy, const float* t_embed, const float* v_embed, int n_local,
                              float* feats, void* stream);
 int mvd_stage_sparse_dense(mvd_ctx* ctx, const float* fused, int train_mode, float* dense_out, int32_t* shape_out, void* stream);
+/* use_spatial_volume=True (morphable_diffusion.py:197-225,259-261; SpatialTime3DNet network.py:235-283).
+ *   mvd_spatial_time_volume  NoisyTargetViewEncoder of ALL num_views views of the active sample slot -> dense unprojection onto
+ *                            the V^3 lattice -> SpatialTime3DNet; the result is ADDED into the slot's volume (call it after
+ *                            mvd_volume_from_fused of the same slot, on the same stream) and, when volume_out is not NULL, the
+ *                            network's own output [64,V,V,V] (before the add, reference layout) is written there.
+ *                            x_noisy [n_views,4,s,s], t_embed [time_dim], v_embed [n_views,view_dim]; n_views must equal
+ *                            num_views.  The stage runs out of an arena of its own (sized at mvd_finalize_weights): no
+ *                            allocation, and no use of the shared workspace.  Errors: switch off, weights not finalized,
+ *                            mvd_set_mesh / mvd_set_cameras not called, wrong view count.
+ *   mvd_stage_unproject      parity probe of the unprojection alone: feats [n_views,16,s,s] -> out [n_views*16,V,V,V] (view-major,
+ *                            the reference's layout; values as the fp16 operand holds them). */
+/* The switch itself: mvd_volume_config keeps its layout (existing callers pass it unchanged), the two new settings arrive
+ * through a setter, like the precision level -- after mvd_create, before the first mvd_upload_weight.  use != 0 turns the stage
+ * on; spatial_dims (NULL: 64,128,256,512) are SpatialTime3DNet's widths.  Checked: spatial_dims[0] == 64 (the volume's channel
+ * count), every dim a positive multiple of 8, spatial_volume_size % 8 == 0 (three stride-2 levels). */
+int mvd_set_spatial_volume(mvd_ctx* ctx, int use, const int* spatial_dims);
+int mvd_spatial_time_volume(mvd_ctx* ctx, const float* x_noisy, const float* t_embed, const float* v_embed, int n_views,
+                            float* volume_out, void* stream);
+int mvd_stage_unproject(mvd_ctx* ctx, const float* feats, int n_views, float* out, void* stream);
 /* The view-sharded step's ONE collective behind the C ABI (replaces nothing in the reference, whose sampler
  * is single-GPU: ldm/models/diffusion/morphable_diffusion.py:701-739).  Rank g owns views [g N/G, (g+1) N/G); every step each
  * rank computes the per-view vertex features of its views (mvd_vertex_view_features) and ALL-GATHERS them, so that every rank

@@ -163,6 +163,7 @@ void mvd_destroy(mvd_ctx* c) {
     hipFree(sl.volume);
   }
   hipFree(c->volume);
+  hipFree(c->sp_ws.base);
   hipFree(c->ws.base);
   for (hipEvent_t ev : c->probe_ev) hipEventDestroy(ev);
   for (auto& gb : c->buckets)
@@ -420,6 +421,36 @@ int mvd_stage_sparse_dense(mvd_ctx* c, const float* fused, int train_mode, float
   const float* rows = nullptr;
   RET_IF(engine_sparse_net(c, fused, S(stream), train_mode != 0, &rows));
   return launch_sparse_densify(rows, m.grid2, (long)m.shape[2][0] * m.shape[2][1] * m.shape[2][2], c->sparse[8].cout, dense_out, S(stream));
+}
+
+int mvd_set_spatial_volume(mvd_ctx* c, int use, const int* spatial_dims) {
+  if (!c) return mvd_fail("null context");
+  if (c->finalized || !c->raw.empty()) return mvd_fail("mvd_set_spatial_volume: call it before the first mvd_upload_weight");
+  const int def[4] = {64, 128, 256, 512};
+  const int* d = spatial_dims ? spatial_dims : def;
+  if (use) {  // SpatialTime3DNet: three stride-2 levels, GroupNorm(8), and its output is added to the 64-channel volume
+    if (d[0] != 64) return mvd_fail("mvd_set_spatial_volume: spatial_dims[0] must be 64 (the volume's channel count)");
+    for (int i = 0; i < 4; ++i)
+      if (d[i] <= 0 || d[i] % 8) return mvd_fail("mvd_set_spatial_volume: every spatial_dims entry must be a positive multiple of 8");
+    if (c->v.spatial_volume_size <= 0 || c->v.spatial_volume_size % 8)
+      return mvd_fail("mvd_set_spatial_volume: use_spatial_volume needs spatial_volume_size % 8 == 0");
+  }
+  c->use_spatial_volume = use ? 1 : 0;
+  for (int i = 0; i < 4; ++i) c->spatial_dims[i] = d[i];
+  return 0;
+}
+
+int mvd_spatial_time_volume(mvd_ctx* c, const float* x_noisy, const float* t_embed, const float* v_embed, int n_views,
+                            float* volume_out, void* stream) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
+  if (!c || !x_noisy || !t_embed || !v_embed) return mvd_fail("mvd_spatial_time_volume: null argument");
+  return engine_spatial_time_volume(c, x_noisy, t_embed, v_embed, n_views, volume_out, S(stream));
+}
+
+int mvd_stage_unproject(mvd_ctx* c, const float* feats, int n_views, float* out, void* stream) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
+  if (!c || !feats || !out) return mvd_fail("mvd_stage_unproject: null argument");
+  return engine_stage_unproject(c, feats, n_views, out, S(stream));
 }
 
 int mvd_set_volume_ready_event(mvd_ctx* c, void* event) {

@@ -243,6 +243,10 @@ struct ViewCam {
 };
 int launch_vertex_gather(const float* feats, const ViewCam* cams, const int* view_idx, int n_views, const float* verts, int Nv, int V,
                          float vol_len, int fsize, int persp, float* out, hipStream_t s);
+int launch_unproject_views(const float* feats, const ViewCam* cams, int N, int V, float vol_len, int S, int persp, half_t* out,
+                           hipStream_t s);
+int launch_rows_f16_to_nchw(const half_t* in, long rows, int C, float* out, hipStream_t s);
+int launch_accumulate_f32(float* dst, const float* src, size_t n, hipStream_t s);
 int launch_fuse_views(const float* vf, int n_views, int Nv, int total_views, const float* w, const float* b,
                       float* out, int accumulate, hipStream_t s);
 // w: [27][Cin][Cout]; wp: the same weights as matrix-core B fragments (launch_sparse_w_frag) or null -> one-site-per-workgroup kernel

@@ -155,6 +155,11 @@ struct FrustumBlockW {
   ConvW conv;
   int cin = 0, cout = 0, stride = 1;
 };
+struct SpatialBlockW {  // SpatialTimeBlock / SpatialUpTimeBlock (network.py:209-233): x + t_conv(t) -> GroupNorm(8) -> SiLU -> conv
+  NormW gn;
+  ConvW conv;
+  int cin = 0, cout = 0;
+};
 struct SparseLayerW {
   std::string wkey, bnkey;  // state_dict keys of the conv weight / of its BatchNorm1d (prefix)
   int layout = 0;           // layout of the uploaded weight (build_sparse_layer): the gradient goes back in the same one
@@ -315,6 +320,18 @@ struct mvd_ctx {
   // FiLM projections (t_conv / v_conv, time_embed / view_embed) of all blocks stacked: one launch each per step
   LinW film_t, film_v, enc_t, enc_v;
   int film_total = 0, film_off[9] = {0};
+  // use_spatial_volume=True: SpatialTime3DNet (network.py:235-283).  sp_blocks: conv0, conv1, conv2_0, conv2_1, conv3, conv4_0,
+  // conv4_1, conv5, conv6_0, conv6_1; sp_up: conv7..9; sp_film_t: the 13 t_conv projections stacked (one launch per call).
+  // sp_ws: the stage's own arena (sized and allocated at finalize) -- engine_spatial_time_volume swaps it in for the shared
+  // workspace, so nothing it launches touches memory that a UNet pass on another stream may be using.
+  int use_spatial_volume = 0;                    // mvd_set_spatial_volume
+  int spatial_dims[4] = {64, 128, 256, 512};
+  bool has_spatial = false;
+  ConvW sp_init;
+  SpatialBlockW sp_blocks[10], sp_up[3];
+  LinW sp_film_t;
+  int sp_film_total = 0, sp_film_off[13] = {0};
+  Workspace sp_ws;
 
   // training (engine_train.hip).  With train_mode set before finalize the uploaded fp32 tensors of the hot path
   // (model.diffusion_model.* | spatial_volume.* | time_embed.*) are kept as the MASTER parameters in one flat arena (sorted by
@@ -540,6 +557,12 @@ int engine_frustum_multi(mvd_ctx* c, int B, const int* slots, const float* t_emb
                          const int32_t* view_idx_dev, int TN, FrustumOut* out, hipStream_t s, bool half0);
 int engine_frustum_batch(mvd_ctx* c, int B, const int* slots, const float* volumes, const float* t_embed, const float* v_rows,
                          const int32_t* view_idx_dev, FrustumOut* out, hipStream_t s);
+// use_spatial_volume=True: encoder -> dense unprojection -> SpatialTime3DNet for all views of the active slot; adds the result
+// into c->volume; volume_out (optional): the network's own output [64,V,V,V]
+int engine_spatial_time_volume(mvd_ctx* c, const float* x_noisy, const float* t_embed, const float* v_embed, int n_views,
+                               float* volume_out, hipStream_t s);
+int engine_stage_unproject(mvd_ctx* c, const float* feats_nchw, int n_views, float* out, hipStream_t s);
+size_t engine_spatial_arena_bytes(const mvd_ctx* c);
 
 // helpers shared by the executors
 struct GemmArgs {

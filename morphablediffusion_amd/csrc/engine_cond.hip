@@ -812,3 +812,140 @@ int engine_frustum_batch(mvd_ctx* c, int B, const int* slots, const float* volum
   const int r2 = engine_select_sample(c, back);
   return r ? r : r2;
 }
+
+// ----------------------------------------------------------------------------------------------------
+// use_spatial_volume=True (morphable_diffusion.py:197-225, 259-261): the SyncDreamer-style dense volume.  The 2-D encoder maps
+// of ALL views are unprojected onto the V^3 lattice (k_cond.hip: unproject_views_kernel) into the channels-last fp16 operand
+// [V^3][16 N] of SpatialTime3DNet (network.py:235-283), a U-shaped 3-D network of the frustum network's make -- GroupNorm(8) +
+// SiLU with the per-block t_conv(t) row folded in, run_conv3d / run_convT3d, the skip sums conv4 +, conv2 +, conv0 + through the
+// transposed convs' residual epilogues -- whose [V^3][64] output is added into the mesh volume.
+namespace {
+// level sizes of the network on a V^3 lattice (V % 8 == 0: V, V/2, V/4, V/8)
+inline size_t sp_vox(int V, int l) {
+  const size_t e = (size_t)(V >> l);
+  return e * e * e;
+}
+inline size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// The stage's intermediates live in c->sp_ws; while the guard is alive that arena stands in for the shared workspace, so the
+// scratch that run_conv3d / run_group_norm / the layered encoder take (split-K slabs, GroupNorm partials) comes from it too.
+struct ArenaSwap {
+  mvd_ctx* c;
+  explicit ArenaSwap(mvd_ctx* c_) : c(c_) {
+    std::swap(c->ws, c->sp_ws);
+    c->ws.off = 0;
+    c->ws.hold = 0;
+  }
+  ~ArenaSwap() { std::swap(c->ws, c->sp_ws); }
+  ArenaSwap(const ArenaSwap&) = delete;
+  ArenaSwap& operator=(const ArenaSwap&) = delete;
+};
+}  // namespace
+
+// Bytes of the arena: every buffer engine_spatial_time_volume allocates (each rounded to the allocator's 256 bytes), the layered
+// encoder's buffers (the one-launch encoder needs none), and room for the convolutions' split-K slabs -- at most 16 slabs of a
+// level-1 output or 4 of a level-0 output, whichever is larger -- plus the GroupNorm partials.
+size_t engine_spatial_arena_bytes(const mvd_ctx* c) {
+  const int V = c->v.spatial_volume_size, N = c->v.num_views, S = c->u.image_size;
+  const int* d = c->spatial_dims;
+  size_t b = 0;
+  b += up256((size_t)N * S * S * 16 * 4);                           // feats
+  b += up256((size_t)N * 48 * 4);                                   // encoder FiLM rows
+  b += up256((size_t)N * S * S * (8 + 16 * 3) * 4) + up256((size_t)N * S * S * 16 * 2) + 5 * 256;  // layered encoder
+  b += up256(sp_vox(V, 0) * 16 * N * 2);                            // unprojected operand
+  b += 2 * up256(sp_vox(V, 0) * d[0] * 4);                          // init_conv output, conv0
+  for (int l = 1; l < 4; ++l) b += 3 * up256(sp_vox(V, l) * d[l] * 4);
+  size_t amax = 0, omax = 0;
+  for (int l = 0; l < 4; ++l) amax = std::max(amax, sp_vox(V, l) * d[l]);
+  b += up256(amax * 2);                                             // GroupNorm output (the conv operand)
+  b += up256((size_t)c->sp_film_total * 4);
+  omax = std::max(4 * sp_vox(V, 0) * d[0], 16 * sp_vox(V, 1) * d[1]);
+  b += up256(omax * 4) + ((size_t)4 << 20);
+  return b;
+}
+
+int engine_stage_unproject(mvd_ctx* c, const float* feats_nchw, int n_views, float* out, hipStream_t s) {
+  if (!c->use_spatial_volume) return mvd_fail("mvd_stage_unproject: use_spatial_volume is off (mvd_set_spatial_volume)");
+  if (!c->finalized || !c->has_spatial) return mvd_fail("mvd_stage_unproject: spatial_volume_feats weights not uploaded / finalized");
+  if (!c->cams) return mvd_fail("mvd_stage_unproject: mvd_set_cameras must be called first");
+  if (n_views != c->v.num_views || c->n_cams < n_views) return mvd_fail("mvd_stage_unproject: expects the maps of all num_views views (and as many cameras)");
+  ArenaSwap swap(c);
+  const int V = c->v.spatial_volume_size, S = c->u.image_size, N = n_views;
+  float* feats = ws_alloc<float>(c, (size_t)N * S * S * 16);
+  half_t* vol = ws_alloc<half_t>(c, sp_vox(V, 0) * 16 * N);
+  WS_CHECK(feats && vol);
+  RET_IF(launch_nchw_to_nhwc(feats_nchw, N, 16, S * S, feats, 16, 16, s));
+  RET_IF(launch_unproject_views(feats, c->cams, N, V, c->v.spatial_volume_length, S, c->v.projection == 0, vol, s));
+  return launch_rows_f16_to_nchw(vol, (long)sp_vox(V, 0), 16 * N, out, s);
+}
+
+int engine_spatial_time_volume(mvd_ctx* c, const float* x_noisy, const float* t_embed, const float* v_embed, int n_views,
+                               float* volume_out, hipStream_t s) {
+  if (!c->use_spatial_volume) return mvd_fail("mvd_spatial_time_volume: use_spatial_volume is off (mvd_set_spatial_volume)");
+  if (!c->finalized || !c->has_cond || !c->has_spatial)
+    return mvd_fail("mvd_spatial_time_volume: spatial_volume_feats weights not uploaded / finalized");
+  if (!c->volume || !c->mesh.Nv) return mvd_fail("mvd_spatial_time_volume: mvd_set_mesh must be called first");
+  if (!c->cams) return mvd_fail("mvd_spatial_time_volume: mvd_set_cameras must be called first");
+  if (n_views != c->v.num_views) return mvd_fail("mvd_spatial_time_volume: expects all num_views views of the sample");
+  if (c->n_cams < n_views) return mvd_fail("mvd_spatial_time_volume: fewer cameras set than num_views");
+  // the volume this adds to may have been produced on another stream (mvd_set_volume_ready_event)
+  if (c->vol_ready) HIP_CHECK_RET(hipStreamWaitEvent(s, c->vol_ready, 0));
+  ArenaSwap swap(c);
+  const int V = c->v.spatial_volume_size, S = c->u.image_size, N = n_views, td = c->v.time_dim;
+  const int* d = c->spatial_dims;
+  const int FT = c->sp_film_total;
+  int E[4];
+  for (int l = 0; l < 4; ++l) E[l] = V >> l;
+  float* feats = ws_alloc<float>(c, (size_t)N * S * S * 16);
+  float* enc_pre = ws_alloc<float>(c, (size_t)N * 48);
+  half_t* vol = ws_alloc<half_t>(c, sp_vox(V, 0) * 16 * N);
+  float* h0 = ws_alloc<float>(c, sp_vox(V, 0) * d[0]);
+  float* skip[4] = {ws_alloc<float>(c, sp_vox(V, 0) * d[0]), nullptr, nullptr, nullptr};  // conv0, conv2, conv4, conv6_1
+  float *ta[4] = {nullptr, nullptr, nullptr, nullptr}, *tb[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int l = 1; l < 4; ++l) {
+    ta[l] = ws_alloc<float>(c, sp_vox(V, l) * d[l]);
+    tb[l] = ws_alloc<float>(c, sp_vox(V, l) * d[l]);
+    skip[l] = ws_alloc<float>(c, sp_vox(V, l) * d[l]);
+    WS_CHECK(ta[l] && tb[l] && skip[l]);
+  }
+  size_t amax = 0;
+  for (int l = 0; l < 4; ++l) amax = std::max(amax, sp_vox(V, l) * d[l]);
+  half_t* a = ws_alloc<half_t>(c, amax);
+  float* pre = ws_alloc<float>(c, (size_t)FT);
+  WS_CHECK(feats && enc_pre && vol && h0 && skip[0] && a && pre);
+  // 2-D encoder of all views (the one-launch form takes its FiLM rows in enc_pre; the layered form allocates from the arena)
+  RET_IF(engine_target_encoder(c, x_noisy, t_embed, v_embed, N, feats, s, engine_encoder_is_fused(c) ? enc_pre : nullptr));
+  RET_IF(launch_unproject_views(feats, c->cams, N, V, c->v.spatial_volume_length, S, c->v.projection == 0, vol, s));
+  // x + t_conv(t) of all 13 blocks in one launch: pre[sp_film_off[i] + c] (there is no view embedding in this network)
+  RET_IF(launch_small_linear(t_embed, td, 1, td, c->sp_film_t.w, c->sp_film_t.bias, FT, ACT_NONE, pre, FT, 0, s));
+  GemmArgs g;
+  g.a = vol; g.lda = 16 * N; g.w = &c->sp_init; g.out = h0; g.ldc = d[0];
+  RET_IF(run_conv3d(c, g, 1, V, V, V, 1, s));
+  // one SpatialTimeBlock: GroupNorm(8) + SiLU of (x + t_conv(t)) -> fp16 operand -> 3x3x3 conv
+  auto block = [&](int i, const float* x, int l_in, int stride, float* out) -> int {
+    const SpatialBlockW& b = c->sp_blocks[i];
+    const int e = E[l_in];
+    RET_IF(run_group_norm(c, x, b.cin, 1, e * e * e, b.gn, 8, 1e-5f, ACT_SILU, pre + c->sp_film_off[i], a, b.cin, s, FT));
+    GemmArgs ga;
+    ga.a = a; ga.lda = b.cin; ga.w = &b.conv; ga.out = out; ga.ldc = b.cout;
+    return run_conv3d(c, ga, 1, e, e, e, stride, s);
+  };
+  RET_IF(block(0, h0, 0, 1, skip[0]));  // conv0
+  for (int l = 1; l < 4; ++l) {         // conv{1,3,5} stride 2, then two stride-1 blocks; the last one is the level's skip
+    RET_IF(block(3 * l - 2, skip[l - 1], l - 1, 2, ta[l]));
+    RET_IF(block(3 * l - 1, ta[l], l, 1, tb[l]));
+    RET_IF(block(3 * l, tb[l], l, 1, skip[l]));
+  }
+  // up path: conv7..9, x_l = skip_l + up(x_{l+1}) in place on skip_l through the residual epilogue
+  for (int l = 2; l >= 0; --l) {
+    const SpatialBlockW& u = c->sp_up[2 - l];
+    const int e = E[l + 1];
+    RET_IF(run_group_norm(c, skip[l + 1], u.cin, 1, e * e * e, u.gn, 8, 1e-5f, ACT_SILU, pre + c->sp_film_off[10 + (2 - l)], a, u.cin, s, FT));
+    GemmArgs ga;
+    ga.a = a; ga.lda = u.cin; ga.w = &u.conv; ga.out = skip[l]; ga.ldc = u.cout; ga.resid = skip[l]; ga.ldr = u.cout;
+    RET_IF(run_convT3d(c, ga, 1, e, e, e, s));
+  }
+  // the caller may ask for the network's own output, so the add into the mesh volume is a pass of its own (2 x 8 MB at V = 32)
+  if (volume_out) RET_IF(launch_nhwc_to_nchw(skip[0], d[0], 1, d[0], (int)sp_vox(V, 0), volume_out, s));
+  return launch_accumulate_f32(c->volume, skip[0], sp_vox(V, 0) * 64, s);
+}

@@ -991,6 +991,43 @@ int build_condnet_section(mvd_ctx* c) {
     for (int i = 0; i < 3; ++i) ep.push_back(S + "target_encoder.out_conv" + std::to_string(i) + ".");
     RET_IF(stack(ep, "time_embed", &c->enc_t, c->v.time_dim));
     RET_IF(stack(ep, "view_embed", &c->enc_v, c->v.view_dim));
+    // SpatialTime3DNet (network.py:235-283), only with use_spatial_volume: init_conv, ten SpatialTimeBlocks (norm named "bn"),
+    // three SpatialUpTimeBlocks (norm named "norm"), packed like the frustum network's; the 13 t_conv projections stacked
+    c->has_spatial = false;
+    if (c->use_spatial_volume) {
+      const std::string T = S + "spatial_volume_feats.";
+      RET_IF(pack_conv(c, T + "init_conv.weight", T + "init_conv.bias", false, false, &c->sp_init));
+      if (c->sp_init.Cin != 16 * c->v.num_views || c->sp_init.N != c->spatial_dims[0])
+        return mvd_fail("spatial_volume_feats.init_conv: expected [spatial_dims[0], 16 * num_views, 3, 3, 3]");
+      const char* names[13] = {"conv0", "conv1", "conv2_0", "conv2_1", "conv3", "conv4_0", "conv4_1", "conv5", "conv6_0", "conv6_1",
+                               "conv7", "conv8", "conv9"};
+      std::vector<std::string> sp;
+      int soff = 0;
+      for (int i = 0; i < 13; ++i) {
+        const std::string p = T + names[i] + ".";
+        SpatialBlockW& b = i < 10 ? c->sp_blocks[i] : c->sp_up[i - 10];
+        RET_IF(load_norm(c, p + (i < 10 ? "bn" : "norm"), &b.gn));
+        RET_IF(pack_conv(c, p + "conv.weight", p + "conv.bias", i >= 10, false, &b.conv));
+        b.cin = b.conv.Cin;
+        b.cout = b.conv.N;
+        if (b.conv.taps != 27 || b.gn.C != b.cin) return mvd_fail("spatial_volume_feats: a block's conv / norm has an unexpected shape");
+        sp.push_back(p);
+        c->sp_film_off[i] = soff;
+        soff += b.cin;
+      }
+      c->sp_film_total = soff;
+      RET_IF(stack(sp, "t_conv", &c->sp_film_t, c->v.time_dim));
+      {  // the widths must chain as dims = spatial_dims does (a checkpoint trained with other dims is a config error)
+        const int* d = c->spatial_dims;
+        const int want[13][2] = {{d[0], d[0]}, {d[0], d[1]}, {d[1], d[1]}, {d[1], d[1]}, {d[1], d[2]}, {d[2], d[2]}, {d[2], d[2]},
+                                 {d[2], d[3]}, {d[3], d[3]}, {d[3], d[3]}, {d[3], d[2]}, {d[2], d[1]}, {d[1], d[0]}};
+        for (int i = 0; i < 13; ++i) {
+          const SpatialBlockW& b = i < 10 ? c->sp_blocks[i] : c->sp_up[i - 10];
+          if (b.cin != want[i][0] || b.cout != want[i][1]) return mvd_fail("spatial_volume_feats: channel widths do not match spatial_dims");
+        }
+      }
+      c->has_spatial = true;
+    }
   }
   return 0;
 }
@@ -1052,6 +1089,11 @@ int engine_finalize(mvd_ctx* c) {
     it = c->raw.erase(it);
   }
   if (c->has_unet) RET_IF(engine_side_init(c));  // side stream + events now, so that nothing is created on the step path
+  if (c->has_spatial && !c->sp_ws.base) {  // the SpatialTime3DNet stage's own arena: nothing is allocated on the step path
+    const size_t bytes = engine_spatial_arena_bytes(c);
+    if (hipMalloc((void**)&c->sp_ws.base, bytes) != hipSuccess) return mvd_fail("finalize: spatial-volume arena allocation failed");
+    c->sp_ws.size = bytes;
+  }
   c->finalized = true;
   return 0;
 }

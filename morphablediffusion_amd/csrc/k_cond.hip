@@ -6,6 +6,7 @@
 //                   eval BatchNorm + ReLU folded (network.py:74-161)
 //   latent_gather   trilinear sample of the sparse CNN output at the 32^3 lattice (:232-257)
 //   frustum_gather  trilinear sample of the fused volume along each target view's frustum (:302-315)
+//   unproject_views the dense unprojection itself (use_spatial_volume=True only): the SpatialTime3DNet's input operand
 #include "common.h"
 
 namespace {
@@ -496,7 +497,123 @@ __global__ __launch_bounds__(256) void frustum_gather_kernel(const float* __rest
   *(h4*)(out + pt * C + cq) = o;
 }
 
+// Dense multi-view unprojection (morphable_diffusion.py:197-225, use_spatial_volume=True): every voxel of the V^3 lattice is
+// projected into each of the N views' [S][S][16] feature maps and sampled bilinearly (grid_sample: zeros padding,
+// align_corners=True).  One thread per (voxel, view), the view index fastest: the 256 threads of a workgroup own a run of
+// 256 / N voxels (N need not divide 256: the run then straddles workgroups) and together write one contiguous piece of the
+// channels-last fp16 operand out[V^3][16 N] -- 32 bytes per thread as two 16-byte stores.  The feature maps (64 KB per view at
+// S = 32 in fp32, 1 MB at 16 views) stay L2-resident: a tap is one 64-byte row, and neighbouring voxels of a run share taps.
+// Same projection arithmetic, in the same order, as vertex_gather_kernel above.
+__global__ __launch_bounds__(256) void unproject_views_kernel(const float* __restrict__ feats, const ViewCam* __restrict__ cams,
+                                                              int N, int V, float vol_len, int S, int persp, half_t* __restrict__ out) {
+  const long total = (long)V * V * V * N;
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int view = (int)(idx % N);
+  const int pt = (int)(idx / N);
+  const int ix = pt % V, iy = (pt / V) % V, iz = pt / (V * V);
+  const float* P = cams[view].P;
+  const float X = linspace_at(-vol_len, vol_len, V, ix), Y = linspace_at(-vol_len, vol_len, V, iy),
+              Z = linspace_at(-vol_len, vol_len, V, iz);
+  const float u = P[0] * X + P[1] * Y + P[2] * Z + P[3];
+  const float v = P[4] * X + P[5] * Y + P[6] * Z + P[7];
+  float px, py;
+  if (persp) {
+    float w = P[8] * X + P[9] * Y + P[10] * Z + P[11];
+    w = w < 1e-4f ? 1e-4f : w;
+    const float hs = (float)(S - 1) * 0.5f;
+    px = ((u / w) / hs - 1.0f + 1.0f) * 0.5f * (float)(S - 1);
+    py = ((v / w) / hs - 1.0f + 1.0f) * 0.5f * (float)(S - 1);
+  } else {
+    px = (u + 1.0f) * 0.5f * (float)(S - 1);
+    py = (v + 1.0f) * 0.5f * (float)(S - 1);
+  }
+  float acc[16];
+#pragma unroll
+  for (int c = 0; c < 16; ++c) acc[c] = 0.f;
+  // a point far outside the map (or a non-finite projection) has no tap inside: skipped before the float -> int conversion
+  if (px > -1.0f && px < (float)S && py > -1.0f && py < (float)S) {
+    const float fx0 = floorf(px), fy0 = floorf(py);
+    const int x0 = (int)fx0, y0 = (int)fy0;
+    const float tx = px - fx0, ty = py - fy0;
+    const float* fv = feats + (long)view * S * S * 16;
+#pragma unroll
+    for (int tap = 0; tap < 4; ++tap) {
+      const int xx = x0 + (tap & 1), yy = y0 + (tap >> 1);
+      if (xx < 0 || xx > S - 1 || yy < 0 || yy > S - 1) continue;
+      const float w2 = ((tap & 1) ? tx : 1.f - tx) * ((tap >> 1) ? ty : 1.f - ty);
+      const float4* f4 = (const float4*)(fv + ((long)yy * S + xx) * 16);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float4 f = f4[q];
+        acc[q * 4 + 0] += w2 * f.x;
+        acc[q * 4 + 1] += w2 * f.y;
+        acc[q * 4 + 2] += w2 * f.z;
+        acc[q * 4 + 3] += w2 * f.w;
+      }
+    }
+  }
+  h8 o0, o1;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    o0[c] = (half_t)acc[c];
+    o1[c] = (half_t)acc[8 + c];
+  }
+  h8* o = (h8*)(out + idx * 16);  // idx = pt * N + view: row pt, columns 16 view .. 16 view + 15
+  o[0] = o0;
+  o[1] = o1;
+}
+
+// channels-last fp16 [rows][C] -> fp32 [C][rows] (the reference layout of the unprojected volume: the parity probe)
+__global__ void rows_f16_to_nchw_kernel(const half_t* __restrict__ in, long rows, int C, float* __restrict__ out) {
+  const long total = rows * C;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long r = i % rows;
+    const int c = (int)(i / rows);
+    out[i] = (float)in[r * C + c];
+  }
+}
+
+// dst += src (the SpatialTime3DNet output into the mesh volume, both channels-last fp32; n % 4 == 0)
+__global__ void accumulate_f32_kernel(float* __restrict__ dst, const float* __restrict__ src, size_t n4) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    float4 d = ((float4*)dst)[i];
+    const float4 v = ((const float4*)src)[i];
+    d.x += v.x; d.y += v.y; d.z += v.z; d.w += v.w;
+    ((float4*)dst)[i] = d;
+  }
+}
+
 }  // namespace
+
+int launch_accumulate_f32(float* dst, const float* src, size_t n, hipStream_t s) {
+  if (n & 3) return mvd_fail("accumulate_f32: n must be a multiple of 4");
+  const size_t n4 = n / 4;
+  const int blocks = (int)((n4 + 255) / 256 > 4096 ? 4096 : (n4 + 255) / 256);
+  if (!blocks) return 0;
+  hipLaunchKernelGGL(accumulate_f32_kernel, dim3(blocks), dim3(256), 0, s, dst, src, n4);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+
+// feats [N][S*S][16] fp32 (channels-last encoder output), cams [N] -> out [V^3][16 N] fp16
+int launch_unproject_views(const float* feats, const ViewCam* cams, int N, int V, float vol_len, int S, int persp, half_t* out,
+                           hipStream_t s) {
+  if (N <= 0 || V < 2 || S < 2) return mvd_fail("unproject_views: needs N >= 1, V >= 2, S >= 2");
+  const long total = (long)V * V * V * N;
+  if ((total + 255) / 256 > 0x7FFFFFFFL) return mvd_fail("unproject_views: lattice too large for one launch");
+  hipLaunchKernelGGL(unproject_views_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, feats, cams, N, V, vol_len, S,
+                     persp, out);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+int launch_rows_f16_to_nchw(const half_t* in, long rows, int C, float* out, hipStream_t s) {
+  const long total = rows * C;
+  const int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+  hipLaunchKernelGGL(rows_f16_to_nchw_kernel, dim3(blocks), dim3(256), 0, s, in, rows, C, out);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
 
 int launch_vertex_gather(const float* feats, const ViewCam* cams, const int* view_idx, int n_views, const float* verts, int Nv, int V,
                          float vol_len, int fsize, int persp, float* out, hipStream_t s) {

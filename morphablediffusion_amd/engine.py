@@ -45,6 +45,7 @@ class Engine:
             raise L.MvdError("no MI355X visible: the denoiser has no CPU path")
         self.lib = L.load()
         ucfg.validate()
+        vcfg.validate()
         self.ucfg, self.vcfg = ucfg, vcfg
         self.device = torch.device(device)
         self._workspace_gb = workspace_gb
@@ -78,6 +79,8 @@ class Engine:
             L.check(self.lib.mvd_create(C.byref(uc), C.byref(vc), self.device.index or 0,
                                         C.c_size_t(int(workspace_gb * (1 << 30))), C.byref(self._ctx)))
         L.check(self.lib.mvd_set_precision_level(self._ctx, self.precision_level))
+        L.check(self.lib.mvd_set_spatial_volume(self._ctx, 1 if vcfg.use_spatial_volume else 0,
+                                                (C.c_int * 4)(*[int(d) for d in vcfg.spatial_dims])))
         L.check(self.lib.mvd_train_enable(self._ctx, 1 if self.train_mode else 0))
         L.check(self.lib.mvd_set_vae_precision(self._ctx, 1 if self.vae_exact else 0))
         self._loaded = False
@@ -356,6 +359,26 @@ class Engine:
         f = _f32(fused, self.device)
         out = torch.empty(*[int(v) for v in shp], device=self.device, dtype=torch.float32)
         L.check(self.lib.mvd_stage_sparse_dense(self._ctx, L.ptr(f), 1 if train else 0, L.ptr(out), shp, _stream()))
+        return out
+
+    def stage_unproject(self, feats):
+        """The dense multi-view unprojection alone (morphable_diffusion.py:197-225): encoder maps [N,16,s,s] of all views of the
+        active sample -> [N*16,V,V,V], view-major as the reference stacks them.  Parity probe (use_spatial_volume=True)."""
+        f = _f32(feats, self.device)
+        V = self.vcfg.spatial_volume_size
+        out = torch.empty(f.shape[0] * 16, V, V, V, device=self.device, dtype=torch.float32)
+        L.check(self.lib.mvd_stage_unproject(self._ctx, L.ptr(f), f.shape[0], L.ptr(out), _stream()))
+        return out
+
+    def spatial_time_volume(self, x_noisy, t_embed, v_embed, want_output=True):
+        """use_spatial_volume=True: encoder -> unprojection -> SpatialTime3DNet for all views of the active sample; the result
+        is added into the volume the engine holds for that sample (call it after volume_from_fused, on the same stream).
+        Returns the network's own output [64,V,V,V] (before the add) when ``want_output``."""
+        dev = self.device
+        x, te, ve = _f32(x_noisy, dev), _f32(t_embed, dev), _f32(v_embed, dev)
+        V = self.vcfg.spatial_volume_size
+        out = torch.empty(64, V, V, V, device=dev, dtype=torch.float32) if want_output else None
+        L.check(self.lib.mvd_spatial_time_volume(self._ctx, L.ptr(x), L.ptr(te), L.ptr(ve), x.shape[0], L.ptr(out), _stream()))
         return out
 
     def set_volume_ready_event(self, event):

@@ -196,18 +196,20 @@ class UNetWrapper(nn.Module):
 
 
 class SpatialVolumeNet(nn.Module):
-    """morphable_diffusion.py:151-320, use_spatial_volume=False (both shipped configs)."""
+    """morphable_diffusion.py:151-320.  ``use_spatial_volume=True`` (off in both shipped configs) adds the dense
+    SpatialTime3DNet volume of all views' unprojected encoder maps to the mesh volume (:161-162, :197-225, :259-261)."""
 
     def __init__(self, time_dim, view_dim, view_num, input_image_size=256, frustum_volume_depth=48,
                  spatial_volume_size=32, spatial_volume_length=0.5, frustum_volume_length=0.86603,
                  projection="perspective", use_spatial_volume=False):
         super().__init__()
-        if use_spatial_volume:
-            raise NotImplementedError("use_spatial_volume=True (SpatialTime3DNet) is not used by any shipped config")
+        self.use_spatial_volume = bool(use_spatial_volume)
         self.cfg = VolumeConfig(time_dim=time_dim, view_dim=view_dim, num_views=view_num,
                                 input_image_size=input_image_size, frustum_volume_depth=frustum_volume_depth,
                                 spatial_volume_size=spatial_volume_size, spatial_volume_length=spatial_volume_length,
-                                frustum_volume_length=frustum_volume_length, projection=projection)
+                                frustum_volume_length=frustum_volume_length, projection=projection,
+                                use_spatial_volume=self.use_spatial_volume)
+        self.cfg.validate()
         self.frustum_volume_size = input_image_size // 8
         self.frustum_volume_depth = frustum_volume_depth
         self.spatial_volume_size = spatial_volume_size
@@ -284,7 +286,10 @@ class SpatialVolumeNet(nn.Module):
         for bi in range(B):
             self._set_sample(batch, bi)
             fused = self._engine.vertex_features(x[bi], t_embed[bi], v_embed[bi], torch.arange(N))
-            vols.append(self._engine.volume_from_fused(fused, train=self.training))
+            vol = self._engine.volume_from_fused(fused, train=self.training)
+            if self.use_spatial_volume:  # volume_feats += spatial_volume_feats(...) (:259-261); the engine's copy gets the same add
+                vol = vol + self._engine.spatial_time_volume(x[bi], t_embed[bi], v_embed[bi])
+            vols.append(vol)
         return torch.stack(vols)
 
     def construct_view_frustum_volume(self, spatial_volume, t_embed, v_embed, target_indices, batch):
@@ -328,6 +333,9 @@ class SyncMultiviewDiffusion(nn.Module):
         (fp16 operands: decoded images within 0.8 of an 8-bit step of the reference's)."""
         if first_stage_precision not in ("fast", "exact"):
             raise ValueError("first_stage_precision must be 'fast' or 'exact'")
+        if use_spatial_volume and train_mode:
+            raise NotImplementedError("train_mode=True with use_spatial_volume=True: SpatialTime3DNet has no backward pass in the "
+                                      "engine (a forward-only training_step(..., backward=False) works without train_mode)")
         super().__init__()
         self.finetune_unet = finetune_unet
         self.scheduler_config = scheduler_config
@@ -963,6 +971,9 @@ class SyncDDIMSampler:
         """What every sampler over this engine shares: view sharding, the exchange, batching of B > 1, persistent buffers."""
         self.latent_size = latent_size
         self.shard_views = shard_views
+        if shard_views and self._spatial_on():
+            raise NotImplementedError("shard_views=True with use_spatial_volume=True: SpatialTime3DNet reads the encoder maps of ALL "
+                                      "views on every rank, a second per-step collective that is not built")
         if exchange not in ("all_gather", "all_reduce"):
             raise ValueError(f"unknown exchange {exchange!r}")
         self.exchange = exchange
@@ -974,6 +985,9 @@ class SyncDDIMSampler:
         self.simulate_world = 0  # timing aid (bench.py --simulate-gpus): run ONE rank's share without a process group
         self._comm = None  # (stream, event after the vertex features, event after the volume), created on first use
         self._bufs = {}    # persistent exchange buffers: never handed back to the allocator while the side stream uses them
+
+    def _spatial_on(self):
+        return bool(getattr(getattr(self.model, "spatial_volume", None), "use_spatial_volume", False))
 
     # -- distributed helpers -------------------------------------------------------------------------
     def _world(self):
@@ -1137,6 +1151,14 @@ class SyncDDIMSampler:
         if real:  # under a launcher the designed path is the library's communicator (falls back to c10d, logged)
             ensure_library_comm(eng, dev)
         side = self.overlap and dev.type == "cuda"
+        spatial = self._spatial_on()
+        if spatial:
+            if world > 1:
+                raise NotImplementedError("shard_views=True with use_spatial_volume=True: SpatialTime3DNet needs every view's "
+                                          "encoder map on every rank")
+            # The dense-volume stage adds into the volume that volume_from_fused leaves, and the frustum stage reads the sum: the
+            # whole tail stays on the caller's stream, in that order, as with overlap=False
+            side = False
         # nn.Module semantics, as in the reference: in train mode the sparse CNN's BatchNorm layers use batch statistics
         # (construct_spatial_volume, morphable_diffusion.py:253-254); callers that sample call .eval() (generate_face.py:77)
         bn_train = bool(getattr(self.model.spatial_volume, "training", False))
@@ -1196,6 +1218,8 @@ class SyncDDIMSampler:
             if dev.type == "cuda":
                 eng.set_volume_ready_event(None)
             tail()
+            if spatial:  # + SpatialTime3DNet(unprojected encoder maps of all views), into the active slot's volume
+                eng.spatial_time_volume(x_local, t_embed, v_embed_local, want_output=False)
             return
         comm, ev_in, ev_vol = self._comm
         ev_in.record(torch.cuda.current_stream(dev))

@@ -225,10 +225,58 @@ class VolumeConfig:
     projection: str = "perspective"
     frustum_dims: Tuple[int, int, int, int] = (64, 128, 256, 512)
     voxel_size: float = 0.005  # hard-coded at morphable_diffusion.py:239 and generate_face.py:221
+    # SpatialVolumeNet(use_spatial_volume=True): the dense SpatialTime3DNet volume added to the mesh volume
+    # (morphable_diffusion.py:161-162,259-261); the reference hard-wires its widths to (64, 128, 256, 512)
+    use_spatial_volume: bool = False
+    spatial_dims: Tuple[int, int, int, int] = (64, 128, 256, 512)
 
     @property
     def frustum_volume_size(self):
         return self.input_image_size // 8
+
+    def validate(self):
+        """The constraints the engine checks in mvd_set_spatial_volume; they bind only when the switch is on."""
+        if not self.use_spatial_volume:
+            return
+        if len(self.spatial_dims) != 4:
+            raise ValueError("spatial_dims must have four entries")
+        if self.spatial_dims[0] != 64:
+            raise ValueError("spatial_dims[0] must be 64: the network's output is added to the 64-channel volume")
+        if any(int(d) <= 0 or int(d) % 8 for d in self.spatial_dims):
+            raise ValueError("every spatial_dims entry must be a positive multiple of 8 (GroupNorm(8))")
+        if self.spatial_volume_size <= 0 or self.spatial_volume_size % 8:
+            raise ValueError("use_spatial_volume needs spatial_volume_size % 8 == 0 (three stride-2 levels)")
+
+
+SPATIAL_TIME_BLOCKS = ("conv0", "conv1", "conv2_0", "conv2_1", "conv3", "conv4_0", "conv4_1", "conv5", "conv6_0", "conv6_1")
+
+
+def spatial_time_manifest(cfg: VolumeConfig) -> Dict[str, Tuple[int, ...]]:
+    """SpatialTime3DNet(input_dim=16 * view_num, time_dim, dims) (network.py:235-283), keys below ``spatial_volume.``."""
+    td, d = cfg.time_dim, cfg.spatial_dims
+    ks: Dict[str, Tuple[int, ...]] = {}
+    sv = "spatial_volume_feats."
+    ks[sv + "init_conv.weight"] = (d[0], 16 * cfg.num_views, 3, 3, 3)
+    ks[sv + "init_conv.bias"] = (d[0],)
+    io = [(d[0], d[0]), (d[0], d[1]), (d[1], d[1]), (d[1], d[1]), (d[1], d[2]), (d[2], d[2]), (d[2], d[2]),
+          (d[2], d[3]), (d[3], d[3]), (d[3], d[3])]
+    for name, (ci, co) in zip(SPATIAL_TIME_BLOCKS, io):
+        p = f"{sv}{name}."
+        ks[p + "t_conv.weight"] = (ci, td, 1, 1, 1)
+        ks[p + "t_conv.bias"] = (ci,)
+        ks[p + "bn.weight"] = (ci,)
+        ks[p + "bn.bias"] = (ci,)
+        ks[p + "conv.weight"] = (co, ci, 3, 3, 3)
+        ks[p + "conv.bias"] = (co,)
+    for name, (ci, co) in zip(("conv7", "conv8", "conv9"), [(d[3], d[2]), (d[2], d[1]), (d[1], d[0])]):
+        p = f"{sv}{name}."
+        ks[p + "t_conv.weight"] = (ci, td, 1, 1, 1)
+        ks[p + "t_conv.bias"] = (ci,)
+        ks[p + "norm.weight"] = (ci,)
+        ks[p + "norm.bias"] = (ci,)
+        ks[p + "conv.weight"] = (ci, co, 3, 3, 3)  # ConvTranspose3d: (in, out, k, k, k)
+        ks[p + "conv.bias"] = (co,)
+    return ks
 
 
 def volume_manifest(cfg: VolumeConfig, prefix: str = SV_PREFIX) -> Dict[str, Tuple[int, ...]]:
@@ -291,6 +339,8 @@ def volume_manifest(cfg: VolumeConfig, prefix: str = SV_PREFIX) -> Dict[str, Tup
         ks[p + "norm.bias"] = (ci,)
         ks[p + "conv.weight"] = (ci, co, 3, 3, 3)  # ConvTranspose3d: (in, out, k, k, k)
         ks[p + "conv.bias"] = (co,)
+    if cfg.use_spatial_volume:
+        ks.update(spatial_time_manifest(cfg))
     return {prefix + k: v for k, v in ks.items()}
 
 

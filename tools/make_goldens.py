@@ -518,6 +518,43 @@ def gold_variants_full(ns, which=("n8", "lat64_n1", "smplx_n32")):
                   radii=(0.18, 0.45, 0.12))
 
 
+def gold_spatial_time(ns):
+    """use_spatial_volume=True: the reference's SpatialVolumeNet with the switch on, at a small lattice (V = 8, four views of a
+    16 x 16 latent), one perspective and one orthographic case.  Stored: the unprojected volume (:197-225), the SpatialTime3DNet
+    output (:260) and the final construct_spatial_volume result; inputs and weights are regenerated from the stored seeds."""
+    from tests.test_spatial_volume_cpu import spatial_time_inputs, stage_batch
+    packs, extra = {}, {}
+    for case, projection, seed, style in (("persp", "perspective", gi.WEIGHT_SEED, "init"),
+                                          ("ortho", "orthographic", gi.TRAINED_SEED, "trained")):
+        N, V, S, nverts, input_seed = 4, 8, 16, 300, 41
+        vcfg = VolumeConfig(num_views=N, projection=projection, input_image_size=8 * S, spatial_volume_size=V,
+                            use_spatial_volume=True)
+        sv = ns.md.SpatialVolumeNet(vcfg.time_dim, vcfg.view_dim, N, input_image_size=8 * S, spatial_volume_size=V,
+                                    projection=projection, use_spatial_volume=True).eval()
+        sv.smpl_feature_extractor.num_views = N  # gotcha G3
+        from morphablediffusion_amd.spec import volume_manifest
+        from morphablediffusion_amd.weights import seeded_state_dict
+        man = volume_manifest(vcfg)
+        W = seeded_state_dict(man, seed, style)
+        ref = {"spatial_volume." + k: tuple(v.shape) for k, v in sv.state_dict().items() if not k.endswith("num_batches_tracked")}
+        assert ref == {k: tuple(v) for k, v in man.items()}, sorted(set(ref) ^ set(man))[:10]
+        sv.load_state_dict({k[len("spatial_volume."):]: v for k, v in W.items()}, strict=False)
+        batch = stage_batch(N, projection, nverts, 8 * S)
+        x, t_embed, v_embed = spatial_time_inputs(N, S, input_seed)
+        sink = {}
+        hook = sv.spatial_volume_feats.register_forward_hook(
+            lambda mod, inp, out: sink.update(unproj=inp[0].detach().clone(), net=out.detach().clone()))
+        with torch.no_grad():
+            vol = sv.construct_spatial_volume(x, t_embed, v_embed, batch)
+        hook.remove()
+        packs[f"{case}.unproj"] = gi.pack(sink["unproj"])
+        packs[f"{case}.net_out"] = gi.pack(sink["net"])
+        packs[f"{case}.volume"] = gi.pack(vol)
+        extra.update({f"{case}.N": N, f"{case}.V": V, f"{case}.S": S, f"{case}.nverts_in": nverts, f"{case}.input_seed": input_seed,
+                      f"{case}.weight_seed": seed, f"{case}.weight_style": style})
+    save("spatial_time_small.npz", packs, extra)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-full", action="store_true")
@@ -530,6 +567,7 @@ def main():
     ap.add_argument("--only-traj", action="store_true", help="only the multi-step trajectory golden")
     ap.add_argument("--only-trained", action="store_true", help="only the goldens on the trained-like weight set")
     ap.add_argument("--only-cameras", action="store_true", help="only the camera-trajectory golden (ast-extracted from generate_face.py)")
+    ap.add_argument("--only-spatial-time", action="store_true", help="only the use_spatial_volume=True golden (unprojection, SpatialTime3DNet)")
     ap.add_argument("--only-clip", action="store_true", help="only the CLIP image-embedding goldens (needs transformers, not the reference)")
     args = ap.parse_args()
     os.makedirs(OUT, exist_ok=True)
@@ -541,6 +579,9 @@ def main():
         gold_cameras()
         return
     ns = ref_import.import_reference_full()
+    if args.only_spatial_time:
+        gold_spatial_time(ns)
+        return
     if args.only_variants:
         gold_variants(ns)
         return
@@ -578,6 +619,7 @@ def main():
     if not args.skip_full:
         gold_variants_full(ns)
     gold_trained(ns, not args.skip_full)
+    gold_spatial_time(ns)
     with open(os.path.join(OUT, "manifest.json"), "w") as f:
         json.dump({k: list(v) for k, v in sorted(hot.items())}, f)
     # DDIM tables from the reference sampler
