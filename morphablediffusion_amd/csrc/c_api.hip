@@ -12,17 +12,6 @@
 #include "engine.h"
 #include "rowchain.h"
 
-int engine_set_cameras(mvd_ctx* c, const float* K, const float* RT, int N, hipStream_t s);
-int engine_set_mesh(mvd_ctx* c, const float* vertices, const int32_t* coord, const int32_t* out_sh, const float* bounds,
-                    int Nv, hipStream_t s);
-int engine_select_sample(mvd_ctx* c, int slot);
-int engine_set_samples(mvd_ctx* c, int B, const int* slots, const float* const* vertices, const int32_t* const* coord,
-                       const int32_t* const* out_sh, const float* const* bounds, const int* Nv, const float* const* K,
-                       const float* const* RT, int N, hipStream_t s);
-int engine_rulebook_build(const int32_t* coord, const int32_t* out_sh, int Nv, int force_hash, int32_t* n_sites, int64_t* lens);
-int engine_rulebook_table(int which, int32_t* out);
-void mesh_free(MeshTables& m);
-
 static thread_local std::string g_err;
 int mvd_fail(const char* msg) {
   g_err = msg ? msg : "unknown error";
@@ -94,24 +83,6 @@ inline int nblk(size_t n) { size_t g = (n + 255) / 256; return (int)(g > 4096 ? 
 
 }  // namespace
 
-int bwd_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, float wd, int step,
-              float inv_scale, const int* skip, hipStream_t s);
-int bwd_finite_check(const float* g, size_t n, int* flag, hipStream_t s);
-
-int bwd_attention(const half_t* qkv, int ld3, const half_t* o, const half_t* dO, int ldo, half_t* dqkv, int ldd, float* lse, float* delta,
-                  int B, int T, int heads, int d, hipStream_t s);
-int bwd_group_norm(const float* x, long ld, const float* pre, int pld, const float* dy, long ldy, int B, int rows, int C, int G,
-                   const float* gamma, const float* beta, float eps, int act, float* dx, long lddx, int accum, float* dg_part,
-                   float* db_part, float* dpre_part, hipStream_t s);
-int bwd_sum_rows_add(const float* part, int R, int C, long ldp, float* out, int accum, hipStream_t s);
-int bwd_gn_slabs(int B, int G, int rows);
-int bwd_group_norm_slab(const float* x, long ld, const float* pre, int pld, const float* dy, long ldy, int B, int rows, int C, int G,
-                        const float* gamma, const float* beta, float eps, int act, float* dx, long lddx, int accum, float* part,
-                        float* part2, float* dg_part, float* db_part, float* dpre_part, int S, hipStream_t s);
-int bwd_ln_max_blocks();
-int bwd_layer_norm(const float* x, long ld, const float* dy, long ldy, int rows, int C, const float* gamma, float eps, float* dx,
-                   long lddx, int accum, float* part, int* nblk, hipStream_t s);
-int bwd_cast_rows(const float* src, long ld, long rows, int C, int Cp, half_t* dst, hipStream_t s, int split = 0);
 extern "C" {
 
 const char* mvd_last_error(void) { return g_err.c_str(); }

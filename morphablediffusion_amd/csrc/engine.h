@@ -532,6 +532,17 @@ int engine_train_step(mvd_ctx* c, const float* x_nhwc, int x_ld, const int64_t* 
                       const Ctx5 src[4], const float* target_nhwc, float loss_scale, int recompute, float* pred_nhwc, float* loss_out,
                       float* const dsrc[4], hipStream_t s);
 // engine_cond.hip
+// per-sample tables (mvd_set_mesh* / mvd_set_cameras* / mvd_set_samples_async / mvd_select_sample) and the host-only rule book
+int engine_set_cameras(mvd_ctx* c, const float* K, const float* RT, int N, hipStream_t s);
+int engine_set_mesh(mvd_ctx* c, const float* vertices, const int32_t* coord, const int32_t* out_sh, const float* bounds,
+                    int Nv, hipStream_t s);
+int engine_select_sample(mvd_ctx* c, int slot);
+int engine_set_samples(mvd_ctx* c, int B, const int* slots, const float* const* vertices, const int32_t* const* coord,
+                       const int32_t* const* out_sh, const float* const* bounds, const int* Nv, const float* const* K,
+                       const float* const* RT, int N, hipStream_t s);
+int engine_rulebook_build(const int32_t* coord, const int32_t* out_sh, int Nv, int force_hash, int32_t* n_sites, int64_t* lens);
+int engine_rulebook_table(int which, int32_t* out);
+void mesh_free(MeshTables& m);
 int engine_vertex_features(mvd_ctx* c, const float* x_noisy, const float* t_embed, const float* v_embed,
                            const int32_t* view_idx_dev, int n_local, int add_bias, float* fused_out, hipStream_t s,
                            float* vf_out = nullptr);

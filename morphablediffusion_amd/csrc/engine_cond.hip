@@ -413,7 +413,6 @@ int engine_rulebook_table(int which, int32_t* out) {
   return 0;
 }
 
-int engine_select_sample(mvd_ctx* c, int slot);
 // mvd_set_samples_async: the tables of B samples (a training step's new batch) -- the rule books are built on B host threads,
 // then committed slot by slot in the order of stream `s`.  Validation of ALL samples precedes the first commit.
 int engine_set_samples(mvd_ctx* c, int B, const int* slots, const float* const* vertices, const int32_t* const* coord,
@@ -758,7 +757,6 @@ int engine_frustum(mvd_ctx* c, const float* t_embed, const float* v_embed, const
   });
 }
 
-int engine_select_sample(mvd_ctx* c, int slot);
 int engine_frustum_multi(mvd_ctx* c, int B, const int* slots, const float* t_embed, const float* v_embed,
                          const int32_t* view_idx_dev, int TN, FrustumOut* out, hipStream_t s, bool half0) {
   if (!c->finalized || !c->has_cond) return mvd_fail("spatial_volume weights not uploaded / finalized");

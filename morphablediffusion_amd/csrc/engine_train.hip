@@ -23,74 +23,6 @@
 
 #include "engine.h"
 
-// k_bwd.hip
-int bwd_tcast(const void* src, int src_f32, long ld, int R, int C, half_t* dst, int Rp, hipStream_t s, int split = 0, half_t* rows16 = nullptr,
-              int Cp = 0);
-int bwd_im2colT(const void* src, int src_f32, long ld, int B, int H, int W, int C, int stride, int ups, half_t* dst, int Rp, hipStream_t s);
-int bwd_cast_rows(const float* src, long ld, long rows, int C, int Cp, half_t* dst, hipStream_t s, int split = 0);
-int bwd_pack_dgrad(const half_t* w, int taps, int N, int ldw, int Cl, int Np, half_t* wT, hipStream_t s, int flip = 1);
-int bwd_group_norm(const float* x, long ld, const float* pre, int pld, const float* dy, long ldy, int B, int rows, int C, int G,
-                   const float* gamma, const float* beta, float eps, int act, float* dx, long lddx, int accum, float* dg_part,
-                   float* db_part, float* dpre_part, hipStream_t s);
-int bwd_sum_rows_add(const float* part, int R, int C, long ldp, float* out, int accum, hipStream_t s);
-int bwd_sum_rows_multi(int n, const float* const* part, const int* R, const int* C, const long* ldp, float* const* out, const int* accum,
-                       hipStream_t s);
-int bwd_gn_slabs(int B, int G, int rows);
-int bwd_group_norm_fwd(const float* x, long ld, int B, int rows, int C, int G, const float* gamma, const float* beta, float eps, int act,
-                       float* y, long ldy, float* part, int S, hipStream_t s);
-int bwd_group_norm_slab(const float* x, long ld, const float* pre, int pld, const float* dy, long ldy, int B, int rows, int C, int G,
-                        const float* gamma, const float* beta, float eps, int act, float* dx, long lddx, int accum, float* part,
-                        float* part2, float* dg_part, float* db_part, float* dpre_part, int S, hipStream_t s);
-int bwd_outer_add(const float* a, long lda, const float* b, long ldb, float* C, int M, int N, int K, hipStream_t s);
-int bwd_colsum_samples(const void* v, int v_f32, long ld, int B, int rows, int C, float* out, long ldo, hipStream_t s);
-int bwd_ln_max_blocks();
-int bwd_layer_norm(const float* x, long ld, const float* dy, long ldy, int rows, int C, const float* gamma, float eps, float* dx,
-                   long lddx, int accum, float* part, int* nblk, hipStream_t s);
-int bwd_geglu(const half_t* pre, const float* dgg, long ldg, long rows, int N, half_t* dpre, hipStream_t s);
-int bwd_geglu_unpermute_add(const float* src, int N, int C, float* dst, hipStream_t s);
-int bwd_add_views(float* out, long ldo, const float* a, long lda, const float* b, long ldb, long rows, int C, int accum, hipStream_t s);
-int bwd_upsample2(const float* dup, int B, int H, int W, int C, float* dx, long lddx, int accum, hipStream_t s);
-int bwd_col2im3(const float* dcol, int B, int H, int W, int C, int stride, float* dx, long lddx, int accum, hipStream_t s);
-int bwd_silu_inplace(float* g, const float* u, size_t n, hipStream_t s);
-int bwd_attention(const half_t* qkv, int ld3, const half_t* o, const half_t* dO, int ldo, half_t* dqkv, int ldd, float* lse, float* delta,
-                  int B, int T, int heads, int d, hipStream_t s);
-int bwd_silu_fwd(const float* u, float* out, size_t n, hipStream_t s);
-// k_cond_bwd.hip
-int cbwd_frustum_scatter(const float* d_out, const ViewCam* cams, const int* view_idx, int TN, int D, int S, int V, float vol_len, int persp,
-                         float* d_vol, hipStream_t s);
-int cbwd_latent_scatter(const float* d_vol, const int* grid, int gd, int gh, int gw, const float* min_xyz, const int* out_sh, float voxel,
-                        int V, float vol_len, float* d_rows, hipStream_t s);
-int cbwd_vertex_scatter(const float* d_out, const ViewCam* cams, const int* view_idx, int n_views, const float* verts, int Nv, int V,
-                        float vol_len, int S, int persp, float* d_feats, hipStream_t s);
-int cbwd_fuse_scratch_floats(int Nv);
-int cbwd_fuse(const float* d_fused, const float* vf, const float* w, int n_views, int Nv, int total_views, float* d_vf, float* dw, float* db,
-              float* part,
-              hipStream_t s);
-int cbwd_bn_scratch_floats(int n, int C);
-int cbwd_bn_rows_relu(const float* xraw, float* dy, int n, int C, const float* gamma, const float* beta, const float* stats,
-                      float* scratch, float* dgamma, float* dbeta, hipStream_t s);
-int cbwd_sparse_wgrad_chunks(int n_out);
-int cbwd_sparse_conv(const float* in, const int* nbr, const float* d_out, int n_out, int Cin, int Cout, const float* w, float* d_in,
-                     float* dw_packed, float* dw_part, hipStream_t s);
-int cbwd_sparse_w_unpack_add(const float* pk, int Cin, int Cout, int layout, float* dst, hipStream_t s);
-int cbwd_sparse_wgrad_mfma(const float* in, const int* nbr, const float* d_out, int n_out, int Cin, int Cout, float* dw_packed,
-                           float* dw_part, hipStream_t s);
-int cbwd_sparse_inverse_table(const int* nbr_down, int n_out, int n_in, int* inv, hipStream_t s);
-int cbwd_sparse_fold_dups(float* d, const int* nbr, int n, int C, hipStream_t s);
-int cbwd_im2colT3d(const void* src, int src_f32, long ld, int B, int D, int H, int W, int C, int stride, half_t* dst, int Rp, hipStream_t s);
-int cbwd_small_linear_bwd(const float* g, long ldg, int rows, int N, const half_t* w, int K, float* out, long ldo, int accum, hipStream_t s);
-// k_train.hip
-int train_im2col3(const float* X, int B, int H, int W, int C, float* col, hipStream_t s);
-int train_col2im3(const float* dcol, int B, int H, int W, int C, float* dX, hipStream_t s);
-int train_perm_w3(const float* src, int N, int C, int to_mat, float* dst, hipStream_t s);
-int train_depth_fwd(const float* q, const float* k, const float* v, int R, int HW, int D, int hn, int hd, float scale, float* attn,
-                    float* z, hipStream_t s);
-int train_depth_bwd(const float* q, const float* k, const float* v, const float* attn, const float* dz, int R, int HW, int D, int hn,
-                    int hd, float scale, float* dq, float* dk, float* dv, hipStream_t s);
-int train_add_inplace(float* a, const float* b, size_t n, hipStream_t s);
-int train_copy_rows(const float* src, int ld, long rows, int C, float* dst, hipStream_t s);
-int train_add_bias_rows(float* x, long rows, int C, const float* bias, hipStream_t s);
-
 // ---------------------------------------------------------------------------------------------------------------------
 // arenas
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1163,8 +1095,6 @@ struct CondSample {
   int sp_nout[9], sp_nin[9];
 };
 }  // namespace
-
-int engine_select_sample(mvd_ctx* c, int slot);
 
 // Backward of the conditioner for B samples whose tables sit in slots[0..B): the per-sample stages (2-D encoder, gathers, sparse
 // CNN: different meshes, cameras, BatchNorm statistics) run sample by sample, the frustum network between them -- the same

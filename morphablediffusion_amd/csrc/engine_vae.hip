@@ -7,9 +7,6 @@
 // rows sum to 1).  Layout: channels-last, residual stream fp32, operand-only tensors fp16 (as in the UNet).
 #include "engine.h"
 
-int bwd_cast_rows(const float* src, long ld, long rows, int C, int Cp, half_t* dst, hipStream_t s, int split);
-int launch_softmax_rows_f32(const float* s, long rows, int cols, float* p, hipStream_t st);
-
 namespace {
 
 // ResnetBlock.forward (model.py:121-141, temb = None): x + conv2(swish(GN(conv1(swish(GN(x))))))

@@ -12,7 +12,7 @@ from .spec import UNetConfig, VolumeConfig
 
 
 def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return torch.cuda.current_stream().cuda_stream
 
 
 def _f32(t, device):
@@ -77,12 +77,12 @@ class Engine:
         self._ctx = C.c_void_p()
         with torch.cuda.device(self.device):
             L.check(self.lib.mvd_create(C.byref(uc), C.byref(vc), self.device.index or 0,
-                                        C.c_size_t(int(workspace_gb * (1 << 30))), C.byref(self._ctx)))
+                                        int(workspace_gb * (1 << 30)), C.byref(self._ctx)))
         L.check(self.lib.mvd_set_precision_level(self._ctx, self.precision_level))
-        L.check(self.lib.mvd_set_spatial_volume(self._ctx, 1 if vcfg.use_spatial_volume else 0,
-                                                (C.c_int * 4)(*[int(d) for d in vcfg.spatial_dims])))
-        L.check(self.lib.mvd_train_enable(self._ctx, 1 if self.train_mode else 0))
-        L.check(self.lib.mvd_set_vae_precision(self._ctx, 1 if self.vae_exact else 0))
+        L.check(self.lib.mvd_set_spatial_volume(self._ctx, bool(vcfg.use_spatial_volume),
+                                                (C.c_int * 4)(*vcfg.spatial_dims)))
+        L.check(self.lib.mvd_train_enable(self._ctx, self.train_mode))
+        L.check(self.lib.mvd_set_vae_precision(self._ctx, self.vae_exact))
         self._loaded = False
         self.flat_params = self.flat_grads = self.flat_m = self.flat_v = None
         self.param_table = {}
@@ -130,8 +130,7 @@ class Engine:
                 continue
             t = v.detach().to(dtype=torch.float32).contiguous()
             shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
-            on_dev = 1 if t.is_cuda else 0
-            L.check(self.lib.mvd_upload_weight(self._ctx, k.encode(), L.ptr(t), shape, t.dim(), on_dev))
+            L.check(self.lib.mvd_upload_weight(self._ctx, k.encode(), L.ptr(t), shape, t.dim(), t.is_cuda))
         L.check(self.lib.mvd_finalize_weights(self._ctx))
         self._loaded = True
         if self.train_mode:
@@ -145,7 +144,7 @@ class Engine:
         """Current value of a resident tensor of a training context (a master parameter or a BatchNorm running statistic)."""
         ref = self._loaded_sd[key]
         out = torch.empty(tuple(ref.shape), device=self.device, dtype=torch.float32)
-        L.check(self.lib.mvd_train_get_tensor(self._ctx, key.encode(), L.ptr(out), C.c_size_t(out.numel()), _stream()))
+        L.check(self.lib.mvd_train_get_tensor(self._ctx, key.encode(), L.ptr(out), out.numel(), _stream()))
         return out
 
     def export_state_dict(self):
@@ -156,7 +155,7 @@ class Engine:
         if not self.train_mode or not self._loaded:
             raise L.MvdError("export_state_dict needs a training context with loaded weights")
         out = collections.OrderedDict()
-        calls = int(self.lib.mvd_train_bn_calls(self._ctx))
+        calls = self.lib.mvd_train_bn_calls(self._ctx)
         for k, v in self._loaded_sd.items():
             if not torch.is_tensor(v):
                 out[k] = v
@@ -223,7 +222,7 @@ class Engine:
     def select_sample(self, slot: int):
         """Makes slot ``slot`` (0..MAX_SAMPLE_SLOTS-1) of per-sample mesh / camera tables the active one; set_mesh /
         set_cameras write into the active slot.  With B > 1 every sample keeps its tables across steps."""
-        L.check(self.lib.mvd_select_sample(self._ctx, int(slot)))
+        L.check(self.lib.mvd_select_sample(self._ctx, slot))
         self._slot = int(slot)
         self.num_vertices = self._slot_nv.get(self._slot, 0)
 
@@ -255,7 +254,7 @@ class Engine:
             raise ValueError("every sample of a batch has the same number of target views")
         arr = lambda ts, ty: (ty * n)(*[C.cast(L.ptr(t), ty) for t in ts])
         fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
-        L.check(self.lib.mvd_set_samples_async(self._ctx, n, (C.c_int * n)(*[int(x) for x in slots]), arr(v, fp), arr(c, ip), arr(o, ip),
+        L.check(self.lib.mvd_set_samples_async(self._ctx, n, (C.c_int * n)(*slots), arr(v, fp), arr(c, ip), arr(o, ip),
                                                arr(b, fp), (C.c_int * n)(*[t.shape[0] for t in v]), arr(k, fp), arr(r, fp),
                                                k[0].shape[0], _stream()))
         for sl, t in zip(slots, v):
@@ -276,7 +275,7 @@ class Engine:
         vi = view_idx.to(device=dev, dtype=torch.int32).contiguous()
         out = torch.empty(self.num_vertices, 16, device=dev, dtype=torch.float32)
         L.check(self.lib.mvd_vertex_features(self._ctx, L.ptr(x), L.ptr(te), L.ptr(ve), L.ptr(vi), x.shape[0],
-                                             1 if add_bias else 0, L.ptr(out), _stream()))
+                                             bool(add_bias), L.ptr(out), _stream()))
         return out
 
     def vertex_view_features(self, x_noisy, t_embed, v_embed, view_idx, out=None):
@@ -319,7 +318,7 @@ class Engine:
             box = [bytes(ident)]
             dist.broadcast_object_list(box, src=0)
             ident = (C.c_char * 128).from_buffer_copy(box[0])
-        L.check(self.lib.mvd_comm_init(self._ctx, C.byref(ident), int(rank), int(world)))
+        L.check(self.lib.mvd_comm_init(self._ctx, C.byref(ident), rank, world))
         self.comm_world = world
 
     def comm_destroy(self):
@@ -335,13 +334,13 @@ class Engine:
     def comm_all_reduce(self, buf):
         """In-place sum all-reduce of a contiguous float32 device tensor on the library's communicator (mvd_comm_all_reduce)."""
         assert buf.is_contiguous() and buf.dtype == torch.float32
-        L.check(self.lib.mvd_comm_all_reduce(self._ctx, L.ptr(buf), C.c_size_t(buf.numel()), _stream()))
+        L.check(self.lib.mvd_comm_all_reduce(self._ctx, L.ptr(buf), buf.numel(), _stream()))
         return buf
 
     def sync_gradients(self, phase, comm_stream):
         """mvd_train_sync_gradients: phase 0 = all buckets of the last train_unet_step on ``comm_stream`` (a torch.cuda.Stream),
         phase 1 = the rest of the arena, the join with the current stream and the 1 / world scale."""
-        L.check(self.lib.mvd_train_sync_gradients(self._ctx, int(phase), C.c_void_p(comm_stream.cuda_stream), _stream()))
+        L.check(self.lib.mvd_train_sync_gradients(self._ctx, phase, comm_stream.cuda_stream, _stream()))
 
     def stage_target_encoder(self, x_noisy, t_embed, v_embed):
         """NoisyTargetViewEncoder alone (network.py:181-207): x_noisy [n,4,s,s], t_embed [time_dim], v_embed [n,view_dim] ->
@@ -358,7 +357,7 @@ class Engine:
         L.check(self.lib.mvd_stage_sparse_dense(self._ctx, None, 0, None, shp, _stream()))
         f = _f32(fused, self.device)
         out = torch.empty(*[int(v) for v in shp], device=self.device, dtype=torch.float32)
-        L.check(self.lib.mvd_stage_sparse_dense(self._ctx, L.ptr(f), 1 if train else 0, L.ptr(out), shp, _stream()))
+        L.check(self.lib.mvd_stage_sparse_dense(self._ctx, L.ptr(f), bool(train), L.ptr(out), shp, _stream()))
         return out
 
     def stage_unproject(self, feats):
@@ -383,8 +382,7 @@ class Engine:
 
     def set_volume_ready_event(self, event):
         """event: torch.cuda.Event recorded after volume_from_fused on another stream (kept alive by the caller), or None."""
-        h = C.c_void_p(0) if event is None else C.c_void_p(event.cuda_event)
-        L.check(self.lib.mvd_set_volume_ready_event(self._ctx, h))
+        L.check(self.lib.mvd_set_volume_ready_event(self._ctx, None if event is None else event.cuda_event))
 
     def volume_from_fused(self, fused, want_output=True, train=False):
         """train: BatchNorm layers of the sparse CNN use batch statistics (the reference's module in train mode)."""
@@ -399,18 +397,18 @@ class Engine:
     def _adopt_arenas(self):
         """The engine's master-parameter and gradient arenas move into torch-owned memory, so that parameters / gradients are
         VIEWS of two flat tensors (one collective for the DDP gradient averaging, torch optimisers work on them too)."""
-        n = int(self.lib.mvd_train_arena_size(self._ctx))
+        n = self.lib.mvd_train_arena_size(self._ctx)
         self.flat_params = torch.empty(n, device=self.device, dtype=torch.float32)
         self.flat_grads = torch.empty(n, device=self.device, dtype=torch.float32)
-        L.check(self.lib.mvd_train_adopt_arena(self._ctx, 0, L.ptr(self.flat_params), C.c_int64(n)))
-        L.check(self.lib.mvd_train_adopt_arena(self._ctx, 1, L.ptr(self.flat_grads), C.c_int64(n)))
+        L.check(self.lib.mvd_train_adopt_arena(self._ctx, 0, L.ptr(self.flat_params), n))
+        L.check(self.lib.mvd_train_adopt_arena(self._ctx, 1, L.ptr(self.flat_grads), n))
         self.flat_m = self.flat_v = None
         self.param_table = {}
         name = C.create_string_buffer(512)
         off, numel, nd = C.c_int64(0), C.c_int64(0), C.c_int(0)
         shape = (C.c_int64 * 8)()
-        for i in range(int(self.lib.mvd_train_param_count(self._ctx))):
-            L.check(self.lib.mvd_train_param_info(self._ctx, i, name, C.c_size_t(len(name)), C.byref(off), C.byref(numel), shape,
+        for i in range(self.lib.mvd_train_param_count(self._ctx)):
+            L.check(self.lib.mvd_train_param_info(self._ctx, i, name, len(name), C.byref(off), C.byref(numel), shape,
                                                   C.byref(nd)))
             self.param_table[name.value.decode()] = (off.value, numel.value, tuple(int(shape[k]) for k in range(nd.value)))
 
@@ -440,8 +438,8 @@ class Engine:
         loss = torch.empty(1, device=dev, dtype=torch.float32)
         dsrc = [torch.empty_like(v) for v in srcs] if want_dsrc else [None] * 4
         L.check(self.lib.mvd_train_unet_step(self._ctx, L.ptr(x), L.ptr(t), L.ptr(ctx), B, L.ptr(srcs[0]), L.ptr(srcs[1]),
-                                             L.ptr(srcs[2]), L.ptr(srcs[3]), depth0, L.ptr(tgt), C.c_float(loss_scale),
-                                             1 if recompute else 0, L.ptr(pred), L.ptr(loss), L.ptr(dsrc[0]), L.ptr(dsrc[1]),
+                                             L.ptr(srcs[2]), L.ptr(srcs[3]), depth0, L.ptr(tgt), loss_scale,
+                                             bool(recompute), L.ptr(pred), L.ptr(loss), L.ptr(dsrc[0]), L.ptr(dsrc[1]),
                                              L.ptr(dsrc[2]), L.ptr(dsrc[3]), _stream()))
         if want_dsrc:
             return pred, loss[0], {s >> lvl: dsrc[lvl] for lvl in range(4)}
@@ -454,7 +452,7 @@ class Engine:
         B, _, H, W = x.shape
         depth0 = context.shape[2] * (self.ucfg.image_size // H)
         dx, dc = torch.empty_like(x), torch.empty_like(context)
-        L.check(self.lib.mvd_train_cond_backward(self._ctx, int(cond_index), L.ptr(x), L.ptr(context), L.ptr(d_out), B, H, W, depth0,
+        L.check(self.lib.mvd_train_cond_backward(self._ctx, cond_index, L.ptr(x), L.ptr(context), L.ptr(d_out), B, H, W, depth0,
                                                  L.ptr(dx), L.ptr(dc), _stream()))
         return dx, dc
 
@@ -471,8 +469,8 @@ class Engine:
             V = self.vcfg.spatial_volume_size
             dbg = [torch.empty(64, V, V, V, device=dev), torch.empty(self.num_vertices, 16, device=dev),
                    torch.empty(x.shape[0], 16, x.shape[2], x.shape[3], device=dev), torch.empty(self.vcfg.time_dim, device=dev)]
-        L.check(self.lib.mvd_train_conditioner_backward(self._ctx, L.ptr(x), C.c_int64(int(timestep)), L.ptr(ve), x.shape[0],
-                                                        int(target_index), L.ptr(ds[0]), L.ptr(ds[1]), L.ptr(ds[2]), L.ptr(ds[3]),
+        L.check(self.lib.mvd_train_conditioner_backward(self._ctx, L.ptr(x), timestep, L.ptr(ve), x.shape[0],
+                                                        target_index, L.ptr(ds[0]), L.ptr(ds[1]), L.ptr(ds[2]), L.ptr(ds[3]),
                                                         L.ptr(dbg[0]), L.ptr(dbg[1]), L.ptr(dbg[2]), L.ptr(dbg[3]), _stream()))
         return dbg if debug else None
 
@@ -487,20 +485,20 @@ class Engine:
         ds = [_f32(dsrc[s >> lvl], dev) for lvl in range(4)]
         assert len(slots) == B == len(timesteps) == len(target_index) and all(d.shape[0] == B for d in ds)
         L.check(self.lib.mvd_train_conditioner_backward_batch(
-            self._ctx, B, (C.c_int * B)(*[int(v) for v in slots]), L.ptr(x), (C.c_int64 * B)(*[int(v) for v in timesteps]), L.ptr(ve),
-            x.shape[1], (C.c_int * B)(*[int(v) for v in target_index]), L.ptr(ds[0]), L.ptr(ds[1]), L.ptr(ds[2]), L.ptr(ds[3]),
+            self._ctx, B, (C.c_int * B)(*slots), L.ptr(x), (C.c_int64 * B)(*timesteps), L.ptr(ve),
+            x.shape[1], (C.c_int * B)(*target_index), L.ptr(ds[0]), L.ptr(ds[1]), L.ptr(ds[2]), L.ptr(ds[3]),
             None, None, None, None, _stream()))
 
     def get_grad(self, key: str, shape):
         out = torch.empty(tuple(shape), device=self.device, dtype=torch.float32)
-        L.check(self.lib.mvd_train_get_grad(self._ctx, key.encode(), L.ptr(out), C.c_size_t(out.numel()), _stream()))
+        L.check(self.lib.mvd_train_get_grad(self._ctx, key.encode(), L.ptr(out), out.numel(), _stream()))
         return out
 
     def grad_buckets(self):
         """Gradient buckets of the last train_unet_step (mvd_train_grad_bucket*): a list, in the order the gradients become final
         during the backward pass, of lists of (offset, length) ranges of ``flat_grads``; together model.diffusion_model.* once."""
         out = []
-        for k in range(int(self.lib.mvd_train_grad_bucket_count(self._ctx))):
+        for k in range(self.lib.mvd_train_grad_bucket_count(self._ctx)):
             n = C.c_int(0)
             L.check(self.lib.mvd_train_grad_bucket(self._ctx, k, 0, None, None, C.byref(n)))
             offs, lens = (C.c_int64 * max(1, n.value))(), (C.c_int64 * max(1, n.value))()
@@ -510,7 +508,7 @@ class Engine:
 
     def grad_bucket_wait(self, k, stream):
         """Makes ``stream`` (a torch.cuda.Stream: the communication stream) wait until bucket k's gradients are final."""
-        L.check(self.lib.mvd_train_grad_bucket_wait(self._ctx, int(k), C.c_void_p(stream.cuda_stream)))
+        L.check(self.lib.mvd_train_grad_bucket_wait(self._ctx, k, stream.cuda_stream))
 
     def set_bucket_snapshot(self, arena):
         """Test hook (mvd_train_set_bucket_snapshot): ``arena`` = a float32 device tensor shaped like ``flat_grads``, or None."""
@@ -523,10 +521,8 @@ class Engine:
         fp16 weights.  Returns True when the update was skipped because a gradient was inf / nan (check=False: not read back)."""
         self.ensure_moments()
         skipped = C.c_int(0)
-        L.check(self.lib.mvd_train_adamw_step(self._ctx, C.c_float(lr), C.c_float(lr_aux), C.c_float(betas[0]),
-                                              C.c_float(betas[1]), C.c_float(eps), C.c_float(weight_decay), int(step),
-                                              C.c_float(inv_scale), 1 if finetune_unet else 0,
-                                              C.byref(skipped) if check else None, _stream()))
+        L.check(self.lib.mvd_train_adamw_step(self._ctx, lr, lr_aux, betas[0], betas[1], eps, weight_decay, step, inv_scale,
+                                              bool(finetune_unet), C.byref(skipped) if check else None, _stream()))
         self.repack()
         return bool(skipped.value)
 
@@ -536,8 +532,8 @@ class Engine:
             self.flat_m = torch.zeros_like(self.flat_params)
             self.flat_v = torch.zeros_like(self.flat_params)
             n = self.flat_params.numel()
-            L.check(self.lib.mvd_train_adopt_arena(self._ctx, 2, L.ptr(self.flat_m), C.c_int64(n)))
-            L.check(self.lib.mvd_train_adopt_arena(self._ctx, 3, L.ptr(self.flat_v), C.c_int64(n)))
+            L.check(self.lib.mvd_train_adopt_arena(self._ctx, 2, L.ptr(self.flat_m), n))
+            L.check(self.lib.mvd_train_adopt_arena(self._ctx, 3, L.ptr(self.flat_v), n))
 
     def repack(self):
         """Re-derive every packed fp16 weight from the master parameters (after they changed), in place, in the order of the
@@ -554,7 +550,7 @@ class Engine:
     def mse_loss(self, a, b):
         a, b = _f32(a, self.device), _f32(b, self.device)
         out = torch.empty(1, device=self.device, dtype=torch.float32)
-        L.check(self.lib.mvd_mse_loss(self._ctx, L.ptr(a), L.ptr(b), C.c_size_t(a.numel()), L.ptr(out), _stream()))
+        L.check(self.lib.mvd_mse_loss(self._ctx, L.ptr(a), L.ptr(b), a.numel(), L.ptr(out), _stream()))
         return out[0]
 
     def frustum_volumes_batch(self, slots, volumes, t_embed, v_rows, view_idx):
@@ -569,7 +565,7 @@ class Engine:
             o = torch.empty(B, self.vcfg.frustum_dims[lvl], Dl, Sl, Sl, device=dev, dtype=torch.float32)
             outs[Sl] = o
             ptrs.append(L.ptr(o))
-        L.check(self.lib.mvd_frustum_volumes_batch(self._ctx, B, (C.c_int * B)(*[int(v) for v in slots]), L.ptr(vol), L.ptr(te), L.ptr(vr),
+        L.check(self.lib.mvd_frustum_volumes_batch(self._ctx, B, (C.c_int * B)(*slots), L.ptr(vol), L.ptr(te), L.ptr(vr),
                                                    L.ptr(vi), *ptrs, _stream()))
         return outs
 
@@ -604,10 +600,8 @@ class Engine:
         nz = None if noise is None else _f32(noise, dev)
         xi, cl, te, ve = _f32(x_input, dev), _f32(clip, dev), _f32(t_embed, dev), _f32(v_embed, dev)
         L.check(self.lib.mvd_denoise_views(
-            self._ctx, L.ptr(x), L.ptr(xi), L.ptr(cl), C.c_int64(int(timestep)),
-            L.ptr(te), L.ptr(ve), L.ptr(vi), TN, C.c_float(cfg_scale), L.ptr(nz),
-            C.c_float(coef[0]), C.c_float(coef[1]), C.c_float(coef[2]), C.c_float(coef[3]), C.c_float(coef[4]),
-            L.ptr(eps), L.ptr(x_prev), _stream()))
+            self._ctx, L.ptr(x), L.ptr(xi), L.ptr(cl), timestep, L.ptr(te), L.ptr(ve), L.ptr(vi), TN, cfg_scale, L.ptr(nz),
+            *coef[:5], L.ptr(eps), L.ptr(x_prev), _stream()))
         if out is not None and x_prev is not out:
             out.copy_(x_prev)
         if want_eps and eps_out is not None and eps is not eps_out:
@@ -627,12 +621,11 @@ class Engine:
         eps = torch.empty_like(x) if want_eps else None
         nz = None if noise is None else _f32(noise, dev)
         xi, cl, te, ve = _f32(x_input, dev), _f32(clip, dev), _f32(t_embed, dev), _f32(v_embed, dev)
-        sl = (C.c_int * B)(*[int(v) for v in slots])
-        ts = (C.c_int64 * B)(*[int(v) for v in timesteps])
+        sl = (C.c_int * B)(*slots)
+        ts = (C.c_int64 * B)(*timesteps)
         L.check(self.lib.mvd_denoise_views_batch(
-            self._ctx, B, sl, L.ptr(x), L.ptr(xi), L.ptr(cl), ts, L.ptr(te), L.ptr(ve), L.ptr(vi), TN, C.c_float(cfg_scale),
-            L.ptr(nz), C.c_float(coef[0]), C.c_float(coef[1]), C.c_float(coef[2]), C.c_float(coef[3]), C.c_float(coef[4]),
-            L.ptr(eps), L.ptr(x_prev), _stream()))
+            self._ctx, B, sl, L.ptr(x), L.ptr(xi), L.ptr(cl), ts, L.ptr(te), L.ptr(ve), L.ptr(vi), TN, cfg_scale,
+            L.ptr(nz), *coef[:5], L.ptr(eps), L.ptr(x_prev), _stream()))
         return (x_prev, eps) if want_eps else x_prev
 
     def denoise_views_ms(self, slots, x_noisy, x_input, clip, timesteps, t_embed, v_embed, view_idx, cfg_scale, noise, coef,
@@ -658,11 +651,11 @@ class Engine:
         eps = (eps_out if direct(eps_out) else torch.empty_like(x)) if want_eps else None
         nz = None if noise is None else _f32(noise, dev)
         xi, cl, te, ve = _f32(x_input, dev), _f32(clip, dev), _f32(t_embed, dev), _f32(v_embed, dev)
-        sl = None if single else (C.c_int * B)(*[int(v) for v in slots])
-        ts = (C.c_int64 * B)(*[int(v) for v in steps])
+        sl = None if single else (C.c_int * B)(*slots)
+        ts = (C.c_int64 * B)(*steps)
         L.check(self.lib.mvd_denoise_views_ms(
-            self._ctx, B, sl, L.ptr(x), L.ptr(xi), L.ptr(cl), ts, L.ptr(te), L.ptr(ve), L.ptr(vi), TN, C.c_float(cfg_scale),
-            L.ptr(nz), *[C.c_float(v) for v in coef], L.ptr(x0_hist), 1 if first else 0, L.ptr(eps), L.ptr(x_next), _stream()))
+            self._ctx, B, sl, L.ptr(x), L.ptr(xi), L.ptr(cl), ts, L.ptr(te), L.ptr(ve), L.ptr(vi), TN, cfg_scale,
+            L.ptr(nz), *coef, L.ptr(x0_hist), bool(first), L.ptr(eps), L.ptr(x_next), _stream()))
         if out is not None and x_next is not out:
             out.copy_(x_next)
         if want_eps and eps_out is not None and eps is not eps_out:
@@ -680,9 +673,8 @@ class Engine:
         assert x0_hist.is_contiguous() and x0_hist.dtype == torch.float32 and x0_hist.numel() == x.numel()
         x_next = torch.empty_like(x)
         eps = torch.empty_like(x) if want_eps else None
-        L.check(self.lib.mvd_op_cfg_ms(L.ptr(ec), L.ptr(eu), C.c_float(scale), L.ptr(x), L.ptr(nz), *[C.c_float(v) for v in coef],
-                                       L.ptr(x0_hist), 1 if first else 0, L.ptr(eps), L.ptr(x_next), C.c_size_t(x.numel()),
-                                       _stream()))
+        L.check(self.lib.mvd_op_cfg_ms(L.ptr(ec), L.ptr(eu), scale, L.ptr(x), L.ptr(nz), *coef, L.ptr(x0_hist), bool(first),
+                                       L.ptr(eps), L.ptr(x_next), x.numel(), _stream()))
         return (x_next, eps) if want_eps else x_next
 
     def op_conv(self, x, w, bias=None, stride=1, upsample=0, resid=None, force_splitk=0):
@@ -711,7 +703,7 @@ class Engine:
         b = None if bias is None else _f32(bias, dev)
         r = None if resid is None else _f32(resid, dev)
         L.check(self.lib.mvd_op_conv3d(self._ctx, L.ptr(x), B, Cin, D, H, W, L.ptr(w), L.ptr(b), Cout, stride,
-                                       1 if transposed else 0, L.ptr(r), L.ptr(out), _stream()))
+                                       bool(transposed), L.ptr(r), L.ptr(out), _stream()))
         return out
 
     def op_linear(self, a, w, bias=None, geglu=False, resid=None, a_half=False, force_splitk=0):
@@ -722,8 +714,8 @@ class Engine:
         out = torch.empty(M, N // 2 if geglu else N, device=dev)
         b = None if bias is None else _f32(bias, dev)
         r = None if resid is None else _f32(resid, dev)
-        L.check(self.lib.mvd_op_linear(self._ctx, L.ptr(a), M, K, L.ptr(w), L.ptr(b), N, 1 if geglu else 0, L.ptr(r),
-                                       1 if a_half else 0, int(force_splitk), L.ptr(out), _stream()))
+        L.check(self.lib.mvd_op_linear(self._ctx, L.ptr(a), M, K, L.ptr(w), L.ptr(b), N, bool(geglu), L.ptr(r),
+                                       bool(a_half), force_splitk, L.ptr(out), _stream()))
         return out
 
     def op_group_norm(self, x, groups, gamma, beta, eps, act=0):
@@ -733,7 +725,7 @@ class Engine:
         HW = x[0, 0].numel()
         out = torch.empty_like(x)
         g, b = _f32(gamma, dev), _f32(beta, dev)  # keep alive across the call
-        L.check(self.lib.mvd_op_group_norm(self._ctx, L.ptr(x), B, Cc, HW, groups, L.ptr(g), L.ptr(b), C.c_float(eps),
+        L.check(self.lib.mvd_op_group_norm(self._ctx, L.ptr(x), B, Cc, HW, groups, L.ptr(g), L.ptr(b), eps,
                                            act, L.ptr(out), _stream()))
         return out
 
@@ -758,9 +750,9 @@ class Engine:
         flags = (1 if ao is not None else 0) | (2 if w_po is not None else 0) | (4 if split else 0) | (8 if xp_out else 0)
         out = torch.empty_like(xin)
         ms = C.c_float(0)
-        L.check(self.lib.mvd_op_st_tail(self._ctx, Cc, rows, int(T or rows), L.ptr(ao_), L.ptr(xin), L.ptr(rb_), L.ptr(wao_), L.ptr(bao_),
+        L.check(self.lib.mvd_op_st_tail(self._ctx, Cc, rows, T or rows, L.ptr(ao_), L.ptr(xin), L.ptr(rb_), L.ptr(wao_), L.ptr(bao_),
                                         L.ptr(g_), L.ptr(b_), L.ptr(w1_), L.ptr(b1_), L.ptr(w2_), L.ptr(b2_), L.ptr(wpo_), L.ptr(bpo_),
-                                        L.ptr(res_), L.ptr(out), flags, int(iters), C.byref(ms), _stream()))
+                                        L.ptr(res_), L.ptr(out), flags, iters, C.byref(ms), _stream()))
         return (out, ms.value) if iters > 0 else out
 
     def op_st_head(self, n0, w_pi, b_pi, ln_g, ln_b, w_q, w_k, w_v, iters=0, xp=False):
@@ -772,7 +764,7 @@ class Engine:
         t0 = torch.empty(rows, Cc, device=dev)
         qkv = torch.empty(rows, 3 * Cc, device=dev)
         ms = C.c_float(0)
-        L.check(self.lib.mvd_op_st_head(self._ctx, rows, 1 if xp else 0, L.ptr(n0), *[L.ptr(t) for t in keep], L.ptr(t0), L.ptr(qkv), int(iters),
+        L.check(self.lib.mvd_op_st_head(self._ctx, rows, bool(xp), L.ptr(n0), *[L.ptr(t) for t in keep], L.ptr(t0), L.ptr(qkv), iters,
                                         C.byref(ms), _stream()))
         return (t0, qkv, ms.value) if iters > 0 else (t0, qkv)
 
@@ -800,7 +792,7 @@ class Engine:
         x, dy, g, b = _f32(x, dev), _f32(dy, dev), _f32(gamma, dev), _f32(beta, dev)
         B, rows, Cc = x.shape
         dx, dg, db = torch.empty_like(x), torch.empty_like(g), torch.empty_like(g)
-        L.check(self.lib.mvd_op_group_norm_bwd(self._ctx, L.ptr(x), L.ptr(dy), B, rows, Cc, groups, L.ptr(g), L.ptr(b), C.c_float(eps),
+        L.check(self.lib.mvd_op_group_norm_bwd(self._ctx, L.ptr(x), L.ptr(dy), B, rows, Cc, groups, L.ptr(g), L.ptr(b), eps,
                                                act, L.ptr(dx), L.ptr(dg), L.ptr(db), _stream()))
         return dx, dg, db
 
@@ -835,8 +827,8 @@ class Engine:
             dx.copy_(self._pad_last(accum[0].permute(0, 2, 3, 1), cp))
             dW.copy_(accum[1].reshape(Cout, -1))
             db.copy_(accum[2])
-        L.check(self.lib.mvd_op_conv_bwd(self._ctx, int(kind), int(k), B, Cin, H, W, Cout, L.ptr(xn), 1 if x_half else 0, L.ptr(ww), L.ptr(dyn),
-                                         1 if xp else 0, 1 if accum is not None else 0, 1 if need_din else 0, 1 if poison else 0,
+        L.check(self.lib.mvd_op_conv_bwd(self._ctx, kind, k, B, Cin, H, W, Cout, L.ptr(xn), bool(x_half), L.ptr(ww), L.ptr(dyn),
+                                         bool(xp), accum is not None, bool(need_din), bool(poison),
                                          L.ptr(dx), L.ptr(dW), L.ptr(db), _stream()))
         dxo = dx[..., :Cin].permute(0, 3, 1, 2).contiguous() if need_din else None
         return dxo, dW.view_as(w), db
@@ -858,9 +850,8 @@ class Engine:
             dx.copy_(self._pad_last(accum[0], kp))
             dW.copy_(accum[1])
             db.copy_(accum[2])
-        L.check(self.lib.mvd_op_linear_bwd(self._ctx, int(B), rows, K, N, L.ptr(xn), 1 if x_half else 0, L.ptr(ww), L.ptr(bb), L.ptr(dyn),
-                                           1 if geglu else 0, 1 if dx_half else 0, 1 if staged else 0, 1 if xp else 0,
-                                           1 if accum is not None else 0, 1 if poison else 0, L.ptr(dx), L.ptr(dW), L.ptr(db), _stream()))
+        L.check(self.lib.mvd_op_linear_bwd(self._ctx, B, rows, K, N, L.ptr(xn), bool(x_half), L.ptr(ww), L.ptr(bb), L.ptr(dyn),
+                                           bool(geglu), bool(dx_half), bool(staged), bool(xp), accum is not None, bool(poison), L.ptr(dx), L.ptr(dW), L.ptr(db), _stream()))
         return dx[:, :K].contiguous(), dW, db
 
     def op_conv3d_bwd(self, x, w, dy, kind=0, x_half=False, accum=None, poison=False):
@@ -879,8 +870,8 @@ class Engine:
             dx.copy_(accum[0].permute(0, 2, 3, 4, 1))
             dW.copy_(accum[1])
             db.copy_(accum[2])
-        L.check(self.lib.mvd_op_conv3d_bwd(self._ctx, int(kind), B, Cin, D, H, W, Cout, L.ptr(xn), 1 if x_half else 0, L.ptr(ww), L.ptr(dyn),
-                                           1 if accum is not None else 0, 1 if poison else 0, L.ptr(dx), L.ptr(dW), L.ptr(db), _stream()))
+        L.check(self.lib.mvd_op_conv3d_bwd(self._ctx, kind, B, Cin, D, H, W, Cout, L.ptr(xn), bool(x_half), L.ptr(ww), L.ptr(dyn),
+                                           accum is not None, bool(poison), L.ptr(dx), L.ptr(dW), L.ptr(db), _stream()))
         return dx.permute(0, 4, 1, 2, 3).contiguous(), dW, db
 
     def op_tgemm(self, a, b, a_trans=False, b_trans=False, a_half=False, b_half=False, xp=False, out=None, poison=False):
@@ -891,9 +882,9 @@ class Engine:
         M, K = (a.shape[1], a.shape[0]) if a_trans else a.shape
         N = b.shape[0] if b_trans else b.shape[1]
         o = torch.zeros(M, N, device=dev) if out is None else _f32(out, dev).clone()
-        L.check(self.lib.mvd_op_tgemm(self._ctx, M, N, K, L.ptr(a), 1 if a_half else 0, 1 if a_trans else 0, C.c_long(a.shape[1]),
-                                      L.ptr(b), 1 if b_half else 0, 1 if b_trans else 0, C.c_long(b.shape[1]), L.ptr(o), N,
-                                      1 if out is not None else 0, 1 if xp else 0, 1 if poison else 0, _stream()))
+        L.check(self.lib.mvd_op_tgemm(self._ctx, M, N, K, L.ptr(a), bool(a_half), bool(a_trans), a.shape[1],
+                                      L.ptr(b), bool(b_half), bool(b_trans), b.shape[1], L.ptr(o), N,
+                                      out is not None, bool(xp), bool(poison), _stream()))
         return o
 
     def bench_conv(self, B, Cc, H, W, Cout, iters=20):
@@ -917,13 +908,13 @@ class Engine:
 
     def probe_config(self, mode, family=None, stride=1):
         """mvd_probe_config: 0 off, 1 every launch of every kernel family, 2 a 1-in-stride sample of ``family``."""
-        L.check(self.lib.mvd_probe_config(self._ctx, int(mode), None if family is None else family.encode(), int(stride)))
+        L.check(self.lib.mvd_probe_config(self._ctx, mode, None if family is None else family.encode(), stride))
 
     def probe_report(self):
         """Per-family table since the last probe_config: list of dicts (family, launches, sampled, ms, flops, bytes, ...)."""
         import json
         buf = C.create_string_buffer(1 << 16)
-        L.check(self.lib.mvd_probe_report(self._ctx, buf, C.c_size_t(len(buf))))
+        L.check(self.lib.mvd_probe_report(self._ctx, buf, len(buf)))
         return json.loads(buf.value.decode())
 
     def vae_decode(self, z):
@@ -951,7 +942,7 @@ class Engine:
         B, ch, H, W = x.shape
         if ch != 3:
             raise ValueError("clip_encode expects [B,3,H,W]")
-        out = torch.empty(B, int(self.lib.mvd_clip_embed_dim(self._ctx)), device=self.device)
+        out = torch.empty(B, self.lib.mvd_clip_embed_dim(self._ctx), device=self.device)
         L.check(self.lib.mvd_clip_encode(self._ctx, L.ptr(x), B, H, W, L.ptr(out), _stream()))
         return out.unsqueeze(1)
 

@@ -1,10 +1,11 @@
-"""ctypes binding of libmvd_hip.so (C ABI in include/mvd.h).
+"""ctypes binding of libmvd_hip.so (C ABI in include/mvd.h: load() derives every restype / argtypes from that header).
 
 The HIP library is the product path: there is NO CPU / PyTorch fallback.  If the shared object is missing
 (or fails to load) every entry point raises, loudly.
 """
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MVD_DTYPE (read once, at the first load): "f16" (default) -> libmvd_hip.so, "bf16" -> libmvd_hip_bf16.so, the same sources
@@ -15,15 +16,51 @@ if DTYPE not in ("f16", "bf16"):
     raise ValueError(f"MVD_DTYPE must be f16 or bf16, not {DTYPE!r}")
 LIB_PATH = os.environ.get("MVD_LIB_PATH", os.path.join(_HERE, "libmvd_hip.so" if DTYPE == "f16" else "libmvd_hip_bf16.so"))
 
-SYMBOLS = [
-    "mvd_create", "mvd_destroy", "mvd_last_error", "mvd_compute_dtype", "mvd_upload_weight", "mvd_set_precision_level", "mvd_set_vae_precision", "mvd_finalize_weights", "mvd_unet_forward", "mvd_unet_block",
-    "mvd_embed_time", "mvd_select_sample", "mvd_set_mesh", "mvd_set_cameras", "mvd_set_mesh_async", "mvd_set_cameras_async", "mvd_set_samples_async", "mvd_rulebook_build", "mvd_rulebook_table", "mvd_vertex_features", "mvd_vertex_view_features", "mvd_vertex_features_stream_safe", "mvd_fuse_vertex_features",
-    "mvd_comm_unique_id", "mvd_comm_init", "mvd_comm_destroy", "mvd_exchange_view_features", "mvd_comm_all_reduce", "mvd_train_sync_gradients",
-    "mvd_stage_target_encoder", "mvd_stage_sparse_dense", "mvd_set_spatial_volume", "mvd_spatial_time_volume", "mvd_stage_unproject", "mvd_set_volume_ready_event", "mvd_volume_from_fused", "mvd_volume_from_fused_train", "mvd_mse_loss", "mvd_set_volume", "mvd_train_enable", "mvd_train_param_count", "mvd_train_param_info", "mvd_train_arena_size", "mvd_train_adopt_arena", "mvd_train_zero_grad", "mvd_train_unet_step", "mvd_train_get_grad", "mvd_train_get_tensor", "mvd_train_bn_calls", "mvd_train_cond_backward", "mvd_train_conditioner_backward", "mvd_train_conditioner_backward_batch", "mvd_train_adamw_step", "mvd_train_repack", "mvd_train_repack_async", "mvd_train_grad_bucket_count", "mvd_train_grad_bucket", "mvd_train_grad_bucket_wait", "mvd_train_set_bucket_snapshot",
-    "mvd_frustum_volumes", "mvd_frustum_volumes_batch", "mvd_denoise_views", "mvd_denoise_views_batch", "mvd_denoise_views_ms", "mvd_op_cfg_ms", "mvd_op_conv", "mvd_op_linear", "mvd_op_group_norm",
-    "mvd_op_layer_norm", "mvd_op_attention", "mvd_op_attention_bwd", "mvd_op_group_norm_bwd", "mvd_op_layer_norm_bwd", "mvd_op_conv3d", "mvd_op_conv_bwd", "mvd_op_linear_bwd", "mvd_op_conv3d_bwd", "mvd_op_tgemm", "mvd_op_st_tail", "mvd_op_st_head", "mvd_bench_conv", "mvd_bench_linear", "mvd_bench_group_norm", "mvd_probe_config", "mvd_probe_report", "mvd_vae_decode", "mvd_vae_encode",
-    "mvd_clip_encode", "mvd_clip_embed_dim",
-]
+HEADER = os.path.join(_HERE, "..", "include", "mvd.h")
+
+
+class MvdError(RuntimeError):
+    pass
+
+
+_CTYPES = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "long": C.c_long, "size_t": C.c_size_t, "float": C.c_float,
+           "const char*": C.c_char_p}
+
+
+def _ctype(decl, func, is_return=False):
+    """ctypes type of one C type as include/mvd.h spells it (a parameter with its name, or a return type)."""
+    decl = re.sub(r"\s*\*\s*", "* ", decl).strip()  # "const float* const* K", "mvd_ctx** out", "int", "const char*"
+    ty = decl if is_return or " " not in decl else decl.rsplit(" ", 1)[0].strip()
+    if ty == "void" and is_return:
+        return None
+    if ty in _CTYPES:
+        return _CTYPES[ty]
+    if ty.endswith("*"):
+        return C.c_void_p
+    raise MvdError(f"include/mvd.h: {func}: no ctypes type for {ty!r} (in {decl!r})")
+
+
+def parse_header(path=HEADER):
+    """{name: (restype, [argtypes])} of every function include/mvd.h declares: the ONE place an entry point's signature is
+    written (c_api.hip is compiled against the same header).  The header keeps to one declaration style -- `RET name(ARGS);`, no
+    macros in signatures, `(void)` for an empty list -- so this is a regular expression, not a C parser; a type outside the
+    table above raises MvdError."""
+    try:
+        with open(path) as fh:
+            text = re.sub(r"/\*.*?\*/", " ", fh.read(), flags=re.S)
+    except OSError as e:
+        raise MvdError(f"cannot read the C ABI header {path}: {e}")
+    protos = {}
+    for ret, name, args in re.findall(r"([\w \t\*]+?)\b(mvd_\w+)\s*\(([^()]*)\)\s*;", text):
+        args = [] if args.strip() == "void" else args.split(",")
+        protos[name] = (_ctype(ret, name, is_return=True), [_ctype(a, name) for a in args])
+    if not protos:
+        raise MvdError(f"{path} declares no mvd_* function")
+    return protos
+
+
+PROTOTYPES = parse_header()
+SYMBOLS = list(PROTOTYPES)  # every entry point of the C ABI, in header order
 
 
 def csrc_sha16():
@@ -56,10 +93,6 @@ class VolumeConfigC(C.Structure):
                 ("frustum_dims", C.c_int * 4), ("voxel_size", C.c_float)]
 
 
-class MvdError(RuntimeError):
-    pass
-
-
 _lib = None
 
 
@@ -72,17 +105,11 @@ def load():
         raise MvdError(f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        f"(hipcc --offload-arch=gfx950). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    lib.mvd_last_error.restype = C.c_char_p
-    lib.mvd_compute_dtype.restype = C.c_char_p
-    lib.mvd_destroy.restype = None
-    for name in SYMBOLS:
+    for name, (restype, argtypes) in PROTOTYPES.items():
         if not hasattr(lib, name):
             raise MvdError(f"libmvd_hip.so does not export {name}")
-    for name in SYMBOLS:
-        if name not in ("mvd_last_error", "mvd_destroy", "mvd_compute_dtype"):
-            getattr(lib, name).restype = C.c_int
-    lib.mvd_train_arena_size.restype = C.c_int64
-    lib.mvd_train_bn_calls.restype = C.c_int64
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if "MVD_LIB_PATH" not in os.environ and lib.mvd_compute_dtype().decode() != DTYPE:
         raise MvdError(f"{LIB_PATH} computes in {lib.mvd_compute_dtype().decode()}, MVD_DTYPE asks for {DTYPE}")
     _lib = lib
@@ -97,6 +124,6 @@ def check(rc):
 def ptr(t):
     """Device/host pointer of a torch tensor (None -> NULL)."""
     if t is None:
-        return C.c_void_p(0)
+        return None
     assert t.is_contiguous(), "tensor must be contiguous at the C boundary"
-    return C.c_void_p(t.data_ptr())
+    return t.data_ptr()

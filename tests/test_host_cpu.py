@@ -27,6 +27,141 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
     assert sorted(lib.SYMBOLS) == declared
 
 
+def _header_declarations():
+    """{name: [parameter text, ...]} of include/mvd.h, read independently of lib.py: comments stripped, commas counted."""
+    header = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "mvd.h")).read(), flags=re.S)
+    decls = {}
+    for name, args in re.findall(r"\b(mvd_\w+)\s*\(([^()]*)\)\s*;", header):
+        decls[name] = [] if args.strip() == "void" else [a.strip() for a in args.split(",")]
+    return decls
+
+
+def test_ctypes_prototypes_come_from_the_header():
+    """lib.load() gives every entry point the restype / argtypes of its declaration in include/mvd.h: the parameter counts
+    agree with the header, nothing is left at the ctypes default, and the type map holds on the parameters a 32-bit default
+    would silently truncate."""
+    import ctypes as C
+    from morphablediffusion_amd import lib
+    L = lib.load()
+    decls = _header_declarations()
+    assert sorted(decls) == sorted(lib.SYMBOLS) and len(decls) >= 80
+    returns_int = set(re.findall(r"^int (mvd_\w+)\(", open(os.path.join(ROOT, "include", "mvd.h")).read(), re.M))
+    assert len(returns_int) == len(decls) - 5
+    for name in lib.SYMBOLS:
+        fn = getattr(L, name)
+        assert fn.argtypes is not None, f"{name}: argtypes left at the ctypes default"
+        assert len(fn.argtypes) == len(decls[name]), f"{name}: {len(fn.argtypes)} argtypes, {len(decls[name])} parameters in mvd.h"
+        assert (fn.restype is C.c_int) == (name in returns_int), f"{name}: restype {fn.restype}"
+
+    def argtype(func, param):
+        idx = [i for i, a in enumerate(decls[func]) if re.search(rf"\b{param}$", a)]
+        assert len(idx) == 1, (func, param, decls[func])
+        return getattr(L, func).argtypes[idx[0]]
+
+    assert argtype("mvd_create", "workspace_bytes") is C.c_size_t
+    assert argtype("mvd_create", "out") is C.c_void_p
+    assert argtype("mvd_denoise_views", "timestep") is C.c_int64
+    assert argtype("mvd_denoise_views", "cfg_scale") is C.c_float
+    assert argtype("mvd_op_tgemm", "lda") is C.c_long and argtype("mvd_op_tgemm", "ldb") is C.c_long
+    assert argtype("mvd_upload_weight", "name") is C.c_char_p
+    assert argtype("mvd_train_param_info", "name") is C.c_void_p
+    assert argtype("mvd_train_param_info", "name_cap") is C.c_size_t
+    assert L.mvd_train_arena_size.restype is C.c_int64 and L.mvd_train_bn_calls.restype is C.c_int64
+    assert L.mvd_last_error.restype is C.c_char_p and L.mvd_compute_dtype.restype is C.c_char_p
+    assert L.mvd_destroy.restype is None
+    assert L.mvd_embed_time.restype is C.c_int
+
+
+def test_c_boundary_checks_argument_count_and_converts_plain_scalars():
+    import ctypes as C
+    from morphablediffusion_amd import lib
+    L = lib.load()
+    with pytest.raises(TypeError):
+        L.mvd_rulebook_table(0)  # two parameters
+    # plain Python floats / ints / None: a null context fails before any HIP call, with the function's own message
+    rc = L.mvd_train_adamw_step(None, 1e-4, 1e-4, 0.9, 0.999, 1e-8, 0.01, 1, 1.0, 1, None, None)
+    assert rc != 0 and b"mvd_train_adamw_step" in L.mvd_last_error()
+    with pytest.raises(C.ArgumentError):
+        L.mvd_train_adamw_step(None, "1e-4", 1e-4, 0.9, 0.999, 1e-8, 0.01, 1, 1.0, 1, None, None)
+
+
+def test_header_with_an_unknown_type_fails_loudly(tmp_path):
+    from morphablediffusion_amd import lib
+    header = open(os.path.join(ROOT, "include", "mvd.h")).read()
+    assert header.count("int mvd_select_sample(mvd_ctx* ctx, int slot);") == 1
+    bad = tmp_path / "mvd.h"
+    bad.write_text(header.replace("int mvd_select_sample(mvd_ctx* ctx, int slot);", "int mvd_select_sample(mvd_ctx* ctx, double slot);"))
+    with pytest.raises(lib.MvdError, match="mvd_select_sample.*double"):
+        lib.parse_header(str(bad))
+    with pytest.raises(lib.MvdError, match="missing.h"):
+        lib.parse_header(str(tmp_path / "missing.h"))
+    good = tmp_path / "same.h"
+    good.write_text(header)
+    assert lib.parse_header(str(good)) == lib.PROTOTYPES
+
+
+def _file_scope(text):
+    """C++ source without comments, literals and preprocessor lines, every brace block replaced by ``{}`` -- except the blocks
+    of ``namespace`` and ``extern "C"``, whose contents are file scope too."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    text = re.sub(r'extern\s+"C"', "extern_C", text)
+    text = re.sub(r'"(?:\\.|[^"\\\n])*"', '""', text)
+    text = re.sub(r"'(?:\\.|[^'\\\n])'", "0", text)
+    text = re.sub(r"^[ \t]*#(?:[^\n]*\\\n)*[^\n]*", " ", text, flags=re.M)
+    out, depth, transparent = [], 0, []
+    for ch in text:
+        if ch == "{":
+            if depth == 0 and re.search(r"(?:\bnamespace(?:\s+\w+)?|\bextern_C)\s*$", re.split(r"[;{}]", "".join(out[-200:]))[-1]):
+                transparent.append(True)
+                out.append(";")
+                continue
+            if depth == 0:
+                out.append("{}")
+            transparent.append(False)
+            depth += 1
+        elif ch == "}":
+            if transparent.pop():
+                out.append(";")
+            else:
+                depth -= 1
+        elif depth == 0:
+            out.append(ch)
+    assert depth == 0 and not transparent
+    return "".join(out)
+
+
+_PROTOTYPE = re.compile(r"(?:^|(?<=[;}]))\s*(?:[\w:<>\*&]+[\s\*&]+)+(\w+)\s*\(([^(){};]*)\)\s*;")  # `type name(params);`, any line count
+_DEFINITION = re.compile(r"\b(\w+)\s*\(([^(){};]*)\)\s*(?:const\s*)?\{\}")
+
+
+def test_every_launcher_is_declared_once_in_a_header():
+    """A function that one .hip file defines and another calls is declared in a header both include, never by a prototype
+    copied into the caller (copies drift: a default argument here, none there, and a changed signature surfaces as a mangled
+    name at link time).  So a prototype at the file scope of a .hip file may only announce a function defined further down
+    in the same file, and no function is prototyped in two headers."""
+    csrc = os.path.join(ROOT, "morphablediffusion_amd", "csrc")
+    assert _PROTOTYPE.findall(_file_scope("namespace {\nint f(int a,\n      float* b = nullptr);\n}\nint g() { return f(1); }\nvoid h(void);")) \
+        == [("f", "int a,\n      float* b = nullptr"), ("h", "void")]
+    foreign, seen_definitions = [], 0
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith(".hip"):
+            scope = _file_scope(open(os.path.join(csrc, f)).read())
+            defined = {m.group(1) for m in _DEFINITION.finditer(scope)}
+            seen_definitions += len(defined)
+            foreign += [(f, name) for name, _ in _PROTOTYPE.findall(scope) if name not in defined]
+    assert seen_definitions > 400, "the scan found too few function definitions to be reading the sources"
+    assert not foreign, f"prototypes of functions defined in another file: {foreign}"
+    where = {}
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith(".h"):
+            for name, _ in _PROTOTYPE.findall(_file_scope(open(os.path.join(csrc, f)).read())):
+                where.setdefault(name, []).append(f)
+    assert len(where) > 150 and where["bwd_cast_rows"] == ["common.h"] and where["engine_select_sample"] == ["engine.h"]
+    twice = {n: fs for n, fs in where.items() if len(fs) > 1}
+    assert not twice, f"declared more than once: {twice}"
+
+
 def _env_table():
     """The rows of csrc/env.h: {name: (lifetime, kind, field, default)}."""
     header = open(os.path.join(ROOT, "morphablediffusion_amd", "csrc", "env.h")).read()

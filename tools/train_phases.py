@@ -69,7 +69,7 @@ for it in range(2 if os.environ.get('PROFILE_COND') else 4):
         else:
             m.engine.train_conditioner_backward_batch(list(range(B)), x_noisy, ts.tolist(), v_embed, ti[:, 0].tolist(), dsrc)
     tick("cond bwd", cb)
-    tick("adamw", lambda: m.engine.lib.mvd_train_adamw_step(m.engine._ctx, *[__import__("ctypes").c_float(v) for v in (1e-6, 1e-5, 0.9, 0.999, 1e-8, 0.01)], it + 1, __import__("ctypes").c_float(1.0 / m.loss_scale), 1, None, None))
+    tick("adamw", lambda: m.engine.lib.mvd_train_adamw_step(m.engine._ctx, 1e-6, 1e-5, 0.9, 0.999, 1e-8, 0.01, it + 1, 1.0 / m.loss_scale, 1, None, None))
     tick("repack", m.engine.repack)
 if os.environ.get("PROFILE_COND"):  # rocprofv3 aid: 10 more conditioner backward passes, nothing else
     torch.cuda.synchronize()
