@@ -233,7 +233,7 @@ int mvd_mse_loss(mvd_ctx* ctx, const float* a, const float* b, size_t n, float* 
  *   mvd_train_param_count / _info   enumerate the parameters: name (state_dict key), offset and numel in the arena (floats),
  *                                   shape (up to 8 dims) -- what nn.Module.named_parameters() is to the reference.
  *   mvd_train_arena_size            floats per arena.
- *   mvd_train_adopt_arena(which, ptr, numel)   moves arena `which` (0 parameters, 1 gradients, 2 / 3 Adam moments) into
+ *   mvd_train_adopt_arena(which, ptr, numel)   moves arena `which` (0 parameters, 1 gradients, 2 / 3 Adam moments, 4 EMA) into
  *                                   caller-owned device memory of the same size (its content is copied over, a not yet
  *                                   existing arena is zeroed): the caller's tensor framework then sees parameters / gradients
  *                                   as views of ONE buffer (one RCCL all-reduce for the DDP gradient averaging of
@@ -260,7 +260,28 @@ int mvd_mse_loss(mvd_ctx* ctx, const float* a, const float* b, size_t n, float* 
  *                                   parameters whose .grad is None (e.g. spatial_volume.* when only mvd_train_unet_step ran).
  *                                   With inv_scale == 1 (no loss scaling: the bfloat16 build) the overflow
  *                                   check is not run -- torch.optim.AdamW's own behaviour -- and *skipped_out stays 0.
- *   mvd_train_repack                after the parameters changed: re-derive every packed fp16 weight in place. */
+ *   mvd_train_repack                after the parameters changed: re-derive every packed fp16 weight in place.
+ * Gradient clipping by global norm (Lightning's gradient_clip_val / clip_grad_norm_) and EMA weights (LDM's LitEma), fused into
+ * the optimiser step:
+ *   mvd_train_adopt_arena(4, ...)   the EMA arena; one that does not exist yet starts as a COPY of the parameter arena (LitEma's
+ *                                   initial shadow), not zeroed.
+ *   mvd_train_grad_norm             norm_out (device, 1 float) = || inv_scale * g || over exactly the ranges mvd_train_adamw_step
+ *                                   would update (same groups, same untouched-group rule; clip_grad_norm_ likewise ignores
+ *                                   parameters without a gradient).  Two-stage sum without atomics on a grid that depends only
+ *                                   on the range lengths: bit-reproducible.
+ *   mvd_train_adamw_step_ex         mvd_train_adamw_step plus: max_grad_norm > 0 multiplies the un-scaled gradients by
+ *                                   min(1, max_grad_norm / (norm + 1e-6)) (<= 0: no clipping); ema_decay >= 0 applies
+ *                                   e -= (1 - ema_decay) (e - p_new) on the EMA arena (created on first use; < 0: no EMA; the
+ *                                   caller computes LitEma's warm-up, ema_decay is THIS step's decay); grad_norm_out (HOST, may
+ *                                   be NULL) receives the norm.  Reading skipped_out or grad_norm_out back synchronises the
+ *                                   stream; with both NULL the call does not.  With inv_scale != 1 the norm pass doubles as the
+ *                                   overflow check: a non-finite norm skips the step -- parameters, moments and EMA untouched,
+ *                                   *skipped_out = 1.  With inv_scale == 1 nothing is special-cased, as in torch.  The norm pass
+ *                                   runs only when clipping, loss scaling or grad_norm_out asks for it.
+ *   mvd_train_last_grad_norm        norm_out (device, 1 float) = the norm of the last mvd_train_adamw_step_ex /
+ *                                   mvd_train_grad_norm pass, copied in stream order: no synchronisation.
+ *   mvd_train_ema_swap              exchanges the parameter arena and the EMA arena in place (sampling / validating from the
+ *                                   averaged weights); the caller re-packs afterwards, and swaps back the same way. */
 int mvd_train_enable(mvd_ctx* ctx, int on);
 int mvd_train_param_count(mvd_ctx* ctx);
 int mvd_train_param_info(mvd_ctx* ctx, int index, char* name, size_t name_cap, int64_t* offset, int64_t* numel, int64_t* shape,
@@ -306,6 +327,12 @@ int mvd_train_get_tensor(mvd_ctx* ctx, const char* name, float* out, size_t nume
 int64_t mvd_train_bn_calls(mvd_ctx* ctx);
 int mvd_train_adamw_step(mvd_ctx* ctx, float lr, float lr_aux, float beta1, float beta2, float eps, float weight_decay, int step,
                          float inv_scale, int finetune_unet, int* skipped_out, void* stream);
+int mvd_train_grad_norm(mvd_ctx* ctx, float inv_scale, int finetune_unet, float* norm_out, void* stream);
+int mvd_train_adamw_step_ex(mvd_ctx* ctx, float lr, float lr_aux, float beta1, float beta2, float eps, float weight_decay, int step,
+                            float inv_scale, int finetune_unet, int* skipped_out, float max_grad_norm, float ema_decay,
+                            float* grad_norm_out, void* stream);
+int mvd_train_last_grad_norm(mvd_ctx* ctx, float* norm_out, void* stream);
+int mvd_train_ema_swap(mvd_ctx* ctx, void* stream);
 int mvd_train_repack(mvd_ctx* ctx);
 /* The same in the order of `stream` (the stream the optimiser update was enqueued on and the next forward will be): no device
  * synchronisation -- the pack launches wait for an event on `stream`, later work on `stream` waits for them. */
@@ -387,6 +414,11 @@ int mvd_denoise_views_ms(mvd_ctx* ctx, int B, const int* slots, const float* x_n
 int mvd_op_cfg_ms(const float* eps_c, const float* eps_u, float scale, const float* x, const float* noise, float s1m, float sqrt_at,
                   float c_x, float c_d, float c_c, float c_n, float* x0_hist, int first, float* eps_out, float* x_next, size_t n,
                   void* stream);
+/* The kernels of mvd_train_adamw_step_ex on raw device buffers of n floats (n % 4 == 0, 16-byte aligned), no context: the
+ * gradient norm (norm_out: device, 1 float, may be NULL), then the fused AdamW (+ clipping for max_grad_norm > 0, + EMA for
+ * e != NULL and ema_decay >= 0) step.  Synchronises the stream when a norm was computed (its scratch lives for the call). */
+int mvd_op_adamw_ex(float* p, const float* g, float* m, float* v, float* e, size_t n, float lr, float beta1, float beta2, float eps,
+                    float wd, int step, float inv_scale, float max_grad_norm, float ema_decay, float* norm_out, void* stream);
 int mvd_op_conv(mvd_ctx* ctx, const float* x_nchw, int B, int Cin, int H, int W, const float* w, const float* bias,
                 int Cout, int ksize, int stride, int upsample, const float* resid_nchw, float* out_nchw, int force_splitk,
                 void* stream);

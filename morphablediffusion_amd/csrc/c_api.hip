@@ -115,10 +115,12 @@ void mvd_destroy(mvd_ctx* c) {
   mvd_comm_destroy(c);
   for (auto& kv : c->raw)
     if (!c->param_index.count(kv.first)) hipFree(kv.second.d);  // master parameters live in the arena
-  float* arenas[4] = {c->arena_p, c->arena_g, c->arena_m, c->arena_v};
-  for (int i = 0; i < 4; ++i)
+  float* arenas[5] = {c->arena_p, c->arena_g, c->arena_m, c->arena_v, c->arena_e};
+  for (int i = 0; i < 5; ++i)
     if (arenas[i] && c->arena_owned[i]) hipFree(arenas[i]);
   hipFree(c->found_inf);
+  hipFree(c->norm_part);
+  hipFree(c->norm_dev);
   for (void* p : c->owned) hipFree(p);
   mesh_free(c->mesh);
   hipFree(c->cams);
@@ -492,13 +494,14 @@ int64_t mvd_train_arena_size(mvd_ctx* c) { return (c && c->train_mode && c->fina
 
 int mvd_train_adopt_arena(mvd_ctx* c, int which, float* ptr, int64_t numel) {
   if (!c || !c->train_mode || !c->finalized) return mvd_fail("mvd_train_adopt_arena: context not finalized in training mode");
-  if (which < 0 || which > 3 || !ptr || numel != (int64_t)c->arena_n) return mvd_fail("mvd_train_adopt_arena: bad argument");
+  if (which < 0 || which > 4 || !ptr || numel != (int64_t)c->arena_n) return mvd_fail("mvd_train_adopt_arena: bad argument");
   HIP_CHECK_RET(hipSetDevice(c->device));
   HIP_CHECK_RET(hipDeviceSynchronize());
-  float** slot[4] = {&c->arena_p, &c->arena_g, &c->arena_m, &c->arena_v};
+  float** slot[5] = {&c->arena_p, &c->arena_g, &c->arena_m, &c->arena_v, &c->arena_e};
   float* old = *slot[which];
   if (old == ptr) return 0;
-  if (old) HIP_CHECK_RET(hipMemcpy(ptr, old, c->arena_n * sizeof(float), hipMemcpyDeviceToDevice));
+  const float* init = old ? old : (which == 4 ? c->arena_p : nullptr);  // a new EMA arena: LitEma's initial shadow, the parameters
+  if (init) HIP_CHECK_RET(hipMemcpy(ptr, init, c->arena_n * sizeof(float), hipMemcpyDeviceToDevice));
   else HIP_CHECK_RET(hipMemset(ptr, 0, c->arena_n * sizeof(float)));
   if (old && c->arena_owned[which]) hipFree(old);
   *slot[which] = ptr;
@@ -660,6 +663,58 @@ int mvd_train_get_tensor(mvd_ctx* c, const char* name, float* out, size_t numel,
 
 int64_t mvd_train_bn_calls(mvd_ctx* c) { return c ? (int64_t)c->bn_train_calls : 0; }
 
+// The arena ranges [off, off + len) one optimiser step updates, with their group: the reference's parameter groups
+// (morphable_diffusion.py:627-646) -- 1: the UNet (all of it with finetune_unet, else the DepthTransformers: attention.py:140-142)
+// at lr, 2: time_embed and spatial_volume at 10 lr (passed in as lr_aux).  Consecutive parameters of one group form one range; a
+// group no backward pass wrote to since zero_grad is left out -- it keeps its parameters AND its moments.
+struct StepRange {
+  size_t off, len;
+  int grp;
+};
+static void step_ranges(mvd_ctx* c, int finetune_unet, std::vector<StepRange>& out) {
+  const std::string U = "model.diffusion_model.";
+  auto group_of = [&](const std::string& k) -> int {
+    if (k.rfind(U, 0) == 0) {
+      if (finetune_unet) return 1;
+      return (k.rfind(U + "middle_conditions.", 0) == 0 || k.rfind(U + "output_conditions.", 0) == 0) ? 1 : 0;
+    }
+    return 2;
+  };
+  out.clear();
+  size_t i = 0;
+  while (i < c->params.size()) {
+    const int grp = group_of(c->params[i].key);
+    size_t j = i;
+    while (j + 1 < c->params.size() && group_of(c->params[j + 1].key) == grp) ++j;
+    if (grp && c->grad_touched[grp]) {
+      const size_t off = c->params[i].off, end = c->params[j].off + ((c->params[j].numel + 63) & ~(size_t)63);
+      out.push_back({off, end - off, grp});
+    }
+    i = j + 1;
+  }
+}
+
+// norm_dev[0] = || inv_scale * g || over the ranges, norm_dev[1] = the clipping coefficient for max_norm (1 when <= 0);
+// *flag (may be null) raised when the sum of squares is not finite
+static int grad_norm_pass(mvd_ctx* c, const std::vector<StepRange>& rs, float inv_scale, float max_norm, int* flag, hipStream_t s) {
+  size_t total = 0;
+  for (const StepRange& r : rs) total += (size_t)bwd_grad_sumsq_blocks(r.len);
+  if (!c->norm_dev) HIP_CHECK_RET(hipMalloc((void**)&c->norm_dev, 2 * sizeof(float)));
+  if (total > c->norm_part_cap) {
+    if (c->norm_part) HIP_CHECK_RET(hipFree(c->norm_part));  // (synchronises: nothing still reads the old buffer)
+    c->norm_part = nullptr;
+    c->norm_part_cap = 0;
+    HIP_CHECK_RET(hipMalloc((void**)&c->norm_part, total * sizeof(float)));
+    c->norm_part_cap = total;
+  }
+  size_t at = 0;
+  for (const StepRange& r : rs) {
+    RET_IF(bwd_grad_sumsq(c->arena_g + r.off, r.len, inv_scale, c->norm_part + at, s));
+    at += (size_t)bwd_grad_sumsq_blocks(r.len);
+  }
+  return bwd_grad_norm_final(c->norm_part, (int)total, max_norm, c->norm_dev, flag, s);
+}
+
 int mvd_train_adamw_step(mvd_ctx* c, float lr, float lr_aux, float beta1, float beta2, float eps, float weight_decay, int step,
                          float inv_scale, int finetune_unet, int* skipped_out, void* stream) {
   if (!c || !c->train_mode || !c->finalized) return mvd_fail("mvd_train_adamw_step: context not finalized in training mode");
@@ -676,34 +731,109 @@ int mvd_train_adamw_step(mvd_ctx* c, float lr, float lr_aux, float beta1, float 
   // The overflow check (a 3.7 GB read: ~1 ms) belongs to loss scaling -- GradScaler's "skip the step, halve the scale".  Without
   // a loss scale (inv_scale == 1: the bfloat16 build) the step is torch.optim.AdamW's own, which checks nothing.
   if (inv_scale != 1.0f) RET_IF(bwd_finite_check(c->arena_g, c->arena_n, c->found_inf, s));
-  // the reference's parameter groups (morphable_diffusion.py:627-646): the UNet (all of it with finetune_unet, else the
-  // DepthTransformers: attention.py:140-142) at lr; time_embed and spatial_volume at 10 lr (passed in as lr_aux).
-  // Consecutive parameters of one group are updated by one launch.
-  const std::string U = "model.diffusion_model.";
-  auto group_of = [&](const std::string& k) -> int {
-    if (k.rfind(U, 0) == 0) {
-      if (finetune_unet) return 1;
-      return (k.rfind(U + "middle_conditions.", 0) == 0 || k.rfind(U + "output_conditions.", 0) == 0) ? 1 : 0;
-    }
-    return 2;
-  };
-  size_t i = 0;
-  while (i < c->params.size()) {
-    const int grp = group_of(c->params[i].key);
-    size_t j = i;
-    while (j + 1 < c->params.size() && group_of(c->params[j + 1].key) == grp) ++j;
-    if (grp && c->grad_touched[grp]) {  // a group no backward pass wrote to since zero_grad keeps its parameters AND its moments
-      const size_t off = c->params[i].off, end = c->params[j].off + ((c->params[j].numel + 63) & ~(size_t)63);
-      RET_IF(bwd_adamw(c->arena_p + off, c->arena_g + off, c->arena_m + off, c->arena_v + off, end - off, grp == 1 ? lr : lr_aux, beta1,
-                       beta2, eps, weight_decay, step, inv_scale, c->found_inf, s));
-    }
-    i = j + 1;
-  }
+  // one launch per contiguous range of a parameter group
+  std::vector<StepRange> rs;
+  step_ranges(c, finetune_unet, rs);
+  for (const StepRange& r : rs)
+    RET_IF(bwd_adamw(c->arena_p + r.off, c->arena_g + r.off, c->arena_m + r.off, c->arena_v + r.off, r.len, r.grp == 1 ? lr : lr_aux,
+                     beta1, beta2, eps, weight_decay, step, inv_scale, c->found_inf, s));
   if (skipped_out) {
     HIP_CHECK_RET(hipMemcpyAsync(skipped_out, c->found_inf, sizeof(int), hipMemcpyDeviceToHost, s));
     HIP_CHECK_RET(hipStreamSynchronize(s));
   }
   return 0;
+}
+
+int mvd_train_grad_norm(mvd_ctx* c, float inv_scale, int finetune_unet, float* norm_out, void* stream) {
+  if (!c || !c->train_mode || !c->finalized) return mvd_fail("mvd_train_grad_norm: context not finalized in training mode");
+  if (!norm_out) return mvd_fail("mvd_train_grad_norm: null argument");
+  HIP_CHECK_RET(hipSetDevice(c->device));
+  hipStream_t s = S(stream);
+  std::vector<StepRange> rs;
+  step_ranges(c, finetune_unet, rs);
+  RET_IF(grad_norm_pass(c, rs, inv_scale, 0.f, nullptr, s));
+  HIP_CHECK_RET(hipMemcpyAsync(norm_out, c->norm_dev, sizeof(float), hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+int mvd_train_last_grad_norm(mvd_ctx* c, float* norm_out, void* stream) {
+  if (!c || !c->train_mode || !c->finalized) return mvd_fail("mvd_train_last_grad_norm: context not finalized in training mode");
+  if (!norm_out || !c->norm_dev) return mvd_fail("mvd_train_last_grad_norm: no gradient norm has been computed");
+  HIP_CHECK_RET(hipSetDevice(c->device));
+  HIP_CHECK_RET(hipMemcpyAsync(norm_out, c->norm_dev, sizeof(float), hipMemcpyDeviceToDevice, S(stream)));
+  return 0;
+}
+
+int mvd_train_ema_swap(mvd_ctx* c, void* stream) {
+  if (!c || !c->train_mode || !c->finalized) return mvd_fail("mvd_train_ema_swap: context not finalized in training mode");
+  if (!c->arena_e) return mvd_fail("mvd_train_ema_swap: no EMA arena (mvd_train_adopt_arena 4, or a step with ema_decay >= 0)");
+  HIP_CHECK_RET(hipSetDevice(c->device));
+  return bwd_swap_f32(c->arena_p, c->arena_e, c->arena_n, S(stream));
+}
+
+int mvd_train_adamw_step_ex(mvd_ctx* c, float lr, float lr_aux, float beta1, float beta2, float eps, float weight_decay, int step,
+                            float inv_scale, int finetune_unet, int* skipped_out, float max_grad_norm, float ema_decay,
+                            float* grad_norm_out, void* stream) {
+  if (!c || !c->train_mode || !c->finalized) return mvd_fail("mvd_train_adamw_step_ex: context not finalized in training mode");
+  if (step < 1) return mvd_fail("mvd_train_adamw_step_ex: step counts from 1");
+  if (ema_decay > 1.f) return mvd_fail("mvd_train_adamw_step_ex: ema_decay is at most 1 (negative: no EMA)");
+  HIP_CHECK_RET(hipSetDevice(c->device));
+  hipStream_t s = S(stream);
+  for (float** a : {&c->arena_m, &c->arena_v})
+    if (!*a) {
+      HIP_CHECK_RET(hipMalloc((void**)a, c->arena_n * sizeof(float)));
+      HIP_CHECK_RET(hipMemset(*a, 0, c->arena_n * sizeof(float)));
+      c->arena_owned[a == &c->arena_m ? 2 : 3] = true;
+    }
+  const bool ema = ema_decay >= 0.f;
+  if (ema && !c->arena_e) {  // LitEma's initial shadow: the parameters as they are before this update
+    HIP_CHECK_RET(hipMalloc((void**)&c->arena_e, c->arena_n * sizeof(float)));
+    c->arena_owned[4] = true;
+    HIP_CHECK_RET(hipMemcpyAsync(c->arena_e, c->arena_p, c->arena_n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  }
+  HIP_CHECK_RET(hipMemsetAsync(c->found_inf, 0, sizeof(int), s));
+  std::vector<StepRange> rs;
+  step_ranges(c, finetune_unet, rs);
+  // One read of the gradients gives the norm, the clipping coefficient and -- with loss scaling -- the overflow flag (the
+  // separate finite check of mvd_train_adamw_step is not run).  Without clipping, loss scaling or a norm to report: no pass.
+  const bool clip = max_grad_norm > 0.f, scaled = inv_scale != 1.0f;
+  const bool norm_pass = clip || scaled || grad_norm_out;
+  if (norm_pass) RET_IF(grad_norm_pass(c, rs, inv_scale, clip ? max_grad_norm : 0.f, scaled ? c->found_inf : nullptr, s));
+  for (const StepRange& r : rs)
+    RET_IF(bwd_adamw_ex(c->arena_p + r.off, c->arena_g + r.off, c->arena_m + r.off, c->arena_v + r.off,
+                        ema ? c->arena_e + r.off : nullptr, r.len, r.grp == 1 ? lr : lr_aux, beta1, beta2, eps, weight_decay, step,
+                        inv_scale, clip ? c->norm_dev + 1 : nullptr, ema_decay, c->found_inf, s));
+  if (skipped_out) HIP_CHECK_RET(hipMemcpyAsync(skipped_out, c->found_inf, sizeof(int), hipMemcpyDeviceToHost, s));
+  if (grad_norm_out) HIP_CHECK_RET(hipMemcpyAsync(grad_norm_out, c->norm_dev, sizeof(float), hipMemcpyDeviceToHost, s));
+  if (skipped_out || grad_norm_out) HIP_CHECK_RET(hipStreamSynchronize(s));
+  return 0;
+}
+
+int mvd_op_adamw_ex(float* p, const float* g, float* m, float* v, float* e, size_t n, float lr, float beta1, float beta2, float eps,
+                    float wd, int step, float inv_scale, float max_grad_norm, float ema_decay, float* norm_out, void* stream) {
+  if (!p || !g || !m || !v || !n) return mvd_fail("mvd_op_adamw_ex: null argument");
+  if (step < 1) return mvd_fail("mvd_op_adamw_ex: step counts from 1");
+  hipStream_t s = S(stream);
+  const bool clip = max_grad_norm > 0.f;
+  float* scratch = nullptr;  // [norm, coefficient | partials]
+  if (clip || norm_out) {
+    const int blocks = bwd_grad_sumsq_blocks(n);
+    HIP_CHECK_RET(hipMalloc((void**)&scratch, (2 + (size_t)blocks) * sizeof(float)));
+    int rc = bwd_grad_sumsq(g, n, inv_scale, scratch + 2, s);
+    if (!rc) rc = bwd_grad_norm_final(scratch + 2, blocks, clip ? max_grad_norm : 0.f, scratch, nullptr, s);
+    if (!rc && norm_out && hipMemcpyAsync(norm_out, scratch, sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
+      rc = mvd_fail("mvd_op_adamw_ex: copy of the norm failed");
+    if (rc) {
+      hipFree(scratch);
+      return rc;
+    }
+  }
+  int rc = bwd_adamw_ex(p, g, m, v, e, n, lr, beta1, beta2, eps, wd, step, inv_scale, clip ? scratch + 1 : nullptr, ema_decay, nullptr, s);
+  if (scratch) {  // a test hook: the scratch lives for this call only
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_adamw_ex: stream synchronisation failed");
+    hipFree(scratch);
+  }
+  return rc;
 }
 
 int mvd_train_repack(mvd_ctx* c) {

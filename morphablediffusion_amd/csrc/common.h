@@ -319,6 +319,13 @@ int bwd_silu_fwd(const float* u, float* out, size_t n, hipStream_t s);
 int bwd_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, float wd, int step,
               float inv_scale, const int* skip, hipStream_t s);
 int bwd_finite_check(const float* g, size_t n, int* flag, hipStream_t s);
+// global-norm clipping + EMA (k_bwd.hip): deterministic two-stage sum of squares, the fused step, the arena exchange
+int bwd_grad_sumsq_blocks(size_t n);
+int bwd_grad_sumsq(const float* g, size_t n, float inv_scale, float* partial, hipStream_t s);
+int bwd_grad_norm_final(const float* partial, int count, float max_norm, float* out, int* flag, hipStream_t s);
+int bwd_adamw_ex(float* p, const float* g, float* m, float* v, float* e, size_t n, float lr, float beta1, float beta2, float eps, float wd,
+                 int step, float inv_scale, const float* clip, float ema_decay, const int* skip, hipStream_t s);
+int bwd_swap_f32(float* a, float* b, size_t n, hipStream_t s);
 // k_cond_bwd.hip
 int cbwd_frustum_scatter(const float* d_out, const ViewCam* cams, const int* view_idx, int TN, int D, int S, int V, float vol_len, int persp,
                          float* d_vol, hipStream_t s);

@@ -365,7 +365,12 @@ struct mvd_ctx {
   std::map<std::string, float*> grad_override;
   size_t arena_n = 0;
   float *arena_p = nullptr, *arena_g = nullptr, *arena_m = nullptr, *arena_v = nullptr;
-  bool arena_owned[4] = {false, false, false, false};  // hipMalloc'ed here (true) or adopted from the caller (mvd_train_adopt_arena)
+  float* arena_e = nullptr;  // EMA of the parameters (LitEma's shadow; arena 4): created on first use as a copy of arena_p
+  bool arena_owned[5] = {false, false, false, false, false};  // hipMalloc'ed here (true) or adopted from the caller (mvd_train_adopt_arena)
+  // gradient-norm pass (mvd_train_grad_norm / mvd_train_adamw_step_ex): the first stage's per-block partials, and
+  // norm_dev[0] = the norm, norm_dev[1] = the clipping coefficient the fused step reads
+  float *norm_part = nullptr, *norm_dev = nullptr;
+  size_t norm_part_cap = 0;
   int* found_inf = nullptr;  // device flag of the last gradient finite-check
   // Gradient buckets of the last mvd_train_unet_step, in the order their gradients become final during the backward pass (one per
   // chain of UNet blocks, then one for everything that completes at the end: the stacked embedding / attn2 projections, the

@@ -885,6 +885,8 @@ int build_unet_section(mvd_ctx* c) {
     for (int k = 0; k < 10; ++k) c->conds[k].res = u.image_size >> lvl[k];
     // stacked context projections per level (mvd_ctx::CtxGroup): [nblk * Cc][Cc] fp16 rows copied from the blocks' own packs,
     // gain / bias concatenated.  Plain (not extended-precision) projections only -- proj_context never is.
+    // The copies read the ten packs above, which a re-pack writes on four streams: all of them are joined first.
+    RET_IF(engine_build_join(c));
     c->ctx_groups.clear();
     for (int L = 0; L < 4; ++L) {
       mvd_ctx::CtxGroup gp;

@@ -811,6 +811,128 @@ __global__ __launch_bounds__(256) void finite_check_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// Global-norm clipping + EMA for the optimiser step (mvd_train_adamw_step_ex).  All three kernels stream float4s: an arena range
+// starts on a 64-float boundary and its length is a multiple of 64 (the launchers check 16 bytes / 4 floats).
+//
+// grad_sumsq_kernel: partial[blockIdx] = sum over the block's elements of (g * inv_scale)^2 -- scaled first, so that loss-scaled
+// gradients near the fp16 limit cannot overflow the fp32 partials.  One grid pass covers gridDim * 4096 floats: four float4 loads
+// in flight per thread, one accumulator per load; the wave (xor butterfly) and the block (waves 0..3 in order) reduce in a fixed
+// order, no atomics.  The grid (sumsq_blocks) is a function of n alone, so the value is bit-reproducible from run to run.
+constexpr int SUMSQ_MAX_BLOCKS = 1024;  // 4 blocks per CU, 64 KiB of loads in flight per CU
+inline int sumsq_blocks(size_t n) {
+  const size_t g = (n + 4095) / 4096;
+  return (int)(g > (size_t)SUMSQ_MAX_BLOCKS ? (size_t)SUMSQ_MAX_BLOCKS : (g < 1 ? 1 : g));
+}
+__device__ __forceinline__ float sumsq4(const float4 x, const float s) {
+  const float a = x.x * s, b = x.y * s, c = x.z * s, d = x.w * s;
+  return (a * a + b * b) + (c * c + d * d);
+}
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float4* __restrict__ g, size_t n4, float inv_scale,
+                                                         float* __restrict__ partial) {
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+  size_t i = (size_t)blockIdx.x * 1024 + threadIdx.x;
+  for (; i + 768 < n4; i += (size_t)gridDim.x * 1024) {  // whole groups: four unconditional loads
+    const float4 x0 = g[i], x1 = g[i + 256], x2 = g[i + 512], x3 = g[i + 768];
+    a0 += sumsq4(x0, inv_scale);
+    a1 += sumsq4(x1, inv_scale);
+    a2 += sumsq4(x2, inv_scale);
+    a3 += sumsq4(x3, inv_scale);
+  }
+  // the range's last, partial group (i only grows: no later group of this thread is inside the range)
+  if (i < n4) a0 += sumsq4(g[i], inv_scale);
+  if (i + 256 < n4) a1 += sumsq4(g[i + 256], inv_scale);
+  if (i + 512 < n4) a2 += sumsq4(g[i + 512], inv_scale);
+  float a = (a0 + a1) + (a2 + a3);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+  __shared__ float wsum[4];
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// Second stage, ONE block: the partials of every range summed in index order in double (thread t takes the t-th contiguous
+// chunk, thread 0 then adds the 256 chunk sums in order).  out[0] = norm = sqrt(sum); out[1] = clip_grad_norm_'s coefficient
+// min(1, max_norm / (norm + 1e-6)) (1 when max_norm <= 0: no clipping); *flag (may be null) = 1 when the sum is inf / nan,
+// which one inf / nan element makes it.
+__global__ __launch_bounds__(256) void grad_norm_final_kernel(const float* __restrict__ partial, int count, float max_norm,
+                                                              float* __restrict__ out, int* __restrict__ flag) {
+  __shared__ double chunk[256];
+  const int per = (count + 255) / 256, lo = threadIdx.x * per, hi = lo + per < count ? lo + per : count;
+  double s = 0.0;
+  for (int i = lo; i < hi; ++i) s += (double)partial[i];
+  chunk[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int i = 0; i < 256; ++i) t += chunk[i];
+    const double norm = sqrt(t);
+    double coef = 1.0;
+    if (max_norm > 0.f) {
+      coef = (double)max_norm / (norm + 1e-6);
+      if (coef > 1.0) coef = 1.0;  // a nan norm stays a nan coefficient, as torch's clamp leaves it
+    }
+    out[0] = (float)norm;
+    out[1] = (float)coef;
+    if (flag && !(t <= 1.7e308)) *flag = 1;
+  }
+}
+
+// adamw_kernel's arithmetic per element, in its order, on float4s; the gradient is g * inv_scale * clip (clip: a device scalar,
+// grad_norm_final_kernel's out[1]; null = 1).  EMA: LitEma's shadow update e -= (1 - decay) (e - p_new) on a fifth stream.
+__device__ __forceinline__ void adamw_elem(float& p, const float g, float& m, float& v, const float lr, const float beta1,
+                                           const float beta2, const float eps, const float wd, const float bc1, const float bc2_sqrt,
+                                           const float inv_scale, const float clip) {
+  const float gi = g * inv_scale * clip;
+  float pi = p * (1.f - lr * wd);
+  const float mi = beta1 * m + (1.f - beta1) * gi;
+  const float vi = beta2 * v + (1.f - beta2) * gi * gi;
+  m = mi;
+  v = vi;
+  const float denom = sqrtf(vi) / bc2_sqrt + eps;
+  pi -= (lr / bc1) * (mi / denom);
+  p = pi;
+}
+template <bool EMA>
+__global__ __launch_bounds__(256) void adamw_ex_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m,
+                                                       float4* __restrict__ v, float4* __restrict__ e, size_t n4, float lr, float beta1,
+                                                       float beta2, float eps, float wd, float bc1, float bc2_sqrt, float inv_scale,
+                                                       const float* __restrict__ clip, float one_minus_decay,
+                                                       const int* __restrict__ skip) {
+  if (skip && *skip) return;
+  const float cl = clip ? *clip : 1.f;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    float4 pi = p[i], mi = m[i], vi = v[i];
+    const float4 gi = g[i];
+    float4 ei;
+    if (EMA) ei = e[i];
+    adamw_elem(pi.x, gi.x, mi.x, vi.x, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, inv_scale, cl);
+    adamw_elem(pi.y, gi.y, mi.y, vi.y, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, inv_scale, cl);
+    adamw_elem(pi.z, gi.z, mi.z, vi.z, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, inv_scale, cl);
+    adamw_elem(pi.w, gi.w, mi.w, vi.w, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, inv_scale, cl);
+    m[i] = mi;
+    v[i] = vi;
+    p[i] = pi;
+    if (EMA) {
+      ei.x -= one_minus_decay * (ei.x - pi.x);
+      ei.y -= one_minus_decay * (ei.y - pi.y);
+      ei.z -= one_minus_decay * (ei.z - pi.z);
+      ei.w -= one_minus_decay * (ei.w - pi.w);
+      e[i] = ei;
+    }
+  }
+}
+
+// in-place exchange of two equally long ranges (mvd_train_ema_swap)
+__global__ __launch_bounds__(256) void swap_f32_kernel(float4* __restrict__ a, float4* __restrict__ b, size_t n4) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    const float4 x = a[i], y = b[i];
+    a[i] = y;
+    b[i] = x;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Self-attention backward (CrossAttention.forward modules/attention.py:170-203, self-attention case), flash style on the
 // matrix cores, in the transposed formulation of k_attn.hip (one query -- or, in the dK/dV kernel, one key -- per lane):
 //   kernel 1 (per 128 queries):  lse_q, delta_q = dO_q . O_q;   dQ^T = K^T dS^T  with  dS^T = P^T o (V dO^T - delta)
@@ -1305,6 +1427,46 @@ int bwd_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, 
 int bwd_finite_check(const float* g, size_t n, int* flag, hipStream_t s) {
   if (!n) return 0;
   hipLaunchKernelGGL(finite_check_kernel, dim3(gridn(n, 4096)), dim3(256), 0, s, g, n, flag);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+int bwd_grad_sumsq_blocks(size_t n) { return n ? sumsq_blocks(n) : 0; }
+// partial[0 .. bwd_grad_sumsq_blocks(n)) = the blocks' sums of (g * inv_scale)^2
+int bwd_grad_sumsq(const float* g, size_t n, float inv_scale, float* partial, hipStream_t s) {
+  if (!n) return 0;
+  if ((n & 3) || ((uintptr_t)g & 15)) return mvd_fail("bwd_grad_sumsq: the range must be 16-byte aligned and a multiple of 4 floats long");
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(sumsq_blocks(n)), dim3(256), 0, s, (const float4*)g, n / 4, inv_scale, partial);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+// out[0] = sqrt(sum of the partials), out[1] = the clipping coefficient; *flag = 1 on a non-finite sum (flag may be null)
+int bwd_grad_norm_final(const float* partial, int count, float max_norm, float* out, int* flag, hipStream_t s) {
+  hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, s, partial, count, max_norm, out, flag);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+// e null or ema_decay < 0: no EMA stream; clip null: coefficient 1
+int bwd_adamw_ex(float* p, const float* g, float* m, float* v, float* e, size_t n, float lr, float beta1, float beta2, float eps, float wd,
+                 int step, float inv_scale, const float* clip, float ema_decay, const int* skip, hipStream_t s) {
+  if (!n) return 0;
+  if ((n & 3) || (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)e) & 15))
+    return mvd_fail("bwd_adamw_ex: the ranges must be 16-byte aligned and a multiple of 4 floats long");
+  const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+  const size_t n4 = n / 4;
+  const dim3 grid(gridn(n4, 2048));  // 8 blocks per CU, grid-stride beyond
+  if (e && ema_decay >= 0.f)
+    hipLaunchKernelGGL(adamw_ex_kernel<true>, grid, dim3(256), 0, s, (float4*)p, (const float4*)g, (float4*)m, (float4*)v, (float4*)e, n4,
+                       lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), inv_scale, clip, 1.f - ema_decay, skip);
+  else
+    hipLaunchKernelGGL(adamw_ex_kernel<false>, grid, dim3(256), 0, s, (float4*)p, (const float4*)g, (float4*)m, (float4*)v,
+                       (float4*)nullptr, n4, lr, beta1, beta2, eps, wd, bc1, sqrtf(bc2), inv_scale, clip, 0.f, skip);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+int bwd_swap_f32(float* a, float* b, size_t n, hipStream_t s) {
+  if (!n) return 0;
+  if ((n & 3) || (((uintptr_t)a | (uintptr_t)b) & 15)) return mvd_fail("bwd_swap_f32: the ranges must be 16-byte aligned and a multiple of 4 floats long");
+  hipLaunchKernelGGL(swap_f32_kernel, dim3(gridn(n / 4, 2048)), dim3(256), 0, s, (float4*)a, (float4*)b, n / 4);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }

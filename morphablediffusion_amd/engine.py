@@ -117,7 +117,7 @@ class Engine:
         want = set(expected)
         have = {k for k, v in sd.items() if torch.is_tensor(v)}
         missing = sorted(want - have)
-        side = ("first_stage_model.", "clip_image_encoder.")
+        side = ("first_stage_model.", "clip_image_encoder.", "model_ema.")  # (EMA shadows: SyncMultiviewDiffusion reads them)
         unexpected = sorted(k for k in have - want if not k.startswith(side))
         if strict and (missing or unexpected):
             raise RuntimeError(f"Error(s) in loading state_dict: missing {missing[:5]} (+{max(0, len(missing) - 5)}), "
@@ -126,7 +126,7 @@ class Engine:
         self.has_vae_encoder = any(k.startswith("first_stage_model.encoder.") for k in sd)
         self.has_clip = any(k.startswith("clip_image_encoder.model.visual.") for k in sd)
         for k, v in sd.items():
-            if not torch.is_tensor(v) or not v.dtype.is_floating_point:
+            if not torch.is_tensor(v) or not v.dtype.is_floating_point or k.startswith("model_ema."):
                 continue
             t = v.detach().to(dtype=torch.float32).contiguous()
             shape = (C.c_int64 * max(t.dim(), 1))(*t.shape)
@@ -137,7 +137,7 @@ class Engine:
             self._adopt_arenas()
             # what a checkpoint written after training must carry besides the masters (export_state_dict): references to the
             # tensors the training step does not change (first stage, CLIP, schedule buffers, ...) -- no copies
-            self._loaded_sd = dict(sd)
+            self._loaded_sd = {k: v for k, v in sd.items() if not k.startswith("model_ema.")}
         return IncompatibleKeys(missing, unexpected)
 
     def get_tensor(self, key):
@@ -402,7 +402,8 @@ class Engine:
         self.flat_grads = torch.empty(n, device=self.device, dtype=torch.float32)
         L.check(self.lib.mvd_train_adopt_arena(self._ctx, 0, L.ptr(self.flat_params), n))
         L.check(self.lib.mvd_train_adopt_arena(self._ctx, 1, L.ptr(self.flat_grads), n))
-        self.flat_m = self.flat_v = None
+        self.flat_m = self.flat_v = self.flat_ema = None
+        self.last_grad_norm = None
         self.param_table = {}
         name = C.create_string_buffer(512)
         off, numel, nd = C.c_int64(0), C.c_int64(0), C.c_int(0)
@@ -516,15 +517,51 @@ class Engine:
         self._bucket_snapshot = arena  # keep it alive while the engine writes to it
 
     def adamw_step(self, lr, lr_aux, step, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, inv_scale=1.0, finetune_unet=True,
-                   check=True):
+                   check=True, max_grad_norm=None, ema_decay=None):
         """torch.optim.AdamW on the arena (two learning-rate groups, morphable_diffusion.py:627-646) + in-place re-pack of the
-        fp16 weights.  Returns True when the update was skipped because a gradient was inf / nan (check=False: not read back)."""
+        fp16 weights.  Returns True when the update was skipped because a gradient was inf / nan (check=False: not read back).
+        max_grad_norm: clip the gradients to that global norm first (clip_grad_norm_); ``last_grad_norm`` then holds the norm as
+        a device scalar (no synchronisation).  ema_decay: this step's decay of the EMA weights in ``flat_ema``.  With either set
+        the step is mvd_train_adamw_step_ex (norm pass + one fused kernel), otherwise mvd_train_adamw_step as before."""
         self.ensure_moments()
         skipped = C.c_int(0)
-        L.check(self.lib.mvd_train_adamw_step(self._ctx, lr, lr_aux, betas[0], betas[1], eps, weight_decay, step, inv_scale,
-                                              bool(finetune_unet), C.byref(skipped) if check else None, _stream()))
+        sk = C.byref(skipped) if check else None
+        if max_grad_norm is None and ema_decay is None:
+            L.check(self.lib.mvd_train_adamw_step(self._ctx, lr, lr_aux, betas[0], betas[1], eps, weight_decay, step, inv_scale,
+                                                  bool(finetune_unet), sk, _stream()))
+        else:
+            if ema_decay is not None:
+                self.ensure_ema()
+            clip = float(max_grad_norm) if max_grad_norm is not None else 0.0
+            L.check(self.lib.mvd_train_adamw_step_ex(self._ctx, lr, lr_aux, betas[0], betas[1], eps, weight_decay, step, inv_scale,
+                                                     bool(finetune_unet), sk, clip, -1.0 if ema_decay is None else float(ema_decay),
+                                                     None, _stream()))
+            if clip > 0.0:
+                norm = torch.empty(1, device=self.device, dtype=torch.float32)
+                L.check(self.lib.mvd_train_last_grad_norm(self._ctx, L.ptr(norm), _stream()))
+                self.last_grad_norm = norm[0]
         self.repack()
         return bool(skipped.value)
+
+    def grad_norm(self, inv_scale=1.0, finetune_unet=True):
+        """Global norm of the (un-scaled) gradients the optimiser step would use, as a device scalar: mvd_train_grad_norm, the
+        deterministic two-stage reduction over the step's arena ranges."""
+        out = torch.empty(1, device=self.device, dtype=torch.float32)
+        L.check(self.lib.mvd_train_grad_norm(self._ctx, inv_scale, bool(finetune_unet), L.ptr(out), _stream()))
+        return out[0]
+
+    def ensure_ema(self):
+        """The EMA arena ``flat_ema`` (LitEma's shadow parameters): created as a copy of the parameters, adopted by the library."""
+        if self.flat_ema is None:
+            self.flat_ema = torch.empty_like(self.flat_params)
+            L.check(self.lib.mvd_train_adopt_arena(self._ctx, 4, L.ptr(self.flat_ema), self.flat_ema.numel()))
+        return self.flat_ema
+
+    def ema_swap(self):
+        """Exchange ``flat_params`` and ``flat_ema`` in place (mvd_train_ema_swap); the caller re-packs (``repack``)."""
+        if self.flat_ema is None:
+            raise L.MvdError("ema_swap: no EMA arena (ensure_ema)")
+        L.check(self.lib.mvd_train_ema_swap(self._ctx, _stream()))
 
     def ensure_moments(self):
         """The two Adam moment arenas (zero until the first update), adopted by the library like the master / gradient arenas."""

@@ -315,6 +315,20 @@ class SpatialVolumeNet(nn.Module):
         return {k: torch.cat([o[k] for o in outs], 0) for k in outs[0]}, None
 
 
+def ema_key(key):
+    """Checkpoint key of a parameter's EMA shadow: LitEma's rule (ldm/modules/ema.py -- the module-relative name with every '.'
+    deleted, registered under ``model_ema``), e.g. model.diffusion_model.input_blocks.0.0.weight ->
+    model_ema.diffusion_modelinput_blocks00weight (the family train_morphable_diffusion.py:204 knows).  LitEma shadows
+    ``self.model``, hence the leading ``model.`` is dropped; spatial_volume.* / time_embed.* -- trainable here -- keep their names."""
+    name = key[len("model."):] if key.startswith("model.") else key
+    return "model_ema." + name.replace(".", "")
+
+
+def ema_decay_at(decay, num_updates):
+    """LitEma's warm-up: the decay of update number ``num_updates`` (counted from 1), min(decay, (1 + n) / (10 + n))."""
+    return min(float(decay), (1.0 + num_updates) / (10.0 + num_updates))
+
+
 class SyncMultiviewDiffusion(nn.Module):
     """morphable_diffusion.py:322-646, inference surface (sample / prepare / embed_time / ...)."""
 
@@ -323,16 +337,22 @@ class SyncMultiviewDiffusion(nn.Module):
                  output_num=8, batch_view_num=4, drop_conditions=False, drop_scheme="default",
                  clip_image_encoder_path=None, sample_type="ddim", sample_steps=50, target_elevation=30,
                  first_stage_model=None, clip_image_encoder=None, device="cuda:0", workspace_gb=16.0, precision_level=3,
-                 train_mode=False, loss_scale=65536.0, recompute=True, first_stage_precision="exact"):
+                 train_mode=False, loss_scale=65536.0, recompute=True, first_stage_precision="exact", use_ema=False,
+                 ema_decay=0.9999):
         """train_mode / loss_scale / recompute are not reference kwargs: train_mode keeps fp32 master parameters, gradients and
         Adam moments in the engine (training_step runs the backward pass); loss_scale multiplies dL/dpred so that the fp16 MFMA
         operands of the backward pass stay in range (un-done by the optimiser); recompute = per-block activation checkpointing
         (the reference's use_checkpoint: True), False keeps every activation (fits the 288 GB of an MI355X, faster).
         first_stage_precision: "exact" (extended precision: <= 1e-3 relative; the default since round 4, so that the shipped
         path meets 1e-3 end to end -- decoding 16 views takes ~3x the fast mode's 16 ms, against a 0.7 s sampling loop) or "fast"
-        (fp16 operands: decoded images within 0.8 of an 8-bit step of the reference's)."""
+        (fp16 operands: decoded images within 0.8 of an 8-bit step of the reference's).
+        use_ema / ema_decay (LDM's LitEma; needs train_mode): every optimiser step also moves an exponential moving average of
+        the parameters (``engine.flat_ema``) inside the fused update kernel, with LitEma's warm-up of the decay; ``ema_scope()``
+        samples from the averaged weights, validation_step does, and state_dict() carries them as ``model_ema.*``."""
         if first_stage_precision not in ("fast", "exact"):
             raise ValueError("first_stage_precision must be 'fast' or 'exact'")
+        if use_ema and not train_mode:
+            raise ValueError("use_ema=True needs train_mode=True: the EMA weights are updated by the optimiser step")
         if use_spatial_volume and train_mode:
             raise NotImplementedError("train_mode=True with use_spatial_volume=True: SpatialTime3DNet has no backward pass in the "
                                       "engine (a forward-only training_step(..., backward=False) works without train_mode)")
@@ -344,6 +364,10 @@ class SyncMultiviewDiffusion(nn.Module):
         self.train_conditioner = True  # training_step also back-propagates into spatial_volume.* / time_embed.*
         self.loss_scale = float(loss_scale)
         self.recompute = bool(recompute)
+        self.use_ema = bool(use_ema)
+        self.ema_decay = float(ema_decay)
+        self.ema_num_updates = 0  # LitEma.num_updates: advanced by every optimiser step that is not skipped
+        self.gradient_clip_val = None  # Lightning's Trainer(gradient_clip_val=...): configure_optimizers passes it to ArenaAdamW
         self.global_step = 0
         self.overlap_grad_sync = True  # DDP: bucketed all-reduces started by training_step (False: one flat all-reduce in sync_gradients)
         self._grad_sync = None
@@ -389,14 +413,55 @@ class SyncMultiviewDiffusion(nn.Module):
         self.spatial_volume.invalidate()
         inc = self.engine.load_state_dict(state_dict, strict=strict)
         self.model.diffusion_model._keep_trainable(state_dict, "model.diffusion_model.")
+        if self.use_ema:
+            # model_ema.* of a checkpoint written by state_dict(); a tensor without one starts from the loaded parameter
+            eng = self.engine
+            ema = eng.ensure_ema()  # (a fresh copy of the parameters: load_state_dict rebuilt the arenas)
+            for k, (off, numel, _) in eng.param_table.items():
+                t = state_dict.get(ema_key(k))
+                if torch.is_tensor(t):
+                    ema[off:off + numel].copy_(t.detach().reshape(-1).to(device=ema.device, dtype=torch.float32))
+            n = state_dict.get("model_ema.num_updates")
+            self.ema_num_updates = max(0, int(n)) if n is not None else 0
         return inc
 
     def state_dict(self, *args, **kwargs):
         """Training mode: the checkpoint of the fine-tuned model under the reference's keys (Engine.export_state_dict) -- what
-        Lightning's ModelCheckpoint saves and generate_face.py / the reference itself loads.  Otherwise nn.Module's."""
+        Lightning's ModelCheckpoint saves and generate_face.py / the reference itself loads -- plus, with use_ema, LitEma's
+        buffers: ``model_ema.<name>`` per parameter (ema_key), ``model_ema.decay`` and ``model_ema.num_updates``.  Otherwise
+        nn.Module's."""
         if getattr(self.engine, "train_mode", False) and getattr(self.engine, "_loaded", False):
-            return self.engine.export_state_dict()
+            out = self.engine.export_state_dict()
+            if self.use_ema:
+                eng = self.engine
+                ema = eng.ensure_ema()
+                for k, (off, numel, shape) in eng.param_table.items():
+                    out[ema_key(k)] = ema[off:off + numel].view(shape).detach().clone().to(dtype=out[k].dtype)
+                out["model_ema.decay"] = torch.tensor(self.ema_decay, dtype=torch.float32)
+                out["model_ema.num_updates"] = torch.tensor(self.ema_num_updates, dtype=torch.int64)
+            return out
         return super().state_dict(*args, **kwargs)
+
+    def ema_scope(self):
+        """LatentDiffusion.ema_scope: inside the context the engine runs on the EMA weights -- the parameter and EMA arenas are
+        exchanged in place and the fp16 packs re-derived, both again on exit (two passes over the arenas each way; nothing is
+        copied aside)."""
+        import contextlib
+        if not self.use_ema:
+            raise RuntimeError("ema_scope needs the model created with use_ema=True")
+
+        @contextlib.contextmanager
+        def ctx():
+            eng = self.engine
+            eng.ensure_ema()
+            eng.ema_swap()
+            eng.repack()
+            try:
+                yield
+            finally:
+                eng.ema_swap()
+                eng.repack()
+        return ctx()
 
     def get_viewpoint_embedding(self, batch):
         d_e = torch.deg2rad(batch["target_elevation"]) - torch.deg2rad(batch["input_elevation"])
@@ -552,7 +617,7 @@ class SyncMultiviewDiffusion(nn.Module):
         te = [_arena_param(eng, k) for k in sorted(eng.param_table) if k.startswith("time_embed.")]
         sv = [_arena_param(eng, k) for k in sorted(eng.param_table) if k.startswith("spatial_volume.")]
         paras = [{"params": unet, "lr": lr}, {"params": te, "lr": lr * 10.0}, {"params": sv, "lr": lr * 10.0}]
-        opt = ArenaAdamW(self, paras, lr=lr)
+        opt = ArenaAdamW(self, paras, lr=lr, max_grad_norm=self.gradient_clip_val)
         if self.scheduler_config is None:
             return [opt], []
         sched = LambdaLinearScheduler(**self.scheduler_config.get("params", {}))
@@ -617,7 +682,9 @@ class SyncMultiviewDiffusion(nn.Module):
             batch_ = {}
             for k, v in batch.items():
                 batch_[k] = {k_: v_[:self.output_num] for k_, v_ in v.items()} if isinstance(v, dict) else v[:self.output_num]
-            x_sample = self.sample(self.sampler, batch_, self.cfg_scale, self.batch_view_num)
+            import contextlib
+            with self.ema_scope() if self.use_ema else contextlib.nullcontext():  # LDM validates from the averaged weights
+                x_sample = self.sample(self.sampler, batch_, self.cfg_scale, self.batch_view_num)
             from pathlib import Path
             from .batch import save_image_grid
             out = Path(self.image_dir) / "images" / "val"
@@ -791,11 +858,19 @@ class ArenaAdamW(torch.optim.Optimizer):
     """torch.optim.AdamW semantics (the reference's optimiser, morphable_diffusion.py:642) on the engine's flat arenas:
     param_groups[0] = the UNet group, [1] / [2] = time_embed / spatial_volume (one learning rate: the reference gives both
     10 lr).  step() = mvd_train_adamw_step (fused HIP kernel per contiguous group range, un-does the loss scale, skips the
-    update when a gradient overflowed) + in-place re-pack of the fp16 weights.  LR schedulers act on param_groups as usual."""
+    update when a gradient overflowed) + in-place re-pack of the fp16 weights.  LR schedulers act on param_groups as usual.
+    max_grad_norm (Lightning's gradient_clip_val): the gradients are clipped to that global norm inside the step
+    (clip_grad_norm_'s rule over the parameters the step updates); ``last_grad_norm`` is the norm before clipping, a device
+    scalar (reading it is the caller's synchronisation, the step adds none).  A model with use_ema gets its EMA update from the
+    same kernel."""
 
-    def __init__(self, model, params, lr=5e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
+    def __init__(self, model, params, lr=5e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError("max_grad_norm must be positive (None: no clipping)")
         self.model = model
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.last_grad_norm = None
         self.steps_done = 0
         self.steps_skipped = 0
         self.growth_interval = 2000  # torch.cuda.amp.GradScaler's defaults: x2 after 2000 clean steps, x0.5 on overflow
@@ -815,9 +890,16 @@ class ArenaAdamW(torch.optim.Optimizer):
         g0 = self.param_groups[0]
         aux = self.param_groups[1]["lr"] if len(self.param_groups) > 1 else g0["lr"]
         m = self.model
+        use_ema = getattr(m, "use_ema", False)
+        ema = ema_decay_at(m.ema_decay, m.ema_num_updates + 1) if use_ema else None  # LitEma: num_updates += 1, then the decay
+        extra = {k: v for k, v in (("max_grad_norm", self.max_grad_norm), ("ema_decay", ema)) if v is not None}
         skipped = m.engine.adamw_step(g0["lr"], aux, self.steps_done + 1, betas=g0["betas"], eps=g0["eps"],
                                       weight_decay=g0["weight_decay"], inv_scale=1.0 / m.loss_scale,
-                                      finetune_unet=m.finetune_unet, check=self.dynamic_scale)
+                                      finetune_unet=m.finetune_unet, check=self.dynamic_scale, **extra)
+        if self.max_grad_norm is not None:
+            self.last_grad_norm = m.engine.last_grad_norm
+        if use_ema and not skipped:
+            m.ema_num_updates += 1
         if skipped:  # torch.cuda.amp.GradScaler's rule: back off and try again
             self.steps_skipped += 1
             self._clean = 0
@@ -843,7 +925,8 @@ class ArenaAdamW(torch.optim.Optimizer):
         eng.ensure_moments()
         sd["arena"] = {"exp_avg": eng.flat_m.detach().clone(), "exp_avg_sq": eng.flat_v.detach().clone(),
                        "step": self.steps_done, "steps_skipped": self.steps_skipped, "clean_steps": self._clean,
-                       "loss_scale": float(self.model.loss_scale), "numel": int(eng.flat_params.numel())}
+                       "loss_scale": float(self.model.loss_scale), "numel": int(eng.flat_params.numel()),
+                       "max_grad_norm": self.max_grad_norm}
         return sd
 
     def load_state_dict(self, state_dict):
@@ -887,6 +970,8 @@ class ArenaAdamW(torch.optim.Optimizer):
         self.steps_skipped = int(arena.get("steps_skipped", 0))
         self._clean = int(arena.get("clean_steps", 0))
         self.model.loss_scale = float(arena["loss_scale"])  # dynamic_scale follows it (property)
+        if "max_grad_norm" in arena:  # (a checkpoint from before clipping existed keeps this optimiser's setting)
+            self.max_grad_norm = None if arena["max_grad_norm"] is None else float(arena["max_grad_norm"])
 
 
 class LambdaLinearScheduler:
