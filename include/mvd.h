@@ -300,7 +300,8 @@ int mvd_train_unet_step(mvd_ctx* ctx, const float* x, const int64_t* timesteps, 
  * returns for that sample, after the condition-dropout mask) into the gradients of spatial_volume.* and time_embed.*
  * (accumulated into the arena).  x_noisy [N,4,s,s], v_embed [N,view_dim] device pointers; timestep / target_index host values.
  * dbg_* (each may be NULL): dL/d(32^3 volume) [64,V,V,V], dL/d(fused vertex features) [Nv,16], dL/d(2-D encoder output)
- * [N,16,s,s], dL/d(step embedding) [time_dim] -- for the parity tests.  The three gather adjoints use fp32 atomic adds. */
+ * [N,16,s,s], dL/d(step embedding) [time_dim] -- for the parity tests.  The three gather adjoints use fp32 atomic adds unless
+ * mvd_train_set_deterministic turned the deterministic mode on. */
 int mvd_train_conditioner_backward(mvd_ctx* ctx, const float* x_noisy, int64_t timestep, const float* v_embed, int n_views,
                                    int target_index, const float* dsrc0, const float* dsrc1, const float* dsrc2, const float* dsrc3,
                                    float* dbg_dvolume, float* dbg_dfused, float* dbg_dfeats, float* dbg_dtembed, void* stream);
@@ -312,6 +313,33 @@ int mvd_train_conditioner_backward_batch(mvd_ctx* ctx, int B, const int* slots, 
                                          const float* v_embed, int n_views, const int* target_index, const float* dsrc0,
                                          const float* dsrc1, const float* dsrc2, const float* dsrc3, float* dbg_dvolume,
                                          float* dbg_dfused, float* dbg_dfeats, float* dbg_dtembed, void* stream);
+/* Deterministic training mode (opt-in, default off; the reference has none: grid_sample's CUDA backward raises under
+ * torch.use_deterministic_algorithms).  The conditioner's backward is the one part of the training step that does not repeat bit
+ * for bit: the adjoints of its three gathers -- frustum gather (morphable_diffusion.py:265-320), lattice gather of the sparse
+ * CNN's rows (:232-257) and vertex gather (:203-231) -- and the fold of duplicate vertices' rows add with fp32 atomics in arrival
+ * order.  With the mode on they run as gathers: no floating-point atomic, every sum in an order fixed by indices alone (view,
+ * depth, row, column of the frustum points; z, y, x of the lattice points; vertex index, then voxel index), so that two backward
+ * calls on the same inputs leave bit-identical gradients.  Values agree with the atomic forms to fp32 summation order.
+ *   mvd_train_set_deterministic  any time on a training context (mvd_train_enable), takes effect from the next backward call; an
+ *                                error on any other context, and when the sparse CNN runs in its site form (MVD_SPARSE_VALU).
+ *   mvd_op_frustum_adjoint       parity hooks: ONE of the three adjoints on device buffers of the caller, deterministic != 0 the
+ *   mvd_op_latent_adjoint        gather form, 0 the atomic form (which accumulates: the hook zeroes the output first); cameras and
+ *   mvd_op_vertex_adjoint        mesh of the active slot, any finalized context with a mesh / cameras set.  Channels-last fp32:
+ *                                frustum  d_out [TN,D,S,S,64] = dL/d(gathered frustum), view_idx [TN] HOST -> d_vol [V,V,V,64];
+ *                                latent   d_vol [V,V,V,64] -> d_rows [n_rows,64], the rows of the coarsest sparse level in the
+ *                                         order of mvd_rulebook_table(5); *n_rows_out (may be NULL) = n_rows, d_rows == NULL
+ *                                         only queries it;
+ *                                vertex   d_vf [n_views,Nv,16] = dL/d(per-view vertex features), view_idx [n_views] HOST ->
+ *                                         d_feats [n_views,s,s,16] = dL/d(2-D encoder maps).
+ *   mvd_probe_adjoint_calls      out[6] = launches so far of the frustum / latent / vertex adjoint in the atomic form (0..2) and
+ *                                in the gather form (3..5), hooks included. */
+int mvd_train_set_deterministic(mvd_ctx* ctx, int on);
+int mvd_op_frustum_adjoint(mvd_ctx* ctx, const float* d_out, const int32_t* view_idx, int TN, int D, int S, int deterministic,
+                           float* d_vol, void* stream);
+int mvd_op_latent_adjoint(mvd_ctx* ctx, const float* d_vol, int deterministic, float* d_rows, int32_t* n_rows_out, void* stream);
+int mvd_op_vertex_adjoint(mvd_ctx* ctx, const float* d_vf, const int32_t* view_idx, int n_views, int deterministic, float* d_feats,
+                          void* stream);
+int mvd_probe_adjoint_calls(mvd_ctx* ctx, int64_t* out);
 /* Parity hook: the backward pass of ONE DepthTransformer (attention.py:49-84; cond_index 0 = middle_conditions, 1 + k =
  * output_conditions.k) given its input x [B,dim,H,W], its context volume [B,C_l,D_l,H,W] and dL/d(output) [B,dim,H,W]:
  * dx, dcontext (may be NULL) are written, parameter gradients accumulated into the arena.  depth0 = D of the finest level. */

@@ -333,6 +333,18 @@ int cbwd_latent_scatter(const float* d_vol, const int* grid, int gd, int gh, int
                         int V, float vol_len, float* d_rows, hipStream_t s);
 int cbwd_vertex_scatter(const float* d_out, const ViewCam* cams, const int* view_idx, int n_views, const float* verts, int Nv, int V,
                         float vol_len, int S, int persp, float* d_feats, hipStream_t s);
+// the same adjoints as gathers (deterministic mode): no floating-point atomics, outputs written, not accumulated into
+int cbwd_frustum_gather_adj(const float* d_out, const ViewCam* cams, const int* view_idx, int TN, int D, int S, int V, float vol_len,
+                            int persp, float* pos, float* d_vol, hipStream_t s);
+int cbwd_latent_gather_adj(const float* d_vol, const int* grid, int gd, int gh, int gw, const float* min_xyz, const int* out_sh, float voxel,
+                           int V, float vol_len, float* d_rows, hipStream_t s);
+size_t cbwd_vertex_adj_scratch_bytes(int n_views, int Nv, int V);
+int cbwd_vertex_gather_adj(const float* d_out, const ViewCam* cams, const int* view_idx, int n_views, const float* verts, int Nv, int V,
+                           float vol_len, int S, int persp, void* scratch, float* d_feats, hipStream_t s);
+int cbwd_lattice_to_views_adj(const float* d_lat, const ViewCam* cams, const int* view_idx, int n_views, const int* vox_list,
+                              const int* n_ptr, int n_max, int V, float vol_len, int S, int persp, float4* rec, float* d_feats,
+                              hipStream_t s);
+int cbwd_sparse_fold_dups_det(float* d, const int* nbr, int n, int C, int* flag, hipStream_t s);
 int cbwd_fuse_scratch_floats(int Nv);
 int cbwd_fuse(const float* d_fused, const float* vf, const float* w, int n_views, int Nv, int total_views, float* d_vf, float* dw, float* db,
               float* part, hipStream_t s);

@@ -338,6 +338,11 @@ struct mvd_ctx {
   // key, so the reference's optimiser groups are contiguous ranges); `raw` keeps pointing into it, gradients / Adam moments
   // live in arenas of the same layout, and engine_repack re-derives every packed fp16 weight from the masters in place.
   bool train_mode = false;
+  // mvd_train_set_deterministic: the conditioner backward's three gather adjoints (and the fold of duplicate vertices' rows) run
+  // as gathers with index-ordered sums instead of fp32 atomic scatters (k_cond_bwd.hip); read at the start of each backward call.
+  bool deterministic = false;
+  // launches of the frustum / latent / vertex adjoint so far: [0..2] the atomic forms, [3..5] the gather forms (mvd_probe_adjoint_calls)
+  int64_t adjoint_calls[6] = {0, 0, 0, 0, 0, 0};
   // which optimiser groups received a gradient since the last mvd_train_zero_grad (1: the UNet, 2: time_embed / spatial_volume):
   // mvd_train_adamw_step leaves the others alone, as torch.optim.AdamW skips parameters whose .grad is None
   bool grad_touched[3] = {false, false, false};

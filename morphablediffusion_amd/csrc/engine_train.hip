@@ -1094,6 +1094,36 @@ struct CondSample {
   const int* sp_nbr[9];
   int sp_nout[9], sp_nin[9];
 };
+
+// The conditioner's three gather adjoints on the ACTIVE slot's cameras / mesh, in the form asked for: det == false the fp32-atomic
+// scatters (they accumulate: the caller zeroes the output first), det == true the gather forms of the deterministic mode (they
+// write every element; their scratch comes from the workspace).  Counted per form in mvd_ctx::adjoint_calls.
+int adj_frustum(mvd_ctx* c, bool det, const float* d_out, const int* view_idx, int TN, int D, int S, float* d_vol, hipStream_t s) {
+  const int V = c->v.spatial_volume_size, persp = c->v.projection == 0;
+  ++c->adjoint_calls[det ? 3 : 0];
+  if (!det) return cbwd_frustum_scatter(d_out, c->cams, view_idx, TN, D, S, V, c->v.spatial_volume_length, persp, d_vol, s);
+  WsScope sc(c, WS_TEMP);
+  float* pos = ws_alloc<float>(c, (size_t)TN * D * S * S * 3);
+  WS_CHECK(pos);
+  return cbwd_frustum_gather_adj(d_out, c->cams, view_idx, TN, D, S, V, c->v.spatial_volume_length, persp, pos, d_vol, s);
+}
+int adj_latent(mvd_ctx* c, bool det, const float* d_vol, float* d_rows, hipStream_t s) {
+  const MeshTables& m = c->mesh;
+  ++c->adjoint_calls[det ? 4 : 1];
+  return (det ? cbwd_latent_gather_adj : cbwd_latent_scatter)(d_vol, m.grid2, m.shape[2][0], m.shape[2][1], m.shape[2][2], m.min_xyz,
+                                                              m.out_sh, c->v.voxel_size, c->v.spatial_volume_size,
+                                                              c->v.spatial_volume_length, d_rows, s);
+}
+int adj_vertex(mvd_ctx* c, bool det, const float* d_vf, const int* view_idx, int n_views, float* d_feats, hipStream_t s) {
+  const MeshTables& m = c->mesh;
+  const int V = c->v.spatial_volume_size, S = c->u.image_size, persp = c->v.projection == 0;
+  ++c->adjoint_calls[det ? 5 : 2];
+  if (!det) return cbwd_vertex_scatter(d_vf, c->cams, view_idx, n_views, m.verts, m.Nv, V, c->v.spatial_volume_length, S, persp, d_feats, s);
+  WsScope sc(c, WS_TEMP);
+  void* scratch = c->ws.alloc(cbwd_vertex_adj_scratch_bytes(n_views, m.Nv, V));
+  WS_CHECK(scratch);
+  return cbwd_vertex_gather_adj(d_vf, c->cams, view_idx, n_views, m.verts, m.Nv, V, c->v.spatial_volume_length, S, persp, scratch, d_feats, s);
+}
 }  // namespace
 
 // Backward of the conditioner for B samples whose tables sit in slots[0..B): the per-sample stages (2-D encoder, gathers, sparse
@@ -1123,6 +1153,7 @@ int engine_train_conditioner_backward_batch(mvd_ctx* c, int B, const int* slots,
   };
   const int N = n_views, S = c->u.image_size, HW = S * S, rows = N * HW, td = c->v.time_dim, vd = c->v.view_dim;
   const int V = c->v.spatial_volume_size, persp = c->v.projection == 0;
+  const bool det = c->deterministic;  // the gather forms of the three adjoints write every element: their zero fills are skipped
   const std::string SV = "spatial_volume.", FV = SV + "frustum_volume_feats.";
   auto F = [&](size_t n) { return ws_alloc<float>(c, n); };
   auto H16 = [&](size_t n) { return ws_alloc<half_t>(c, n); };
@@ -1167,7 +1198,7 @@ int engine_train_conditioner_backward_batch(mvd_ctx* c, int B, const int* slots,
   float* d_gath_all = F((size_t)B * vox[0] * 64);
   float *feats_all = F((size_t)B * rows * 16), *d_feats_all = F((size_t)B * rows * 16);
   WS_CHECK(t_emb_all && d_temb_all && vt_all && pre_f_all && gath_all && d_gath_all && feats_all && d_feats_all);
-  HIP_CHECK_RET(hipMemsetAsync(d_feats_all, 0, (size_t)B * rows * 16 * sizeof(float), s));
+  if (!det) HIP_CHECK_RET(hipMemsetAsync(d_feats_all, 0, (size_t)B * rows * 16 * sizeof(float), s));
   HIP_CHECK_RET(hipMemsetAsync(d_temb_all, 0, (size_t)B * td * sizeof(float), s));
   std::vector<CondSample> st(B);
 
@@ -1418,12 +1449,13 @@ int engine_train_conditioner_backward_batch(mvd_ctx* c, int B, const int* slots,
   float* d_vol = F((size_t)V * V * V * 64);
   float* d_cur = F((size_t)sp_nout[8] * 64);
   WS_CHECK(d_vol && d_cur);
-  HIP_CHECK_RET(hipMemsetAsync(d_vol, 0, (size_t)V * V * V * 64 * sizeof(float), s));
-  HIP_CHECK_RET(hipMemsetAsync(d_cur, 0, (size_t)sp_nout[8] * 64 * sizeof(float), s));
-  RET_IF(cbwd_frustum_scatter(d_gath_all + (size_t)bi * vox[0] * 64, c->cams, vidx + N, 1, Dl[0], Sl[0], V, c->v.spatial_volume_length, persp, d_vol, s));
+  if (!det) {
+    HIP_CHECK_RET(hipMemsetAsync(d_vol, 0, (size_t)V * V * V * 64 * sizeof(float), s));
+    HIP_CHECK_RET(hipMemsetAsync(d_cur, 0, (size_t)sp_nout[8] * 64 * sizeof(float), s));
+  }
+  RET_IF(adj_frustum(c, det, d_gath_all + (size_t)bi * vox[0] * 64, vidx + N, 1, Dl[0], Sl[0], d_vol, s));
   if (dbg_dvolume) RET_IF(launch_nhwc_to_nchw(d_vol, 64, 1, 64, V * V * V, dbg_dvolume, s));
-  RET_IF(cbwd_latent_scatter(d_vol, m.grid2, m.shape[2][0], m.shape[2][1], m.shape[2][2], m.min_xyz, m.out_sh, c->v.voxel_size, V,
-                             c->v.spatial_volume_length, d_cur, s));
+  RET_IF(adj_latent(c, det, d_vol, d_cur, s));
   mark("bwd: scatters");
   // sparse voxel CNN
   for (int i = 8; i >= 0; --i) {
@@ -1446,7 +1478,13 @@ int engine_train_conditioner_backward_batch(mvd_ctx* c, int B, const int* slots,
       // flipped (submanifold) or through the inverse table (strided) -- no atomics, no zero fill.  At level 0 the gradients of
       // duplicate vertices' rows are folded into their representatives' first (the table is symmetric over those only).
       const bool lvl0_subm = !L.strided && sp_nbr[i] == m.nbr_subm[0];
-      if (lvl0_subm) RET_IF(cbwd_sparse_fold_dups(d_cur, sp_nbr[i], sp_nout[i], L.cout, s));
+      if (lvl0_subm && !det) RET_IF(cbwd_sparse_fold_dups(d_cur, sp_nbr[i], sp_nout[i], L.cout, s));
+      if (lvl0_subm && det) {  // the same fold with the duplicates' rows added in row order
+        WsScope sc(c, WS_TEMP);
+        int* flag = (int*)F((size_t)sp_nout[i]);
+        WS_CHECK(flag);
+        RET_IF(cbwd_sparse_fold_dups_det(d_cur, sp_nbr[i], sp_nout[i], L.cout, flag, s));
+      }
       {
         WsScope sc(c, WS_TEMP);
         float* dw_part = F((size_t)cbwd_sparse_wgrad_chunks(sp_nout[i]) * 27 * L.cin * L.cout);
@@ -1463,6 +1501,8 @@ int engine_train_conditioner_backward_batch(mvd_ctx* c, int B, const int* slots,
       }
       RET_IF(launch_sparse_conv(d_cur, table, sp_nin[i], L.cout, L.cin, nullptr, L.wd, nullptr, nullptr, d_in, s, lvl0_subm ? 1 : 0));
     } else {
+      if (det) return mvd_fail("deterministic mode: this sparse layer has no matrix-core form (its site-form data gradient adds with "
+                               "fp32 atomics); unset MVD_SPARSE_VALU");
       HIP_CHECK_RET(hipMemsetAsync(d_in, 0, (size_t)sp_nin[i] * L.cin * sizeof(float), s));
       WsScope sc(c, WS_TEMP);
       float* dw_part = F((size_t)cbwd_sparse_wgrad_chunks(sp_nout[i]) * 27 * L.cin * L.cout);
@@ -1481,7 +1521,7 @@ int engine_train_conditioner_backward_batch(mvd_ctx* c, int B, const int* slots,
   WS_CHECK(d_vf && fuse_part);
   RET_IF(cbwd_fuse(d_fused, vf, c->fuse_w, N, Nv, N, d_vf, engine_grad(c, SV + "smpl_feature_extractor.conv0.weight"),
                    engine_grad(c, SV + "smpl_feature_extractor.conv0.bias"), fuse_part, s));
-  RET_IF(cbwd_vertex_scatter(d_vf, c->cams, vidx, N, m.verts, Nv, V, c->v.spatial_volume_length, S, persp, d_feats, s));
+  RET_IF(adj_vertex(c, det, d_vf, vidx, N, d_feats, s));
   if (dbg_dfeats) RET_IF(launch_nhwc_to_nchw(d_feats, 16, N, 16, HW, dbg_dfeats, s));
   mark("bwd: fuse + vertex scatter");
   return 0;
@@ -1765,4 +1805,74 @@ int mvd_op_tgemm(mvd_ctx* c, int M, int N, int K, const float* a, int a_f16, int
   }
   if (poison) RET_IF(ws_poison(c, s));
   return tgemm(c, A, Bm, out, ldc, M, N, K, accum != 0, s, xp != 0);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// deterministic mode (include/mvd.h): the switch, and the conditioner's three gather adjoints one at a time on the caller's
+// buffers in either form, through the same dispatch functions the backward pass uses (tests/test_gpu_train_deterministic.py)
+// ---------------------------------------------------------------------------------------------------------------------
+int mvd_train_set_deterministic(mvd_ctx* c, int on) {
+  if (!c) return mvd_fail("null context");
+  if (!c->train_mode) return mvd_fail("mvd_train_set_deterministic: not a training context (mvd_train_enable)");
+  if (on && c->finalized)  // (before finalize the layers are not packed yet: the backward call checks again)
+    for (const SparseLayerW& L : c->sparse)
+      if (!L.wp || !L.wd)
+        return mvd_fail("mvd_train_set_deterministic: the sparse CNN runs in its site form (MVD_SPARSE_VALU), whose data gradient adds "
+                        "with fp32 atomics; the mode needs the matrix-core form");
+  c->deterministic = on != 0;
+  return 0;
+}
+int mvd_probe_adjoint_calls(mvd_ctx* c, int64_t* out) {
+  if (!c || !out) return mvd_fail("mvd_probe_adjoint_calls: null argument");
+  for (int i = 0; i < 6; ++i) out[i] = c->adjoint_calls[i];
+  return 0;
+}
+namespace {
+// host view indices, checked against the active slot's cameras -> device copy in the workspace
+int hook_views(mvd_ctx* c, const int32_t* view_idx, int n, const int** out, hipStream_t s) {
+  if (!c->cams) return mvd_fail("adjoint hook: mvd_set_cameras must be called first");
+  for (int i = 0; i < n; ++i)
+    if (view_idx[i] < 0 || view_idx[i] >= c->n_cams) return mvd_fail("adjoint hook: view index outside the cameras of the active slot");
+  int* d = ws_alloc<int>(c, (size_t)n);
+  WS_CHECK(d);
+  HIP_CHECK_RET(hipMemcpyAsync(d, view_idx, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+  *out = d;
+  return 0;
+}
+}  // namespace
+int mvd_op_frustum_adjoint(mvd_ctx* c, const float* d_out, const int32_t* view_idx, int TN, int D, int S, int deterministic, float* d_vol,
+                           void* stream) {
+  RET_IF(hook_begin(c));
+  if (!d_out || !view_idx || !d_vol || TN <= 0 || D <= 0 || S <= 1) return mvd_fail("mvd_op_frustum_adjoint: bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  WsScope ws_scope(c);
+  const int* vidx;
+  RET_IF(hook_views(c, view_idx, TN, &vidx, s));
+  const size_t V = (size_t)c->v.spatial_volume_size;
+  if (!deterministic) HIP_CHECK_RET(hipMemsetAsync(d_vol, 0, V * V * V * 64 * sizeof(float), s));
+  return adj_frustum(c, deterministic != 0, d_out, vidx, TN, D, S, d_vol, s);
+}
+int mvd_op_latent_adjoint(mvd_ctx* c, const float* d_vol, int deterministic, float* d_rows, int32_t* n_rows_out, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!c->mesh.Nv) return mvd_fail("mvd_op_latent_adjoint: mvd_set_mesh must be called first");
+  const int n_rows = c->mesh.n_sites[2];
+  if (n_rows_out) *n_rows_out = n_rows;
+  if (!d_rows) return 0;  // row-count query
+  if (!d_vol) return mvd_fail("mvd_op_latent_adjoint: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  if (!deterministic) HIP_CHECK_RET(hipMemsetAsync(d_rows, 0, (size_t)n_rows * 64 * sizeof(float), s));
+  return adj_latent(c, deterministic != 0, d_vol, d_rows, s);
+}
+int mvd_op_vertex_adjoint(mvd_ctx* c, const float* d_vf, const int32_t* view_idx, int n_views, int deterministic, float* d_feats,
+                          void* stream) {
+  RET_IF(hook_begin(c));
+  if (!d_vf || !view_idx || !d_feats || n_views <= 0) return mvd_fail("mvd_op_vertex_adjoint: bad argument");
+  if (!c->mesh.Nv) return mvd_fail("mvd_op_vertex_adjoint: mvd_set_mesh must be called first");
+  hipStream_t s = (hipStream_t)stream;
+  WsScope ws_scope(c);
+  const int* vidx;
+  RET_IF(hook_views(c, view_idx, n_views, &vidx, s));
+  const size_t S = (size_t)c->u.image_size;
+  if (!deterministic) HIP_CHECK_RET(hipMemsetAsync(d_feats, 0, (size_t)n_views * S * S * 16 * sizeof(float), s));
+  return adj_vertex(c, deterministic != 0, d_vf, vidx, n_views, d_feats, s);
 }

@@ -4,6 +4,9 @@
 // the transposing im2col for the frustum network's 3-D convolutions.
 // The three scatters use hardware fp32 atomic adds (unsafeAtomicAdd: the returning CAS loop of plain atomicAdd is 30x slower here) (unordered: the conditioner's gradients are reproducible to rounding, not bit
 // for bit -- the UNet's are); everything else has fixed summation orders.
+// Those atomic forms are the DEFAULT.  The deterministic mode (mvd_train_set_deterministic) runs the three adjoints, and the fold
+// of duplicate vertices' rows, as gathers instead (cbwd_*_gather_adj, cbwd_lattice_to_views_adj, cbwd_sparse_fold_dups_det below):
+// no floating-point atomic to HBM or LDS, every sum in an order fixed by indices alone, every output element written.
 #include "common.h"
 
 namespace {
@@ -168,6 +171,398 @@ __global__ __launch_bounds__(1024) void vertex_scatter_kernel(const float* __res
   for (int i = threadIdx.x; i < S * S * 16; i += blockDim.x) {
     const float v = s_img[(i & 15) * SS + (i >> 4)];
     if (v != 0.f) unsafeAtomicAdd(fv + i, v);
+  }
+}
+
+// ---- deterministic mode: the same three adjoints as GATHERS -- one thread owns an output element, finds its contributions and
+// adds them in an order that is a function of indices only; no floating-point atomic, every output element written (no zero
+// fill).  Candidates come from a conservative index box, membership is decided by the forward's own position arithmetic, so
+// every (point, corner) pair is counted exactly once whatever the box's rounding.
+constexpr float BOX_FINITE = 1e9f;  // a box bound beyond this (or NaN) means: scan everything
+
+// Lattice positions pos[point][3] of all frustum points, one thread per point: the head of frustum_scatter_kernel statement for
+// statement.  The gather below reads them instead of recomputing them per candidate: once per point, not once per (candidate,
+// channel quad), and -- a straight-line kernel of the same expressions gets the same fused multiply-adds, whereas the same code
+// inside the gather's loops is fused differently after hoisting -- the same fp32 positions as the atomic form's.  (With
+// positions recomputed in the loops the two forms' dL/d(volume) differed by 1.07e-5 relative L2 at V = 32, with positions in
+// double by 0.99e-5: fp32 rounding of x * depth against Pinv's small entries, not summation order.)
+__global__ __launch_bounds__(256) void frustum_positions_kernel(const ViewCam* __restrict__ cams, const int* __restrict__ view_idx, int TN,
+                                                                int D, int S, int V, float vol_len, int persp, float* __restrict__ pos) {
+  const long pt = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long npts = (long)TN * D * S * S;
+  if (pt >= npts) return;
+  const int x = (int)(pt % S), y = (int)((pt / S) % S), d = (int)((pt / ((long)S * S)) % D), tv = (int)(pt / ((long)S * S * D));
+  const ViewCam cam = cams[view_idx[tv]];
+  const float depth = linspace_at(0.f, 1.f, D, d) * (cam.far_ - cam.near_) + cam.near_;
+  float wx, wy, wz;
+  if (persp) {
+    const float a = (float)x * depth, b = (float)y * depth, c = depth;
+    wx = cam.Pinv[0] * a + cam.Pinv[1] * b + cam.Pinv[2] * c + cam.Pinv[3];
+    wy = cam.Pinv[4] * a + cam.Pinv[5] * b + cam.Pinv[6] * c + cam.Pinv[7];
+    wz = cam.Pinv[8] * a + cam.Pinv[9] * b + cam.Pinv[10] * c + cam.Pinv[11];
+  } else {
+    const float gx = 2.f * (float)x / (float)(S - 1) - 1.f, gy = 2.f * (float)y / (float)(S - 1) - 1.f;
+    const float a = cam.Kinv[0] * gx + cam.Kinv[1] * gy + cam.Kinv[2];
+    const float b = cam.Kinv[3] * gx + cam.Kinv[4] * gy + cam.Kinv[5];
+    const float c = depth;
+    wx = cam.Pinv[0] * a + cam.Pinv[1] * b + cam.Pinv[2] * c + cam.Pinv[3];
+    wy = cam.Pinv[4] * a + cam.Pinv[5] * b + cam.Pinv[6] * c + cam.Pinv[7];
+    wz = cam.Pinv[8] * a + cam.Pinv[9] * b + cam.Pinv[10] * c + cam.Pinv[11];
+  }
+  const float px = (wx / vol_len + 1.f) * 0.5f * (float)(V - 1), py = (wy / vol_len + 1.f) * 0.5f * (float)(V - 1),
+              pz = (wz / vol_len + 1.f) * 0.5f * (float)(V - 1);
+  pos[pt * 3 + 0] = px;
+  pos[pt * 3 + 1] = py;
+  pos[pt * 3 + 2] = pz;
+}
+
+// [lo, hi] := the indices 0..n-1 inside [mn - 1, mx + 1]; false when a bound is not a usable number
+__device__ __forceinline__ bool index_window(float mn, float mx, int n, int& lo, int& hi) {
+  if (!(fabsf(mn) < BOX_FINITE) || !(fabsf(mx) < BOX_FINITE)) return false;
+  lo = max(0, (int)floorf(mn) - 1);
+  hi = min(n - 1, (int)ceilf(mx) + 1);
+  return true;
+}
+
+// Index box (d, y, x) of the frustum points that can have lattice voxel (xx, yy, zz) among their eight corners: they lie in the
+// voxel's +-1 cube, whose image under the inverse of the forward's map (the affine Pinv inverted here, then the perspective
+// divide or the inverse of Kinv's 2x2 block) is inside the bounding box of its eight corners' images -- as long as the
+// projective map keeps its orientation on the cube, i.e. every corner's depth is at least the forward's clamp.  Otherwise, and
+// whenever a bound is not a finite number, the box is the whole frustum.
+__device__ void frustum_box(const ViewCam& cam, int xx, int yy, int zz, int D, int S, int V, float vol_len, int persp, int lo[3],
+                            int hi[3]) {
+  lo[0] = lo[1] = lo[2] = 0;
+  hi[0] = D - 1;
+  hi[1] = hi[2] = S - 1;
+  const float* m = cam.Pinv;
+  const float c00 = m[5] * m[10] - m[6] * m[9], c01 = m[2] * m[9] - m[1] * m[10], c02 = m[1] * m[6] - m[2] * m[5];
+  const float c10 = m[6] * m[8] - m[4] * m[10], c11 = m[0] * m[10] - m[2] * m[8], c12 = m[2] * m[4] - m[0] * m[6];
+  const float c20 = m[4] * m[9] - m[5] * m[8], c21 = m[1] * m[8] - m[0] * m[9], c22 = m[0] * m[5] - m[1] * m[4];
+  const float inv_det = 1.f / (m[0] * c00 + m[1] * c10 + m[2] * c20);
+  const float k_det = cam.Kinv[0] * cam.Kinv[4] - cam.Kinv[1] * cam.Kinv[3];
+  const float hs = 0.5f * (float)(S - 1), d_scale = (float)(D - 1) / (cam.far_ - cam.near_);
+  float mn[3] = {3e38f, 3e38f, 3e38f}, mx[3] = {-3e38f, -3e38f, -3e38f};
+  bool ok = true;
+#pragma unroll
+  for (int corner = 0; corner < 8; ++corner) {
+    const float lx = (float)(xx + ((corner & 1) ? 1 : -1)), ly = (float)(yy + ((corner & 2) ? 1 : -1)),
+                lz = (float)(zz + ((corner & 4) ? 1 : -1));
+    const float wx = (lx / (float)(V - 1) * 2.f - 1.f) * vol_len - m[3], wy = (ly / (float)(V - 1) * 2.f - 1.f) * vol_len - m[7],
+                wz = (lz / (float)(V - 1) * 2.f - 1.f) * vol_len - m[11];
+    const float a = (c00 * wx + c01 * wy + c02 * wz) * inv_det, b = (c10 * wx + c11 * wy + c12 * wz) * inv_det,
+                c = (c20 * wx + c21 * wy + c22 * wz) * inv_det;
+    float fx, fy;
+    if (persp) {
+      if (!(c >= 1e-4f)) ok = false;
+      fx = a / c;
+      fy = b / c;
+    } else {
+      const float ra = a - cam.Kinv[2], rb = b - cam.Kinv[5];
+      fx = ((cam.Kinv[4] * ra - cam.Kinv[1] * rb) / k_det + 1.f) * hs;
+      fy = ((cam.Kinv[0] * rb - cam.Kinv[3] * ra) / k_det + 1.f) * hs;
+    }
+    const float f[3] = {(c - cam.near_) * d_scale, fy, fx};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      if (!(fabsf(f[k]) < BOX_FINITE)) ok = false;
+      mn[k] = fminf(mn[k], f[k]);
+      mx[k] = fmaxf(mx[k], f[k]);
+    }
+  }
+  if (!ok) return;
+  int l[3], h[3];
+  const int n[3] = {D, S, S};
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    if (!index_window(mn[k], mx[k], n[k], l[k], h[k])) return;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    lo[k] = l[k];
+    hi[k] = h[k];
+  }
+}
+
+// is lattice index `i` one of floor(p), floor(p) + 1?  -> its linear weight; compared as floats (p may be far outside int range)
+__device__ __forceinline__ bool corner_weight(float p, int i, float& w) {
+  const float f = floorf(p), e = (float)i - f, t = p - f;
+  w = e == 0.f ? 1.f - t : t;
+  return e == 0.f || e == 1.f;
+}
+
+// d_vol[voxel][c] = sum over (view, d, y, x) ascending of w * d_out[point][c]: one thread per (voxel, channel quad)
+__global__ __launch_bounds__(256) void frustum_gather_adj_kernel(const float* __restrict__ d_out, const ViewCam* __restrict__ cams,
+                                                                 const int* __restrict__ view_idx, const float* __restrict__ pos, int TN,
+                                                                 int D, int S, int V, float vol_len, int persp,
+                                                                 float* __restrict__ d_vol) {
+  constexpr int C = 64;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long vox = gid >> 4;
+  const int cq = (int)(gid & 15) * 4;
+  if (vox >= (long)V * V * V) return;
+  const int xx = (int)(vox % V), yy = (int)((vox / V) % V), zz = (int)(vox / ((long)V * V));
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int tv = 0; tv < TN; ++tv) {
+    const ViewCam cam = cams[view_idx[tv]];
+    int lo[3], hi[3];
+    frustum_box(cam, xx, yy, zz, D, S, V, vol_len, persp, lo, hi);
+    for (int d = lo[0]; d <= hi[0]; ++d)
+      for (int y = lo[1]; y <= hi[1]; ++y)
+        for (int x = lo[2]; x <= hi[2]; ++x) {
+          const long pt = (((long)tv * D + d) * S + y) * S + x;
+          float wx, wy, wz;
+          if (!corner_weight(pos[pt * 3], xx, wx) || !corner_weight(pos[pt * 3 + 1], yy, wy) || !corner_weight(pos[pt * 3 + 2], zz, wz))
+            continue;
+          const float wgt = wx * wy * wz;
+          const float4 g = *(const float4*)(d_out + pt * C + cq);
+          acc.x += wgt * g.x;
+          acc.y += wgt * g.y;
+          acc.z += wgt * g.z;
+          acc.w += wgt * g.w;
+        }
+  }
+  *(float4*)(d_vol + vox * C + cq) = acc;
+}
+
+// Lattice indices whose grid coordinate p(i) = k (X(i) - mn), X(i) = -L + i 2L / (V - 1), can fall into (cell - 1, cell + 1),
+// padded by one; the whole axis when the map is degenerate (a one-cell axis: k = 0)
+__device__ __forceinline__ void latent_axis_window(float mn, float sh, int g, int cell, float voxel, int V, float vol_len, int& lo,
+                                                   int& hi) {
+  lo = 0;
+  hi = V - 1;
+  const float k = (float)(g - 1) / (voxel * sh), istep = (float)(V - 1) / (2.f * vol_len);
+  if (!(k > 0.f)) return;
+  const float a = (((float)(cell - 1)) / k + mn + vol_len) * istep, b = (((float)(cell + 1)) / k + mn + vol_len) * istep;
+  int l, h;
+  if (index_window(fminf(a, b), fmaxf(a, b), V, l, h)) {
+    lo = l;
+    hi = h;
+  }
+}
+__device__ __forceinline__ float latent_axis_pos(float mn, float sh, int g, float voxel, int V, float vol_len, int i) {
+  const float X = linspace_at(-vol_len, vol_len, V, i);
+  const float gx = (X - mn) / voxel / sh * 2.f - 1.f;
+  return (gx + 1.f) * 0.5f * (float)(g - 1);
+}
+// d_rows[grid[cell]][c] = sum over lattice points (iz, iy, ix) ascending of w * d_vol[point][c]: one thread per (cell, channel);
+// cells without a row are skipped, every row belongs to exactly one cell, so every row is written
+__global__ __launch_bounds__(256) void latent_gather_adj_kernel(const float* __restrict__ d_vol, const int* __restrict__ grid, int gd,
+                                                                int gh, int gw, float minx, float miny, float minz, float shx, float shy,
+                                                                float shz, float voxel, int V, float vol_len, float* __restrict__ d_rows) {
+  constexpr int C = 64;
+  const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long cell = gid >> 6;
+  const int c = (int)(gid & 63);
+  if (cell >= (long)gd * gh * gw) return;
+  const int row = grid[cell];
+  if (row < 0) return;
+  const int xx = (int)(cell % gw), yy = (int)((cell / gw) % gh), zz = (int)(cell / ((long)gw * gh));
+  int x0, x1, y0, y1, z0, z1;
+  latent_axis_window(minx, shx, gw, xx, voxel, V, vol_len, x0, x1);
+  latent_axis_window(miny, shy, gh, yy, voxel, V, vol_len, y0, y1);
+  latent_axis_window(minz, shz, gd, zz, voxel, V, vol_len, z0, z1);
+  float acc = 0.f;
+  for (int iz = z0; iz <= z1; ++iz) {
+    float wz;
+    if (!corner_weight(latent_axis_pos(minz, shz, gd, voxel, V, vol_len, iz), zz, wz)) continue;
+    for (int iy = y0; iy <= y1; ++iy) {
+      float wy;
+      if (!corner_weight(latent_axis_pos(miny, shy, gh, voxel, V, vol_len, iy), yy, wy)) continue;
+      for (int ix = x0; ix <= x1; ++ix) {
+        float wx;
+        if (!corner_weight(latent_axis_pos(minx, shx, gw, voxel, V, vol_len, ix), xx, wx)) continue;
+        acc += wx * wy * wz * d_vol[(((long)iz * V + iy) * V + ix) * C + c];
+      }
+    }
+  }
+  d_rows[(long)row * C + c] = acc;
+}
+
+// ---- vertex adjoint in two stages through the lattice: d_feats = B^T (A^T d_vf), weight = w3(vertex, corner) * w2(voxel, view, tap)
+// The voxel -> (vertex, corner) lists are built inside the call without atomics: every voxel's thread walks the vertices in
+// index order twice (count, then fill behind an exclusive scan of the counts), so a list is in ascending vertex order by
+// construction (a vertex has at most one corner on a voxel).  The walk reads one packed int per vertex.
+constexpr int VKEY_BITS = 10, VKEY_MASK = (1 << VKEY_BITS) - 1;  // per axis: floor(position) + 2, clamped to [0, V + 2]
+__global__ void vertex_key_kernel(const float* __restrict__ verts, int Nv, int V, float vol_len, int* __restrict__ key) {
+  const int vi = blockIdx.x * blockDim.x + threadIdx.x;
+  if (vi >= Nv) return;
+  int k = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float g = verts[vi * 3 + a] / vol_len;
+    const float pos = (g + 1.0f) * 0.5f * (float)(V - 1);
+    const float f = fminf(fmaxf(floorf(pos), -2.f), (float)V);  // (outside [-1, V - 1] no corner is on the lattice)
+    k |= ((int)f + 2) << (VKEY_BITS * a);
+  }
+  key[vi] = k;
+}
+// corner (0..7) of vertex key k that sits on voxel (xx, yy, zz), or -1
+__device__ __forceinline__ int vertex_corner_on(int k, int xx, int yy, int zz) {
+  const int dx = xx + 2 - (k & VKEY_MASK), dy = yy + 2 - ((k >> VKEY_BITS) & VKEY_MASK), dz = zz + 2 - ((k >> (2 * VKEY_BITS)) & VKEY_MASK);
+  return ((unsigned)dx <= 1u && (unsigned)dy <= 1u && (unsigned)dz <= 1u) ? (dx | (dy << 1) | (dz << 2)) : -1;
+}
+// FILL = false: cnt[voxel] = its (vertex, corner) pairs.  FILL = true: the pairs (vertex, w3) behind off[voxel], and the
+// compact list of occupied voxels (ascending: occ_rank is a prefix sum over voxel order).
+template <bool FILL>
+__global__ __launch_bounds__(256) void vertex_bins_kernel(const int* __restrict__ key, const float* __restrict__ verts, int Nv, int V,
+                                                          float vol_len, int* __restrict__ cnt, const int* __restrict__ off,
+                                                          const int* __restrict__ occ_rank, int* __restrict__ list_v,
+                                                          float* __restrict__ list_w, int* __restrict__ occ_list) {
+  const int vox = blockIdx.x * blockDim.x + threadIdx.x;
+  if (vox >= V * V * V) return;
+  const int xx = vox % V, yy = (vox / V) % V, zz = vox / (V * V);
+  int n = FILL ? off[vox] : 0;
+  const int first = n;
+  for (int vi = 0; vi < Nv; ++vi) {
+    const int corner = vertex_corner_on(key[vi], xx, yy, zz);
+    if (corner < 0) continue;
+    if (FILL) {
+      float fr[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {  // vertex_scatter_kernel's arithmetic
+        const float g = verts[vi * 3 + a] / vol_len;
+        const float pos = (g + 1.0f) * 0.5f * (float)(V - 1);
+        fr[a] = pos - floorf(pos);
+      }
+      const int bx = corner & 1, by = (corner >> 1) & 1, bz = corner >> 2;
+      list_v[n] = vi;
+      list_w[n] = (bx ? fr[0] : 1.f - fr[0]) * (by ? fr[1] : 1.f - fr[1]) * (bz ? fr[2] : 1.f - fr[2]);
+    }
+    ++n;
+  }
+  if (!FILL) cnt[vox] = n;
+  else if (n > first) occ_list[occ_rank[vox]] = vox;
+}
+// One workgroup: off[0..n] = exclusive prefix sum of cnt, occ_rank[0..n) = exclusive prefix count of non-empty entries,
+// *n_occ = their number.  Integers only.
+__global__ __launch_bounds__(1024) void vertex_scan_kernel(const int* __restrict__ cnt, int n, int* __restrict__ off,
+                                                           int* __restrict__ occ_rank, int* __restrict__ n_occ) {
+  __shared__ int s_a[1024], s_b[1024];
+  const int t = threadIdx.x, per = (n + 1023) / 1024, b = min(n, t * per), e = min(n, b + per);
+  int a = 0, q = 0;
+  for (int i = b; i < e; ++i) {
+    a += cnt[i];
+    q += cnt[i] > 0;
+  }
+  s_a[t] = a;
+  s_b[t] = q;
+  __syncthreads();
+  for (int d = 1; d < 1024; d <<= 1) {
+    const int va = t >= d ? s_a[t - d] : 0, vb = t >= d ? s_b[t - d] : 0;
+    __syncthreads();
+    s_a[t] += va;
+    s_b[t] += vb;
+    __syncthreads();
+  }
+  a = s_a[t] - a;  // exclusive
+  q = s_b[t] - q;
+  for (int i = b; i < e; ++i) {
+    off[i] = a;
+    occ_rank[i] = q;
+    a += cnt[i];
+    q += cnt[i] > 0;
+  }
+  if (t == 1023) {
+    off[n] = s_a[1023];
+    *n_occ = s_b[1023];
+  }
+}
+// stage A: d_lat[view][j][c] = sum over the list of occupied voxel j (ascending vertex) of w3 * d_vf[view][vertex][c]
+__global__ __launch_bounds__(256) void vertex_to_lattice_adj_kernel(const float* __restrict__ d_vf, const int* __restrict__ off,
+                                                                    const int* __restrict__ occ_list, const int* __restrict__ n_occ,
+                                                                    const int* __restrict__ list_v, const float* __restrict__ list_w,
+                                                                    int Nv, int stride, float* __restrict__ d_lat) {
+  const int view = blockIdx.y, gid = blockIdx.x * blockDim.x + threadIdx.x, j = gid >> 4, c = gid & 15;
+  if (j >= min(*n_occ, stride)) return;
+  const int vox = occ_list[j], b = off[vox], e = off[vox + 1];
+  const float* src = d_vf + (long)view * Nv * 16 + c;
+  float acc = 0.f;
+  for (int i = b; i < e; ++i) acc += list_w[i] * src[(long)list_v[i] * 16];
+  d_lat[((long)view * stride + j) * 16 + c] = acc;
+}
+// stage B, step 1: where lattice voxel vox_list[j] (NULL: voxel j) lands in every view's map -- vertex_scatter_kernel's
+// arithmetic -- as (x0, y0, tx, ty), once per (view, voxel).  Positions far outside the map are pulled to its rim + 1, where no
+// tap is inside either.
+__global__ void lattice_project_kernel(const ViewCam* __restrict__ cams, const int* __restrict__ view_idx, const int* __restrict__ vox_list,
+                                       const int* __restrict__ n_ptr, int n_max, int V, float vol_len, int S, int persp,
+                                       float4* __restrict__ rec) {
+  const int view = blockIdx.y, j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= (n_ptr ? min(*n_ptr, n_max) : n_max)) return;
+  const ViewCam cam = cams[view_idx[view]];
+  const int vox = vox_list ? vox_list[j] : j;
+  const int ix = vox % V, iy = (vox / V) % V, iz = vox / (V * V);
+  const float X = linspace_at(-vol_len, vol_len, V, ix), Y = linspace_at(-vol_len, vol_len, V, iy),
+              Z = linspace_at(-vol_len, vol_len, V, iz);
+  const float u = cam.P[0] * X + cam.P[1] * Y + cam.P[2] * Z + cam.P[3];
+  const float v = cam.P[4] * X + cam.P[5] * Y + cam.P[6] * Z + cam.P[7];
+  float px, py;
+  if (persp) {
+    float w = cam.P[8] * X + cam.P[9] * Y + cam.P[10] * Z + cam.P[11];
+    w = w < 1e-4f ? 1e-4f : w;
+    const float hs = (float)(S - 1) * 0.5f;
+    px = ((u / w) / hs - 1.0f + 1.0f) * 0.5f * (float)(S - 1);
+    py = ((v / w) / hs - 1.0f + 1.0f) * 0.5f * (float)(S - 1);
+  } else {
+    px = (u + 1.0f) * 0.5f * (float)(S - 1);
+    py = (v + 1.0f) * 0.5f * (float)(S - 1);
+  }
+  px = fminf(fmaxf(px, -2.f), (float)(S + 1));
+  py = fminf(fmaxf(py, -2.f), (float)(S + 1));
+  const float fx0 = floorf(px), fy0 = floorf(py);
+  rec[(long)view * n_max + j] = make_float4(__int_as_float((int)fx0), __int_as_float((int)fy0), px - fx0, py - fy0);
+}
+// stage B, step 2: d_feats[view][pixel][c] = sum over voxels j ascending of w2 * d_lat[view][j][c] (a pixel is at most one of a
+// voxel's four taps): one thread per (pixel, channel quad); the voxels' records stream past every pixel of the view through LDS
+__global__ __launch_bounds__(256) void lattice_to_views_adj_kernel(const float* __restrict__ d_lat, const float4* __restrict__ rec,
+                                                                   const int* __restrict__ n_ptr, int n_max, int S,
+                                                                   float* __restrict__ d_feats) {
+  __shared__ float4 s_rec[256];
+  const int view = blockIdx.y, t = threadIdx.x, pix = blockIdx.x * 64 + (t >> 2), q = (t & 3) * 4;
+  const int n = n_ptr ? min(*n_ptr, n_max) : n_max;
+  const bool valid = pix < S * S;
+  const int xp = pix % S, yp = pix / S;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int base = 0; base < n; base += 256) {
+    __syncthreads();
+    if (base + t < n) s_rec[t] = rec[(long)view * n_max + base + t];
+    __syncthreads();
+    const int m = min(256, n - base);
+    if (!valid) continue;
+    for (int i = 0; i < m; ++i) {
+      const float4 r = s_rec[i];
+      const int dx = xp - __float_as_int(r.x), dy = yp - __float_as_int(r.y);
+      if ((unsigned)dx > 1u || (unsigned)dy > 1u) continue;
+      const float w = (dx ? r.z : 1.f - r.z) * (dy ? r.w : 1.f - r.w);
+      const float4 g = *(const float4*)(d_lat + ((long)view * n_max + base + i) * 16 + q);
+      acc.x += w * g.x;
+      acc.y += w * g.y;
+      acc.z += w * g.z;
+      acc.w += w * g.w;
+    }
+  }
+  if (valid) *(float4*)(d_feats + ((long)view * S * S + pix) * 16 + q) = acc;
+}
+
+// sparse_fold_dups_kernel without atomics: a representative that has duplicates (flagged by them) adds their rows in row order
+__global__ void fold_dups_flag_kernel(const int* __restrict__ nbr, int n, int* __restrict__ flag) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= n) return;
+  const int r = nbr[(long)s * 27 + 13];
+  if (r != s && r >= 0) flag[r] = 1;
+}
+__global__ void fold_dups_sum_kernel(float* __restrict__ d, const int* __restrict__ nbr, const int* __restrict__ flag, int n, int C) {
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < (long)n * C; e += (long)gridDim.x * blockDim.x) {
+    const int r = (int)(e / C);
+    if (!flag[r]) continue;
+    float acc = d[e];  // (only duplicates' rows are read below, only representatives' rows written: disjoint)
+    for (int s = r + 1; s < n; ++s)  // the representative is the voxel's FIRST row
+      if (nbr[(long)s * 27 + 13] == r) acc += d[(long)s * C + (e - (long)r * C)];
+    d[e] = acc;
+  }
+}
+__global__ void fold_dups_clear_kernel(float* __restrict__ d, const int* __restrict__ nbr, int n, int C) {
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < (long)n * C; e += (long)gridDim.x * blockDim.x) {
+    const int s = (int)(e / C), r = nbr[(long)s * 27 + 13];
+    if (r != s && r >= 0) d[e] = 0.f;
   }
 }
 
@@ -591,6 +986,101 @@ int cbwd_vertex_scatter(const float* d_out, const ViewCam* cams, const int* view
   }
   hipLaunchKernelGGL(vertex_scatter_kernel, dim3(n_views, 16), dim3(1024), lds, s, d_out, cams, view_idx, verts, Nv, V, vol_len, S, persp,
                      d_feats);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+// ---- deterministic mode (gather forms: every output element is written, nothing is accumulated into) ----
+// pos: scratch of TN * D * S * S * 3 floats
+int cbwd_frustum_gather_adj(const float* d_out, const ViewCam* cams, const int* view_idx, int TN, int D, int S, int V, float vol_len,
+                            int persp, float* pos, float* d_vol, hipStream_t s) {
+  const long npts = (long)TN * D * S * S, threads = (long)V * V * V * 16;
+  hipLaunchKernelGGL(frustum_positions_kernel, dim3((int)((npts + 255) / 256)), dim3(256), 0, s, cams, view_idx, TN, D, S, V, vol_len,
+                     persp, pos);
+  hipLaunchKernelGGL(frustum_gather_adj_kernel, dim3((int)((threads + 255) / 256)), dim3(256), 0, s, d_out, cams, view_idx, pos, TN, D, S, V,
+                     vol_len, persp, d_vol);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+int cbwd_latent_gather_adj(const float* d_vol, const int* grid, int gd, int gh, int gw, const float* min_xyz, const int* out_sh, float voxel,
+                           int V, float vol_len, float* d_rows, hipStream_t s) {
+  const long threads = (long)gd * gh * gw * 64;
+  hipLaunchKernelGGL(latent_gather_adj_kernel, dim3((int)((threads + 255) / 256)), dim3(256), 0, s, d_vol, grid, gd, gh, gw, min_xyz[0],
+                     min_xyz[1], min_xyz[2], (float)out_sh[2], (float)out_sh[1], (float)out_sh[0], voxel, V, vol_len, d_rows);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+// Adjoint of the bilinear sampling of a lattice's voxels in every view's map (vertex gather stage B; unproject_views_kernel):
+// d_lat [n_views][n_max][16] holds dL/d(sample) of voxel vox_list[j] (vox_list NULL: the dense lattice, n_max = V^3) for the
+// first *n_ptr (NULL: n_max) entries j, in ascending voxel order; d_feats [n_views][S*S][16] is written.
+// rec: scratch of n_views * n_max float4.
+// Only the compact form (vox_list / n_ptr given) has a caller and tests today; the dense form is written for the backward of
+// use_spatial_volume=True and has not run yet.
+int cbwd_lattice_to_views_adj(const float* d_lat, const ViewCam* cams, const int* view_idx, int n_views, const int* vox_list,
+                              const int* n_ptr, int n_max, int V, float vol_len, int S, int persp, float4* rec, float* d_feats,
+                              hipStream_t s) {
+  if (n_views <= 0 || n_max <= 0) return mvd_fail("lattice adjoint: bad shape");
+  hipLaunchKernelGGL(lattice_project_kernel, dim3(cdiv(n_max, 256), n_views), dim3(256), 0, s, cams, view_idx, vox_list, n_ptr, n_max, V,
+                     vol_len, S, persp, rec);
+  hipLaunchKernelGGL(lattice_to_views_adj_kernel, dim3(cdiv(S * S, 64), n_views), dim3(256), 0, s, d_lat, rec, n_ptr, n_max, S, d_feats);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+namespace {
+struct VertexAdjScratch {  // the pieces of cbwd_vertex_gather_adj's scratch, each 256-byte aligned
+  size_t key, cnt, off, rank, n_occ, occ, list_v, list_w, rec, lat, total;
+  int cap;
+  VertexAdjScratch(int n_views, int Nv, int V) {
+    const size_t vox = (size_t)V * V * V, pairs = (size_t)Nv * 8;
+    cap = (int)std::min(vox, pairs);
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+      const size_t at = o;
+      o += (bytes + 255) & ~(size_t)255;
+      return at;
+    };
+    key = take((size_t)Nv * 4);
+    cnt = take(vox * 4);
+    off = take((vox + 1) * 4);
+    rank = take(vox * 4);
+    n_occ = take(4);
+    occ = take((size_t)cap * 4);
+    list_v = take(pairs * 4);
+    list_w = take(pairs * 4);
+    rec = take((size_t)n_views * cap * 16);
+    lat = take((size_t)n_views * cap * 64);
+    total = o;
+  }
+};
+}  // namespace
+size_t cbwd_vertex_adj_scratch_bytes(int n_views, int Nv, int V) { return VertexAdjScratch(n_views, Nv, V).total; }
+// scratch: cbwd_vertex_adj_scratch_bytes(n_views, Nv, V) bytes, 256-byte aligned
+int cbwd_vertex_gather_adj(const float* d_out, const ViewCam* cams, const int* view_idx, int n_views, const float* verts, int Nv, int V,
+                           float vol_len, int S, int persp, void* scratch, float* d_feats, hipStream_t s) {
+  if (Nv <= 0 || V <= 0 || V + 2 > VKEY_MASK || (long)V * V * V > (1l << 30)) return mvd_fail("vertex adjoint: bad lattice size");
+  const VertexAdjScratch L(n_views, Nv, V);
+  char* b = (char*)scratch;
+  int *key = (int*)(b + L.key), *cnt = (int*)(b + L.cnt), *off = (int*)(b + L.off), *rank = (int*)(b + L.rank),
+      *n_occ = (int*)(b + L.n_occ), *occ = (int*)(b + L.occ), *list_v = (int*)(b + L.list_v);
+  float *list_w = (float*)(b + L.list_w), *lat = (float*)(b + L.lat);
+  const int vox = V * V * V;
+  hipLaunchKernelGGL(vertex_key_kernel, dim3(cdiv(Nv, 256)), dim3(256), 0, s, verts, Nv, V, vol_len, key);
+  hipLaunchKernelGGL(vertex_bins_kernel<false>, dim3(cdiv(vox, 256)), dim3(256), 0, s, key, verts, Nv, V, vol_len, cnt, (const int*)nullptr,
+                     (const int*)nullptr, (int*)nullptr, (float*)nullptr, (int*)nullptr);
+  hipLaunchKernelGGL(vertex_scan_kernel, dim3(1), dim3(1024), 0, s, cnt, vox, off, rank, n_occ);
+  hipLaunchKernelGGL(vertex_bins_kernel<true>, dim3(cdiv(vox, 256)), dim3(256), 0, s, key, verts, Nv, V, vol_len, (int*)nullptr, off, rank,
+                     list_v, list_w, occ);
+  hipLaunchKernelGGL(vertex_to_lattice_adj_kernel, dim3(cdiv(L.cap * 16, 256), n_views), dim3(256), 0, s, d_out, off, occ, n_occ, list_v,
+                     list_w, Nv, L.cap, lat);
+  HIP_CHECK_RET(hipGetLastError());
+  return cbwd_lattice_to_views_adj(lat, cams, view_idx, n_views, occ, n_occ, L.cap, V, vol_len, S, persp, (float4*)(b + L.rec), d_feats, s);
+}
+// flag: scratch of n ints
+int cbwd_sparse_fold_dups_det(float* d, const int* nbr, int n, int C, int* flag, hipStream_t s) {
+  if (n <= 0) return 0;
+  HIP_CHECK_RET(hipMemsetAsync(flag, 0, (size_t)n * sizeof(int), s));
+  hipLaunchKernelGGL(fold_dups_flag_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, nbr, n, flag);
+  hipLaunchKernelGGL(fold_dups_sum_kernel, dim3(gridn((size_t)n * C)), dim3(256), 0, s, d, nbr, flag, n, C);
+  hipLaunchKernelGGL(fold_dups_clear_kernel, dim3(gridn((size_t)n * C)), dim3(256), 0, s, d, nbr, n, C);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }

@@ -35,9 +35,13 @@ def _level_dims(d, s):
 
 class Engine:
     def __init__(self, ucfg: UNetConfig, vcfg: VolumeConfig, device="cuda:0", workspace_gb: float = 16.0,
-                 precision_level: int = 3, train: bool = False, vae_exact: bool = False):
+                 precision_level: int = 3, train: bool = False, vae_exact: bool = False, deterministic: bool = False):
         """precision_level: mvd_set_precision_level (0..6): how many of the output-side layers run with split fp16 operands
-        (extended precision); 3 is the default the parity bounds are stated for (include/mvd.h: the ladder)."""
+        (extended precision); 3 is the default the parity bounds are stated for (include/mvd.h: the ladder).
+        deterministic (needs train): mvd_train_set_deterministic, see ``train_set_deterministic``."""
+        if deterministic and not train:
+            raise ValueError("deterministic=True needs train=True: the mode selects kernels of the backward pass")
+        self.deterministic = bool(deterministic)
         self.precision_level = int(precision_level)
         self.vae_exact = bool(vae_exact)  # mvd_set_vae_precision: first-stage model in extended precision (~3x its cost)
         self.train_mode = bool(train)  # mvd_train_enable: master parameters / gradients kept in flat arenas (training step)
@@ -82,6 +86,8 @@ class Engine:
         L.check(self.lib.mvd_set_spatial_volume(self._ctx, bool(vcfg.use_spatial_volume),
                                                 (C.c_int * 4)(*vcfg.spatial_dims)))
         L.check(self.lib.mvd_train_enable(self._ctx, self.train_mode))
+        if self.deterministic:  # (a context rebuilt by load_state_dict keeps the mode)
+            L.check(self.lib.mvd_train_set_deterministic(self._ctx, True))
         L.check(self.lib.mvd_set_vae_precision(self._ctx, self.vae_exact))
         self._loaded = False
         self.flat_params = self.flat_grads = self.flat_m = self.flat_v = None
@@ -489,6 +495,60 @@ class Engine:
             self._ctx, B, (C.c_int * B)(*slots), L.ptr(x), (C.c_int64 * B)(*timesteps), L.ptr(ve),
             x.shape[1], (C.c_int * B)(*target_index), L.ptr(ds[0]), L.ptr(ds[1]), L.ptr(ds[2]), L.ptr(ds[3]),
             None, None, None, None, _stream()))
+
+    def train_set_deterministic(self, on=True):
+        """mvd_train_set_deterministic: from the next backward call on, the conditioner's three gather adjoints (frustum, lattice,
+        vertex) and the fold of duplicate vertices' rows run as gathers with index-ordered sums instead of fp32 atomic scatters:
+        identical inputs then give bit-identical gradients over the whole arena.  Off (the default) restores the atomic forms."""
+        L.check(self.lib.mvd_train_set_deterministic(self._ctx, bool(on)))
+        self.deterministic = bool(on)
+
+    def adjoint_calls(self):
+        """mvd_probe_adjoint_calls: launches so far of the (frustum, latent, vertex) adjoints as {"atomic": (..), "gather": (..)}."""
+        n = (C.c_int64 * 6)()
+        L.check(self.lib.mvd_probe_adjoint_calls(self._ctx, n))
+        return {"atomic": tuple(int(v) for v in n[:3]), "gather": tuple(int(v) for v in n[3:])}
+
+    def _view_idx(self, view_idx, n):
+        idx = list(range(n)) if view_idx is None else [int(v) for v in view_idx]
+        return (C.c_int32 * len(idx))(*idx), len(idx)
+
+    def op_frustum_adjoint(self, d_out, view_idx=None, deterministic=False):
+        """mvd_op_frustum_adjoint: the adjoint of the frustum gather alone.  d_out [TN,D,S,S,64] (channels-last) = dL/d(gathered
+        frustum) of the views ``view_idx`` (default 0..TN-1) of the active sample -> dL/d(volume) [V,V,V,64]."""
+        g = _f32(d_out, self.device)
+        TN, D, S = g.shape[0], g.shape[1], g.shape[2]
+        assert g.dim() == 5 and g.shape[3] == S and g.shape[4] == 64
+        idx, n = self._view_idx(view_idx, TN)
+        assert n == TN
+        V = self.vcfg.spatial_volume_size
+        out = torch.full((V, V, V, 64), float("nan"), device=self.device, dtype=torch.float32)
+        L.check(self.lib.mvd_op_frustum_adjoint(self._ctx, L.ptr(g), idx, TN, D, S, bool(deterministic), L.ptr(out), _stream()))
+        return out
+
+    def op_latent_adjoint(self, d_vol, deterministic=False):
+        """mvd_op_latent_adjoint: the adjoint of the lattice gather alone.  d_vol [V,V,V,64] (channels-last) -> the gradient of the
+        coarsest sparse level's rows [n_rows,64] of the active sample's mesh."""
+        g = _f32(d_vol, self.device)
+        V = self.vcfg.spatial_volume_size
+        assert tuple(g.shape) == (V, V, V, 64)
+        n = C.c_int32(0)
+        L.check(self.lib.mvd_op_latent_adjoint(self._ctx, None, 0, None, C.byref(n), _stream()))
+        out = torch.full((n.value, 64), float("nan"), device=self.device, dtype=torch.float32)
+        L.check(self.lib.mvd_op_latent_adjoint(self._ctx, L.ptr(g), bool(deterministic), L.ptr(out), None, _stream()))
+        return out
+
+    def op_vertex_adjoint(self, d_vf, view_idx=None, deterministic=False):
+        """mvd_op_vertex_adjoint: the adjoint of the vertex gather alone.  d_vf [n,Nv,16] = dL/d(per-view vertex features) of the
+        views ``view_idx`` (default 0..n-1) of the active sample -> dL/d(2-D encoder maps) [n,s,s,16] (channels-last)."""
+        g = _f32(d_vf, self.device)
+        assert g.dim() == 3 and g.shape[1] == self.num_vertices and g.shape[2] == 16
+        idx, n = self._view_idx(view_idx, g.shape[0])
+        assert n == g.shape[0]
+        s = self.ucfg.image_size
+        out = torch.full((n, s, s, 16), float("nan"), device=self.device, dtype=torch.float32)
+        L.check(self.lib.mvd_op_vertex_adjoint(self._ctx, L.ptr(g), idx, n, bool(deterministic), L.ptr(out), _stream()))
+        return out
 
     def get_grad(self, key: str, shape):
         out = torch.empty(tuple(shape), device=self.device, dtype=torch.float32)

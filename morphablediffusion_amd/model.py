@@ -338,7 +338,7 @@ class SyncMultiviewDiffusion(nn.Module):
                  clip_image_encoder_path=None, sample_type="ddim", sample_steps=50, target_elevation=30,
                  first_stage_model=None, clip_image_encoder=None, device="cuda:0", workspace_gb=16.0, precision_level=3,
                  train_mode=False, loss_scale=65536.0, recompute=True, first_stage_precision="exact", use_ema=False,
-                 ema_decay=0.9999):
+                 ema_decay=0.9999, deterministic=False):
         """train_mode / loss_scale / recompute are not reference kwargs: train_mode keeps fp32 master parameters, gradients and
         Adam moments in the engine (training_step runs the backward pass); loss_scale multiplies dL/dpred so that the fp16 MFMA
         operands of the backward pass stay in range (un-done by the optimiser); recompute = per-block activation checkpointing
@@ -348,11 +348,17 @@ class SyncMultiviewDiffusion(nn.Module):
         (fp16 operands: decoded images within 0.8 of an 8-bit step of the reference's).
         use_ema / ema_decay (LDM's LitEma; needs train_mode): every optimiser step also moves an exponential moving average of
         the parameters (``engine.flat_ema``) inside the fused update kernel, with LitEma's warm-up of the decay; ``ema_scope()``
-        samples from the averaged weights, validation_step does, and state_dict() carries them as ``model_ema.*``."""
+        samples from the averaged weights, validation_step does, and state_dict() carries them as ``model_ema.*``.
+        deterministic (needs train_mode; also settable later as ``model.deterministic``): the conditioner's backward runs its
+        three gather adjoints without floating-point atomics, so that identical steps give bit-identical gradients -- conditioner
+        parameters included -- and a run can be replayed or resumed bit for bit.  Explicit: torch's global
+        ``use_deterministic_algorithms`` flag is not consulted."""
         if first_stage_precision not in ("fast", "exact"):
             raise ValueError("first_stage_precision must be 'fast' or 'exact'")
         if use_ema and not train_mode:
             raise ValueError("use_ema=True needs train_mode=True: the EMA weights are updated by the optimiser step")
+        if deterministic and not train_mode:
+            raise ValueError("deterministic=True needs train_mode=True: the mode selects kernels of the backward pass")
         if use_spatial_volume and train_mode:
             raise NotImplementedError("train_mode=True with use_spatial_volume=True: SpatialTime3DNet has no backward pass in the "
                                       "engine (a forward-only training_step(..., backward=False) works without train_mode)")
@@ -392,7 +398,7 @@ class SyncMultiviewDiffusion(nn.Module):
                                                use_spatial_volume=use_spatial_volume)
         self.engine = Engine(self.model.diffusion_model.cfg, self.spatial_volume.cfg, device=device,
                              workspace_gb=workspace_gb, precision_level=precision_level, train=train_mode,
-                             vae_exact=first_stage_precision == "exact")
+                             vae_exact=first_stage_precision == "exact", deterministic=bool(deterministic))
         self.model.diffusion_model.bind(self.engine)
         self.spatial_volume.bind(self.engine)
         self._device = torch.device(device)
@@ -406,6 +412,18 @@ class SyncMultiviewDiffusion(nn.Module):
     @property
     def device(self):
         return self._device
+
+    @property
+    def deterministic(self):
+        """Deterministic training mode (Engine.train_set_deterministic); setting it takes effect from the next backward pass."""
+        return self.engine.deterministic
+
+    @deterministic.setter
+    def deterministic(self, on):
+        if on and not self.train_mode:
+            raise ValueError("deterministic=True needs train_mode=True: the mode selects kernels of the backward pass")
+        if bool(on) != self.engine.deterministic:
+            self.engine.train_set_deterministic(on)
 
     def load_state_dict(self, state_dict, strict=False):
         """generate_face.py:76 calls this with strict=False on ``ckpt['state_dict']``; returns torch's
