@@ -97,11 +97,14 @@ int mvd_unet_forward(mvd_ctx* ctx, const float* x, const int64_t* timesteps, con
  *      SpatialTransformer.forward (modules/attention.py:325-336; needs context [B,1,context_dim]), Downsample / Upsample /
  *      the input convolution (openaimodel.py:100-157);
  *   "middle_conditions" / "output_conditions.K": DepthTransformer.forward (ldm/models/diffusion/attention.py:78-84; needs
- *      volume [B,C_l,D,H,W], every sample conditional).
+ *      volume [n_ctx,C_l,D,H,W] for the FIRST n_ctx samples; the remaining B - n_ctx samples are context-free (all-zero volumes,
+ *      the classifier-free-guidance half, as in mvd_unet_forward) and take the production forms of that case: x + K, or with
+ *      MVD_NO_COND_CONST=1 the relu(beta) fill rows.  n_ctx == 0: volume may be NULL).  Other blocks ignore n_ctx.
  * x [B,C,H,W] at a UNet resolution (image_size >> level); out receives [B,Cout,Ho,Wo] (at most out_capacity floats) and
  * out_shape[4] its shape.  Used by the block-level parity tests. */
 int mvd_unet_block(mvd_ctx* ctx, const char* path, const float* x, int B, int C, int H, int W, const int64_t* timesteps,
-                   const float* context, const float* volume, int D, float* out, int out_capacity, int* out_shape, void* stream);
+                   const float* context, const float* volume, int D, int n_ctx, float* out, int out_capacity, int* out_shape,
+                   void* stream);
 
 
 /* SyncMultiviewDiffusion.embed_time -- morphable_diffusion.py:491-494. t [B] int64 -> out [B,time_dim] */
@@ -463,6 +466,16 @@ int mvd_op_layer_norm(mvd_ctx* ctx, const float* x, int rows, int C, const float
                       void* stream);
 int mvd_op_attention(mvd_ctx* ctx, const float* q, const float* k, const float* v, int B, int T, int heads, int d,
                      float* out, void* stream);
+/* depth_attn_kernel (csrc/k_depth.hip) on its own, in the kernel's layouts: qk [n_cond*HW][4][Cc] fp32 (the folded query),
+ * context [n_cond][D][HW][Cc] fp32 (rounded to fp16 here into rows of ldx >= Cc halfs, ldx % 8 == 0, 0 = Cc; the pad columns hold NaN
+ * bit patterns, so a read past Cc shows in the result), fill_row [4*Cc] fp32 (nfill > 0; rounded to fp16, with split != 0 to the
+ * [hi | lo | hi] row relu_beta_tile_kernel writes).  out [n_cond*HW + nfill + 1][4*Cc] fp32: z, then the nfill fill rows, then ONE
+ * guard row behind what the launch may write, preset to NaN bit patterns (it must come back NaN).  split != 0: the kernel writes
+ * [hi | lo | hi] rows, out receives hi + lo (NaN where the third block differs from the first) and hi_out (may be NULL) hi alone.
+ * check_only != 0: nothing is allocated or launched, the call returns what the launcher's argument check returns (0, or non-zero
+ * with its text in mvd_last_error). */
+int mvd_op_depth_attn(mvd_ctx* ctx, const float* qk, const float* context, const float* fill_row, int n_cond, int HW, int D, int Cc,
+                      int heads, int ldx, int split, int nfill, int check_only, float* out, float* hi_out, void* stream);
 int mvd_op_conv3d(mvd_ctx* ctx, const float* x_ncdhw, int B, int Cin, int D, int H, int W, const float* w,
                   const float* bias, int Cout, int stride, int transposed, const float* resid, float* out, void* stream);
 /* backward-kernel hooks used by tests/test_gpu_train_ops.py (each is compared with torch.autograd of the same op):

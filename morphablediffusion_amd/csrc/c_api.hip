@@ -32,6 +32,15 @@ __global__ void f16_to_f32_kernel(const half_t* in, float* out, size_t n) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
     out[i] = (float)in[i];
 }
+// fp32 [rows][C] -> fp16 rows ldo halfs apart (the pad columns are left as they are), and the reverse from rows ldi apart
+__global__ void rows_f32_to_f16_ld_kernel(const float* in, size_t rows, int C, half_t* out, int ldo) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * C; i += (size_t)gridDim.x * blockDim.x)
+    out[(i / C) * ldo + i % C] = (half_t)in[i];
+}
+__global__ void rows_f16_ld_to_f32_kernel(const half_t* in, size_t rows, int C, int ldi, float* out) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * C; i += (size_t)gridDim.x * blockDim.x)
+    out[i] = (float)in[(i / C) * ldi + i % C];
+}
 // q,k,v [rows][C] fp32 -> fp16 [rows][3C] (the layout of a fused q|k|v projection)
 __global__ void pack_qkv_rows_kernel(const float* q, const float* k, const float* v, int rows, int C, half_t* qkv) {
   const long total = (long)rows * C;
@@ -314,10 +323,12 @@ int mvd_unet_forward(mvd_ctx* c, const float* x, const int64_t* timesteps, const
 }
 
 int mvd_unet_block(mvd_ctx* c, const char* path, const float* x, int B, int C, int H, int W, const int64_t* timesteps,
-                   const float* context, const float* volume, int D, float* out, int out_capacity, int* out_shape, void* stream) {
+                   const float* context, const float* volume, int D, int n_ctx, float* out, int out_capacity, int* out_shape,
+                   void* stream) {
   if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
   if (!c || !c->finalized || !path || !x || !out || !out_shape || B <= 0 || C <= 0 || (C & 7) || H <= 0 || W <= 0)
     return mvd_fail("mvd_unet_block: bad argument");
+  if (n_ctx < 0 || n_ctx > B) return mvd_fail("mvd_unet_block: n_ctx out of range");
   hipStream_t s = S(stream);
   WsScope ws_scope(c);
   const int HW = H * W;
@@ -327,17 +338,17 @@ int mvd_unet_block(mvd_ctx* c, const char* path, const float* x, int B, int C, i
   WS_CHECK(xn && on);
   RET_IF(launch_nchw_to_nhwc(x, B, C, HW, xn, C, C, s));
   float* vn = nullptr;
-  if (volume) {
+  if (volume && n_ctx > 0) {
     int level = 0;
     for (int r = c->u.image_size; r > H; r >>= 1) ++level;
     if (level > 3 || D <= 0) return mvd_fail("mvd_unet_block: bad volume");
     const int Cc = c->u.volume_dims[level];
-    vn = ws_alloc<float>(c, (size_t)B * D * HW * Cc);
+    vn = ws_alloc<float>(c, (size_t)n_ctx * D * HW * Cc);
     WS_CHECK(vn);
-    RET_IF(launch_nchw_to_nhwc(volume, B, Cc, D * HW, vn, Cc, Cc, s));
+    RET_IF(launch_nchw_to_nhwc(volume, n_ctx, Cc, D * HW, vn, Cc, Cc, s));
   }
   int Co = 0, Ho = 0;
-  RET_IF(engine_unet_block(c, path, xn, B, C, H, W, timesteps, context, vn, D, on, &Co, &Ho, s));
+  RET_IF(engine_unet_block(c, path, xn, B, C, H, W, timesteps, context, vn, D, n_ctx, on, &Co, &Ho, s));
   if ((size_t)B * Co * Ho * Ho > (size_t)out_capacity) return mvd_fail("mvd_unet_block: output buffer too small");
   RET_IF(launch_nhwc_to_nchw(on, Co, B, Co, Ho * Ho, out, s));
   out_shape[0] = B; out_shape[1] = Co; out_shape[2] = Ho; out_shape[3] = Ho;
@@ -1353,6 +1364,45 @@ int mvd_op_attention(mvd_ctx* c, const float* q, const float* k, const float* v,
   hipLaunchKernelGGL(pack_qkv_rows_kernel, dim3(nblk((size_t)rows * C)), dim3(256), 0, s, q, k, v, rows, C, qkv);
   RET_IF(launch_attention(qkv, 3 * C, qkv + 2 * C, 3 * C, o, C, B, T, heads, d, s));
   hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk((size_t)rows * C)), dim3(256), 0, s, o, out, (size_t)rows * C);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+
+// depth_attn_kernel on the caller's data (tests/test_gpu_depth_attn.py).  Everything the launch may touch is poisoned first: the
+// context's pad columns (ldx > Cc) and one guard row behind z hold 0xFFFF halfs, NaN in fp16 and in bfloat16.
+int mvd_op_depth_attn(mvd_ctx* c, const float* qk, const float* context, const float* fill_row, int n_cond, int HW, int D, int Cc,
+                      int heads, int ldx, int split, int nfill, int check_only, float* out, float* hi_out, void* stream) {
+  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
+  if (!c) return mvd_fail("null context");
+  if (depth_attn_check(D, Cc, heads, ldx, nfill)) return -1;  // the launcher's own refusals, before anything is sized by them
+  if (check_only) return 0;
+  if (n_cond < 0 || HW <= 0 || D <= 0 || Cc <= 0 || !out || (n_cond > 0 && (!qk || !context)) || (nfill > 0 && !fill_row))
+    return mvd_fail("op_depth_attn: bad argument");
+  hipStream_t s = S(stream);
+  WsScope ws_scope(c);
+  if (ldx == 0) ldx = Cc;
+  split = split ? 1 : 0;
+  const int W4 = 4 * Cc, wz = split ? 3 : 1;
+  const size_t npix = (size_t)n_cond * HW, rows = npix + nfill, crows = npix * D;
+  half_t* cn = ws_alloc<half_t>(c, crows * ldx + 8);
+  half_t* z = ws_alloc<half_t>(c, (rows + 1) * W4 * wz);
+  half_t* fr = ws_alloc<half_t>(c, (size_t)W4 * 3);
+  WS_CHECK(cn && z && fr);
+  HIP_CHECK_RET(hipMemsetAsync(cn, 0xFF, (crows * ldx + 8) * sizeof(half_t), s));
+  HIP_CHECK_RET(hipMemsetAsync(z, 0xFF, (rows + 1) * W4 * wz * sizeof(half_t), s));
+  if (crows) hipLaunchKernelGGL(rows_f32_to_f16_ld_kernel, dim3(nblk(crows * Cc)), dim3(256), 0, s, context, crows, Cc, cn, ldx);
+  if (nfill > 0) {
+    if (split) RET_IF(launch_rows_f32_to_f16_split(fill_row, W4, 1, W4, fr, s));
+    else RET_IF(launch_f32_to_f16(fill_row, fr, W4, s));
+  }
+  RET_IF(launch_depth_attn(qk, cn, z, n_cond, HW, D, Cc, heads, s, split, nfill, nfill > 0 ? fr : nullptr, ldx));
+  const size_t n = (rows + 1) * W4;
+  if (split) {  // the guard row's three blocks are all NaN: NaN != NaN, so it comes back NaN
+    hipLaunchKernelGGL(split_rows_to_f32_kernel, dim3(nblk(n)), dim3(256), 0, s, z, (int)(rows + 1), W4, out);
+    if (hi_out) hipLaunchKernelGGL(rows_f16_ld_to_f32_kernel, dim3(nblk(n)), dim3(256), 0, s, z, rows + 1, W4, 3 * W4, hi_out);
+  } else {
+    hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk(n)), dim3(256), 0, s, z, out, n);
+  }
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }

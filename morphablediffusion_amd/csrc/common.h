@@ -200,6 +200,7 @@ int launch_softmax_rows_f32(const float* s, long rows, int cols, float* p, hipSt
 // ldx (0 = Cc): halfs between consecutive rows of ctxn (the block's column slice of a context fold shared by one level)
 int launch_depth_attn(const float* qk, const half_t* ctxn, half_t* z, int n_cond, int HW, int D, int Cc, int heads,
                       hipStream_t s, int split = 0, int nfill = 0, const half_t* fill_row = nullptr, int ldx = 0);
+int depth_attn_check(int D, int Cc, int heads, int ldx, int nfill);  // the launcher's shape check alone: 0, or mvd_fail
 int launch_small_linear(const float* a, int lda, int rows, int K, const half_t* w, const float* bias, int N,
                         int act_in, float* out, int ldo, int accumulate, hipStream_t s);
 int launch_timestep_embedding(const int64_t* t, int B, int dim, float* out, hipStream_t s);

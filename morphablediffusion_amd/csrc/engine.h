@@ -502,7 +502,8 @@ struct Carry;
 int unet_embeddings(mvd_ctx* c, const int64_t* t, const float* context, int Bv, hipStream_t s, float** e0_out, float** e1_out,
                     float** e2_out, float** ea_out, float** a2_out);
 int engine_unet_block(mvd_ctx* c, const char* path, const float* x_nhwc, int B, int C, int H, int W, const int64_t* t,
-                      const float* context, const float* vol_ndhwc, int D, float* out_nhwc, int* Cout, int* Hout, hipStream_t s);
+                      const float* context, const float* vol_ndhwc, int D, int n_ctx, float* out_nhwc, int* Cout, int* Hout,
+                      hipStream_t s);
 int unet_do_res(Fwd& f, const ResW& r, View in, View out, int H, int W, ResSaved* sv = nullptr, Carry* in_carry = nullptr,
                 Carry* out_carry = nullptr);
 int unet_do_st(Fwd& f, const STW& t, View in, View out, int H, int W, STSaved* sv = nullptr, Carry* in_carry = nullptr,

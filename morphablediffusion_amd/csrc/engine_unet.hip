@@ -1449,7 +1449,8 @@ int engine_unet(mvd_ctx* c, const float* x_nhwc, int x_ld, const int64_t* t, con
 // One block of the UNet on its own input (include/mvd.h: mvd_unet_block): the block-level parity tests of SURVEY section 8
 // rows a19-a22 run the production block code -- same plans, same kernels -- against the reference's block goldens.
 int engine_unet_block(mvd_ctx* c, const char* path, const float* x_nhwc, int B, int C, int H, int W, const int64_t* t,
-                      const float* context, const float* vol_ndhwc, int D, float* out_nhwc, int* Cout, int* Hout, hipStream_t s) {
+                      const float* context, const float* vol_ndhwc, int D, int n_ctx, float* out_nhwc, int* Cout, int* Hout,
+                      hipStream_t s) {
   if (!c->finalized || !c->has_unet) return mvd_fail("UNet weights not uploaded / finalized");
   const mvd_unet_config& u = c->u;
   int level = 0;
@@ -1473,24 +1474,27 @@ int engine_unet_block(mvd_ctx* c, const char* path, const float* x_nhwc, int B, 
   }
   WsScope ws_scope(c);
   Ctx5 src[4];
-  Fwd f{c, s, B, cond ? B : 0, cond ? D << level : 0, nullptr, context, nullptr, src, {nullptr, nullptr, nullptr, nullptr}};
+  // a DepthTransformer: the first n_ctx samples have a context volume, the others are context-free (mvd_unet_forward's n_ctx)
+  Fwd f{c, s, B, cond ? n_ctx : 0, cond && n_ctx > 0 ? D << level : 0, nullptr, context, nullptr, src, {nullptr, nullptr, nullptr, nullptr}};
   View in, out;
   in.p = const_cast<float*>(x_nhwc); in.ld = C; in.C = C;
   out.p = out_nhwc;
   if (cond) {
     if (C != cond->dim) return mvd_fail("mvd_unet_block: channel count does not match the DepthTransformer");
-    if (!vol_ndhwc || D <= 0) return mvd_fail("mvd_unet_block: a DepthTransformer needs its context volume");
-    src[level].p = vol_ndhwc;
-    src[level].f32 = 1;
-    const size_t n = (size_t)B * D * H * W * cond->Cc;
-    half_t* h = ws_alloc<half_t>(c, n);  // the forward's fp16 view of the context volume (engine_unet: fork_ctx)
-    WS_CHECK(h);
-    RET_IF(launch_f32_to_f16(vol_ndhwc, h, n, s));
-    f.src16[level] = h;
+    if (n_ctx > 0) {
+      if (!vol_ndhwc || D <= 0) return mvd_fail("mvd_unet_block: a DepthTransformer needs its context volume");
+      src[level].p = vol_ndhwc;
+      src[level].f32 = 1;
+      const size_t n = (size_t)n_ctx * D * H * W * cond->Cc;
+      half_t* h = ws_alloc<half_t>(c, n);  // the forward's fp16 view of the context volume (engine_unet: fork_ctx)
+      WS_CHECK(h);
+      RET_IF(launch_f32_to_f16(vol_ndhwc, h, n, s));
+      f.src16[level] = h;
+    }
     out.ld = out.C = cond->dim;
     *Cout = cond->dim;
     *Hout = H;
-    return unet_do_cond(f, *cond, in, out, H, W, level, -1);
+    return unet_do_cond(f, *cond, in, out, H, W, level, cond_idx);  // the block's own index: its x + K constant (CondConst)
   }
   if (C != op->cin) return mvd_fail("mvd_unet_block: channel count does not match the block");
   if (op->kind == OP_RES && !t) return mvd_fail("mvd_unet_block: a ResBlock needs the timesteps");

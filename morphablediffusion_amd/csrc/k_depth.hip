@@ -100,7 +100,9 @@ __global__ __launch_bounds__(256) void depth_attn_kernel(const float* __restrict
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[k] += a * (float)xv[k];
       }
-      for (int o = pairs; o < 64; o <<= 1) {  // P > 1: lanes it, it + pairs, ... hold the same (head, octet)
+      // P > 1 (then pairs * P == 64, every lane is in the loop): lanes it, it + pairs, ... hold the same (head, octet).  P == 1 runs
+      // no step: with a pair count below 64 that is no power of two the lanes it ^ o hold OTHER pairs or are outside the loop
+      for (int o = pairs; o < pairs * P; o <<= 1) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[k] += __shfl_xor(acc[k], o);
       }
@@ -124,20 +126,31 @@ __global__ __launch_bounds__(256) void depth_attn_kernel(const float* __restrict
 
 }  // namespace
 
-int launch_depth_attn(const float* qk, const half_t* ctxn, half_t* z, int n_cond, int HW, int D, int Cc, int heads,
-                      hipStream_t s, int split, int nfill, const half_t* fill_row, int ldx) {
+// the launcher's argument check on its own (no pointers): 0, or mvd_fail with the reason.  ldx as the launcher takes it (0 = Cc)
+int depth_attn_check(int D, int Cc, int heads, int ldx, int nfill) {
   if (heads != 4) return mvd_fail("depth_attn: the reference always uses 4 heads (attention.py:97-115)");
   if (Cc % 8 || D > 64) return mvd_fail("depth_attn: Cc must be a multiple of 8 and D <= 64");
+  if (ldx == 0) ldx = Cc;
+  if (ldx < Cc || (ldx & 7)) return mvd_fail("depth_attn: context rows must be 16-byte aligned and at least Cc wide");
+  if (nfill < 0) return mvd_fail("depth_attn: bad fill row");
+  const int x_bytes = ((D * (Cc + 8) * 2 + 15) / 16) * 16;
+  const int per_wave = x_bytes + 4 * Cc * 4 + 64 * 4 * 4;
+  if (per_wave * 4 > 160 * 1024) return mvd_fail("depth_attn: LDS budget exceeded");
+  return 0;
+}
+
+int launch_depth_attn(const float* qk, const half_t* ctxn, half_t* z, int n_cond, int HW, int D, int Cc, int heads,
+                      hipStream_t s, int split, int nfill, const half_t* fill_row, int ldx) {
+  const int npix = n_cond * HW;
+  if (depth_attn_check(D, Cc, heads, ldx, nfill)) return -1;
   if (((uintptr_t)z & 15)) return mvd_fail("depth_attn: output must be 16-byte aligned");
   if (ldx == 0) ldx = Cc;
-  if (ldx < Cc || (ldx & 7) || ((uintptr_t)ctxn & 15)) return mvd_fail("depth_attn: context rows must be 16-byte aligned and at least Cc wide");
-  const int npix = n_cond * HW;
-  if (nfill < 0 || (nfill > 0 && (!fill_row || ((uintptr_t)fill_row & 15)))) return mvd_fail("depth_attn: bad fill row");
+  if ((uintptr_t)ctxn & 15) return mvd_fail("depth_attn: context rows must be 16-byte aligned and at least Cc wide");
+  if (nfill > 0 && (!fill_row || ((uintptr_t)fill_row & 15))) return mvd_fail("depth_attn: bad fill row");
   if (npix + nfill == 0) return 0;
   const int x_bytes = ((D * (Cc + 8) * 2 + 15) / 16) * 16;
   const int per_wave = x_bytes + 4 * Cc * 4 + 64 * 4 * 4;
   const int lds = per_wave * 4;
-  if (lds > 160 * 1024) return mvd_fail("depth_attn: LDS budget exceeded");
   static bool attr_done[MVD_MAX_DEVICES] = {false};  // the attribute is per device
   bool& attr_set = attr_done[mvd_current_device()];
   if (!attr_set) {

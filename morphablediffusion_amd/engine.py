@@ -201,21 +201,28 @@ class Engine:
                                           L.ptr(srcs[1]), L.ptr(srcs[2]), L.ptr(srcs[3]), depth0, L.ptr(out), _stream()))
         return out
 
-    def unet_block(self, path, x, timesteps=None, context=None, volume=None):
+    def unet_block(self, path, x, timesteps=None, context=None, volume=None, n_ctx=None):
         """One block of DepthWiseAttention through the production block code: ``path`` is the reference module path below
         ``model.diffusion_model`` ("input_blocks.4.0", "output_blocks.8.2", "middle_conditions", "output_conditions.8", ...);
-        ResBlocks take ``timesteps`` [B], SpatialTransformers ``context`` [B,1,768], DepthTransformers ``volume`` [B,C,D,H,W]."""
+        ResBlocks take ``timesteps`` [B], SpatialTransformers ``context`` [B,1,768], DepthTransformers ``volume`` [n_ctx,C,D,H,W]:
+        the context volumes of the FIRST ``n_ctx`` samples (default: as many as ``volume`` holds), the other samples are
+        context-free (classifier-free guidance's unconditional half); ``n_ctx=0`` needs no volume."""
         dev = self.device
         x = _f32(x, dev)
         B, Cx, H, W = x.shape
         t = timesteps.to(device=dev, dtype=torch.int64).contiguous() if timesteps is not None else None
         ctx = _f32(context, dev) if context is not None else None
         vol = _f32(volume, dev) if volume is not None else None
+        if n_ctx is None:
+            n_ctx = vol.shape[0] if vol is not None else B
+        if vol is not None and vol.shape[0] != n_ctx:
+            raise ValueError(f"unet_block: volume holds {vol.shape[0]} samples, n_ctx is {n_ctx}")
         cap = B * H * W * 4 * self.ucfg.model_channels * 8
         out = torch.empty(cap, device=dev, dtype=torch.float32)
         shape = (C.c_int * 4)()
-        L.check(self.lib.mvd_unet_block(self._ctx, path.encode(), L.ptr(x), B, Cx, H, W, L.ptr(t), L.ptr(ctx), L.ptr(vol),
-                                        vol.shape[2] if vol is not None else 0, L.ptr(out), cap, shape, _stream()))
+        L.check(self.lib.mvd_unet_block(self._ctx, path.encode(), L.ptr(x), B, Cx, H, W, L.ptr(t), L.ptr(ctx),
+                                        L.ptr(vol) if n_ctx > 0 else None, vol.shape[2] if vol is not None else 0, n_ctx,
+                                        L.ptr(out), cap, shape, _stream()))
         n = shape[0] * shape[1] * shape[2] * shape[3]
         return out[:n].view(shape[0], shape[1], shape[2], shape[3]).clone()
 
@@ -873,6 +880,31 @@ class Engine:
         L.check(self.lib.mvd_op_attention(self._ctx, L.ptr(q), L.ptr(k), L.ptr(v), B, T, heads, Cc // heads, L.ptr(out),
                                           _stream()))
         return out
+
+    def op_depth_attn(self, qk, ctx, fill_row=None, nfill=0, split=False, ldx=0, heads=4, return_hi=False):
+        """depth_attn_kernel (csrc/k_depth.hip) on its own: qk [n_cond*HW, 4, Cc] (the folded query), ctx [n_cond, D, HW, Cc]
+        (rounded to fp16 by the hook, rows ``ldx`` halfs apart, pad columns NaN), fill_row [4*Cc] with nfill > 0.  Returns
+        [n_cond*HW + nfill + 1, 4*Cc] fp32: z, the fill rows, and the hook's guard row (NaN when the launch kept inside its rows);
+        split: the kernel's [hi | lo | hi] form, returned as hi + lo (with return_hi also hi alone)."""
+        dev = self.device
+        qk, ctx = _f32(qk, dev), _f32(ctx, dev)
+        n_cond, D, HW, Cc = ctx.shape
+        fr = None if fill_row is None else _f32(fill_row, dev)
+        err = self.op_depth_attn_check(D, Cc, heads=heads, ldx=ldx, nfill=nfill)
+        if err is not None:
+            raise L.MvdError(err)
+        if qk.numel() != n_cond * HW * 4 * Cc or (nfill > 0 and (fr is None or fr.numel() != 4 * Cc)):
+            raise ValueError("op_depth_attn: qk / fill_row do not match the context's shape")
+        out = torch.empty(n_cond * HW + nfill + 1, 4 * Cc, device=dev, dtype=torch.float32)
+        hi = torch.empty_like(out) if split and return_hi else None
+        L.check(self.lib.mvd_op_depth_attn(self._ctx, L.ptr(qk), L.ptr(ctx), L.ptr(fr), n_cond, HW, D, Cc, heads, ldx, bool(split),
+                                           nfill, 0, L.ptr(out), L.ptr(hi), _stream()))
+        return (out, hi) if return_hi else out
+
+    def op_depth_attn_check(self, D, Cc, heads=4, ldx=0, nfill=0):
+        """The depth-attention launcher's verdict on a shape, without launching: None, or the text of its refusal."""
+        rc = self.lib.mvd_op_depth_attn(self._ctx, None, None, None, 0, 1, D, Cc, heads, ldx, 0, nfill, 1, None, None, _stream())
+        return None if rc == 0 else self.lib.mvd_last_error().decode()
 
     def op_attention_bwd(self, q, k, v, d_out, heads):
         dev = self.device
