@@ -561,8 +561,43 @@ int engine_vertex_features(mvd_ctx* c, const float* x_noisy, const float* t_embe
 int engine_target_encoder(mvd_ctx* c, const float* x_noisy, const float* t_embed, const float* v_embed, int n_local, float* feats,
                           hipStream_t s, float* pre_own = nullptr);
 bool engine_encoder_is_fused(const mvd_ctx* c);
-// the sparse voxel CNN alone: *rows_out = feature rows [n_sites[2]][64] of the coarsest level (mesh ping-pong buffer)
-int engine_sparse_net(mvd_ctx* c, const float* fused, hipStream_t s, bool bn_batch_stats, const float** rows_out);
+// ---- the conditioner's forwards are shared with its backward (engine_train.hip), like unet_do_res / unet_do_st: each takes the
+// per-layer destinations of its intermediates.  Inference aliases them onto a few reused buffers, the backward keeps them apart.
+struct EncBufs {  // layered 2-D encoder: block inputs / output, conv1 outputs, the three GroupNorm outputs of a block, the final one
+  float *cur[4], *r1[3];
+  half_t *a1[3], *a2[3], *af;
+};
+// init conv -> 3 x [GN+SiLU+FiLM -> conv -> GN+SiLU -> conv + residual] -> GN+SiLU -> conv on n views.  w: the eight convs in
+// that order; xp: they are extended-precision packs (x0 is the [hi | lo | hi] fp16 split of the 8-wide input rows and the
+// GroupNorm outputs are 48 wide), otherwise x0 is the fp32 rows themselves and the GroupNorm outputs are 16 wide.
+int engine_encoder_layers(mvd_ctx* c, const ConvW* const w[8], bool xp, const void* x0, int n, const float* pre, const EncBufs& b,
+                          float* feats, hipStream_t s);
+struct SparseSaved {  // per layer: input rows, raw conv output, post-activation rows, BatchNorm [mean | rstd], table, row counts
+  const float* in[9];
+  float *raw[9], *post[9], *stats[9];
+  const int* nbr[9];
+  int n_out[9], n_in[9];
+};
+// the sparse voxel CNN alone: *rows_out = feature rows [n_sites[2]][64] of the coarsest level (mesh ping-pong buffer).
+// sv (training tape; batch statistics): every layer's rows go to workspace buffers of the caller's scope instead, [mean | rstd]
+// is kept, and the running statistics and bn_train_calls are left alone.
+int engine_sparse_net(mvd_ctx* c, const float* fused, hipStream_t s, bool bn_batch_stats, const float** rows_out,
+                      SparseSaved* sv = nullptr);
+struct FrustumGeom {  // FrustumTV3DNet's four levels: depth, side, voxels per volume
+  int D[4], S[4];
+  size_t vox[4];
+};
+FrustumGeom frustum_geom(const mvd_ctx* c);
+struct FrustumBufs {
+  float *xd[4], *xf[4];            // level outputs before / after the up path (inference: the same buffers, summed in place)
+  float* tmp[3];                   // stride-2 conv outputs
+  half_t *a1[3], *a2[3], *au[3];   // GroupNorm outputs of the two down blocks and the up block of a level
+  half_t* x0h = nullptr;           // level 0 after the up path in fp16 instead of xf[0]
+};
+// conv0 -> down path -> up path on TN gathered volumes gath [TN][vox[0]][64]; pre [TN][film_total]: the FiLM rows, filled by
+// `film` between conv0 and the first block (nullptr: they are filled already)
+int engine_frustum_layers(mvd_ctx* c, int TN, const half_t* gath, const float* pre, const FrustumBufs& b, hipStream_t s,
+                          const std::function<int()>* film = nullptr);
 int engine_fuse_vertex_features(mvd_ctx* c, const float* vf_all, int n_views, float* fused_out, hipStream_t s);
 // bn_batch_stats: the sparse CNN's BatchNorm1d layers normalise with the statistics of the active rows (the module in train
 // mode, as during the reference's training_step) instead of the running buffers

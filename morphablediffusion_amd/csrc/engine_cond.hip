@@ -520,12 +520,12 @@ int engine_target_encoder(mvd_ctx* c, const float* x_noisy, const float* t_embed
   // all views of the sample): pre[v][16*i + c]
   RET_IF(launch_small_linear(t_embed, td, -n_local, td, c->enc_t.w, c->enc_t.bias, 48, ACT_NONE, pre, 48, 0, s));
   RET_IF(launch_small_linear(v_embed, vd, n_local, vd, c->enc_v.w, c->enc_v.bias, 48, ACT_NONE, pre, 48, 1, s));
+  const ConvW* cw[8] = {&c->enc_init, &c->enc_blocks[0].c1, &c->enc_blocks[0].c2, &c->enc_blocks[1].c1, &c->enc_blocks[1].c2,
+                        &c->enc_blocks[2].c1, &c->enc_blocks[2].c2, &c->enc_final};
   if (fused_enc) {  // the whole encoder in one launch, one workgroup per view (k_enc.hip)
     const half_t* w[8];
     const float *bias[8], *gamma[7], *beta[7];
     int cin[8];
-    const ConvW* cw[8] = {&c->enc_init, &c->enc_blocks[0].c1, &c->enc_blocks[0].c2, &c->enc_blocks[1].c1, &c->enc_blocks[1].c2,
-                          &c->enc_blocks[2].c1, &c->enc_blocks[2].c2, &c->enc_final};
     const NormW* nw[7] = {&c->enc_blocks[0].n1, &c->enc_blocks[0].n2, &c->enc_blocks[1].n1, &c->enc_blocks[1].n2,
                           &c->enc_blocks[2].n1, &c->enc_blocks[2].n2, &c->enc_final_norm};
     for (int i = 0; i < 8; ++i) {
@@ -540,29 +540,30 @@ int engine_target_encoder(mvd_ctx* c, const float* x_noisy, const float* t_embed
     return launch_target_encoder(x_noisy, pre, n_local, w, bias, cin, gamma, beta, feats, s);
   }
   RET_IF(launch_nchw_to_nhwc(x_noisy, n_local, 4, HW, x8, 8, 8, s));
-  GemmArgs g;
+  const EncBufs b = {{h, h2, h, h2}, {r1, r1, r1}, {a, a, a}, {a, a, a}, a};  // ping-pong: one operand buffer, one conv1 output
+  return engine_encoder_layers(c, cw, false, x8, n_local, pre, b, feats, s);
+}
+
+int engine_encoder_layers(mvd_ctx* c, const ConvW* const w[8], bool xp, const void* x0, int n, const float* pre, const EncBufs& b,
+                          float* feats, hipStream_t s) {
+  const int S = c->u.image_size, HW = S * S, lda = xp ? 48 : 16;
   // no split-K anywhere in the encoder: a view's features must not depend on how many views share the launch (the sharded
   // step is bit-identical to the single-GPU one only if every per-view quantity is)
-  g.a = x8; g.a_f32 = 1; g.lda = 8; g.w = &c->enc_init; g.out = h; g.ldc = 16; g.force_splitk = 1;
-  RET_IF(run_conv2d(c, g, n_local, S, S, 1, 0, s));
-  float* cur = h;
-  float* nxt = h2;
+  auto conv = [&](const void* a, int a_ld, const ConvW* cw, float* out, const float* resid = nullptr, int a_f32 = 0) -> int {
+    GemmArgs g;
+    g.a = a; g.a_f32 = a_f32; g.lda = a_ld; g.w = cw; g.out = out; g.ldc = 16; g.resid = resid; g.ldr = resid ? 16 : 0; g.force_splitk = 1;
+    return run_conv2d(c, g, n, S, S, 1, 0, s);
+  };
+  RET_IF(conv(x0, xp ? 24 : 8, w[0], b.cur[0], nullptr, !xp));
   for (int i = 0; i < 3; ++i) {
     const EncBlockW& e = c->enc_blocks[i];
-    RET_IF(run_group_norm(c, cur, 16, n_local, HW, e.n1, 8, 1e-5f, ACT_SILU, pre + 16 * i, a, 16, s, 48));
-    g = GemmArgs();
-    g.a = a; g.lda = 16; g.w = &e.c1; g.out = r1; g.ldc = 16; g.force_splitk = 1;
-    RET_IF(run_conv2d(c, g, n_local, S, S, 1, 0, s));
-    RET_IF(run_group_norm(c, r1, 16, n_local, HW, e.n2, 8, 1e-5f, ACT_SILU, nullptr, a, 16, s));
-    g = GemmArgs();
-    g.a = a; g.lda = 16; g.w = &e.c2; g.out = nxt; g.ldc = 16; g.resid = cur; g.ldr = 16; g.force_splitk = 1;
-    RET_IF(run_conv2d(c, g, n_local, S, S, 1, 0, s));
-    std::swap(cur, nxt);
+    RET_IF(run_group_norm(c, b.cur[i], 16, n, HW, e.n1, 8, 1e-5f, ACT_SILU, pre + 16 * i, b.a1[i], lda, s, 48, xp));
+    RET_IF(conv(b.a1[i], lda, w[1 + 2 * i], b.r1[i]));
+    RET_IF(run_group_norm(c, b.r1[i], 16, n, HW, e.n2, 8, 1e-5f, ACT_SILU, nullptr, b.a2[i], lda, s, 0, xp));
+    RET_IF(conv(b.a2[i], lda, w[2 + 2 * i], b.cur[i + 1], b.cur[i]));
   }
-  RET_IF(run_group_norm(c, cur, 16, n_local, HW, c->enc_final_norm, 8, 1e-5f, ACT_SILU, nullptr, a, 16, s));
-  g = GemmArgs();
-  g.a = a; g.lda = 16; g.w = &c->enc_final; g.out = feats; g.ldc = 16; g.force_splitk = 1;
-  return run_conv2d(c, g, n_local, S, S, 1, 0, s);
+  RET_IF(run_group_norm(c, b.cur[3], 16, n, HW, c->enc_final_norm, 8, 1e-5f, ACT_SILU, nullptr, b.af, lda, s, 0, xp));
+  return conv(b.af, lda, w[7], feats);
 }
 
 int engine_vertex_features(mvd_ctx* c, const float* x_noisy, const float* t_embed, const float* v_embed,
@@ -612,35 +613,44 @@ int engine_fuse_vertex_features(mvd_ctx* c, const float* vf_all, int n_views, fl
 }
 
 // SparseConvNet (network.py:74-96): fused [Nv,16] -> feature rows of the coarsest level's active sites [n_sites[2]][64]
-// (*rows_out points into the mesh's ping-pong buffers)
-int engine_sparse_net(mvd_ctx* c, const float* fused, hipStream_t s, bool bn_batch_stats, const float** rows_out) {
+// (*rows_out points into the mesh's ping-pong buffers, or is the tape's post[8])
+int engine_sparse_net(mvd_ctx* c, const float* fused, hipStream_t s, bool bn_batch_stats, const float** rows_out, SparseSaved* sv) {
   MeshTables& m = c->mesh;
   if (!m.Nv) return mvd_fail("mvd_set_mesh must be called first");
+  if (sv && !bn_batch_stats) return mvd_fail("engine_sparse_net: the tape is of the batch-statistics form");
   const float* in = fused;
-  int lvl = 0, pp = 0;
+  int lvl = 0, pp = 0, n_in = m.Nv;
   for (int i = 0; i < 9; ++i) {
     const SparseLayerW& L = c->sparse[i];
     const int* nbr;
-    int n_out;
     if (L.strided) {
       nbr = m.nbr_down[lvl];
       ++lvl;
-      n_out = m.n_sites[lvl];
     } else {
       nbr = m.nbr_subm[lvl];
-      n_out = m.n_sites[lvl];
     }
+    const int n_out = m.n_sites[lvl];
     float* out = m.feat[pp];
-    if (bn_batch_stats) {  // train mode: raw conv, then BatchNorm1d(eps 1e-3) on the statistics of the active rows + ReLU
+    if (sv) {  // raw conv output and post-activation rows of every layer, BatchNorm [mean | rstd]
+      sv->in[i] = in, sv->nbr[i] = nbr, sv->n_out[i] = n_out, sv->n_in[i] = n_in;
+      sv->raw[i] = ws_alloc<float>(c, (size_t)n_out * L.cout);
+      sv->post[i] = out = ws_alloc<float>(c, (size_t)n_out * L.cout);
+      WS_CHECK(sv->raw[i] && sv->post[i]);
+      sv->stats[i] = ws_alloc<float>(c, (size_t)2 * L.cout);
+      WS_CHECK(sv->stats[i]);
+      RET_IF(launch_sparse_conv(in, nbr, n_out, L.cin, L.cout, L.w, L.wp, nullptr, nullptr, sv->raw[i], s));
+      RET_IF(launch_bn_rows_relu(sv->raw[i], out, n_out, L.cout, L.gamma, L.beta, 1e-3f, sv->stats[i], s));
+    } else if (bn_batch_stats) {  // train mode: raw conv, then BatchNorm1d(eps 1e-3) on the statistics of the active rows + ReLU
       RET_IF(launch_sparse_conv(in, nbr, n_out, L.cin, L.cout, L.w, L.wp, nullptr, nullptr, out, s));
       RET_IF(launch_bn_rows_relu(out, out, n_out, L.cout, L.gamma, L.beta, 1e-3f, nullptr, s, L.rmean, L.rvar, 0.01f));
     } else {
       RET_IF(launch_sparse_conv(in, nbr, n_out, L.cin, L.cout, L.w, L.wp, L.scale, L.shift, out, s));
     }
     in = out;
+    n_in = n_out;
     pp ^= 1;
   }
-  if (bn_batch_stats && c->sparse[0].rmean) ++c->bn_train_calls;
+  if (bn_batch_stats && !sv && c->sparse[0].rmean) ++c->bn_train_calls;
   *rows_out = in;
   return 0;
 }
@@ -655,21 +665,69 @@ int engine_volume_from_fused(mvd_ctx* c, const float* fused, hipStream_t s, bool
   return 0;
 }
 
-// construct_view_frustum_volume (morphable_diffusion.py:265-320): frustum gather + FrustumTV3DNet
-// (network.py:313-347).  Outputs stay channels-last fp32 in the workspace (caller owns the mark).
-// FrustumTV3DNet (network.py:313-347) on TN gathered frustum volumes; the caller fills `gath` [TN][D0*S0*S0][64] fp16 through
-// `gather` and `pre` [TN][film_total] (x + t_conv(t) + v_conv(v) of all nine blocks) through `film`.  The launch order --
-// gather, conv0, FiLM projections -- is the one the side-stream determinism runs of DESIGN section 4 were made with.
+// One block of the two U-shaped 3-D networks (FrustumTV3DNet, SpatialTime3DNet): GroupNorm(8) + SiLU of x [B][D*H*W][cin] with
+// the block's FiLM row folded in -> fp16 operand `a` -> g's 3x3x3 conv of stride 1 / 2 or, stride 0, its transposed conv.
+// g carries the weights, the output and the residual.
+static int film_block3d(mvd_ctx* c, const float* x, int cin, const NormW& gn, const float* film, int film_ld, half_t* a, GemmArgs g,
+                        int B, int D, int H, int W, int stride, hipStream_t s) {
+  RET_IF(run_group_norm(c, x, cin, B, D * H * W, gn, 8, 1e-5f, ACT_SILU, film, a, cin, s, film_ld));
+  g.a = a; g.lda = cin;
+  return stride ? run_conv3d(c, g, B, D, H, W, stride, s) : run_convT3d(c, g, B, D, H, W, s);
+}
+
+FrustumGeom frustum_geom(const mvd_ctx* c) {
+  FrustumGeom g;
+  for (int l = 0; l < 4; ++l) {
+    g.D[l] = l ? (g.D[l - 1] - 1) / 2 + 1 : c->v.frustum_volume_depth;
+    g.S[l] = l ? (g.S[l - 1] - 1) / 2 + 1 : c->v.input_image_size / 8;
+    g.vox[l] = (size_t)g.D[l] * g.S[l] * g.S[l];
+  }
+  return g;
+}
+
+// FrustumTV3DNet (network.py:313-347) on TN gathered frustum volumes
+int engine_frustum_layers(mvd_ctx* c, int TN, const half_t* gath, const float* pre, const FrustumBufs& b, hipStream_t s,
+                          const std::function<int()>* film) {
+  const FrustumGeom geo = frustum_geom(c);
+  const int *fd = c->v.frustum_dims, *D = geo.D, *S = geo.S, FT = c->film_total;
+  GemmArgs g;
+  g.a = gath; g.lda = 64; g.w = &c->fr_conv0; g.out = b.xd[0]; g.ldc = fd[0];
+  RET_IF(run_conv3d(c, g, TN, D[0], S[0], S[0], 1, s));
+  if (film) RET_IF((*film)());
+  // down path: conv{1,3,5} stride 2, conv{2,4,6} stride 1
+  for (int l = 0; l < 3; ++l) {
+    const FrustumBlockW& b1 = c->fr_blocks[2 * l];
+    const FrustumBlockW& b2 = c->fr_blocks[2 * l + 1];
+    g = GemmArgs();
+    g.w = &b1.conv; g.out = b.tmp[l]; g.ldc = fd[l + 1];
+    RET_IF(film_block3d(c, b.xd[l], fd[l], b1.gn, pre + c->film_off[2 * l], FT, b.a1[l], g, TN, D[l], S[l], S[l], 2, s));
+    g = GemmArgs();
+    g.w = &b2.conv; g.out = b.xd[l + 1]; g.ldc = fd[l + 1];
+    RET_IF(film_block3d(c, b.tmp[l], fd[l + 1], b2.gn, pre + c->film_off[2 * l + 1], FT, b.a2[l], g, TN, D[l + 1], S[l + 1], S[l + 1], 1, s));
+  }
+  // up path: xf_l = up(xf_{l+1}) + xd_l through the residual epilogue (in place where xf_l == xd_l); xf_3 is xd_3
+  for (int l = 2; l >= 0; --l) {
+    const FrustumBlockW& u = c->fr_up[2 - l];
+    g = GemmArgs();
+    g.w = &u.conv; g.out = b.xf[l]; g.ldc = fd[l]; g.resid = b.xd[l]; g.ldr = fd[l];
+    if (l == 0 && b.x0h) {
+      g.out = b.x0h;
+      g.out_f32 = 0;
+    }
+    RET_IF(film_block3d(c, b.xf[l + 1], fd[l + 1], u.gn, pre + c->film_off[6 + (2 - l)], FT, b.au[l], g, TN, D[l + 1], S[l + 1], S[l + 1], 0, s));
+  }
+  return 0;
+}
+
+// construct_view_frustum_volume (morphable_diffusion.py:265-320): frustum gather + FrustumTV3DNet.  Outputs stay channels-last
+// fp32 in the workspace (caller owns the mark).  The caller fills `gath` [TN][D0*S0*S0][64] fp16 through `gather` and `pre`
+// [TN][film_total] (x + t_conv(t) + v_conv(v) of all nine blocks) through `film`.  The launch order -- gather, conv0, FiLM
+// projections -- is the one the side-stream determinism runs of DESIGN section 4 were made with.
 template <typename Gather, typename Film>
 static int frustum_net(mvd_ctx* c, int TN, FrustumOut* out, hipStream_t s, bool half0, Gather&& gather, Film&& film) {
-  const int D0 = c->v.frustum_volume_depth, S0 = c->v.input_image_size / 8;
+  const FrustumGeom geo = frustum_geom(c);
   const int* fd = c->v.frustum_dims;
-  int D[4], S[4];
-  for (int l = 0; l < 4; ++l) {
-    D[l] = l ? (D[l - 1] - 1) / 2 + 1 : D0;
-    S[l] = l ? (S[l - 1] - 1) / 2 + 1 : S0;
-  }
-  auto vox = [&](int l) { return (size_t)TN * D[l] * S[l] * S[l]; };
+  auto vox = [&](int l) { return (size_t)TN * geo.vox[l]; };
   // outputs (persist for the caller)
   float* x[4];
   for (int l = 0; l < 4; ++l) {
@@ -702,40 +760,10 @@ static int frustum_net(mvd_ctx* c, int TN, FrustumOut* out, hipStream_t s, bool 
     c->dbg.push_back({"x2", x[2], vox(2) * fd[2] * 4});
     c->dbg.push_back({"x3", x[3], vox(3) * fd[3] * 4});
   }
-  GemmArgs g;
-  g.a = gath; g.lda = 64; g.w = &c->fr_conv0; g.out = x[0]; g.ldc = fd[0];
-  RET_IF(run_conv3d(c, g, TN, D0, S0, S0, 1, s));
-  const int FT = c->film_total;
-  RET_IF(film(pre));
-  // down path: conv{1,3,5} stride 2, conv{2,4,6} stride 1
-  for (int l = 0; l < 3; ++l) {
-    const FrustumBlockW& b1 = c->fr_blocks[2 * l];
-    const FrustumBlockW& b2 = c->fr_blocks[2 * l + 1];
-    RET_IF(run_group_norm(c, x[l], fd[l], TN, D[l] * S[l] * S[l], b1.gn, 8, 1e-5f, ACT_SILU, pre + c->film_off[2 * l], a,
-                          fd[l], s, FT));
-    g = GemmArgs();
-    g.a = a; g.lda = fd[l]; g.w = &b1.conv; g.out = tmp; g.ldc = fd[l + 1];
-    RET_IF(run_conv3d(c, g, TN, D[l], S[l], S[l], 2, s));
-    RET_IF(run_group_norm(c, tmp, fd[l + 1], TN, D[l + 1] * S[l + 1] * S[l + 1], b2.gn, 8, 1e-5f, ACT_SILU,
-                          pre + c->film_off[2 * l + 1], a, fd[l + 1], s, FT));
-    g = GemmArgs();
-    g.a = a; g.lda = fd[l + 1]; g.w = &b2.conv; g.out = x[l + 1]; g.ldc = fd[l + 1];
-    RET_IF(run_conv3d(c, g, TN, D[l + 1], S[l + 1], S[l + 1], 1, s));
-  }
-  // up path: x_l = up(x_{l+1}) + x_l  (in place on x_l through the residual epilogue)
-  for (int l = 2; l >= 0; --l) {
-    const FrustumBlockW& u = c->fr_up[2 - l];
-    RET_IF(run_group_norm(c, x[l + 1], fd[l + 1], TN, D[l + 1] * S[l + 1] * S[l + 1], u.gn, 8, 1e-5f, ACT_SILU,
-                          pre + c->film_off[6 + (2 - l)], a, fd[l + 1], s, FT));
-    g = GemmArgs();
-    g.a = a; g.lda = fd[l + 1]; g.w = &u.conv; g.out = x[l]; g.ldc = fd[l]; g.resid = x[l]; g.ldr = fd[l];
-    if (l == 0 && x0h) {
-      g.out = x0h;
-      g.out_f32 = 0;
-    }
-    RET_IF(run_convT3d(c, g, TN, D[l + 1], S[l + 1], S[l + 1], s));
-  }
-  return 0;
+  // one buffer per level, summed in place by the up path; one stride-2 output, one operand
+  const FrustumBufs b = {{x[0], x[1], x[2], x[3]}, {x[0], x[1], x[2], x[3]}, {tmp, tmp, tmp}, {a, a, a}, {a, a, a}, {a, a, a}, x0h};
+  const std::function<int()> fill = [&]() -> int { return film(pre); };
+  return engine_frustum_layers(c, TN, gath, pre, b, s, &fill);
 }
 
 int engine_frustum(mvd_ctx* c, const float* t_embed, const float* v_embed, const int32_t* view_idx_dev, int TN,
@@ -923,10 +951,9 @@ int engine_spatial_time_volume(mvd_ctx* c, const float* x_noisy, const float* t_
   auto block = [&](int i, const float* x, int l_in, int stride, float* out) -> int {
     const SpatialBlockW& b = c->sp_blocks[i];
     const int e = E[l_in];
-    RET_IF(run_group_norm(c, x, b.cin, 1, e * e * e, b.gn, 8, 1e-5f, ACT_SILU, pre + c->sp_film_off[i], a, b.cin, s, FT));
     GemmArgs ga;
-    ga.a = a; ga.lda = b.cin; ga.w = &b.conv; ga.out = out; ga.ldc = b.cout;
-    return run_conv3d(c, ga, 1, e, e, e, stride, s);
+    ga.w = &b.conv; ga.out = out; ga.ldc = b.cout;
+    return film_block3d(c, x, b.cin, b.gn, pre + c->sp_film_off[i], FT, a, ga, 1, e, e, e, stride, s);
   };
   RET_IF(block(0, h0, 0, 1, skip[0]));  // conv0
   for (int l = 1; l < 4; ++l) {         // conv{1,3,5} stride 2, then two stride-1 blocks; the last one is the level's skip
@@ -938,10 +965,9 @@ int engine_spatial_time_volume(mvd_ctx* c, const float* x_noisy, const float* t_
   for (int l = 2; l >= 0; --l) {
     const SpatialBlockW& u = c->sp_up[2 - l];
     const int e = E[l + 1];
-    RET_IF(run_group_norm(c, skip[l + 1], u.cin, 1, e * e * e, u.gn, 8, 1e-5f, ACT_SILU, pre + c->sp_film_off[10 + (2 - l)], a, u.cin, s, FT));
     GemmArgs ga;
-    ga.a = a; ga.lda = u.cin; ga.w = &u.conv; ga.out = skip[l]; ga.ldc = u.cout; ga.resid = skip[l]; ga.ldr = u.cout;
-    RET_IF(run_convT3d(c, ga, 1, e, e, e, s));
+    ga.w = &u.conv; ga.out = skip[l]; ga.ldc = u.cout; ga.resid = skip[l]; ga.ldr = u.cout;
+    RET_IF(film_block3d(c, skip[l + 1], u.cin, u.gn, pre + c->sp_film_off[10 + (2 - l)], FT, a, ga, 1, e, e, e, 0, s));
   }
   // the caller may ask for the network's own output, so the add into the mesh volume is a pass of its own (2 x 8 MB at V = 32)
   if (volume_out) RET_IF(launch_nhwc_to_nchw(skip[0], d[0], 1, d[0], (int)sp_vox(V, 0), volume_out, s));

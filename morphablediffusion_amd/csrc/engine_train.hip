@@ -1085,16 +1085,6 @@ int engine_train_cond_backward(mvd_ctx* c, int cond_idx, const float* x, const f
 
 // ---------------------------------------------------------------------------------------------------------------------
 namespace {
-// what the per-sample stages of the conditioner's backward hand to each other (all pointers into the call's workspace scope)
-struct CondSample {
-  int* vidx;
-  float* vf;
-  const float* sp_in[9];
-  float *sp_raw[9], *sp_post[9], *sp_stats[9];
-  const int* sp_nbr[9];
-  int sp_nout[9], sp_nin[9];
-};
-
 // The conditioner's three gather adjoints on the ACTIVE slot's cameras / mesh, in the form asked for: det == false the fp32-atomic
 // scatters (they accumulate: the caller zeroes the output first), det == true the gather forms of the deterministic mode (they
 // write every element; their scratch comes from the workspace).  Counted per form in mvd_ctx::adjoint_calls.
@@ -1124,12 +1114,323 @@ int adj_vertex(mvd_ctx* c, bool det, const float* d_vf, const int* view_idx, int
   WS_CHECK(scratch);
   return cbwd_vertex_gather_adj(d_vf, c->cams, view_idx, n_views, m.verts, m.Nv, V, c->v.spatial_volume_length, S, persp, scratch, d_feats, s);
 }
+
+// what a sample's forward leaves for its backward (pointers into the call's workspace scope)
+struct CondSample {
+  int* vidx;  // [0..N): the views, [N]: the target view
+  float* vf;  // per-view vertex features
+  SparseSaved sp;
+};
+
+// State of one engine_train_conditioner_backward_batch call: the dimensions, the call's arguments, what crosses its stages (all
+// samples; pointers into the call's workspace scope) and each sample's tape.
+struct CondBwd {
+  mvd_ctx* c;
+  hipStream_t s;
+  int B, N, S, HW, rows, td, vd, V, persp, FT, BN;
+  size_t rows_all;
+  bool det;  // the gather forms of the three adjoints write every element: their zero fills are skipped
+  FrustumGeom geo;
+  const float* v_embed_all;
+  const int* target_idx;
+  float* const* dsrc;
+  float *dbg_dvolume, *dbg_dfused, *dbg_dfeats, *dbg_dtembed;
+  float *t_emb_all, *d_temb_all, *vt_all, *pre_f_all, *d_gath_all, *feats_all, *d_feats_all;
+  half_t* gath_all;
+  float *e0, *u1, *e1;  // step MLP: temb(t), W0 temb + b0, its SiLU
+  float *x8, *pre_e;    // 2-D encoder: padded input rows, FiLM rows
+  EncBufs enc;
+  std::vector<CondSample> st;
+  // MVD_COND_BWD_TIMING=1: host-side enqueue time of each phase on stderr (development aid)
+  bool host_timing;
+  double t_last;
+
+  float* F(size_t n) const { return ws_alloc<float>(c, n); }
+  half_t* H16(size_t n) const { return ws_alloc<half_t>(c, n); }
+  static double now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+  void mark(const char* what) {
+    if (!host_timing) return;
+    const double t = now();
+    fprintf(stderr, "[cond-bwd host] %-28s %7.3f ms\n", what, t - t_last);
+    t_last = t;
+  }
+};
+
+// stage 1, per sample (its slot active): forward up to the gathered frustum features and the FiLM rows of the frustum network
+int cond_fwd_sample(CondBwd& q, int bi) {
+  mvd_ctx* c = q.c;
+  hipStream_t s = q.s;
+  if (!c->mesh.Nv || !c->cams) return mvd_fail("mvd_set_mesh / mvd_set_cameras must be called first");
+  MeshTables& m = c->mesh;
+  const int N = q.N, Nv = m.Nv, td = q.td, vd = q.vd, V = q.V, FT = q.FT, tgt = q.target_idx[bi];
+  const float* v_embed = q.v_embed_all + (size_t)bi * N * vd;
+  CondSample& P = q.st[bi];
+  P.vidx = (int*)c->ws.alloc(sizeof(int) * (N + 1));
+  WS_CHECK(P.vidx);
+  hipLaunchKernelGGL(iota_kernel, dim3(1), dim3(64), 0, s, P.vidx, N, 0);
+  hipLaunchKernelGGL(iota_kernel, dim3(1), dim3(64), 0, s, P.vidx + N, 1, tgt);
+  HIP_CHECK_RET(hipGetLastError());
+  const float *t_emb = q.t_emb_all + (size_t)bi * td, *feats = q.feats_all + (size_t)bi * q.rows * 16;
+  // vertex features, view fusion
+  P.vf = q.F((size_t)N * Nv * 16);
+  float* fused = q.F((size_t)Nv * 16);
+  WS_CHECK(P.vf && fused);
+  RET_IF(launch_vertex_gather(feats, c->cams, P.vidx, N, m.verts, Nv, V, c->v.spatial_volume_length, q.S, q.persp, P.vf, s));
+  RET_IF(launch_fuse_views(P.vf, N, Nv, N, c->fuse_w, c->fuse_b, fused, 0, s));
+  const float* sp_rows = nullptr;  // sparse voxel CNN, train mode
+  RET_IF(engine_sparse_net(c, fused, s, true, &sp_rows, &P.sp));
+  q.mark("fwd: gather, fuse, sparse net");
+  float* volume = q.F((size_t)V * V * V * 64);
+  WS_CHECK(volume);
+  RET_IF(launch_latent_gather(sp_rows, m.grid2, m.shape[2][0], m.shape[2][1], m.shape[2][2], m.min_xyz, m.out_sh, c->v.voxel_size, V,
+                              c->v.spatial_volume_length, volume, s));
+  RET_IF(launch_frustum_gather(volume, c->cams, P.vidx + N, 1, q.geo.D[0], q.geo.S[0], V, c->v.spatial_volume_length, q.persp,
+                               q.gath_all + (size_t)bi * q.geo.vox[0] * 64, s));
+  float* pre_row = q.pre_f_all + (size_t)bi * FT;
+  RET_IF(launch_small_linear(t_emb, td, 1, td, c->film_t.w, c->film_t.bias, FT, ACT_NONE, pre_row, FT, 0, s));
+  RET_IF(launch_small_linear(v_embed + (size_t)tgt * vd, vd, 1, vd, c->film_v.w, c->film_v.bias, FT, ACT_NONE, pre_row, FT, 1, s));
+  HIP_CHECK_RET(hipMemcpyAsync(q.vt_all + (size_t)bi * vd, v_embed + (size_t)tgt * vd, vd * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+// stage 2: FrustumTV3DNet forward + backward on samples [b0, b0 + Bc), the samples as its batch (Bc <= 16: 32-bit operand offsets
+// of the level-0 weight-gradient GEMM)
+int cond_frustum_chunk(CondBwd& q, int b0, size_t Bc) {
+  mvd_ctx* c = q.c;
+  hipStream_t s = q.s;
+  const int *fd = c->v.frustum_dims, *Dl = q.geo.D, *Sl = q.geo.S, FT = q.FT, td = q.td, vd = q.vd;
+  const size_t* vox = q.geo.vox;
+  WsScope chunk_scope(c, WS_BLOCK);
+  half_t* gath = q.gath_all + (size_t)b0 * vox[0] * 64;
+  float* pre_f = q.pre_f_all + (size_t)b0 * FT;
+  FrustumBufs fb;  // every layer's output in a buffer of its own; level 3 has no up block: xf[3] is xd[3]
+  for (int l = 0; l < 4; ++l) {
+    fb.xd[l] = q.F(Bc * vox[l] * fd[l]);
+    fb.xf[l] = l < 3 ? q.F(Bc * vox[l] * fd[l]) : fb.xd[l];
+    WS_CHECK(fb.xd[l] && fb.xf[l]);
+  }
+  for (int l = 0; l < 3; ++l) {
+    fb.tmp[l] = q.F(Bc * vox[l + 1] * fd[l + 1]);
+    fb.a1[l] = q.H16(Bc * vox[l] * fd[l]);
+    fb.a2[l] = q.H16(Bc * vox[l + 1] * fd[l + 1]);
+    fb.au[l] = q.H16(Bc * vox[l + 1] * fd[l + 1]);
+    WS_CHECK(fb.tmp[l] && fb.a1[l] && fb.a2[l] && fb.au[l]);
+  }
+  RET_IF(engine_frustum_layers(c, (int)Bc, gath, pre_f, fb, s));
+  q.mark("fwd: frustum net");
+  Fwd f{c, s, (int)Bc, (int)Bc, 0, nullptr, nullptr, nullptr, nullptr, {nullptr, nullptr, nullptr, nullptr}};
+  TrainTape tape;
+  Bwd b{c, s, (int)Bc, &f, &tape};
+  float* d_pre_f = q.F(Bc * FT);
+  WS_CHECK(d_pre_f);
+  HIP_CHECK_RET(hipMemsetAsync(d_pre_f, 0, Bc * FT * sizeof(float), s));
+  half_t* dy16;
+  float* gl[4];
+  for (int l = 0; l < 4; ++l) gl[l] = q.dsrc[l] + (size_t)b0 * vox[l] * fd[l];  // dL/d x_l, accumulated in place
+  // up path (forward order l = 2, 1, 0): x_l = xd_l + convT(silu(GN(xf_{l+1} + film)))
+  for (int l = 0; l <= 2; ++l) {
+    WsScope sc(c, WS_BLOCK);
+    const FrustumBlockW& u = c->fr_up[2 - l];
+    float* d_au = q.F(Bc * vox[l + 1] * fd[l + 1]);
+    WS_CHECK(d_au);
+    RET_IF(grad16(c, gl[l], fd[l], (long)(Bc * vox[l]), fd[l], &dy16, s));
+    RET_IF(dgrad_conv3d(b, u.conv, 2, dy16, d_au, fd[l + 1], Dl[l], Sl[l], Sl[l], false));
+    RET_IF(wgrad_convT3d(b, u.conv, gl[l], fd[l], fb.au[l], 0, fd[l + 1], Dl[l + 1], Sl[l + 1], Sl[l + 1]));
+    RET_IF(gn_backward(b, u.gn, 8, 1e-5f, ACT_SILU, fb.xf[l + 1], fd[l + 1], d_au, fd[l + 1], (int)vox[l + 1], gl[l + 1], fd[l + 1], true,
+                       pre_f + c->film_off[6 + (2 - l)], FT, d_pre_f + c->film_off[6 + (2 - l)], FT));
+  }
+  q.mark("bwd: frustum up path");
+  // down path (forward order l = 0, 1, 2)
+  for (int l = 2; l >= 0; --l) {
+    WsScope sc(c, WS_BLOCK);
+    const FrustumBlockW& b1 = c->fr_blocks[2 * l];
+    const FrustumBlockW& b2 = c->fr_blocks[2 * l + 1];
+    float *d_a2 = q.F(Bc * vox[l + 1] * fd[l + 1]), *d_tmp = q.F(Bc * vox[l + 1] * fd[l + 1]), *d_a1 = q.F(Bc * vox[l] * fd[l]);
+    WS_CHECK(d_a2 && d_tmp && d_a1);
+    RET_IF(grad16(c, gl[l + 1], fd[l + 1], (long)(Bc * vox[l + 1]), fd[l + 1], &dy16, s));
+    RET_IF(dgrad_conv3d(b, b2.conv, 0, dy16, d_a2, fd[l + 1], Dl[l + 1], Sl[l + 1], Sl[l + 1], false));
+    RET_IF(wgrad_conv3d(b, b2.conv, gl[l + 1], fd[l + 1], fb.a2[l], 0, fd[l + 1], Dl[l + 1], Sl[l + 1], Sl[l + 1], fd[l + 1], 1));
+    RET_IF(gn_backward(b, b2.gn, 8, 1e-5f, ACT_SILU, fb.tmp[l], fd[l + 1], d_a2, fd[l + 1], (int)vox[l + 1], d_tmp, fd[l + 1], false,
+                       pre_f + c->film_off[2 * l + 1], FT, d_pre_f + c->film_off[2 * l + 1], FT));
+    RET_IF(grad16(c, d_tmp, fd[l + 1], (long)(Bc * vox[l + 1]), fd[l + 1], &dy16, s));
+    RET_IF(dgrad_conv3d(b, b1.conv, 1, dy16, d_a1, fd[l], Dl[l + 1], Sl[l + 1], Sl[l + 1], false));
+    RET_IF(wgrad_conv3d(b, b1.conv, d_tmp, fd[l + 1], fb.a1[l], 0, fd[l], Dl[l], Sl[l], Sl[l], fd[l], 2));
+    RET_IF(gn_backward(b, b1.gn, 8, 1e-5f, ACT_SILU, fb.xd[l], fd[l], d_a1, fd[l], (int)vox[l], gl[l], fd[l], true,
+                       pre_f + c->film_off[2 * l], FT, d_pre_f + c->film_off[2 * l], FT));
+  }
+  q.mark("bwd: frustum down path");
+  // conv0 on the gathered frustum features
+  float* d_gath = q.d_gath_all + (size_t)b0 * vox[0] * 64;
+  RET_IF(grad16(c, gl[0], fd[0], (long)(Bc * vox[0]), fd[0], &dy16, s));
+  RET_IF(dgrad_conv3d(b, c->fr_conv0, 0, dy16, d_gath, 64, Dl[0], Sl[0], Sl[0], false));
+  RET_IF(wgrad_conv3d(b, c->fr_conv0, gl[0], fd[0], gath, 0, 64, Dl[0], Sl[0], Sl[0], 64, 1));
+  // FiLM projections of the nine frustum blocks: film = t_conv(t_emb) + v_conv(v_embed[target])
+  for (int i = 0; i < 9; ++i) {
+    const FrustumBlockW& blk = i < 6 ? c->fr_blocks[i] : c->fr_up[i - 6];
+    const float* dp = d_pre_f + c->film_off[i];
+    RET_IF(lin_wgrad(c, blk.t_conv.key, dp, FT, q.t_emb_all + (size_t)b0 * td, td, (int)Bc, blk.cin, td, s));
+    RET_IF(lin_wgrad(c, blk.v_conv.key, dp, FT, q.vt_all + (size_t)b0 * vd, vd, (int)Bc, blk.cin, vd, s));
+  }
+  RET_IF(cbwd_small_linear_bwd(d_pre_f, FT, (int)Bc, FT, c->film_t.w, td, q.d_temb_all + (size_t)b0 * td, td, 1, s));
+  q.mark("bwd: frustum net, conv0 + FiLM");
+  return 0;
+}
+
+// stage 3, per sample (its slot active): the gathers' adjoints, sparse CNN, view fusion, vertex gather
+int cond_bwd_sample(CondBwd& q, int bi) {
+  mvd_ctx* c = q.c;
+  hipStream_t s = q.s;
+  const bool det = q.det;
+  const int N = q.N, V = q.V, Nv = c->mesh.Nv;
+  const std::string SV = "spatial_volume.";
+  WsScope sample_scope(c, WS_BLOCK);
+  const CondSample& P = q.st[bi];
+  const SparseSaved& sp = P.sp;
+  const MeshTables& m = c->mesh;
+  // frustum gather, latent-code gather: scatter adjoints
+  float* d_vol = q.F((size_t)V * V * V * 64);
+  float* d_cur = q.F((size_t)sp.n_out[8] * 64);
+  WS_CHECK(d_vol && d_cur);
+  if (!det) {
+    HIP_CHECK_RET(hipMemsetAsync(d_vol, 0, (size_t)V * V * V * 64 * sizeof(float), s));
+    HIP_CHECK_RET(hipMemsetAsync(d_cur, 0, (size_t)sp.n_out[8] * 64 * sizeof(float), s));
+  }
+  RET_IF(adj_frustum(c, det, q.d_gath_all + (size_t)bi * q.geo.vox[0] * 64, P.vidx + N, 1, q.geo.D[0], q.geo.S[0], d_vol, s));
+  if (q.dbg_dvolume) RET_IF(launch_nhwc_to_nchw(d_vol, 64, 1, 64, V * V * V, q.dbg_dvolume, s));
+  RET_IF(adj_latent(c, det, d_vol, d_cur, s));
+  q.mark("bwd: scatters");
+  for (int i = 8; i >= 0; --i) {  // sparse voxel CNN
+    const SparseLayerW& L = c->sparse[i];
+    const int n_out = sp.n_out[i], n_in = sp.n_in[i];
+    const int* nbr = sp.nbr[i];
+    float* Gg = engine_grad(c, L.bnkey + ".weight");
+    float* Gb = engine_grad(c, L.bnkey + ".bias");
+    float* Gw = engine_grad(c, L.wkey);
+    if (!Gg || !Gb || !Gw) return mvd_fail("conditioner backward: sparse layer parameters missing from the arena");
+    {
+      WsScope sc(c, WS_TEMP);
+      float* bn_scr = q.F((size_t)cbwd_bn_scratch_floats(n_out, L.cout));
+      WS_CHECK(bn_scr);
+      RET_IF(cbwd_bn_rows_relu(sp.raw[i], d_cur, n_out, L.cout, L.gamma, L.beta, sp.stats[i], bn_scr, Gg, Gb, s));
+    }
+    float* dwp = q.F((size_t)27 * L.cin * L.cout);
+    float* d_in = q.F((size_t)n_in * L.cin);
+    WS_CHECK(dwp && d_in);
+    if (L.wp && L.wd) {
+      // matrix-core form (k_cond.hip / k_cond_bwd.hip): gather-form data gradient through the layer's own table with the tap
+      // flipped (submanifold) or through the inverse table (strided) -- no atomics, no zero fill.  At level 0 the gradients of
+      // duplicate vertices' rows are folded into their representatives' first (the table is symmetric over those only).
+      const bool lvl0_subm = !L.strided && nbr == m.nbr_subm[0];
+      if (lvl0_subm && !det) RET_IF(cbwd_sparse_fold_dups(d_cur, nbr, n_out, L.cout, s));
+      if (lvl0_subm && det) {  // the same fold with the duplicates' rows added in row order
+        WsScope sc(c, WS_TEMP);
+        int* flag = (int*)q.F((size_t)n_out);
+        WS_CHECK(flag);
+        RET_IF(cbwd_sparse_fold_dups_det(d_cur, nbr, n_out, L.cout, flag, s));
+      }
+      {
+        WsScope sc(c, WS_TEMP);
+        float* dw_part = q.F((size_t)cbwd_sparse_wgrad_chunks(n_out) * 27 * L.cin * L.cout);
+        WS_CHECK(dw_part);
+        RET_IF(cbwd_sparse_wgrad_mfma(sp.in[i], nbr, d_cur, n_out, L.cin, L.cout, dwp, dw_part, s));
+      }
+      const int* table = nbr;
+      WsScope sc(c, WS_TEMP);
+      if (L.strided) {
+        int* inv = (int*)q.F((size_t)n_in * 27);
+        WS_CHECK(inv);
+        RET_IF(cbwd_sparse_inverse_table(nbr, n_out, n_in, inv, s));
+        table = inv;
+      }
+      RET_IF(launch_sparse_conv(d_cur, table, n_in, L.cout, L.cin, nullptr, L.wd, nullptr, nullptr, d_in, s, lvl0_subm ? 1 : 0));
+    } else {
+      if (det) return mvd_fail("deterministic mode: this sparse layer has no matrix-core form (its site-form data gradient adds with "
+                               "fp32 atomics); unset MVD_SPARSE_VALU");
+      HIP_CHECK_RET(hipMemsetAsync(d_in, 0, (size_t)n_in * L.cin * sizeof(float), s));
+      WsScope sc(c, WS_TEMP);
+      float* dw_part = q.F((size_t)cbwd_sparse_wgrad_chunks(n_out) * 27 * L.cin * L.cout);
+      WS_CHECK(dw_part);
+      RET_IF(cbwd_sparse_conv(sp.in[i], nbr, d_cur, n_out, L.cin, L.cout, L.w, d_in, dwp, dw_part, s));
+    }
+    RET_IF(cbwd_sparse_w_unpack_add(dwp, L.cin, L.cout, L.layout, Gw, s));
+    d_cur = d_in;
+  }
+  q.mark("bwd: sparse net");
+  float* d_fused = d_cur;  // [Nv][16]
+  if (q.dbg_dfused) HIP_CHECK_RET(hipMemcpyAsync(q.dbg_dfused, d_fused, (size_t)Nv * 16 * sizeof(float), hipMemcpyDeviceToDevice, s));
+  // view fusion, vertex gather
+  float *d_vf = q.F((size_t)N * Nv * 16), *d_feats = q.d_feats_all + (size_t)bi * q.rows * 16;
+  float* fuse_part = q.F((size_t)cbwd_fuse_scratch_floats(Nv));
+  WS_CHECK(d_vf && fuse_part);
+  RET_IF(cbwd_fuse(d_fused, P.vf, c->fuse_w, N, Nv, N, d_vf, engine_grad(c, SV + "smpl_feature_extractor.conv0.weight"),
+                   engine_grad(c, SV + "smpl_feature_extractor.conv0.bias"), fuse_part, s));
+  RET_IF(adj_vertex(c, det, d_vf, P.vidx, N, d_feats, s));
+  if (q.dbg_dfeats) RET_IF(launch_nhwc_to_nchw(d_feats, 16, N, 16, q.HW, q.dbg_dfeats, s));
+  q.mark("bwd: fuse + vertex scatter");
+  return 0;
+}
+
+// stage 4, all samples at once: 2-D encoder backward (B * N views as its batch), FiLM projections, step MLP
+int cond_bwd_head(CondBwd& q) {
+  mvd_ctx* c = q.c;
+  hipStream_t s = q.s;
+  const int B = q.B, N = q.N, S = q.S, HW = q.HW, td = q.td, vd = q.vd, BN = q.BN;
+  const size_t rows_all = q.rows_all;
+  const EncBufs& e = q.enc;
+  Fwd f{c, s, BN, BN, 0, nullptr, nullptr, nullptr, nullptr, {nullptr, nullptr, nullptr, nullptr}};
+  TrainTape tape;
+  Bwd b{c, s, BN, &f, &tape};
+  half_t* dy16;
+  float *d_a = q.F(rows_all * 16), *d_r = q.F(rows_all * 16), *d_x = q.F(rows_all * 16), *d_nxt = q.F(rows_all * 16);
+  float* d_pre_e = q.F((size_t)BN * 48);
+  WS_CHECK(d_a && d_r && d_x && d_nxt && d_pre_e);
+  RET_IF(grad16(c, q.d_feats_all, 16, (long)rows_all, 16, &dy16, s));
+  RET_IF(dgrad_conv3(b, c->enc_final, dy16, d_a, 16, S, S, false));
+  RET_IF(wgrad_conv3(b, c->enc_final, q.d_feats_all, 16, e.af, 0, 48, S, S, 16, 1, 0));
+  RET_IF(gn_backward(b, c->enc_final_norm, 8, 1e-5f, ACT_SILU, e.cur[3], 16, d_a, 16, HW, d_nxt, 16, false));
+  for (int i = 2; i >= 0; --i) {
+    const EncBlockW& w = c->enc_blocks[i];
+    RET_IF(grad16(c, d_nxt, 16, (long)rows_all, 16, &dy16, s));
+    RET_IF(dgrad_conv3(b, w.c2, dy16, d_a, 16, S, S, false));
+    RET_IF(wgrad_conv3(b, w.c2, d_nxt, 16, e.a2[i], 0, 48, S, S, 16, 1, 0));
+    RET_IF(gn_backward(b, w.n2, 8, 1e-5f, ACT_SILU, e.r1[i], 16, d_a, 16, HW, d_r, 16, false));
+    RET_IF(grad16(c, d_r, 16, (long)rows_all, 16, &dy16, s));
+    RET_IF(dgrad_conv3(b, w.c1, dy16, d_a, 16, S, S, false));
+    RET_IF(wgrad_conv3(b, w.c1, d_r, 16, e.a1[i], 0, 48, S, S, 16, 1, 0));
+    RET_IF(gn_backward(b, w.n1, 8, 1e-5f, ACT_SILU, e.cur[i], 16, d_a, 16, HW, d_x, 16, false, q.pre_e + 16 * i, 48, d_pre_e + 16 * i, 48));
+    RET_IF(bwd_add_views(d_x, 16, d_nxt, 16, nullptr, 0, (long)rows_all, 16, 1, s));  // + the residual branch
+    std::swap(d_x, d_nxt);
+  }
+  RET_IF(wgrad_conv3(b, c->enc_init, d_nxt, 16, q.x8, 1, 8, S, S, 4, 1, 0));  // 4 latent channels (the pack pads them to 8)
+  {  // FiLM of the three encoder blocks: pre[b, v] = time_embed_i(t_emb[b]) + view_embed_i(v_embed[b, v])
+    float* dsum = q.F((size_t)B * 48);
+    WS_CHECK(dsum);
+    RET_IF(bwd_colsum_samples(d_pre_e, 1, 48, B, N, 48, dsum, 48, s));  // per sample: its N views
+    for (int i = 0; i < 3; ++i) {
+      const EncBlockW& w = c->enc_blocks[i];
+      RET_IF(lin_wgrad(c, w.t.key, dsum + 16 * i, 48, q.t_emb_all, td, B, 16, td, s));
+      RET_IF(lin_wgrad(c, w.v.key, d_pre_e + 16 * i, 48, q.v_embed_all, vd, BN, 16, vd, s));
+    }
+    RET_IF(cbwd_small_linear_bwd(dsum, 48, B, 48, c->enc_t.w, td, q.d_temb_all, td, 1, s));
+  }
+  q.mark("bwd: 2-D encoder + FiLM");
+  if (q.dbg_dtembed) HIP_CHECK_RET(hipMemcpyAsync(q.dbg_dtembed, q.d_temb_all, td * sizeof(float), hipMemcpyDeviceToDevice, s));
+  // step MLP
+  RET_IF(lin_wgrad(c, c->step_te2.key, q.d_temb_all, td, q.e1, td, B, td, td, s));
+  float* d_e1 = q.F((size_t)B * td);
+  WS_CHECK(d_e1);
+  RET_IF(cbwd_small_linear_bwd(q.d_temb_all, td, B, td, c->step_te2.w, td, d_e1, td, 0, s));
+  RET_IF(bwd_silu_inplace(d_e1, q.u1, (size_t)B * td, s));
+  return lin_wgrad(c, c->step_te0.key, d_e1, td, q.e0, td, B, td, td, s);
+}
 }  // namespace
 
-// Backward of the conditioner for B samples whose tables sit in slots[0..B): the per-sample stages (2-D encoder, gathers, sparse
-// CNN: different meshes, cameras, BatchNorm statistics) run sample by sample, the frustum network between them -- the same
-// weights on same-shaped volumes -- runs ONCE with the samples as its batch (its 8^3 / 4^3 levels are 96- and 768-row GEMMs per
-// sample).  x_noisy [B][N,4,s,s], v_embed [B][N,vd], dsrc[l] [B][vox_l][C_l] channels-last (accumulated in place).
+// Backward of the conditioner for B samples whose tables sit in slots[0..B): the per-sample stages (gathers, sparse CNN:
+// different meshes, cameras, BatchNorm statistics) run sample by sample, the 2-D encoder with the B * N views as its batch, and
+// the frustum network between them -- the same weights on same-shaped volumes -- runs ONCE with the samples as its batch (its
+// 8^3 / 4^3 levels are 96- and 768-row GEMMs per sample).  The forward that fills the tape is the inference code with its
+// per-layer destinations kept apart: engine_encoder_layers, engine_sparse_net, engine_frustum_layers (engine_cond.hip).
+// x_noisy [B][N,4,s,s], v_embed [B][N,vd], dsrc[l] [B][vox_l][C_l] channels-last (accumulated in place).
 int engine_train_conditioner_backward_batch(mvd_ctx* c, int B, const int* slots, const float* x_noisy_all, const int64_t* timesteps,
                                             const float* v_embed_all, int n_views, const int* target_idx, float* const dsrc[4],
                                             float* dbg_dvolume, float* dbg_dfused, float* dbg_dfeats, float* dbg_dtembed, hipStream_t s) {
@@ -1141,31 +1442,17 @@ int engine_train_conditioner_backward_batch(mvd_ctx* c, int B, const int* slots,
   for (int l = 0; l < 4; ++l)
     if (!dsrc[l]) return mvd_fail("conditioner backward: dL/d(frustum volume) of every level is required");
   WsScope scope(c);
-  // MVD_COND_BWD_TIMING=1: host-side enqueue time of each phase on stderr (development aid)
-  const bool host_timing = mvd_env().cond_bwd_timing;
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  double t_last = now();
-  auto mark = [&](const char* what) {
-    if (!host_timing) return;
-    const double t = now();
-    fprintf(stderr, "[cond-bwd host] %-28s %7.3f ms\n", what, t - t_last);
-    t_last = t;
-  };
-  const int N = n_views, S = c->u.image_size, HW = S * S, rows = N * HW, td = c->v.time_dim, vd = c->v.view_dim;
-  const int V = c->v.spatial_volume_size, persp = c->v.projection == 0;
-  const bool det = c->deterministic;  // the gather forms of the three adjoints write every element: their zero fills are skipped
-  const std::string SV = "spatial_volume.", FV = SV + "frustum_volume_feats.";
-  auto F = [&](size_t n) { return ws_alloc<float>(c, n); };
-  auto H16 = [&](size_t n) { return ws_alloc<half_t>(c, n); };
-  const int* fd = c->v.frustum_dims;
-  int Dl[4], Sl[4];
-  size_t vox[4];
-  for (int l = 0; l < 4; ++l) {
-    Dl[l] = l ? (Dl[l - 1] - 1) / 2 + 1 : c->v.frustum_volume_depth;
-    Sl[l] = l ? (Sl[l - 1] - 1) / 2 + 1 : c->v.input_image_size / 8;
-    vox[l] = (size_t)Dl[l] * Sl[l] * Sl[l];
-  }
-  const int FT = c->film_total;
+  CondBwd q{};
+  q.c = c, q.s = s;
+  q.host_timing = mvd_env().cond_bwd_timing, q.t_last = CondBwd::now();
+  q.B = B, q.N = n_views, q.S = c->u.image_size, q.HW = q.S * q.S, q.rows = q.N * q.HW, q.td = c->v.time_dim, q.vd = c->v.view_dim;
+  q.V = c->v.spatial_volume_size, q.persp = c->v.projection == 0, q.FT = c->film_total, q.BN = B * q.N, q.rows_all = (size_t)q.BN * q.HW;
+  q.det = c->deterministic;
+  q.geo = frustum_geom(c);
+  q.v_embed_all = v_embed_all, q.target_idx = target_idx, q.dsrc = dsrc;
+  q.dbg_dvolume = dbg_dvolume, q.dbg_dfused = dbg_dfused, q.dbg_dfeats = dbg_dfeats, q.dbg_dtembed = dbg_dtembed;
+  const int N = q.N, rows = q.rows, td = q.td, vd = q.vd, BN = q.BN;
+  const size_t rows_all = q.rows_all;
   struct SlotGuard {  // the active slot is the caller's again on every exit path
     mvd_ctx* c;
     int slot;
@@ -1181,405 +1468,75 @@ int engine_train_conditioner_backward_batch(mvd_ctx* c, int B, const int* slots,
     o->cin_l = Cl;
     o->Cin = 3 * Cl;
     o->wT = nullptr;
-    o->w = H16((size_t)w.taps * w.N * 3 * Cl);
+    o->w = q.H16((size_t)w.taps * w.N * 3 * Cl);
     WS_CHECK(o->w);
     return launch_pack_weight(mw, w.N, 3 * Cl, w.taps, 0, 0, o->w, s, cin_src, 1);
   };
-  ConvW x_init, x_c1[3], x_c2[3], x_final;
-  RET_IF(xp_pack(c->enc_init, 4, &x_init));
+  ConvW xw[8];  // init, (c1, c2) of the three blocks, final
+  const ConvW* xwp[8];
+  RET_IF(xp_pack(c->enc_init, 4, &xw[0]));
   for (int i = 0; i < 3; ++i) {
-    RET_IF(xp_pack(c->enc_blocks[i].c1, 16, &x_c1[i]));
-    RET_IF(xp_pack(c->enc_blocks[i].c2, 16, &x_c2[i]));
+    RET_IF(xp_pack(c->enc_blocks[i].c1, 16, &xw[1 + 2 * i]));
+    RET_IF(xp_pack(c->enc_blocks[i].c2, 16, &xw[2 + 2 * i]));
   }
-  RET_IF(xp_pack(c->enc_final, 16, &x_final));
+  RET_IF(xp_pack(c->enc_final, 16, &xw[7]));
+  for (int i = 0; i < 8; ++i) xwp[i] = &xw[i];
   // what crosses the stages, for all samples
-  float *t_emb_all = F((size_t)B * td), *d_temb_all = F((size_t)B * td), *vt_all = F((size_t)B * vd), *pre_f_all = F((size_t)B * FT);
-  half_t* gath_all = H16((size_t)B * vox[0] * 64);
-  float* d_gath_all = F((size_t)B * vox[0] * 64);
-  float *feats_all = F((size_t)B * rows * 16), *d_feats_all = F((size_t)B * rows * 16);
-  WS_CHECK(t_emb_all && d_temb_all && vt_all && pre_f_all && gath_all && d_gath_all && feats_all && d_feats_all);
-  if (!det) HIP_CHECK_RET(hipMemsetAsync(d_feats_all, 0, (size_t)B * rows * 16 * sizeof(float), s));
-  HIP_CHECK_RET(hipMemsetAsync(d_temb_all, 0, (size_t)B * td * sizeof(float), s));
-  std::vector<CondSample> st(B);
+  q.t_emb_all = q.F((size_t)B * td), q.d_temb_all = q.F((size_t)B * td), q.vt_all = q.F((size_t)B * vd), q.pre_f_all = q.F((size_t)B * q.FT);
+  q.gath_all = q.H16((size_t)B * q.geo.vox[0] * 64);
+  q.d_gath_all = q.F((size_t)B * q.geo.vox[0] * 64);
+  q.feats_all = q.F((size_t)B * rows * 16), q.d_feats_all = q.F((size_t)B * rows * 16);
+  WS_CHECK(q.t_emb_all && q.d_temb_all && q.vt_all && q.pre_f_all && q.gath_all && q.d_gath_all && q.feats_all && q.d_feats_all);
+  if (!q.det) HIP_CHECK_RET(hipMemsetAsync(q.d_feats_all, 0, (size_t)B * rows * 16 * sizeof(float), s));
+  HIP_CHECK_RET(hipMemsetAsync(q.d_temb_all, 0, (size_t)B * td * sizeof(float), s));
+  q.st.resize(B);
 
-  // ---------------- stage 0, all samples at once: step embedding MLP and the 2-D encoder (B * N views as its batch) ----------------
+  // ---- stage 0, all samples at once: step embedding MLP and the 2-D encoder (B * N views as its batch) ----
   // step embedding (morphable_diffusion.py:491-494): t_emb = W2 silu(W0 temb(t) + b0) + b2
-  const int BN = B * N;
-  const size_t rows_all = (size_t)BN * HW;
   int64_t* t_dev = (int64_t*)c->ws.alloc(sizeof(int64_t) * B);
-  float *e0 = F((size_t)B * td), *u1 = F((size_t)B * td), *e1 = F((size_t)B * td);
-  WS_CHECK(t_dev && e0 && u1 && e1);
+  q.e0 = q.F((size_t)B * td), q.u1 = q.F((size_t)B * td), q.e1 = q.F((size_t)B * td);
+  WS_CHECK(t_dev && q.e0 && q.u1 && q.e1);
   for (int bi = 0; bi < B; ++bi) hipLaunchKernelGGL(set_i64_kernel, dim3(1), dim3(1), 0, s, t_dev + bi, timesteps[bi]);
   HIP_CHECK_RET(hipGetLastError());
-  RET_IF(launch_timestep_embedding(t_dev, B, td, e0, s));
-  RET_IF(launch_small_linear(e0, td, B, td, c->step_te0.w, c->step_te0.bias, td, ACT_NONE, u1, td, 0, s));
-  RET_IF(bwd_silu_fwd(u1, e1, (size_t)B * td, s));
-  RET_IF(launch_small_linear(e1, td, B, td, c->step_te2.w, c->step_te2.bias, td, ACT_NONE, t_emb_all, td, 0, s));
+  RET_IF(launch_timestep_embedding(t_dev, B, td, q.e0, s));
+  RET_IF(launch_small_linear(q.e0, td, B, td, c->step_te0.w, c->step_te0.bias, td, ACT_NONE, q.u1, td, 0, s));
+  RET_IF(bwd_silu_fwd(q.u1, q.e1, (size_t)B * td, s));
+  RET_IF(launch_small_linear(q.e1, td, B, td, c->step_te2.w, c->step_te2.bias, td, ACT_NONE, q.t_emb_all, td, 0, s));
   // 2-D encoder (NoisyTargetViewEncoder, network.py:181-207), layer by layer and in EXTENDED precision (hi/lo operand split on
-  // packs made here from the master weights; 16 channels: the cost is nothing): the sparse CNN behind it has nine BatchNorm +
+  // packs made from the master weights; 16 channels: the cost is nothing): the sparse CNN behind it has nine BatchNorm +
   // ReLU layers whose masks are re-derived from these features -- an fp16-rounded encoder moves the gradients upstream of them
-  // by 4-10e-2 (measured), the extended-precision one by 1e-3.  No split-K: a view's features do not depend on the batch.
-  float *x8 = F(rows_all * 8), *pre_e = F((size_t)BN * 48);
-  float* cur_e[4];
-  float* r1_e[3];
-  half_t *a1_e[3], *a2_e[3], *af = H16(rows_all * 48), *x8s = H16(rows_all * 24);
-  for (int i = 0; i < 4; ++i) cur_e[i] = F(rows_all * 16);
+  // by 4-10e-2 (measured), the extended-precision one by 1e-3.
+  EncBufs& e = q.enc;
+  q.x8 = q.F(rows_all * 8), q.pre_e = q.F((size_t)BN * 48);
+  e.af = q.H16(rows_all * 48);
+  half_t* x8s = q.H16(rows_all * 24);
+  for (int i = 0; i < 4; ++i) e.cur[i] = q.F(rows_all * 16);
   for (int i = 0; i < 3; ++i) {
-    r1_e[i] = F(rows_all * 16);
-    a1_e[i] = H16(rows_all * 48);
-    a2_e[i] = H16(rows_all * 48);
-    WS_CHECK(r1_e[i] && a1_e[i] && a2_e[i]);
+    e.r1[i] = q.F(rows_all * 16);
+    e.a1[i] = q.H16(rows_all * 48);
+    e.a2[i] = q.H16(rows_all * 48);
+    WS_CHECK(e.r1[i] && e.a1[i] && e.a2[i]);
   }
-  WS_CHECK(x8 && pre_e && af && x8s && cur_e[0] && cur_e[1] && cur_e[2] && cur_e[3]);
+  WS_CHECK(q.x8 && q.pre_e && e.af && x8s && e.cur[0] && e.cur[1] && e.cur[2] && e.cur[3]);
   for (int bi = 0; bi < B; ++bi)  // pre[b, v] = time_embed_i(t_emb[b]) + view_embed_i(v_embed[b, v]), the three blocks side by side
-    RET_IF(launch_small_linear(t_emb_all + (size_t)bi * td, td, -N, td, c->enc_t.w, c->enc_t.bias, 48, ACT_NONE, pre_e + (size_t)bi * N * 48, 48, 0, s));
-  RET_IF(launch_small_linear(v_embed_all, vd, BN, vd, c->enc_v.w, c->enc_v.bias, 48, ACT_NONE, pre_e, 48, 1, s));
-  RET_IF(launch_nchw_to_nhwc(x_noisy_all, BN, 4, HW, x8, 8, 8, s));
-  RET_IF(launch_rows_f32_to_f16_split(x8, 8, (long)rows_all, 8, x8s, s));
-  {
-    GemmArgs g;
-    g.a = x8s; g.lda = 24; g.w = &x_init; g.out = cur_e[0]; g.ldc = 16; g.force_splitk = 1;
-    RET_IF(run_conv2d(c, g, BN, S, S, 1, 0, s));
-    for (int i = 0; i < 3; ++i) {
-      const EncBlockW& e = c->enc_blocks[i];
-      RET_IF(run_group_norm(c, cur_e[i], 16, BN, HW, e.n1, 8, 1e-5f, ACT_SILU, pre_e + 16 * i, a1_e[i], 48, s, 48, 1));
-      g = GemmArgs();
-      g.a = a1_e[i]; g.lda = 48; g.w = &x_c1[i]; g.out = r1_e[i]; g.ldc = 16; g.force_splitk = 1;
-      RET_IF(run_conv2d(c, g, BN, S, S, 1, 0, s));
-      RET_IF(run_group_norm(c, r1_e[i], 16, BN, HW, e.n2, 8, 1e-5f, ACT_SILU, nullptr, a2_e[i], 48, s, 0, 1));
-      g = GemmArgs();
-      g.a = a2_e[i]; g.lda = 48; g.w = &x_c2[i]; g.out = cur_e[i + 1]; g.ldc = 16; g.resid = cur_e[i]; g.ldr = 16; g.force_splitk = 1;
-      RET_IF(run_conv2d(c, g, BN, S, S, 1, 0, s));
-    }
-    RET_IF(run_group_norm(c, cur_e[3], 16, BN, HW, c->enc_final_norm, 8, 1e-5f, ACT_SILU, nullptr, af, 48, s, 0, 1));
-    g = GemmArgs();
-    g.a = af; g.lda = 48; g.w = &x_final; g.out = feats_all; g.ldc = 16; g.force_splitk = 1;
-    RET_IF(run_conv2d(c, g, BN, S, S, 1, 0, s));
-  }
-  mark("fwd: step mlp + 2-D encoder");
+    RET_IF(launch_small_linear(q.t_emb_all + (size_t)bi * td, td, -N, td, c->enc_t.w, c->enc_t.bias, 48, ACT_NONE,
+                               q.pre_e + (size_t)bi * N * 48, 48, 0, s));
+  RET_IF(launch_small_linear(q.v_embed_all, vd, BN, vd, c->enc_v.w, c->enc_v.bias, 48, ACT_NONE, q.pre_e, 48, 1, s));
+  RET_IF(launch_nchw_to_nhwc(x_noisy_all, BN, 4, q.HW, q.x8, 8, 8, s));
+  RET_IF(launch_rows_f32_to_f16_split(q.x8, 8, (long)rows_all, 8, x8s, s));
+  RET_IF(engine_encoder_layers(c, xwp, true, x8s, BN, q.pre_e, e, q.feats_all, s));
+  q.mark("fwd: step mlp + 2-D encoder");
 
-  // ---------------- stage 1, per sample: forward up to the gathered frustum features ----------------
-  auto stage1 = [&](int bi) -> int {
-  if (!c->mesh.Nv || !c->cams) return mvd_fail("mvd_set_mesh / mvd_set_cameras must be called first");
-  MeshTables& m = c->mesh;
-  const int Nv = m.Nv;
-  const float* v_embed = v_embed_all + (size_t)bi * N * vd;
-  int* vidx = (int*)c->ws.alloc(sizeof(int) * (N + 1));
-  WS_CHECK(vidx);
-  hipLaunchKernelGGL(iota_kernel, dim3(1), dim3(64), 0, s, vidx, N, 0);
-  hipLaunchKernelGGL(iota_kernel, dim3(1), dim3(64), 0, s, vidx + N, 1, target_idx[bi]);
-  HIP_CHECK_RET(hipGetLastError());
-  const float *t_emb = t_emb_all + (size_t)bi * td, *feats = feats_all + (size_t)bi * rows * 16;
-  // vertex features, view fusion
-  float *vf = F((size_t)N * Nv * 16), *fused = F((size_t)Nv * 16);
-  WS_CHECK(vf && fused);
-  RET_IF(launch_vertex_gather(feats, c->cams, vidx, N, m.verts, Nv, V, c->v.spatial_volume_length, S, persp, vf, s));
-  RET_IF(launch_fuse_views(vf, N, Nv, N, c->fuse_w, c->fuse_b, fused, 0, s));
-  // sparse voxel CNN, train mode: raw conv output and post-activation rows of every layer
-  const float* sp_in[9];
-  float *sp_raw[9], *sp_post[9], *sp_stats[9];  // raw conv output, post-activation rows, BatchNorm [mean | rstd]
-  const int* sp_nbr[9];
-  int sp_nout[9], sp_nin[9];
-  {
-    const float* in = fused;
-    int lvl = 0, n_in = Nv;
-    for (int i = 0; i < 9; ++i) {
-      const SparseLayerW& L = c->sparse[i];
-      if (L.strided) {
-        sp_nbr[i] = m.nbr_down[lvl];
-        ++lvl;
-      } else {
-        sp_nbr[i] = m.nbr_subm[lvl];
-      }
-      sp_nout[i] = m.n_sites[lvl];
-      sp_nin[i] = n_in;
-      sp_in[i] = in;
-      sp_raw[i] = F((size_t)sp_nout[i] * L.cout);
-      sp_post[i] = F((size_t)sp_nout[i] * L.cout);
-      WS_CHECK(sp_raw[i] && sp_post[i]);
-      sp_stats[i] = F((size_t)2 * L.cout);
-      WS_CHECK(sp_stats[i]);
-      RET_IF(launch_sparse_conv(in, sp_nbr[i], sp_nout[i], L.cin, L.cout, L.w, L.wp, nullptr, nullptr, sp_raw[i], s));
-      RET_IF(launch_bn_rows_relu(sp_raw[i], sp_post[i], sp_nout[i], L.cout, L.gamma, L.beta, 1e-3f, sp_stats[i], s));
-      in = sp_post[i];
-      n_in = sp_nout[i];
-    }
-  }
-  mark("fwd: gather, fuse, sparse net");
-  float* volume = F((size_t)V * V * V * 64);
-  WS_CHECK(volume);
-  RET_IF(launch_latent_gather(sp_post[8], m.grid2, m.shape[2][0], m.shape[2][1], m.shape[2][2], m.min_xyz, m.out_sh, c->v.voxel_size, V,
-                              c->v.spatial_volume_length, volume, s));
-  RET_IF(launch_frustum_gather(volume, c->cams, vidx + N, 1, Dl[0], Sl[0], V, c->v.spatial_volume_length, persp,
-                               gath_all + (size_t)bi * vox[0] * 64, s));
-  float* pre_row = pre_f_all + (size_t)bi * FT;
-  RET_IF(launch_small_linear(t_emb, td, 1, td, c->film_t.w, c->film_t.bias, FT, ACT_NONE, pre_row, FT, 0, s));
-  RET_IF(launch_small_linear(v_embed + (size_t)target_idx[bi] * vd, vd, 1, vd, c->film_v.w, c->film_v.bias, FT, ACT_NONE, pre_row, FT, 1, s));
-  HIP_CHECK_RET(hipMemcpyAsync(vt_all + (size_t)bi * vd, v_embed + (size_t)target_idx[bi] * vd, vd * sizeof(float), hipMemcpyDeviceToDevice, s));
-  CondSample& P = st[bi];
-  P.vidx = vidx, P.vf = vf;
-  for (int i = 0; i < 9; ++i)
-    P.sp_in[i] = sp_in[i], P.sp_raw[i] = sp_raw[i], P.sp_post[i] = sp_post[i], P.sp_stats[i] = sp_stats[i], P.sp_nbr[i] = sp_nbr[i],
-    P.sp_nout[i] = sp_nout[i], P.sp_nin[i] = sp_nin[i];
-  return 0;
-  };
   for (int bi = 0; bi < B; ++bi) {
     RET_IF(engine_select_sample(c, slots[bi]));
-    RET_IF(stage1(bi));
+    RET_IF(cond_fwd_sample(q, bi));
   }
-
-  // ---------------- stage 2: FrustumTV3DNet forward + backward, the samples as its batch (chunks of at most 16: 32-bit operand
-  // offsets of the level-0 weight-gradient GEMM) ----------------
-  for (int b0 = 0; b0 < B; b0 += 16) {
-  const size_t Bc = (size_t)std::min(16, B - b0);
-  WsScope chunk_scope(c, WS_BLOCK);
-  half_t* gath = gath_all + (size_t)b0 * vox[0] * 64;
-  float* pre_f = pre_f_all + (size_t)b0 * FT;
-  GemmArgs g;
-  float *xd[4], *xf[4], *tmp_f[3];
-  half_t *a1_f[3], *a2_f[3], *au_f[3];
-  for (int l = 0; l < 4; ++l) {
-    xd[l] = F(Bc * vox[l] * fd[l]);
-    xf[l] = F(Bc * vox[l] * fd[l]);
-    WS_CHECK(xd[l] && xf[l]);
-  }
-  for (int l = 0; l < 3; ++l) {
-    tmp_f[l] = F(Bc * vox[l + 1] * fd[l + 1]);
-    a1_f[l] = H16(Bc * vox[l] * fd[l]);
-    a2_f[l] = H16(Bc * vox[l + 1] * fd[l + 1]);
-    au_f[l] = H16(Bc * vox[l + 1] * fd[l + 1]);
-    WS_CHECK(tmp_f[l] && a1_f[l] && a2_f[l] && au_f[l]);
-  }
-  g = GemmArgs();
-  g.a = gath; g.lda = 64; g.w = &c->fr_conv0; g.out = xd[0]; g.ldc = fd[0];
-  RET_IF(run_conv3d(c, g, (int)Bc, Dl[0], Sl[0], Sl[0], 1, s));
-  for (int l = 0; l < 3; ++l) {
-    const FrustumBlockW& b1 = c->fr_blocks[2 * l];
-    const FrustumBlockW& b2 = c->fr_blocks[2 * l + 1];
-    RET_IF(run_group_norm(c, xd[l], fd[l], (int)Bc, (int)vox[l], b1.gn, 8, 1e-5f, ACT_SILU, pre_f + c->film_off[2 * l], a1_f[l], fd[l], s, FT));
-    g = GemmArgs();
-    g.a = a1_f[l]; g.lda = fd[l]; g.w = &b1.conv; g.out = tmp_f[l]; g.ldc = fd[l + 1];
-    RET_IF(run_conv3d(c, g, (int)Bc, Dl[l], Sl[l], Sl[l], 2, s));
-    RET_IF(run_group_norm(c, tmp_f[l], fd[l + 1], (int)Bc, (int)vox[l + 1], b2.gn, 8, 1e-5f, ACT_SILU, pre_f + c->film_off[2 * l + 1], a2_f[l],
-                          fd[l + 1], s, FT));
-    g = GemmArgs();
-    g.a = a2_f[l]; g.lda = fd[l + 1]; g.w = &b2.conv; g.out = xd[l + 1]; g.ldc = fd[l + 1];
-    RET_IF(run_conv3d(c, g, (int)Bc, Dl[l + 1], Sl[l + 1], Sl[l + 1], 1, s));
-  }
-  HIP_CHECK_RET(hipMemcpyAsync(xf[3], xd[3], Bc * vox[3] * fd[3] * sizeof(float), hipMemcpyDeviceToDevice, s));
-  for (int l = 2; l >= 0; --l) {
-    const FrustumBlockW& u = c->fr_up[2 - l];
-    RET_IF(run_group_norm(c, xf[l + 1], fd[l + 1], (int)Bc, (int)vox[l + 1], u.gn, 8, 1e-5f, ACT_SILU, pre_f + c->film_off[6 + (2 - l)], au_f[l],
-                          fd[l + 1], s, FT));
-    g = GemmArgs();
-    g.a = au_f[l]; g.lda = fd[l + 1]; g.w = &u.conv; g.out = xf[l]; g.ldc = fd[l]; g.resid = xd[l]; g.ldr = fd[l];
-    RET_IF(run_convT3d(c, g, (int)Bc, Dl[l + 1], Sl[l + 1], Sl[l + 1], s));
-  }
-  mark("fwd: frustum net");
-  Fwd f{c, s, (int)Bc, (int)Bc, 0, nullptr, nullptr, nullptr, nullptr, {nullptr, nullptr, nullptr, nullptr}};
-  TrainTape tape;
-  Bwd b{c, s, (int)Bc, &f, &tape};
-  float* d_pre_f = F(Bc * FT);
-  WS_CHECK(d_pre_f);
-  HIP_CHECK_RET(hipMemsetAsync(d_pre_f, 0, Bc * FT * sizeof(float), s));
-  half_t* dy16;
-  float* gl[4];
-  for (int l = 0; l < 4; ++l) gl[l] = dsrc[l] + (size_t)b0 * vox[l] * fd[l];  // dL/d x_l, accumulated in place
-  // up path (forward order l = 2, 1, 0): x_l = xd_l + convT(silu(GN(xf_{l+1} + film)))
-  for (int l = 0; l <= 2; ++l) {
-    WsScope sc(c, WS_BLOCK);
-    const FrustumBlockW& u = c->fr_up[2 - l];
-    float* d_au = F(Bc * vox[l + 1] * fd[l + 1]);
-    WS_CHECK(d_au);
-    RET_IF(grad16(c, gl[l], fd[l], (long)(Bc * vox[l]), fd[l], &dy16, s));
-    RET_IF(dgrad_conv3d(b, u.conv, 2, dy16, d_au, fd[l + 1], Dl[l], Sl[l], Sl[l], false));
-    RET_IF(wgrad_convT3d(b, u.conv, gl[l], fd[l], au_f[l], 0, fd[l + 1], Dl[l + 1], Sl[l + 1], Sl[l + 1]));
-    RET_IF(gn_backward(b, u.gn, 8, 1e-5f, ACT_SILU, xf[l + 1], fd[l + 1], d_au, fd[l + 1], (int)vox[l + 1], gl[l + 1], fd[l + 1], true,
-                       pre_f + c->film_off[6 + (2 - l)], FT, d_pre_f + c->film_off[6 + (2 - l)], FT));
-  }
-  mark("bwd: frustum up path");
-  // down path (forward order l = 0, 1, 2)
-  for (int l = 2; l >= 0; --l) {
-    WsScope sc(c, WS_BLOCK);
-    const FrustumBlockW& b1 = c->fr_blocks[2 * l];
-    const FrustumBlockW& b2 = c->fr_blocks[2 * l + 1];
-    float *d_a2 = F(Bc * vox[l + 1] * fd[l + 1]), *d_tmp = F(Bc * vox[l + 1] * fd[l + 1]), *d_a1 = F(Bc * vox[l] * fd[l]);
-    WS_CHECK(d_a2 && d_tmp && d_a1);
-    RET_IF(grad16(c, gl[l + 1], fd[l + 1], (long)(Bc * vox[l + 1]), fd[l + 1], &dy16, s));
-    RET_IF(dgrad_conv3d(b, b2.conv, 0, dy16, d_a2, fd[l + 1], Dl[l + 1], Sl[l + 1], Sl[l + 1], false));
-    RET_IF(wgrad_conv3d(b, b2.conv, gl[l + 1], fd[l + 1], a2_f[l], 0, fd[l + 1], Dl[l + 1], Sl[l + 1], Sl[l + 1], fd[l + 1], 1));
-    RET_IF(gn_backward(b, b2.gn, 8, 1e-5f, ACT_SILU, tmp_f[l], fd[l + 1], d_a2, fd[l + 1], (int)vox[l + 1], d_tmp, fd[l + 1], false,
-                       pre_f + c->film_off[2 * l + 1], FT, d_pre_f + c->film_off[2 * l + 1], FT));
-    RET_IF(grad16(c, d_tmp, fd[l + 1], (long)(Bc * vox[l + 1]), fd[l + 1], &dy16, s));
-    RET_IF(dgrad_conv3d(b, b1.conv, 1, dy16, d_a1, fd[l], Dl[l + 1], Sl[l + 1], Sl[l + 1], false));
-    RET_IF(wgrad_conv3d(b, b1.conv, d_tmp, fd[l + 1], a1_f[l], 0, fd[l], Dl[l], Sl[l], Sl[l], fd[l], 2));
-    RET_IF(gn_backward(b, b1.gn, 8, 1e-5f, ACT_SILU, xd[l], fd[l], d_a1, fd[l], (int)vox[l], gl[l], fd[l], true,
-                       pre_f + c->film_off[2 * l], FT, d_pre_f + c->film_off[2 * l], FT));
-  }
-  mark("bwd: frustum down path");
-  // conv0 on the gathered frustum features
-  float* d_gath = d_gath_all + (size_t)b0 * vox[0] * 64;
-  RET_IF(grad16(c, gl[0], fd[0], (long)(Bc * vox[0]), fd[0], &dy16, s));
-  RET_IF(dgrad_conv3d(b, c->fr_conv0, 0, dy16, d_gath, 64, Dl[0], Sl[0], Sl[0], false));
-  RET_IF(wgrad_conv3d(b, c->fr_conv0, gl[0], fd[0], gath, 0, 64, Dl[0], Sl[0], Sl[0], 64, 1));
-  // FiLM projections of the nine frustum blocks: film = t_conv(t_emb) + v_conv(v_embed[target])
-  for (int i = 0; i < 9; ++i) {
-    const FrustumBlockW& fb = i < 6 ? c->fr_blocks[i] : c->fr_up[i - 6];
-    const float* dp = d_pre_f + c->film_off[i];
-    RET_IF(lin_wgrad(c, fb.t_conv.key, dp, FT, t_emb_all + (size_t)b0 * td, td, (int)Bc, fb.cin, td, s));
-    RET_IF(lin_wgrad(c, fb.v_conv.key, dp, FT, vt_all + (size_t)b0 * vd, vd, (int)Bc, fb.cin, vd, s));
-  }
-  RET_IF(cbwd_small_linear_bwd(d_pre_f, FT, (int)Bc, FT, c->film_t.w, td, d_temb_all + (size_t)b0 * td, td, 1, s));
-  mark("bwd: frustum net, conv0 + FiLM");
-  }
-
-  // ---------------- stage 3, per sample: scatters, sparse CNN, view fusion, 2-D encoder, step MLP ----------------
-  auto stage3 = [&](int bi) -> int {
-  WsScope sample_scope(c, WS_BLOCK);
-  MeshTables& m = c->mesh;
-  const int Nv = m.Nv;
-  CondSample& P = st[bi];
-  int* vidx = P.vidx;
-  float* vf = P.vf;
-  const float** sp_in = P.sp_in;
-  float **sp_raw = P.sp_raw, **sp_stats = P.sp_stats;
-  const int** sp_nbr = P.sp_nbr;
-  int *sp_nout = P.sp_nout, *sp_nin = P.sp_nin;
-  // frustum gather, latent-code gather: scatter adjoints
-  float* d_vol = F((size_t)V * V * V * 64);
-  float* d_cur = F((size_t)sp_nout[8] * 64);
-  WS_CHECK(d_vol && d_cur);
-  if (!det) {
-    HIP_CHECK_RET(hipMemsetAsync(d_vol, 0, (size_t)V * V * V * 64 * sizeof(float), s));
-    HIP_CHECK_RET(hipMemsetAsync(d_cur, 0, (size_t)sp_nout[8] * 64 * sizeof(float), s));
-  }
-  RET_IF(adj_frustum(c, det, d_gath_all + (size_t)bi * vox[0] * 64, vidx + N, 1, Dl[0], Sl[0], d_vol, s));
-  if (dbg_dvolume) RET_IF(launch_nhwc_to_nchw(d_vol, 64, 1, 64, V * V * V, dbg_dvolume, s));
-  RET_IF(adj_latent(c, det, d_vol, d_cur, s));
-  mark("bwd: scatters");
-  // sparse voxel CNN
-  for (int i = 8; i >= 0; --i) {
-    const SparseLayerW& L = c->sparse[i];
-    float* Gg = engine_grad(c, L.bnkey + ".weight");
-    float* Gb = engine_grad(c, L.bnkey + ".bias");
-    float* Gw = engine_grad(c, L.wkey);
-    if (!Gg || !Gb || !Gw) return mvd_fail("conditioner backward: sparse layer parameters missing from the arena");
-    {
-      WsScope sc(c, WS_TEMP);
-      float* bn_scr = F((size_t)cbwd_bn_scratch_floats(sp_nout[i], L.cout));
-      WS_CHECK(bn_scr);
-      RET_IF(cbwd_bn_rows_relu(sp_raw[i], d_cur, sp_nout[i], L.cout, L.gamma, L.beta, sp_stats[i], bn_scr, Gg, Gb, s));
-    }
-    float* dwp = F((size_t)27 * L.cin * L.cout);
-    float* d_in = F((size_t)sp_nin[i] * L.cin);
-    WS_CHECK(dwp && d_in);
-    if (L.wp && L.wd) {
-      // matrix-core form (k_cond.hip / k_cond_bwd.hip): gather-form data gradient through the layer's own table with the tap
-      // flipped (submanifold) or through the inverse table (strided) -- no atomics, no zero fill.  At level 0 the gradients of
-      // duplicate vertices' rows are folded into their representatives' first (the table is symmetric over those only).
-      const bool lvl0_subm = !L.strided && sp_nbr[i] == m.nbr_subm[0];
-      if (lvl0_subm && !det) RET_IF(cbwd_sparse_fold_dups(d_cur, sp_nbr[i], sp_nout[i], L.cout, s));
-      if (lvl0_subm && det) {  // the same fold with the duplicates' rows added in row order
-        WsScope sc(c, WS_TEMP);
-        int* flag = (int*)F((size_t)sp_nout[i]);
-        WS_CHECK(flag);
-        RET_IF(cbwd_sparse_fold_dups_det(d_cur, sp_nbr[i], sp_nout[i], L.cout, flag, s));
-      }
-      {
-        WsScope sc(c, WS_TEMP);
-        float* dw_part = F((size_t)cbwd_sparse_wgrad_chunks(sp_nout[i]) * 27 * L.cin * L.cout);
-        WS_CHECK(dw_part);
-        RET_IF(cbwd_sparse_wgrad_mfma(sp_in[i], sp_nbr[i], d_cur, sp_nout[i], L.cin, L.cout, dwp, dw_part, s));
-      }
-      const int* table = sp_nbr[i];
-      WsScope sc(c, WS_TEMP);
-      if (L.strided) {
-        int* inv = (int*)F((size_t)sp_nin[i] * 27);
-        WS_CHECK(inv);
-        RET_IF(cbwd_sparse_inverse_table(sp_nbr[i], sp_nout[i], sp_nin[i], inv, s));
-        table = inv;
-      }
-      RET_IF(launch_sparse_conv(d_cur, table, sp_nin[i], L.cout, L.cin, nullptr, L.wd, nullptr, nullptr, d_in, s, lvl0_subm ? 1 : 0));
-    } else {
-      if (det) return mvd_fail("deterministic mode: this sparse layer has no matrix-core form (its site-form data gradient adds with "
-                               "fp32 atomics); unset MVD_SPARSE_VALU");
-      HIP_CHECK_RET(hipMemsetAsync(d_in, 0, (size_t)sp_nin[i] * L.cin * sizeof(float), s));
-      WsScope sc(c, WS_TEMP);
-      float* dw_part = F((size_t)cbwd_sparse_wgrad_chunks(sp_nout[i]) * 27 * L.cin * L.cout);
-      WS_CHECK(dw_part);
-      RET_IF(cbwd_sparse_conv(sp_in[i], sp_nbr[i], d_cur, sp_nout[i], L.cin, L.cout, L.w, d_in, dwp, dw_part, s));
-    }
-    RET_IF(cbwd_sparse_w_unpack_add(dwp, L.cin, L.cout, L.layout, Gw, s));
-    d_cur = d_in;
-  }
-  mark("bwd: sparse net");
-  float* d_fused = d_cur;  // [Nv][16]
-  if (dbg_dfused) HIP_CHECK_RET(hipMemcpyAsync(dbg_dfused, d_fused, (size_t)Nv * 16 * sizeof(float), hipMemcpyDeviceToDevice, s));
-  // view fusion, vertex gather
-  float *d_vf = F((size_t)N * Nv * 16), *d_feats = d_feats_all + (size_t)bi * rows * 16;
-  float* fuse_part = F((size_t)cbwd_fuse_scratch_floats(Nv));
-  WS_CHECK(d_vf && fuse_part);
-  RET_IF(cbwd_fuse(d_fused, vf, c->fuse_w, N, Nv, N, d_vf, engine_grad(c, SV + "smpl_feature_extractor.conv0.weight"),
-                   engine_grad(c, SV + "smpl_feature_extractor.conv0.bias"), fuse_part, s));
-  RET_IF(adj_vertex(c, det, d_vf, vidx, N, d_feats, s));
-  if (dbg_dfeats) RET_IF(launch_nhwc_to_nchw(d_feats, 16, N, 16, HW, dbg_dfeats, s));
-  mark("bwd: fuse + vertex scatter");
-  return 0;
-  };
+  for (int b0 = 0; b0 < B; b0 += 16) RET_IF(cond_frustum_chunk(q, b0, (size_t)std::min(16, B - b0)));
   for (int bi = 0; bi < B; ++bi) {
     RET_IF(engine_select_sample(c, slots[bi]));
-    RET_IF(stage3(bi));
+    RET_IF(cond_bwd_sample(q, bi));
   }
-
-  // ---------------- stage 4, all samples at once: 2-D encoder backward (B * N views as its batch), FiLM projections, step MLP ----------------
-  {
-  Fwd f{c, s, BN, BN, 0, nullptr, nullptr, nullptr, nullptr, {nullptr, nullptr, nullptr, nullptr}};
-  TrainTape tape;
-  Bwd b{c, s, BN, &f, &tape};
-  half_t* dy16;
-  float *d_a = F(rows_all * 16), *d_r = F(rows_all * 16), *d_x = F(rows_all * 16), *d_nxt = F(rows_all * 16);
-  float* d_pre_e = F((size_t)BN * 48);
-  WS_CHECK(d_a && d_r && d_x && d_nxt && d_pre_e);
-  RET_IF(grad16(c, d_feats_all, 16, (long)rows_all, 16, &dy16, s));
-  RET_IF(dgrad_conv3(b, c->enc_final, dy16, d_a, 16, S, S, false));
-  RET_IF(wgrad_conv3(b, c->enc_final, d_feats_all, 16, af, 0, 48, S, S, 16, 1, 0));
-  RET_IF(gn_backward(b, c->enc_final_norm, 8, 1e-5f, ACT_SILU, cur_e[3], 16, d_a, 16, HW, d_nxt, 16, false));
-  for (int i = 2; i >= 0; --i) {
-    const EncBlockW& e = c->enc_blocks[i];
-    RET_IF(grad16(c, d_nxt, 16, (long)rows_all, 16, &dy16, s));
-    RET_IF(dgrad_conv3(b, e.c2, dy16, d_a, 16, S, S, false));
-    RET_IF(wgrad_conv3(b, e.c2, d_nxt, 16, a2_e[i], 0, 48, S, S, 16, 1, 0));
-    RET_IF(gn_backward(b, e.n2, 8, 1e-5f, ACT_SILU, r1_e[i], 16, d_a, 16, HW, d_r, 16, false));
-    RET_IF(grad16(c, d_r, 16, (long)rows_all, 16, &dy16, s));
-    RET_IF(dgrad_conv3(b, e.c1, dy16, d_a, 16, S, S, false));
-    RET_IF(wgrad_conv3(b, e.c1, d_r, 16, a1_e[i], 0, 48, S, S, 16, 1, 0));
-    RET_IF(gn_backward(b, e.n1, 8, 1e-5f, ACT_SILU, cur_e[i], 16, d_a, 16, HW, d_x, 16, false, pre_e + 16 * i, 48, d_pre_e + 16 * i, 48));
-    RET_IF(bwd_add_views(d_x, 16, d_nxt, 16, nullptr, 0, (long)rows_all, 16, 1, s));  // + the residual branch
-    std::swap(d_x, d_nxt);
-  }
-  RET_IF(wgrad_conv3(b, c->enc_init, d_nxt, 16, x8, 1, 8, S, S, 4, 1, 0));  // 4 latent channels (the pack pads them to 8)
-  {  // FiLM of the three encoder blocks: pre[b, v] = time_embed_i(t_emb[b]) + view_embed_i(v_embed[b, v])
-    float* dsum = F((size_t)B * 48);
-    WS_CHECK(dsum);
-    RET_IF(bwd_colsum_samples(d_pre_e, 1, 48, B, N, 48, dsum, 48, s));  // per sample: its N views
-    for (int i = 0; i < 3; ++i) {
-      const EncBlockW& e = c->enc_blocks[i];
-      RET_IF(lin_wgrad(c, e.t.key, dsum + 16 * i, 48, t_emb_all, td, B, 16, td, s));
-      RET_IF(lin_wgrad(c, e.v.key, d_pre_e + 16 * i, 48, v_embed_all, vd, BN, 16, vd, s));
-    }
-    RET_IF(cbwd_small_linear_bwd(dsum, 48, B, 48, c->enc_t.w, td, d_temb_all, td, 1, s));
-  }
-  mark("bwd: 2-D encoder + FiLM");
-  if (dbg_dtembed) HIP_CHECK_RET(hipMemcpyAsync(dbg_dtembed, d_temb_all, td * sizeof(float), hipMemcpyDeviceToDevice, s));
-  // step MLP
-  RET_IF(lin_wgrad(c, c->step_te2.key, d_temb_all, td, e1, td, B, td, td, s));
-  float* d_e1 = F((size_t)B * td);
-  WS_CHECK(d_e1);
-  RET_IF(cbwd_small_linear_bwd(d_temb_all, td, B, td, c->step_te2.w, td, d_e1, td, 0, s));
-  RET_IF(bwd_silu_inplace(d_e1, u1, (size_t)B * td, s));
-  RET_IF(lin_wgrad(c, c->step_te0.key, d_e1, td, e0, td, B, td, td, s));
-  }
-  return 0;
+  return cond_bwd_head(q);
 }
 
 // one sample: the active slot (parity hook with the debug outputs; dsrc as above with B = 1)
