@@ -343,6 +343,16 @@ int mvd_op_latent_adjoint(mvd_ctx* ctx, const float* d_vol, int deterministic, f
 int mvd_op_vertex_adjoint(mvd_ctx* ctx, const float* d_vf, const int32_t* view_idx, int n_views, int deterministic, float* d_feats,
                           void* stream);
 int mvd_probe_adjoint_calls(mvd_ctx* ctx, int64_t* out);
+/* Parity hooks for the forward gathers those adjoints belong to: ONE production launch of the vertex / lattice / frustum gather on
+ * device buffers of the caller, with the cameras and the mesh of the active slot (any finalized context).  Channels-last fp32:
+ *   mvd_op_vertex_gather    feats [n_views,s,s,16] (the layout mvd_op_vertex_adjoint writes), view_idx [n_views] HOST ->
+ *                           vf_out [n_views,Nv,16];
+ *   mvd_op_latent_gather    rows [n_rows,64] in the order of mvd_rulebook_table(5) -> vol_out [V,V,V,64];
+ *   mvd_op_frustum_gather   vol [V,V,V,64], view_idx [TN] HOST -> out [TN,D,S,S,64]: the values exactly as the kernel stored them
+ *                           in the operand type (mvd_compute_dtype), widened to fp32. */
+int mvd_op_vertex_gather(mvd_ctx* ctx, const float* feats, const int32_t* view_idx, int n_views, float* vf_out, void* stream);
+int mvd_op_latent_gather(mvd_ctx* ctx, const float* rows, float* vol_out, void* stream);
+int mvd_op_frustum_gather(mvd_ctx* ctx, const float* vol, const int32_t* view_idx, int TN, int D, int S, float* out, void* stream);
 /* Parity hook: the backward pass of ONE DepthTransformer (attention.py:49-84; cond_index 0 = middle_conditions, 1 + k =
  * output_conditions.k) given its input x [B,dim,H,W], its context volume [B,C_l,D_l,H,W] and dL/d(output) [B,dim,H,W]:
  * dx, dcontext (may be NULL) are written, parameter gradients accumulated into the arena.  depth0 = D of the finest level. */

@@ -1833,3 +1833,40 @@ int mvd_op_vertex_adjoint(mvd_ctx* c, const float* d_vf, const int32_t* view_idx
   if (!deterministic) HIP_CHECK_RET(hipMemsetAsync(d_feats, 0, (size_t)n_views * S * S * 16 * sizeof(float), s));
   return adj_vertex(c, deterministic != 0, d_vf, vidx, n_views, d_feats, s);
 }
+
+// the forward gathers themselves, one production launch each on the caller's buffers (tests/test_gpu_cond_gathers.py)
+int mvd_op_vertex_gather(mvd_ctx* c, const float* feats, const int32_t* view_idx, int n_views, float* vf_out, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!feats || !view_idx || !vf_out || n_views <= 0) return mvd_fail("mvd_op_vertex_gather: bad argument");
+  if (!c->mesh.Nv) return mvd_fail("mvd_op_vertex_gather: mvd_set_mesh must be called first");
+  hipStream_t s = (hipStream_t)stream;
+  WsScope ws_scope(c);
+  const int* vidx;
+  RET_IF(hook_views(c, view_idx, n_views, &vidx, s));
+  return launch_vertex_gather(feats, c->cams, vidx, n_views, c->mesh.verts, c->mesh.Nv, c->v.spatial_volume_size,
+                              c->v.spatial_volume_length, c->u.image_size, c->v.projection == 0, vf_out, s);
+}
+int mvd_op_latent_gather(mvd_ctx* c, const float* rows, float* vol_out, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!rows || !vol_out) return mvd_fail("mvd_op_latent_gather: null argument");
+  const MeshTables& m = c->mesh;
+  if (!m.Nv) return mvd_fail("mvd_op_latent_gather: mvd_set_mesh must be called first");
+  return launch_latent_gather(rows, m.grid2, m.shape[2][0], m.shape[2][1], m.shape[2][2], m.min_xyz, m.out_sh, c->v.voxel_size,
+                              c->v.spatial_volume_size, c->v.spatial_volume_length, vol_out, (hipStream_t)stream);
+}
+int mvd_op_frustum_gather(mvd_ctx* c, const float* vol, const int32_t* view_idx, int TN, int D, int S, float* out, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!vol || !view_idx || !out || TN <= 0 || D <= 0 || S <= 1) return mvd_fail("mvd_op_frustum_gather: bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  WsScope ws_scope(c);
+  const int* vidx;
+  RET_IF(hook_views(c, view_idx, TN, &vidx, s));
+  const size_t n = (size_t)TN * D * S * S * 64;
+  half_t* gath = ws_alloc<half_t>(c, n);
+  WS_CHECK(gath);
+  RET_IF(launch_frustum_gather(vol, c->cams, vidx, TN, D, S, c->v.spatial_volume_size, c->v.spatial_volume_length,
+                               c->v.projection == 0, gath, s));
+  hipLaunchKernelGGL(hook_f16_to_f32_kernel, dim3(256), dim3(256), 0, s, gath, out, n);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}

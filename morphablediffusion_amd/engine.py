@@ -557,6 +557,41 @@ class Engine:
         L.check(self.lib.mvd_op_vertex_adjoint(self._ctx, L.ptr(g), idx, n, bool(deterministic), L.ptr(out), _stream()))
         return out
 
+    def op_vertex_gather(self, feats, view_idx=None):
+        """mvd_op_vertex_gather: the vertex gather alone.  feats [n,s,s,16] (channels-last 2-D encoder maps) of the views
+        ``view_idx`` (default 0..n-1) of the active sample -> per-view vertex features [n,Nv,16]."""
+        f = _f32(feats, self.device)
+        s = self.ucfg.image_size
+        assert f.dim() == 4 and tuple(f.shape[1:]) == (s, s, 16)
+        idx, n = self._view_idx(view_idx, f.shape[0])
+        assert n == f.shape[0]
+        out = torch.full((n, self.num_vertices, 16), float("nan"), device=self.device, dtype=torch.float32)
+        L.check(self.lib.mvd_op_vertex_gather(self._ctx, L.ptr(f), idx, n, L.ptr(out), _stream()))
+        return out
+
+    def op_latent_gather(self, rows):
+        """mvd_op_latent_gather: the lattice gather alone.  rows [n_rows,64] of the coarsest sparse level of the active sample's
+        mesh -> the mesh volume [V,V,V,64] (channels-last)."""
+        r = _f32(rows, self.device)
+        n = C.c_int32(0)
+        L.check(self.lib.mvd_op_latent_adjoint(self._ctx, None, 0, None, C.byref(n), _stream()))
+        assert tuple(r.shape) == (n.value, 64)
+        V = self.vcfg.spatial_volume_size
+        out = torch.full((V, V, V, 64), float("nan"), device=self.device, dtype=torch.float32)
+        L.check(self.lib.mvd_op_latent_gather(self._ctx, L.ptr(r), L.ptr(out), _stream()))
+        return out
+
+    def op_frustum_gather(self, vol, view_idx, D, S):
+        """mvd_op_frustum_gather: the frustum gather alone.  vol [V,V,V,64] (channels-last) -> the D x S x S frusta of the views
+        ``view_idx`` of the active sample [TN,D,S,S,64], the operand-type values widened to fp32."""
+        v = _f32(vol, self.device)
+        V = self.vcfg.spatial_volume_size
+        assert tuple(v.shape) == (V, V, V, 64)
+        idx, TN = self._view_idx(view_idx, 0)
+        out = torch.full((TN, D, S, S, 64), float("nan"), device=self.device, dtype=torch.float32)
+        L.check(self.lib.mvd_op_frustum_gather(self._ctx, L.ptr(v), idx, TN, D, S, L.ptr(out), _stream()))
+        return out
+
     def get_grad(self, key: str, shape):
         out = torch.empty(tuple(shape), device=self.device, dtype=torch.float32)
         L.check(self.lib.mvd_train_get_grad(self._ctx, key.encode(), L.ptr(out), out.numel(), _stream()))

@@ -77,6 +77,41 @@ def test_stage_unproject_matches_the_restatement(V, S, projection):
     r = R.rel_l2(got, want)
     print(f"[spatial] unproject V={V} S={S} {projection}: relL2={r:.2e} zero share={zero:.3f}")
     assert r <= UNPROJECT_BOUND
+    # the boundary cases of tests/test_cond_gathers_cpu.py (this rig, the near rig, the rig with the cameras inside the cube) against
+    # its float64 restatement: no element unwritten, exact zeros where no tap is in range, e_kernel <= 1.1 e_round + 4 e_oracle32
+    # over the whole output and over the partially-outside rows alone, identical bits from two calls
+    from morphablediffusion_amd import lib as L
+    from tests import test_cond_gathers_cpu as GC
+    from tests.test_train_deterministic_cpu import rel_l2 as rel64
+    opd = torch.bfloat16 if L.DTYPE == "bf16" else torch.float16
+    for case in [c for c in GC.UNPROJECT_CASES if c[:3] == (V, S, projection)]:
+        c = GC.unproject_case(*case)
+        if case[3] == "stage":
+            assert torch.equal(c["K"], batch["target_K"][0]) and torch.equal(c["RT"], batch["target_RT"][0]) and torch.equal(c["x"], feats)
+        eng.set_cameras(c["K"], c["RT"])
+        x = c["x"].cuda()
+        first, second = eng.stage_unproject(x), eng.stage_unproject(x)
+        torch.cuda.synchronize()
+        assert torch.equal(first, second)
+        got, want64 = first.cpu(), c["want"]
+        assert torch.isfinite(got).all()
+        rows = lambda t: t.reshape(N, 16, -1).transpose(1, 2)
+        taps = c["taps"]
+        partial = (taps > 0) & (taps < 4)
+        e_round, e32 = rel64(want64.to(opd), want64), c["e_oracle32"]
+        e_all, r32 = rel64(got, want64), R.rel_l2(got, R.unproject_views(c["x"], c["K"], c["RT"], V, vcfg.spatial_volume_length, 8 * S, projection))
+        e_part = e_round_p = e32_p = 0.0
+        if partial.any():
+            wp = rows(want64)[partial]
+            e_part, e_round_p, e32_p = rel64(rows(got)[partial], wp), rel64(wp.to(opd), wp), rel64(rows(c["oracle32"])[partial], wp)
+        outside, p_share, none = GC.shares(c)
+        print(f"[gather] unproject {GC.case_id(case)}: e_kernel={e_all:.3e} (partial rows {e_part:.3e}) e_oracle32={e32:.3e} (partial rows "
+              f"{e32_p:.3e}) e_round={e_round:.3e} (partial rows {e_round_p:.3e}) taps outside={outside:.3f} rows partial={p_share:.3f} "
+              f"rows without a tap={none:.3f} relL2 vs the fp32 restatement={r32:.2e}")
+        assert (rows(got)[taps == 0] == 0).all(), "a lattice point without a tap inside the map is not exactly zero"
+        assert r32 <= UNPROJECT_BOUND
+        assert e_all <= 1.1 * e_round + 4 * e32
+        assert e_part <= 1.1 * e_round_p + 4 * e32_p
     eng.close()
 
 
