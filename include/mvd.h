@@ -378,6 +378,37 @@ int mvd_train_repack(mvd_ctx* ctx);
 /* The same in the order of `stream` (the stream the optimiser update was enqueued on and the next forward will be): no device
  * synchronisation -- the pack launches wait for an event on `stream`, later work on `stream` waits for them. */
 int mvd_train_repack_async(mvd_ctx* ctx, void* stream);
+/* LoRA fine-tuning of a training context: low-rank adapters on chosen weight matrices, W_eff = W0 + s B A with A [rank][in],
+ * B [out][rank], s = alpha / rank.  The forward and the backward pass are unchanged: the backward writes the dense gradient dW of
+ * every UNet weight into the gradient arena as before, and the optimiser step projects it onto the adapters (dA = s B^T dW,
+ * dB = s dW A^T), updates them with the fused AdamW kernel and writes W0 + s B A back into the master arena; the caller then
+ * re-packs (mvd_train_repack*).  The projection is linear in dW, so it runs after the gradient averaging of a multi-GPU run.
+ *   mvd_lora_attach        keys: n parameter names, each of shape (out, in) followed only by 1s (Linear, 1x1 and 1x1x1 convolution
+ *                          weights); 1 <= rank <= 64, one rank per attach.  Snapshots W0 (a compact fp32 copy of the targets) and
+ *                          allocates the adapter arenas -- parameters, gradients, two Adam moments, all zero: per target A then B,
+ *                          each padded to 64 floats.  The masters are not changed (B = 0).  An attached context detaches first.
+ *   mvd_lora_arena_size / _target_count / _info   floats per adapter arena; the targets in attach order: name, offsets of A and B
+ *                          in the adapter arenas, out, in (each pointer may be NULL).
+ *   mvd_lora_adopt_arena   as mvd_train_adopt_arena, for adapter arena `which` (0 parameters, 1 gradients, 2 / 3 moments).
+ *   mvd_lora_project       the projection alone: the adapter gradient arena is OVERWRITTEN with s B^T dW / s dW A^T of the gradient
+ *                          arena as it is (inspection, timing; mvd_lora_step does it itself).
+ *   mvd_lora_step          projection (overwrites the adapter gradients, which keep dW's loss scale) -> the gradient-norm pass over
+ *                          the adapter gradients when clipping, loss scaling or grad_norm_out asks for it (as in
+ *                          mvd_train_adamw_step_ex; mvd_train_last_grad_norm reports it too) -> AdamW on the adapter arenas -> merge.
+ *                          An overflowed step (*skipped_out = 1) leaves adapters, moments and masters as they were.
+ *   mvd_lora_set_scale     merges at another strength s (0: the masters are W0 again) without touching the adapters; later steps
+ *                          use that s.  Also the call that merges adapters written into the parameter arena by the caller.
+ *   mvd_lora_detach        keep_merged == 0 restores W0 first; frees the LoRA state.  The caller re-packs. */
+int mvd_lora_attach(mvd_ctx* ctx, const char* const* keys, int n, int rank, float alpha);
+int mvd_lora_arena_size(mvd_ctx* ctx, int64_t* numel);
+int mvd_lora_target_count(mvd_ctx* ctx);
+int mvd_lora_info(mvd_ctx* ctx, int i, char* name, size_t cap, int64_t* a_off, int64_t* b_off, int64_t* out, int64_t* in);
+int mvd_lora_adopt_arena(mvd_ctx* ctx, int which, float* ptr, int64_t numel);
+int mvd_lora_project(mvd_ctx* ctx, void* stream);
+int mvd_lora_step(mvd_ctx* ctx, float lr, float beta1, float beta2, float eps, float weight_decay, int step, float inv_scale,
+                  float max_grad_norm, int* skipped_out, float* grad_norm_out, void* stream);
+int mvd_lora_set_scale(mvd_ctx* ctx, float scale, void* stream);
+int mvd_lora_detach(mvd_ctx* ctx, int keep_merged);
 /* DDP's bucketed, overlapped gradient averaging (train_morphable_diffusion.py:302-303: Lightning wraps the module in
  * DistributedDataParallel, whose reducer all-reduces a bucket as soon as its gradients are ready).  mvd_train_unet_step leaves
  * its UNet gradients as buckets in the order they become final during the backward pass -- one per chain of blocks (output
@@ -460,6 +491,21 @@ int mvd_op_cfg_ms(const float* eps_c, const float* eps_u, float scale, const flo
  * e != NULL and ema_decay >= 0) step.  Synchronises the stream when a norm was computed (its scratch lives for the call). */
 int mvd_op_adamw_ex(float* p, const float* g, float* m, float* v, float* e, size_t n, float lr, float beta1, float beta2, float eps,
                     float wd, int step, float inv_scale, float max_grad_norm, float ema_decay, float* norm_out, void* stream);
+/* The LoRA kernels (below: mvd_lora_*) on raw device buffers, one target, no context: dW / W0 / W [out][in], A [r][in],
+ * B [out][r], gA / gB shaped like A / B, all fp32; 1 <= r <= 64.  mvd_op_lora_project OVERWRITES gA = scale B^T dW and
+ * gB = scale dW A^T; mvd_op_lora_merge writes W = W0 + scale B A.  A bad argument returns an error and launches nothing.  Both
+ * synchronise the stream (their table and scratch live for the call). */
+int mvd_op_lora_project(const float* dW, const float* A, const float* B, int out, int in, int r, float scale, float* gA, float* gB,
+                        void* stream);
+int mvd_op_lora_merge(const float* W0, const float* A, const float* B, int out, int in, int r, float scale, float* W, void* stream);
+/* The same for n targets in one launch, as mvd_lora_step runs them: per target the offsets (floats) of dW / W from `dW` / `W`, of
+ * its compact W0 from `W0`, of A from `A` (gA from `gA`) and of B from `B` (gB from `gB`), and out / in. */
+int mvd_op_lora_project_grouped(const float* dW, const float* A, const float* B, int n, const int64_t* w_off, const int64_t* out,
+                                const int64_t* in, const int64_t* a_off, const int64_t* b_off, int r, float scale, float* gA, float* gB,
+                                void* stream);
+int mvd_op_lora_merge_grouped(const float* W0, const float* A, const float* B, int n, const int64_t* w_off, const int64_t* w0_off,
+                              const int64_t* out, const int64_t* in, const int64_t* a_off, const int64_t* b_off, int r, float scale,
+                              float* W, void* stream);
 int mvd_op_conv(mvd_ctx* ctx, const float* x_nchw, int B, int Cin, int H, int W, const float* w, const float* bias,
                 int Cout, int ksize, int stride, int upsample, const float* resid_nchw, float* out_nchw, int force_splitk,
                 void* stream);

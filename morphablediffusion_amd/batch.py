@@ -139,10 +139,12 @@ def stack_batches(samples) -> Dict[str, torch.Tensor]:
     return {k: torch.cat([s[k] for s in samples], 0) for k in samples[0]}
 
 
-def load_model(cfg, ckpt, device="cuda:0", **overrides):
+def load_model(cfg, ckpt, device="cuda:0", lora=None, lora_scale=1.0, **overrides):
     """generate_face.py:71-78 ``load_model``: read the YAML (configs/facescape.yaml layout), instantiate ``config.model``
     through the ``target:`` reflection, torch.load the checkpoint and load ``ckpt['state_dict']`` with strict=False.
-    ``cfg`` is a path or an already parsed dict; ``overrides`` are extra constructor kwargs (e.g. workspace_gb)."""
+    ``cfg`` is a path or an already parsed dict; ``overrides`` are extra constructor kwargs (e.g. workspace_gb).
+    lora / lora_scale (not reference arguments): a LoRA adapter file (``SyncMultiviewDiffusion.save_lora``), merged into the
+    weights at that strength before they are packed."""
     from .model import instantiate_from_config
     if isinstance(cfg, (str, bytes)) or hasattr(cfg, "__fspath__"):
         import yaml
@@ -153,7 +155,11 @@ def load_model(cfg, ckpt, device="cuda:0", **overrides):
     model = instantiate_from_config(mc)
     print(f"loading model from {ckpt} ...")
     state = torch.load(ckpt, map_location="cpu")
-    model.load_state_dict(state["state_dict"], strict=False)
+    if lora is not None:
+        print(f"merging LoRA adapters from {lora} at strength {lora_scale} ...")
+        model.load_state_dict(state["state_dict"], strict=False, lora=lora, lora_scale=lora_scale)
+    else:
+        model.load_state_dict(state["state_dict"], strict=False)
     return model.eval()
 
 

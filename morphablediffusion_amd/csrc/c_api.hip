@@ -117,11 +117,14 @@ int mvd_create(const mvd_unet_config* ucfg, const mvd_volume_config* vcfg, int d
   return 0;
 }
 
+static void lora_free(mvd_ctx* c);
+
 void mvd_destroy(mvd_ctx* c) {
   if (!c) return;
   hipSetDevice(c->device);
   hipDeviceSynchronize();
   mvd_comm_destroy(c);
+  lora_free(c);
   for (auto& kv : c->raw)
     if (!c->param_index.count(kv.first)) hipFree(kv.second.d);  // master parameters live in the arena
   float* arenas[5] = {c->arena_p, c->arena_g, c->arena_m, c->arena_v, c->arena_e};
@@ -706,8 +709,9 @@ static void step_ranges(mvd_ctx* c, int finetune_unet, std::vector<StepRange>& o
 }
 
 // norm_dev[0] = || inv_scale * g || over the ranges, norm_dev[1] = the clipping coefficient for max_norm (1 when <= 0);
-// *flag (may be null) raised when the sum of squares is not finite
-static int grad_norm_pass(mvd_ctx* c, const std::vector<StepRange>& rs, float inv_scale, float max_norm, int* flag, hipStream_t s) {
+// *flag (may be null) raised when the sum of squares is not finite.  g: the arena the ranges index (gradients, or LoRA's)
+static int grad_norm_pass(mvd_ctx* c, const float* g, const std::vector<StepRange>& rs, float inv_scale, float max_norm, int* flag,
+                          hipStream_t s) {
   size_t total = 0;
   for (const StepRange& r : rs) total += (size_t)bwd_grad_sumsq_blocks(r.len);
   if (!c->norm_dev) HIP_CHECK_RET(hipMalloc((void**)&c->norm_dev, 2 * sizeof(float)));
@@ -720,7 +724,7 @@ static int grad_norm_pass(mvd_ctx* c, const std::vector<StepRange>& rs, float in
   }
   size_t at = 0;
   for (const StepRange& r : rs) {
-    RET_IF(bwd_grad_sumsq(c->arena_g + r.off, r.len, inv_scale, c->norm_part + at, s));
+    RET_IF(bwd_grad_sumsq(g + r.off, r.len, inv_scale, c->norm_part + at, s));
     at += (size_t)bwd_grad_sumsq_blocks(r.len);
   }
   return bwd_grad_norm_final(c->norm_part, (int)total, max_norm, c->norm_dev, flag, s);
@@ -762,7 +766,7 @@ int mvd_train_grad_norm(mvd_ctx* c, float inv_scale, int finetune_unet, float* n
   hipStream_t s = S(stream);
   std::vector<StepRange> rs;
   step_ranges(c, finetune_unet, rs);
-  RET_IF(grad_norm_pass(c, rs, inv_scale, 0.f, nullptr, s));
+  RET_IF(grad_norm_pass(c, c->arena_g, rs, inv_scale, 0.f, nullptr, s));
   HIP_CHECK_RET(hipMemcpyAsync(norm_out, c->norm_dev, sizeof(float), hipMemcpyDeviceToDevice, s));
   return 0;
 }
@@ -809,7 +813,7 @@ int mvd_train_adamw_step_ex(mvd_ctx* c, float lr, float lr_aux, float beta1, flo
   // separate finite check of mvd_train_adamw_step is not run).  Without clipping, loss scaling or a norm to report: no pass.
   const bool clip = max_grad_norm > 0.f, scaled = inv_scale != 1.0f;
   const bool norm_pass = clip || scaled || grad_norm_out;
-  if (norm_pass) RET_IF(grad_norm_pass(c, rs, inv_scale, clip ? max_grad_norm : 0.f, scaled ? c->found_inf : nullptr, s));
+  if (norm_pass) RET_IF(grad_norm_pass(c, c->arena_g, rs, inv_scale, clip ? max_grad_norm : 0.f, scaled ? c->found_inf : nullptr, s));
   for (const StepRange& r : rs)
     RET_IF(bwd_adamw_ex(c->arena_p + r.off, c->arena_g + r.off, c->arena_m + r.off, c->arena_v + r.off,
                         ema ? c->arena_e + r.off : nullptr, r.len, r.grp == 1 ? lr : lr_aux, beta1, beta2, eps, weight_decay, step,
@@ -845,6 +849,251 @@ int mvd_op_adamw_ex(float* p, const float* g, float* m, float* v, float* e, size
     hipFree(scratch);
   }
   return rc;
+}
+
+// ---- LoRA (k_lora.hip) ---------------------------------------------------------------------------------------------------------
+// the kernels on raw buffers: a table and the projection's partial sums that live for the call
+static int lora_op_table(const char* who, int n, const int64_t* w_off, const int64_t* w0_off, const int64_t* out, const int64_t* in,
+                         const int64_t* a_off, const int64_t* b_off, int r, std::vector<LoraTarget>& tab, int* tiles, int* red,
+                         size_t* part_n) {
+  static thread_local std::string msg;
+  msg.clear();
+  if (n < 1 || !w_off || !out || !in || !a_off || !b_off) msg = std::string(who) + ": null argument";
+  else if (r < 1 || r > LORA_MAX_RANK) msg = std::string(who) + ": the rank must be in 1..64";
+  for (int i = 0; msg.empty() && i < n; ++i) {
+    if (out[i] < 1 || in[i] < 1 || out[i] >= (1 << 30) || in[i] >= (1 << 30) || w_off[i] < 0 || a_off[i] < 0 || b_off[i] < 0 ||
+        (w0_off && w0_off[i] < 0)) {
+      msg = std::string(who) + ": out and in must be positive, offsets non-negative";
+      break;
+    }
+    LoraTarget T{};
+    T.out = (int)out[i], T.in = (int)in[i];
+    T.w_off = w_off[i], T.w0_off = w0_off ? w0_off[i] : 0, T.a_off = a_off[i], T.b_off = b_off[i];
+    tab.push_back(T);
+  }
+  if (!msg.empty()) return mvd_fail(msg.c_str());
+  lora_plan(tab.data(), n, r, tiles, red, part_n);
+  if (*tiles < 1 || *red < 1) return mvd_fail("lora op: more than 2^31 tiles");
+  return 0;
+}
+
+int mvd_op_lora_project_grouped(const float* dW, const float* A, const float* B, int n, const int64_t* w_off, const int64_t* out,
+                                const int64_t* in, const int64_t* a_off, const int64_t* b_off, int r, float scale, float* gA, float* gB,
+                                void* stream) {
+  if (!dW || !A || !B || !gA || !gB) return mvd_fail("mvd_op_lora_project: null argument");
+  std::vector<LoraTarget> tab;
+  int tiles = 0, red = 0;
+  size_t part_n = 0;
+  RET_IF(lora_op_table("mvd_op_lora_project", n, w_off, nullptr, out, in, a_off, b_off, r, tab, &tiles, &red, &part_n));
+  hipStream_t s = S(stream);
+  float* scratch = nullptr;  // [partials | table]
+  HIP_CHECK_RET(hipMalloc((void**)&scratch, part_n * sizeof(float) + tab.size() * sizeof(LoraTarget)));
+  LoraTarget* d_tab = (LoraTarget*)(scratch + part_n);
+  int rc = hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(LoraTarget), hipMemcpyHostToDevice, s) == hipSuccess
+               ? 0 : mvd_fail("mvd_op_lora_project: table upload failed");
+  if (!rc) rc = lora_project(d_tab, n, tiles, red, dW, A, B, r, scale, scratch, gA, gB, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_lora_project: stream synchronisation failed");
+  hipFree(scratch);
+  return rc;
+}
+
+int mvd_op_lora_merge_grouped(const float* W0, const float* A, const float* B, int n, const int64_t* w_off, const int64_t* w0_off,
+                              const int64_t* out, const int64_t* in, const int64_t* a_off, const int64_t* b_off, int r, float scale,
+                              float* W, void* stream) {
+  if (!W0 || !A || !B || !W || !w0_off) return mvd_fail("mvd_op_lora_merge: null argument");
+  std::vector<LoraTarget> tab;
+  int tiles = 0, red = 0;
+  size_t part_n = 0;
+  RET_IF(lora_op_table("mvd_op_lora_merge", n, w_off, w0_off, out, in, a_off, b_off, r, tab, &tiles, &red, &part_n));
+  hipStream_t s = S(stream);
+  LoraTarget* d_tab = nullptr;
+  HIP_CHECK_RET(hipMalloc((void**)&d_tab, tab.size() * sizeof(LoraTarget)));
+  int rc = hipMemcpyAsync(d_tab, tab.data(), tab.size() * sizeof(LoraTarget), hipMemcpyHostToDevice, s) == hipSuccess
+               ? 0 : mvd_fail("mvd_op_lora_merge: table upload failed");
+  if (!rc) rc = lora_merge(d_tab, n, tiles, W0, A, B, r, scale, W, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_lora_merge: stream synchronisation failed");
+  hipFree(d_tab);
+  return rc;
+}
+
+int mvd_op_lora_project(const float* dW, const float* A, const float* B, int out, int in, int r, float scale, float* gA, float* gB,
+                        void* stream) {
+  const int64_t zero = 0, o = out, i = in;
+  return mvd_op_lora_project_grouped(dW, A, B, 1, &zero, &o, &i, &zero, &zero, r, scale, gA, gB, stream);
+}
+
+int mvd_op_lora_merge(const float* W0, const float* A, const float* B, int out, int in, int r, float scale, float* W, void* stream) {
+  const int64_t zero = 0, o = out, i = in;
+  return mvd_op_lora_merge_grouped(W0, A, B, 1, &zero, &zero, &o, &i, &zero, &zero, r, scale, W, stream);
+}
+
+static void lora_free(mvd_ctx* c) {
+  mvd_ctx::Lora& l = c->lora;
+  for (int i = 0; i < 4; ++i)
+    if (l.arena[i] && l.owned[i]) hipFree(l.arena[i]);
+  hipFree(l.w0);
+  hipFree(l.part);
+  hipFree(l.d_tab);
+  l = mvd_ctx::Lora();
+}
+
+int mvd_lora_detach(mvd_ctx* c, int keep_merged) {
+  if (!c || !c->train_mode || !c->finalized) return mvd_fail("mvd_lora_detach: context not finalized in training mode");
+  if (!c->lora.rank) return 0;
+  HIP_CHECK_RET(hipSetDevice(c->device));
+  HIP_CHECK_RET(hipDeviceSynchronize());
+  if (!keep_merged)
+    for (const LoraTarget& T : c->lora.tab)
+      HIP_CHECK_RET(hipMemcpy(c->arena_p + T.w_off, c->lora.w0 + T.w0_off, (size_t)T.out * T.in * sizeof(float), hipMemcpyDeviceToDevice));
+  lora_free(c);
+  return 0;
+}
+
+int mvd_lora_attach(mvd_ctx* c, const char* const* keys, int n, int rank, float alpha) {
+  if (!c || !c->train_mode || !c->finalized) return mvd_fail("mvd_lora_attach: context not finalized in training mode");
+  if (!keys || n < 1) return mvd_fail("mvd_lora_attach: no target");
+  if (rank < 1 || rank > LORA_MAX_RANK) return mvd_fail("mvd_lora_attach: the rank must be in 1..64");
+  HIP_CHECK_RET(hipSetDevice(c->device));
+  static thread_local std::string msg;
+  mvd_ctx::Lora l;
+  auto pad = [](size_t v) { return (v + 63) & ~(size_t)63; };
+  for (int i = 0; i < n; ++i) {
+    auto it = keys[i] ? c->param_index.find(keys[i]) : c->param_index.end();
+    if (it == c->param_index.end()) {
+      msg = std::string("mvd_lora_attach: not a parameter of this context: ") + (keys[i] ? keys[i] : "(null)");
+      return mvd_fail(msg.c_str());
+    }
+    const mvd_ctx::ParamRec& p = c->params[it->second];
+    bool ok = p.shape.size() >= 2 && p.shape[0] >= 1 && p.shape[1] >= 1 && p.shape[0] < (1 << 30) && p.shape[1] < (1 << 30);
+    for (size_t d = 2; d < p.shape.size(); ++d) ok = ok && p.shape[d] == 1;
+    for (size_t j : l.param) ok = ok && j != it->second;  // (a key named twice)
+    if (!ok) {
+      msg = "mvd_lora_attach: " + p.key + " is not an (out, in[, 1...]) weight (or is named twice)";
+      return mvd_fail(msg.c_str());
+    }
+    LoraTarget T{};
+    T.out = (int)p.shape[0], T.in = (int)p.shape[1];
+    T.w_off = (long long)p.off;
+    T.w0_off = (long long)l.w0_n;
+    l.w0_n += pad(p.numel);
+    T.a_off = (long long)l.n;
+    l.n += pad((size_t)rank * T.in);
+    T.b_off = (long long)l.n;
+    l.n += pad((size_t)T.out * rank);
+    l.tab.push_back(T);
+    l.param.push_back(it->second);
+  }
+  size_t part_n = 0;
+  lora_plan(l.tab.data(), n, rank, &l.tiles, &l.red_blocks, &part_n);
+  if (l.tiles < 1 || l.red_blocks < 1) return mvd_fail("mvd_lora_attach: more than 2^31 tiles");
+  RET_IF(mvd_lora_detach(c, 0));  // (synchronises the device)
+  l.rank = rank;
+  l.scale = alpha / (float)rank;
+  c->lora = l;
+  mvd_ctx::Lora& L_ = c->lora;
+  auto fail = [&](const char* m) {
+    lora_free(c);
+    return mvd_fail(m);
+  };
+  if (hipMalloc((void**)&L_.w0, L_.w0_n * sizeof(float)) != hipSuccess || hipMalloc((void**)&L_.part, part_n * sizeof(float)) != hipSuccess ||
+      hipMalloc((void**)&L_.d_tab, (size_t)n * sizeof(LoraTarget)) != hipSuccess)
+    return fail("mvd_lora_attach: allocation failed");
+  for (int i = 0; i < 4; ++i) {
+    if (hipMalloc((void**)&L_.arena[i], L_.n * sizeof(float)) != hipSuccess) return fail("mvd_lora_attach: allocation failed");
+    L_.owned[i] = true;
+    if (hipMemset(L_.arena[i], 0, L_.n * sizeof(float)) != hipSuccess) return fail("mvd_lora_attach: memset failed");
+  }
+  if (hipMemset(L_.w0, 0, L_.w0_n * sizeof(float)) != hipSuccess || hipMemset(L_.part, 0, part_n * sizeof(float)) != hipSuccess ||
+      hipMemcpy(L_.d_tab, L_.tab.data(), (size_t)n * sizeof(LoraTarget), hipMemcpyHostToDevice) != hipSuccess)
+    return fail("mvd_lora_attach: table upload failed");
+  for (const LoraTarget& T : L_.tab)
+    if (hipMemcpy(L_.w0 + T.w0_off, c->arena_p + T.w_off, (size_t)T.out * T.in * sizeof(float), hipMemcpyDeviceToDevice) != hipSuccess)
+      return fail("mvd_lora_attach: snapshot of the base weights failed");
+  return 0;
+}
+
+int mvd_lora_arena_size(mvd_ctx* c, int64_t* numel) {
+  if (!c || !c->lora.rank || !numel) return mvd_fail("mvd_lora_arena_size: no adapters attached");
+  *numel = (int64_t)c->lora.n;
+  return 0;
+}
+int mvd_lora_target_count(mvd_ctx* c) { return (c && c->lora.rank) ? (int)c->lora.tab.size() : 0; }
+
+int mvd_lora_info(mvd_ctx* c, int i, char* name, size_t cap, int64_t* a_off, int64_t* b_off, int64_t* out, int64_t* in) {
+  if (!c || !c->lora.rank) return mvd_fail("mvd_lora_info: no adapters attached");
+  if (i < 0 || i >= (int)c->lora.tab.size()) return mvd_fail("mvd_lora_info: index out of range");
+  const LoraTarget& T = c->lora.tab[i];
+  const std::string& key = c->params[c->lora.param[i]].key;
+  if (name) {
+    if (key.size() + 1 > cap) return mvd_fail("mvd_lora_info: name buffer too small");
+    memcpy(name, key.c_str(), key.size() + 1);
+  }
+  if (a_off) *a_off = T.a_off;
+  if (b_off) *b_off = T.b_off;
+  if (out) *out = T.out;
+  if (in) *in = T.in;
+  return 0;
+}
+
+int mvd_lora_adopt_arena(mvd_ctx* c, int which, float* ptr, int64_t numel) {
+  if (!c || !c->lora.rank) return mvd_fail("mvd_lora_adopt_arena: no adapters attached");
+  if (which < 0 || which > 3 || !ptr || numel != (int64_t)c->lora.n) return mvd_fail("mvd_lora_adopt_arena: bad argument");
+  HIP_CHECK_RET(hipSetDevice(c->device));
+  HIP_CHECK_RET(hipDeviceSynchronize());
+  float* old = c->lora.arena[which];
+  if (old == ptr) return 0;
+  HIP_CHECK_RET(hipMemcpy(ptr, old, c->lora.n * sizeof(float), hipMemcpyDeviceToDevice));
+  if (c->lora.owned[which]) hipFree(old);
+  c->lora.arena[which] = ptr;
+  c->lora.owned[which] = false;
+  return 0;
+}
+
+static int lora_merge_ctx(mvd_ctx* c, hipStream_t s) {
+  const mvd_ctx::Lora& l = c->lora;
+  return lora_merge(l.d_tab, (int)l.tab.size(), l.tiles, l.w0, l.arena[0], l.arena[0], l.rank, l.scale, c->arena_p, s);
+}
+
+int mvd_lora_set_scale(mvd_ctx* c, float scale, void* stream) {
+  if (!c || !c->lora.rank) return mvd_fail("mvd_lora_set_scale: no adapters attached");
+  HIP_CHECK_RET(hipSetDevice(c->device));
+  c->lora.scale = scale;
+  return lora_merge_ctx(c, S(stream));
+}
+
+static int lora_project_ctx(mvd_ctx* c, hipStream_t s) {
+  const mvd_ctx::Lora& l = c->lora;
+  return lora_project(l.d_tab, (int)l.tab.size(), l.tiles, l.red_blocks, c->arena_g, l.arena[0], l.arena[0], l.rank, l.scale, l.part,
+                      l.arena[1], l.arena[1], s);
+}
+
+int mvd_lora_project(mvd_ctx* c, void* stream) {
+  if (!c || !c->lora.rank) return mvd_fail("mvd_lora_project: no adapters attached");
+  HIP_CHECK_RET(hipSetDevice(c->device));
+  return lora_project_ctx(c, S(stream));
+}
+
+int mvd_lora_step(mvd_ctx* c, float lr, float beta1, float beta2, float eps, float weight_decay, int step, float inv_scale,
+                  float max_grad_norm, int* skipped_out, float* grad_norm_out, void* stream) {
+  if (!c || !c->lora.rank) return mvd_fail("mvd_lora_step: no adapters attached");
+  if (step < 1) return mvd_fail("mvd_lora_step: step counts from 1");
+  HIP_CHECK_RET(hipSetDevice(c->device));
+  hipStream_t s = S(stream);
+  const mvd_ctx::Lora& l = c->lora;
+  RET_IF(lora_project_ctx(c, s));
+  HIP_CHECK_RET(hipMemsetAsync(c->found_inf, 0, sizeof(int), s));
+  const bool clip = max_grad_norm > 0.f, scaled = inv_scale != 1.0f;
+  if (clip || scaled || grad_norm_out) {
+    const std::vector<StepRange> rs{{0, l.n, 1}};
+    RET_IF(grad_norm_pass(c, l.arena[1], rs, inv_scale, clip ? max_grad_norm : 0.f, scaled ? c->found_inf : nullptr, s));
+  }
+  RET_IF(bwd_adamw_ex(l.arena[0], l.arena[1], l.arena[2], l.arena[3], nullptr, l.n, lr, beta1, beta2, eps, weight_decay, step, inv_scale,
+                      clip ? c->norm_dev + 1 : nullptr, -1.f, c->found_inf, s));
+  RET_IF(lora_merge_ctx(c, s));
+  if (skipped_out) HIP_CHECK_RET(hipMemcpyAsync(skipped_out, c->found_inf, sizeof(int), hipMemcpyDeviceToHost, s));
+  if (grad_norm_out) HIP_CHECK_RET(hipMemcpyAsync(grad_norm_out, c->norm_dev, sizeof(float), hipMemcpyDeviceToHost, s));
+  if (skipped_out || grad_norm_out) HIP_CHECK_RET(hipStreamSynchronize(s));
+  return 0;
 }
 
 int mvd_train_repack(mvd_ctx* c) {

@@ -327,6 +327,24 @@ int bwd_grad_norm_final(const float* partial, int count, float max_norm, float* 
 int bwd_adamw_ex(float* p, const float* g, float* m, float* v, float* e, size_t n, float lr, float beta1, float beta2, float eps, float wd,
                  int step, float inv_scale, const float* clip, float ema_decay, const int* skip, hipStream_t s);
 int bwd_swap_f32(float* a, float* b, size_t n, hipStream_t s);
+// k_lora.hip: low-rank adapters W0 + s B A (A [r][in], B [out][r]) on fp32 arenas.  One table entry per adapted tensor; offsets in
+// floats: w_off into the arena of dW / W, w0_off into the compact copy of the adapted tensors, a_off / b_off into the adapter
+// arenas, pa_off / pb_off into the projection's partial-sum workspace.  tile0 / red0: the target's first workgroup in the tile
+// launches (LORA_TILE_O x LORA_TILE_I tiles, row-tile major) and in the projection's reduce launch (lora_plan fills the last four).
+#define LORA_MAX_RANK 64
+#define LORA_TILE_O 32
+#define LORA_TILE_I 128
+struct LoraTarget {
+  long long w_off, w0_off, a_off, b_off, pa_off, pb_off;
+  int out, in, tile0, red0;
+};
+void lora_plan(LoraTarget* tab, int n, int r, int* tiles, int* red_blocks, size_t* part_floats);
+// gA = scale B^T dW, gB = scale dW A^T for every target (overwritten; two launches, no atomic, bit-reproducible)
+int lora_project(const LoraTarget* tab, int n, int tiles, int red_blocks, const float* dW, const float* A, const float* B, int r,
+                 float scale, float* part, float* gA, float* gB, hipStream_t s);
+// W = W0 + scale B A for every target: exactly out x in elements each
+int lora_merge(const LoraTarget* tab, int n, int tiles, const float* W0, const float* A, const float* B, int r, float scale, float* W,
+               hipStream_t s);
 // k_cond_bwd.hip
 int cbwd_frustum_scatter(const float* d_out, const ViewCam* cams, const int* view_idx, int TN, int D, int S, int V, float vol_len, int persp,
                          float* d_vol, hipStream_t s);

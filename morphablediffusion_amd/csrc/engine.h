@@ -377,6 +377,21 @@ struct mvd_ctx {
   float *norm_part = nullptr, *norm_dev = nullptr;
   size_t norm_part_cap = 0;
   int* found_inf = nullptr;  // device flag of the last gradient finite-check
+  // LoRA (mvd_lora_attach .. mvd_lora_detach): the adapted tensors' masters are W0 + s B A, re-merged by every mvd_lora_step; the
+  // backward pass is unchanged, the step projects its dense dW onto the adapters (k_lora.hip).  Adapter arenas: 0 parameters
+  // (A then B of each target, each padded to 64 floats), 1 gradients, 2 / 3 Adam moments -- owned here or adopted like the others.
+  struct Lora {
+    int rank = 0;
+    float scale = 0.f;                // s = alpha / rank (mvd_lora_set_scale: another strength)
+    std::vector<LoraTarget> tab;      // host copy of d_tab
+    std::vector<size_t> param;        // index into `params` per target
+    LoraTarget* d_tab = nullptr;
+    int tiles = 0, red_blocks = 0;
+    size_t n = 0, w0_n = 0;           // floats per adapter arena / in the compact W0 copy
+    float *w0 = nullptr, *part = nullptr;
+    float* arena[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool owned[4] = {false, false, false, false};
+  } lora;
   // Gradient buckets of the last mvd_train_unet_step, in the order their gradients become final during the backward pass (one per
   // chain of UNet blocks, then one for everything that completes at the end: the stacked embedding / attn2 projections, the
   // head): arena ranges + an event recorded behind the last kernel that writes them.  The caller starts one all-reduce per

@@ -92,6 +92,8 @@ class Engine:
         self._loaded = False
         self.flat_params = self.flat_grads = self.flat_m = self.flat_v = None
         self.param_table = {}
+        self.lora_params = self.lora_grads = self.lora_m = self.lora_v = None  # lora_attach
+        self.lora_table, self.lora_rank = {}, 0
         self.num_vertices = 0
         self._slot_nv = {}
 
@@ -681,6 +683,75 @@ class Engine:
             L.check(self.lib.mvd_train_repack(self._ctx))
         else:
             L.check(self.lib.mvd_train_repack_async(self._ctx, _stream()))
+
+    # ---- LoRA (mvd_lora_*) ---------------------------------------------------------------------------------------------
+    def lora_attach(self, keys, rank, alpha):
+        """Low-rank adapters W0 + (alpha / rank) B A on the parameters ``keys`` (each of shape (out, in[, 1...])): the library
+        snapshots W0 and creates four adapter arenas, adopted here as ``lora_params`` / ``lora_grads`` / ``lora_m`` / ``lora_v``
+        (flat fp32 device tensors, zero: the masters do not change until B does).  ``lora_table[key]`` = (offset of A, offset of
+        B, out, in); ``lora_view`` gives the tensors."""
+        if not self.train_mode or not self._loaded:
+            raise L.MvdError("lora_attach needs a training context with loaded weights")
+        keys = list(keys)
+        was_attached = bool(self.lora_rank)
+        arr = (C.c_char_p * max(1, len(keys)))(*[k.encode() for k in keys])
+        L.check(self.lib.mvd_lora_attach(self._ctx, arr, len(keys), int(rank), float(alpha)))
+        numel = C.c_int64(0)
+        L.check(self.lib.mvd_lora_arena_size(self._ctx, C.byref(numel)))
+        n = numel.value
+        flats = [torch.empty(n, device=self.device, dtype=torch.float32) for _ in range(4)]
+        for which, t in enumerate(flats):
+            L.check(self.lib.mvd_lora_adopt_arena(self._ctx, which, L.ptr(t), n))
+        self.lora_params, self.lora_grads, self.lora_m, self.lora_v = flats
+        self.lora_rank, self.lora_alpha, self.lora_scale = int(rank), float(alpha), float(alpha) / int(rank)
+        self.lora_table = {}
+        name = C.create_string_buffer(512)
+        a, b, o, i = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        for t in range(self.lib.mvd_lora_target_count(self._ctx)):
+            L.check(self.lib.mvd_lora_info(self._ctx, t, name, len(name), C.byref(a), C.byref(b), C.byref(o), C.byref(i)))
+            self.lora_table[name.value.decode()] = (a.value, b.value, o.value, i.value)
+        if was_attached:  # the library put W0 back into the masters before it took the new snapshot
+            self.repack()
+
+    def lora_detach(self, keep_merged=False):
+        """Frees the adapters; keep_merged=False puts W0 back into the masters first.  Re-packs."""
+        L.check(self.lib.mvd_lora_detach(self._ctx, bool(keep_merged)))
+        self.lora_params = self.lora_grads = self.lora_m = self.lora_v = None
+        self.lora_table, self.lora_rank = {}, 0
+        self.repack()
+
+    def lora_view(self, key, which, grad=False):
+        """A ([rank, in]) or B ([out, rank]) of one target -- or its gradient -- as a view of the flat adapter arena."""
+        a, b, out, in_ = self.lora_table[key]
+        flat = self.lora_grads if grad else self.lora_params
+        if which == "A":
+            return flat[a:a + self.lora_rank * in_].view(self.lora_rank, in_)
+        return flat[b:b + out * self.lora_rank].view(out, self.lora_rank)
+
+    def lora_project(self):
+        """mvd_lora_project: ``lora_grads`` = the projection of the dense gradients in ``flat_grads`` (what lora_step starts with)."""
+        L.check(self.lib.mvd_lora_project(self._ctx, _stream()))
+
+    def lora_set_scale(self, scale):
+        """Merge W0 + scale B A into the masters (0: W0 again) and re-pack; the adapters are not touched."""
+        L.check(self.lib.mvd_lora_set_scale(self._ctx, float(scale), _stream()))
+        self.lora_scale = float(scale)
+        self.repack()
+
+    def lora_step(self, lr, step, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, inv_scale=1.0, check=True, max_grad_norm=None):
+        """mvd_lora_step (project the dense gradients onto the adapters, norm pass, fused AdamW on the adapter arenas, merge) +
+        re-pack.  Returns True when the update was skipped for a non-finite gradient; with max_grad_norm ``last_grad_norm`` holds
+        the norm of the un-scaled adapter gradients as a device scalar."""
+        skipped = C.c_int(0)
+        clip = float(max_grad_norm) if max_grad_norm is not None else 0.0
+        L.check(self.lib.mvd_lora_step(self._ctx, lr, betas[0], betas[1], eps, weight_decay, step, inv_scale, clip,
+                                       C.byref(skipped) if check else None, None, _stream()))
+        if clip > 0.0:
+            norm = torch.empty(1, device=self.device, dtype=torch.float32)
+            L.check(self.lib.mvd_train_last_grad_norm(self._ctx, L.ptr(norm), _stream()))
+            self.last_grad_norm = norm[0]
+        self.repack()
+        return bool(skipped.value)
 
     def set_volume(self, volume):
         v = _f32(volume, self.device)

@@ -130,7 +130,15 @@ def build_parser():
     p.add_argument("--camera_file", type=str, default="./assets/facescape_test_traj.pkl",
                    help="not a reference flag: the camera dict of --camera_trajectory real (the reference hard-codes this path)")
     p.add_argument("--device", type=str, default="cuda:0", help="not a reference flag")
+    p.add_argument("--lora", type=str, default=None,
+                   help="not a reference flag: a LoRA adapter file (save_lora), merged into the checkpoint's weights at load time")
+    p.add_argument("--lora_scale", type=float, default=1.0, help="not a reference flag: strength of --lora (0: the base model)")
     return p
+
+
+def load_model(cfg, ckpt, device="cuda:0", lora=None, lora_scale=1.0, **overrides):
+    """batch.load_model: the reference's ``load_model`` plus ``lora`` / ``lora_scale`` (an adapter file merged at load time)."""
+    return B.load_model(cfg, ckpt, device=device, lora=lora, lora_scale=lora_scale, **overrides)
 
 
 def run(flags, model=None):
@@ -143,7 +151,8 @@ def run(flags, model=None):
     torch.random.manual_seed(flags.seed)
     input_img = load_input_image(flags.input_img)
     if model is None:
-        model = B.load_model(flags.cfg, flags.ckpt, device=flags.device)
+        model = load_model(flags.cfg, flags.ckpt, device=flags.device, lora=getattr(flags, "lora", None),
+                           lora_scale=getattr(flags, "lora_scale", 1.0))
     assert isinstance(model, SyncMultiviewDiffusion)
     Path(flags.output_dir).mkdir(exist_ok=True, parents=True)
     if flags.sampler == "ddim":

@@ -15,6 +15,7 @@ import torch.nn as nn
 
 from .engine import Engine
 from .schedule import SOLVERS, DDIMSchedule, DPMSolverSchedule
+from .lora import check_rank, init_adapters, is_target_shape, merge_lora, pack_lora, select_targets, unpack_lora
 from .spec import UNetConfig, VolumeConfig
 
 
@@ -338,7 +339,7 @@ class SyncMultiviewDiffusion(nn.Module):
                  clip_image_encoder_path=None, sample_type="ddim", sample_steps=50, target_elevation=30,
                  first_stage_model=None, clip_image_encoder=None, device="cuda:0", workspace_gb=16.0, precision_level=3,
                  train_mode=False, loss_scale=65536.0, recompute=True, first_stage_precision="exact", use_ema=False,
-                 ema_decay=0.9999, deterministic=False):
+                 ema_decay=0.9999, deterministic=False, lora_rank=None, lora_alpha=None, lora_targets=None):
         """train_mode / loss_scale / recompute are not reference kwargs: train_mode keeps fp32 master parameters, gradients and
         Adam moments in the engine (training_step runs the backward pass); loss_scale multiplies dL/dpred so that the fp16 MFMA
         operands of the backward pass stay in range (un-done by the optimiser); recompute = per-block activation checkpointing
@@ -352,13 +353,20 @@ class SyncMultiviewDiffusion(nn.Module):
         deterministic (needs train_mode; also settable later as ``model.deterministic``): the conditioner's backward runs its
         three gather adjoints without floating-point atomics, so that identical steps give bit-identical gradients -- conditioner
         parameters included -- and a run can be replayed or resumed bit for bit.  Explicit: torch's global
-        ``use_deterministic_algorithms`` flag is not consulted."""
+        ``use_deterministic_algorithms`` flag is not consulted.
+        lora_rank / lora_alpha / lora_targets (need train_mode): ``enable_lora`` with these at the end of every load_state_dict."""
         if first_stage_precision not in ("fast", "exact"):
             raise ValueError("first_stage_precision must be 'fast' or 'exact'")
         if use_ema and not train_mode:
             raise ValueError("use_ema=True needs train_mode=True: the EMA weights are updated by the optimiser step")
         if deterministic and not train_mode:
             raise ValueError("deterministic=True needs train_mode=True: the mode selects kernels of the backward pass")
+        if lora_rank is not None:
+            if not train_mode:
+                raise ValueError("lora_rank needs train_mode=True (inference merges adapters: load_state_dict(sd, lora=...))")
+            if use_ema:
+                raise ValueError("use_ema=True together with LoRA: an EMA of adapters is not implemented")
+            check_rank(lora_rank)
         if use_spatial_volume and train_mode:
             raise NotImplementedError("train_mode=True with use_spatial_volume=True: SpatialTime3DNet has no backward pass in the "
                                       "engine (a forward-only training_step(..., backward=False) works without train_mode)")
@@ -372,6 +380,7 @@ class SyncMultiviewDiffusion(nn.Module):
         self.recompute = bool(recompute)
         self.use_ema = bool(use_ema)
         self.ema_decay = float(ema_decay)
+        self._lora_kw = None if lora_rank is None else dict(rank=lora_rank, alpha=lora_alpha, targets=lora_targets)
         self.ema_num_updates = 0  # LitEma.num_updates: advanced by every optimiser step that is not skipped
         self.gradient_clip_val = None  # Lightning's Trainer(gradient_clip_val=...): configure_optimizers passes it to ArenaAdamW
         self.global_step = 0
@@ -425,9 +434,14 @@ class SyncMultiviewDiffusion(nn.Module):
         if bool(on) != self.engine.deterministic:
             self.engine.train_set_deterministic(on)
 
-    def load_state_dict(self, state_dict, strict=False):
+    def load_state_dict(self, state_dict, strict=False, lora=None, lora_scale=1.0):
         """generate_face.py:76 calls this with strict=False on ``ckpt['state_dict']``; returns torch's
-        (missing_keys, unexpected_keys) pair w.r.t. the keys the denoising path consumes."""
+        (missing_keys, unexpected_keys) pair w.r.t. the keys the denoising path consumes.
+        lora (an adapter file's dict or path, ``save_lora``) / lora_scale: the adapters are merged into the weights on the host
+        first (``merge_lora``), at that strength -- the engine then packs and runs an ordinary model.  (Adapters that should stay
+        trainable are loaded with ``load_lora`` instead.)"""
+        if lora is not None:
+            state_dict = merge_lora(state_dict, lora, lora_scale)
         self.spatial_volume.invalidate()
         inc = self.engine.load_state_dict(state_dict, strict=strict)
         self.model.diffusion_model._keep_trainable(state_dict, "model.diffusion_model.")
@@ -441,7 +455,78 @@ class SyncMultiviewDiffusion(nn.Module):
                     ema[off:off + numel].copy_(t.detach().reshape(-1).to(device=ema.device, dtype=torch.float32))
             n = state_dict.get("model_ema.num_updates")
             self.ema_num_updates = max(0, int(n)) if n is not None else 0
+        if self._lora_kw is not None:
+            self.enable_lora(**self._lora_kw)
         return inc
+
+    # ---- LoRA fine-tuning ----------------------------------------------------------------------------------------------
+    @property
+    def lora_enabled(self):
+        return bool(getattr(self.engine, "lora_rank", 0))
+
+    def enable_lora(self, rank=8, alpha=None, targets=None, seed=0):
+        """Low-rank adapters on UNet weights (after load_state_dict, train_mode only): W = W0 + (alpha / rank) B A with
+        A [rank, in] ~ U(-1/sqrt(in), 1/sqrt(in)) (one generator seeded with ``seed``, keys in sorted order) and B = 0, so the
+        model starts as the loaded one.  targets: fnmatch patterns over the UNet's keys (default: the SpatialTransformers' attn1 /
+        attn2 to_q / to_k / to_v / to_out.0 weights); alpha defaults to rank.  From here on configure_optimizers() returns a
+        LoraAdamW whose only parameters are the adapters: the base UNet, time_embed and the conditioner are frozen
+        (finetune_unet is ignored), training_step is unchanged, state_dict() carries the MERGED weights (a complete stand-alone
+        checkpoint), lora_state_dict() / save_lora() the few MB of adapters."""
+        if not self.train_mode:
+            raise RuntimeError("enable_lora needs the model created with train_mode=True (inference: load_state_dict(sd, lora=...))")
+        if self.use_ema:
+            raise ValueError("use_ema=True together with LoRA: an EMA of adapters is not implemented")
+        eng = self.engine
+        if not getattr(eng, "_loaded", False):
+            raise RuntimeError("enable_lora: call load_state_dict first")
+        rank = check_rank(rank)
+        alpha = float(rank if alpha is None else alpha)
+        shapes = {k: s_ for k, (_, _, s_) in eng.param_table.items()}
+        keys = select_targets(shapes, targets)
+        eng.lora_attach(keys, rank, alpha)
+        for k, (a, b) in init_adapters(keys, shapes, rank, seed).items():
+            eng.lora_view(k, "A").copy_(a)
+            eng.lora_view(k, "B").copy_(b)
+        return keys
+
+    def disable_lora(self, keep_merged=False):
+        """Drops the adapters: the masters go back to the base weights W0 (keep_merged=True: they stay W0 + s B A, which from
+        then on is an ordinary, fully trainable model); configure_optimizers() returns ArenaAdamW again."""
+        if self.lora_enabled:
+            self.engine.lora_detach(keep_merged)
+        self._lora_kw = None
+
+    def lora_state_dict(self):
+        """The adapter file's contents: ``lora.<state_dict key>.A`` / ``.B`` per target, ``lora.rank``, ``lora.alpha`` (CPU)."""
+        if not self.lora_enabled:
+            raise RuntimeError("lora_state_dict: LoRA is not enabled (enable_lora)")
+        eng = self.engine
+        return pack_lora({k: (eng.lora_view(k, "A"), eng.lora_view(k, "B")) for k in eng.lora_table}, eng.lora_rank, eng.lora_alpha)
+
+    def save_lora(self, path):
+        torch.save(self.lora_state_dict(), path)
+
+    def load_lora(self, lora):
+        """Adapters of ``save_lora`` (a dict or a path) into this training model, still trainable: LoRA is enabled on the file's
+        targets with its rank and alpha (an enabled model with other targets starts over from its base weights), A / B are
+        copied in and merged on the device.  Optimiser moments travel with the optimiser's own state_dict."""
+        adapters, rank, alpha = unpack_lora(lora)
+        if not self.train_mode:
+            raise RuntimeError("load_lora needs train_mode=True (inference: load_state_dict(sd, lora=...))")
+        if self.use_ema:
+            raise ValueError("use_ema=True together with LoRA: an EMA of adapters is not implemented")
+        eng = self.engine
+        for k, (a, b) in adapters.items():
+            if k not in eng.param_table or not is_target_shape(eng.param_table[k][2]) or \
+                    tuple(eng.param_table[k][2][:2]) != (b.shape[0], a.shape[1]):
+                raise ValueError(f"LoRA adapter for {k} does not fit this model")
+        if not (self.lora_enabled and sorted(eng.lora_table) == sorted(adapters) and eng.lora_rank == rank):
+            eng.lora_attach(sorted(adapters), rank, alpha)
+        eng.lora_alpha = alpha
+        for k, (a, b) in adapters.items():
+            eng.lora_view(k, "A").copy_(a)
+            eng.lora_view(k, "B").copy_(b)
+        eng.lora_set_scale(alpha / rank)
 
     def state_dict(self, *args, **kwargs):
         """Training mode: the checkpoint of the fine-tuned model under the reference's keys (Engine.export_state_dict) -- what
@@ -629,6 +714,12 @@ class SyncMultiviewDiffusion(nn.Module):
         print(f"setting learning rate to {lr:.4f} ...")
         if not self.train_mode:
             raise RuntimeError("configure_optimizers needs the model created with train_mode=True")
+        if self.lora_enabled:  # the adapters are the only parameters; everything else is frozen
+            opt = LoraAdamW(self, lr=lr, max_grad_norm=self.gradient_clip_val)
+            if self.scheduler_config is None:
+                return [opt], []
+            sched = LambdaLinearScheduler(**self.scheduler_config.get("params", {}))
+            return [opt], [{"scheduler": LambdaLR(opt, lr_lambda=sched.schedule), "interval": "step", "frequency": 1}]
         dm = self.model.diffusion_model
         unet = [p_ for _, p_ in dm.named_parameters_all()] if self.finetune_unet else self.model.get_trainable_parameters()
         eng = self.engine
@@ -911,9 +1002,7 @@ class ArenaAdamW(torch.optim.Optimizer):
         use_ema = getattr(m, "use_ema", False)
         ema = ema_decay_at(m.ema_decay, m.ema_num_updates + 1) if use_ema else None  # LitEma: num_updates += 1, then the decay
         extra = {k: v for k, v in (("max_grad_norm", self.max_grad_norm), ("ema_decay", ema)) if v is not None}
-        skipped = m.engine.adamw_step(g0["lr"], aux, self.steps_done + 1, betas=g0["betas"], eps=g0["eps"],
-                                      weight_decay=g0["weight_decay"], inv_scale=1.0 / m.loss_scale,
-                                      finetune_unet=m.finetune_unet, check=self.dynamic_scale, **extra)
+        skipped = self._update(g0, aux, extra)
         if self.max_grad_norm is not None:
             self.last_grad_norm = m.engine.last_grad_norm
         if use_ema and not skipped:
@@ -930,6 +1019,12 @@ class ArenaAdamW(torch.optim.Optimizer):
                 self._clean = 0
                 m.loss_scale = min(m.loss_scale * 2.0, 2.0 ** 24)
         return loss
+
+    def _update(self, g0, aux, extra):
+        m = self.model
+        return m.engine.adamw_step(g0["lr"], aux, self.steps_done + 1, betas=g0["betas"], eps=g0["eps"],
+                                   weight_decay=g0["weight_decay"], inv_scale=1.0 / m.loss_scale,
+                                   finetune_unet=m.finetune_unet, check=self.dynamic_scale, **extra)
 
     def zero_grad(self, set_to_none=False):
         self.model.engine.zero_grad()  # the .grad views stay attached to the (now zero) arena
@@ -990,6 +1085,58 @@ class ArenaAdamW(torch.optim.Optimizer):
         self.model.loss_scale = float(arena["loss_scale"])  # dynamic_scale follows it (property)
         if "max_grad_norm" in arena:  # (a checkpoint from before clipping existed keeps this optimiser's setting)
             self.max_grad_norm = None if arena["max_grad_norm"] is None else float(arena["max_grad_norm"])
+
+
+class LoraAdamW(ArenaAdamW):
+    """ArenaAdamW for a model with LoRA enabled: the only parameters are the adapters (nn.Parameter views of the engine's adapter
+    arena, ``.grad`` views of its gradient arena, one group, one learning rate).  step() = mvd_lora_step -- the dense gradients
+    of the backward pass projected onto the adapters, the norm pass, the fused AdamW kernel on the adapter arenas, W0 + s B A
+    merged back into the masters -- + the re-pack.  Clipping (max_grad_norm, over the adapter gradients), dynamic loss scaling,
+    ``last_grad_norm`` and LR schedulers work as in ArenaAdamW; call it after ``sync_gradients()``.  The adapter ``.grad``s are
+    valid after step() (they are written by it, not by the backward pass)."""
+
+    def __init__(self, model, lr=5e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_grad_norm=None):
+        eng = model.engine
+        if not getattr(eng, "lora_rank", 0):
+            raise RuntimeError("LoraAdamW needs a model with LoRA enabled (enable_lora)")
+        params = []
+        for k in sorted(eng.lora_table):
+            for which in ("A", "B"):
+                p_ = nn.Parameter(eng.lora_view(k, which), requires_grad=True)
+                p_.grad = eng.lora_view(k, which, grad=True)
+                params.append(p_)
+        super().__init__(model, params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+
+    def _update(self, g0, aux, extra):
+        m = self.model
+        return m.engine.lora_step(g0["lr"], self.steps_done + 1, betas=g0["betas"], eps=g0["eps"], weight_decay=g0["weight_decay"],
+                                  inv_scale=1.0 / m.loss_scale, check=self.dynamic_scale, max_grad_norm=self.max_grad_norm)
+
+    def state_dict(self):
+        sd = torch.optim.Optimizer.state_dict(self)
+        eng = self.model.engine
+        sd["arena"] = {"exp_avg": eng.lora_m.detach().clone(), "exp_avg_sq": eng.lora_v.detach().clone(),
+                       "step": self.steps_done, "steps_skipped": self.steps_skipped, "clean_steps": self._clean,
+                       "loss_scale": float(self.model.loss_scale), "numel": int(eng.lora_params.numel()),
+                       "max_grad_norm": self.max_grad_norm, "lora_rank": int(eng.lora_rank)}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        arena = state_dict.get("arena")
+        eng = self.model.engine
+        if arena is None or "lora_rank" not in arena:
+            raise ValueError("LoraAdamW: not the state_dict of a LoraAdamW")
+        if int(arena["numel"]) != eng.lora_params.numel() or int(arena["lora_rank"]) != eng.lora_rank:
+            raise ValueError(f"LoraAdamW: checkpoint adapters (rank {arena['lora_rank']}, {arena['numel']} elements) do not match "
+                             f"this model's (rank {eng.lora_rank}, {eng.lora_params.numel()})")
+        torch.optim.Optimizer.load_state_dict(self, {k: v for k, v in state_dict.items() if k != "arena"})
+        eng.lora_m.copy_(arena["exp_avg"].to(eng.lora_m.device))  # in place: the library holds these pointers
+        eng.lora_v.copy_(arena["exp_avg_sq"].to(eng.lora_v.device))
+        self.steps_done = int(arena["step"])
+        self.steps_skipped = int(arena.get("steps_skipped", 0))
+        self._clean = int(arena.get("clean_steps", 0))
+        self.model.loss_scale = float(arena["loss_scale"])
+        self.max_grad_norm = None if arena["max_grad_norm"] is None else float(arena["max_grad_norm"])
 
 
 class LambdaLinearScheduler:
