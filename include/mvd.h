@@ -296,6 +296,35 @@ int mvd_train_unet_step(mvd_ctx* ctx, const float* x, const int64_t* timesteps, 
                         const float* src1, const float* src2, const float* src3, int depth0, const float* target, float loss_scale,
                         int recompute, float* pred_out, float* loss_out, float* dsrc0, float* dsrc1, float* dsrc2, float* dsrc3,
                         void* stream);
+/* Loss options of the training step (not in the reference, whose objective is the plain mean above): sample weights (Min-SNR),
+ * a pixel weight (foreground mask), a Huber branch, and per-sample read-outs.  With d = pred - target in fp32:
+ *     rho(d) = d^2,  rho'(d) = 2 d                                        loss_type 0 (l2), and 1 (huber) where |d| <= huber_delta
+ *     rho(d) = 2 delta |d| - delta^2,  rho'(d) = 2 delta sign(d)          loss_type 1 where |d| > huber_delta
+ *   (twice torch's huber_loss, so that it IS l2 inside the threshold; |d| == delta takes the quadratic branch)
+ *     a_b   = sum_hw m[b,h,w]                                             m = pixel_w >= 0, NULL = 1
+ *     l_b   = sum_{c,h,w} m[b,h,w] rho(d[b,c,h,w]) / (C a_b)              a_b == 0: l_b = 0 and the sample's gradient is exactly 0
+ *     L     = (1/B) sum_b w_b l_b                                         w = sample_w, NULL = 1; all NULL and l2: mean(d^2)
+ *     dpred = c_b m[b,h,w] rho'(d)/2,  c_b = ((2 loss_scale) w_b) / ((float)(B C) a_b)   in fp32, in this order: a power-of-two
+ *                                                                         change of w or loss_scale changes dpred exactly
+ *     mse_b = mean_{c,h,w} d^2                                            unweighted, unmasked: what is logged / validated on
+ * One fused kernel between an area pass (only with pixel_w) and a finalise launch (csrc/k_loss.hip): pred and target are read
+ * once, sums are double partials combined in an order that depends on (B, HW, C) alone, no atomics -- two calls agree bit for bit.
+ * Negative or non-finite weights are NOT checked (the weights live on the device): they give what the formulas give.
+ *   mvd_train_unet_step_ex   mvd_train_unet_step with that loss stage.  sample_w [B], pixel_w [B,1,s,s] (device, either may be
+ *                            NULL); loss_out receives L; loss_per_sample / mse_per_sample (device, B floats, either may be NULL)
+ *                            receive l_b / mse_b.  loss_type outside {0, 1}, or huber_delta <= 0 with huber, is an error and
+ *                            launches nothing.  mvd_train_unet_step itself is unchanged and keeps its own two loss kernels.
+ *   mvd_op_train_loss        the loss stage alone on raw channels-last device buffers, no context: pred / target [B,HW,C],
+ *                            pixel_w [B,HW], dpred [B,HW,C] (NULL: forward only -- the held-out loss), loss_out (1 float, may be
+ *                            NULL).  The parity hook of the stage.  Synchronises the stream (its scratch lives for the call). */
+int mvd_train_unet_step_ex(mvd_ctx* ctx, const float* x, const int64_t* timesteps, const float* context, int B, const float* src0,
+                           const float* src1, const float* src2, const float* src3, int depth0, const float* target, float loss_scale,
+                           int recompute, const float* sample_w, const float* pixel_w, int loss_type, float huber_delta,
+                           float* pred_out, float* loss_out, float* loss_per_sample, float* mse_per_sample, float* dsrc0, float* dsrc1,
+                           float* dsrc2, float* dsrc3, void* stream);
+int mvd_op_train_loss(const float* pred, const float* target, int B, int HW, int C, const float* sample_w, const float* pixel_w,
+                      int loss_type, float huber_delta, float loss_scale, float* dpred, float* loss_out, float* loss_per_sample,
+                      float* mse_per_sample, void* stream);
 /* The conditioner's backward for ONE sample (its mesh / cameras active: mvd_select_sample): re-runs construct_spatial_volume and
  * construct_view_frustum_volume (morphable_diffusion.py:203-320: step embedding, 2-D encoder on the N noisy views, vertex gather,
  * view fusion, sparse voxel CNN in train mode, lattice gather, frustum gather and FrustumTV3DNet for the target view) with every

@@ -536,17 +536,20 @@ int mvd_train_zero_grad(mvd_ctx* c, void* stream) {
   return 0;
 }
 
-int mvd_train_unet_step(mvd_ctx* c, const float* x, const int64_t* timesteps, const float* context, int B, const float* src0,
-                        const float* src1, const float* src2, const float* src3, int depth0, const float* target, float loss_scale,
-                        int recompute, float* pred_out, float* loss_out, float* dsrc0, float* dsrc1, float* dsrc2, float* dsrc3,
-                        void* stream) {
+// mvd_train_unet_step (lo == nullptr: the plain mean squared error) and mvd_train_unet_step_ex (lo: its loss stage)
+static int train_unet_step(mvd_ctx* c, const float* x, const int64_t* timesteps, const float* context, int B, const float* src0,
+                           const float* src1, const float* src2, const float* src3, int depth0, const float* target, float loss_scale,
+                           int recompute, float* pred_out, float* loss_out, float* dsrc0, float* dsrc1, float* dsrc2, float* dsrc3,
+                           void* stream, const TrainLossOpts* lo) {
+  const std::string who = lo ? "mvd_train_unet_step_ex" : "mvd_train_unet_step";  // the entry point mvd_last_error names
   if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
   if (!c || !c->finalized) return mvd_fail("weights not finalized");
-  if (!x || !timesteps || !context || !target || !pred_out || B <= 0) return mvd_fail("mvd_train_unet_step: bad argument");
+  if (!x || !timesteps || !context || !target || !pred_out || B <= 0) return mvd_fail((who + ": bad argument").c_str());
   hipStream_t s = S(stream);
   const mvd_unet_config& u = c->u;
-  WsScope ws_scope(c);
   const int HW = u.image_size * u.image_size, cin = u.in_channels, oc = u.out_channels;
+  if (lo) RET_IF(train_loss_check(who.c_str(), B, HW, oc, lo->loss_type, lo->huber_delta));
+  WsScope ws_scope(c);
   if (cin % 8) return mvd_fail("in_channels must be a multiple of 8");
   float* xn = ws_alloc<float>(c, (size_t)B * HW * cin);
   float* eps = ws_alloc<float>(c, (size_t)B * HW * oc);
@@ -560,7 +563,7 @@ int mvd_train_unet_step(mvd_ctx* c, const float* x, const int64_t* timesteps, co
   float* dcl[4] = {nullptr, nullptr, nullptr, nullptr};
   size_t nvol[4];
   for (int l = 0; l < 4; ++l) {
-    if (!srcs[l]) return mvd_fail("mvd_train_unet_step: missing source_dict level");
+    if (!srcs[l]) return mvd_fail((who + ": missing source_dict level").c_str());
     const int sl = u.image_size >> l, Dl = depth0 >> l, C = u.volume_dims[l];
     nvol[l] = (size_t)B * Dl * sl * sl * C;
     float* t = ws_alloc<float>(c, nvol[l]);
@@ -574,7 +577,7 @@ int mvd_train_unet_step(mvd_ctx* c, const float* x, const int64_t* timesteps, co
       HIP_CHECK_RET(hipMemsetAsync(dcl[l], 0, nvol[l] * sizeof(float), s));
     }
   }
-  RET_IF(engine_train_step(c, xn, cin, timesteps, context, B, depth0, cl, tgt, loss_scale, recompute, eps, loss_out, dcl, s));
+  RET_IF(engine_train_step(c, xn, cin, timesteps, context, B, depth0, cl, tgt, loss_scale, recompute, eps, loss_out, dcl, s, lo));
   c->grad_touched[1] = true;
   RET_IF(launch_nhwc_to_nchw(eps, oc, B, oc, HW, pred_out, s));
   for (int l = 0; l < 4; ++l)
@@ -583,6 +586,40 @@ int mvd_train_unet_step(mvd_ctx* c, const float* x, const int64_t* timesteps, co
       RET_IF(launch_nhwc_to_nchw(dcl[l], C, B, C, Dl * sl * sl, douts[l], s));
     }
   return 0;
+}
+
+int mvd_train_unet_step(mvd_ctx* c, const float* x, const int64_t* timesteps, const float* context, int B, const float* src0,
+                        const float* src1, const float* src2, const float* src3, int depth0, const float* target, float loss_scale,
+                        int recompute, float* pred_out, float* loss_out, float* dsrc0, float* dsrc1, float* dsrc2, float* dsrc3,
+                        void* stream) {
+  return train_unet_step(c, x, timesteps, context, B, src0, src1, src2, src3, depth0, target, loss_scale, recompute, pred_out, loss_out,
+                         dsrc0, dsrc1, dsrc2, dsrc3, stream, nullptr);
+}
+
+int mvd_train_unet_step_ex(mvd_ctx* c, const float* x, const int64_t* timesteps, const float* context, int B, const float* src0,
+                           const float* src1, const float* src2, const float* src3, int depth0, const float* target, float loss_scale,
+                           int recompute, const float* sample_w, const float* pixel_w, int loss_type, float huber_delta,
+                           float* pred_out, float* loss_out, float* loss_per_sample, float* mse_per_sample, float* dsrc0, float* dsrc1,
+                           float* dsrc2, float* dsrc3, void* stream) {
+  // pixel_w [B,1,s,s] is the loss kernel's [B][HW] as it stands: one channel
+  const TrainLossOpts lo{sample_w, pixel_w, loss_type, huber_delta, loss_per_sample, mse_per_sample};
+  return train_unet_step(c, x, timesteps, context, B, src0, src1, src2, src3, depth0, target, loss_scale, recompute, pred_out, loss_out,
+                         dsrc0, dsrc1, dsrc2, dsrc3, stream, &lo);
+}
+
+int mvd_op_train_loss(const float* pred, const float* target, int B, int HW, int C, const float* sample_w, const float* pixel_w,
+                      int loss_type, float huber_delta, float loss_scale, float* dpred, float* loss_out, float* loss_per_sample,
+                      float* mse_per_sample, void* stream) {
+  if (!pred || !target) return mvd_fail("mvd_op_train_loss: null argument");
+  RET_IF(train_loss_check("mvd_op_train_loss", B, HW, C, loss_type, huber_delta));
+  hipStream_t s = S(stream);
+  void* scratch = nullptr;  // the areas and the partial sums live for this call only
+  HIP_CHECK_RET(hipMalloc(&scratch, train_loss_scratch_bytes(B, HW)));
+  int rc = launch_train_loss(pred, target, B, HW, C, sample_w, pixel_w, loss_type, huber_delta, loss_scale, dpred, loss_out,
+                             loss_per_sample, mse_per_sample, scratch, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_train_loss: stream synchronisation failed");
+  hipFree(scratch);
+  return rc;
 }
 
 int mvd_train_cond_backward(mvd_ctx* c, int cond_index, const float* x, const float* context, const float* d_out, int B, int H,

@@ -264,6 +264,14 @@ int launch_bn_fold(const float* gamma, const float* beta, const float* mean, con
 int launch_bn_rows_relu(const float* x, float* y, int n, int C, const float* gamma, const float* beta, float eps, float* stats_out,
                         hipStream_t s, float* rmean = nullptr, float* rvar = nullptr, float momentum = 0.f);
 int launch_mse(const float* a, const float* b, size_t n, float* out, hipStream_t s);
+// k_loss.hip: the weighted / masked / Huber training objective on channels-last [B][HW][C] (include/mvd.h: mvd_op_train_loss).
+// train_loss_check: the argument errors (0 = fine); scratch: train_loss_scratch_bytes(B, HW) bytes, 8-byte aligned, alive until the
+// launches have run.  w [B], m [B][HW], dpred and the three outputs may be null.
+size_t train_loss_scratch_bytes(int B, int HW);
+int train_loss_check(const char* who, int B, int HW, int C, int loss_type, float huber_delta);
+int launch_train_loss(const float* pred, const float* target, int B, int HW, int C, const float* w, const float* m, int loss_type,
+                      float huber_delta, float loss_scale, float* dpred, float* loss_out, float* loss_ps, float* mse_ps, void* scratch,
+                      hipStream_t s);
 int launch_latent_gather(const float* feats, const int* grid, int gd, int gh, int gw, const float* min_xyz,
                          const int* out_sh, float voxel, int V, float vol_len, float* out, hipStream_t s);
 int launch_sparse_densify(const float* feats, const int* grid, long nvox, int C, float* out, hipStream_t s);

@@ -552,11 +552,21 @@ int engine_train_conditioner_backward(mvd_ctx* c, const float* x_noisy_nchw, int
 int engine_train_conditioner_backward_batch(mvd_ctx* c, int B, const int* slots, const float* x_noisy_all, const int64_t* timesteps,
                                             const float* v_embed_all, int n_views, const int* target_idx, float* const dsrc[4],
                                             float* dbg_dvolume, float* dbg_dfused, float* dbg_dfeats, float* dbg_dtembed, hipStream_t s);
+// The loss stage of mvd_train_unet_step_ex (k_loss.hip): device pointers, each may be null; pixel_w [B][HW].  engine_train_step
+// without one runs the plain mean squared error (launch_mse + mse_grad_kernel).
+struct TrainLossOpts {
+  const float* sample_w;
+  const float* pixel_w;
+  int loss_type;  // 0 l2, 1 huber
+  float huber_delta;
+  float* loss_per_sample;
+  float* mse_per_sample;
+};
 int engine_train_cond_backward(mvd_ctx* c, int cond_idx, const float* x, const float* ctx_vol, const float* dout, int B, int H, int W,
                                int level, int depth0, float* dx, float* dctx, hipStream_t s);
 int engine_train_step(mvd_ctx* c, const float* x_nhwc, int x_ld, const int64_t* t, const float* context, int B, int depth0,
                       const Ctx5 src[4], const float* target_nhwc, float loss_scale, int recompute, float* pred_nhwc, float* loss_out,
-                      float* const dsrc[4], hipStream_t s);
+                      float* const dsrc[4], hipStream_t s, const TrainLossOpts* lo = nullptr);
 // engine_cond.hip
 // per-sample tables (mvd_set_mesh* / mvd_set_cameras* / mvd_set_samples_async / mvd_select_sample) and the host-only rule book
 int engine_set_cameras(mvd_ctx* c, const float* K, const float* RT, int N, hipStream_t s);

@@ -899,7 +899,7 @@ static std::string strip_leaf(const std::string& k) {  // "a.b.weight" -> "a.b."
 
 int engine_train_step(mvd_ctx* c, const float* x_nhwc, int x_ld, const int64_t* t, const float* context, int B, int depth0,
                       const Ctx5 src[4], const float* target_nhwc, float loss_scale, int recompute, float* pred_nhwc, float* loss_out,
-                      float* const dsrc[4], hipStream_t s) {
+                      float* const dsrc[4], hipStream_t s, const TrainLossOpts* lo) {
   if (!c->finalized || !c->has_unet) return mvd_fail("UNet weights not uploaded / finalized");
   if (!c->train_mode) return mvd_fail("training step: enable training mode (mvd_train_enable) before mvd_finalize_weights");
   const mvd_unet_config& u = c->u;
@@ -917,8 +917,14 @@ int engine_train_step(mvd_ctx* c, const float* x_nhwc, int x_ld, const int64_t* 
   (void)fwd_top;
   float* dpred = ws_alloc<float>(c, npred);
   WS_CHECK(dpred);
-  if (loss_out) RET_IF(launch_mse(target_nhwc, pred_nhwc, npred, loss_out, s));
-  {  // d mean((pred - target)^2) / d pred, times the loss scale
+  if (lo) {  // the weighted / masked / Huber objective: one fused pass writes dpred and the per-sample sums
+    void* scratch = ws_alloc<double>(c, train_loss_scratch_bytes(B, S * S) / sizeof(double));
+    WS_CHECK(scratch);
+    RET_IF(launch_train_loss(pred_nhwc, target_nhwc, B, S * S, oc, lo->sample_w, lo->pixel_w, lo->loss_type, lo->huber_delta, loss_scale,
+                             dpred, loss_out, lo->loss_per_sample, lo->mse_per_sample, scratch, s));
+  } else {
+    if (loss_out) RET_IF(launch_mse(target_nhwc, pred_nhwc, npred, loss_out, s));
+    // d mean((pred - target)^2) / d pred, times the loss scale
     const float k = 2.0f * loss_scale / (float)npred;
     const int blocks = (int)std::min<size_t>((npred + 255) / 256, 4096);
     hipLaunchKernelGGL(mse_grad_kernel, dim3(blocks), dim3(256), 0, s, pred_nhwc, target_nhwc, k, npred, dpred);

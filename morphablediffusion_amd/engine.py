@@ -19,6 +19,38 @@ def _f32(t, device):
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
+LOSS_TYPES = ("l2", "huber")  # loss_type of mvd_train_unet_step_ex / mvd_op_train_loss, by index
+
+
+def op_train_loss(pred, target, sample_weight=None, pixel_weight=None, loss_type="l2", huber_delta=1.0, loss_scale=1.0,
+                  want_grad=False, device=None, lib=None):
+    """Engine.op_train_loss without an engine (the hook takes no context): runs on ``device`` (default: pred's)."""
+    if loss_type not in LOSS_TYPES:
+        raise ValueError(f"loss_type must be one of {LOSS_TYPES}, not {loss_type!r}")
+    lib = lib or L.load()
+    dev = pred.device if device is None else device
+    p, tg = _f32(pred, dev), _f32(target, dev)
+    if p.dim() != 3 or p.shape != tg.shape:
+        raise ValueError(f"op_train_loss: pred and target must both be [B,HW,C], got {tuple(p.shape)} and {tuple(tg.shape)}")
+    B, HW, C = p.shape
+    w = None if sample_weight is None else _f32(sample_weight, dev).reshape(-1)
+    m = None if pixel_weight is None else _f32(pixel_weight, dev).reshape(B, -1)
+    if w is not None and w.numel() != B:
+        raise ValueError(f"op_train_loss: sample_weight must have {B} elements")
+    if m is not None and m.shape[1] != HW:
+        raise ValueError(f"op_train_loss: pixel_weight must be [{B},{HW}]")
+    nan = float("nan")
+    loss = torch.full((1,), nan, device=dev, dtype=torch.float32)
+    lps = torch.full((B,), nan, device=dev, dtype=torch.float32)
+    mps = torch.full((B,), nan, device=dev, dtype=torch.float32)
+    dpred = torch.full_like(p, nan) if want_grad else None
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_train_loss(L.ptr(p), L.ptr(tg), B, HW, C, L.ptr(w), L.ptr(m), LOSS_TYPES.index(loss_type),
+                                      float(huber_delta), float(loss_scale), L.ptr(dpred), L.ptr(loss), L.ptr(lps), L.ptr(mps),
+                                      _stream()))
+    return (loss[0], lps, mps, dpred) if want_grad else (loss[0], lps, mps)
+
+
 IncompatibleKeys = collections.namedtuple("IncompatibleKeys", ["missing_keys", "unexpected_keys"])
 MAX_SAMPLE_SLOTS = 64  # per-sample mesh / camera tables kept resident in the context (mvd_select_sample)
 
@@ -154,6 +186,10 @@ class Engine:
         out = torch.empty(tuple(ref.shape), device=self.device, dtype=torch.float32)
         L.check(self.lib.mvd_train_get_tensor(self._ctx, key.encode(), L.ptr(out), out.numel(), _stream()))
         return out
+
+    def train_bn_calls(self):
+        """mvd_train_bn_calls: train-mode forwards of the sparse CNN so far (each moves its BatchNorm running statistics)."""
+        return int(self.lib.mvd_train_bn_calls(self._ctx))
 
     def export_state_dict(self):
         """The loaded state_dict with every trained tensor replaced by its current value: master parameters from the arena, the
@@ -436,11 +472,17 @@ class Engine:
     def zero_grad(self):
         L.check(self.lib.mvd_train_zero_grad(self._ctx, _stream()))
 
-    def train_unet_step(self, x, timesteps, context, source_dict, target, loss_scale=1.0, recompute=False, want_dsrc=False):
+    def train_unet_step(self, x, timesteps, context, source_dict, target, loss_scale=1.0, recompute=False, want_dsrc=False,
+                        sample_weight=None, pixel_weight=None, loss_type="l2", huber_delta=1.0, per_sample=False):
         """mvd_train_unet_step: forward + MSE loss + backward through every UNet block.  Returns (pred, loss[, dsrc dict]);
-        parameter gradients (x loss_scale) are accumulated into ``flat_grads``."""
+        parameter gradients (x loss_scale) are accumulated into ``flat_grads``.
+        sample_weight [B] / pixel_weight [B,1,s,s] / loss_type "l2" | "huber" (with huber_delta) / per_sample: any of them set
+        runs mvd_train_unet_step_ex, the step with the weighted / masked / Huber loss stage (include/mvd.h); per_sample appends
+        (loss_per_sample [B], mse_per_sample [B]) to the result.  With the defaults the call is mvd_train_unet_step as before."""
         if not self.train_mode:
             raise L.MvdError("the engine was not created with train=True")
+        if loss_type not in LOSS_TYPES:
+            raise ValueError(f"loss_type must be one of {LOSS_TYPES}, not {loss_type!r}")
         dev = self.device
         B = x.shape[0]
         s = self.ucfg.image_size
@@ -453,13 +495,40 @@ class Engine:
         pred = torch.empty(B, self.ucfg.out_channels, s, s, device=dev, dtype=torch.float32)
         loss = torch.empty(1, device=dev, dtype=torch.float32)
         dsrc = [torch.empty_like(v) for v in srcs] if want_dsrc else [None] * 4
-        L.check(self.lib.mvd_train_unet_step(self._ctx, L.ptr(x), L.ptr(t), L.ptr(ctx), B, L.ptr(srcs[0]), L.ptr(srcs[1]),
-                                             L.ptr(srcs[2]), L.ptr(srcs[3]), depth0, L.ptr(tgt), loss_scale,
-                                             bool(recompute), L.ptr(pred), L.ptr(loss), L.ptr(dsrc[0]), L.ptr(dsrc[1]),
-                                             L.ptr(dsrc[2]), L.ptr(dsrc[3]), _stream()))
+        ex = sample_weight is not None or pixel_weight is not None or loss_type != "l2" or per_sample
+        extra = ()
+        if not ex:
+            L.check(self.lib.mvd_train_unet_step(self._ctx, L.ptr(x), L.ptr(t), L.ptr(ctx), B, L.ptr(srcs[0]), L.ptr(srcs[1]),
+                                                 L.ptr(srcs[2]), L.ptr(srcs[3]), depth0, L.ptr(tgt), loss_scale,
+                                                 bool(recompute), L.ptr(pred), L.ptr(loss), L.ptr(dsrc[0]), L.ptr(dsrc[1]),
+                                                 L.ptr(dsrc[2]), L.ptr(dsrc[3]), _stream()))
+        else:
+            w = None if sample_weight is None else _f32(sample_weight, dev).reshape(-1)
+            m = None if pixel_weight is None else _f32(pixel_weight, dev)
+            if w is not None and w.numel() != B:
+                raise ValueError(f"sample_weight must have {B} elements, got {tuple(sample_weight.shape)}")
+            if m is not None and tuple(m.shape) not in ((B, 1, s, s), (B, s, s)):
+                raise ValueError(f"pixel_weight must be [{B},1,{s},{s}], got {tuple(pixel_weight.shape)}")
+            lps = torch.empty(B, device=dev, dtype=torch.float32) if per_sample else None
+            mps = torch.empty(B, device=dev, dtype=torch.float32) if per_sample else None
+            L.check(self.lib.mvd_train_unet_step_ex(self._ctx, L.ptr(x), L.ptr(t), L.ptr(ctx), B, L.ptr(srcs[0]), L.ptr(srcs[1]),
+                                                    L.ptr(srcs[2]), L.ptr(srcs[3]), depth0, L.ptr(tgt), loss_scale,
+                                                    bool(recompute), L.ptr(w), L.ptr(m), LOSS_TYPES.index(loss_type),
+                                                    float(huber_delta), L.ptr(pred), L.ptr(loss), L.ptr(lps), L.ptr(mps),
+                                                    L.ptr(dsrc[0]), L.ptr(dsrc[1]), L.ptr(dsrc[2]), L.ptr(dsrc[3]), _stream()))
+            if per_sample:
+                extra = (lps, mps)
         if want_dsrc:
-            return pred, loss[0], {s >> lvl: dsrc[lvl] for lvl in range(4)}
-        return pred, loss[0]
+            return (pred, loss[0], {s >> lvl: dsrc[lvl] for lvl in range(4)}) + extra
+        return (pred, loss[0]) + extra
+
+    def op_train_loss(self, pred, target, sample_weight=None, pixel_weight=None, loss_type="l2", huber_delta=1.0, loss_scale=1.0,
+                      want_grad=False):
+        """mvd_op_train_loss: the loss stage of mvd_train_unet_step_ex alone, on channels-last buffers -- pred / target [B,HW,C],
+        sample_weight [B], pixel_weight [B,HW].  Returns (L, loss_per_sample [B], mse_per_sample [B][, dpred [B,HW,C]]); without
+        ``want_grad`` nothing but the loss is computed (the held-out loss of ``validation_loss``).  Needs no training context."""
+        return op_train_loss(pred, target, sample_weight, pixel_weight, loss_type, huber_delta, loss_scale, want_grad,
+                             device=self.device, lib=self.lib)
 
     def train_cond_backward(self, cond_index, x, context, d_out):
         """mvd_train_cond_backward (parity hook): one DepthTransformer's backward from exact inputs -> (dx, dcontext)."""

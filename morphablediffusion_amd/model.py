@@ -13,8 +13,8 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .engine import Engine
-from .schedule import SOLVERS, DDIMSchedule, DPMSolverSchedule
+from .engine import LOSS_TYPES, Engine
+from .schedule import SOLVERS, DDIMSchedule, DPMSolverSchedule, min_snr_weights
 from .lora import check_rank, init_adapters, is_target_shape, merge_lora, pack_lora, select_targets, unpack_lora
 from .spec import UNetConfig, VolumeConfig
 
@@ -161,9 +161,11 @@ class UNetWrapper(nn.Module):
             xc[:, :4] = xc[:, :4] / 0.18215
         return self.diffusion_model(torch.cat([x, xc], 1), t, clip_embed, source_dict=volume_feats)
 
-    def train_step(self, x, t, clip_embed, volume_feats, x_concat, target, drop_random=None, loss_scale=1.0, recompute=True):
+    def train_step(self, x, t, clip_embed, volume_feats, x_concat, target, drop_random=None, loss_scale=1.0, recompute=True,
+                   **loss_kw):
         """forward(is_train=True) (morphable_diffusion.py:95-130) + MSE + backward in one engine call.  Returns
-        (pred, loss, dsrc): dsrc[res] = dL/d(volume_feats[res]) * loss_scale, after the dropout mask."""
+        (pred, loss, dsrc): dsrc[res] = dL/d(volume_feats[res]) * loss_scale, after the dropout mask.  loss_kw: the loss options
+        of Engine.train_unet_step; with per_sample=True the result ends with (loss_per_sample, mse_per_sample)."""
         vm = None
         if self.drop_conditions:
             B = x.shape[0]
@@ -177,11 +179,11 @@ class UNetWrapper(nn.Module):
         if self.use_zero_123:
             xc[:, :4] = xc[:, :4] / 0.18215
         eng = self.diffusion_model._engine
-        pred, loss, dsrc = eng.train_unet_step(torch.cat([x, xc], 1), t, clip_embed, volume_feats, target, loss_scale=loss_scale,
-                                               recompute=recompute, want_dsrc=True)
+        pred, loss, dsrc, *extra = eng.train_unet_step(torch.cat([x, xc], 1), t, clip_embed, volume_feats, target,
+                                                       loss_scale=loss_scale, recompute=recompute, want_dsrc=True, **loss_kw)
         if vm is not None:  # the dropout is a multiplication by the mask: so is its adjoint
             dsrc = {k: self.drop(v, vm) for k, v in dsrc.items()}
-        return pred, loss, dsrc
+        return (pred, loss, dsrc, *extra)
 
     def predict_with_unconditional_scale(self, x, t, clip_embed, volume_feats, x_concat, unconditional_scale):
         x_ = torch.cat([x] * 2, 0)
@@ -316,6 +318,42 @@ class SpatialVolumeNet(nn.Module):
         return {k: torch.cat([o[k] for o in outs], 0) for k in outs[0]}, None
 
 
+def pool_loss_mask(m, size):
+    """A pixel weight [B,1,H,W] -> [B,1,size,size] by average pooling (H = W a multiple of size; H == size: unchanged)."""
+    if m.dim() != 4 or m.shape[1] != 1 or m.shape[2] != m.shape[3] or m.shape[2] % size:
+        raise ValueError(f"loss_mask must be [B,1,H,W] with H = W a multiple of {size}, got {tuple(m.shape)}")
+    m = m.float()
+    k = m.shape[2] // size
+    return m if k == 1 else torch.nn.functional.avg_pool2d(m, k)
+
+
+def foreground_mask(batch, target_index, size, background_weight=0.1):
+    """The pixel weight of loss_mask="foreground": [B,1,size,size], in torch on the batch's device.  fg is 1 where the chosen
+    target view ``batch["target_image"][b, target_index[b]]`` ([B,N,H,W,3], values in [-1, 1]) is not white background -- a pixel
+    is background iff all three channels are >= 1 - 2/255 -- or ``batch["target_mask"][b, target_index[b]]`` ([B,N,H,W] in [0, 1])
+    when the batch has one; the weight background_weight + (1 - background_weight) fg is average-pooled down to the latent grid.
+    No random draw."""
+    if batch is None or (batch.get("target_mask") is None and batch.get("target_image") is None):
+        raise ValueError("loss_mask='foreground' needs batch['target_image'] or batch['target_mask']")
+    idx = torch.as_tensor(target_index).reshape(-1).long()
+    if batch.get("target_mask") is not None:
+        tm = batch["target_mask"]
+        fg = tm[torch.arange(tm.shape[0], device=tm.device), idx.to(tm.device)].float()
+    else:
+        ti = batch["target_image"]
+        view = ti[torch.arange(ti.shape[0], device=ti.device), idx.to(ti.device)].float()  # [B,H,W,3]
+        fg = 1.0 - (view >= 1.0 - 2.0 / 255.0).all(-1).float()
+    # the weight is affine in fg, so pooling fg first is the same average -- and an all-background view gives background_weight
+    # itself, not a rounded sum of 64 copies of it
+    bw = float(background_weight)
+    return bw + (1.0 - bw) * pool_loss_mask(fg[:, None], size)
+
+
+def _channels_last(x):
+    """[B,C,h,w] -> [B,h*w,C], the layout of the loss stage (Engine.op_train_loss)."""
+    return x.permute(0, 2, 3, 1).reshape(x.shape[0], -1, x.shape[1]).contiguous()
+
+
 def ema_key(key):
     """Checkpoint key of a parameter's EMA shadow: LitEma's rule (ldm/modules/ema.py -- the module-relative name with every '.'
     deleted, registered under ``model_ema``), e.g. model.diffusion_model.input_blocks.0.0.weight ->
@@ -339,7 +377,8 @@ class SyncMultiviewDiffusion(nn.Module):
                  clip_image_encoder_path=None, sample_type="ddim", sample_steps=50, target_elevation=30,
                  first_stage_model=None, clip_image_encoder=None, device="cuda:0", workspace_gb=16.0, precision_level=3,
                  train_mode=False, loss_scale=65536.0, recompute=True, first_stage_precision="exact", use_ema=False,
-                 ema_decay=0.9999, deterministic=False, lora_rank=None, lora_alpha=None, lora_targets=None):
+                 ema_decay=0.9999, deterministic=False, lora_rank=None, lora_alpha=None, lora_targets=None, loss_weighting=None,
+                 snr_gamma=5.0, loss_type="l2", huber_delta=1.0, loss_mask=None, background_weight=0.1):
         """train_mode / loss_scale / recompute are not reference kwargs: train_mode keeps fp32 master parameters, gradients and
         Adam moments in the engine (training_step runs the backward pass); loss_scale multiplies dL/dpred so that the fp16 MFMA
         operands of the backward pass stay in range (un-done by the optimiser); recompute = per-block activation checkpointing
@@ -354,7 +393,13 @@ class SyncMultiviewDiffusion(nn.Module):
         three gather adjoints without floating-point atomics, so that identical steps give bit-identical gradients -- conditioner
         parameters included -- and a run can be replayed or resumed bit for bit.  Explicit: torch's global
         ``use_deterministic_algorithms`` flag is not consulted.
-        lora_rank / lora_alpha / lora_targets (need train_mode): ``enable_lora`` with these at the end of every load_state_dict."""
+        lora_rank / lora_alpha / lora_targets (need train_mode): ``enable_lora`` with these at the end of every load_state_dict.
+        Loss options (none is a reference kwarg; all off by default, all plain attributes that may be changed between steps; a
+        backward pass with one of them on needs train_mode).  loss_weighting="min_snr" with snr_gamma: every sample's loss is
+        weighted by min(SNR_t, gamma) / SNR_t (schedule.min_snr_weights).  loss_type="huber" with huber_delta: quadratic up to
+        |pred - target| = delta, linear beyond.  loss_mask="foreground" with background_weight: a per-pixel weight derived from
+        the target view (``foreground_mask``), 1 on the subject and background_weight on the white background, normalised by
+        its area per sample.  The definitions are in include/mvd.h (mvd_train_unet_step_ex)."""
         if first_stage_precision not in ("fast", "exact"):
             raise ValueError("first_stage_precision must be 'fast' or 'exact'")
         if use_ema and not train_mode:
@@ -371,6 +416,12 @@ class SyncMultiviewDiffusion(nn.Module):
             raise NotImplementedError("train_mode=True with use_spatial_volume=True: SpatialTime3DNet has no backward pass in the "
                                       "engine (a forward-only training_step(..., backward=False) works without train_mode)")
         super().__init__()
+        self.loss_weighting, self.snr_gamma = loss_weighting, snr_gamma
+        self.loss_type, self.huber_delta = loss_type, huber_delta
+        self.loss_mask, self.background_weight = loss_mask, background_weight
+        self.log_per_sample = False  # keep last_loss_per_sample / last_mse_per_sample even when no loss option is on
+        self.last_loss_per_sample = self.last_mse_per_sample = None
+        self._check_loss_options()
         self.finetune_unet = finetune_unet
         self.scheduler_config = scheduler_config
         self.learning_rate = 5e-5  # train_morphable_diffusion.py:313-321 sets model.learning_rate before fit
@@ -637,8 +688,49 @@ class SyncMultiviewDiffusion(nn.Module):
         x_noisy = ac.sqrt()[t].view(shape) * x_start + (1.0 - ac).sqrt()[t].view(shape) * noise
         return x_noisy, noise
 
+    def _check_loss_options(self):
+        if self.loss_weighting not in (None, "min_snr"):
+            raise ValueError(f"loss_weighting must be None or 'min_snr', not {self.loss_weighting!r}")
+        if self.loss_type not in LOSS_TYPES:
+            raise ValueError(f"loss_type must be one of {LOSS_TYPES}, not {self.loss_type!r}")
+        if self.loss_mask not in (None, "foreground"):
+            raise ValueError(f"loss_mask must be None or 'foreground', not {self.loss_mask!r}")
+        if self.loss_weighting == "min_snr" and not float(self.snr_gamma) > 0.0:
+            raise ValueError(f"snr_gamma must be > 0, got {self.snr_gamma!r}")
+        if self.loss_type == "huber" and not float(self.huber_delta) > 0.0:
+            raise ValueError(f"huber_delta must be > 0, got {self.huber_delta!r}")
+        if self.loss_mask == "foreground" and not 0.0 <= float(self.background_weight) <= 1.0:
+            raise ValueError(f"background_weight must be in [0, 1], got {self.background_weight!r}")
+
+    def foreground_mask(self, batch, target_index, size):
+        """The pixel weight of loss_mask="foreground" for this batch: ``foreground_mask`` with self.background_weight."""
+        return foreground_mask(batch, target_index, size, self.background_weight)
+
+    def _loss_options(self, batch, time_steps, target_index, size, sample_weight, loss_mask):
+        """(on, kwargs for Engine.train_unet_step) of this step: the constructor's options and the step's explicit weights."""
+        self._check_loss_options()
+        B = time_steps.shape[0]
+        w = None
+        if self.loss_weighting == "min_snr":
+            w = min_snr_weights(self.sampler.schedule.alphas_cumprod, time_steps, self.snr_gamma)
+        if sample_weight is not None:
+            sw = torch.as_tensor(sample_weight, dtype=torch.float32).reshape(-1)
+            if sw.numel() != B:
+                raise ValueError(f"sample_weight must have shape [{B}], got {tuple(sw.shape)}")
+            w = sw.to(self.device) if w is None else w.to(self.device) * sw.to(self.device)
+        m = None
+        if loss_mask is not None:  # an explicit mask replaces the derived one
+            m = pool_loss_mask(torch.as_tensor(loss_mask), size)
+            if m.shape[0] != B:
+                raise ValueError(f"loss_mask must have {B} samples, got {tuple(m.shape)}")
+        elif self.loss_mask == "foreground":
+            m = self.foreground_mask(batch, target_index, size)
+        on = w is not None or m is not None or self.loss_type != "l2"
+        kw = dict(sample_weight=w, pixel_weight=m, loss_type=self.loss_type, huber_delta=float(self.huber_delta))
+        return on, kw
+
     def training_step(self, batch, prepared=None, time_steps=None, noise=None, target_index=None, drop_random=None,
-                      backward=None):
+                      backward=None, sample_weight=None, loss_mask=None):
         """SyncMultiviewDiffusion.training_step (morphable_diffusion.py:520-549) in the HIP engine: random time steps, prepare
         (VAE-encode the N target views + the input view, CLIP), add_noise, one random target view per sample, the 32^3 volume
         from ALL noisy views (BatchNorm in train mode), one frustum volume per sample, the UNet with condition dropout, MSE
@@ -650,10 +742,19 @@ class SyncMultiviewDiffusion(nn.Module):
         ``prepared`` = (x, clip_embed, input_info) replaces self.prepare(batch); the random draws may be passed in (parity
         tests), otherwise they are made on the host in the reference's order (randint for the time steps BEFORE prepare's
         posterior samples, then randn_like, randint, rand) so that torch.manual_seed reproduces the reference's CPU stream.
-        Returns the loss (a device scalar, no autograd graph); the prediction is kept in ``self.last_noise_predict``."""
+        Returns the loss (a device scalar, no autograd graph); the prediction is kept in ``self.last_noise_predict``.
+        Loss options (constructor): sample_weight [B] multiplies the Min-SNR weights (or stands alone), loss_mask [B,1,H,W] or
+        [B,1,h,w] replaces the derived pixel weight; neither draws random numbers, the reference's draw order is unchanged.  With
+        an option on -- or ``self.log_per_sample`` -- ``self.last_loss_per_sample`` / ``self.last_mse_per_sample`` hold the
+        weighted per-sample loss and the plain per-sample mean squared error as device tensors [B]."""
         dev = self.device
         if backward is None:
             backward = self.train_mode
+        self._check_loss_options()
+        if backward and not self.train_mode and (self.loss_weighting is not None or self.loss_type != "l2" or
+                                                 self.loss_mask is not None or sample_weight is not None or
+                                                 loss_mask is not None):
+            raise ValueError("a loss option with a backward pass needs the model created with train_mode=True")
         B = batch["target_image"].shape[0] if prepared is None else prepared[0].shape[0]
         if time_steps is None:  # drawn first, as the reference does (:521-522)
             time_steps = torch.randint(0, self.num_timesteps, (B,)).long()
@@ -665,6 +766,11 @@ class SyncMultiviewDiffusion(nn.Module):
             target_index = torch.randint(0, N, (B, 1)).long()
         if drop_random is None and self.model.drop_conditions:
             drop_random = torch.rand(B, dtype=torch.float32)
+        # the step's weights, from the draws as they are (host tensors unless the caller passed device ones): nothing is copied
+        # back from the device, and a bad mask raises before anything is launched
+        on, loss_kw = self._loss_options(batch, time_steps, target_index, x.shape[-1], sample_weight, loss_mask)
+        keep = on or self.log_per_sample
+        self.last_loss_per_sample = self.last_mse_per_sample = None
         time_steps, target_index = time_steps.to(dev), target_index.to(dev)
         x_noisy, noise = self.add_noise(x.to(dev), time_steps, noise.to(dev))
         was_training = self.training
@@ -683,9 +789,18 @@ class SyncMultiviewDiffusion(nn.Module):
         if not backward:
             pred = self.model(x_t, time_steps, clip_, vf, xc, is_train=True, drop_random=drop_random)
             self.last_noise_predict = pred
-            return self.engine.mse_loss(target, pred)
-        pred, loss, dsrc = self.model.train_step(x_t, time_steps, clip_, vf, xc, target, drop_random=drop_random,
-                                                 loss_scale=self.loss_scale, recompute=self.recompute)
+            if not keep:
+                return self.engine.mse_loss(target, pred)
+            loss, self.last_loss_per_sample, self.last_mse_per_sample = self.engine.op_train_loss(
+                _channels_last(pred), _channels_last(target), **loss_kw)
+            return loss
+        if keep:
+            pred, loss, dsrc, self.last_loss_per_sample, self.last_mse_per_sample = self.model.train_step(
+                x_t, time_steps, clip_, vf, xc, target, drop_random=drop_random, loss_scale=self.loss_scale,
+                recompute=self.recompute, per_sample=True, **loss_kw)
+        else:
+            pred, loss, dsrc = self.model.train_step(x_t, time_steps, clip_, vf, xc, target, drop_random=drop_random,
+                                                     loss_scale=self.loss_scale, recompute=self.recompute)
         self.last_noise_predict, self.last_dsrc = pred, dsrc
         self._start_grad_sync()  # DDP: the UNet's buckets are reduced while the rest of the backward runs
         if self.train_conditioner:  # spatial_volume.* / time_embed.*: per sample, from dL/d(its frustum volumes)
@@ -781,6 +896,52 @@ class SyncMultiviewDiffusion(nn.Module):
         else:  # CPU stand-ins of the engine (tests): no streams, the buckets are reduced in order
             self._grad_sync = BucketedGradSync(eng.flat_grads, eng.grad_buckets())
         self._grad_sync.start()
+
+    @torch.no_grad()
+    def validation_loss(self, batch, timesteps=(100, 300, 500, 700, 900), seed=0, target_index=None, prepared=None):
+        """Held-out loss: the plain per-sample mean squared error of the noise prediction at fixed timesteps, forward only and
+        without side effects -- the number to stop a fine-tuning run on.  The module runs in eval mode (the sparse CNN's
+        BatchNorm layers use their running statistics and do not move them; the previous mode is restored), no condition
+        dropout, the EMA weights inside ``ema_scope()`` when use_ema.  The noise comes from a CPU generator of its own seeded with
+        ``seed``; prepare's posterior samples come from the default CPU generator, seeded with ``seed`` for the call and put back
+        afterwards; no device generator is seeded or drawn from: the global random streams, CPU and GPU, are left where they
+        were.  The target view is ``target_index``
+        ([B] or [B,1]) or view 0 of every sample.  ``prepared`` = (x, clip_embed, input_info) replaces self.prepare(batch).
+        Works on an inference model too.  Returns {"per_timestep": {t: mse_b [B] on the device}, "mean": float}."""
+        import contextlib
+        dev = self.device
+        if prepared is None:
+            with torch.random.fork_rng(devices=[]):  # saves and restores the default CPU generator, the only one touched:
+                torch.default_generator.manual_seed(int(seed))  # (torch.manual_seed would re-seed every device generator too)
+                prepared = self.prepare(batch, encode_targets=True)
+        x, clip_embed, input_info = prepared
+        x = x.to(dev)
+        B, N = x.shape[:2]
+        noise = torch.randn(x.shape, generator=torch.Generator().manual_seed(int(seed))).to(dev)
+        if target_index is None:
+            target_index = torch.zeros(B, 1, dtype=torch.long)
+        target_index = torch.as_tensor(target_index).long().reshape(B, 1).to(dev)
+        ar = torch.arange(B, device=dev)[:, None]
+        target = _channels_last(noise[ar, target_index][:, 0])
+        v_embed = self.get_viewpoint_embedding(batch).to(dev)
+        was_training = self.training
+        self.eval()
+        out = {}
+        try:
+            with self.ema_scope() if self.use_ema else contextlib.nullcontext():
+                for t in timesteps:
+                    ts = torch.full((B,), int(t), dtype=torch.long, device=dev)
+                    x_noisy, _ = self.add_noise(x, ts, noise)
+                    t_embed = self.embed_time(ts)
+                    sv = self.spatial_volume.construct_spatial_volume(x_noisy, t_embed, v_embed, batch)
+                    clip_, vf, xc = self.get_target_view_feats(input_info["x"].to(dev), sv, clip_embed.to(dev), t_embed, v_embed,
+                                                               target_index, batch)
+                    pred = self.model(x_noisy[ar, target_index][:, 0], ts, clip_, vf, xc, is_train=False)
+                    out[int(t)] = self.engine.op_train_loss(_channels_last(pred), target)[2]
+        finally:
+            self.train(was_training)
+        mean = float(torch.stack(list(out.values())).double().mean()) if out else float("nan")
+        return {"per_timestep": out, "mean": mean}
 
     @torch.no_grad()
     def validation_step(self, batch, batch_idx):

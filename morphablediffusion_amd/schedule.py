@@ -112,3 +112,18 @@ class DPMSolverSchedule:
     def coefficients(self, i):
         """(s1m, sqrt_at, c_x, c_d, c_c, c_n) of step i as python floats (fp32 values)."""
         return tuple(float(v) for v in self.rows[i])
+
+
+# ---- loss weighting ---------------------------------------------------------------------------------------------------
+def min_snr_weights(alphas_cumprod, t, gamma):
+    """Min-SNR-gamma loss weights (Hang et al. 2023, "Efficient Diffusion Training via Min-SNR Weighting Strategy") of the
+    eps-prediction objective: min(SNR_t, gamma) / SNR_t with SNR = abar / (1 - abar).  1 where SNR_t <= gamma (the noisy steps),
+    gamma / SNR_t < 1 on the low-noise steps that dominate a uniform-timestep mean squared error.  Computed in float64 from the
+    schedule's abar table, returned as float32 on t's device."""
+    gamma = float(gamma)
+    if not gamma > 0.0:
+        raise ValueError(f"min_snr_weights: gamma must be > 0, got {gamma!r}")
+    t = torch.as_tensor(t)
+    ac = torch.as_tensor(alphas_cumprod).detach().double().cpu()[t.detach().long().cpu()]
+    snr = ac / (1.0 - ac)
+    return (torch.clamp(snr, max=gamma) / snr).float().to(t.device)
