@@ -535,6 +535,38 @@ int mvd_op_lora_project_grouped(const float* dW, const float* A, const float* B,
 int mvd_op_lora_merge_grouped(const float* W0, const float* A, const float* B, int n, const int64_t* w_off, const int64_t* w0_off,
                               const int64_t* out, const int64_t* in, const int64_t* a_off, const int64_t* b_off, int r, float scale,
                               float* W, void* stream);
+/* The sparse voxel CNN's kernels (csrc/k_cond.hip, k_cond_bwd.hip) one at a time on raw device buffers, no context: the parity hooks
+ * of tests/test_gpu_sparse_cnn_ops.py.  Rows are channels-last fp32; nbr [n_out][27] is a rule-book table (mvd_rulebook_table: row
+ * index of the input at tap k = (kd*3 + kh)*3 + kw, or -1).  w is the 3x3x3 kernel in one of the checkpoint layouts -- layout 0
+ * [Cout][Cin][27], 1 [Cout][27][Cin], 2 [27][Cin][Cout] -- packed here by the functions that pack a loaded checkpoint.  form 0 is the
+ * one-site-per-workgroup kernel, form 1 the matrix-core kernel; form 1 with channel counts that kernel does not take is an
+ * error, never a fall-back.  A bad argument returns an error and launches nothing.  Every hook synchronises the stream (its
+ * scratch lives for the call).
+ *   mvd_op_sparse_conv        ONE production launch of the layer: in [n_in][Cin] -> out [n_out][Cout].  scale / shift (both or
+ *                             neither) [Cout]: out = relu(conv * scale + shift), the eval path's folded BatchNorm; NULL: the raw
+ *                             conv output of the train path.
+ *   mvd_op_bn_rows_relu       train-mode BatchNorm1d (batch statistics, biased variance) + ReLU over x [n][C] -> y (may be x);
+ *                             stats_out [2][C] = [mean | rstd] (may be NULL); rmean / rvar [C] (both or neither): the running
+ *                             statistics, updated with `momentum` as nn.BatchNorm1d does.  MVD_BN_LOOP selects the looped form.
+ *   mvd_op_bn_rows_relu_bwd   its backward: xraw [n][C] the forward's input, stats what the forward wrote, dy [n][C] =
+ *                             dL/d(output) on entry and dL/d(xraw) on return; dgamma / dbeta [C] are ADDED to.  C must divide 256.
+ *   mvd_op_sparse_conv_bwd    the backward of ONE layer as the conditioner's backward runs it per layer: in [n_in][Cin] the
+ *                             layer's input, d_out [n_out][Cout] (form 1 with level0_subm: the duplicate fold rewrites it in
+ *                             place) -> d_in [n_in][Cin] written, the weight gradient ADDED to gw, laid out like w.  strided: the
+ *                             stride-2 layer (data gradient through the inverse table), else submanifold (n_in == n_out; tap
+ *                             flip).  level0_subm (form 1): nbr may hold duplicate rows (centre tap != own row), whose
+ *                             gradients are folded into their representatives first -- with atomics, or for deterministic != 0
+ *                             in row order.  form 0 zero-fills d_in and scatters with atomics (deterministic != 0: an error).
+ * poison != 0: the hook's scratch (partial sums, inverse table, flags) is filled with 0xFF bytes before use. */
+int mvd_op_sparse_conv(const float* in, const int32_t* nbr, int n_out, int Cin, int Cout, const float* w, int layout, const float* scale,
+                       const float* shift, int form, float* out, void* stream);
+int mvd_op_bn_rows_relu(const float* x, int n, int C, const float* gamma, const float* beta, float eps, float momentum, float* y,
+                        float* stats_out, float* rmean, float* rvar, void* stream);
+int mvd_op_bn_rows_relu_bwd(const float* xraw, float* dy, int n, int C, const float* gamma, const float* beta, const float* stats,
+                            int poison, float* dgamma, float* dbeta, void* stream);
+int mvd_op_sparse_conv_bwd(const float* in, const int32_t* nbr, float* d_out, int n_in, int n_out, int Cin, int Cout, int strided,
+                           int level0_subm, int deterministic, int form, const float* w, int layout, int poison, float* d_in, float* gw,
+                           void* stream);
 int mvd_op_conv(mvd_ctx* ctx, const float* x_nchw, int B, int Cin, int H, int W, const float* w, const float* bias,
                 int Cout, int ksize, int stride, int upsample, const float* resid_nchw, float* out_nchw, int force_splitk,
                 void* stream);

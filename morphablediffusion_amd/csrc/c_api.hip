@@ -622,6 +622,104 @@ int mvd_op_train_loss(const float* pred, const float* target, int B, int HW, int
   return rc;
 }
 
+// ---- parity hooks of the sparse voxel CNN (tests/test_gpu_sparse_cnn_ops.py): no context, the caller's device buffers, scratch and
+// weight packs that live for the call (freed after the stream has been synchronised)
+namespace {
+struct OpScratch {
+  std::vector<void*> bufs;
+  ~OpScratch() {
+    for (void* b : bufs) hipFree(b);
+  }
+  // elems of 4 bytes; poison: 0xFF bytes (NaN as a float, -1 as an int) before use
+  int get(size_t elems, bool poison, hipStream_t s, void** out) {
+    void* b = nullptr;
+    if (hipMalloc(&b, std::max<size_t>(elems, 1) * 4) != hipSuccess) return mvd_fail("parity hook: scratch allocation failed");
+    bufs.push_back(b);
+    if (poison && hipMemsetAsync(b, 0xFF, std::max<size_t>(elems, 1) * 4, s) != hipSuccess) return mvd_fail("parity hook: memset failed");
+    *out = b;
+    return 0;
+  }
+};
+int op_sync(const char* who, hipStream_t s, int rc) {
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail((std::string(who) + ": stream synchronisation failed").c_str());
+  return rc;
+}
+int sparse_op_check(const char* who, int n_out, int Cin, int Cout, int layout, int form) {
+  const std::string w(who);
+  if (n_out <= 0 || Cin <= 0 || Cout <= 0 || Cin > 256 || Cout > 256) return mvd_fail((w + ": row or channel count out of range").c_str());
+  if (layout < 0 || layout > 2) return mvd_fail((w + ": weight layout 0..2").c_str());
+  if (form != 0 && form != 1) return mvd_fail((w + ": form 0 (site) or 1 (matrix-core)").c_str());
+  if (form == 1 && !sparse_mfma_takes(Cin, Cout)) return mvd_fail((w + ": no matrix-core kernel for these channel counts").c_str());
+  return 0;
+}
+}  // namespace
+
+int mvd_op_sparse_conv(const float* in, const int32_t* nbr, int n_out, int Cin, int Cout, const float* w, int layout, const float* scale,
+                       const float* shift, int form, float* out, void* stream) {
+  if (!in || !nbr || !w || !out || !scale != !shift) return mvd_fail("mvd_op_sparse_conv: null argument");
+  RET_IF(sparse_op_check("mvd_op_sparse_conv", n_out, Cin, Cout, layout, form));
+  hipStream_t s = S(stream);
+  OpScratch z;
+  const size_t nw = (size_t)27 * Cin * Cout;
+  float *wpk = nullptr, *wp = nullptr;
+  RET_IF(z.get(nw, false, s, (void**)&wpk));
+  if (form == 1) RET_IF(z.get(nw, false, s, (void**)&wp));
+  int rc = launch_sparse_w_pack(w, Cin, Cout, layout, wpk, s);
+  if (!rc && wp) rc = launch_sparse_w_frag(wpk, Cin, Cout, 0, 0, wp, s);
+  if (!rc) rc = launch_sparse_conv(in, nbr, n_out, Cin, Cout, wpk, wp, scale, shift, out, s);
+  return op_sync("mvd_op_sparse_conv", s, rc);
+}
+
+int mvd_op_bn_rows_relu(const float* x, int n, int C, const float* gamma, const float* beta, float eps, float momentum, float* y,
+                        float* stats_out, float* rmean, float* rvar, void* stream) {
+  if (!x || !y || !gamma || !beta || !rmean != !rvar) return mvd_fail("mvd_op_bn_rows_relu: null argument");
+  if (n <= 0 || C <= 0) return mvd_fail("mvd_op_bn_rows_relu: row or channel count out of range");
+  hipStream_t s = S(stream);
+  return op_sync("mvd_op_bn_rows_relu", s, launch_bn_rows_relu(x, y, n, C, gamma, beta, eps, stats_out, s, rmean, rvar, momentum));
+}
+
+int mvd_op_bn_rows_relu_bwd(const float* xraw, float* dy, int n, int C, const float* gamma, const float* beta, const float* stats,
+                            int poison, float* dgamma, float* dbeta, void* stream) {
+  if (!xraw || !dy || !gamma || !beta || !stats || !dgamma || !dbeta) return mvd_fail("mvd_op_bn_rows_relu_bwd: null argument");
+  if (n <= 0 || C <= 0) return mvd_fail("mvd_op_bn_rows_relu_bwd: row or channel count out of range");
+  if (C > 256 || 256 % C) return mvd_fail("mvd_op_bn_rows_relu_bwd: the channel count must divide 256");
+  hipStream_t s = S(stream);
+  OpScratch z;
+  float* part = nullptr;
+  RET_IF(z.get((size_t)cbwd_bn_scratch_floats(n, C), poison != 0, s, (void**)&part));
+  return op_sync("mvd_op_bn_rows_relu_bwd", s, cbwd_bn_rows_relu(xraw, dy, n, C, gamma, beta, stats, part, dgamma, dbeta, s));
+}
+
+int mvd_op_sparse_conv_bwd(const float* in, const int32_t* nbr, float* d_out, int n_in, int n_out, int Cin, int Cout, int strided,
+                           int level0_subm, int deterministic, int form, const float* w, int layout, int poison, float* d_in, float* gw,
+                           void* stream) {
+  if (!in || !nbr || !d_out || !w || !d_in || !gw) return mvd_fail("mvd_op_sparse_conv_bwd: null argument");
+  RET_IF(sparse_op_check("mvd_op_sparse_conv_bwd", n_out, Cin, Cout, layout, form));
+  if (n_in <= 0) return mvd_fail("mvd_op_sparse_conv_bwd: row or channel count out of range");
+  if (strided && level0_subm) return mvd_fail("mvd_op_sparse_conv_bwd: level0_subm is a submanifold layer");
+  if (!strided && n_in != n_out) return mvd_fail("mvd_op_sparse_conv_bwd: a submanifold layer has n_in == n_out");
+  if (form == 0 && deterministic) return mvd_fail("mvd_op_sparse_conv_bwd: the site form's data gradient adds with fp32 atomics");
+  hipStream_t s = S(stream);
+  const bool mfma = form == 1, lvl0 = mfma && level0_subm != 0, det = deterministic != 0;
+  const SparseLayerScratch q = cbwd_sparse_layer_scratch(n_in, n_out, Cin, Cout, strided != 0, lvl0, det, mfma);
+  OpScratch z;
+  const size_t nw = (size_t)27 * Cin * Cout;
+  float *wpk = nullptr, *wd = nullptr, *dwp = nullptr, *dw_part = nullptr;
+  int *flag = nullptr, *inv = nullptr;
+  RET_IF(z.get(nw, false, s, (void**)&wpk));
+  if (mfma) RET_IF(z.get(nw, false, s, (void**)&wd));
+  RET_IF(z.get(q.dwp, poison != 0, s, (void**)&dwp));
+  RET_IF(z.get(q.dw_part, poison != 0, s, (void**)&dw_part));
+  if (q.flag) RET_IF(z.get(q.flag, poison != 0, s, (void**)&flag));
+  if (q.inv) RET_IF(z.get(q.inv, poison != 0, s, (void**)&inv));
+  int rc = launch_sparse_w_pack(w, Cin, Cout, layout, wpk, s);  // the packs of build_sparse_layer (engine_weights.hip)
+  if (!rc && mfma) rc = launch_sparse_w_frag(wpk, Cout, Cin, 1, strided ? 0 : 1, wd, s);
+  if (!rc)
+    rc = cbwd_sparse_layer(in, nbr, d_out, n_in, n_out, Cin, Cout, strided != 0, lvl0, det, wpk, wd, layout, dwp, dw_part, flag, inv, d_in,
+                           gw, s);
+  return op_sync("mvd_op_sparse_conv_bwd", s, rc);
+}
+
 int mvd_train_cond_backward(mvd_ctx* c, int cond_index, const float* x, const float* context, const float* d_out, int B, int H,
                             int W, int depth0, float* dx, float* dcontext, void* stream) {
   if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");

@@ -386,6 +386,14 @@ int cbwd_sparse_wgrad_mfma(const float* in, const int* nbr, const float* d_out, 
                            float* dw_part, hipStream_t s);
 int cbwd_sparse_inverse_table(const int* nbr_down, int n_out, int n_in, int* inv, hipStream_t s);
 int cbwd_sparse_fold_dups(float* d, const int* nbr, int n, int C, hipStream_t s);
+// one sparse layer's conv backward (k_cond_bwd.hip): its scratch in elements (dwp / dw_part floats, flag / inv ints; 0 = not used)
+struct SparseLayerScratch {
+  size_t dwp, dw_part, flag, inv;
+};
+SparseLayerScratch cbwd_sparse_layer_scratch(int n_in, int n_out, int Cin, int Cout, bool strided, bool lvl0_subm, bool det, bool mfma);
+int cbwd_sparse_layer(const float* in, const int* nbr, float* d_out, int n_in, int n_out, int Cin, int Cout, bool strided, bool lvl0_subm,
+                      bool det, const float* w, const float* wd, int layout, float* dwp, float* dw_part, int* flag, int* inv, float* d_in,
+                      float* gw, hipStream_t s);
 int cbwd_im2colT3d(const void* src, int src_f32, long ld, int B, int D, int H, int W, int C, int stride, half_t* dst, int Rp, hipStream_t s);
 int cbwd_small_linear_bwd(const float* g, long ldg, int rows, int N, const half_t* w, int K, float* out, long ldo, int accum, hipStream_t s);
 // k_train.hip

@@ -1319,46 +1319,21 @@ int cond_bwd_sample(CondBwd& q, int bi) {
       WS_CHECK(bn_scr);
       RET_IF(cbwd_bn_rows_relu(sp.raw[i], d_cur, n_out, L.cout, L.gamma, L.beta, sp.stats[i], bn_scr, Gg, Gb, s));
     }
-    float* dwp = q.F((size_t)27 * L.cin * L.cout);
+    // the layer's conv backward (k_cond_bwd.hip: cbwd_sparse_layer, matrix-core form where the layer has its fragments)
+    const bool mfma = L.wp && L.wd, lvl0_subm = mfma && !L.strided && nbr == m.nbr_subm[0];
+    const SparseLayerScratch z = cbwd_sparse_layer_scratch(n_in, n_out, L.cin, L.cout, L.strided, lvl0_subm, det, mfma);
+    float* dwp = q.F(z.dwp);
     float* d_in = q.F((size_t)n_in * L.cin);
     WS_CHECK(dwp && d_in);
-    if (L.wp && L.wd) {
-      // matrix-core form (k_cond.hip / k_cond_bwd.hip): gather-form data gradient through the layer's own table with the tap
-      // flipped (submanifold) or through the inverse table (strided) -- no atomics, no zero fill.  At level 0 the gradients of
-      // duplicate vertices' rows are folded into their representatives' first (the table is symmetric over those only).
-      const bool lvl0_subm = !L.strided && nbr == m.nbr_subm[0];
-      if (lvl0_subm && !det) RET_IF(cbwd_sparse_fold_dups(d_cur, nbr, n_out, L.cout, s));
-      if (lvl0_subm && det) {  // the same fold with the duplicates' rows added in row order
-        WsScope sc(c, WS_TEMP);
-        int* flag = (int*)q.F((size_t)n_out);
-        WS_CHECK(flag);
-        RET_IF(cbwd_sparse_fold_dups_det(d_cur, nbr, n_out, L.cout, flag, s));
-      }
-      {
-        WsScope sc(c, WS_TEMP);
-        float* dw_part = q.F((size_t)cbwd_sparse_wgrad_chunks(n_out) * 27 * L.cin * L.cout);
-        WS_CHECK(dw_part);
-        RET_IF(cbwd_sparse_wgrad_mfma(sp.in[i], nbr, d_cur, n_out, L.cin, L.cout, dwp, dw_part, s));
-      }
-      const int* table = nbr;
+    {
       WsScope sc(c, WS_TEMP);
-      if (L.strided) {
-        int* inv = (int*)q.F((size_t)n_in * 27);
-        WS_CHECK(inv);
-        RET_IF(cbwd_sparse_inverse_table(nbr, n_out, n_in, inv, s));
-        table = inv;
-      }
-      RET_IF(launch_sparse_conv(d_cur, table, n_in, L.cout, L.cin, nullptr, L.wd, nullptr, nullptr, d_in, s, lvl0_subm ? 1 : 0));
-    } else {
-      if (det) return mvd_fail("deterministic mode: this sparse layer has no matrix-core form (its site-form data gradient adds with "
-                               "fp32 atomics); unset MVD_SPARSE_VALU");
-      HIP_CHECK_RET(hipMemsetAsync(d_in, 0, (size_t)n_in * L.cin * sizeof(float), s));
-      WsScope sc(c, WS_TEMP);
-      float* dw_part = q.F((size_t)cbwd_sparse_wgrad_chunks(n_out) * 27 * L.cin * L.cout);
-      WS_CHECK(dw_part);
-      RET_IF(cbwd_sparse_conv(sp.in[i], nbr, d_cur, n_out, L.cin, L.cout, L.w, d_in, dwp, dw_part, s));
+      float* dw_part = q.F(z.dw_part);
+      int* flag = z.flag ? (int*)q.F(z.flag) : nullptr;
+      int* inv = z.inv ? (int*)q.F(z.inv) : nullptr;
+      WS_CHECK(dw_part && (flag || !z.flag) && (inv || !z.inv));
+      RET_IF(cbwd_sparse_layer(sp.in[i], nbr, d_cur, n_in, n_out, L.cin, L.cout, L.strided, lvl0_subm, det, L.w, mfma ? L.wd : nullptr,
+                               L.layout, dwp, dw_part, flag, inv, d_in, Gw, s));
     }
-    RET_IF(cbwd_sparse_w_unpack_add(dwp, L.cin, L.cout, L.layout, Gw, s));
     d_cur = d_in;
   }
   q.mark("bwd: sparse net");

@@ -1162,6 +1162,43 @@ int cbwd_sparse_w_unpack_add(const float* pk, int Cin, int Cout, int layout, flo
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }
+// The backward of ONE sparse conv layer behind its BatchNorm backward, as the conditioner's backward runs it per layer and as the
+// parity hook mvd_op_sparse_conv_bwd runs it on the caller's buffers: d_out [n_out][Cout] (level 0 of the matrix-core form: folded in
+// place) -> d_in [n_in][Cin] written, the weight gradient added to gw in the parameter's own `layout`.
+// wd != null: matrix-core form (k_cond.hip / here): gather-form data gradient through the layer's own table with the tap flipped
+// (submanifold) or through the inverse table (strided) -- no atomics, no zero fill.  At level 0 (lvl0_subm) the gradients of
+// duplicate vertices' rows are folded into their representatives' first (the table is symmetric over those only), with atomics or,
+// det, in row order.  wd == null: site form on w ([27][Cin][Cout]): zero fill, scatter-form data gradient with fp32 atomics.
+SparseLayerScratch cbwd_sparse_layer_scratch(int n_in, int n_out, int Cin, int Cout, bool strided, bool lvl0_subm, bool det, bool mfma) {
+  SparseLayerScratch z;
+  z.dwp = (size_t)27 * Cin * Cout;
+  z.dw_part = (size_t)cbwd_sparse_wgrad_chunks(n_out) * 27 * Cin * Cout;
+  z.flag = mfma && lvl0_subm && det ? (size_t)n_out : 0;
+  z.inv = mfma && strided ? (size_t)n_in * 27 : 0;
+  return z;
+}
+int cbwd_sparse_layer(const float* in, const int* nbr, float* d_out, int n_in, int n_out, int Cin, int Cout, bool strided, bool lvl0_subm,
+                      bool det, const float* w, const float* wd, int layout, float* dwp, float* dw_part, int* flag, int* inv, float* d_in,
+                      float* gw, hipStream_t s) {
+  int rc = 0;
+  if (wd) {
+    if (lvl0_subm && !det) rc = cbwd_sparse_fold_dups(d_out, nbr, n_out, Cout, s);
+    if (lvl0_subm && det) rc = cbwd_sparse_fold_dups_det(d_out, nbr, n_out, Cout, flag, s);  // the same fold, rows added in row order
+    if (!rc) rc = cbwd_sparse_wgrad_mfma(in, nbr, d_out, n_out, Cin, Cout, dwp, dw_part, s);
+    const int* table = nbr;
+    if (!rc && strided) {
+      rc = cbwd_sparse_inverse_table(nbr, n_out, n_in, inv, s);
+      table = inv;
+    }
+    if (!rc) rc = launch_sparse_conv(d_out, table, n_in, Cout, Cin, nullptr, wd, nullptr, nullptr, d_in, s, lvl0_subm ? 1 : 0);
+  } else {
+    if (det) return mvd_fail("deterministic mode: this sparse layer has no matrix-core form (its site-form data gradient adds with "
+                             "fp32 atomics); unset MVD_SPARSE_VALU");
+    HIP_CHECK_RET(hipMemsetAsync(d_in, 0, (size_t)n_in * Cin * sizeof(float), s));
+    rc = cbwd_sparse_conv(in, nbr, d_out, n_out, Cin, Cout, w, d_in, dwp, dw_part, s);
+  }
+  return rc ? rc : cbwd_sparse_w_unpack_add(dwp, Cin, Cout, layout, gw, s);
+}
 int cbwd_im2colT3d(const void* src, int src_f32, long ld, int B, int D, int H, int W, int C, int stride, half_t* dst, int Rp, hipStream_t s) {
   const int Do = (D - 1) / stride + 1, Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
   if (Rp < B * Do * Ho * Wo) return mvd_fail("im2colT3d: bad shape");

@@ -51,6 +51,85 @@ def op_train_loss(pred, target, sample_weight=None, pixel_weight=None, loss_type
     return (loss[0], lps, mps, dpred) if want_grad else (loss[0], lps, mps)
 
 
+# ---- the sparse voxel CNN's kernels one at a time (include/mvd.h: mvd_op_sparse_conv ...): context-free like op_train_loss.
+# w: the 3x3x3 kernel in checkpoint layout 0 [Cout,Cin,3,3,3], 1 [Cout,3,3,3,Cin] or 2 [3,3,3,Cin,Cout]; nbr [n_out,27] int32.
+SPARSE_FORMS = ("site", "mfma")  # form of mvd_op_sparse_conv / mvd_op_sparse_conv_bwd, by index
+
+
+def _sparse_args(x, nbr, w, layout, form, device, lib):
+    if form not in SPARSE_FORMS:
+        raise ValueError(f"form must be one of {SPARSE_FORMS}, not {form!r}")
+    dev = x.device if device is None else device
+    x, w = _f32(x, dev), _f32(w, dev)
+    nbr = nbr.detach().to(device=dev, dtype=torch.int32).contiguous()
+    cin = x.shape[1]
+    if x.dim() != 2 or nbr.dim() != 2 or nbr.shape[1] != 27 or w.numel() % (27 * cin):
+        raise ValueError("sparse op: x [n_in,Cin], nbr [n_out,27], w with 27 * Cin * Cout elements expected")
+    if nbr.numel() and (int(nbr.max()) >= x.shape[0] or int(nbr.min()) < -1):
+        raise ValueError("sparse op: nbr indexes rows outside x")
+    return lib or L.load(), dev, x, nbr, w, cin, w.numel() // (27 * cin), SPARSE_FORMS.index(form)
+
+
+def op_sparse_conv(x, nbr, w, layout, form="mfma", scale=None, shift=None, device=None, lib=None):
+    """mvd_op_sparse_conv: one production launch of a sparse layer -> [n_out,Cout]; scale / shift: the folded BatchNorm + ReLU."""
+    lib, dev, x, nbr, w, cin, cout, f = _sparse_args(x, nbr, w, layout, form, device, lib)
+    sc, sh = (None if t is None else _f32(t, dev) for t in (scale, shift))
+    out = torch.full((nbr.shape[0], cout), float("nan"), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_sparse_conv(L.ptr(x), L.ptr(nbr), nbr.shape[0], cin, cout, L.ptr(w), int(layout), L.ptr(sc), L.ptr(sh), f,
+                                       L.ptr(out), _stream()))
+    return out
+
+
+def op_sparse_conv_bwd(x, nbr, d_out, w, layout, form="mfma", strided=False, level0_subm=False, deterministic=False, grad_w=None,
+                       poison=False, device=None, lib=None):
+    """mvd_op_sparse_conv_bwd: one layer's backward as the conditioner's backward runs it -> (d_in [n_in,Cin], dW shaped like w).
+    grad_w (shaped like w): the weight gradient is added to a copy of it (default zeros).  d_in starts from NaN: every element
+    must be written."""
+    lib, dev, x, nbr, w, cin, cout, f = _sparse_args(x, nbr, w, layout, form, device, lib)
+    dy = _f32(d_out, dev).clone()  # level 0: folded in place
+    if dy.shape != (nbr.shape[0], cout):
+        raise ValueError(f"op_sparse_conv_bwd: d_out must be [{nbr.shape[0]},{cout}]")
+    gw = torch.zeros_like(w) if grad_w is None else _f32(grad_w, dev).clone().reshape(w.shape)
+    d_in = torch.full_like(x, float("nan"))
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_sparse_conv_bwd(L.ptr(x), L.ptr(nbr), L.ptr(dy), x.shape[0], nbr.shape[0], cin, cout, bool(strided),
+                                           bool(level0_subm), bool(deterministic), f, L.ptr(w), int(layout), bool(poison),
+                                           L.ptr(d_in), L.ptr(gw), _stream()))
+    return d_in, gw
+
+
+def op_bn_rows_relu(x, gamma, beta, eps=1e-3, running=None, momentum=0.01, inplace=False, want_stats=True, device=None, lib=None):
+    """mvd_op_bn_rows_relu: train-mode BatchNorm1d + ReLU over x [n,C] -> (y, stats [2,C] = [mean | rstd] or None, running).
+    running = (mean, var): copies of them are updated with ``momentum`` and returned; inplace: y aliases the kernel's input."""
+    lib = lib or L.load()
+    dev = x.device if device is None else device
+    x, g, b = _f32(x, dev), _f32(gamma, dev), _f32(beta, dev)
+    n, Cc = x.shape
+    xin = x.clone()
+    y = xin if inplace else torch.full_like(x, float("nan"))
+    stats = torch.full((2, Cc), float("nan"), device=dev, dtype=torch.float32) if want_stats else None
+    rm, rv = (None, None) if running is None else (_f32(running[0], dev).clone(), _f32(running[1], dev).clone())
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_bn_rows_relu(L.ptr(xin), n, Cc, L.ptr(g), L.ptr(b), float(eps), float(momentum), L.ptr(y), L.ptr(stats),
+                                        L.ptr(rm), L.ptr(rv), _stream()))
+    return y, stats, (None if running is None else (rm, rv))
+
+
+def op_bn_rows_relu_bwd(xraw, dy, stats, gamma, beta, accum=None, poison=False, device=None, lib=None):
+    """mvd_op_bn_rows_relu_bwd -> (d xraw [n,C], dgamma [C], dbeta [C]); accum = (dgamma0, dbeta0): what the gradients start from."""
+    lib = lib or L.load()
+    dev = xraw.device if device is None else device
+    x, st, g, b = _f32(xraw, dev), _f32(stats, dev), _f32(gamma, dev), _f32(beta, dev)
+    d = _f32(dy, dev).clone()
+    n, Cc = x.shape
+    dg, db = (torch.zeros_like(g), torch.zeros_like(g)) if accum is None else (_f32(accum[0], dev).clone(), _f32(accum[1], dev).clone())
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_bn_rows_relu_bwd(L.ptr(x), L.ptr(d), n, Cc, L.ptr(g), L.ptr(b), L.ptr(st), bool(poison), L.ptr(dg), L.ptr(db),
+                                            _stream()))
+    return d, dg, db
+
+
 IncompatibleKeys = collections.namedtuple("IncompatibleKeys", ["missing_keys", "unexpected_keys"])
 MAX_SAMPLE_SLOTS = 64  # per-sample mesh / camera tables kept resident in the context (mvd_select_sample)
 
@@ -529,6 +608,21 @@ class Engine:
         ``want_grad`` nothing but the loss is computed (the held-out loss of ``validation_loss``).  Needs no training context."""
         return op_train_loss(pred, target, sample_weight, pixel_weight, loss_type, huber_delta, loss_scale, want_grad,
                              device=self.device, lib=self.lib)
+
+    # the sparse voxel CNN's kernels one at a time: the module-level functions above on this engine's device and library
+    def op_sparse_conv(self, x, nbr, w, layout, form="mfma", scale=None, shift=None):
+        return op_sparse_conv(x, nbr, w, layout, form, scale, shift, device=self.device, lib=self.lib)
+
+    def op_sparse_conv_bwd(self, x, nbr, d_out, w, layout, form="mfma", strided=False, level0_subm=False, deterministic=False,
+                           grad_w=None, poison=False):
+        return op_sparse_conv_bwd(x, nbr, d_out, w, layout, form, strided, level0_subm, deterministic, grad_w, poison,
+                                  device=self.device, lib=self.lib)
+
+    def op_bn_rows_relu(self, x, gamma, beta, eps=1e-3, running=None, momentum=0.01, inplace=False, want_stats=True):
+        return op_bn_rows_relu(x, gamma, beta, eps, running, momentum, inplace, want_stats, device=self.device, lib=self.lib)
+
+    def op_bn_rows_relu_bwd(self, xraw, dy, stats, gamma, beta, accum=None, poison=False):
+        return op_bn_rows_relu_bwd(xraw, dy, stats, gamma, beta, accum, poison, device=self.device, lib=self.lib)
 
     def train_cond_backward(self, cond_index, x, context, d_out):
         """mvd_train_cond_backward (parity hook): one DepthTransformer's backward from exact inputs -> (dx, dcontext)."""
