@@ -325,6 +325,27 @@ int mvd_train_unet_step_ex(mvd_ctx* ctx, const float* x, const int64_t* timestep
 int mvd_op_train_loss(const float* pred, const float* target, int B, int HW, int C, const float* sample_w, const float* pixel_w,
                       int loss_type, float huber_delta, float loss_scale, float* dpred, float* loss_out, float* loss_per_sample,
                       float* mse_per_sample, void* stream);
+/* 2-D image metrics of generated views against captured views (SSIM, squared / absolute error) under the reference's evaluation
+ * protocol: 8-bit images, skimage's structural_similarity at its uint8 defaults.  No context; one fused kernel and a finalise
+ * launch (csrc/k_metrics.hip), no atomics, every order of summation a function of (V, H, W) alone: two calls agree bit for bit.
+ *   pixel values  a float image in [-1, 1] is quantised q = trunc(((clamp(x, -1, 1) + 1) * 0.5) * 255), every step in fp32 in
+ *                 that order (batch.views_to_uint8's bytes); a uint8 image is taken as it is.
+ *   background    where a pixel is background the PREDICTED pixel becomes 255 in all three channels, the target stays (the
+ *                 ground truth was composited on white).  mask_mode 0: none; 1: mask [V,H,W] uint8, nonzero = background;
+ *                 2: derived from the target -- background iff all three quantised target channels are >= 254.
+ *   ssim          per channel, 7 x 7 uniform window, K1 = 0.01, K2 = 0.03, L = 255, C1 = (K1 L)^2, C2 = (K2 L)^2, sample
+ *                 (co)variances (normalised by 49/48):  S = (2 mx my + C1)(2 sxy + C2) / ((mx^2 + my^2 + C1)(sx + sy + C2)),
+ *                 averaged over the window centres whose window lies inside the image (rows 3..H-4, columns 3..W-4), then over
+ *                 the three channels.  The five window sums are exact integers; only S is evaluated, in fp64.
+ *   sse, sae      sums of (p - t)^2 and |p - t| over all 3 H W quantised values after the background rule: exact integers.
+ *   non-finite    NaNs and infinities of a float image are counted per view; a view with any reports NaN for ssim, sse, sae and the
+ *                 background count, so that nothing derived from them is a plausible number.
+ * pred / target: device pointers; dtype 0 = float32, 1 = uint8; layout 0 = [V,3,H,W], 1 = [V,H,W,3] (the two may differ in
+ * both).  out: device, [V][5] doubles = ssim, sse, sae, background pixels, non-finite values.  Null pred / target / out,
+ * H < 7, W < 7, V < 1, V > 65535, V H W 3 >= 2^31, an unknown dtype / layout / mode, or mode 1 without a mask are errors and
+ * launch nothing.  Synchronises the stream (its scratch lives for the call). */
+int mvd_op_image_metrics(const void* pred, int pred_dtype, int pred_layout, const void* target, int target_dtype, int target_layout,
+                         const unsigned char* mask, int mask_mode, int V, int H, int W, double* out, void* stream);
 /* The conditioner's backward for ONE sample (its mesh / cameras active: mvd_select_sample): re-runs construct_spatial_volume and
  * construct_view_frustum_volume (morphable_diffusion.py:203-320: step embedding, 2-D encoder on the N noisy views, vertex gather,
  * view fusion, sparse voxel CNN in train mode, lattice gather, frustum gather and FrustumTV3DNet for the target view) with every

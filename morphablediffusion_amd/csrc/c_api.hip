@@ -622,6 +622,20 @@ int mvd_op_train_loss(const float* pred, const float* target, int B, int HW, int
   return rc;
 }
 
+int mvd_op_image_metrics(const void* pred, int pred_dtype, int pred_layout, const void* target, int target_dtype, int target_layout,
+                         const unsigned char* mask, int mask_mode, int V, int H, int W, double* out, void* stream) {
+  RET_IF(image_metrics_check("mvd_op_image_metrics", pred, pred_dtype, pred_layout, target, target_dtype, target_layout, mask, mask_mode,
+                             V, H, W, out));
+  hipStream_t s = S(stream);
+  void* scratch = nullptr;  // the per-tile partial sums live for this call only
+  HIP_CHECK_RET(hipMalloc(&scratch, image_metrics_scratch_bytes(V, H, W)));
+  int rc = launch_image_metrics(pred, pred_dtype, pred_layout, target, target_dtype, target_layout, mask, mask_mode, V, H, W, out,
+                                scratch, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_image_metrics: stream synchronisation failed");
+  hipFree(scratch);
+  return rc;
+}
+
 // ---- parity hooks of the sparse voxel CNN (tests/test_gpu_sparse_cnn_ops.py): no context, the caller's device buffers, scratch and
 // weight packs that live for the call (freed after the stream has been synchronised)
 namespace {

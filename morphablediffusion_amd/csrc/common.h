@@ -272,6 +272,14 @@ int train_loss_check(const char* who, int B, int HW, int C, int loss_type, float
 int launch_train_loss(const float* pred, const float* target, int B, int HW, int C, const float* w, const float* m, int loss_type,
                       float huber_delta, float loss_scale, float* dpred, float* loss_out, float* loss_ps, float* mse_ps, void* scratch,
                       hipStream_t s);
+// k_metrics.hip: SSIM / squared / absolute error of 8-bit views (include/mvd.h: mvd_op_image_metrics).  dtype 0 float32, 1 uint8;
+// layout 0 [V][3][H][W], 1 [V][H][W][3]; mask [V][H][W] (mode 1).  image_metrics_check: the argument errors (0 = fine); scratch:
+// image_metrics_scratch_bytes(V, H, W) bytes, 8-byte aligned, alive until the launches have run; out [V][5] doubles.
+size_t image_metrics_scratch_bytes(int V, int H, int W);
+int image_metrics_check(const char* who, const void* pred, int pred_dtype, int pred_layout, const void* target, int target_dtype,
+                        int target_layout, const unsigned char* mask, int mask_mode, int V, int H, int W, const double* out);
+int launch_image_metrics(const void* pred, int pred_dtype, int pred_layout, const void* target, int target_dtype, int target_layout,
+                         const unsigned char* mask, int mask_mode, int V, int H, int W, double* out, void* scratch, hipStream_t s);
 int launch_latent_gather(const float* feats, const int* grid, int gd, int gh, int gw, const float* min_xyz,
                          const int* out_sh, float voxel, int V, float vol_len, float* out, hipStream_t s);
 int launch_sparse_densify(const float* feats, const int* grid, long nvox, int C, float* out, hipStream_t s);

@@ -51,6 +51,52 @@ def op_train_loss(pred, target, sample_weight=None, pixel_weight=None, loss_type
     return (loss[0], lps, mps, dpred) if want_grad else (loss[0], lps, mps)
 
 
+MASK_MODES = ("none", "explicit", "white")  # mask_mode of mvd_op_image_metrics, by index
+METRIC_COLUMNS = ("ssim", "sse", "sae", "background", "nonfinite")  # the columns of its output
+
+
+def _image_arg(name, t):
+    """(dtype code, layout code, (V, H, W)) of one image batch [V,3,H,W] / [V,H,W,3], float or uint8."""
+    if t.dim() != 4 or (t.shape[1] == 3) == (t.shape[3] == 3):
+        raise ValueError(f"op_image_metrics: {name} must be [V,3,H,W] or [V,H,W,3], got {tuple(t.shape)}")
+    if t.dtype != torch.uint8 and not t.is_floating_point():
+        raise ValueError(f"op_image_metrics: {name} must be a float tensor or uint8, not {t.dtype}")
+    layout = 0 if t.shape[1] == 3 else 1
+    shape = (t.shape[0], t.shape[2], t.shape[3]) if layout == 0 else tuple(t.shape[:3])
+    return int(t.dtype == torch.uint8), layout, shape
+
+
+def op_image_metrics(pred, target, mask=None, mask_mode=None, device=None, lib=None):
+    """mvd_op_image_metrics on ``device`` (default: pred's): pred / target [V,3,H,W] or [V,H,W,3] (the two may differ), float
+    (taken as [-1, 1], quantised like batch.views_to_uint8) or uint8; mask [V,H,W], nonzero = background, with mask_mode
+    "explicit" (the default with a mask); "white" derives the background from the target, "none" (the default without a mask)
+    has none.  Returns [V,5] float64 on the device, columns METRIC_COLUMNS.  Shapes and dtypes are checked before anything is
+    copied or launched; the one host synchronisation is the entry point's own."""
+    mask_mode = mask_mode or ("none" if mask is None else "explicit")
+    if mask_mode not in MASK_MODES:
+        raise ValueError(f"mask_mode must be one of {MASK_MODES}, not {mask_mode!r}")
+    if (mask_mode == "explicit") != (mask is not None):
+        raise ValueError("op_image_metrics: mask_mode 'explicit' goes with a mask, the other modes without one")
+    pd, pl, shape = _image_arg("pred", pred)
+    td, tl, tshape = _image_arg("target", target)
+    if shape != tshape:
+        raise ValueError(f"op_image_metrics: pred is (V, H, W) = {shape}, target {tshape}")
+    V, H, W = shape
+    if V < 1 or H < 7 or W < 7:
+        raise ValueError(f"op_image_metrics: at least one view of at least 7 x 7 pixels is needed, got (V, H, W) = {shape}")
+    if mask is not None and tuple(mask.shape) != shape:
+        raise ValueError(f"op_image_metrics: mask must be [V,H,W] = {list(shape)}, got {tuple(mask.shape)}")
+    dev = pred.device if device is None else device
+    p, tg = (t.detach().to(device=dev, dtype=torch.uint8 if d else torch.float32).contiguous() for t, d in ((pred, pd), (target, td)))
+    m = None if mask is None else (mask.detach().to(dev) != 0).to(torch.uint8).contiguous()
+    lib = lib or L.load()
+    out = torch.full((V, len(METRIC_COLUMNS)), float("nan"), device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_image_metrics(L.ptr(p), pd, pl, L.ptr(tg), td, tl, L.ptr(m), MASK_MODES.index(mask_mode), V, H, W,
+                                         L.ptr(out), _stream()))
+    return out
+
+
 # ---- the sparse voxel CNN's kernels one at a time (include/mvd.h: mvd_op_sparse_conv ...): context-free like op_train_loss.
 # w: the 3x3x3 kernel in checkpoint layout 0 [Cout,Cin,3,3,3], 1 [Cout,3,3,3,Cin] or 2 [3,3,3,Cin,Cout]; nbr [n_out,27] int32.
 SPARSE_FORMS = ("site", "mfma")  # form of mvd_op_sparse_conv / mvd_op_sparse_conv_bwd, by index
@@ -608,6 +654,10 @@ class Engine:
         ``want_grad`` nothing but the loss is computed (the held-out loss of ``validation_loss``).  Needs no training context."""
         return op_train_loss(pred, target, sample_weight, pixel_weight, loss_type, huber_delta, loss_scale, want_grad,
                              device=self.device, lib=self.lib)
+
+    def op_image_metrics(self, pred, target, mask=None, mask_mode=None):
+        """mvd_op_image_metrics on this engine's device: see the module-level op_image_metrics."""
+        return op_image_metrics(pred, target, mask, mask_mode, device=self.device, lib=self.lib)
 
     # the sparse voxel CNN's kernels one at a time: the module-level functions above on this engine's device and library
     def op_sparse_conv(self, x, nbr, w, layout, form="mfma", scale=None, shift=None):

@@ -3,7 +3,7 @@ MI355X engine: same flags, same batch construction, same outputs.
 
   --input_img IMG --exp_img IMG --mesh MESH.{ply,obj} --cfg configs/facescape.yaml --ckpt CKPT --output_dir DIR
   [--cfg_scale 2.0] [--batch_view_num 8] [--seed 6033] [--sampler ddim|dpmpp_2m|dpmpp_2m_sde] [--sample_steps 50]
-  [--camera_trajectory virtual|real] [--prepare_neus2_data]
+  [--camera_trajectory virtual|real] [--prepare_neus2_data] [--gt_dir DIR]
 
 writes ``<output_dir>/<input>_<exp>.png`` (the input view followed by the 16 generated views, generate_face.py:244-253) and, with
 --prepare_neus2_data, ``<output_dir>/neus2_data/<input>_<exp>/{transform.json, images/00..15.png}`` (:145-192,255-262).
@@ -15,7 +15,9 @@ Differences, all outside the denoising path and stated here:
     (alpha = 1), which is what the reference's demo inputs are after matting;
   * meshes are read by a small PLY / OBJ vertex reader instead of trimesh (``process=False``: vertices as stored);
   * --camera_file names the pickle / JSON of the 'real' trajectory (default: the reference's ./assets/facescape_test_traj.pkl);
-  * --exp_img only names the output, as in the reference (the expression enters through the mesh).
+  * --exp_img only names the output, as in the reference (the expression enters through the mesh);
+  * --gt_dir DIR (not a reference flag) scores the saved strip's 16 views against the captured views in DIR (metrics.py: SSIM,
+    PSNR, MSE, MAE under the reference's evaluation protocol) and writes ``<output_dir>/<input>_<exp>_metrics.json``.
 """
 import argparse
 import json
@@ -133,6 +135,9 @@ def build_parser():
     p.add_argument("--lora", type=str, default=None,
                    help="not a reference flag: a LoRA adapter file (save_lora), merged into the checkpoint's weights at load time")
     p.add_argument("--lora_scale", type=float, default=1.0, help="not a reference flag: strength of --lora (0: the base model)")
+    p.add_argument("--gt_dir", type=str, default=None,
+                   help="not a reference flag: a folder with the 16 captured views (sorted *.png, 256 x 256; RGBA: alpha 0 is "
+                        "background); the saved strip's views are scored against them into <output_dir>/<img>_<exp>_metrics.json")
     return p
 
 
@@ -177,6 +182,13 @@ def run(flags, model=None):
     strip = B.views_to_uint8(x_sample, data["input_image"])
     output_fn = Path(flags.output_dir) / f"{img_name}_{exp_name}.png"
     Image.fromarray(strip).save(output_fn)
+    if getattr(flags, "gt_dir", None):
+        # scored from the strip's bytes, which are what the reference's evaluation reads back from the saved file
+        from . import metrics as M
+        gt, gt_mask = M.load_target_views(flags.gt_dir, NUM_VIEWS, 256)
+        res = M.summarise(M.image_metrics(M.strip_to_views(strip, NUM_VIEWS, 256)[0].to(model.device), gt, gt_mask))
+        with open(Path(flags.output_dir) / f"{img_name}_{exp_name}_metrics.json", "w") as f:
+            json.dump(dict(res, sampler=flags.sampler, sample_steps=flags.sample_steps), f, indent=2)
     if neus2_root:
         # generate_face.py:255-262 slices idx*256 of the strip for idx in range(16): view 0 of the export is the INPUT view and
         # the last generated view is dropped -- reproduced as is

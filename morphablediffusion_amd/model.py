@@ -440,6 +440,8 @@ class SyncMultiviewDiffusion(nn.Module):
         self._grad_comm = None
         self.global_rank = 0
         self.image_dir = "."
+        self.val_metrics = False  # validation_step also scores its views against batch["target_image"] (metrics.image_metrics)
+        self.last_val_metrics = None
         self.view_num = view_num
         self.viewpoint_dim = 4
         self.output_num = output_num
@@ -960,7 +962,38 @@ class SyncMultiviewDiffusion(nn.Module):
             out = Path(self.image_dir) / "images" / "val"
             out.mkdir(exist_ok=True, parents=True)
             save_image_grid(x_sample, batch_, str(out / f"{self.global_step}.jpg"))
+            if self.val_metrics and batch_.get("target_image") is not None:
+                import json
+                from .metrics import summarise
+                self.last_val_metrics = self.evaluate_views(batch_, x_sample=x_sample)
+                with open(out / f"{self.global_step}.json", "w") as f:
+                    json.dump(dict(summarise(self.last_val_metrics), global_step=self.global_step), f, indent=2)
             return x_sample
+
+    @torch.no_grad()
+    def evaluate_views(self, batch, x_sample=None, mask="auto", sampler=None, cfg_scale=None, batch_view_num=None):
+        """Image quality of the generated views against the captured ones: ``metrics.image_metrics`` of ``x_sample`` [B,N,3,H,W]
+        against ``batch["target_image"]`` [B,N,H,W,3] (not a reference method; its evaluation script computes the same numbers
+        from files).  Without ``x_sample`` the batch is sampled first, the way validation_step does: in eval mode, with
+        ``sampler`` / ``cfg_scale`` / ``batch_view_num`` defaulting to the model's own, inside ``ema_scope()`` when use_ema.
+        mask: "auto" -- ``batch["target_mask"] < 0.5`` ([B,N,H,W], 1 = foreground) when the batch has one, else none; "white",
+        None or a tensor as image_metrics takes them.  Returns its dict (float64 device tensors [B,N]: ssim, psnr, mse, mae,
+        background, nonfinite) plus "x_sample"."""
+        from .metrics import image_metrics
+        if batch.get("target_image") is None:
+            raise ValueError("evaluate_views needs batch['target_image']")
+        if x_sample is None:
+            import contextlib
+            self.eval()
+            with self.ema_scope() if self.use_ema else contextlib.nullcontext():
+                x_sample = self.sample(self.sampler if sampler is None else sampler, batch,
+                                       self.cfg_scale if cfg_scale is None else cfg_scale,
+                                       self.batch_view_num if batch_view_num is None else batch_view_num)
+        if isinstance(mask, str) and mask == "auto":
+            mask = batch["target_mask"] < 0.5 if batch.get("target_mask") is not None else None
+        out = image_metrics(x_sample, batch["target_image"], mask)
+        out["x_sample"] = x_sample
+        return out
 
     def log_image(self, x_sample, batch, step, output_dir):
         """morphable_diffusion.py:589-599: one row per sample -- the input view followed by the N generated views -- as

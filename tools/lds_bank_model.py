@@ -113,6 +113,26 @@ def conv3x_key_position(IW):     # halo_key<IW> of k_conv3x.hip: from the pixel'
     return lambda r: (((r % HWD) >> 1) + 4 * (((r % (HWD * HWD)) // HWD) & 1))
 
 
+# ---- metrics_tile_kernel (k_metrics.hip): ds_read_u8 of the 7 x 7 taps from the byte halo tile, rows of PITCH bytes ---------------------
+def metrics_tap_read_cycles(PITCH=40, TILE=32):
+    """Average LDS cycles per 32-lane group (1.0 = conflict-free) over every wave, centre row step and tap: lane -> centre
+    (t % TILE, t / TILE + 8 j), tap (dy, dx) reads byte (cy + dy) * PITCH + cx + dx; lanes on one dword share the access."""
+    tot = n = 0
+    for wave in range(4):
+        for j in range(4):
+            for dy in range(7):
+                for dx in range(7):
+                    for g in range(2):
+                        banks = {}
+                        for lane in range(32 * g, 32 * g + 32):
+                            t = wave * 64 + lane
+                            a = (t // TILE + 8 * j + dy) * PITCH + t % TILE + dx
+                            banks.setdefault((a // 4) % 32, set()).add(a // 4)
+                        tot += _worst(banks)
+                        n += 1
+    return tot / n
+
+
 def main():
     print("attn_kernel, transposed V image: LDS cycles per workgroup and key tile (stores + 4 waves x fragment reads)")
     for D in (40, 80):
@@ -128,6 +148,8 @@ def main():
     for IW in (16, 8):
         print(f"  {IW} x {IW} tiles: key from the linear row {conv3x_halo_read_cycles(conv3x_key_linear(IW), IW):.3f}, "
               f"from the position in the halo block {conv3x_halo_read_cycles(conv3x_key_position(IW), IW):.3f}")
+    print("metrics_tile_kernel, 7 x 7 tap reads of the byte halo tile: average LDS cycles per 32-lane group (1.0 = conflict-free)")
+    print("  " + ", ".join(f"pitch {p}: {metrics_tap_read_cycles(p):.3f}" for p in (38, 40, 64, 128)))
 
 
 if __name__ == "__main__":
