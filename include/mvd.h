@@ -671,6 +671,57 @@ int mvd_op_st_tail(mvd_ctx* ctx, int C, int rows, int T, const float* ao, const 
 int mvd_op_st_head(mvd_ctx* ctx, int rows, int xp, const float* n0, const float* w_pi, const float* b_pi, const float* ln_g,
                    const float* ln_b, const float* w_q, const float* w_k, const float* w_v, float* t0_out, float* qkv_out,
                    int iters, float* ms_out, void* stream);
+/* Forward-form hooks (tests/test_gpu_epilogue_forms.py): the forward kernels in the forms the inference path and the first-stage
+ * model launch them in.  Common rules: operands are fp32 in the reference's layouts (activations channels-last, weights [N][K] /
+ * [Cout][Cin][k][k]); result buffers are the caller's, written by the production launch itself, as fp32 or as the library's
+ * 16-bit type (mvd_compute_dtype) -- the caller sizes them with one guard row behind the last row (and pad columns where ld > width)
+ * and presets them to 0xFF bytes, so a write outside the result shows; a bad argument returns non-zero before anything is
+ * launched; poison != 0 fills the free workspace (the launch's own scratch: split-K slabs, operand copies) with 0xFF bytes once
+ * the operands are staged; the stream is synchronised before the call returns.
+ *
+ * mvd_op_linear_ex (run_linear) / mvd_op_conv_ex (run_conv2d, or run_upconv2d with up_fold): every GemmArgs field.  B samples of
+ * rows / B rows; rowbias [B][rb_ld] (conv: rb_ld % 4 == 0); out = act(alpha * acc + bias + rowbias[sample] + resid) with act 0 / 1 (SiLU); use_bias = 0
+ * ignores the bias; out_f16: 16-bit result, with out_split as [hi | lo | hi] blocks of N columns (ldc >= 3 N); resid [rows][ldr]
+ * fp32, rounded to 16 bits first when resid_f16; a_half: the activation is rounded to 16 bits in memory first (else the kernels
+ * read fp32); xp: extended precision -- the activation is split into [a_hi | a_lo | a_hi] (launch_rows_f32_to_f16_split) and the
+ * weight packed as [w_hi | w_hi | w_lo]; force_splitk > 0 fixes the split.  slabs (may be NULL): a buffer of slabs_cap floats offered
+ * for a deferred split-K reduction (GemmArgs::slabs, defer_epilogue); *sk_used is the split left in it (1: `out` is finished).
+ * conv only: x [B][H][W][Cin] (Cin % 8 == 0), stride 1 / 2, upsample 0 / 1 (fused nearest x2), tap_shift = 1: zero padding on the right
+ * and bottom only (the first-stage encoder's Downsample: 3x3, stride 2, even H and W only); conv3x_stream != 0 also packs the
+ * weights as a conv3x fragment stream where the shape has one. */
+int mvd_op_linear_ex(mvd_ctx* ctx, const float* a, int B, int rows, int K, const float* w, const float* bias, int N,
+                     const float* rowbias, int rb_ld, float alpha, int act, int use_bias, int out_f16, int out_split, int ldc,
+                     const float* resid, int resid_f16, int ldr, int a_half, int force_splitk, int xp, float* slabs,
+                     size_t slabs_cap, int defer_epilogue, int* sk_used, int poison, void* out, void* stream);
+int mvd_op_conv_ex(mvd_ctx* ctx, const float* x, int B, int H, int W, int Cin, const float* w, const float* bias, int Cout, int ksize,
+                   int stride, int upsample, int up_fold, int tap_shift, const float* rowbias, int rb_ld, float alpha, int act,
+                   int use_bias, int out_f16, int out_split, int ldc, const float* resid, int resid_f16, int ldr, int a_half,
+                   int force_splitk, int xp, int conv3x_stream, float* slabs, size_t slabs_cap, int defer_epilogue, int* sk_used,
+                   int poison, void* out, void* stream);
+/* GroupNorm(+act) of sum(slabs) + bias2 + preadd[sample] + resid.  x: nslab slabs of [B][rows][ld] fp32, slab_stride floats apart.
+ * form 0: run_group_norm's own choice of kernel; form 1: the two-pass pair called directly (one slab, no bias2 / resid / mat).
+ * split 0: out [B*rows + 1][ldo] 16-bit; 1: [hi | lo | hi] blocks of C columns; 2: fp32 rows of ldo / 2 floats.  mat (may be NULL):
+ * the summed tensor in fp32, [B*rows + 1][ldm]. */
+int mvd_op_group_norm_ex(mvd_ctx* ctx, const float* x, int B, int rows, int C, int ld, int groups, const float* gamma,
+                         const float* beta, float eps, int act, int form, const float* preadd, int pld, int split, int nslab,
+                         size_t slab_stride, const float* bias2, const float* resid, int ldr, float* mat, int ldm, int ldo,
+                         int poison, void* out, void* stream);
+/* LayerNorm of sum(slabs) + bias + rowbias[row / T] + resid (launch_layernorm_slabs; mat [rows + 1][C] receives that row in fp32,
+ * raw -- may be NULL -- its 16-bit copy, rows ld_raw apart).  plain != 0: launch_layernorm on one slab, raw optional, no mat. */
+int mvd_op_layer_norm_slabs(mvd_ctx* ctx, const float* slabs, int nslab, size_t slab_stride, int rows, int C, const float* bias,
+                            const float* rowbias, int rb_ld, int T, const float* resid, int ldr, const float* gamma,
+                            const float* beta, float eps, int plain, int ld_raw, int poison, float* mat, void* raw, void* out,
+                            void* stream);
+/* GroupNorm folded into two GEMM passes (the UNet's context fold): statistics-only GEMM -> partials [B * rps / 256 + 1][N / cpg][2]
+ * (sum, sum of squares per 256-row tile and group), launch_gn_finalize -> scale, shift [B + 1][N], apply GEMM -> out
+ * [B * rps + 1][N] 16-bit = relu(group_norm(x @ w^T)).  Refuses what the engine does not fold: rps % 256 != 0, cpg not 8 / 16 / 32. */
+int mvd_op_folded_group_norm(mvd_ctx* ctx, const float* x, int B, int rps, int K, const float* w, int N, int cpg,
+                             const float* gamma, const float* beta, float eps, int poison, float* partials, float* scale,
+                             float* shift, void* out, void* stream);
+/* row softmax of [rows][cols] fp32 scores, cols <= 4096: 16-bit (out_f32 == 0) or fp32 probabilities, out [rows + 1][cols] */
+int mvd_op_softmax_rows(mvd_ctx* ctx, const float* scores, int rows, int cols, int out_f32, void* out, void* stream);
+/* launch_rows_f32_to_f16_split: fp32 rows lda floats apart -> out [rows + 1][3 C] 16-bit, [hi | lo | hi] */
+int mvd_op_rows_split(mvd_ctx* ctx, const float* x, int lda, int rows, int C, void* out, void* stream);
 /* time of the dominant kernel, for bench.py: runs the 3x3 conv implicit GEMM `iters` times on stream and
  * returns the mean kernel time in ms measured with HIP events on that stream */
 int mvd_bench_conv(mvd_ctx* ctx, int B, int C, int H, int W, int Cout, int iters, float* ms_out, void* stream);

@@ -2205,4 +2205,280 @@ int mvd_op_st_head(mvd_ctx* c, int rows, int xp, const float* n0, const float* w
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------- forward-form hooks
+// tests/test_gpu_epilogue_forms.py: the forward kernels in the forms the inference path and the first-stage model launch them in
+// (every GemmArgs field, extended precision, deferred split-K and its consumers, the folded GroupNorm, the row softmax).
+// Operands are fp32 in the reference's layouts (activations channels-last); the production launch writes straight into the
+// caller's result buffers, which the caller presets to 0xFF bytes with a guard row (and pad columns) behind what may be written.
+// Arguments are checked before anything is allocated or launched; poison != 0 fills the free workspace (everything the launch
+// allocates for itself: split-K slabs, operand copies) with 0xFF bytes once the operands are staged; the stream is synchronised.
+namespace {
+int ex_begin(mvd_ctx* c) {
+  if (!c) return mvd_fail("null context");
+  if (hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
+  return 0;
+}
+int ex_poison(mvd_ctx* c, hipStream_t s) {
+  const size_t o = (c->ws.off + 255) & ~(size_t)255;
+  if (o < c->ws.size) HIP_CHECK_RET(hipMemsetAsync(c->ws.base + o, 0xFF, c->ws.size - o, s));
+  return 0;
+}
+// the epilogue fields shared by mvd_op_linear_ex and mvd_op_conv_ex
+struct ExEpi {
+  const float *bias, *rowbias, *resid;
+  int rb_ld, act, use_bias, out_f16, out_split, ldc, resid_f16, ldr, force_splitk;
+  float alpha;
+  float* slabs;
+  size_t slabs_cap;
+  int defer_epilogue;
+  int* sk_used;
+  void* out;
+};
+// rb_unaligned_ok: per-sample rows of any stride (a plain GEMM then runs on the gather kernel with its element-wise epilogue)
+int ex_epi_check(const char* who, const ExEpi& e, int N, bool rb_unaligned_ok = false) {
+  const std::string w(who);
+  if (!e.out) return mvd_fail((w + ": null result").c_str());
+  if (N <= 0 || (N & 3)) return mvd_fail((w + ": N must be a positive multiple of 4").c_str());
+  if (e.act != ACT_NONE && e.act != ACT_SILU) return mvd_fail((w + ": act is 0 (none) or 1 (SiLU)").c_str());
+  if (!(e.alpha == e.alpha) || e.alpha - e.alpha != 0.0f) return mvd_fail((w + ": alpha must be finite").c_str());
+  if (e.use_bias && !e.bias) return mvd_fail((w + ": use_bias without a bias").c_str());
+  if (e.rowbias && (e.rb_ld < N || (!rb_unaligned_ok && (e.rb_ld & 3)))) return mvd_fail((w + ": rb_ld must be a multiple of 4, >= N").c_str());
+  if (e.resid && (e.ldr < N || (e.ldr & 3))) return mvd_fail((w + ": ldr must be a multiple of 4, >= N").c_str());
+  if (e.out_split && !e.out_f16) return mvd_fail((w + ": out_split is a form of the fp16 result").c_str());
+  if ((e.ldc & 3) || e.ldc < (e.out_split ? 3 : 1) * N) return mvd_fail((w + ": ldc must be a multiple of 4, >= N (3 N with out_split)").c_str());
+  if (e.force_splitk < 0) return mvd_fail((w + ": force_splitk >= 0").c_str());
+  if (e.slabs && !e.sk_used) return mvd_fail((w + ": a slab buffer needs sk_used").c_str());
+  if (e.slabs && ((uintptr_t)e.slabs & 15)) return mvd_fail((w + ": the slab buffer must be 16-byte aligned").c_str());
+  if ((uintptr_t)e.out & 15) return mvd_fail((w + ": the result must be 16-byte aligned").c_str());
+  return 0;
+}
+// fills the GemmArgs from the checked fields; an fp16 residual is staged from the caller's fp32 rows
+int ex_epi_fill(mvd_ctx* c, const ExEpi& e, size_t out_rows, int N, GemmArgs& g, hipStream_t s) {
+  g.out = e.out; g.out_f32 = e.out_f16 ? 0 : 1; g.ldc = e.ldc; g.out_split = e.out_split ? N : 0;
+  g.rowbias = e.rowbias; g.rb_ld = e.rb_ld; g.alpha = e.alpha; g.act = e.act; g.use_bias = e.use_bias != 0;
+  g.force_splitk = e.force_splitk;
+  if (e.resid) {
+    g.resid = e.resid; g.resid_f32 = 1; g.ldr = e.ldr;
+    if (e.resid_f16) {
+      half_t* rh = ws_alloc<half_t>(c, out_rows * e.ldr);
+      WS_CHECK(rh);
+      RET_IF(launch_f32_to_f16(e.resid, rh, out_rows * e.ldr, s));
+      g.resid = rh; g.resid_f32 = 0;
+    }
+  }
+  if (e.slabs) {
+    g.slabs = e.slabs; g.slabs_cap = e.slabs_cap; g.sk_used = e.sk_used; g.defer_epilogue = e.defer_epilogue != 0;
+  }
+  return 0;
+}
+}  // namespace
+
+int mvd_op_linear_ex(mvd_ctx* c, const float* a, int B, int rows, int K, const float* w, const float* bias, int N, const float* rowbias,
+                     int rb_ld, float alpha, int act, int use_bias, int out_f16, int out_split, int ldc, const float* resid,
+                     int resid_f16, int ldr, int a_half, int force_splitk, int xp, float* slabs, size_t slabs_cap, int defer_epilogue,
+                     int* sk_used, int poison, void* out, void* stream) {
+  RET_IF(ex_begin(c));
+  if (!a || !w) return mvd_fail("op_linear_ex: null operand");
+  if (B <= 0 || rows <= 0 || rows % B || K <= 0 || (K & 7)) return mvd_fail("op_linear_ex: rows % B == 0 and K % 8 == 0 expected");
+  const ExEpi e{bias, rowbias, resid, rb_ld, act, use_bias, out_f16, out_split, ldc, resid_f16, ldr, force_splitk, alpha,
+                slabs, slabs_cap, defer_epilogue, sk_used, out};
+  RET_IF(ex_epi_check("op_linear_ex", e, N, true));
+  hipStream_t s = S(stream);
+  WsScope ws_scope(c);
+  const int Kp = xp ? 3 * K : K;
+  half_t* wp = ws_alloc<half_t>(c, (size_t)N * Kp);
+  WS_CHECK(wp);
+  RET_IF(launch_pack_weight(w, N, Kp, 1, 0, 0, wp, s, K, xp ? 1 : 0));  // xp: [w_hi | w_hi | w_lo], as pack_conv does
+  ConvW cw;
+  cw.w = wp; cw.bias = const_cast<float*>(bias); cw.N = N; cw.Cin = Kp; cw.taps = 1; cw.xp = xp ? 1 : 0; cw.cin_l = K;
+  GemmArgs g;
+  g.a = a; g.a_f32 = 1; g.lda = K; g.w = &cw;
+  if (xp || a_half) {
+    half_t* ah = ws_alloc<half_t>(c, (size_t)rows * Kp);
+    WS_CHECK(ah);
+    if (xp) RET_IF(launch_rows_f32_to_f16_split(a, K, rows, K, ah, s));  // [a_hi | a_lo | a_hi]
+    else RET_IF(launch_f32_to_f16(a, ah, (size_t)rows * K, s));
+    g.a = ah; g.a_f32 = 0; g.lda = Kp;
+  }
+  RET_IF(ex_epi_fill(c, e, (size_t)rows, N, g, s));
+  if (sk_used) *sk_used = 1;
+  if (poison) RET_IF(ex_poison(c, s));
+  return op_sync("op_linear_ex", s, run_linear(c, g, B, rows, s));
+}
+
+// x / resid / out channels-last ([B][H][W][Cin], [B][Ho][Wo][ldr], [B*Ho*Wo + 1][ldc]); w [Cout][Cin][k][k].  tap_shift = 1 is the
+// first-stage encoder's Downsample (zero padding on the right and bottom only): 3x3, stride 2, EVEN H and W only -- the encoder
+// never runs it otherwise, and for an odd side the output grid of F.pad(x, (0, 1, 0, 1)) + conv(k3, s2, p0) is not run_conv2d's.
+// upsample: the fused nearest x2 (run_conv2d), or with up_fold != 0 the four parity-folded 2x2 convolutions (run_upconv2d).
+int mvd_op_conv_ex(mvd_ctx* c, const float* x, int B, int H, int W, int Cin, const float* w, const float* bias, int Cout, int ksize,
+                   int stride, int upsample, int up_fold, int tap_shift, const float* rowbias, int rb_ld, float alpha, int act,
+                   int use_bias, int out_f16, int out_split, int ldc, const float* resid, int resid_f16, int ldr, int a_half,
+                   int force_splitk, int xp, int conv3x_stream, float* slabs, size_t slabs_cap, int defer_epilogue, int* sk_used,
+                   int poison, void* out, void* stream) {
+  RET_IF(ex_begin(c));
+  if (!x || !w) return mvd_fail("op_conv_ex: null operand");
+  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || (Cin & 7)) return mvd_fail("op_conv_ex: Cin % 8 == 0 expected");
+  if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2) || (upsample != 0 && upsample != 1))
+    return mvd_fail("op_conv_ex: 1x1 or 3x3, stride 1 or 2, upsample 0 or 1");
+  if (tap_shift != 0 && (tap_shift != 1 || ksize != 3 || stride != 2 || upsample || (H & 1) || (W & 1)))
+    return mvd_fail("op_conv_ex: tap_shift = 1 is the 3x3 stride-2 Downsample of even H and W");
+  if (up_fold && (!upsample || ksize != 3 || stride != 1 || xp || slabs))
+    return mvd_fail("op_conv_ex: the parity-folded form is a 3x3 stride-1 upsample conv without xp or a slab buffer");
+  const ExEpi e{bias, rowbias, resid, rb_ld, act, use_bias, out_f16, out_split, ldc, resid_f16, ldr, force_splitk, alpha,
+                slabs, slabs_cap, defer_epilogue, sk_used, out};
+  RET_IF(ex_epi_check("op_conv_ex", e, Cout));
+  hipStream_t s = S(stream);
+  WsScope ws_scope(c);
+  const int taps = ksize * ksize, Cp = xp ? 3 * Cin : Cin;
+  const int Ho = ((H << upsample) - 1) / stride + 1, Wo = ((W << upsample) - 1) / stride + 1;
+  const size_t rows_in = (size_t)B * H * W, rows_out = (size_t)B * Ho * Wo;
+  half_t* wp = ws_alloc<half_t>(c, (size_t)taps * Cout * Cp);
+  WS_CHECK(wp);
+  RET_IF(launch_pack_weight(w, Cout, Cp, taps, 0, 0, wp, s, Cin, xp ? 1 : 0));
+  ConvW cw;
+  cw.w = wp; cw.bias = const_cast<float*>(bias); cw.N = Cout; cw.Cin = Cp; cw.taps = taps; cw.xp = xp ? 1 : 0; cw.cin_l = Cin;
+  GemmArgs g;
+  g.a = x; g.a_f32 = 1; g.lda = Cin; g.w = &cw; g.tap_shift = tap_shift;
+  if (xp || a_half) {
+    half_t* xh = ws_alloc<half_t>(c, rows_in * Cp);
+    WS_CHECK(xh);
+    if (xp) RET_IF(launch_rows_f32_to_f16_split(x, Cin, (long)rows_in, Cin, xh, s));
+    else RET_IF(launch_f32_to_f16(x, xh, rows_in * Cin, s));
+    g.a = xh; g.a_f32 = 0; g.lda = Cp;
+  }
+  const int bnx = Cout % 160 == 0 ? 160 : (Cout % 128 == 0 ? 128 : 0);
+  if (conv3x_stream && taps == 9 && bnx && Cp % 64 == 0 && !g.a_f32) {  // the weights as a conv3x fragment stream too (k_conv3x.hip)
+    cw.wx = ws_alloc<half_t>(c, conv3x_stream_halfs(Cout, Cp, bnx));
+    WS_CHECK(cw.wx);
+    RET_IF(conv3x_pack(wp, Cout, Cp, bnx, cw.wx, s));
+    cw.wx_bn = bnx;
+  }
+  if (up_fold) {
+    cw.w_up = ws_alloc<half_t>(c, (size_t)16 * Cout * Cin);
+    WS_CHECK(cw.w_up);
+    RET_IF(launch_pack_upconv_weight(w, Cout, Cin, cw.w_up, s));
+  }
+  RET_IF(ex_epi_fill(c, e, rows_out, Cout, g, s));
+  if (sk_used) *sk_used = 1;
+  if (poison) RET_IF(ex_poison(c, s));
+  return op_sync("op_conv_ex", s, up_fold ? run_upconv2d(c, g, B, H, W, s) : run_conv2d(c, g, B, H, W, stride, upsample, s));
+}
+
+// x: nslab slabs of channels-last [B][rows][ld] fp32, slab_stride floats apart.  form 0: run_group_norm's own choice; form 1: the
+// two-pass pair (launch_gn_stats + launch_gn_apply) called directly, which takes one slab and writes neither `mat` nor fp32.
+// out: [B * rows + 1][ldo] halfs (split = 1: [hi | lo | hi] rows; split = 2: fp32 rows of ldo / 2 floats); mat: [B * rows + 1][ldm].
+int mvd_op_group_norm_ex(mvd_ctx* c, const float* x, int B, int rows, int C, int ld, int groups, const float* gamma, const float* beta,
+                         float eps, int act, int form, const float* preadd, int pld, int split, int nslab, size_t slab_stride,
+                         const float* bias2, const float* resid, int ldr, float* mat, int ldm, int ldo, int poison, void* out,
+                         void* stream) {
+  RET_IF(ex_begin(c));
+  if (!x || !gamma || !beta || !out) return mvd_fail("op_group_norm_ex: null operand");
+  if (B <= 0 || rows <= 0 || C <= 0 || groups <= 0 || C % groups || ld < C) return mvd_fail("op_group_norm_ex: C % groups == 0 and ld >= C expected");
+  if (act < ACT_NONE || act > ACT_RELU || (form != 0 && form != 1) || split < 0 || split > 2) return mvd_fail("op_group_norm_ex: act 0..2, form 0..1, split 0..2");
+  if (ldo < (split == 1 ? 3 : (split == 2 ? 2 : 1)) * C) return mvd_fail("op_group_norm_ex: ldo >= C halfs (3 C with split = 1, 2 C with split = 2)");
+  if (nslab < 1 || (nslab > 1 && slab_stride < (size_t)B * rows * ld)) return mvd_fail("op_group_norm_ex: slabs overlap");
+  if (preadd && pld < C) return mvd_fail("op_group_norm_ex: pld >= C expected");
+  if ((resid && ldr < C) || (mat && ldm < C)) return mvd_fail("op_group_norm_ex: ldr, ldm >= C expected");
+  const bool one_pass = !mvd_env().gn_two_pass && gn_group_eligible(ld, rows, C, groups, preadd ? pld : 0, ldo);
+  if ((form == 1 || !one_pass) && (nslab > 1 || bias2 || resid || mat || split == 2))
+    return mvd_fail("op_group_norm_ex: slabs, bias2, resid, mat and the fp32 result need the single-pass form");
+  hipStream_t s = S(stream);
+  WsScope ws_scope(c);
+  NormW n;
+  n.g = const_cast<float*>(gamma); n.b = const_cast<float*>(beta); n.C = C;
+  half_t* o = (half_t*)out;
+  if (form == 0) {
+    if (poison) RET_IF(ex_poison(c, s));
+    return op_sync("op_group_norm_ex", s,
+                   run_group_norm(c, x, ld, B, rows, n, groups, eps, act, preadd, o, ldo, s, pld, split, nslab, slab_stride, bias2, resid,
+                                  ldr, mat, ldm));
+  }
+  if (C > 2560 || groups > 32 || (C & 3) || (ld & 3) || (ldo & 3) || (preadd && (pld & 3)))
+    return mvd_fail("op_group_norm_ex: the two-pass form takes C <= 2560, groups <= 32 and C, ld, ldo, pld % 4 == 0");
+  float* partial = ws_alloc<float>(c, (size_t)B * gn_max_slabs() * groups * 2);
+  WS_CHECK(partial);
+  if (poison) RET_IF(ex_poison(c, s));
+  int nsl = 0;
+  int rc = launch_gn_stats(x, ld, B, rows, C, groups, preadd, pld, partial, &nsl, s);
+  if (!rc) rc = launch_gn_apply(x, ld, B, rows, C, groups, preadd, pld, partial, nsl, gamma, beta, eps, act, o, ldo, s, split);
+  return op_sync("op_group_norm_ex", s, rc);
+}
+
+// plain == 0: launch_layernorm_slabs with every LnSlabs field (mat [rows + 1][C] is required); plain != 0: launch_layernorm on
+// one slab, where only the fp16 copy `raw` ([rows + 1][ld_raw] halfs, may be NULL) is left of them.  out: [rows + 1][C] halfs.
+int mvd_op_layer_norm_slabs(mvd_ctx* c, const float* slabs, int nslab, size_t slab_stride, int rows, int C, const float* bias,
+                            const float* rowbias, int rb_ld, int T, const float* resid, int ldr, const float* gamma, const float* beta,
+                            float eps, int plain, int ld_raw, int poison, float* mat, void* raw, void* out, void* stream) {
+  RET_IF(ex_begin(c));
+  if (!slabs || !gamma || !beta || !out) return mvd_fail("op_layer_norm_slabs: null operand");
+  if (rows <= 0 || C <= 0 || nslab < 1 || T < 1) return mvd_fail("op_layer_norm_slabs: bad argument");
+  if (raw && ld_raw < C) return mvd_fail("op_layer_norm_slabs: ld_raw >= C expected");
+  hipStream_t s = S(stream);
+  if (plain) {
+    if (nslab != 1 || bias || rowbias || resid || mat) return mvd_fail("op_layer_norm_slabs: the plain LayerNorm takes one slab and writes no mat");
+    if (poison) RET_IF(ex_poison(c, s));
+    return op_sync("op_layer_norm_slabs", s, launch_layernorm(slabs, rows, C, gamma, beta, eps, (half_t*)out, s, (half_t*)raw, ld_raw));
+  }
+  if (!mat) return mvd_fail("op_layer_norm_slabs: mat is required");
+  if (nslab > 1 && slab_stride < (size_t)rows * C) return mvd_fail("op_layer_norm_slabs: slabs overlap");
+  if ((rowbias && rb_ld < C) || (resid && ldr < C)) return mvd_fail("op_layer_norm_slabs: rb_ld, ldr >= C expected");
+  if (poison) RET_IF(ex_poison(c, s));
+  return op_sync("op_layer_norm_slabs", s,
+                 launch_layernorm_slabs(slabs, nslab, slab_stride, rows, C, bias, rowbias, rb_ld, T, resid, ldr, mat, gamma, beta, eps,
+                                        (half_t*)out, s, (half_t*)raw, ld_raw));
+}
+
+// The three steps of the folded GroupNorm(proj_context(volume)) (engine_unet.hip: ctx_fold) on caller data: x [B * rps][K], w [N][K],
+// N / cpg groups.  partials [B * rps / 256 + 1][N / cpg][2], scale and shift [B + 1][N], out [B * rps + 1][N] halfs.
+int mvd_op_folded_group_norm(mvd_ctx* c, const float* x, int B, int rps, int K, const float* w, int N, int cpg, const float* gamma,
+                             const float* beta, float eps, int poison, float* partials, float* scale, float* shift, void* out,
+                             void* stream) {
+  RET_IF(ex_begin(c));
+  if (!x || !w || !gamma || !beta || !partials || !scale || !shift || !out) return mvd_fail("op_folded_group_norm: null operand");
+  if (B <= 0 || rps <= 0 || K <= 0 || (K & 7) || N <= 0 || (N & 3)) return mvd_fail("op_folded_group_norm: K % 8 == 0 and N % 4 == 0 expected");
+  // what ctx_fold_ok asks of a context level
+  if (rps % 256 || (cpg != 8 && cpg != 16 && cpg != 32) || (long)B * rps < 512)
+    return mvd_fail("op_folded_group_norm: rps % 256 == 0, 8 / 16 / 32 channels per group and at least 512 rows expected");
+  if (N % cpg || N / cpg > 32) return mvd_fail("op_folded_group_norm: at most 32 whole groups expected");
+  hipStream_t s = S(stream);
+  WsScope ws_scope(c);
+  const int rows = B * rps, G = N / cpg, ntile = rps / 256;
+  half_t* wp = ws_alloc<half_t>(c, (size_t)N * K);
+  half_t* xh = ws_alloc<half_t>(c, (size_t)rows * K);
+  WS_CHECK(wp && xh);
+  RET_IF(launch_pack_weight(w, N, K, 1, 0, 0, wp, s, K, 0));
+  RET_IF(launch_f32_to_f16(x, xh, (size_t)rows * K, s));
+  ConvW cw;
+  cw.w = wp; cw.N = N; cw.Cin = K; cw.taps = 1;
+  if (poison) RET_IF(ex_poison(c, s));
+  GemmArgs g;
+  g.a = xh; g.lda = K; g.w = &cw; g.use_bias = false; g.gn_partial = partials; g.gn_cpg = cpg; g.force_splitk = 1;
+  int rc = run_linear(c, g, B, rows, s);
+  if (!rc) rc = launch_gn_finalize(partials, B, ntile, rps, N, G, gamma, beta, eps, scale, shift, N, s);
+  if (!rc) {
+    g = GemmArgs();
+    g.a = xh; g.lda = K; g.w = &cw; g.use_bias = false; g.out = out; g.out_f32 = 0; g.ldc = N;
+    g.rowscale = scale; g.rs_ld = N; g.rowbias = shift; g.rb_ld = N; g.act = ACT_RELU; g.force_splitk = 1;
+    rc = run_linear(c, g, B, rows, s);
+  }
+  return op_sync("op_folded_group_norm", s, rc);
+}
+
+// softmax_rows_kernel (out_f32 == 0: fp16 probabilities) / softmax_rows_f32_kernel on [rows][cols] fp32 scores; out [rows + 1][cols]
+int mvd_op_softmax_rows(mvd_ctx* c, const float* scores, int rows, int cols, int out_f32, void* out, void* stream) {
+  RET_IF(ex_begin(c));
+  if (!scores || !out || rows <= 0 || cols <= 0) return mvd_fail("op_softmax_rows: bad argument");
+  hipStream_t s = S(stream);
+  return op_sync("op_softmax_rows", s,
+                 out_f32 ? launch_softmax_rows_f32(scores, rows, cols, (float*)out, s) : launch_softmax_rows(scores, rows, cols, (half_t*)out, s));
+}
+
+// launch_rows_f32_to_f16_split: fp32 rows `lda` floats apart -> [hi | lo | hi] rows of 3 C halfs; out [rows + 1][3 C]
+int mvd_op_rows_split(mvd_ctx* c, const float* x, int lda, int rows, int C, void* out, void* stream) {
+  RET_IF(ex_begin(c));
+  if (!x || !out || rows <= 0 || C <= 0 || lda < C) return mvd_fail("op_rows_split: bad argument");
+  hipStream_t s = S(stream);
+  return op_sync("op_rows_split", s, launch_rows_f32_to_f16_split(x, lda, rows, C, (half_t*)out, s));
+}
+
 }  // extern "C"

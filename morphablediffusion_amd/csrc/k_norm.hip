@@ -697,7 +697,6 @@ int launch_gn_finalize(const float* partial, int B, int nslabs, int rows_per_sam
 
 int launch_layernorm(const float* x, int rows, int C, const float* gamma, const float* beta, float eps, half_t* out,
                      hipStream_t s, half_t* raw, int ld_raw) {
-  if (C > 64 * 24) return mvd_fail("layernorm: C too large");
   if (raw && (!layernorm_slabs_takes(C) || (ld_raw & 7) || ((uintptr_t)raw & 15) || (((uintptr_t)x | (uintptr_t)out) & 15)))
     return mvd_fail("layernorm: the fp16 copy of the input needs a width of 8 * L * 5 and 16-byte aligned rows");
   LnSlabs sl = LnSlabs();
@@ -719,6 +718,7 @@ int launch_layernorm(const float* x, int rows, int C, const float* gamma, const 
 #undef MVD_LNV
   }
   if (raw) return mvd_fail("layernorm: the fp16 copy of the input is written by the vector form only (MVD_LN_SCALAR / alignment)");
+  if (C > 64 * 24) return mvd_fail("layernorm: C too large");  // the element-per-thread form holds 24 values per lane
   hipLaunchKernelGGL(layernorm_kernel<half_t>, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, (long)C, rows, C, gamma, beta, eps, out);
   HIP_CHECK_RET(hipGetLastError());
   return 0;

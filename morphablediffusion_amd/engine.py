@@ -3,6 +3,7 @@ library by pointer (PyTorch is used for device memory and streams only)."""
 import collections
 import ctypes as C
 import os
+import types
 from typing import Dict, Optional
 
 import torch
@@ -1140,6 +1141,226 @@ class Engine:
         L.check(self.lib.mvd_op_linear(self._ctx, L.ptr(a), M, K, L.ptr(w), L.ptr(b), N, bool(geglu), L.ptr(r),
                                        bool(a_half), force_splitk, L.ptr(out), _stream()))
         return out
+
+    # ---- forward-form hooks (tests/test_gpu_epilogue_forms.py): result buffers are allocated here with one guard row behind them
+    # (and pad columns where ld > width), preset to 0xFF bytes -- NaN in every type the kernels write; each wrapper asserts that
+    # the guard came back unchanged
+    def _guarded(self, rows, ld, f32=True):
+        dt = torch.float32 if f32 else (torch.float16 if L.DTYPE == "f16" else torch.bfloat16)
+        t = torch.empty(rows + 1, ld, device=self.device, dtype=dt)
+        t.view(torch.int32 if f32 else torch.int16).fill_(-1)
+        return t
+
+    @staticmethod
+    def _guard_intact(t, rows, width, what):
+        bits = t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+        ok = bool((bits[rows:] == -1).all()) and bool((bits[:rows, width:] == -1).all())
+        assert ok, f"{what}: the launch wrote outside its result (guard row / pad columns changed)"
+
+    def _epi_args(self, rows, N, B, bias, rowbias, rb_ld, resid, ldr, out_f16, out_split, ldc, defer_cap):
+        """Stages the epilogue operands shared by op_linear_ex / op_conv_ex; rows: output rows."""
+        dev = self.device
+        if out_split and not out_f16:
+            raise ValueError("out_split is a form of the 16-bit result")
+        width = 3 * N if out_split else N
+        ldc = ldc or width
+        b = None if bias is None else _f32(bias, dev)
+        rb = None
+        if rowbias is not None:
+            rb_ld = rb_ld or N
+            rb = torch.full((B, rb_ld), float("nan"), device=dev)
+            rb[:, :N] = _f32(rowbias, dev).reshape(B, N)
+        r = None
+        if resid is not None:
+            ldr = ldr or N
+            r = torch.full((rows, ldr), float("nan"), device=dev)
+            r[:, :N] = _f32(resid, dev).reshape(rows, N)
+        out = self._guarded(rows, ldc, f32=not out_f16)
+        slabs = None
+        if defer_cap:
+            slabs = torch.empty(defer_cap + N, device=dev)  # one guard row behind the offered capacity
+            slabs.view(torch.int32).fill_(-1)
+        return b, rb, rb_ld or 0, r, ldr or 0, out, ldc, width, slabs
+
+    def _epi_result(self, what, out, rows, N, width, out_split, slabs, defer_cap, sk_used):
+        self._guard_intact(out, rows, width, what)
+        res = types.SimpleNamespace(raw=out[:rows], sk_used=sk_used, slabs=None, hi=None, lo=None, third=None)
+        bits = out.view(torch.int32 if out.dtype == torch.float32 else torch.int16)
+        res.out_untouched = bool((bits == -1).all())
+        if out_split:
+            res.hi, res.lo, res.third = out[:rows, :N], out[:rows, N:2 * N], out[:rows, 2 * N:3 * N]
+            res.out = res.hi.float() + res.lo.float()
+        else:
+            res.out = out[:rows, :N].float()
+        if slabs is not None:
+            used = sk_used * rows * N if sk_used > 1 else 0
+            assert used <= defer_cap, f"{what}: sk_used = {sk_used} does not fit the offered slab capacity"
+            assert bool((slabs.view(torch.int32)[used:] == -1).all()), f"{what}: the launch wrote behind the slabs it reported"
+            if sk_used > 1:
+                res.slabs = slabs[:used].reshape(sk_used, rows, N)
+        return res
+
+    def op_linear_ex(self, a, w, bias=None, B=1, rowbias=None, rb_ld=0, alpha=1.0, act=0, use_bias=True, out_f16=False,
+                     out_split=False, ldc=0, resid=None, resid_f16=False, ldr=0, a_half=False, force_splitk=0, xp=False, defer_cap=0,
+                     defer_epilogue=False, poison=True):
+        """mvd_op_linear_ex: a [rows][K], w [N][K], rowbias [B][N], resid [rows][N] -> a namespace with .out (fp32 [rows][N]; hi + lo
+        with out_split, then also .hi / .lo / .third, the raw 16-bit blocks), .raw (the result rows as written), .sk_used, .slabs
+        ([sk_used][rows][N] when the launch deferred its reduction, else None) and .out_untouched (all of `out` still 0xFF)."""
+        dev = self.device
+        a, w = _f32(a, dev), _f32(w, dev)
+        rows, K = a.shape
+        N = w.shape[0]
+        b, rb, rb_ld, r, ldr, out, ldc, width, slabs = self._epi_args(rows, N, B, bias, rowbias, rb_ld, resid, ldr, out_f16, out_split,
+                                                                      ldc, defer_cap)
+        sk = C.c_int(-1)
+        L.check(self.lib.mvd_op_linear_ex(self._ctx, L.ptr(a), B, rows, K, L.ptr(w), L.ptr(b), N, L.ptr(rb), rb_ld, alpha, act,
+                                          bool(use_bias and b is not None), bool(out_f16), bool(out_split), ldc, L.ptr(r), bool(resid_f16),
+                                          ldr, bool(a_half), force_splitk, bool(xp), L.ptr(slabs), defer_cap, bool(defer_epilogue),
+                                          C.byref(sk), bool(poison), L.ptr(out), _stream()))
+        return self._epi_result("op_linear_ex", out, rows, N, width, out_split, slabs, defer_cap, sk.value)
+
+    def op_conv_ex(self, x, w, bias=None, stride=1, upsample=0, up_fold=False, tap_shift=0, rowbias=None, rb_ld=0, alpha=1.0, act=0,
+                   use_bias=True, out_f16=False, out_split=False, ldc=0, resid=None, resid_f16=False, ldr=0, a_half=True, force_splitk=0,
+                   xp=False, conv3x=True, defer_cap=0, defer_epilogue=False, poison=True):
+        """mvd_op_conv_ex: x [B,Cin,H,W], w [Cout,Cin,k,k], rowbias [B,Cout], resid [B,Cout,Ho,Wo] (reference layouts; the hook's
+        channels-last images are made here) -> the namespace of op_linear_ex, plus .nchw ([B,Cout,Ho,Wo] fp32)."""
+        dev = self.device
+        x, w = _f32(x, dev), _f32(w, dev)
+        B, Cin, H, W = x.shape
+        Cout, k = w.shape[0], w.shape[2]
+        Ho, Wo = ((H << upsample) - 1) // stride + 1, ((W << upsample) - 1) // stride + 1
+        rows = B * Ho * Wo
+        xl = x.permute(0, 2, 3, 1).contiguous()
+        rl = None if resid is None else _f32(resid, dev).permute(0, 2, 3, 1).reshape(rows, Cout)
+        b, rb, rb_ld, r, ldr, out, ldc, width, slabs = self._epi_args(rows, Cout, B, bias, rowbias, rb_ld, rl, ldr, out_f16, out_split,
+                                                                      ldc, defer_cap)
+        sk = C.c_int(-1)
+        L.check(self.lib.mvd_op_conv_ex(self._ctx, L.ptr(xl), B, H, W, Cin, L.ptr(w), L.ptr(b), Cout, k, stride, upsample, bool(up_fold),
+                                        tap_shift, L.ptr(rb), rb_ld, alpha, act, bool(use_bias and b is not None), bool(out_f16),
+                                        bool(out_split), ldc, L.ptr(r), bool(resid_f16), ldr, bool(a_half), force_splitk, bool(xp),
+                                        bool(conv3x), L.ptr(slabs), defer_cap, bool(defer_epilogue), C.byref(sk), bool(poison), L.ptr(out),
+                                        _stream()))
+        res = self._epi_result("op_conv_ex", out, rows, Cout, width, out_split, slabs, defer_cap, sk.value)
+        res.nchw = res.out.reshape(B, Ho, Wo, Cout).permute(0, 3, 1, 2).contiguous()
+        return res
+
+    def op_group_norm_ex(self, x, groups, gamma, beta, eps=1e-5, act=0, form=0, ld=0, preadd=None, pld=0, split=0, bias2=None,
+                         resid=None, ldr=0, mat=False, ldm=0, ldo=0, poison=True):
+        """mvd_op_group_norm_ex: x [nslab, B, rows, C] channels-last slabs (or [B, rows, C]); preadd [B, C], bias2 [C], resid
+        [B, rows, C] -> (out fp32 [B, rows, C] -- hi + lo with split = 1, NaN where the third block differs from the first --,
+        mat fp32 [B, rows, C] or None).  ld / pld / ldr / ldm / ldo: row strides (0: dense); pad columns of the inputs hold NaN."""
+        dev = self.device
+        x = _f32(x, dev)
+        if x.dim() == 3:
+            x = x[None]
+        nslab, B, rows, Cc = x.shape
+        ld = ld or Cc
+
+        def padded(t, lead, ldt):
+            p = torch.full((*lead, ldt), float("nan"), device=dev)
+            p[..., :Cc] = _f32(t, dev).reshape(*lead, Cc)
+            return p
+        xs = padded(x, (nslab, B, rows), ld)
+        pre = None if preadd is None else padded(preadd, (B,), pld or Cc)
+        res = None if resid is None else padded(resid, (B, rows), ldr or Cc)
+        b2 = None if bias2 is None else _f32(bias2, dev)
+        g, bt = _f32(gamma, dev), _f32(beta, dev)
+        wmul = 3 if split == 1 else 1
+        ldo_h = ldo or ((2 if split == 2 else wmul) * Cc)  # in 16-bit elements, as run_group_norm counts it
+        if split == 2:
+            out = self._guarded(B * rows, ldo_h // 2, f32=True)
+        else:
+            out = self._guarded(B * rows, ldo_h, f32=False)
+        m = self._guarded(B * rows, ldm or Cc, f32=True) if mat else None
+        L.check(self.lib.mvd_op_group_norm_ex(self._ctx, L.ptr(xs), B, rows, Cc, ld, groups, L.ptr(g), L.ptr(bt), eps, act, form,
+                                              L.ptr(pre), (pld or Cc) if pre is not None else 0, split, nslab, B * rows * ld, L.ptr(b2),
+                                              L.ptr(res), (ldr or Cc) if res is not None else 0, L.ptr(m), (ldm or Cc) if mat else 0,
+                                              ldo_h, bool(poison), L.ptr(out), _stream()))
+        self._guard_intact(out, B * rows, wmul * Cc, "op_group_norm_ex")
+        if mat:
+            self._guard_intact(m, B * rows, Cc, "op_group_norm_ex (mat)")
+        if split == 1:
+            hi, lo, third = out[:-1, :Cc], out[:-1, Cc:2 * Cc], out[:-1, 2 * Cc:3 * Cc]
+            y = hi.float() + lo.float()
+            y[hi.view(torch.int16) != third.view(torch.int16)] = float("nan")
+        else:
+            y = out[:-1, :Cc].float()
+        return y.reshape(B, rows, Cc), (m[:-1, :Cc].reshape(B, rows, Cc).clone() if mat else None)
+
+    def op_layer_norm_slabs(self, slabs, gamma, beta, bias=None, rowbias=None, rb_ld=0, T=None, resid=None, ldr=0, eps=1e-5,
+                            plain=False, raw=False, ld_raw=0, poison=True):
+        """mvd_op_layer_norm_slabs: slabs [nslab, rows, C] (or [rows, C]), rowbias [ceil(rows / T), C], resid [rows, C] ->
+        (out fp32 [rows, C], mat fp32 [rows, C] or None with plain, raw 16-bit [rows, C] or None)."""
+        dev = self.device
+        x = _f32(slabs, dev)
+        if x.dim() == 2:
+            x = x[None]
+        nslab, rows, Cc = x.shape
+        g, bt = _f32(gamma, dev), _f32(beta, dev)
+        b = None if bias is None else _f32(bias, dev)
+        rb = None
+        if rowbias is not None:
+            rb = torch.full((rowbias.shape[0], rb_ld or Cc), float("nan"), device=dev)
+            rb[:, :Cc] = _f32(rowbias, dev)
+        r = None
+        if resid is not None:
+            r = torch.full((rows, ldr or Cc), float("nan"), device=dev)
+            r[:, :Cc] = _f32(resid, dev)
+        out = self._guarded(rows, Cc, f32=False)
+        m = None if plain else self._guarded(rows, Cc, f32=True)
+        rw = self._guarded(rows, ld_raw or Cc, f32=False) if raw else None
+        L.check(self.lib.mvd_op_layer_norm_slabs(self._ctx, L.ptr(x), nslab, rows * Cc, rows, Cc, L.ptr(b), L.ptr(rb),
+                                                 (rb_ld or Cc) if rb is not None else 0, T or rows, L.ptr(r),
+                                                 (ldr or Cc) if r is not None else 0, L.ptr(g), L.ptr(bt), eps, bool(plain),
+                                                 (ld_raw or Cc) if raw else 0, bool(poison), L.ptr(m), L.ptr(rw), L.ptr(out), _stream()))
+        self._guard_intact(out, rows, Cc, "op_layer_norm_slabs")
+        if m is not None:
+            self._guard_intact(m, rows, Cc, "op_layer_norm_slabs (mat)")
+        if rw is not None:
+            self._guard_intact(rw, rows, Cc, "op_layer_norm_slabs (raw)")
+        return out[:rows].float(), (None if m is None else m[:rows].clone()), (None if rw is None else rw[:rows, :Cc].clone())
+
+    def op_folded_group_norm(self, x, w, cpg, gamma, beta, B, eps=1e-5, poison=True):
+        """mvd_op_folded_group_norm: x [B * rps][K], w [N][K] -> (partials [B, rps / 256, N / cpg, 2], scale [B, N], shift [B, N],
+        out fp32 [B * rps][N] = relu(group_norm(x @ w^T)) as the apply pass wrote it in 16 bits)."""
+        dev = self.device
+        x, w, g, bt = _f32(x, dev), _f32(w, dev), _f32(gamma, dev), _f32(beta, dev)
+        rows, K = x.shape
+        N = w.shape[0]
+        if B <= 0 or rows % B or cpg <= 0 or N % cpg:
+            raise L.MvdError("op_folded_group_norm: rows % B == 0 and N % cpg == 0 expected")
+        rps, G = rows // B, N // cpg
+        ntile = max(rps // 256, 1)
+        part = self._guarded(B * ntile, 2 * G)
+        sc, sh = self._guarded(B, N), self._guarded(B, N)
+        out = self._guarded(rows, N, f32=False)
+        L.check(self.lib.mvd_op_folded_group_norm(self._ctx, L.ptr(x), B, rps, K, L.ptr(w), N, cpg, L.ptr(g), L.ptr(bt), eps,
+                                                  bool(poison), L.ptr(part), L.ptr(sc), L.ptr(sh), L.ptr(out), _stream()))
+        for t, n, name in ((part, B * ntile, "partials"), (sc, B, "scale"), (sh, B, "shift"), (out, rows, "out")):
+            self._guard_intact(t, n, t.shape[1], f"op_folded_group_norm ({name})")
+        return part[:-1].reshape(B, ntile, G, 2).clone(), sc[:B].clone(), sh[:B].clone(), out[:rows].float()
+
+    def op_softmax_rows(self, scores, out_f32=False):
+        """mvd_op_softmax_rows: [rows][cols] fp32 scores -> probabilities, fp32 or the kernels' 16-bit type (returned as written)."""
+        s = _f32(scores, self.device)
+        rows, cols = s.shape
+        out = self._guarded(rows, cols, f32=bool(out_f32))
+        L.check(self.lib.mvd_op_softmax_rows(self._ctx, L.ptr(s), rows, cols, bool(out_f32), L.ptr(out), _stream()))
+        self._guard_intact(out, rows, cols, "op_softmax_rows")
+        return out[:rows].clone()
+
+    def op_rows_split(self, x, lda=0):
+        """mvd_op_rows_split (launch_rows_f32_to_f16_split): x [rows][C] -> (hi, lo, third), the raw 16-bit blocks."""
+        dev = self.device
+        x = _f32(x, dev)
+        rows, Cc = x.shape
+        lda = lda or Cc
+        xp = torch.full((rows, lda), float("nan"), device=dev)
+        xp[:, :Cc] = x
+        out = self._guarded(rows, 3 * Cc, f32=False)
+        L.check(self.lib.mvd_op_rows_split(self._ctx, L.ptr(xp), lda, rows, Cc, L.ptr(out), _stream()))
+        self._guard_intact(out, rows, 3 * Cc, "op_rows_split")
+        return out[:rows, :Cc].clone(), out[:rows, Cc:2 * Cc].clone(), out[:rows, 2 * Cc:].clone()
 
     def op_group_norm(self, x, groups, gamma, beta, eps, act=0):
         dev = self.device
