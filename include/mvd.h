@@ -346,6 +346,52 @@ int mvd_op_train_loss(const float* pred, const float* target, int B, int HW, int
  * launch nothing.  Synchronises the stream (its scratch lives for the call). */
 int mvd_op_image_metrics(const void* pred, int pred_dtype, int pred_layout, const void* target, int target_dtype, int target_layout,
                          const unsigned char* mask, int mask_mode, int V, int H, int W, double* out, void* stream);
+/* Mesh texturing from generated views (csrc/k_mesh.hip): an exact visibility rasteriser of the conditioning mesh into the N target
+ * cameras and a per-vertex fusion of the view colours under that visibility.  No context; device pointers; each call
+ * synchronises the stream (the rasteriser's scratch lives for the call).  Everything downstream of the projection is integer
+ * arithmetic, defined here so that it can be reproduced exactly.
+ *   constants     SUB = 4: screen coordinates are int32 in 1/16 pixel; KMAX = 2^24 - 1; guard band |u|, |v| <= 4096 px.  These
+ *                 keep every edge function within 2^35 and every key interpolation within 2^59 in int64.
+ *   mvd_op_mesh_project   one thread per (view, vertex), fp32: cam = R x + t (RT [N,3,4], world -> camera),
+ *                 u = (K00 X + K01 Y) / Z + K02, v = K11 Y / Z + K12 (K [N,3,3]); pixel (i, j) has its centre at (u, v) = (j, i),
+ *                 the conditioner's convention.  xy [N,Nv,2] = rint(16 u), rint(16 v); key [N,Nv] = clamp(rint(z_near / Z KMAX),
+ *                 1, KMAX): a larger key is nearer, and z_near / Z is linear in screen space, so that integer interpolation of
+ *                 keys orders depth correctly.  key = 0 (and xy = 0) marks an invalid vertex: Z < z_near, a non-finite value, or
+ *                 a point outside the guard band.
+ *   mvd_op_mesh_raster    faces [Nf,3] int32.  A face is skipped in a view if one of its vertices is invalid there (key outside
+ *                 1..KMAX or a coordinate beyond the guard band, whoever produced them), if one of its indices is outside
+ *                 [0, Nv) -- never dereferenced, and counted once per face into *bad_faces (one device int) -- or if
+ *                 A = (x1 - x0)(y2 - y0) - (y1 - y0)(x2 - x0) is zero.  A < 0: vertices 1 and 2 are swapped (both windings are
+ *                 drawn).  Edge functions: for k = 0, 1, 2 with a = v[(k+1)%3], b = v[(k+2)%3], dx = bx - ax, dy = by - ay,
+ *                 e_k(p) = dx (py - ay) - dy (px - ax) at p = (16 j, 16 i).  Pixel (i, j) is covered iff for every k: e_k > 0, or
+ *                 e_k == 0 and the edge is owned (dy < 0, or dy == 0 and dx > 0) -- a shared edge belongs to exactly one of
+ *                 its two faces.  Pixel key = (e_0 key_0 + e_1 key_1 + e_2 key_2) / A, int64, truncating.  Winner per pixel: the
+ *                 largest key, ties to the smallest face index, independent of arrival order (a 64-bit atomic maximum of
+ *                 (key << 32) | (0xFFFFFFFF - f), then a resolve launch).  face_id [N,H,W]: -1 background; pix_key [N,H,W]:
+ *                 0 background.  Bounding boxes are clamped to the image before any loop.
+ *   mvd_op_mesh_vertex_colors   one thread per vertex, views in index order.  Nearest pixel pj = (xs + 8) >> 4,
+ *                 pi = (ys + 8) >> 4.  The vertex is visible in view n iff it is valid there, that pixel is inside the image and
+ *                 covered, and the winning face there has the vertex as a corner or key_v + bias >= pix_key.  Weight
+ *                 w_n = max(0, cos)^power (two_sided: |cos|^power), cos between the vertex normal (normals [Nv,3], any length)
+ *                 and the direction from the vertex (verts [Nv,3]) to the camera centre (centres [N,3]); a zero normal weighs 0.
+ *                 Colour of a view: bilinear, clamp to edge, sampled at the SNAPPED position (xs / 16, ys / 16); images are
+ *                 dtype 0 float32 in [-1, 1] mapped (clamp + 1) / 2, or 1 uint8 / 255; layout 0 [N,3,H,W], 1 [N,H,W,3].
+ *                 color [Nv,3] = sum w c / sum w; weight_sum [Nv]; n_seen [Nv] = views passing the integer visibility test,
+ *                 whatever their weight; spread [Nv] = sqrt(sum_n w_n mean_c (c_n - color)^2 / sum w) from a second pass over
+ *                 the views; visible [N,Nv] bytes (may be NULL): the visibility test per view.  sum w == 0: the fill colour and
+ *                 a NaN spread.  fp32 in a fixed order, no floating-point atomics: two calls agree bit for bit.
+ * Errors, which launch nothing: a null pointer (but visible); N < 1, Nv < 1, Nf < 1; H or W < 1 or > 4096; N H W >= 2^31;
+ * z_near <= 0 or non-finite; power < 1; an unknown dtype or layout; N > 65535, N Nv >= 2^30.
+ * Not computed: UV texture maps, perspective-correct attribute rendering. */
+int mvd_op_mesh_project(const float* verts, const float* K, const float* RT, int N, int Nv, float z_near, int32_t* xy, int32_t* key,
+                        void* stream);
+int mvd_op_mesh_raster(const int32_t* xy, const int32_t* key, const int32_t* faces, int N, int Nv, int Nf, int H, int W, int32_t* face_id,
+                       int32_t* pix_key, int32_t* bad_faces, void* stream);
+int mvd_op_mesh_vertex_colors(const void* images, int dtype, int layout, const int32_t* xy, const int32_t* key, const int32_t* faces,
+                              const int32_t* face_id, const int32_t* pix_key, const float* verts, const float* normals,
+                              const float* centres, int N, int Nv, int Nf, int H, int W, float power, int bias, int two_sided,
+                              float fill_r, float fill_g, float fill_b, float* color, float* weight_sum, int32_t* n_seen, float* spread,
+                              unsigned char* visible, void* stream);
 /* The conditioner's backward for ONE sample (its mesh / cameras active: mvd_select_sample): re-runs construct_spatial_volume and
  * construct_view_frustum_volume (morphable_diffusion.py:203-320: step embedding, 2-D encoder on the N noisy views, vertex gather,
  * view fusion, sparse voxel CNN in train mode, lattice gather, frustum gather and FrustumTV3DNet for the target view) with every

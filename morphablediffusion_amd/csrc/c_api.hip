@@ -636,6 +636,42 @@ int mvd_op_image_metrics(const void* pred, int pred_dtype, int pred_layout, cons
   return rc;
 }
 
+// ---- mesh texturing from views (csrc/k_mesh.hip): no context, the caller's device buffers
+int mvd_op_mesh_project(const float* verts, const float* K, const float* RT, int N, int Nv, float z_near, int32_t* xy, int32_t* key,
+                        void* stream) {
+  RET_IF(mesh_project_check("mvd_op_mesh_project", verts, K, RT, N, Nv, z_near, xy, key));
+  hipStream_t s = S(stream);
+  int rc = launch_mesh_project(verts, K, RT, N, Nv, z_near, xy, key, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_mesh_project: stream synchronisation failed");
+  return rc;
+}
+
+int mvd_op_mesh_raster(const int32_t* xy, const int32_t* key, const int32_t* faces, int N, int Nv, int Nf, int H, int W, int32_t* face_id,
+                       int32_t* pix_key, int32_t* bad_faces, void* stream) {
+  RET_IF(mesh_raster_check("mvd_op_mesh_raster", xy, key, faces, N, Nv, Nf, H, W, face_id, pix_key, bad_faces));
+  hipStream_t s = S(stream);
+  void* scratch = nullptr;  // the packed per-pixel winners live for this call only
+  HIP_CHECK_RET(hipMalloc(&scratch, mesh_raster_scratch_bytes(N, H, W)));
+  int rc = launch_mesh_raster(xy, key, faces, N, Nv, Nf, H, W, face_id, pix_key, bad_faces, scratch, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_mesh_raster: stream synchronisation failed");
+  hipFree(scratch);
+  return rc;
+}
+
+int mvd_op_mesh_vertex_colors(const void* images, int dtype, int layout, const int32_t* xy, const int32_t* key, const int32_t* faces,
+                              const int32_t* face_id, const int32_t* pix_key, const float* verts, const float* normals,
+                              const float* centres, int N, int Nv, int Nf, int H, int W, float power, int bias, int two_sided,
+                              float fill_r, float fill_g, float fill_b, float* color, float* weight_sum, int32_t* n_seen, float* spread,
+                              unsigned char* visible, void* stream) {
+  RET_IF(mesh_vertex_colors_check("mvd_op_mesh_vertex_colors", images, dtype, layout, xy, key, faces, face_id, pix_key, verts, normals,
+                                  centres, N, Nv, Nf, H, W, power, color, weight_sum, n_seen, spread));
+  hipStream_t s = S(stream);
+  int rc = launch_mesh_vertex_colors(images, dtype, layout, xy, key, faces, face_id, pix_key, verts, normals, centres, N, Nv, Nf, H, W,
+                                     power, bias, two_sided, fill_r, fill_g, fill_b, color, weight_sum, n_seen, spread, visible, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_mesh_vertex_colors: stream synchronisation failed");
+  return rc;
+}
+
 // ---- parity hooks of the sparse voxel CNN (tests/test_gpu_sparse_cnn_ops.py): no context, the caller's device buffers, scratch and
 // weight packs that live for the call (freed after the stream has been synchronised)
 namespace {

@@ -280,6 +280,26 @@ int image_metrics_check(const char* who, const void* pred, int pred_dtype, int p
                         int target_layout, const unsigned char* mask, int mask_mode, int V, int H, int W, const double* out);
 int launch_image_metrics(const void* pred, int pred_dtype, int pred_layout, const void* target, int target_dtype, int target_layout,
                          const unsigned char* mask, int mask_mode, int V, int H, int W, double* out, void* scratch, hipStream_t s);
+// k_mesh.hip: mesh texturing from views (include/mvd.h: mvd_op_mesh_project / _raster / _vertex_colors).  The *_check functions
+// are the argument errors (0 = fine).  xy [N][Nv][2] / key [N][Nv]: 1/16-pixel screen coordinates and depth keys (0 = invalid);
+// face_id / pix_key [N][H][W]; raster scratch: mesh_raster_scratch_bytes(N, H, W) bytes, 8-byte aligned, alive until the launches
+// have run; bad_faces: one device int, the faces with an index outside [0, Nv); visible [N][Nv] bytes may be null.
+int mesh_project_check(const char* who, const float* verts, const float* K, const float* RT, int N, int Nv, float z_near, const int* xy,
+                       const int* key);
+int launch_mesh_project(const float* verts, const float* K, const float* RT, int N, int Nv, float z_near, int* xy, int* key, hipStream_t s);
+int mesh_raster_check(const char* who, const int* xy, const int* key, const int* faces, int N, int Nv, int Nf, int H, int W,
+                      const int* face_id, const int* pix_key, const int* bad_faces);
+size_t mesh_raster_scratch_bytes(int N, int H, int W);
+int launch_mesh_raster(const int* xy, const int* key, const int* faces, int N, int Nv, int Nf, int H, int W, int* face_id, int* pix_key,
+                       int* bad_faces, void* scratch, hipStream_t s);
+int mesh_vertex_colors_check(const char* who, const void* images, int dtype, int layout, const int* xy, const int* key, const int* faces,
+                             const int* face_id, const int* pix_key, const float* verts, const float* normals, const float* centres, int N,
+                             int Nv, int Nf, int H, int W, float power, const float* color, const float* weight_sum, const int* n_seen,
+                             const float* spread);
+int launch_mesh_vertex_colors(const void* images, int dtype, int layout, const int* xy, const int* key, const int* faces, const int* face_id,
+                              const int* pix_key, const float* verts, const float* normals, const float* centres, int N, int Nv, int Nf,
+                              int H, int W, float power, int bias, int two_sided, float fill_r, float fill_g, float fill_b, float* color,
+                              float* weight_sum, int* n_seen, float* spread, unsigned char* visible, hipStream_t s);
 int launch_latent_gather(const float* feats, const int* grid, int gd, int gh, int gw, const float* min_xyz,
                          const int* out_sh, float voxel, int V, float vol_len, float* out, hipStream_t s);
 int launch_sparse_densify(const float* feats, const int* grid, long nvox, int C, float* out, hipStream_t s);

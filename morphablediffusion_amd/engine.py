@@ -98,6 +98,122 @@ def op_image_metrics(pred, target, mask=None, mask_mode=None, device=None, lib=N
     return out
 
 
+# ---- mesh texturing from views (include/mvd.h: mvd_op_mesh_project / _raster / _vertex_colors; csrc/k_mesh.hip): context-free.
+MESH_SUB, MESH_KMAX, MESH_GUARD_PX = 4, (1 << 24) - 1, 4096  # 1/16-pixel coordinates, the largest depth key, the guard band
+
+
+def _i32(name, t, shape, who):
+    """t as it is if it is an int32 tensor of that shape (None = any size), else ValueError: integers are never converted."""
+    if t.dtype != torch.int32 or t.dim() != len(shape) or any(s is not None and s != d for s, d in zip(shape, t.shape)):
+        raise ValueError(f"{who}: {name} must be int32 {list(shape)}, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def _mesh_image_dims(who, N, H, W):
+    if N < 1 or not (1 <= H <= 4096 and 1 <= W <= 4096) or N * H * W >= 2 ** 31:
+        raise ValueError(f"{who}: needs N >= 1, H and W in 1..4096 and N H W < 2^31, got (N, H, W) = {(N, H, W)}")
+
+
+def op_mesh_project(verts, K, RT, z_near, device=None, lib=None):
+    """mvd_op_mesh_project on ``device`` (default: verts'): verts [Nv,3], K [N,3,3], RT [N,3,4] (world -> camera), float tensors.
+    Returns (xy [N,Nv,2] int32 in 1/16 pixel, key [N,Nv] int32, 0 = invalid vertex) on the device."""
+    who = "op_mesh_project"
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] < 1:
+        raise ValueError(f"{who}: verts must be [Nv,3] with Nv >= 1, got {tuple(verts.shape)}")
+    if K.dim() != 3 or tuple(K.shape[1:]) != (3, 3) or RT.dim() != 3 or tuple(RT.shape[1:]) != (3, 4) or K.shape[0] != RT.shape[0] \
+            or K.shape[0] < 1:
+        raise ValueError(f"{who}: K must be [N,3,3] and RT [N,3,4] with N >= 1, got {tuple(K.shape)} and {tuple(RT.shape)}")
+    if not all(t.is_floating_point() for t in (verts, K, RT)):
+        raise ValueError(f"{who}: verts, K and RT must be float tensors")
+    z_near = float(z_near)
+    if not (z_near > 0.0 and z_near < float("inf")):
+        raise ValueError(f"{who}: z_near must be positive and finite, got {z_near}")
+    dev = verts.device if device is None else device
+    N, Nv = K.shape[0], verts.shape[0]
+    v, k, rt = _f32(verts, dev), _f32(K, dev), _f32(RT, dev)
+    lib = lib or L.load()
+    xy = torch.zeros((N, Nv, 2), device=dev, dtype=torch.int32)
+    key = torch.zeros((N, Nv), device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_mesh_project(L.ptr(v), L.ptr(k), L.ptr(rt), N, Nv, z_near, L.ptr(xy), L.ptr(key), _stream()))
+    return xy, key
+
+
+def op_mesh_raster(xy, key, faces, H, W, device=None, lib=None):
+    """mvd_op_mesh_raster on ``device`` (default: xy's): xy [N,Nv,2], key [N,Nv], faces [Nf,3], all int32.  Returns (face_id
+    [N,H,W] int32, -1 = background; pix_key [N,H,W] int32, 0 = background; bad_faces [1] int32: the faces with an index outside
+    [0, Nv), which were not drawn) on the device."""
+    who = "op_mesh_raster"
+    _i32("xy", xy, (None, None, 2), who)
+    N, Nv = xy.shape[:2]
+    _i32("key", key, (N, Nv), who)
+    _i32("faces", faces, (None, 3), who)
+    Nf, H, W = faces.shape[0], int(H), int(W)
+    if Nv < 1 or Nf < 1:
+        raise ValueError(f"{who}: at least one vertex and one face are needed, got Nv = {Nv}, Nf = {Nf}")
+    _mesh_image_dims(who, N, H, W)
+    dev = xy.device if device is None else device
+    xy, key, faces = (t.detach().to(dev).contiguous() for t in (xy, key, faces))
+    lib = lib or L.load()
+    face_id = torch.full((N, H, W), -1, device=dev, dtype=torch.int32)
+    pix_key = torch.zeros((N, H, W), device=dev, dtype=torch.int32)
+    bad = torch.zeros((1,), device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_mesh_raster(L.ptr(xy), L.ptr(key), L.ptr(faces), N, Nv, Nf, H, W, L.ptr(face_id), L.ptr(pix_key), L.ptr(bad),
+                                       _stream()))
+    return face_id, pix_key, bad
+
+
+def op_mesh_vertex_colors(images, xy, key, faces, face_id, pix_key, verts, normals, centres, power=2.0, bias=4096, two_sided=False,
+                          fill=(0.5, 0.5, 0.5), device=None, lib=None):
+    """mvd_op_mesh_vertex_colors on ``device`` (default: images'): images [N,3,H,W] or [N,H,W,3], float (taken as [-1, 1]) or
+    uint8; xy / key / faces / face_id / pix_key int32 as op_mesh_project and op_mesh_raster return them; verts / normals [Nv,3],
+    centres [N,3] (the camera centres), float.  Returns a dict of device tensors: color [Nv,3], weight_sum [Nv], spread [Nv]
+    (float32), n_seen [Nv] (int32), visible [N,Nv] (bool)."""
+    who = "op_mesh_vertex_colors"
+    if images.dim() != 4 or (images.shape[1] == 3) == (images.shape[3] == 3):
+        raise ValueError(f"{who}: images must be [N,3,H,W] or [N,H,W,3], got {tuple(images.shape)}")
+    if images.dtype != torch.uint8 and not images.is_floating_point():
+        raise ValueError(f"{who}: images must be a float tensor or uint8, not {images.dtype}")
+    dtype, layout = int(images.dtype == torch.uint8), 0 if images.shape[1] == 3 else 1
+    N, H, W = (images.shape[0], images.shape[2], images.shape[3]) if layout == 0 else tuple(images.shape[:3])
+    _mesh_image_dims(who, N, H, W)
+    _i32("xy", xy, (N, None, 2), who)
+    Nv = xy.shape[1]
+    _i32("key", key, (N, Nv), who)
+    _i32("faces", faces, (None, 3), who)
+    _i32("face_id", face_id, (N, H, W), who)
+    _i32("pix_key", pix_key, (N, H, W), who)
+    Nf = faces.shape[0]
+    if Nv < 1 or Nf < 1:
+        raise ValueError(f"{who}: at least one vertex and one face are needed, got Nv = {Nv}, Nf = {Nf}")
+    for name, t, shape in (("verts", verts, (Nv, 3)), ("normals", normals, (Nv, 3)), ("centres", centres, (N, 3))):
+        if tuple(t.shape) != shape or not t.is_floating_point():
+            raise ValueError(f"{who}: {name} must be a float tensor {list(shape)}, got {t.dtype} {tuple(t.shape)}")
+    power, fill = float(power), tuple(float(c) for c in fill)
+    if not (power >= 1.0 and power < float("inf")):
+        raise ValueError(f"{who}: power must be at least 1 and finite, got {power}")
+    if len(fill) != 3:
+        raise ValueError(f"{who}: fill must be three numbers")
+    dev = images.device if device is None else device
+    img = images.detach().to(device=dev, dtype=torch.uint8 if dtype else torch.float32).contiguous()
+    xy, key, faces, face_id, pix_key = (t.detach().to(dev).contiguous() for t in (xy, key, faces, face_id, pix_key))
+    v, nrm, cen = _f32(verts, dev), _f32(normals, dev), _f32(centres, dev)
+    lib = lib or L.load()
+    nan = float("nan")
+    out = {"color": torch.full((Nv, 3), nan, device=dev), "weight_sum": torch.full((Nv,), nan, device=dev),
+           "n_seen": torch.full((Nv,), -1, device=dev, dtype=torch.int32), "spread": torch.full((Nv,), nan, device=dev)}
+    visible = torch.zeros((N, Nv), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_mesh_vertex_colors(L.ptr(img), dtype, layout, L.ptr(xy), L.ptr(key), L.ptr(faces), L.ptr(face_id),
+                                              L.ptr(pix_key), L.ptr(v), L.ptr(nrm), L.ptr(cen), N, Nv, Nf, H, W, power, int(bias),
+                                              int(bool(two_sided)), fill[0], fill[1], fill[2], L.ptr(out["color"]),
+                                              L.ptr(out["weight_sum"]), L.ptr(out["n_seen"]), L.ptr(out["spread"]), L.ptr(visible),
+                                              _stream()))
+    out["visible"] = visible.bool()
+    return out
+
+
 # ---- the sparse voxel CNN's kernels one at a time (include/mvd.h: mvd_op_sparse_conv ...): context-free like op_train_loss.
 # w: the 3x3x3 kernel in checkpoint layout 0 [Cout,Cin,3,3,3], 1 [Cout,3,3,3,Cin] or 2 [3,3,3,Cin,Cout]; nbr [n_out,27] int32.
 SPARSE_FORMS = ("site", "mfma")  # form of mvd_op_sparse_conv / mvd_op_sparse_conv_bwd, by index
@@ -659,6 +775,19 @@ class Engine:
     def op_image_metrics(self, pred, target, mask=None, mask_mode=None):
         """mvd_op_image_metrics on this engine's device: see the module-level op_image_metrics."""
         return op_image_metrics(pred, target, mask, mask_mode, device=self.device, lib=self.lib)
+
+    def op_mesh_project(self, verts, K, RT, z_near):
+        """mvd_op_mesh_project on this engine's device: see the module-level op_mesh_project."""
+        return op_mesh_project(verts, K, RT, z_near, device=self.device, lib=self.lib)
+
+    def op_mesh_raster(self, xy, key, faces, H, W):
+        """mvd_op_mesh_raster on this engine's device: see the module-level op_mesh_raster."""
+        return op_mesh_raster(xy, key, faces, H, W, device=self.device, lib=self.lib)
+
+    def op_mesh_vertex_colors(self, images, xy, key, faces, face_id, pix_key, verts, normals, centres, **kw):
+        """mvd_op_mesh_vertex_colors on this engine's device: see the module-level op_mesh_vertex_colors."""
+        return op_mesh_vertex_colors(images, xy, key, faces, face_id, pix_key, verts, normals, centres, device=self.device,
+                                     lib=self.lib, **kw)
 
     # the sparse voxel CNN's kernels one at a time: the module-level functions above on this engine's device and library
     def op_sparse_conv(self, x, nbr, w, layout, form="mfma", scale=None, shift=None):

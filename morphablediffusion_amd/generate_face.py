@@ -3,7 +3,7 @@ MI355X engine: same flags, same batch construction, same outputs.
 
   --input_img IMG --exp_img IMG --mesh MESH.{ply,obj} --cfg configs/facescape.yaml --ckpt CKPT --output_dir DIR
   [--cfg_scale 2.0] [--batch_view_num 8] [--seed 6033] [--sampler ddim|dpmpp_2m|dpmpp_2m_sde] [--sample_steps 50]
-  [--camera_trajectory virtual|real] [--prepare_neus2_data] [--gt_dir DIR]
+  [--camera_trajectory virtual|real] [--prepare_neus2_data] [--gt_dir DIR] [--export_mesh] [--mesh_overlay]
 
 writes ``<output_dir>/<input>_<exp>.png`` (the input view followed by the 16 generated views, generate_face.py:244-253) and, with
 --prepare_neus2_data, ``<output_dir>/neus2_data/<input>_<exp>/{transform.json, images/00..15.png}`` (:145-192,255-262).
@@ -17,7 +17,10 @@ Differences, all outside the denoising path and stated here:
   * --camera_file names the pickle / JSON of the 'real' trajectory (default: the reference's ./assets/facescape_test_traj.pkl);
   * --exp_img only names the output, as in the reference (the expression enters through the mesh);
   * --gt_dir DIR (not a reference flag) scores the saved strip's 16 views against the captured views in DIR (metrics.py: SSIM,
-    PSNR, MSE, MAE under the reference's evaluation protocol) and writes ``<output_dir>/<input>_<exp>_metrics.json``.
+    PSNR, MSE, MAE under the reference's evaluation protocol) and writes ``<output_dir>/<input>_<exp>_metrics.json``;
+  * --export_mesh / --mesh_overlay (not reference flags; mesh.py): the conditioning mesh coloured from the 16 generated views as
+    ``<output_dir>/<input>_<exp>_mesh.ply`` with its statistics in ``<input>_<exp>_mesh.json``, and the mesh drawn over the views
+    as ``<input>_<exp>_overlay.png`` (a check of the mesh's alignment).  Both need a mesh file with faces.
 """
 import argparse
 import json
@@ -32,6 +35,29 @@ import torch
 from . import batch as B
 
 NUM_VIEWS = 16  # hard-wired in the reference (generate_face.py:141,156,256)
+
+
+def read_ply_header(f, path):
+    """The header of a PLY file opened in binary mode, leaving ``f`` at the first byte of the data: (format, elements) with
+    elements = [(name, count, properties)] in file order and a property (name, type), or (name, "list", count type, item type)."""
+    if f.readline().strip() != b"ply":
+        raise ValueError(f"{path}: not a PLY file")
+    fmt, elements = None, []
+    while True:
+        line = f.readline()
+        if not line:
+            raise ValueError(f"{path}: truncated PLY header")
+        t = line.decode("ascii", "replace").split()
+        if not t:
+            continue
+        if t[0] == "format":
+            fmt = t[1]
+        elif t[0] == "element":
+            elements.append((t[1], int(t[2]), []))
+        elif t[0] == "property" and elements:
+            elements[-1][2].append((t[4], "list", t[2], t[3]) if t[1] == "list" else (t[2], t[1]))
+        elif t[0] == "end_header":
+            return fmt, elements
 
 
 def read_mesh_vertices(path) -> np.ndarray:
@@ -51,28 +77,13 @@ def read_mesh_vertices(path) -> np.ndarray:
     if not path.lower().endswith(".ply"):
         raise ValueError(f"{path}: expected a .ply or .obj mesh")
     with open(path, "rb") as f:
-        if f.readline().strip() != b"ply":
-            raise ValueError(f"{path}: not a PLY file")
-        fmt, nverts, props, in_vertex = None, 0, [], False
-        while True:
-            line = f.readline()
-            if not line:
-                raise ValueError(f"{path}: truncated PLY header")
-            t = line.decode("ascii", "replace").split()
-            if not t:
-                continue
-            if t[0] == "format":
-                fmt = t[1]
-            elif t[0] == "element":
-                in_vertex = t[1] == "vertex"
-                if in_vertex:
-                    nverts = int(t[2])
-            elif t[0] == "property" and in_vertex:
-                if t[1] == "list":
-                    raise ValueError(f"{path}: list property on vertices is not supported")
-                props.append((t[2], t[1]))
-            elif t[0] == "end_header":
-                break
+        fmt, elements = read_ply_header(f, path)
+        nverts, props = 0, []
+        for name, count, eprops in elements:
+            if name == "vertex":
+                nverts, props = count, eprops
+        if any(p[1] == "list" for p in props):
+            raise ValueError(f"{path}: list property on vertices is not supported")
         names = [p[0] for p in props]
         if not all(a in names for a in "xyz"):
             raise ValueError(f"{path}: vertex element has no x/y/z")
@@ -138,7 +149,40 @@ def build_parser():
     p.add_argument("--gt_dir", type=str, default=None,
                    help="not a reference flag: a folder with the 16 captured views (sorted *.png, 256 x 256; RGBA: alpha 0 is "
                         "background); the saved strip's views are scored against them into <output_dir>/<img>_<exp>_metrics.json")
+    p.add_argument("--export_mesh", action="store_true",
+                   help="not a reference flag: write <output_dir>/<img>_<exp>_mesh.ply (the mesh file's vertices and faces with "
+                        "colours fused from the generated views) and <img>_<exp>_mesh.json (coverage, consistency, visible counts)")
+    p.add_argument("--mesh_overlay", action="store_true",
+                   help="not a reference flag: write <output_dir>/<img>_<exp>_overlay.png, the mesh drawn over the generated views")
     return p
+
+
+def mesh_outputs(x_sample, cams, verts, faces, file_verts, output_dir, stem, export_mesh=False, mesh_overlay=False, **kw):
+    """The post-sampling work of --export_mesh / --mesh_overlay: x_sample [N,3,H,W] (or [B,N,3,H,W]: sample 0) in [-1, 1], cams
+    (K [N,4,4] or [N,3,3], RT [N,3,4]), verts [Nv,3] in the frame of batch["vertices"], faces [Nf,3], file_verts [Nv,3] as the
+    mesh file stores them (what the PLY holds).  Writes <output_dir>/<stem>_mesh.ply and <stem>_mesh.json with export_mesh,
+    <stem>_overlay.png with mesh_overlay, nothing without either; kw goes to mesh.texture_mesh.  Returns the paths written."""
+    written = {}
+    if not (export_mesh or mesh_overlay):
+        return written
+    from . import mesh as MS
+    x = x_sample[0] if x_sample.dim() == 5 else x_sample
+    K, RT = cams
+    tex = MS.texture_mesh(x, verts, faces, K, RT, **kw)
+    out = Path(output_dir)
+    if export_mesh:
+        written["ply"] = str(out / f"{stem}_mesh.ply")
+        MS.write_ply(written["ply"], np.asarray(file_verts), faces, tex["colors"])
+        written["json"] = str(out / f"{stem}_mesh.json")
+        with open(written["json"], "w") as f:
+            json.dump({"vertices": int(tex["colors"].shape[0]), "faces": int(len(faces)), "coverage": tex["coverage"],
+                       "consistency": None if np.isnan(tex["consistency"]) else tex["consistency"], "visible_per_view": tex["visible"].sum(1).tolist(),
+                       "seen_in_two_or_more_views": int((tex["n_seen"] >= 2).sum())}, f, indent=2)
+    if mesh_overlay:
+        from PIL import Image
+        written["overlay"] = str(out / f"{stem}_overlay.png")
+        Image.fromarray(MS.overlay_views(x, tex["mask"], tex["face_id"]).cpu().numpy()).save(written["overlay"])
+    return written
 
 
 def load_model(cfg, ckpt, device="cuda:0", lora=None, lora_scale=1.0, **overrides):
@@ -170,7 +214,16 @@ def run(flags, model=None):
         cams = B.cameras_from_dict(load_camera_dict(flags.camera_file), NUM_VIEWS)
     else:
         cams = B.virtual_cameras(NUM_VIEWS, 256)
-    verts = B.align_flame_vertices(torch.from_numpy(read_mesh_vertices(flags.mesh)).float())
+    want_mesh = getattr(flags, "export_mesh", False) or getattr(flags, "mesh_overlay", False)
+    faces = None
+    if want_mesh:
+        from .mesh import read_mesh
+        file_verts, faces = read_mesh(flags.mesh)
+        if not len(faces):
+            raise ValueError(f"{flags.mesh}: --export_mesh / --mesh_overlay need a mesh with faces")
+    else:
+        file_verts = read_mesh_vertices(flags.mesh)
+    verts = B.align_flame_vertices(torch.from_numpy(file_verts).float())
     data = B.build_batch(input_img, verts, num_views=NUM_VIEWS, image_size=256, device=model.device, cameras=cams)
     neus2_root = None
     if flags.prepare_neus2_data:
@@ -189,6 +242,9 @@ def run(flags, model=None):
         res = M.summarise(M.image_metrics(M.strip_to_views(strip, NUM_VIEWS, 256)[0].to(model.device), gt, gt_mask))
         with open(Path(flags.output_dir) / f"{img_name}_{exp_name}_metrics.json", "w") as f:
             json.dump(dict(res, sampler=flags.sampler, sample_steps=flags.sample_steps), f, indent=2)
+    if want_mesh:
+        mesh_outputs(x_sample, cams, verts, faces, file_verts, flags.output_dir, f"{img_name}_{exp_name}",
+                     export_mesh=getattr(flags, "export_mesh", False), mesh_overlay=getattr(flags, "mesh_overlay", False))
     if neus2_root:
         # generate_face.py:255-262 slices idx*256 of the strip for idx in range(16): view 0 of the export is the INPUT view and
         # the last generated view is dropped -- reproduced as is

@@ -995,6 +995,29 @@ class SyncMultiviewDiffusion(nn.Module):
         out["x_sample"] = x_sample
         return out
 
+    @torch.no_grad()
+    def texture_mesh(self, batch, x_sample, faces, sample=0, **kw):
+        """A coloured mesh out of generated views (not a reference method): ``mesh.texture_mesh`` of ``x_sample[sample]``
+        ([B,N,3,H,W], what ``sample`` returns) on the mesh the sample was conditioned on -- ``batch["vertices"][sample]`` with
+        the triangles ``faces`` [Nf,3] -- under ``batch["target_K"][sample, :, :3, :3]`` and ``batch["target_RT"][sample]``.
+        H and W must be the conditioner's input_image_size (``image_size``): the cameras are in pixels of that size.  ``kw``:
+        power, bias, two_sided, fill, z_near.  Returns mesh.texture_mesh's dict."""
+        from .mesh import texture_mesh
+        for k in ("vertices", "target_K", "target_RT"):
+            if batch.get(k) is None:
+                raise ValueError(f"texture_mesh needs batch[{k!r}]")
+        if x_sample.dim() != 5 or x_sample.shape[2] != 3:
+            raise ValueError(f"texture_mesh: x_sample must be [B,N,3,H,W], got {tuple(x_sample.shape)}")
+        B, N, _, H, W = x_sample.shape
+        if H != self.image_size or W != self.image_size:
+            raise ValueError(f"texture_mesh: the views are {H} x {W}, the cameras are in pixels of input_image_size = {self.image_size}")
+        if not 0 <= sample < B or batch["vertices"].shape[0] != B:
+            raise ValueError(f"texture_mesh: sample {sample} of a batch of {B} (vertices: {batch['vertices'].shape[0]})")
+        if batch["target_K"].shape[1] != N or batch["target_RT"].shape[1] != N:
+            raise ValueError(f"texture_mesh: {N} views but {batch['target_K'].shape[1]} cameras")
+        return texture_mesh(x_sample[sample], batch["vertices"][sample], faces, batch["target_K"][sample][..., :3, :3],
+                            batch["target_RT"][sample], **kw)
+
     def log_image(self, x_sample, batch, step, output_dir):
         """morphable_diffusion.py:589-599: one row per sample -- the input view followed by the N generated views -- as
         <output_dir>/<step>.jpg."""
