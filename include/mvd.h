@@ -768,6 +768,41 @@ int mvd_op_folded_group_norm(mvd_ctx* ctx, const float* x, int B, int rps, int K
 int mvd_op_softmax_rows(mvd_ctx* ctx, const float* scores, int rows, int cols, int out_f32, void* out, void* stream);
 /* launch_rows_f32_to_f16_split: fp32 rows lda floats apart -> out [rows + 1][3 C] 16-bit, [hi | lo | hi] */
 int mvd_op_rows_split(mvd_ctx* ctx, const float* x, int lda, int rows, int C, void* out, void* stream);
+/* Attention hooks (tests/test_gpu_attention.py).  q, k, v (and d_out) are fp32 [B][T][heads*d]; a bad argument (T < 1, Tstride
+ * non-zero and < T, ld_pad % 8 != 0, a head width without a kernel, a null pointer) returns non-zero before anything is launched;
+ * the stream is synchronised before the call returns.
+ *
+ * mvd_op_attention_ex: attn_kernel on the engine's fused 16-bit image [token][q | k | v] with rows of 3 C + ld_pad elements
+ * (C = heads * d) and samples Tstride rows apart (0 = T; CLIP runs 257 tokens in 264 rows).  The whole image -- pad rows
+ * T .. Tstride - 1 of every sample, pad columns, and one guard row behind the last sample -- is filled with 0xFF bytes (NaN in
+ * fp16 and in bfloat16) before q, k, v are packed into it, and so is the kernel's result [B * Tstride + 1][C]; out receives
+ * those result rows as fp32, pad and guard rows included: they must come back NaN.  xcd: -1 = the workgroup order
+ * MVD_ATTN_NO_XCD asks for, 0 = without the XCD remap, 1 = with it.
+ *
+ * mvd_op_attention_bwd_ex: mvd_op_attention_bwd's sequence (forward, cast of d_out, bwd_attention) with one guard row behind the
+ * last sample of the qkv, o, dO and dqkv images; dqkv, lse and delta start as 0xFF bytes.  dq, dk, dv, o: [B * T + 1][C] fp32
+ * (the last row is the guard); lse (log2 units, as the kernels keep it), delta: [B * heads * T + 1] fp32, the last element the
+ * guard. */
+int mvd_op_attention_ex(mvd_ctx* ctx, const float* q, const float* k, const float* v, int B, int T, int heads, int d, int Tstride,
+                        int ld_pad, int xcd, float* out, void* stream);
+int mvd_op_attention_bwd_ex(mvd_ctx* ctx, const float* q, const float* k, const float* v, const float* d_out, int B, int T,
+                            int heads, int d, float* dq, float* dk, float* dv, float* lse, float* delta, float* o, void* stream);
+/* The fp32 kernels of the DepthTransformer's training form (csrc/k_train.hip) one at a time on raw device buffers, no context.
+ * The caller presets every result buffer to NaN (with a guard row behind it); what a launcher refuses comes back as its error,
+ * nothing is launched and the results stay as they were; the stream is synchronised.
+ *   mvd_op_train_depth_attn      q [R][I], k / v [(R / HW) * D * HW][I] (row = (b * D + depth) * HW + pixel), I = hn * hd, scale
+ *                                hd^-0.5 -> attn [R][hn][D], z [R][I]
+ *   mvd_op_train_depth_attn_bwd  its backward from attn and dz [R][I] -> dq [R][I], dk / dv shaped like k
+ *   mvd_op_train_im2col3         x [B][H][W][C] -> col [B*H*W][9*C], tap = (dy + 1) * 3 + (dx + 1), zero outside
+ *   mvd_op_train_col2im3         the transpose: dcol [B*H*W][9*C] -> dx [B][H][W][C]
+ *   mvd_op_train_perm_w3         to_mat != 0: conv weight [N][C][3][3] -> GEMM matrix [N][9][C]; 0: the reverse */
+int mvd_op_train_depth_attn(const float* q, const float* k, const float* v, int R, int HW, int D, int hn, int hd, float* attn,
+                            float* z, void* stream);
+int mvd_op_train_depth_attn_bwd(const float* q, const float* k, const float* v, const float* attn, const float* dz, int R, int HW,
+                                int D, int hn, int hd, float* dq, float* dk, float* dv, void* stream);
+int mvd_op_train_im2col3(const float* x, int B, int H, int W, int C, float* col, void* stream);
+int mvd_op_train_col2im3(const float* dcol, int B, int H, int W, int C, float* dx, void* stream);
+int mvd_op_train_perm_w3(const float* src, int N, int C, int to_mat, float* dst, void* stream);
 /* time of the dominant kernel, for bench.py: runs the 3x3 conv implicit GEMM `iters` times on stream and
  * returns the mean kernel time in ms measured with HIP events on that stream */
 int mvd_bench_conv(mvd_ctx* ctx, int B, int C, int H, int W, int Cout, int iters, float* ms_out, void* stream);

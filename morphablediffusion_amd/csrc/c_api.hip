@@ -51,6 +51,17 @@ __global__ void pack_qkv_rows_kernel(const float* q, const float* k, const float
     qkv[(long)r * 3 * C + 2 * C + c] = (half_t)v[i];
   }
 }
+// q,k,v [B][T][C] fp32 -> the fused 16-bit image [B][Tstride][ld] (q | k | v in the first 3 C columns); what lies between is left as it is
+__global__ void pack_qkv_image_kernel(const float* q, const float* k, const float* v, int B, int T, int C, int Tstride, int ld, half_t* qkv) {
+  const long total = (long)B * T * C;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C);
+    const long r = i / C, row = (r / T) * Tstride + r % T;
+    qkv[row * ld + c] = (half_t)q[i];
+    qkv[row * ld + C + c] = (half_t)k[i];
+    qkv[row * ld + 2 * C + c] = (half_t)v[i];
+  }
+}
 // UNetWrapper.predict_with_unconditional_scale input assembly (morphable_diffusion.py:133-146), channels-last:
 // rows [0,TN) = [x | x_input / 0.18215], rows [TN,2TN) = [x | 0]
 // UNet input of one sample's TN views: rows [0, TN) of `out` = the conditional copies, rows [half_off, half_off + TN) the
@@ -2515,6 +2526,123 @@ int mvd_op_rows_split(mvd_ctx* c, const float* x, int lda, int rows, int C, void
   if (!x || !out || rows <= 0 || C <= 0 || lda < C) return mvd_fail("op_rows_split: bad argument");
   hipStream_t s = S(stream);
   return op_sync("op_rows_split", s, launch_rows_f32_to_f16_split(x, lda, rows, C, (half_t*)out, s));
+}
+
+
+// tests/test_gpu_attention.py: attn_kernel and the two backward kernels on the engine's images, with everything the launches may touch
+// beside their operands and results poisoned first (0xFFFF is NaN in fp16 and in bfloat16)
+namespace {
+int attn_ex_check(const char* who, const void* q, const void* k, const void* v, int B, int T, int heads, int d) {
+  const std::string w(who);
+  if (!q || !k || !v) return mvd_fail((w + ": null operand").c_str());
+  if (B < 1 || T < 1 || heads < 1) return mvd_fail((w + ": B, T, heads >= 1 expected").c_str());
+  if (d != 8 && d != 16 && d != 32 && d != 40 && d != 64 && d != 80 && d != 160) return mvd_fail((w + ": unsupported head dim").c_str());
+  return 0;
+}
+}  // namespace
+
+int mvd_op_attention_ex(mvd_ctx* c, const float* q, const float* k, const float* v, int B, int T, int heads, int d, int Tstride,
+                        int ld_pad, int xcd, float* out, void* stream) {
+  RET_IF(ex_begin(c));
+  RET_IF(attn_ex_check("op_attention_ex", q, k, v, B, T, heads, d));
+  if (!out) return mvd_fail("op_attention_ex: null operand");
+  if (Tstride < 0 || (Tstride != 0 && Tstride < T)) return mvd_fail("op_attention_ex: Tstride >= T (or 0) expected");
+  if (ld_pad < 0 || ld_pad % 8) return mvd_fail("op_attention_ex: ld_pad must be a multiple of 8");
+  if (xcd < -1 || xcd > 1) return mvd_fail("op_attention_ex: xcd is -1, 0 or 1");
+  hipStream_t s = S(stream);
+  WsScope ws_scope(c);
+  const int C = heads * d, ld = 3 * C + ld_pad, Ts = Tstride ? Tstride : T;
+  const size_t rows = (size_t)B * Ts + 1;
+  half_t* qkv = ws_alloc<half_t>(c, rows * ld);
+  half_t* o = ws_alloc<half_t>(c, rows * C);
+  WS_CHECK(qkv && o);
+  HIP_CHECK_RET(hipMemsetAsync(qkv, 0xFF, rows * ld * sizeof(half_t), s));
+  HIP_CHECK_RET(hipMemsetAsync(o, 0xFF, rows * C * sizeof(half_t), s));
+  hipLaunchKernelGGL(pack_qkv_image_kernel, dim3(nblk((size_t)B * T * C)), dim3(256), 0, s, q, k, v, B, T, C, Ts, ld, qkv);
+  int rc = launch_attention(qkv, ld, qkv + 2 * C, ld, o, C, B, T, heads, d, s, Ts, xcd);
+  if (!rc) {
+    hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk(rows * C)), dim3(256), 0, s, o, out, rows * C);
+    if (hipGetLastError() != hipSuccess) rc = mvd_fail("op_attention_ex: launch failed");
+  }
+  return op_sync("op_attention_ex", s, rc);
+}
+
+int mvd_op_attention_bwd_ex(mvd_ctx* c, const float* q, const float* k, const float* v, const float* d_out, int B, int T, int heads,
+                            int d, float* dq, float* dk, float* dv, float* lse, float* delta, float* o_out, void* stream) {
+  RET_IF(ex_begin(c));
+  RET_IF(attn_ex_check("op_attention_bwd_ex", q, k, v, B, T, heads, d));
+  if (!d_out || !dq || !dk || !dv || !lse || !delta || !o_out) return mvd_fail("op_attention_bwd_ex: null operand");
+  hipStream_t s = S(stream);
+  WsScope ws_scope(c);
+  const int C = heads * d;
+  const size_t rows = (size_t)B * T, nstat = (size_t)B * heads * T + 1;
+  half_t* qkv = ws_alloc<half_t>(c, (rows + 1) * 3 * C);
+  half_t* o = ws_alloc<half_t>(c, (rows + 1) * C);
+  half_t* do16 = ws_alloc<half_t>(c, (rows + 1) * C);
+  half_t* dqkv = ws_alloc<half_t>(c, (rows + 1) * 3 * C);
+  float* lse_d = ws_alloc<float>(c, nstat);
+  float* delta_d = ws_alloc<float>(c, nstat);
+  float* tmp = ws_alloc<float>(c, (rows + 1) * 3 * C);
+  WS_CHECK(qkv && o && do16 && dqkv && lse_d && delta_d && tmp);
+  HIP_CHECK_RET(hipMemsetAsync(qkv, 0xFF, (rows + 1) * 3 * C * sizeof(half_t), s));
+  HIP_CHECK_RET(hipMemsetAsync(o, 0xFF, (rows + 1) * C * sizeof(half_t), s));
+  HIP_CHECK_RET(hipMemsetAsync(do16, 0xFF, (rows + 1) * C * sizeof(half_t), s));
+  HIP_CHECK_RET(hipMemsetAsync(dqkv, 0xFF, (rows + 1) * 3 * C * sizeof(half_t), s));
+  HIP_CHECK_RET(hipMemsetAsync(lse_d, 0xFF, nstat * sizeof(float), s));
+  HIP_CHECK_RET(hipMemsetAsync(delta_d, 0xFF, nstat * sizeof(float), s));
+  hipLaunchKernelGGL(pack_qkv_image_kernel, dim3(nblk(rows * C)), dim3(256), 0, s, q, k, v, B, T, C, T, 3 * C, qkv);
+  int rc = launch_attention(qkv, 3 * C, qkv + 2 * C, 3 * C, o, C, B, T, heads, d, s);
+  if (!rc) rc = bwd_cast_rows(d_out, C, (long)rows, C, C, do16, s);
+  if (!rc) rc = bwd_attention(qkv, 3 * C, o, do16, C, dqkv, 3 * C, lse_d, delta_d, B, T, heads, d, s);
+  if (!rc) {
+    hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk((rows + 1) * 3 * C)), dim3(256), 0, s, dqkv, tmp, (rows + 1) * 3 * C);
+    hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk((rows + 1) * C)), dim3(256), 0, s, o, o_out, (rows + 1) * C);
+    if (hipGetLastError() != hipSuccess) rc = mvd_fail("op_attention_bwd_ex: launch failed");
+    float* outs[3] = {dq, dk, dv};
+    for (int i = 0; i < 3 && !rc; ++i)
+      if (hipMemcpy2DAsync(outs[i], (size_t)C * 4, tmp + (size_t)i * C, (size_t)3 * C * 4, (size_t)C * 4, rows + 1, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        rc = mvd_fail("op_attention_bwd_ex: copy failed");
+    if (!rc && (hipMemcpyAsync(lse, lse_d, nstat * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+                hipMemcpyAsync(delta, delta_d, nstat * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess))
+      rc = mvd_fail("op_attention_bwd_ex: copy failed");
+  }
+  return op_sync("op_attention_bwd_ex", s, rc);
+}
+
+// the DepthTransformer's fp32 training kernels (csrc/k_train.hip) on the caller's device buffers; no context
+int mvd_op_train_depth_attn(const float* q, const float* k, const float* v, int R, int HW, int D, int hn, int hd, float* attn, float* z,
+                            void* stream) {
+  if (!q || !k || !v || !attn || !z) return mvd_fail("mvd_op_train_depth_attn: null argument");
+  if (R <= 0 || HW <= 0 || R % HW || D <= 0 || hn <= 0 || hd <= 0) return mvd_fail("mvd_op_train_depth_attn: R a positive multiple of HW, D, hn, hd >= 1 expected");
+  hipStream_t s = S(stream);
+  return op_sync("mvd_op_train_depth_attn", s, train_depth_fwd(q, k, v, R, HW, D, hn, hd, 1.0f / sqrtf((float)hd), attn, z, s));
+}
+
+int mvd_op_train_depth_attn_bwd(const float* q, const float* k, const float* v, const float* attn, const float* dz, int R, int HW, int D,
+                                int hn, int hd, float* dq, float* dk, float* dv, void* stream) {
+  if (!q || !k || !v || !attn || !dz || !dq || !dk || !dv) return mvd_fail("mvd_op_train_depth_attn_bwd: null argument");
+  if (R <= 0 || HW <= 0 || R % HW || D <= 0 || hn <= 0 || hd <= 0) return mvd_fail("mvd_op_train_depth_attn_bwd: R a positive multiple of HW, D, hn, hd >= 1 expected");
+  hipStream_t s = S(stream);
+  return op_sync("mvd_op_train_depth_attn_bwd", s,
+                 train_depth_bwd(q, k, v, attn, dz, R, HW, D, hn, hd, 1.0f / sqrtf((float)hd), dq, dk, dv, s));
+}
+
+int mvd_op_train_im2col3(const float* x, int B, int H, int W, int C, float* col, void* stream) {
+  if (!x || !col || B <= 0 || H <= 0 || W <= 0 || C <= 0) return mvd_fail("mvd_op_train_im2col3: bad argument");
+  hipStream_t s = S(stream);
+  return op_sync("mvd_op_train_im2col3", s, train_im2col3(x, B, H, W, C, col, s));
+}
+
+int mvd_op_train_col2im3(const float* dcol, int B, int H, int W, int C, float* dx, void* stream) {
+  if (!dcol || !dx || B <= 0 || H <= 0 || W <= 0 || C <= 0) return mvd_fail("mvd_op_train_col2im3: bad argument");
+  hipStream_t s = S(stream);
+  return op_sync("mvd_op_train_col2im3", s, train_col2im3(dcol, B, H, W, C, dx, s));
+}
+
+int mvd_op_train_perm_w3(const float* src, int N, int C, int to_mat, float* dst, void* stream) {
+  if (!src || !dst || N <= 0 || C <= 0) return mvd_fail("mvd_op_train_perm_w3: bad argument");
+  hipStream_t s = S(stream);
+  return op_sync("mvd_op_train_perm_w3", s, train_perm_w3(src, N, C, to_mat, dst, s));
 }
 
 }  // extern "C"

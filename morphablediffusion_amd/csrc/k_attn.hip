@@ -347,13 +347,13 @@ int launch_softmax_rows(const float* s, long rows, int cols, half_t* p, hipStrea
 }
 
 int launch_attention(const half_t* qk, int ldqk, const half_t* v, int ldv, half_t* out, int ldo, int B, int T, int heads,
-                     int d, hipStream_t s, int Tstride) {
+                     int d, hipStream_t s, int Tstride, int xcd) {
   if (Tstride <= 0) Tstride = T;
   if (Tstride < T || ldqk % 8 || ldv % 8 || ldo % 4 || d % 8 || ((uintptr_t)qk & 15) || ((uintptr_t)v & 15))
     return mvd_fail("attention: alignment (row strides and d multiples of 8, 16-byte aligned operands)");
   if ((long)cdiv(T, 128) * heads * B > 0x7FFFFFFFL) return mvd_fail("attention: grid too large");
   dim3 grid((unsigned)(cdiv(T, 128) * heads * B));
-  const int xcd_remap = mvd_env().attn_xcd;
+  const int xcd_remap = xcd < 0 ? (int)mvd_env().attn_xcd : (xcd != 0);
   const float scale = 1.4426950408889634f / sqrtf((float)d);  // softmax scale * log2(e): the kernel uses exp2
 #define MVD_ATTN(DD) \
   case DD: hipLaunchKernelGGL(attn_kernel<DD>, grid, dim3(256), 0, s, qk, ldqk, v, ldv, out, ldo, T, heads, scale, Tstride, xcd_remap); break;

@@ -293,6 +293,94 @@ def op_bn_rows_relu_bwd(xraw, dy, stats, gamma, beta, accum=None, poison=False, 
     return d, dg, db
 
 
+def _nan_guarded(rows, width, dev):
+    """[rows + 1][width] fp32 of NaN bit patterns (0xFF bytes): a result buffer with one guard row behind it."""
+    t = torch.empty(rows + 1, width, device=dev, dtype=torch.float32)
+    t.view(torch.int32).fill_(-1)
+    return t
+
+
+def _nan_guard_intact(t, rows, what):
+    assert bool((t.view(torch.int32)[rows:] == -1).all()), f"{what}: the launch wrote behind its result (guard row changed)"
+
+
+def op_train_depth_attn(q, k, v, HW, D, hn, device=None, lib=None):
+    """mvd_op_train_depth_attn (depth_fwd_kernel): q [R,I], k / v [(R/HW)*D*HW, I] -> (attn [R,hn,D], z [R,I]).  Results start as NaN
+    with a guard row behind them; a shape the launcher refuses raises MvdError with its text."""
+    lib = lib or L.load()
+    dev = q.device if device is None else device
+    q, k, v = _f32(q, dev), _f32(k, dev), _f32(v, dev)
+    R, I = q.shape
+    if I % hn or R % HW or k.shape != (R // HW * D * HW, I) or v.shape != k.shape:
+        raise ValueError("op_train_depth_attn: q [R,I], k and v [(R/HW)*D*HW, I] with I = hn * hd expected")
+    attn, z = _nan_guarded(R, hn * D, dev), _nan_guarded(R, I, dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_train_depth_attn(L.ptr(q), L.ptr(k), L.ptr(v), R, HW, D, hn, I // hn, L.ptr(attn), L.ptr(z), _stream()))
+    _nan_guard_intact(attn, R, "op_train_depth_attn (attn)")
+    _nan_guard_intact(z, R, "op_train_depth_attn (z)")
+    return attn[:R].reshape(R, hn, D).clone(), z[:R].clone()
+
+
+def op_train_depth_attn_bwd(q, k, v, attn, dz, HW, D, hn, device=None, lib=None):
+    """mvd_op_train_depth_attn_bwd (depth_bwd_kernel) -> (dq [R,I], dk, dv shaped like k); NaN presets and guard rows as above."""
+    lib = lib or L.load()
+    dev = q.device if device is None else device
+    q, k, v, a, dz = _f32(q, dev), _f32(k, dev), _f32(v, dev), _f32(attn, dev), _f32(dz, dev)
+    R, I = q.shape
+    RC = R // HW * D * HW
+    if I % hn or R % HW or k.shape != (RC, I) or v.shape != k.shape or a.numel() != R * hn * D or dz.shape != q.shape:
+        raise ValueError("op_train_depth_attn_bwd: operands do not match q [R,I]")
+    dq, dk, dv = _nan_guarded(R, I, dev), _nan_guarded(RC, I, dev), _nan_guarded(RC, I, dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_train_depth_attn_bwd(L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(a), L.ptr(dz), R, HW, D, hn, I // hn, L.ptr(dq),
+                                                L.ptr(dk), L.ptr(dv), _stream()))
+    for t, n, name in ((dq, R, "dq"), (dk, RC, "dk"), (dv, RC, "dv")):
+        _nan_guard_intact(t, n, f"op_train_depth_attn_bwd ({name})")
+    return dq[:R].clone(), dk[:RC].clone(), dv[:RC].clone()
+
+
+def op_train_im2col3(x, device=None, lib=None):
+    """mvd_op_train_im2col3: x [B,H,W,C] -> col [B*H*W, 9*C] (tap-major columns, zero outside the image)."""
+    lib = lib or L.load()
+    dev = x.device if device is None else device
+    x = _f32(x, dev)
+    B, H, W, Cc = x.shape
+    col = _nan_guarded(B * H * W, 9 * Cc, dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_train_im2col3(L.ptr(x), B, H, W, Cc, L.ptr(col), _stream()))
+    _nan_guard_intact(col, B * H * W, "op_train_im2col3")
+    return col[:B * H * W].clone()
+
+
+def op_train_col2im3(dcol, B, H, W, device=None, lib=None):
+    """mvd_op_train_col2im3: dcol [B*H*W, 9*C] -> dx [B,H,W,C], the transpose of op_train_im2col3."""
+    lib = lib or L.load()
+    dev = dcol.device if device is None else device
+    dcol = _f32(dcol, dev)
+    if dcol.dim() != 2 or dcol.shape[0] != B * H * W or dcol.shape[1] % 9:
+        raise ValueError("op_train_col2im3: dcol [B*H*W, 9*C] expected")
+    Cc = dcol.shape[1] // 9
+    dx = _nan_guarded(B * H * W, Cc, dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_train_col2im3(L.ptr(dcol), B, H, W, Cc, L.ptr(dx), _stream()))
+    _nan_guard_intact(dx, B * H * W, "op_train_col2im3")
+    return dx[:B * H * W].reshape(B, H, W, Cc).clone()
+
+
+def op_train_perm_w3(src, N, Cc, to_mat, device=None, lib=None):
+    """mvd_op_train_perm_w3: conv weight [N,C,3,3] -> GEMM matrix [N,9,C] (to_mat) or the reverse."""
+    lib = lib or L.load()
+    dev = src.device if device is None else device
+    src = _f32(src, dev)
+    if src.numel() != N * Cc * 9:
+        raise ValueError("op_train_perm_w3: N * C * 9 elements expected")
+    dst = _nan_guarded(N, 9 * Cc, dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_train_perm_w3(L.ptr(src), N, Cc, bool(to_mat), L.ptr(dst), _stream()))
+    _nan_guard_intact(dst, N, "op_train_perm_w3")
+    return dst[:N].reshape((N, 9, Cc) if to_mat else (N, Cc, 3, 3)).clone()
+
+
 IncompatibleKeys = collections.namedtuple("IncompatibleKeys", ["missing_keys", "unexpected_keys"])
 MAX_SAMPLE_SLOTS = 64  # per-sample mesh / camera tables kept resident in the context (mvd_select_sample)
 
@@ -1549,6 +1637,39 @@ class Engine:
         L.check(self.lib.mvd_op_attention(self._ctx, L.ptr(q), L.ptr(k), L.ptr(v), B, T, heads, Cc // heads, L.ptr(out),
                                           _stream()))
         return out
+
+    def op_attention_ex(self, q, k, v, heads, Tstride=0, ld_pad=0, xcd=-1):
+        """mvd_op_attention_ex: attn_kernel on the fused 16-bit image with samples ``Tstride`` rows apart (0 = T) and ``ld_pad`` pad
+        columns, everything but q, k, v preset to NaN.  Asserts that every pad row and the guard row of the result are still NaN
+        (the kernel wrote its own rows only) and returns [B,T,C] fp32.  xcd: -1 environment, 0 / 1 without / with the XCD remap."""
+        dev = self.device
+        q, k, v = _f32(q, dev), _f32(k, dev), _f32(v, dev)
+        B, T, Cc = q.shape
+        Ts = Tstride or T
+        out = torch.zeros(B * max(Ts, T) + 1, Cc, device=dev, dtype=torch.float32)
+        L.check(self.lib.mvd_op_attention_ex(self._ctx, L.ptr(q), L.ptr(k), L.ptr(v), B, T, heads, Cc // heads, Tstride, ld_pad, xcd,
+                                             L.ptr(out), _stream()))
+        body = out[:B * Ts].reshape(B, Ts, Cc)
+        assert bool(torch.isnan(out[B * Ts:]).all()) and bool(torch.isnan(body[:, T:]).all()), \
+            "op_attention_ex: the launch wrote outside its result (a pad row or the guard row changed)"
+        return body[:, :T].clone()
+
+    def op_attention_bwd_ex(self, q, k, v, d_out, heads):
+        """mvd_op_attention_bwd_ex -> (dq, dk, dv [B,T,C], lse [B,heads,T] in log2 units, delta [B,heads,T], o [B,T,C]).  Asserts the
+        guard rows behind dqkv, o, lse and delta and that the kernels wrote every element they return."""
+        dev = self.device
+        q, k, v, d_out = _f32(q, dev), _f32(k, dev), _f32(v, dev), _f32(d_out, dev)
+        B, T, Cc = q.shape
+        rows, nstat = B * T, B * heads * T
+        dq, dk, dv, o = (torch.zeros(rows + 1, Cc, device=dev, dtype=torch.float32) for _ in range(4))
+        lse, delta = (torch.zeros(nstat + 1, device=dev, dtype=torch.float32) for _ in range(2))
+        L.check(self.lib.mvd_op_attention_bwd_ex(self._ctx, L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(d_out), B, T, heads, Cc // heads,
+                                                 L.ptr(dq), L.ptr(dk), L.ptr(dv), L.ptr(lse), L.ptr(delta), L.ptr(o), _stream()))
+        for t, n, name in ((dq, rows, "dq"), (dk, rows, "dk"), (dv, rows, "dv"), (o, rows, "o"), (lse, nstat, "lse"), (delta, nstat, "delta")):
+            assert bool(torch.isnan(t[n:]).all()), f"op_attention_bwd_ex: the launch wrote behind {name} (guard changed)"
+            assert not bool(torch.isnan(t[:n]).any()), f"op_attention_bwd_ex: elements of {name} were never written (still NaN)"
+        return (dq[:rows].reshape(B, T, Cc), dk[:rows].reshape(B, T, Cc), dv[:rows].reshape(B, T, Cc),
+                lse[:nstat].reshape(B, heads, T), delta[:nstat].reshape(B, heads, T), o[:rows].reshape(B, T, Cc))
 
     def op_depth_attn(self, qk, ctx, fill_row=None, nfill=0, split=False, ldx=0, heads=4, return_hi=False):
         """depth_attn_kernel (csrc/k_depth.hip) on its own: qk [n_cond*HW, 4, Cc] (the folded query), ctx [n_cond, D, HW, Cc]
