@@ -392,6 +392,41 @@ int mvd_op_mesh_vertex_colors(const void* images, int dtype, int layout, const i
                               const float* centres, int N, int Nv, int Nf, int H, int W, float power, int bias, int two_sided,
                               float fill_r, float fill_g, float fill_b, float* color, float* weight_sum, int32_t* n_seen, float* spread,
                               unsigned char* visible, void* stream);
+/* The morphable-model forward (csrc/k_morph.hip): FLAME / SMPL-X parameters to vertices by linear blend skinning, the formulas of
+ * the reference's third_party/MICA/models/lbs.py.  No context; device pointers but `parents`; each call synchronises the stream.
+ * Everything is fp32 on the vector ALU with fused multiply-adds in an order fixed by indices alone, no atomics: two calls agree
+ * bit for bit, frame f of a batch equals the same frame computed alone, and both library builds give the same bits.
+ *   mvd_op_morph_pose     one wave per frame.  betas [F,NB], pose [F,J,3] (axis-angle), j_template [J,3], j_dirs [NB,J*3]:
+ *                 the joint regressor folded into the template and the shape directions at load (J_reg (t + S b) = J_reg t +
+ *                 (J_reg S) b), so j_rest [F,J,3] = j_template + sum_n betas[f,n] j_dirs[n], n ascending.  Rodrigues as the
+ *                 reference writes it: q = r + 1e-8 per component, angle = |q|, k = r / angle, D = sin(angle) K + (1 - cos(angle))
+ *                 K^2 with K the cross-product matrix of k, R = I + D: a zero vector gives D = 0 and R = I exactly.
+ *                 rot [F,J,9] = R; pose_feature [F,9 (J-1)] = R_j - I for j >= 1, taken as D_j (may be NULL when J == 1).
+ *                 Chain, joints in index order with p = parents[j]: G_j = G_p R_j (G_0 = R_0) and the translation of the
+ *                 relative transform directly, a_j = a_p - G_p (D_j j_rest_j) (a_0 = -D_0 j_rest_0), which is the reference's
+ *                 t_j - G_j j_rest_j with the rest offsets cancelled analytically: a zero pose gives A = [I|0] exactly.
+ *                 A [F,J,12] = [G_j | a_j] (3x4 row-major; the reference's fourth row is constant); joints [F,J,3], the posed
+ *                 joints, as the reference chains them: t_j = G_p (j_rest_j - j_rest_p) + t_p, t_0 = j_rest_0.
+ *                 parents: HOST array of J <= 64 entries, parents[0] == -1 and
+ *                 0 <= parents[j] < j, checked here and passed to the kernel by value.
+ *   mvd_op_morph_skin     basis [L,3V]: the shape directions re-packed to [NB,3V] with the pose directions [9 (J-1),3V] appended,
+ *                 coef [F,L] = betas with the pose feature appended, L = NB + 9 (J-1); v_template [V,3], weights [V,J],
+ *                 A [F,J,12], post [12] (3x4, may be NULL).  b_k = fma chain over l ascending starting from v_template[v,k];
+ *                 T = sum_j weights[v,j] A[f,j], j ascending; out_i = fma(T_i0, b_0, fma(T_i1, b_1, fma(T_i2, b_2, T_i3))); then
+ *                 the same form with post if given.  verts [F,V,3].  A workgroup owns 16 vertices and a tile of 32 frames: the
+ *                 basis is read once per 32 frames, and the order over l does not depend on the tiling.
+ *   mvd_op_morph_landmarks   verts [F,V,3], faces [Nf,3] int32, lmk_face [M] int32, lmk_bary [M,3]: out [F,M,3] =
+ *                 fma(w_2, x_2, fma(w_1, x_1, w_0 x_0)) over the corners of face lmk_face[m] (a static embedding).  A face or
+ *                 vertex index out of range is never dereferenced: that landmark is NaN.
+ * Errors, which return before the first HIP call: a null pointer (but post, and pose_feature when J == 1); F, V, L, NB, M or
+ * Nf < 1; J < 1 or J > 64; L != NB + 9 (J-1); a bad parents; F V 3 >= 2^31 (and F M 3, F J 12, NB J 3 likewise).
+ * Not computed: the pose-dependent contour landmarks, vertex normals, any backward pass. */
+int mvd_op_morph_pose(const float* betas, const float* pose, const float* j_template, const float* j_dirs, const int32_t* parents, int F,
+                      int NB, int J, float* j_rest, float* rot, float* pose_feature, float* joints, float* A, void* stream);
+int mvd_op_morph_skin(const float* basis, const float* v_template, const float* coef, const float* weights, const float* A,
+                      const float* post, int F, int V, int L, int NB, int J, float* verts, void* stream);
+int mvd_op_morph_landmarks(const float* verts, const int32_t* faces, const int32_t* lmk_face, const float* lmk_bary, int F, int V, int Nf,
+                           int M, float* out, void* stream);
 /* The conditioner's backward for ONE sample (its mesh / cameras active: mvd_select_sample): re-runs construct_spatial_volume and
  * construct_view_frustum_volume (morphable_diffusion.py:203-320: step embedding, 2-D encoder on the N noisy views, vertex gather,
  * view fusion, sparse voxel CNN in train mode, lattice gather, frustum gather and FrustumTV3DNet for the target view) with every

@@ -683,6 +683,34 @@ int mvd_op_mesh_vertex_colors(const void* images, int dtype, int layout, const i
   return rc;
 }
 
+// ---- the morphable-model forward (csrc/k_morph.hip): no context, the caller's device buffers; parents is a host array
+int mvd_op_morph_pose(const float* betas, const float* pose, const float* j_template, const float* j_dirs, const int32_t* parents, int F,
+                      int NB, int J, float* j_rest, float* rot, float* pose_feature, float* joints, float* A, void* stream) {
+  RET_IF(morph_pose_check("mvd_op_morph_pose", betas, pose, j_template, j_dirs, parents, F, NB, J, j_rest, rot, pose_feature, joints, A));
+  hipStream_t s = S(stream);
+  int rc = launch_morph_pose(betas, pose, j_template, j_dirs, parents, F, NB, J, j_rest, rot, pose_feature, joints, A, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_morph_pose: stream synchronisation failed");
+  return rc;
+}
+
+int mvd_op_morph_skin(const float* basis, const float* v_template, const float* coef, const float* weights, const float* A,
+                      const float* post, int F, int V, int L, int NB, int J, float* verts, void* stream) {
+  RET_IF(morph_skin_check("mvd_op_morph_skin", basis, v_template, coef, weights, A, F, V, L, NB, J, verts));
+  hipStream_t s = S(stream);
+  int rc = launch_morph_skin(basis, v_template, coef, weights, A, post, F, V, L, J, verts, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_morph_skin: stream synchronisation failed");
+  return rc;
+}
+
+int mvd_op_morph_landmarks(const float* verts, const int32_t* faces, const int32_t* lmk_face, const float* lmk_bary, int F, int V, int Nf,
+                           int M, float* out, void* stream) {
+  RET_IF(morph_landmarks_check("mvd_op_morph_landmarks", verts, faces, lmk_face, lmk_bary, F, V, Nf, M, out));
+  hipStream_t s = S(stream);
+  int rc = launch_morph_landmarks(verts, faces, lmk_face, lmk_bary, F, V, Nf, M, out, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_morph_landmarks: stream synchronisation failed");
+  return rc;
+}
+
 // ---- parity hooks of the sparse voxel CNN (tests/test_gpu_sparse_cnn_ops.py): no context, the caller's device buffers, scratch and
 // weight packs that live for the call (freed after the stream has been synchronised)
 namespace {

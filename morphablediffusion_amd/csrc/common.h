@@ -301,6 +301,23 @@ int launch_mesh_vertex_colors(const void* images, int dtype, int layout, const i
                               const int* pix_key, const float* verts, const float* normals, const float* centres, int N, int Nv, int Nf,
                               int H, int W, float power, int bias, int two_sided, float fill_r, float fill_g, float fill_b, float* color,
                               float* weight_sum, int* n_seen, float* spread, unsigned char* visible, hipStream_t s);
+// k_morph.hip: the morphable-model forward (include/mvd.h: mvd_op_morph_pose / _skin / _landmarks).  The *_check functions are the
+// argument errors (0 = fine) and touch no device; parents [J] is a HOST array, copied into the pose kernel's argument struct.
+// pose_feature [F][9 (J - 1)] may be null when J == 1, post [12] may be null; everything else is a device buffer of the caller.
+constexpr int MORPH_MAX_JOINTS = 64;
+int morph_pose_check(const char* who, const float* betas, const float* pose, const float* j_template, const float* j_dirs,
+                     const int* parents, int F, int NB, int J, const float* j_rest, const float* rot, const float* pose_feature,
+                     const float* joints, const float* A);
+int launch_morph_pose(const float* betas, const float* pose, const float* j_template, const float* j_dirs, const int* parents, int F,
+                      int NB, int J, float* j_rest, float* rot, float* pose_feature, float* joints, float* A, hipStream_t s);
+int morph_skin_check(const char* who, const float* basis, const float* v_template, const float* coef, const float* weights,
+                     const float* A, int F, int V, int L, int NB, int J, const float* verts);
+int launch_morph_skin(const float* basis, const float* v_template, const float* coef, const float* weights, const float* A,
+                      const float* post, int F, int V, int L, int J, float* verts, hipStream_t s);
+int morph_landmarks_check(const char* who, const float* verts, const int* faces, const int* lmk_face, const float* lmk_bary, int F, int V,
+                          int Nf, int M, const float* out);
+int launch_morph_landmarks(const float* verts, const int* faces, const int* lmk_face, const float* lmk_bary, int F, int V, int Nf, int M,
+                           float* out, hipStream_t s);
 int launch_latent_gather(const float* feats, const int* grid, int gd, int gh, int gw, const float* min_xyz,
                          const int* out_sh, float voxel, int V, float vol_len, float* out, hipStream_t s);
 int launch_sparse_densify(const float* feats, const int* grid, long nvox, int C, float* out, hipStream_t s);

@@ -214,6 +214,120 @@ def op_mesh_vertex_colors(images, xy, key, faces, face_id, pix_key, verts, norma
     return out
 
 
+# ---- the morphable-model forward (include/mvd.h: mvd_op_morph_pose / _skin / _landmarks; csrc/k_morph.hip): context-free.
+MORPH_MAX_JOINTS = 64
+
+
+def _float_arg(who, name, t, shape):
+    """ValueError unless t is a float tensor of that shape (None = any size >= 1)."""
+    if not torch.is_tensor(t) or not t.is_floating_point() or t.dim() != len(shape) or \
+            any((d < 1) if s is None else (s != d) for s, d in zip(shape, t.shape)):
+        raise ValueError(f"{who}: {name} must be a float tensor {list(shape)}, got {getattr(t, 'dtype', type(t))} "
+                         f"{tuple(getattr(t, 'shape', ()))}")
+
+
+def morph_parents(who, parents, J=None):
+    """parents as a list of ints after the C entry point's own rule: parents[0] == -1 and 0 <= parents[j] < j, at most 64 joints."""
+    p = [int(v) for v in (parents.tolist() if hasattr(parents, "tolist") else parents)]
+    if len(p) < 1 or len(p) > MORPH_MAX_JOINTS or (J is not None and len(p) != J):
+        raise ValueError(f"{who}: parents must have J = {J if J is not None else '1..64'} entries (at most {MORPH_MAX_JOINTS}), got {len(p)}")
+    if p[0] != -1 or any(not (0 <= p[j] < j) for j in range(1, len(p))):
+        raise ValueError(f"{who}: parents[0] must be -1 and 0 <= parents[j] < j, got {p}")
+    return p
+
+
+def op_morph_pose(betas, pose, j_template, j_dirs, parents, device=None, lib=None):
+    """mvd_op_morph_pose on ``device`` (default: betas'): betas [F,NB], pose [F,J,3] (axis-angle), j_template [J,3], j_dirs
+    [NB,J*3] (the joint regressor folded into the template and the shape directions), parents: J host integers.  Returns a dict
+    of float32 device tensors: j_rest [F,J,3], rot [F,J,3,3], pose_feature [F,9 (J-1)], joints [F,J,3] (posed), A [F,J,3,4]."""
+    who = "op_morph_pose"
+    _float_arg(who, "betas", betas, (None, None))
+    F, NB = betas.shape
+    _float_arg(who, "pose", pose, (F, None, 3))
+    J = pose.shape[1]
+    if J > MORPH_MAX_JOINTS:
+        raise ValueError(f"{who}: at most {MORPH_MAX_JOINTS} joints, got {J}")
+    _float_arg(who, "j_template", j_template, (J, 3))
+    _float_arg(who, "j_dirs", j_dirs, (NB, J * 3))
+    par = morph_parents(who, parents, J)
+    if F * J * 12 >= 2 ** 31:
+        raise ValueError(f"{who}: F J 12 must be below 2^31")
+    dev = betas.device if device is None else device
+    b, p, jt, jd = _f32(betas, dev), _f32(pose, dev), _f32(j_template, dev), _f32(j_dirs, dev)
+    lib = lib or L.load()
+    nan = float("nan")
+    out = {"j_rest": torch.full((F, J, 3), nan, device=dev), "rot": torch.full((F, J, 3, 3), nan, device=dev),
+           "pose_feature": torch.full((F, 9 * (J - 1)), nan, device=dev), "joints": torch.full((F, J, 3), nan, device=dev),
+           "A": torch.full((F, J, 3, 4), nan, device=dev)}
+    par_c = (C.c_int32 * J)(*par)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_morph_pose(L.ptr(b), L.ptr(p), L.ptr(jt), L.ptr(jd), C.addressof(par_c), F, NB, J, L.ptr(out["j_rest"]),
+                                      L.ptr(out["rot"]), L.ptr(out["pose_feature"]) if J > 1 else None, L.ptr(out["joints"]),
+                                      L.ptr(out["A"]), _stream()))
+    return out
+
+
+def op_morph_skin(basis, v_template, coef, weights, A, post=None, n_betas=None, device=None, lib=None):
+    """mvd_op_morph_skin on ``device`` (default: basis'): basis [L,3V] (shape directions [NB,3V], then pose directions
+    [9 (J-1),3V]), v_template [V,3], coef [F,L], weights [V,J], A [F,J,3,4] or [F,J,12], post [3,4] or None.  n_betas: NB
+    (default L - 9 (J-1)); L must be NB + 9 (J-1).  Returns verts [F,V,3] float32 on the device."""
+    who = "op_morph_skin"
+    _float_arg(who, "v_template", v_template, (None, 3))
+    V = v_template.shape[0]
+    _float_arg(who, "basis", basis, (None, 3 * V))
+    Lb = basis.shape[0]
+    _float_arg(who, "coef", coef, (None, Lb))
+    F = coef.shape[0]
+    _float_arg(who, "weights", weights, (V, None))
+    J = weights.shape[1]
+    if J > MORPH_MAX_JOINTS:
+        raise ValueError(f"{who}: at most {MORPH_MAX_JOINTS} joints, got {J}")
+    if torch.is_tensor(A) and A.dim() == 4:
+        _float_arg(who, "A", A, (F, J, 3, 4))
+    else:
+        _float_arg(who, "A", A, (F, J, 12))
+    NB = Lb - 9 * (J - 1) if n_betas is None else int(n_betas)
+    if NB < 1 or Lb != NB + 9 * (J - 1):
+        raise ValueError(f"{who}: basis has L = {Lb} rows, which must be NB + 9 (J - 1) with NB >= 1 (J = {J}, NB = {NB})")
+    if post is not None:
+        _float_arg(who, "post", post, (3, 4))
+    if F * V * 3 >= 2 ** 31:
+        raise ValueError(f"{who}: F V 3 must be below 2^31, got F = {F}, V = {V}")
+    dev = basis.device if device is None else device
+    bs, vt, cf, wt, a = _f32(basis, dev), _f32(v_template, dev), _f32(coef, dev), _f32(weights, dev), _f32(A, dev)
+    ps = None if post is None else _f32(post, dev)
+    lib = lib or L.load()
+    verts = torch.full((F, V, 3), float("nan"), device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_morph_skin(L.ptr(bs), L.ptr(vt), L.ptr(cf), L.ptr(wt), L.ptr(a), L.ptr(ps), F, V, Lb, NB, J, L.ptr(verts),
+                                      _stream()))
+    return verts
+
+
+def op_morph_landmarks(verts, faces, lmk_face, lmk_bary, device=None, lib=None):
+    """mvd_op_morph_landmarks on ``device`` (default: verts'): verts [F,V,3] float, faces [Nf,3] and lmk_face [M] int32, lmk_bary
+    [M,3] float.  Returns [F,M,3] float32 on the device; a landmark whose face or vertex index is out of range is NaN."""
+    who = "op_morph_landmarks"
+    _float_arg(who, "verts", verts, (None, None, 3))
+    F, V = verts.shape[:2]
+    _i32("faces", faces, (None, 3), who)
+    _i32("lmk_face", lmk_face, (None,), who)
+    Nf, M = faces.shape[0], lmk_face.shape[0]
+    if Nf < 1 or M < 1:
+        raise ValueError(f"{who}: at least one face and one landmark are needed, got Nf = {Nf}, M = {M}")
+    _float_arg(who, "lmk_bary", lmk_bary, (M, 3))
+    if F * V * 3 >= 2 ** 31 or F * M * 3 >= 2 ** 31:
+        raise ValueError(f"{who}: F V 3 and F M 3 must be below 2^31")
+    dev = verts.device if device is None else device
+    v, bc = _f32(verts, dev), _f32(lmk_bary, dev)
+    fc, lf = (t.detach().to(dev).contiguous() for t in (faces, lmk_face))
+    lib = lib or L.load()
+    out = torch.full((F, M, 3), float("nan"), device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_morph_landmarks(L.ptr(v), L.ptr(fc), L.ptr(lf), L.ptr(bc), F, V, Nf, M, L.ptr(out), _stream()))
+    return out
+
+
 # ---- the sparse voxel CNN's kernels one at a time (include/mvd.h: mvd_op_sparse_conv ...): context-free like op_train_loss.
 # w: the 3x3x3 kernel in checkpoint layout 0 [Cout,Cin,3,3,3], 1 [Cout,3,3,3,Cin] or 2 [3,3,3,Cin,Cout]; nbr [n_out,27] int32.
 SPARSE_FORMS = ("site", "mfma")  # form of mvd_op_sparse_conv / mvd_op_sparse_conv_bwd, by index

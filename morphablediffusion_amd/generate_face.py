@@ -21,6 +21,13 @@ Differences, all outside the denoising path and stated here:
   * --export_mesh / --mesh_overlay (not reference flags; mesh.py): the conditioning mesh coloured from the 16 generated views as
     ``<output_dir>/<input>_<exp>_mesh.ply`` with its statistics in ``<input>_<exp>_mesh.json``, and the mesh drawn over the views
     as ``<input>_<exp>_overlay.png`` (a check of the mesh's alignment).  Both need a mesh file with faces.
+  * --flame_model MODEL.{npz,pkl} --flame_params PARAMS.npz (not reference flags; morphable.py) replace --mesh: the conditioning
+    mesh is computed from FLAME parameters (any of shape, expression, global_pose, neck, jaw, eyes; a leading frame axis gives
+    several frames) on the device, the step the reference leaves to MICA's FLAME module, and aligned in the same pass.  With
+    --neutral_params NEUTRAL.npz --frames K the K frames sweep from the neutral to the target parameters.  One frame writes
+    ``<input>_<exp>.png`` as before, several write ``<input>_<exp>_fNN.png`` each (and the --export_mesh / --mesh_overlay /
+    --gt_dir files with the same ``_fNN``); frames are sampled --frame_batch at a time.  With none of these flags the program
+    does exactly what it did without them.
 """
 import argparse
 import json
@@ -128,7 +135,7 @@ def build_parser():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument("--input_img", type=str, required=True)
     p.add_argument("--exp_img", type=str, required=True)
-    p.add_argument("--mesh", type=str, required=True)
+    p.add_argument("--mesh", type=str, default=None, help="required unless --flame_model / --flame_params are given")
     p.add_argument("--cfg", type=str, default="configs/facescape.yaml")
     p.add_argument("--ckpt", type=str, default="ckpt/facescape_flame.ckpt")
     p.add_argument("--output_dir", type=str, required=True)
@@ -154,7 +161,72 @@ def build_parser():
                         "colours fused from the generated views) and <img>_<exp>_mesh.json (coverage, consistency, visible counts)")
     p.add_argument("--mesh_overlay", action="store_true",
                    help="not a reference flag: write <output_dir>/<img>_<exp>_overlay.png, the mesh drawn over the generated views")
+    p.add_argument("--flame_model", type=str, default=None,
+                   help="not a reference flag: a FLAME model file (.npz or .pkl with the FLAME pickle's key names); with "
+                        "--flame_params the mesh is computed from parameters instead of read from --mesh")
+    p.add_argument("--flame_params", type=str, default=None,
+                   help="not a reference flag: an .npz with any of shape, expression, global_pose, neck, jaw, eyes (a leading "
+                        "frame axis is allowed)")
+    p.add_argument("--neutral_params", type=str, default=None,
+                   help="not a reference flag: an .npz like --flame_params; with --frames K the frames sweep from it to --flame_params")
+    p.add_argument("--frames", type=int, default=1, help="not a reference flag: frames of the sweep (needs --neutral_params)")
+    p.add_argument("--frame_batch", type=int, default=1, help="not a reference flag: frames sampled in one batch")
+    p.add_argument("--flame_n_shape", type=int, default=None,
+                   help="not a reference flag: identity columns of the model's shapedirs to keep (MICA: 300; default: all)")
+    p.add_argument("--flame_n_exp", type=int, default=None,
+                   help="not a reference flag: expression columns (from column 300 on) to keep (MICA: 100; default: all)")
     return p
+
+
+FLAME_PARAM_KEYS = ("shape", "expression", "global_pose", "neck", "jaw", "eyes")
+
+
+def parse_args(argv=None):
+    """build_parser().parse_args plus the rules between the flags: --mesh alone as ever; --flame_model and --flame_params go
+    together and replace --mesh; --neutral_params and --frames > 1 go together and need them."""
+    p = build_parser()
+    flags = p.parse_args(argv)
+    flame = [flags.flame_model, flags.flame_params]
+    if not any(flame) and (flags.neutral_params or flags.frames != 1 or flags.frame_batch != 1):
+        p.error("--neutral_params, --frames and --frame_batch need --flame_model and --flame_params")
+    if any(flame):
+        if not all(flame):
+            p.error("--flame_model and --flame_params go together")
+        if flags.mesh:
+            p.error("give either --mesh or --flame_model / --flame_params, not both")
+        if flags.frames < 1 or flags.frame_batch < 1:
+            p.error("--frames and --frame_batch must be at least 1")
+        if (flags.frames > 1) != bool(flags.neutral_params):
+            p.error("--neutral_params and --frames K > 1 go together")
+    elif not flags.mesh:
+        p.error("the following arguments are required: --mesh (or --flame_model and --flame_params)")
+    return flags
+
+
+def load_flame_params(path):
+    """{key: float64 array} of the FLAME_PARAM_KEYS an .npz holds; any other key is an error (a misspelt name would be zeros)."""
+    with np.load(path, allow_pickle=False) as z:
+        unknown = [k for k in z.files if k not in FLAME_PARAM_KEYS]
+        if unknown:
+            raise ValueError(f"{path}: unknown parameter names {unknown}; known: {list(FLAME_PARAM_KEYS)}")
+        return {k: np.asarray(z[k], dtype=np.float64) for k in z.files}
+
+
+def flame_frames(flags, device):
+    """The conditioning meshes of --flame_model / --flame_params: (verts [F,Nv,3] on the device in the frame of
+    batch["vertices"], model-frame vertices [F,Nv,3] as a mesh file would store them, faces [Nf,3] or None)."""
+    from . import morphable as MM
+    fm = MM.MorphableModel.load(flags.flame_model, n_shape=flags.flame_n_shape, n_exp=flags.flame_n_exp, device=device)
+    params = load_flame_params(flags.flame_params)
+    if flags.neutral_params:
+        if any(v.ndim > 1 for v in params.values()):
+            raise ValueError(f"{flags.flame_params}: a sweep goes to ONE target, parameters with a frame axis cannot be swept to")
+        params = MM.interpolate_params(load_flame_params(flags.neutral_params), params, flags.frames)
+    if "shape" not in params:
+        params["shape"] = np.zeros(fm.n_shape)
+    verts = fm.flame(post=MM.flame_alignment(), **params)["vertices"]
+    stored = fm.flame(**params)["vertices"]
+    return verts, stored.cpu().numpy().astype(np.float64), None if fm.faces is None else fm.faces.cpu().numpy()
 
 
 def mesh_outputs(x_sample, cams, verts, faces, file_verts, output_dir, stem, export_mesh=False, mesh_overlay=False, **kw):
@@ -215,6 +287,8 @@ def run(flags, model=None):
     else:
         cams = B.virtual_cameras(NUM_VIEWS, 256)
     want_mesh = getattr(flags, "export_mesh", False) or getattr(flags, "mesh_overlay", False)
+    if getattr(flags, "flame_model", None):
+        return run_flame(flags, model, sampler, cams, input_img, img_name, exp_name, want_mesh)
     faces = None
     if want_mesh:
         from .mesh import read_mesh
@@ -255,8 +329,52 @@ def run(flags, model=None):
     return strip, str(output_fn)
 
 
+def run_flame(flags, model, sampler, cams, input_img, img_name, exp_name, want_mesh):
+    """run() with the mesh computed from FLAME parameters: every frame is one sample of a batch (frames_to_batch), sampled
+    --frame_batch at a time; returns (strip of the LAST frame, its path).  --prepare_neus2_data is a single-mesh export and is
+    refused for more than one frame."""
+    from PIL import Image
+    from . import morphable as MM
+    verts, stored, faces = flame_frames(flags, model.device)
+    F = verts.shape[0]
+    if want_mesh and faces is None:
+        raise ValueError(f"{flags.flame_model}: --export_mesh / --mesh_overlay need a model file with faces ('f')")
+    if flags.prepare_neus2_data and F > 1:
+        raise ValueError("--prepare_neus2_data exports one mesh's views: run it with a single frame")
+    strip, output_fn = None, None
+    for f0 in range(0, F, flags.frame_batch):
+        chunk = verts[f0:f0 + flags.frame_batch]
+        data = MM.frames_to_batch(input_img, chunk, num_views=NUM_VIEWS, image_size=256, device=model.device, cameras=cams)
+        x_sample = model.sample(sampler, data, flags.cfg_scale, flags.batch_view_num)
+        for i in range(chunk.shape[0]):
+            f = f0 + i
+            stem = f"{img_name}_{exp_name}" + (f"_f{f:02d}" if F > 1 else "")
+            strip = B.views_to_uint8(x_sample[i:i + 1], data["input_image"][i:i + 1])
+            output_fn = Path(flags.output_dir) / f"{stem}.png"
+            Image.fromarray(strip).save(output_fn)
+            if getattr(flags, "gt_dir", None):
+                from . import metrics as M
+                gt, gt_mask = M.load_target_views(flags.gt_dir, NUM_VIEWS, 256)
+                res = M.summarise(M.image_metrics(M.strip_to_views(strip, NUM_VIEWS, 256)[0].to(model.device), gt, gt_mask))
+                with open(Path(flags.output_dir) / f"{stem}_metrics.json", "w") as fh:
+                    json.dump(dict(res, sampler=flags.sampler, sample_steps=flags.sample_steps), fh, indent=2)
+            if want_mesh:
+                mesh_outputs(x_sample[i], cams, chunk[i], faces, stored[f], flags.output_dir, stem,
+                             export_mesh=getattr(flags, "export_mesh", False), mesh_overlay=getattr(flags, "mesh_overlay", False))
+    if flags.prepare_neus2_data:
+        neus2_root = os.path.join(flags.output_dir, "neus2_data", f"{img_name}_{exp_name}")
+        os.makedirs(os.path.join(neus2_root, "images"), exist_ok=True)
+        with open(os.path.join(neus2_root, "transform.json"), "w") as fh:
+            json.dump(B.neus2_transform(cams[0], cams[1], 256), fh, indent=4)
+        for idx in range(NUM_VIEWS):
+            bgra = B.neus2_view_bgra(strip, idx, 256)
+            rgba = np.concatenate([bgra[:, :, 2::-1], bgra[:, :, 3:]], -1).astype(np.uint8)
+            Image.fromarray(rgba, "RGBA").save(os.path.join(neus2_root, f"images/{str(idx).zfill(2)}.png"))
+    return strip, str(output_fn)
+
+
 def main(argv=None):
-    run(build_parser().parse_args(argv))
+    run(parse_args(argv))
 
 
 if __name__ == "__main__":

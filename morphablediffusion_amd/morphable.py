@@ -1,0 +1,292 @@
+"""The morphable-model forward: FLAME / SMPL-X parameters to vertices on the device (csrc/k_morph.hip through engine.op_morph_*).
+
+The reference conditions on a mesh file that a second program writes: MICA's ``FLAME`` module (third_party/MICA/models/flame.py,
+lbs.py) turns shape, expression and pose parameters into 5023 vertices.  ``MorphableModel`` is that step: it loads the model
+arrays (an ``.npz`` or the licensed ``.pkl`` with the same key names), folds the joint regressor into the template and the shape
+directions, re-packs the blend shapes to one [L,3V] basis, and runs linear blend skinning for one frame or a sweep of them.  The
+vertices go straight into ``batch.build_batch`` / ``stack_batches`` / ``model.sample`` / ``mesh.texture_mesh`` / ``write_ply``.
+
+    fm = MorphableModel.load("flame.npz", n_shape=300, n_exp=100)
+    out = fm.flame(shape, expression=exp, jaw=jaw, post=flame_alignment())
+    batch = frames_to_batch(input_image, out["vertices"], device="cuda:0")
+
+Units: FLAME's forward is in metres, and so are the mesh files of the reference pipeline, so ``unit_scale``
+defaults to 1.0.  Not here: the pose-dependent contour landmarks, fitting parameters to a mesh, vertex normals on the device.
+"""
+import io
+import pickle
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import batch as B
+from . import engine as E
+
+FLAME_EXPRESSION_OFFSET = 300  # FLAME's shapedirs: identity in columns 0..299, expression from column 300 on (flame.py:68)
+FLAME_JOINTS = ("global", "neck", "jaw", "eye_left", "eye_right")
+MODEL_KEYS = ("v_template", "shapedirs", "posedirs", "J_regressor", "kintree_table", "weights", "f")
+LANDMARK_KEYS = ("static_lmk_faces_idx", "static_lmk_bary_coords")  # optional, the names of FLAME's landmark embedding
+
+
+class _ChumpyArray:
+    """Stand-in for every ``chumpy.*`` class of a model pickle: keeps the pickled state, whose ``x`` is the array."""
+
+    def __setstate__(self, state):
+        self.__dict__.update(state if isinstance(state, dict) else {"x": state})
+
+    def array(self):
+        if "x" in self.__dict__:
+            return np.asarray(self.__dict__["x"])
+        for v in self.__dict__.values():
+            if isinstance(v, np.ndarray):
+                return v
+        raise pickle.UnpicklingError("a chumpy object of the model file holds no array")
+
+
+_NUMPY_GLOBALS = {(m, n) for m in ("numpy.core.multiarray", "numpy._core.multiarray") for n in ("_reconstruct", "scalar")} | \
+    {("numpy", "ndarray"), ("numpy", "dtype"), ("numpy.core.numeric", "_frombuffer"), ("numpy._core.numeric", "_frombuffer")}
+# object construction without a constructor call (protocols 0 and 1), and the str -> bytes step of arrays that Python 3 wrote at
+# protocol 2 or below
+_PLAIN_GLOBALS = {("copyreg", "_reconstructor"), ("copy_reg", "_reconstructor"), ("builtins", "object"), ("__builtin__", "object"),
+                  ("_codecs", "encode")}
+_SCIPY_CLASSES = {"csc_matrix", "csr_matrix", "coo_matrix", "csc_array", "csr_array", "coo_array"}
+
+
+class RestrictedUnpickler(pickle.Unpickler):
+    """Reads a FLAME / SMPL-X model pickle and nothing else: numpy array reconstruction, a scipy sparse matrix if scipy imports,
+    ``chumpy.*`` as a stand-in that keeps the array (chumpy itself is not needed); any other global raises UnpicklingError."""
+
+    def find_class(self, module, name):
+        if (module, name) in _NUMPY_GLOBALS or (module, name) in _PLAIN_GLOBALS:
+            return super().find_class(module, name)
+        if module == "chumpy" or module.startswith("chumpy."):
+            return _ChumpyArray
+        if module.startswith("scipy.sparse") and name in _SCIPY_CLASSES:
+            try:
+                import scipy.sparse  # noqa: F401
+            except ImportError:
+                raise pickle.UnpicklingError(f"the model file holds a {module}.{name}, and scipy is not installed")
+            return super().find_class(module, name)
+        raise pickle.UnpicklingError(f"global {module}.{name} is not allowed in a morphable-model file")
+
+
+def _plain(v):
+    """A value of a model file as a numpy array: chumpy stand-ins and sparse matrices unwrapped."""
+    if isinstance(v, _ChumpyArray):
+        v = v.array()
+    if hasattr(v, "toarray") and not isinstance(v, np.ndarray):
+        v = v.toarray()
+    return np.asarray(v)
+
+
+def read_model_file(path) -> Dict[str, np.ndarray]:
+    """{key: array} of an ``.npz`` (read without pickle) or a ``.pkl`` (through RestrictedUnpickler, latin1 as the Python 2
+    pickles need) with the FLAME / SMPL-X key names; only the keys the forward needs are returned."""
+    path = str(path)
+    if path.lower().endswith(".npz"):
+        with np.load(path, allow_pickle=False) as z:
+            d = {k: z[k] for k in z.files}
+    elif path.lower().endswith(".pkl"):
+        with open(path, "rb") as f:
+            d = RestrictedUnpickler(io.BytesIO(f.read()), encoding="latin1").load()
+        if not isinstance(d, dict):
+            raise ValueError(f"{path}: expected a pickled dict of model arrays")
+    else:
+        raise ValueError(f"{path}: expected a .npz or .pkl model file")
+    missing = [k for k in MODEL_KEYS[:-1] if k not in d]
+    if missing:
+        raise ValueError(f"{path}: missing {missing}")
+    return {k: _plain(d[k]) for k in MODEL_KEYS + LANDMARK_KEYS if k in d}
+
+
+def _rows(x, F, width, name):
+    """x as a float64 [F,width] array; a vector is one row, one row is repeated for every frame, None is zeros."""
+    if x is None:
+        return np.zeros((F, width))
+    x = np.asarray(x.detach().cpu() if torch.is_tensor(x) else x, dtype=np.float64)
+    x = x.reshape(1, -1) if x.ndim == 1 else x
+    if x.ndim != 2 or x.shape[1] != width or x.shape[0] not in (1, F):
+        raise ValueError(f"{name} must be [{width}] or [F,{width}] with F = {F}, got {x.shape}")
+    return np.broadcast_to(x, (F, width))
+
+
+class MorphableModel:
+    """A linear-blend-skinning model on one device: v_template [V,3], basis [L,3V] (shape directions, then pose directions),
+    weights [V,J], the folded joint regressor (j_template [J,3], j_dirs [NB,3J]) and the host list ``parents``."""
+
+    def __init__(self):
+        raise TypeError("use MorphableModel.from_arrays or MorphableModel.load")
+
+    @classmethod
+    def from_arrays(cls, v_template, shapedirs, posedirs, J_regressor, parents, weights, faces=None, lmk_face=None, lmk_bary=None,
+                    device="cuda:0", unit_scale=1.0, n_shape=None):
+        """v_template [V,3], shapedirs [V,3,NB], posedirs [V,3,9 (J-1)] (the pickle's layout) or [9 (J-1),3V] (lbs.py's),
+        J_regressor [J,V] (dense or scipy sparse), parents [J] (parents[0] is taken as the root whatever it holds), weights [V,J];
+        optional faces [Nf,3] and a static landmark embedding lmk_face [M], lmk_bary [M,3].  The folds run in float64:
+        j_template = J_regressor v_template, j_dirs = J_regressor shapedirs, basis = [shapedirs^T; posedirs]; lengths are
+        multiplied by unit_scale; the device gets float32.  n_shape: how many leading betas ``flame`` takes as identity."""
+        who = "MorphableModel.from_arrays"
+        vt = _plain(v_template).astype(np.float64)
+        if vt.ndim != 2 or vt.shape[1] != 3 or vt.shape[0] < 1:
+            raise ValueError(f"{who}: v_template must be [V,3], got {vt.shape}")
+        V = vt.shape[0]
+        S = _plain(shapedirs).astype(np.float64)
+        if S.ndim != 3 or S.shape[:2] != (V, 3) or S.shape[2] < 1:
+            raise ValueError(f"{who}: shapedirs must be [V,3,NB] with V = {V}, got {S.shape}")
+        NB = S.shape[2]
+        Jr = _plain(J_regressor).astype(np.float64)
+        if Jr.ndim != 2 or Jr.shape[1] != V or Jr.shape[0] < 1:
+            raise ValueError(f"{who}: J_regressor must be [J,V] with V = {V}, got {Jr.shape}")
+        J = Jr.shape[0]
+        if J > E.MORPH_MAX_JOINTS:
+            raise ValueError(f"{who}: at most {E.MORPH_MAX_JOINTS} joints, got {J}")
+        par = [int(p) for p in np.asarray(_plain(parents)).reshape(-1).astype(np.int64)]
+        if par:
+            par[0] = -1  # kintree_table stores 2^32 - 1 there (flame.py:82-83)
+        par = E.morph_parents(who, par, J)
+        W = _plain(weights).astype(np.float64)
+        if W.shape != (V, J):
+            raise ValueError(f"{who}: weights must be [V,J] = [{V},{J}], got {W.shape}")
+        P = _plain(posedirs).astype(np.float64)
+        NP = 9 * (J - 1)
+        if P.ndim == 3 and P.shape == (V, 3, NP):
+            P = P.reshape(3 * V, NP).T
+        elif P.ndim != 2 or P.shape != (NP, 3 * V):
+            raise ValueError(f"{who}: posedirs must be [V,3,{NP}] or [{NP},{3 * V}], got {P.shape}")
+        s = float(unit_scale)
+        self = object.__new__(cls)
+        self.V, self.NB, self.J, self.parents, self.unit_scale = V, NB, J, par, s
+        self.n_shape = NB if n_shape is None else int(n_shape)
+        if not 0 <= self.n_shape <= NB:
+            raise ValueError(f"{who}: n_shape must be in 0..{NB}, got {n_shape}")
+        self.device = torch.device(device)
+        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(self.device)
+        self.v_template = f32(vt * s)
+        self.basis = f32(np.concatenate([S.reshape(3 * V, NB).T, P], 0) * s)
+        self.weights = f32(W)
+        self.j_template = f32(Jr @ vt * s)
+        self.j_dirs = f32(np.einsum("jv,vkn->njk", Jr, S).reshape(NB, 3 * J) * s)
+        self.faces = self.lmk_face = self.lmk_bary = None
+        if faces is not None:
+            fc = np.asarray(_plain(faces)).astype(np.int64)
+            if fc.ndim != 2 or fc.shape[1] != 3 or fc.shape[0] < 1 or fc.min() < 0 or fc.max() >= V:
+                raise ValueError(f"{who}: faces must be [Nf,3] with indices in 0..{V - 1}, got {fc.shape}")
+            self.faces = torch.from_numpy(fc.astype(np.int32)).to(self.device)
+        if (lmk_face is None) != (lmk_bary is None):
+            raise ValueError(f"{who}: lmk_face and lmk_bary go together")
+        if lmk_face is not None:
+            if self.faces is None:
+                raise ValueError(f"{who}: a landmark embedding needs faces")
+            lf, lb = np.asarray(_plain(lmk_face)).astype(np.int64).reshape(-1), _plain(lmk_bary).astype(np.float64)
+            if len(lf) < 1 or lb.shape != (len(lf), 3) or lf.min() < 0 or lf.max() >= self.faces.shape[0]:
+                raise ValueError(f"{who}: lmk_face must be [M] face indices and lmk_bary [M,3], got {lf.shape} and {lb.shape}")
+            self.lmk_face, self.lmk_bary = torch.from_numpy(lf.astype(np.int32)).to(self.device), f32(lb)
+        return self
+
+    @classmethod
+    def load(cls, path, n_shape=None, n_exp=None, device="cuda:0", unit_scale=1.0):
+        """A model file (read_model_file).  n_shape / n_exp select columns of shapedirs as the reference's FLAME.__init__ does:
+        the first n_shape, then those from column 300 on (the first n_exp of them if n_exp is given); with neither, every
+        column is kept."""
+        d = read_model_file(path)
+        S = d["shapedirs"]
+        if S.ndim != 3:
+            raise ValueError(f"{path}: shapedirs must be [V,3,NB], got {S.shape}")
+        if n_shape is not None or n_exp is not None:
+            ns = min(FLAME_EXPRESSION_OFFSET, S.shape[2]) if n_shape is None else int(n_shape)
+            exp = S[:, :, FLAME_EXPRESSION_OFFSET:]
+            ne = exp.shape[2] if n_exp is None else int(n_exp)
+            if not (0 <= ns <= S.shape[2]) or not (0 <= ne <= exp.shape[2]) or ns + ne < 1:
+                raise ValueError(f"{path}: shapedirs has {S.shape[2]} columns ({exp.shape[2]} from column {FLAME_EXPRESSION_OFFSET} "
+                                 f"on), cannot take n_shape = {n_shape}, n_exp = {n_exp}")
+            S, n_shape = np.concatenate([S[:, :, :ns], exp[:, :, :ne]], 2), ns
+        kt = np.asarray(d["kintree_table"])
+        lm = {"lmk_face": d.get(LANDMARK_KEYS[0]), "lmk_bary": d.get(LANDMARK_KEYS[1])}
+        return cls.from_arrays(d["v_template"], S, d["posedirs"], d["J_regressor"], kt[0] if kt.ndim == 2 else kt, d["weights"],
+                               faces=d.get("f"), device=device, unit_scale=unit_scale, n_shape=n_shape, **lm)
+
+    def forward(self, betas, pose, post=None) -> Dict[str, Optional[torch.Tensor]]:
+        """betas [F,NB], pose [F,J,3] or [F,3J] (axis-angle), post [3,4] or None: an affine applied to the vertices in the
+        skinning pass (flame_alignment()).  Returns device tensors: vertices [F,V,3], joints [F,J,3] (the posed joints, in the
+        model's frame: post is not applied to them), landmarks [F,M,3] (of the returned vertices) or None without an embedding."""
+        who = "MorphableModel.forward"
+        if self.device.type != "cuda":
+            raise ValueError(f"{who}: the model is on {self.device}; the forward runs on the GPU only (model.to('cuda:0'))")
+        if not torch.is_tensor(betas) or not torch.is_tensor(pose):
+            betas, pose = torch.as_tensor(np.asarray(betas)), torch.as_tensor(np.asarray(pose))
+        if betas.dim() != 2 or betas.shape[1] != self.NB:
+            raise ValueError(f"{who}: betas must be [F,{self.NB}], got {tuple(betas.shape)}")
+        F = betas.shape[0]
+        if pose.dim() == 2 and pose.shape == (F, 3 * self.J):
+            pose = pose.reshape(F, self.J, 3)
+        if tuple(pose.shape) != (F, self.J, 3):
+            raise ValueError(f"{who}: pose must be [F,{self.J},3] or [F,{3 * self.J}] with F = {F}, got {tuple(pose.shape)}")
+        dev = self.device
+        betas = betas.detach().to(device=dev, dtype=torch.float32).contiguous()
+        p = E.op_morph_pose(betas, pose, self.j_template, self.j_dirs, self.parents, device=dev)
+        coef = torch.cat([betas, p["pose_feature"]], 1) if self.J > 1 else betas
+        verts = E.op_morph_skin(self.basis, self.v_template, coef, self.weights, p["A"], post=post, n_betas=self.NB, device=dev)
+        lmk = None if self.lmk_face is None else E.op_morph_landmarks(verts, self.faces, self.lmk_face, self.lmk_bary, device=dev)
+        return {"vertices": verts, "joints": p["joints"], "landmarks": lmk}
+
+    def flame(self, shape, expression=None, global_pose=None, neck=None, jaw=None, eyes=None, post=None):
+        """The reference's FLAME.forward (flame.py:252-279): betas = [shape, expression], full_pose = [global, neck, jaw, eyes]
+        (3, 3, 3 and 6 numbers); missing parts are zero.  Every argument is a vector or has a leading frame axis; single rows
+        are repeated for every frame."""
+        if self.J != len(FLAME_JOINTS):
+            raise ValueError(f"MorphableModel.flame: a FLAME model has {len(FLAME_JOINTS)} joints, this one {self.J}")
+        parts = {"shape": shape, "expression": expression, "global_pose": global_pose, "neck": neck, "jaw": jaw, "eyes": eyes}
+        F = max([1] + [int(v.shape[0]) for v in parts.values() if v is not None and np.ndim(v) == 2])
+        sh = np.asarray(shape.detach().cpu() if torch.is_tensor(shape) else shape)
+        n_sh = sh.shape[-1]
+        if n_sh > self.NB:
+            raise ValueError(f"MorphableModel.flame: shape has {n_sh} entries, the model {self.NB} betas")
+        betas = np.concatenate([_rows(shape, F, n_sh, "shape"), _rows(expression, F, self.NB - n_sh, "expression")], 1)
+        pose = np.concatenate([_rows(global_pose, F, 3, "global_pose"), _rows(neck, F, 3, "neck"), _rows(jaw, F, 3, "jaw"),
+                               _rows(eyes, F, 6, "eyes")], 1)
+        return self.forward(torch.from_numpy(betas), torch.from_numpy(pose), post=post)
+
+    def to(self, device):
+        self.device = torch.device(device)
+        for k in ("v_template", "basis", "weights", "j_template", "j_dirs", "faces", "lmk_face", "lmk_bary"):
+            if getattr(self, k) is not None:
+                setattr(self, k, getattr(self, k).to(self.device))
+        return self
+
+
+def flame_alignment() -> torch.Tensor:
+    """batch.align_flame_vertices as one 3x4 (float64): x -> S (2.5 (R (1.087 x) + T)) with S the axis swap, composed in
+    float64; pass it as ``post`` and the similarity rides along in the skinning pass."""
+    pose = torch.tensor(B.FLAME_POSE, dtype=torch.float64)
+    R = B.so3_exponential_map(pose[None, :3])[0]
+    S = torch.tensor([[1., 0., 0.], [0., 0., 1.], [0., -1., 0.]], dtype=torch.float64)
+    return torch.cat([S @ R * (2.5 * B.FLAME_SCALE), (S @ pose[3:] * 2.5)[:, None]], 1)
+
+
+def interpolate_params(a, b, K):
+    """K frames from parameter set ``a`` to ``b`` (dicts of vectors, e.g. shape / expression / jaw): every key of either, a
+    key missing on one side being zero there; betas linearly, poses linearly in axis-angle.  Frame 0 is ``a`` and frame K - 1
+    is ``b`` exactly (K = 1: ``b``).  Returns {key: float64 array [K,n]}."""
+    K = int(K)
+    if K < 1:
+        raise ValueError(f"interpolate_params: K must be at least 1, got {K}")
+    t = np.linspace(0.0, 1.0, K)[:, None] if K > 1 else np.ones((1, 1))
+    out = {}
+    for k in list(a) + [k for k in b if k not in a]:
+        x, y = (None if d.get(k) is None else np.asarray(d[k], dtype=np.float64).reshape(-1) for d in (a, b))
+        x = np.zeros_like(y) if x is None else x
+        y = np.zeros_like(x) if y is None else y
+        if x.shape != y.shape:
+            raise ValueError(f"interpolate_params: {k} has {x.shape[0]} entries on one side and {y.shape[0]} on the other")
+        out[k] = (1.0 - t) * x[None] + t * y[None]  # t = 0 and t = 1 give the end points exactly
+    return out
+
+
+def frames_to_batch(input_image, vertices_F, num_views=16, image_size=256, device="cpu", cameras=None):
+    """batch.build_batch for every frame of vertices_F [F,Nv,3] (already in the cube frame: post=flame_alignment()) with the
+    same input image and cameras, stacked by batch.stack_batches: a batch of F samples for model.sample."""
+    if vertices_F.dim() != 3 or vertices_F.shape[2] != 3 or vertices_F.shape[0] < 1:
+        raise ValueError(f"frames_to_batch: vertices must be [F,Nv,3], got {tuple(vertices_F.shape)}")
+    return B.stack_batches([B.build_batch(input_image, v, num_views=num_views, image_size=image_size, device=device, cameras=cameras)
+                            for v in vertices_F])
