@@ -611,7 +611,21 @@ int mvd_denoise_views_ms(mvd_ctx* ctx, int B, const int* slots, const float* x_n
                          float cfg_scale, const float* noise, float s1m, float sqrt_at, float c_x, float c_d, float c_c, float c_n,
                          float* x0_hist, int first, float* eps_out, float* x_next, void* stream);
 
-/* ---- single-kernel hooks used by the parity tests (tests/test_gpu_ops.py) ---- */
+/* ---- per-op hooks: one kernel, or one layer's launch sequence, on the caller's data ----
+ * The stateless product ops (mvd_op_cfg_ms, mvd_op_adamw_ex, mvd_op_lora_*, and above mvd_op_train_loss, mvd_op_image_metrics,
+ * mvd_op_mesh_*, mvd_op_morph_*) are defined with the product API in csrc/c_api.hip.  Everything else from here to the end of
+ * the section is a test or bench hook: csrc/c_api_hooks.hip, and for the backward, adjoint and gather hooks (which call the
+ * training step's file-local functions) the end of csrc/engine_train.hip, both on the scaffold of csrc/hooks.h.  Every hook
+ * that takes a context refuses a NULL one ("null context") before it touches anything.  The hooks come in two kinds:
+ *   asynchronous   mvd_op_conv, mvd_op_conv3d, mvd_op_linear, mvd_op_group_norm, mvd_op_depth_attn, mvd_op_group_norm_bwd,
+ *                  mvd_op_layer_norm_bwd, mvd_op_conv_bwd, mvd_op_linear_bwd, mvd_op_conv3d_bwd, mvd_op_tgemm and the adjoint /
+ *                  gather hooks (mvd_op_*_adjoint, mvd_op_*_gather): they enqueue on `stream` and return without synchronising
+ *                  it, so they can run beside work on another stream (tests/test_gpu_determinism.py, tools/race_micro.py);
+ *                  their scratch is the context's workspace, which the stream's order protects.
+ *   synchronous    every *_ex hook, mvd_op_layer_norm_slabs, mvd_op_folded_group_norm, mvd_op_softmax_rows, mvd_op_rows_split,
+ *                  the context-free sparse-CNN and mvd_op_train_* hooks, and the timing hooks (mvd_bench_*, mvd_op_st_tail /
+ *                  mvd_op_st_head with iters > 0): the stream is synchronised before the call returns.  The *_ex kind also checks
+ *                  its arguments before anything is launched and writes into caller buffers that carry guard rows. */
 /* The update kernel of mvd_denoise_views_ms on its own, over n device floats: eps = eps_u + scale (eps_c - eps_u) (eps_u NULL:
  * eps = eps_c), then the update above.  No context: runs on the current device. */
 int mvd_op_cfg_ms(const float* eps_c, const float* eps_u, float scale, const float* x, const float* noise, float s1m, float sqrt_at,
@@ -681,10 +695,6 @@ int mvd_op_linear(mvd_ctx* ctx, const float* a, int M, int K, const float* w, co
                   const float* resid, int a_half, int force_splitk, float* out, void* stream);
 int mvd_op_group_norm(mvd_ctx* ctx, const float* x_nchw, int B, int C, int HW, int groups, const float* gamma,
                       const float* beta, float eps, int act, float* out_nchw, void* stream);
-int mvd_op_layer_norm(mvd_ctx* ctx, const float* x, int rows, int C, const float* gamma, const float* beta, float* out,
-                      void* stream);
-int mvd_op_attention(mvd_ctx* ctx, const float* q, const float* k, const float* v, int B, int T, int heads, int d,
-                     float* out, void* stream);
 /* depth_attn_kernel (csrc/k_depth.hip) on its own, in the kernel's layouts: qk [n_cond*HW][4][Cc] fp32 (the folded query),
  * context [n_cond][D][HW][Cc] fp32 (rounded to fp16 here into rows of ldx >= Cc halfs, ldx % 8 == 0, 0 = Cc; the pad columns hold NaN
  * bit patterns, so a read past Cc shows in the result), fill_row [4*Cc] fp32 (nfill > 0; rounded to fp16, with split != 0 to the
@@ -697,11 +707,9 @@ int mvd_op_depth_attn(mvd_ctx* ctx, const float* qk, const float* context, const
                       int heads, int ldx, int split, int nfill, int check_only, float* out, float* hi_out, void* stream);
 int mvd_op_conv3d(mvd_ctx* ctx, const float* x_ncdhw, int B, int Cin, int D, int H, int W, const float* w,
                   const float* bias, int Cout, int stride, int transposed, const float* resid, float* out, void* stream);
-/* backward-kernel hooks used by tests/test_gpu_train_ops.py (each is compared with torch.autograd of the same op):
- * self-attention backward (q, k, v, d_out, dq, dk, dv: [B,T,heads*d] fp32; the kernels themselves work on fp16), GroupNorm
- * (+ SiLU / ReLU) backward and LayerNorm backward on channels-last fp32 ([B,rows,C] / [rows,C]). */
-int mvd_op_attention_bwd(mvd_ctx* ctx, const float* q, const float* k, const float* v, const float* d_out, int B, int T, int heads,
-                         int d, float* dq, float* dk, float* dv, void* stream);
+/* backward-kernel hooks used by tests/test_gpu_train_ops.py (each is compared with torch.autograd of the same op): GroupNorm
+ * (+ SiLU / ReLU) backward and LayerNorm backward on channels-last fp32 ([B,rows,C] / [rows,C]).  (The self-attention backward
+ * is mvd_op_attention_bwd_ex below.) */
 int mvd_op_group_norm_bwd(mvd_ctx* ctx, const float* x, const float* dy, int B, int rows, int C, int groups, const float* gamma,
                           const float* beta, float eps, int act, float* dx, float* dgamma, float* dbeta, void* stream);
 int mvd_op_layer_norm_bwd(mvd_ctx* ctx, const float* x, const float* dy, int rows, int C, const float* gamma, float* dx,
@@ -814,7 +822,8 @@ int mvd_op_rows_split(mvd_ctx* ctx, const float* x, int lda, int rows, int C, vo
  * those result rows as fp32, pad and guard rows included: they must come back NaN.  xcd: -1 = the workgroup order
  * MVD_ATTN_NO_XCD asks for, 0 = without the XCD remap, 1 = with it.
  *
- * mvd_op_attention_bwd_ex: mvd_op_attention_bwd's sequence (forward, cast of d_out, bwd_attention) with one guard row behind the
+ * mvd_op_attention_bwd_ex: the training step's sequence (attn_kernel forward, cast of d_out to 16 bits, bwd_attention; the kernels
+ * themselves work on the 16-bit images) with one guard row behind the
  * last sample of the qkv, o, dO and dqkv images; dqkv, lse and delta start as 0xFF bytes.  dq, dk, dv, o: [B * T + 1][C] fp32
  * (the last row is the guard); lse (log2 units, as the kernels keep it), delta: [B * heads * T + 1] fp32, the last element the
  * guard. */

@@ -21,47 +21,6 @@ const char* mvd_error_text() { return g_err.c_str(); }
 
 namespace {
 
-__global__ void split_rows_to_f32_kernel(const half_t* in, int rows, int C, float* out) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (size_t)rows * C; i += (size_t)gridDim.x * blockDim.x) {
-    const size_t r = i / C, c = i % C;
-    const half_t hi = in[r * 3 * C + c], lo = in[r * 3 * C + C + c], h2 = in[r * 3 * C + 2 * C + c];
-    out[i] = (float)hi == (float)h2 ? (float)hi + (float)lo : __builtin_nanf("");
-  }
-}
-__global__ void f16_to_f32_kernel(const half_t* in, float* out, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    out[i] = (float)in[i];
-}
-// fp32 [rows][C] -> fp16 rows ldo halfs apart (the pad columns are left as they are), and the reverse from rows ldi apart
-__global__ void rows_f32_to_f16_ld_kernel(const float* in, size_t rows, int C, half_t* out, int ldo) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * C; i += (size_t)gridDim.x * blockDim.x)
-    out[(i / C) * ldo + i % C] = (half_t)in[i];
-}
-__global__ void rows_f16_ld_to_f32_kernel(const half_t* in, size_t rows, int C, int ldi, float* out) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * C; i += (size_t)gridDim.x * blockDim.x)
-    out[i] = (float)in[(i / C) * ldi + i % C];
-}
-// q,k,v [rows][C] fp32 -> fp16 [rows][3C] (the layout of a fused q|k|v projection)
-__global__ void pack_qkv_rows_kernel(const float* q, const float* k, const float* v, int rows, int C, half_t* qkv) {
-  const long total = (long)rows * C;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int r = (int)(i / C), c = (int)(i % C);
-    qkv[(long)r * 3 * C + c] = (half_t)q[i];
-    qkv[(long)r * 3 * C + C + c] = (half_t)k[i];
-    qkv[(long)r * 3 * C + 2 * C + c] = (half_t)v[i];
-  }
-}
-// q,k,v [B][T][C] fp32 -> the fused 16-bit image [B][Tstride][ld] (q | k | v in the first 3 C columns); what lies between is left as it is
-__global__ void pack_qkv_image_kernel(const float* q, const float* k, const float* v, int B, int T, int C, int Tstride, int ld, half_t* qkv) {
-  const long total = (long)B * T * C;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % C);
-    const long r = i / C, row = (r / T) * Tstride + r % T;
-    qkv[row * ld + c] = (half_t)q[i];
-    qkv[row * ld + C + c] = (half_t)k[i];
-    qkv[row * ld + 2 * C + c] = (half_t)v[i];
-  }
-}
 // UNetWrapper.predict_with_unconditional_scale input assembly (morphable_diffusion.py:133-146), channels-last:
 // rows [0,TN) = [x | x_input / 0.18215], rows [TN,2TN) = [x | 0]
 // UNet input of one sample's TN views: rows [0, TN) of `out` = the conditional copies, rows [half_off, half_off + TN) the
@@ -88,13 +47,6 @@ __global__ void build_cfg_context_kernel(const float* clip, int TN, int dim, int
     const long row = (long)(b / TN) * half_off + (b % TN);
     ctx[row * dim + j] = b < TN ? clip[j] : 0.f;
     if (j == 0) t[row] = step;
-  }
-}
-__global__ void fill_pattern_f16_kernel(half_t* p, size_t n, unsigned seed) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    unsigned h = (unsigned)i * 2654435761u + seed;
-    h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;
-    p[i] = (half_t)(((float)(h & 0xFFFF) / 32768.0f) - 1.0f);
   }
 }
 
@@ -709,104 +661,6 @@ int mvd_op_morph_landmarks(const float* verts, const int32_t* faces, const int32
   int rc = launch_morph_landmarks(verts, faces, lmk_face, lmk_bary, F, V, Nf, M, out, s);
   if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_morph_landmarks: stream synchronisation failed");
   return rc;
-}
-
-// ---- parity hooks of the sparse voxel CNN (tests/test_gpu_sparse_cnn_ops.py): no context, the caller's device buffers, scratch and
-// weight packs that live for the call (freed after the stream has been synchronised)
-namespace {
-struct OpScratch {
-  std::vector<void*> bufs;
-  ~OpScratch() {
-    for (void* b : bufs) hipFree(b);
-  }
-  // elems of 4 bytes; poison: 0xFF bytes (NaN as a float, -1 as an int) before use
-  int get(size_t elems, bool poison, hipStream_t s, void** out) {
-    void* b = nullptr;
-    if (hipMalloc(&b, std::max<size_t>(elems, 1) * 4) != hipSuccess) return mvd_fail("parity hook: scratch allocation failed");
-    bufs.push_back(b);
-    if (poison && hipMemsetAsync(b, 0xFF, std::max<size_t>(elems, 1) * 4, s) != hipSuccess) return mvd_fail("parity hook: memset failed");
-    *out = b;
-    return 0;
-  }
-};
-int op_sync(const char* who, hipStream_t s, int rc) {
-  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail((std::string(who) + ": stream synchronisation failed").c_str());
-  return rc;
-}
-int sparse_op_check(const char* who, int n_out, int Cin, int Cout, int layout, int form) {
-  const std::string w(who);
-  if (n_out <= 0 || Cin <= 0 || Cout <= 0 || Cin > 256 || Cout > 256) return mvd_fail((w + ": row or channel count out of range").c_str());
-  if (layout < 0 || layout > 2) return mvd_fail((w + ": weight layout 0..2").c_str());
-  if (form != 0 && form != 1) return mvd_fail((w + ": form 0 (site) or 1 (matrix-core)").c_str());
-  if (form == 1 && !sparse_mfma_takes(Cin, Cout)) return mvd_fail((w + ": no matrix-core kernel for these channel counts").c_str());
-  return 0;
-}
-}  // namespace
-
-int mvd_op_sparse_conv(const float* in, const int32_t* nbr, int n_out, int Cin, int Cout, const float* w, int layout, const float* scale,
-                       const float* shift, int form, float* out, void* stream) {
-  if (!in || !nbr || !w || !out || !scale != !shift) return mvd_fail("mvd_op_sparse_conv: null argument");
-  RET_IF(sparse_op_check("mvd_op_sparse_conv", n_out, Cin, Cout, layout, form));
-  hipStream_t s = S(stream);
-  OpScratch z;
-  const size_t nw = (size_t)27 * Cin * Cout;
-  float *wpk = nullptr, *wp = nullptr;
-  RET_IF(z.get(nw, false, s, (void**)&wpk));
-  if (form == 1) RET_IF(z.get(nw, false, s, (void**)&wp));
-  int rc = launch_sparse_w_pack(w, Cin, Cout, layout, wpk, s);
-  if (!rc && wp) rc = launch_sparse_w_frag(wpk, Cin, Cout, 0, 0, wp, s);
-  if (!rc) rc = launch_sparse_conv(in, nbr, n_out, Cin, Cout, wpk, wp, scale, shift, out, s);
-  return op_sync("mvd_op_sparse_conv", s, rc);
-}
-
-int mvd_op_bn_rows_relu(const float* x, int n, int C, const float* gamma, const float* beta, float eps, float momentum, float* y,
-                        float* stats_out, float* rmean, float* rvar, void* stream) {
-  if (!x || !y || !gamma || !beta || !rmean != !rvar) return mvd_fail("mvd_op_bn_rows_relu: null argument");
-  if (n <= 0 || C <= 0) return mvd_fail("mvd_op_bn_rows_relu: row or channel count out of range");
-  hipStream_t s = S(stream);
-  return op_sync("mvd_op_bn_rows_relu", s, launch_bn_rows_relu(x, y, n, C, gamma, beta, eps, stats_out, s, rmean, rvar, momentum));
-}
-
-int mvd_op_bn_rows_relu_bwd(const float* xraw, float* dy, int n, int C, const float* gamma, const float* beta, const float* stats,
-                            int poison, float* dgamma, float* dbeta, void* stream) {
-  if (!xraw || !dy || !gamma || !beta || !stats || !dgamma || !dbeta) return mvd_fail("mvd_op_bn_rows_relu_bwd: null argument");
-  if (n <= 0 || C <= 0) return mvd_fail("mvd_op_bn_rows_relu_bwd: row or channel count out of range");
-  if (C > 256 || 256 % C) return mvd_fail("mvd_op_bn_rows_relu_bwd: the channel count must divide 256");
-  hipStream_t s = S(stream);
-  OpScratch z;
-  float* part = nullptr;
-  RET_IF(z.get((size_t)cbwd_bn_scratch_floats(n, C), poison != 0, s, (void**)&part));
-  return op_sync("mvd_op_bn_rows_relu_bwd", s, cbwd_bn_rows_relu(xraw, dy, n, C, gamma, beta, stats, part, dgamma, dbeta, s));
-}
-
-int mvd_op_sparse_conv_bwd(const float* in, const int32_t* nbr, float* d_out, int n_in, int n_out, int Cin, int Cout, int strided,
-                           int level0_subm, int deterministic, int form, const float* w, int layout, int poison, float* d_in, float* gw,
-                           void* stream) {
-  if (!in || !nbr || !d_out || !w || !d_in || !gw) return mvd_fail("mvd_op_sparse_conv_bwd: null argument");
-  RET_IF(sparse_op_check("mvd_op_sparse_conv_bwd", n_out, Cin, Cout, layout, form));
-  if (n_in <= 0) return mvd_fail("mvd_op_sparse_conv_bwd: row or channel count out of range");
-  if (strided && level0_subm) return mvd_fail("mvd_op_sparse_conv_bwd: level0_subm is a submanifold layer");
-  if (!strided && n_in != n_out) return mvd_fail("mvd_op_sparse_conv_bwd: a submanifold layer has n_in == n_out");
-  if (form == 0 && deterministic) return mvd_fail("mvd_op_sparse_conv_bwd: the site form's data gradient adds with fp32 atomics");
-  hipStream_t s = S(stream);
-  const bool mfma = form == 1, lvl0 = mfma && level0_subm != 0, det = deterministic != 0;
-  const SparseLayerScratch q = cbwd_sparse_layer_scratch(n_in, n_out, Cin, Cout, strided != 0, lvl0, det, mfma);
-  OpScratch z;
-  const size_t nw = (size_t)27 * Cin * Cout;
-  float *wpk = nullptr, *wd = nullptr, *dwp = nullptr, *dw_part = nullptr;
-  int *flag = nullptr, *inv = nullptr;
-  RET_IF(z.get(nw, false, s, (void**)&wpk));
-  if (mfma) RET_IF(z.get(nw, false, s, (void**)&wd));
-  RET_IF(z.get(q.dwp, poison != 0, s, (void**)&dwp));
-  RET_IF(z.get(q.dw_part, poison != 0, s, (void**)&dw_part));
-  if (q.flag) RET_IF(z.get(q.flag, poison != 0, s, (void**)&flag));
-  if (q.inv) RET_IF(z.get(q.inv, poison != 0, s, (void**)&inv));
-  int rc = launch_sparse_w_pack(w, Cin, Cout, layout, wpk, s);  // the packs of build_sparse_layer (engine_weights.hip)
-  if (!rc && mfma) rc = launch_sparse_w_frag(wpk, Cout, Cin, 1, strided ? 0 : 1, wd, s);
-  if (!rc)
-    rc = cbwd_sparse_layer(in, nbr, d_out, n_in, n_out, Cin, Cout, strided != 0, lvl0, det, wpk, wd, layout, dwp, dw_part, flag, inv, d_in,
-                           gw, s);
-  return op_sync("mvd_op_sparse_conv_bwd", s, rc);
 }
 
 int mvd_train_cond_backward(mvd_ctx* c, int cond_index, const float* x, const float* context, const float* d_out, int B, int H,
@@ -1665,324 +1519,6 @@ int mvd_train_sync_gradients(mvd_ctx* c, int phase, void* comm_stream, void* str
   return launch_scale_copy(c->arena_g, c->arena_n, 1.0f / (float)c->comm_world, c->arena_g, ms);
 }
 
-// ------------------------------------------------------------------------------------------ test hooks
-int mvd_op_conv(mvd_ctx* c, const float* x_nchw, int B, int Cin, int H, int W, const float* w, const float* bias, int Cout,
-                int ksize, int stride, int upsample, const float* resid_nchw, float* out_nchw, int force_splitk,
-                void* stream) {
-  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  const int cpad = (Cin + 7) / 8 * 8, taps = ksize * ksize;
-  const int Hv = H << upsample, Wv = W << upsample;
-  const int Ho = (Hv - 1) / stride + 1, Wo = (Wv - 1) / stride + 1;
-  float* xn = ws_alloc<float>(c, (size_t)B * H * W * cpad);
-  half_t* wp = ws_alloc<half_t>(c, (size_t)taps * Cout * cpad);
-  float* on = ws_alloc<float>(c, (size_t)B * Ho * Wo * Cout);
-  float* rn = resid_nchw ? ws_alloc<float>(c, (size_t)B * Ho * Wo * Cout) : nullptr;
-  WS_CHECK(xn && wp && on);
-  RET_IF(launch_nchw_to_nhwc(x_nchw, B, Cin, H * W, xn, cpad, cpad, s));
-  RET_IF(launch_pack_weight(w, Cout, cpad, taps, 0, 0, wp, s, Cin));
-  if (rn) RET_IF(launch_nchw_to_nhwc(resid_nchw, B, Cout, Ho * Wo, rn, Cout, Cout, s));
-  if (force_splitk == -3) {  // the UNet's last layer at inference: exact fp32 on the vector ALU (launch_out_conv_f32)
-    if (taps != 9 || stride != 1 || upsample || rn || cpad != Cin) return mvd_fail("op_conv: the fp32 output-head form is 3x3, stride 1, no residual");
-    RET_IF(launch_out_conv_f32(xn, Cin, w, bias, Cout, B, H, W, on, Cout, s));
-    RET_IF(launch_nhwc_to_nchw(on, Cout, B, Cout, Ho * Wo, out_nchw, s));
-    return 0;
-  }
-  if (force_splitk == -2) {  // the UNet's first layer at inference: exact fp32 on the vector ALU (launch_conv_in_f32)
-    if (taps != 9 || stride != 1 || upsample || rn) return mvd_fail("op_conv: the fp32 first-layer form is 3x3, stride 1, no residual");
-    RET_IF(launch_conv_in_f32(xn, cpad, w, Cin, bias, Cout, B, H, W, on, Cout, s));
-    RET_IF(launch_nhwc_to_nchw(on, Cout, B, Cout, Ho * Wo, out_nchw, s));
-    return 0;
-  }
-  ConvW cw;
-  cw.w = wp; cw.bias = const_cast<float*>(bias); cw.N = Cout; cw.Cin = cpad; cw.taps = taps;
-  GemmArgs g;
-  g.a = xn; g.a_f32 = 1; g.lda = cpad; g.w = &cw; g.out = on; g.ldc = Cout; g.resid = rn; g.ldr = Cout;
-  g.use_bias = bias != nullptr; g.force_splitk = force_splitk;
-  if (cpad % 64 == 0) {  // exercise the fp16-source paths (incl. the LDS-halo 3x3 kernels) the UNet uses
-    half_t* xh = ws_alloc<half_t>(c, (size_t)B * H * W * cpad);
-    WS_CHECK(xh);
-    RET_IF(launch_f32_to_f16(xn, xh, (size_t)B * H * W * cpad, s));
-    g.a = xh;
-    g.a_f32 = 0;
-    const int bnx = Cout % 160 == 0 ? 160 : (Cout % 128 == 0 ? 128 : 0);
-    if (taps == 9 && bnx && mvd_env_call::conv3x()) {  // ... and the conv3x form of the weights (k_conv3x.hip), as build_conv3x_streams does
-      cw.wx = ws_alloc<half_t>(c, conv3x_stream_halfs(Cout, cpad, bnx));
-      WS_CHECK(cw.wx);
-      RET_IF(conv3x_pack(wp, Cout, cpad, bnx, cw.wx, s));
-      cw.wx_bn = bnx;
-    }
-  }
-  if (upsample && taps == 9 && stride == 1 && cpad == Cin && B * H * W >= 2048) {
-    // the UNet's path for large upsample convs: four parity-folded 2x2 convs (fp32 source, as in the decoder)
-    cw.w_up = ws_alloc<half_t>(c, (size_t)16 * Cout * Cin);
-    WS_CHECK(cw.w_up);
-    RET_IF(launch_pack_upconv_weight(w, Cout, Cin, cw.w_up, s));
-    g.a = xn; g.a_f32 = 1;
-    RET_IF(run_upconv2d(c, g, B, H, W, s));
-  } else {
-    RET_IF(run_conv2d(c, g, B, H, W, stride, upsample, s));
-  }
-  RET_IF(launch_nhwc_to_nchw(on, Cout, B, Cout, Ho * Wo, out_nchw, s));
-  return 0;
-}
-
-int mvd_op_conv3d(mvd_ctx* c, const float* x, int B, int Cin, int D, int H, int W, const float* w, const float* bias,
-                  int Cout, int stride, int transposed, const float* resid, float* out, void* stream) {
-  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  if (Cin % 8) return mvd_fail("op_conv3d: Cin must be a multiple of 8");
-  const int Do = transposed ? 2 * D : (D - 1) / stride + 1, Ho = transposed ? 2 * H : (H - 1) / stride + 1,
-            Wo = transposed ? 2 * W : (W - 1) / stride + 1;
-  float* xn = ws_alloc<float>(c, (size_t)B * D * H * W * Cin);
-  half_t* wp = ws_alloc<half_t>(c, (size_t)27 * Cout * Cin);
-  float* on = ws_alloc<float>(c, (size_t)B * Do * Ho * Wo * Cout);
-  WS_CHECK(xn && wp && on);
-  RET_IF(launch_nchw_to_nhwc(x, B, Cin, D * H * W, xn, Cin, Cin, s));
-  RET_IF(launch_pack_weight(w, Cout, Cin, 27, transposed, 0, wp, s, Cin));
-  if (resid) RET_IF(launch_nchw_to_nhwc(resid, B, Cout, Do * Ho * Wo, on, Cout, Cout, s));
-  ConvW cw;
-  cw.w = wp; cw.bias = const_cast<float*>(bias); cw.N = Cout; cw.Cin = Cin; cw.taps = 27;
-  GemmArgs g;
-  g.a = xn; g.a_f32 = 1; g.lda = Cin; g.w = &cw; g.out = on; g.ldc = Cout; g.use_bias = bias != nullptr;
-  if (resid) { g.resid = on; g.ldr = Cout; }
-  if (Cin % 64 == 0) {  // fp16-source path (LDS-DMA implicit GEMM), as in the frustum network's inner layers
-    half_t* xh = ws_alloc<half_t>(c, (size_t)B * D * H * W * Cin);
-    WS_CHECK(xh);
-    RET_IF(launch_f32_to_f16(xn, xh, (size_t)B * D * H * W * Cin, s));
-    g.a = xh;
-    g.a_f32 = 0;
-  }
-  if (transposed) RET_IF(run_convT3d(c, g, B, D, H, W, s));
-  else RET_IF(run_conv3d(c, g, B, D, H, W, stride, s));
-  RET_IF(launch_nhwc_to_nchw(on, Cout, B, Cout, Do * Ho * Wo, out, s));
-  return 0;
-}
-
-int mvd_op_linear(mvd_ctx* c, const float* a, int M, int K, const float* w, const float* bias, int N, int geglu,
-                  const float* resid, int a_half, int force_splitk, float* out, void* stream) {
-  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  if (K % 8) return mvd_fail("op_linear: K must be a multiple of 8");
-  half_t* wp = ws_alloc<half_t>(c, (size_t)N * K);
-  float* bp = ws_alloc<float>(c, (size_t)N);
-  WS_CHECK(wp && bp);
-  RET_IF(launch_pack_weight(w, N, K, 1, 0, geglu, wp, s, K));
-  if (bias) {
-    if (geglu) RET_IF(launch_permute_geglu_bias(bias, N, bp, s));
-    else HIP_CHECK_RET(hipMemcpyAsync(bp, bias, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
-  }
-  ConvW cw;
-  cw.w = wp; cw.bias = bias ? bp : nullptr; cw.N = N; cw.Cin = K; cw.taps = 1;
-  GemmArgs g;
-  g.a = a; g.a_f32 = 1; g.lda = K; g.w = &cw; g.out = out; g.ldc = geglu ? N / 2 : N; g.geglu = geglu;
-  g.use_bias = bias != nullptr;
-  g.force_splitk = force_splitk;
-  if (resid) {
-    g.resid = resid; g.resid_f32 = 1; g.ldr = N;
-  }
-  if (a_half) {
-    half_t* ah = ws_alloc<half_t>(c, (size_t)M * K);
-    WS_CHECK(ah);
-    RET_IF(launch_f32_to_f16(a, ah, (size_t)M * K, s));
-    g.a = ah; g.a_f32 = 0;
-  }
-  RET_IF(run_linear(c, g, 1, M, s));
-  return 0;
-}
-
-int mvd_op_group_norm(mvd_ctx* c, const float* x_nchw, int B, int C, int HW, int groups, const float* gamma,
-                      const float* beta, float eps, int act, float* out_nchw, void* stream) {
-  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  float* xn = ws_alloc<float>(c, (size_t)B * HW * C);
-  half_t* y = ws_alloc<half_t>(c, (size_t)B * HW * C);
-  float* yf = ws_alloc<float>(c, (size_t)B * HW * C);
-  WS_CHECK(xn && y && yf);
-  RET_IF(launch_nchw_to_nhwc(x_nchw, B, C, HW, xn, C, C, s));
-  NormW n;
-  n.g = const_cast<float*>(gamma); n.b = const_cast<float*>(beta); n.C = C;
-  RET_IF(run_group_norm(c, xn, C, B, HW, n, groups, eps, act, nullptr, y, C, s));
-  hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk((size_t)B * HW * C)), dim3(256), 0, s, y, yf, (size_t)B * HW * C);
-  RET_IF(launch_nhwc_to_nchw(yf, C, B, C, HW, out_nchw, s));
-  return 0;
-}
-
-int mvd_op_layer_norm(mvd_ctx* c, const float* x, int rows, int C, const float* gamma, const float* beta, float* out,
-                      void* stream) {
-  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  half_t* y = ws_alloc<half_t>(c, (size_t)rows * C);
-  WS_CHECK(y);
-  RET_IF(launch_layernorm(x, rows, C, gamma, beta, 1e-5f, y, s));
-  hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk((size_t)rows * C)), dim3(256), 0, s, y, out, (size_t)rows * C);
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
-}
-
-int mvd_op_attention(mvd_ctx* c, const float* q, const float* k, const float* v, int B, int T, int heads, int d, float* out,
-                     void* stream) {
-  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  const int C = heads * d, rows = B * T;
-  half_t* qkv = ws_alloc<half_t>(c, (size_t)rows * 3 * C);
-  half_t* o = ws_alloc<half_t>(c, (size_t)rows * C);
-  WS_CHECK(qkv && o);
-  hipLaunchKernelGGL(pack_qkv_rows_kernel, dim3(nblk((size_t)rows * C)), dim3(256), 0, s, q, k, v, rows, C, qkv);
-  RET_IF(launch_attention(qkv, 3 * C, qkv + 2 * C, 3 * C, o, C, B, T, heads, d, s));
-  hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk((size_t)rows * C)), dim3(256), 0, s, o, out, (size_t)rows * C);
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
-}
-
-// depth_attn_kernel on the caller's data (tests/test_gpu_depth_attn.py).  Everything the launch may touch is poisoned first: the
-// context's pad columns (ldx > Cc) and one guard row behind z hold 0xFFFF halfs, NaN in fp16 and in bfloat16.
-int mvd_op_depth_attn(mvd_ctx* c, const float* qk, const float* context, const float* fill_row, int n_cond, int HW, int D, int Cc,
-                      int heads, int ldx, int split, int nfill, int check_only, float* out, float* hi_out, void* stream) {
-  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
-  if (!c) return mvd_fail("null context");
-  if (depth_attn_check(D, Cc, heads, ldx, nfill)) return -1;  // the launcher's own refusals, before anything is sized by them
-  if (check_only) return 0;
-  if (n_cond < 0 || HW <= 0 || D <= 0 || Cc <= 0 || !out || (n_cond > 0 && (!qk || !context)) || (nfill > 0 && !fill_row))
-    return mvd_fail("op_depth_attn: bad argument");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  if (ldx == 0) ldx = Cc;
-  split = split ? 1 : 0;
-  const int W4 = 4 * Cc, wz = split ? 3 : 1;
-  const size_t npix = (size_t)n_cond * HW, rows = npix + nfill, crows = npix * D;
-  half_t* cn = ws_alloc<half_t>(c, crows * ldx + 8);
-  half_t* z = ws_alloc<half_t>(c, (rows + 1) * W4 * wz);
-  half_t* fr = ws_alloc<half_t>(c, (size_t)W4 * 3);
-  WS_CHECK(cn && z && fr);
-  HIP_CHECK_RET(hipMemsetAsync(cn, 0xFF, (crows * ldx + 8) * sizeof(half_t), s));
-  HIP_CHECK_RET(hipMemsetAsync(z, 0xFF, (rows + 1) * W4 * wz * sizeof(half_t), s));
-  if (crows) hipLaunchKernelGGL(rows_f32_to_f16_ld_kernel, dim3(nblk(crows * Cc)), dim3(256), 0, s, context, crows, Cc, cn, ldx);
-  if (nfill > 0) {
-    if (split) RET_IF(launch_rows_f32_to_f16_split(fill_row, W4, 1, W4, fr, s));
-    else RET_IF(launch_f32_to_f16(fill_row, fr, W4, s));
-  }
-  RET_IF(launch_depth_attn(qk, cn, z, n_cond, HW, D, Cc, heads, s, split, nfill, nfill > 0 ? fr : nullptr, ldx));
-  const size_t n = (rows + 1) * W4;
-  if (split) {  // the guard row's three blocks are all NaN: NaN != NaN, so it comes back NaN
-    hipLaunchKernelGGL(split_rows_to_f32_kernel, dim3(nblk(n)), dim3(256), 0, s, z, (int)(rows + 1), W4, out);
-    if (hi_out) hipLaunchKernelGGL(rows_f16_ld_to_f32_kernel, dim3(nblk(n)), dim3(256), 0, s, z, rows + 1, W4, 3 * W4, hi_out);
-  } else {
-    hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk(n)), dim3(256), 0, s, z, out, n);
-  }
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
-}
-
-// backward-kernel hooks (tests/test_gpu_train_ops.py): each against torch.autograd of the same op
-int mvd_op_attention_bwd(mvd_ctx* c, const float* q, const float* k, const float* v, const float* d_out, int B, int T, int heads, int d,
-                         float* dq, float* dk, float* dv, void* stream) {
-  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
-  if (!c) return mvd_fail("null context");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  const int C = heads * d, rows = B * T;
-  half_t* qkv = ws_alloc<half_t>(c, (size_t)rows * 3 * C);
-  half_t* o = ws_alloc<half_t>(c, (size_t)rows * C);
-  half_t* do16 = ws_alloc<half_t>(c, (size_t)rows * C);
-  half_t* dqkv = ws_alloc<half_t>(c, (size_t)rows * 3 * C);
-  float* lse = ws_alloc<float>(c, (size_t)B * heads * T);
-  float* delta = ws_alloc<float>(c, (size_t)B * heads * T);
-  float* tmp = ws_alloc<float>(c, (size_t)rows * 3 * C);
-  WS_CHECK(qkv && o && do16 && dqkv && lse && delta && tmp);
-  hipLaunchKernelGGL(pack_qkv_rows_kernel, dim3(nblk((size_t)rows * C)), dim3(256), 0, s, q, k, v, rows, C, qkv);
-  RET_IF(launch_attention(qkv, 3 * C, qkv + 2 * C, 3 * C, o, C, B, T, heads, d, s));
-  RET_IF(bwd_cast_rows(d_out, C, rows, C, C, do16, s));
-  RET_IF(bwd_attention(qkv, 3 * C, o, do16, C, dqkv, 3 * C, lse, delta, B, T, heads, d, s));
-  hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk((size_t)rows * 3 * C)), dim3(256), 0, s, dqkv, tmp, (size_t)rows * 3 * C);
-  HIP_CHECK_RET(hipGetLastError());
-  float* outs[3] = {dq, dk, dv};
-  for (int i = 0; i < 3; ++i)
-    HIP_CHECK_RET(hipMemcpy2DAsync(outs[i], (size_t)C * 4, tmp + (size_t)i * C, (size_t)3 * C * 4, (size_t)C * 4, rows, hipMemcpyDeviceToDevice, s));
-  return 0;
-}
-
-// x, dy, dx: [B, rows, C] channels-last
-int mvd_op_group_norm_bwd(mvd_ctx* c, const float* x, const float* dy, int B, int rows, int C, int groups, const float* gamma,
-                          const float* beta, float eps, int act, float* dx, float* dgamma, float* dbeta, void* stream) {
-  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
-  if (!c) return mvd_fail("null context");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  // the slabbed form the training step uses; MVD_GN_BWD_ONE_BLOCK=1: the one-workgroup-per-(sample, group) kernel
-  const bool one_block = mvd_env().gn_bwd_one_block;
-  const int S = one_block ? 1 : bwd_gn_slabs(B, groups, rows);
-  float* dg = ws_alloc<float>(c, (size_t)B * S * C);
-  float* db = ws_alloc<float>(c, (size_t)B * S * C);
-  float* part = ws_alloc<float>(c, (size_t)B * groups * S * 4);
-  WS_CHECK(dg && db && part);
-  if (one_block)
-    RET_IF(bwd_group_norm(x, C, nullptr, 0, dy, C, B, rows, C, groups, gamma, beta, eps, act, dx, C, 0, dg, db, nullptr, s));
-  else
-    RET_IF(bwd_group_norm_slab(x, C, nullptr, 0, dy, C, B, rows, C, groups, gamma, beta, eps, act, dx, C, 0, part,
-                               part + (size_t)B * groups * S * 2, dg, db, nullptr, S, s));
-  RET_IF(bwd_sum_rows_add(dg, B * S, C, C, dgamma, 0, s));
-  return bwd_sum_rows_add(db, B * S, C, C, dbeta, 0, s);
-}
-
-int mvd_op_layer_norm_bwd(mvd_ctx* c, const float* x, const float* dy, int rows, int C, const float* gamma, float* dx, float* dgamma,
-                          float* dbeta, void* stream) {
-  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
-  if (!c) return mvd_fail("null context");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  float* part = ws_alloc<float>(c, (size_t)bwd_ln_max_blocks() * 2 * C);
-  WS_CHECK(part);
-  int nb = 0;
-  RET_IF(bwd_layer_norm(x, C, dy, C, rows, C, gamma, 1e-5f, dx, C, 0, part, &nb, s));
-  RET_IF(bwd_sum_rows_add(part, nb, C, 2 * C, dgamma, 0, s));
-  return bwd_sum_rows_add(part + C, nb, C, 2 * C, dbeta, 0, s);
-}
-
-int mvd_bench_conv(mvd_ctx* c, int B, int C, int H, int W, int Cout, int iters, float* ms_out, void* stream) {
-  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  const size_t na = (size_t)B * H * W * C, nw = (size_t)9 * Cout * C;
-  half_t* a = ws_alloc<half_t>(c, na);
-  half_t* w = ws_alloc<half_t>(c, nw);
-  float* o = ws_alloc<float>(c, (size_t)B * H * W * Cout);
-  WS_CHECK(a && w && o);
-  hipLaunchKernelGGL(fill_pattern_f16_kernel, dim3(nblk(na)), dim3(256), 0, s, a, na, 17u);
-  hipLaunchKernelGGL(fill_pattern_f16_kernel, dim3(nblk(nw)), dim3(256), 0, s, w, nw, 91u);
-  ConvW cw;
-  cw.w = w; cw.N = Cout; cw.Cin = C; cw.taps = 9;
-  const int bnx = Cout % 160 == 0 ? 160 : (Cout % 128 == 0 ? 128 : 0);
-  if (C % 64 == 0 && bnx && mvd_env_call::conv3x()) {
-    cw.wx = ws_alloc<half_t>(c, conv3x_stream_halfs(Cout, C, bnx));
-    WS_CHECK(cw.wx);
-    RET_IF(conv3x_pack(w, Cout, C, bnx, cw.wx, s));
-    cw.wx_bn = bnx;
-  }
-  GemmArgs g;
-  g.a = a; g.lda = C; g.w = &cw; g.out = o; g.ldc = Cout; g.use_bias = false;
-  RET_IF(run_conv2d(c, g, B, H, W, 1, 0, s));  // warm-up
-  hipEvent_t e0, e1;
-  HIP_CHECK_RET(hipEventCreate(&e0));
-  HIP_CHECK_RET(hipEventCreate(&e1));
-  HIP_CHECK_RET(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i) RET_IF(run_conv2d(c, g, B, H, W, 1, 0, s));
-  HIP_CHECK_RET(hipEventRecord(e1, s));
-  HIP_CHECK_RET(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIP_CHECK_RET(hipEventElapsedTime(&ms, e0, e1));
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  *ms_out = ms / (float)iters;
-  return 0;
-}
-
 int mvd_vae_decode(mvd_ctx* c, const float* z, int B, int h, int w, float* out, void* stream) {
   if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
   if (!c || !c->finalized) return mvd_fail("weights not finalized");
@@ -2078,599 +1614,6 @@ int mvd_probe_report(mvd_ctx* c, char* buf, size_t cap) {
   if (out.size() + 1 > cap) return mvd_fail("mvd_probe_report: buffer too small");
   memcpy(buf, out.c_str(), out.size() + 1);
   return 0;
-}
-
-int mvd_bench_linear(mvd_ctx* c, int M, int K, int N, int flags, int iters, float* ms_out, void* stream) {
-  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  const size_t na = (size_t)M * K, nw = (size_t)N * K, no = (size_t)M * N;
-  const bool cold = flags & 32;  // evict the operands (L2 + memory-side cache) before every timed launch
-  const size_t flush_bytes = cold ? (size_t)768 << 20 : 0;
-  half_t* a = ws_alloc<half_t>(c, na);
-  half_t* w = ws_alloc<half_t>(c, nw);
-  float* o = ws_alloc<float>(c, no);
-  float* r = ws_alloc<float>(c, no);
-  float* bias = ws_alloc<float>(c, (size_t)N + 64 * (size_t)N);
-  char* flush = cold ? ws_alloc<char>(c, flush_bytes) : nullptr;
-  float* a32 = (flags & 64) ? ws_alloc<float>(c, na) : nullptr;  // fp32 activations (converted while staged)
-  WS_CHECK(a && w && o && r && bias && (!cold || flush) && (!(flags & 64) || a32));
-  hipLaunchKernelGGL(fill_pattern_f16_kernel, dim3(nblk(na)), dim3(256), 0, s, a, na, 17u);
-  if (a32) hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk(na)), dim3(256), 0, s, a, a32, na);
-  hipLaunchKernelGGL(fill_pattern_f16_kernel, dim3(nblk(nw)), dim3(256), 0, s, w, nw, 91u);
-  HIP_CHECK_RET(hipMemsetAsync(r, 0, no * sizeof(float), s));
-  HIP_CHECK_RET(hipMemsetAsync(bias, 0, ((size_t)N + 64 * (size_t)N) * sizeof(float), s));
-  ConvW cw;
-  cw.w = w; cw.N = N; cw.Cin = K; cw.taps = 1; cw.bias = bias;
-  GemmArgs g;
-  g.a = a; g.lda = K; g.w = &cw; g.out = o; g.use_bias = (flags & 8) != 0;
-  if (a32) { g.a = a32; g.a_f32 = 1; }
-  g.geglu = (flags & 4) ? 1 : 0;
-  g.ldc = g.geglu ? N / 2 : N;
-  g.out_f32 = (flags & 2) ? 0 : 1;
-  if (flags & 1) { g.resid = r; g.resid_f32 = 1; g.ldr = N; }
-  const int nb = M % 32 == 0 ? 32 : 1;  // samples (per-sample bias rows)
-  if (flags & 16) { g.rowbias = bias + N; g.rb_ld = N; }
-  RET_IF(run_linear(c, g, nb, M, s));  // warm-up
-  hipEvent_t e0, e1;
-  HIP_CHECK_RET(hipEventCreate(&e0));
-  HIP_CHECK_RET(hipEventCreate(&e1));
-  float total = 0.f;
-  if (cold) {
-    for (int i = 0; i < iters; ++i) {
-      HIP_CHECK_RET(hipMemsetAsync(flush, i & 0xFF, flush_bytes, s));
-      HIP_CHECK_RET(hipEventRecord(e0, s));
-      RET_IF(run_linear(c, g, nb, M, s));
-      HIP_CHECK_RET(hipEventRecord(e1, s));
-      HIP_CHECK_RET(hipEventSynchronize(e1));
-      float ms = 0.f;
-      HIP_CHECK_RET(hipEventElapsedTime(&ms, e0, e1));
-      total += ms;
-    }
-  } else {
-    HIP_CHECK_RET(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) RET_IF(run_linear(c, g, nb, M, s));
-    HIP_CHECK_RET(hipEventRecord(e1, s));
-    HIP_CHECK_RET(hipEventSynchronize(e1));
-    HIP_CHECK_RET(hipEventElapsedTime(&total, e0, e1));
-  }
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  *ms_out = total / (float)iters;
-  return 0;
-}
-
-int mvd_bench_group_norm(mvd_ctx* c, int B, int C, int HW, int groups, int flags, int iters, float* ms_out, void* stream) {
-  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  const size_t n = (size_t)B * HW * C;
-  const int split = flags & 1, wo = split ? 3 : 1;
-  float* x = ws_alloc<float>(c, n);
-  half_t* tmp = ws_alloc<half_t>(c, n);
-  half_t* y = ws_alloc<half_t>(c, n * wo);
-  float* gb = ws_alloc<float>(c, (size_t)2 * C);
-  WS_CHECK(x && tmp && y && gb);
-  hipLaunchKernelGGL(fill_pattern_f16_kernel, dim3(nblk(n)), dim3(256), 0, s, tmp, n, 29u);
-  hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk(n)), dim3(256), 0, s, tmp, x, n);
-  hipLaunchKernelGGL(fill_pattern_f16_kernel, dim3(nblk((size_t)2 * C)), dim3(256), 0, s, tmp, (size_t)2 * C, 5u);
-  hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk((size_t)2 * C)), dim3(256), 0, s, tmp, gb, (size_t)2 * C);
-  NormW nw;
-  nw.g = gb; nw.b = gb + C; nw.C = C;
-  RET_IF(run_group_norm(c, x, C, B, HW, nw, groups, 1e-5f, ACT_SILU, nullptr, y, C * wo, s, 0, split));  // warm-up
-  // flags & 2: the APPLY pass alone (statistics given): what a GroupNorm costs once its statistics come out of the producer's epilogue
-  float* partial = nullptr;
-  int nslabs = 0;
-  if (flags & 2) {
-    partial = ws_alloc<float>(c, (size_t)B * gn_max_slabs() * groups * 2);
-    WS_CHECK(partial);
-    RET_IF(launch_gn_stats(x, C, B, HW, C, groups, nullptr, 0, partial, &nslabs, s));
-  }
-  hipEvent_t e0, e1;
-  HIP_CHECK_RET(hipEventCreate(&e0));
-  HIP_CHECK_RET(hipEventCreate(&e1));
-  HIP_CHECK_RET(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i) {
-    if (flags & 2) RET_IF(launch_gn_apply(x, C, B, HW, C, groups, nullptr, 0, partial, nslabs, nw.g, nw.b, 1e-5f, ACT_SILU, y, C * wo, s, split));
-    else RET_IF(run_group_norm(c, x, C, B, HW, nw, groups, 1e-5f, ACT_SILU, nullptr, y, C * wo, s, 0, split));
-  }
-  HIP_CHECK_RET(hipEventRecord(e1, s));
-  HIP_CHECK_RET(hipEventSynchronize(e1));
-  float ms = 0.f;
-  HIP_CHECK_RET(hipEventElapsedTime(&ms, e0, e1));
-  hipEventDestroy(e0);
-  hipEventDestroy(e1);
-  *ms_out = ms / (float)iters;
-  return 0;
-}
-
-// The row-chain kernel (k_rowchain.hip) on fp32 operands in the reference's layouts: packs the weight stream, runs the kernel
-// once (iters > 0: `iters` more times between two events -> *ms_out = mean milliseconds) and returns the result in fp32.
-int mvd_op_st_tail(mvd_ctx* c, int C, int rows, int T, const float* ao, const float* xin, const float* rowbias, const float* w_ao,
-                   const float* b_ao, const float* ln_g, const float* ln_b, const float* w1, const float* b1, const float* w2,
-                   const float* b2, const float* w_po, const float* b_po, const float* resid, float* out, int flags, int iters,
-                   float* ms_out, void* stream) {
-  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
-  if (!c) return mvd_fail("null context");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  const int has_ao = flags & 1, has_po = (flags & 2) ? ((flags & 8) ? 2 : 1) : 0, split = (flags & 4) && !has_po;
-  if (!rowchain_takes(C, rows, T)) return mvd_fail("op_st_tail: shape not supported by the row-chain kernel");
-  const size_t n = (size_t)rows * C;
-  half_t* stream_w = ws_alloc<half_t>(c, rowchain_stream_halfs(C, has_ao, has_po));
-  float* tmp = ws_alloc<float>(c, (size_t)8 * C);
-  half_t* aoh = has_ao ? ws_alloc<half_t>(c, n) : nullptr;
-  half_t* oh = has_po ? nullptr : ws_alloc<half_t>(c, n * (split ? 3 : 1));
-  WS_CHECK(stream_w && tmp && (!has_ao || aoh) && (has_po || oh));
-  RcWeights w;
-  w.w_ao = w_ao; w.ln_g = ln_g; w.ln_b = ln_b; w.w1 = w1; w.b1 = b1; w.w2 = w2; w.b2 = b2; w.w_po = w_po;
-  RET_IF(rowchain_pack(w, C, has_ao, has_po, tmp, stream_w, s));
-  if (has_ao) RET_IF(launch_f32_to_f16(ao, aoh, n, s));
-  RowChain p;
-  memset(&p, 0, sizeof p);
-  p.stream = stream_w; p.rows = rows; p.T = T;
-  p.ao = aoh; p.ld_ao = C; p.xin = xin; p.ld_x = C; p.b_ao = b_ao; p.rowbias = rowbias; p.rb_ld = C;
-  p.b_po = b_po; p.resid = resid; p.ld_r = C;
-  p.out = has_po ? (void*)out : (void*)oh; p.ld_o = has_po ? C : (split ? 3 * C : C); p.out_split = split ? C : 0;
-  RET_IF(launch_rowchain(p, C, has_ao, has_po, s));
-  if (iters > 0) {
-    hipEvent_t e0, e1;
-    HIP_CHECK_RET(hipEventCreate(&e0));
-    HIP_CHECK_RET(hipEventCreate(&e1));
-    HIP_CHECK_RET(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) RET_IF(launch_rowchain(p, C, has_ao, has_po, s));
-    HIP_CHECK_RET(hipEventRecord(e1, s));
-    HIP_CHECK_RET(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_CHECK_RET(hipEventElapsedTime(&ms, e0, e1));
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    if (ms_out) *ms_out = ms / (float)iters;
-  }
-  if (!has_po) {
-    if (split) {  // [hi | lo | hi] rows -> hi + lo (NaN where the third block differs from the first)
-      hipLaunchKernelGGL(split_rows_to_f32_kernel, dim3(nblk(n)), dim3(256), 0, s, oh, rows, C, out);
-    } else {
-      hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk(n)), dim3(256), 0, s, oh, out, n);
-    }
-  }
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
-}
-
-// The row-head kernel (k_rowchain.hip: proj_in -> t0, LayerNorm1, q | k | v) on fp32 operands in the reference's layouts, C = 320.
-int mvd_op_st_head(mvd_ctx* c, int rows, int xp, const float* n0, const float* w_pi, const float* b_pi, const float* ln_g, const float* ln_b,
-                   const float* w_q, const float* w_k, const float* w_v, float* t0_out, float* qkv_out, int iters, float* ms_out,
-                   void* stream) {
-  if (c && hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
-  if (!c) return mvd_fail("null context");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  const int C = RH_C;
-  const size_t n = (size_t)rows * C;
-  half_t* stream_w = ws_alloc<half_t>(c, rowhead_stream_halfs(xp));
-  float* tmp = ws_alloc<float>(c, (size_t)3 * C);
-  half_t* n0h = ws_alloc<half_t>(c, n * (xp ? 3 : 1));
-  half_t* qkvh = ws_alloc<half_t>(c, 3 * n);
-  WS_CHECK(stream_w && tmp && n0h && qkvh);
-  RhWeights w;
-  w.w_pi = w_pi; w.ln_g = ln_g; w.ln_b = ln_b; w.w_q = w_q; w.w_k = w_k; w.w_v = w_v;
-  RET_IF(rowhead_pack(w, xp, tmp, stream_w, s));
-  if (xp) RET_IF(launch_rows_f32_to_f16_split(n0, C, rows, C, n0h, s));  // [hi | lo | hi] rows, as the GroupNorm's split mode writes
-  else RET_IF(launch_f32_to_f16(n0, n0h, n, s));
-  RowHead p;
-  p.stream = stream_w; p.rows = rows; p.n0 = n0h; p.ld_n0 = xp ? 3 * C : C; p.b_pi = b_pi; p.t0 = t0_out; p.ld_t0 = C; p.qkv = qkvh; p.ld_qkv = 3 * C;
-  RET_IF(launch_rowhead(p, xp, s));
-  if (iters > 0) {
-    hipEvent_t e0, e1;
-    HIP_CHECK_RET(hipEventCreate(&e0));
-    HIP_CHECK_RET(hipEventCreate(&e1));
-    HIP_CHECK_RET(hipEventRecord(e0, s));
-    for (int i = 0; i < iters; ++i) RET_IF(launch_rowhead(p, xp, s));
-    HIP_CHECK_RET(hipEventRecord(e1, s));
-    HIP_CHECK_RET(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIP_CHECK_RET(hipEventElapsedTime(&ms, e0, e1));
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    if (ms_out) *ms_out = ms / (float)iters;
-  }
-  hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk(3 * n)), dim3(256), 0, s, qkvh, qkv_out, 3 * n);
-  HIP_CHECK_RET(hipGetLastError());
-  return 0;
-}
-
-// ---------------------------------------------------------------------------------------------- forward-form hooks
-// tests/test_gpu_epilogue_forms.py: the forward kernels in the forms the inference path and the first-stage model launch them in
-// (every GemmArgs field, extended precision, deferred split-K and its consumers, the folded GroupNorm, the row softmax).
-// Operands are fp32 in the reference's layouts (activations channels-last); the production launch writes straight into the
-// caller's result buffers, which the caller presets to 0xFF bytes with a guard row (and pad columns) behind what may be written.
-// Arguments are checked before anything is allocated or launched; poison != 0 fills the free workspace (everything the launch
-// allocates for itself: split-K slabs, operand copies) with 0xFF bytes once the operands are staged; the stream is synchronised.
-namespace {
-int ex_begin(mvd_ctx* c) {
-  if (!c) return mvd_fail("null context");
-  if (hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
-  return 0;
-}
-int ex_poison(mvd_ctx* c, hipStream_t s) {
-  const size_t o = (c->ws.off + 255) & ~(size_t)255;
-  if (o < c->ws.size) HIP_CHECK_RET(hipMemsetAsync(c->ws.base + o, 0xFF, c->ws.size - o, s));
-  return 0;
-}
-// the epilogue fields shared by mvd_op_linear_ex and mvd_op_conv_ex
-struct ExEpi {
-  const float *bias, *rowbias, *resid;
-  int rb_ld, act, use_bias, out_f16, out_split, ldc, resid_f16, ldr, force_splitk;
-  float alpha;
-  float* slabs;
-  size_t slabs_cap;
-  int defer_epilogue;
-  int* sk_used;
-  void* out;
-};
-// rb_unaligned_ok: per-sample rows of any stride (a plain GEMM then runs on the gather kernel with its element-wise epilogue)
-int ex_epi_check(const char* who, const ExEpi& e, int N, bool rb_unaligned_ok = false) {
-  const std::string w(who);
-  if (!e.out) return mvd_fail((w + ": null result").c_str());
-  if (N <= 0 || (N & 3)) return mvd_fail((w + ": N must be a positive multiple of 4").c_str());
-  if (e.act != ACT_NONE && e.act != ACT_SILU) return mvd_fail((w + ": act is 0 (none) or 1 (SiLU)").c_str());
-  if (!(e.alpha == e.alpha) || e.alpha - e.alpha != 0.0f) return mvd_fail((w + ": alpha must be finite").c_str());
-  if (e.use_bias && !e.bias) return mvd_fail((w + ": use_bias without a bias").c_str());
-  if (e.rowbias && (e.rb_ld < N || (!rb_unaligned_ok && (e.rb_ld & 3)))) return mvd_fail((w + ": rb_ld must be a multiple of 4, >= N").c_str());
-  if (e.resid && (e.ldr < N || (e.ldr & 3))) return mvd_fail((w + ": ldr must be a multiple of 4, >= N").c_str());
-  if (e.out_split && !e.out_f16) return mvd_fail((w + ": out_split is a form of the fp16 result").c_str());
-  if ((e.ldc & 3) || e.ldc < (e.out_split ? 3 : 1) * N) return mvd_fail((w + ": ldc must be a multiple of 4, >= N (3 N with out_split)").c_str());
-  if (e.force_splitk < 0) return mvd_fail((w + ": force_splitk >= 0").c_str());
-  if (e.slabs && !e.sk_used) return mvd_fail((w + ": a slab buffer needs sk_used").c_str());
-  if (e.slabs && ((uintptr_t)e.slabs & 15)) return mvd_fail((w + ": the slab buffer must be 16-byte aligned").c_str());
-  if ((uintptr_t)e.out & 15) return mvd_fail((w + ": the result must be 16-byte aligned").c_str());
-  return 0;
-}
-// fills the GemmArgs from the checked fields; an fp16 residual is staged from the caller's fp32 rows
-int ex_epi_fill(mvd_ctx* c, const ExEpi& e, size_t out_rows, int N, GemmArgs& g, hipStream_t s) {
-  g.out = e.out; g.out_f32 = e.out_f16 ? 0 : 1; g.ldc = e.ldc; g.out_split = e.out_split ? N : 0;
-  g.rowbias = e.rowbias; g.rb_ld = e.rb_ld; g.alpha = e.alpha; g.act = e.act; g.use_bias = e.use_bias != 0;
-  g.force_splitk = e.force_splitk;
-  if (e.resid) {
-    g.resid = e.resid; g.resid_f32 = 1; g.ldr = e.ldr;
-    if (e.resid_f16) {
-      half_t* rh = ws_alloc<half_t>(c, out_rows * e.ldr);
-      WS_CHECK(rh);
-      RET_IF(launch_f32_to_f16(e.resid, rh, out_rows * e.ldr, s));
-      g.resid = rh; g.resid_f32 = 0;
-    }
-  }
-  if (e.slabs) {
-    g.slabs = e.slabs; g.slabs_cap = e.slabs_cap; g.sk_used = e.sk_used; g.defer_epilogue = e.defer_epilogue != 0;
-  }
-  return 0;
-}
-}  // namespace
-
-int mvd_op_linear_ex(mvd_ctx* c, const float* a, int B, int rows, int K, const float* w, const float* bias, int N, const float* rowbias,
-                     int rb_ld, float alpha, int act, int use_bias, int out_f16, int out_split, int ldc, const float* resid,
-                     int resid_f16, int ldr, int a_half, int force_splitk, int xp, float* slabs, size_t slabs_cap, int defer_epilogue,
-                     int* sk_used, int poison, void* out, void* stream) {
-  RET_IF(ex_begin(c));
-  if (!a || !w) return mvd_fail("op_linear_ex: null operand");
-  if (B <= 0 || rows <= 0 || rows % B || K <= 0 || (K & 7)) return mvd_fail("op_linear_ex: rows % B == 0 and K % 8 == 0 expected");
-  const ExEpi e{bias, rowbias, resid, rb_ld, act, use_bias, out_f16, out_split, ldc, resid_f16, ldr, force_splitk, alpha,
-                slabs, slabs_cap, defer_epilogue, sk_used, out};
-  RET_IF(ex_epi_check("op_linear_ex", e, N, true));
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  const int Kp = xp ? 3 * K : K;
-  half_t* wp = ws_alloc<half_t>(c, (size_t)N * Kp);
-  WS_CHECK(wp);
-  RET_IF(launch_pack_weight(w, N, Kp, 1, 0, 0, wp, s, K, xp ? 1 : 0));  // xp: [w_hi | w_hi | w_lo], as pack_conv does
-  ConvW cw;
-  cw.w = wp; cw.bias = const_cast<float*>(bias); cw.N = N; cw.Cin = Kp; cw.taps = 1; cw.xp = xp ? 1 : 0; cw.cin_l = K;
-  GemmArgs g;
-  g.a = a; g.a_f32 = 1; g.lda = K; g.w = &cw;
-  if (xp || a_half) {
-    half_t* ah = ws_alloc<half_t>(c, (size_t)rows * Kp);
-    WS_CHECK(ah);
-    if (xp) RET_IF(launch_rows_f32_to_f16_split(a, K, rows, K, ah, s));  // [a_hi | a_lo | a_hi]
-    else RET_IF(launch_f32_to_f16(a, ah, (size_t)rows * K, s));
-    g.a = ah; g.a_f32 = 0; g.lda = Kp;
-  }
-  RET_IF(ex_epi_fill(c, e, (size_t)rows, N, g, s));
-  if (sk_used) *sk_used = 1;
-  if (poison) RET_IF(ex_poison(c, s));
-  return op_sync("op_linear_ex", s, run_linear(c, g, B, rows, s));
-}
-
-// x / resid / out channels-last ([B][H][W][Cin], [B][Ho][Wo][ldr], [B*Ho*Wo + 1][ldc]); w [Cout][Cin][k][k].  tap_shift = 1 is the
-// first-stage encoder's Downsample (zero padding on the right and bottom only): 3x3, stride 2, EVEN H and W only -- the encoder
-// never runs it otherwise, and for an odd side the output grid of F.pad(x, (0, 1, 0, 1)) + conv(k3, s2, p0) is not run_conv2d's.
-// upsample: the fused nearest x2 (run_conv2d), or with up_fold != 0 the four parity-folded 2x2 convolutions (run_upconv2d).
-int mvd_op_conv_ex(mvd_ctx* c, const float* x, int B, int H, int W, int Cin, const float* w, const float* bias, int Cout, int ksize,
-                   int stride, int upsample, int up_fold, int tap_shift, const float* rowbias, int rb_ld, float alpha, int act,
-                   int use_bias, int out_f16, int out_split, int ldc, const float* resid, int resid_f16, int ldr, int a_half,
-                   int force_splitk, int xp, int conv3x_stream, float* slabs, size_t slabs_cap, int defer_epilogue, int* sk_used,
-                   int poison, void* out, void* stream) {
-  RET_IF(ex_begin(c));
-  if (!x || !w) return mvd_fail("op_conv_ex: null operand");
-  if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || (Cin & 7)) return mvd_fail("op_conv_ex: Cin % 8 == 0 expected");
-  if ((ksize != 1 && ksize != 3) || (stride != 1 && stride != 2) || (upsample != 0 && upsample != 1))
-    return mvd_fail("op_conv_ex: 1x1 or 3x3, stride 1 or 2, upsample 0 or 1");
-  if (tap_shift != 0 && (tap_shift != 1 || ksize != 3 || stride != 2 || upsample || (H & 1) || (W & 1)))
-    return mvd_fail("op_conv_ex: tap_shift = 1 is the 3x3 stride-2 Downsample of even H and W");
-  if (up_fold && (!upsample || ksize != 3 || stride != 1 || xp || slabs))
-    return mvd_fail("op_conv_ex: the parity-folded form is a 3x3 stride-1 upsample conv without xp or a slab buffer");
-  const ExEpi e{bias, rowbias, resid, rb_ld, act, use_bias, out_f16, out_split, ldc, resid_f16, ldr, force_splitk, alpha,
-                slabs, slabs_cap, defer_epilogue, sk_used, out};
-  RET_IF(ex_epi_check("op_conv_ex", e, Cout));
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  const int taps = ksize * ksize, Cp = xp ? 3 * Cin : Cin;
-  const int Ho = ((H << upsample) - 1) / stride + 1, Wo = ((W << upsample) - 1) / stride + 1;
-  const size_t rows_in = (size_t)B * H * W, rows_out = (size_t)B * Ho * Wo;
-  half_t* wp = ws_alloc<half_t>(c, (size_t)taps * Cout * Cp);
-  WS_CHECK(wp);
-  RET_IF(launch_pack_weight(w, Cout, Cp, taps, 0, 0, wp, s, Cin, xp ? 1 : 0));
-  ConvW cw;
-  cw.w = wp; cw.bias = const_cast<float*>(bias); cw.N = Cout; cw.Cin = Cp; cw.taps = taps; cw.xp = xp ? 1 : 0; cw.cin_l = Cin;
-  GemmArgs g;
-  g.a = x; g.a_f32 = 1; g.lda = Cin; g.w = &cw; g.tap_shift = tap_shift;
-  if (xp || a_half) {
-    half_t* xh = ws_alloc<half_t>(c, rows_in * Cp);
-    WS_CHECK(xh);
-    if (xp) RET_IF(launch_rows_f32_to_f16_split(x, Cin, (long)rows_in, Cin, xh, s));
-    else RET_IF(launch_f32_to_f16(x, xh, rows_in * Cin, s));
-    g.a = xh; g.a_f32 = 0; g.lda = Cp;
-  }
-  const int bnx = Cout % 160 == 0 ? 160 : (Cout % 128 == 0 ? 128 : 0);
-  if (conv3x_stream && taps == 9 && bnx && Cp % 64 == 0 && !g.a_f32) {  // the weights as a conv3x fragment stream too (k_conv3x.hip)
-    cw.wx = ws_alloc<half_t>(c, conv3x_stream_halfs(Cout, Cp, bnx));
-    WS_CHECK(cw.wx);
-    RET_IF(conv3x_pack(wp, Cout, Cp, bnx, cw.wx, s));
-    cw.wx_bn = bnx;
-  }
-  if (up_fold) {
-    cw.w_up = ws_alloc<half_t>(c, (size_t)16 * Cout * Cin);
-    WS_CHECK(cw.w_up);
-    RET_IF(launch_pack_upconv_weight(w, Cout, Cin, cw.w_up, s));
-  }
-  RET_IF(ex_epi_fill(c, e, rows_out, Cout, g, s));
-  if (sk_used) *sk_used = 1;
-  if (poison) RET_IF(ex_poison(c, s));
-  return op_sync("op_conv_ex", s, up_fold ? run_upconv2d(c, g, B, H, W, s) : run_conv2d(c, g, B, H, W, stride, upsample, s));
-}
-
-// x: nslab slabs of channels-last [B][rows][ld] fp32, slab_stride floats apart.  form 0: run_group_norm's own choice; form 1: the
-// two-pass pair (launch_gn_stats + launch_gn_apply) called directly, which takes one slab and writes neither `mat` nor fp32.
-// out: [B * rows + 1][ldo] halfs (split = 1: [hi | lo | hi] rows; split = 2: fp32 rows of ldo / 2 floats); mat: [B * rows + 1][ldm].
-int mvd_op_group_norm_ex(mvd_ctx* c, const float* x, int B, int rows, int C, int ld, int groups, const float* gamma, const float* beta,
-                         float eps, int act, int form, const float* preadd, int pld, int split, int nslab, size_t slab_stride,
-                         const float* bias2, const float* resid, int ldr, float* mat, int ldm, int ldo, int poison, void* out,
-                         void* stream) {
-  RET_IF(ex_begin(c));
-  if (!x || !gamma || !beta || !out) return mvd_fail("op_group_norm_ex: null operand");
-  if (B <= 0 || rows <= 0 || C <= 0 || groups <= 0 || C % groups || ld < C) return mvd_fail("op_group_norm_ex: C % groups == 0 and ld >= C expected");
-  if (act < ACT_NONE || act > ACT_RELU || (form != 0 && form != 1) || split < 0 || split > 2) return mvd_fail("op_group_norm_ex: act 0..2, form 0..1, split 0..2");
-  if (ldo < (split == 1 ? 3 : (split == 2 ? 2 : 1)) * C) return mvd_fail("op_group_norm_ex: ldo >= C halfs (3 C with split = 1, 2 C with split = 2)");
-  if (nslab < 1 || (nslab > 1 && slab_stride < (size_t)B * rows * ld)) return mvd_fail("op_group_norm_ex: slabs overlap");
-  if (preadd && pld < C) return mvd_fail("op_group_norm_ex: pld >= C expected");
-  if ((resid && ldr < C) || (mat && ldm < C)) return mvd_fail("op_group_norm_ex: ldr, ldm >= C expected");
-  const bool one_pass = !mvd_env().gn_two_pass && gn_group_eligible(ld, rows, C, groups, preadd ? pld : 0, ldo);
-  if ((form == 1 || !one_pass) && (nslab > 1 || bias2 || resid || mat || split == 2))
-    return mvd_fail("op_group_norm_ex: slabs, bias2, resid, mat and the fp32 result need the single-pass form");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  NormW n;
-  n.g = const_cast<float*>(gamma); n.b = const_cast<float*>(beta); n.C = C;
-  half_t* o = (half_t*)out;
-  if (form == 0) {
-    if (poison) RET_IF(ex_poison(c, s));
-    return op_sync("op_group_norm_ex", s,
-                   run_group_norm(c, x, ld, B, rows, n, groups, eps, act, preadd, o, ldo, s, pld, split, nslab, slab_stride, bias2, resid,
-                                  ldr, mat, ldm));
-  }
-  if (C > 2560 || groups > 32 || (C & 3) || (ld & 3) || (ldo & 3) || (preadd && (pld & 3)))
-    return mvd_fail("op_group_norm_ex: the two-pass form takes C <= 2560, groups <= 32 and C, ld, ldo, pld % 4 == 0");
-  float* partial = ws_alloc<float>(c, (size_t)B * gn_max_slabs() * groups * 2);
-  WS_CHECK(partial);
-  if (poison) RET_IF(ex_poison(c, s));
-  int nsl = 0;
-  int rc = launch_gn_stats(x, ld, B, rows, C, groups, preadd, pld, partial, &nsl, s);
-  if (!rc) rc = launch_gn_apply(x, ld, B, rows, C, groups, preadd, pld, partial, nsl, gamma, beta, eps, act, o, ldo, s, split);
-  return op_sync("op_group_norm_ex", s, rc);
-}
-
-// plain == 0: launch_layernorm_slabs with every LnSlabs field (mat [rows + 1][C] is required); plain != 0: launch_layernorm on
-// one slab, where only the fp16 copy `raw` ([rows + 1][ld_raw] halfs, may be NULL) is left of them.  out: [rows + 1][C] halfs.
-int mvd_op_layer_norm_slabs(mvd_ctx* c, const float* slabs, int nslab, size_t slab_stride, int rows, int C, const float* bias,
-                            const float* rowbias, int rb_ld, int T, const float* resid, int ldr, const float* gamma, const float* beta,
-                            float eps, int plain, int ld_raw, int poison, float* mat, void* raw, void* out, void* stream) {
-  RET_IF(ex_begin(c));
-  if (!slabs || !gamma || !beta || !out) return mvd_fail("op_layer_norm_slabs: null operand");
-  if (rows <= 0 || C <= 0 || nslab < 1 || T < 1) return mvd_fail("op_layer_norm_slabs: bad argument");
-  if (raw && ld_raw < C) return mvd_fail("op_layer_norm_slabs: ld_raw >= C expected");
-  hipStream_t s = S(stream);
-  if (plain) {
-    if (nslab != 1 || bias || rowbias || resid || mat) return mvd_fail("op_layer_norm_slabs: the plain LayerNorm takes one slab and writes no mat");
-    if (poison) RET_IF(ex_poison(c, s));
-    return op_sync("op_layer_norm_slabs", s, launch_layernorm(slabs, rows, C, gamma, beta, eps, (half_t*)out, s, (half_t*)raw, ld_raw));
-  }
-  if (!mat) return mvd_fail("op_layer_norm_slabs: mat is required");
-  if (nslab > 1 && slab_stride < (size_t)rows * C) return mvd_fail("op_layer_norm_slabs: slabs overlap");
-  if ((rowbias && rb_ld < C) || (resid && ldr < C)) return mvd_fail("op_layer_norm_slabs: rb_ld, ldr >= C expected");
-  if (poison) RET_IF(ex_poison(c, s));
-  return op_sync("op_layer_norm_slabs", s,
-                 launch_layernorm_slabs(slabs, nslab, slab_stride, rows, C, bias, rowbias, rb_ld, T, resid, ldr, mat, gamma, beta, eps,
-                                        (half_t*)out, s, (half_t*)raw, ld_raw));
-}
-
-// The three steps of the folded GroupNorm(proj_context(volume)) (engine_unet.hip: ctx_fold) on caller data: x [B * rps][K], w [N][K],
-// N / cpg groups.  partials [B * rps / 256 + 1][N / cpg][2], scale and shift [B + 1][N], out [B * rps + 1][N] halfs.
-int mvd_op_folded_group_norm(mvd_ctx* c, const float* x, int B, int rps, int K, const float* w, int N, int cpg, const float* gamma,
-                             const float* beta, float eps, int poison, float* partials, float* scale, float* shift, void* out,
-                             void* stream) {
-  RET_IF(ex_begin(c));
-  if (!x || !w || !gamma || !beta || !partials || !scale || !shift || !out) return mvd_fail("op_folded_group_norm: null operand");
-  if (B <= 0 || rps <= 0 || K <= 0 || (K & 7) || N <= 0 || (N & 3)) return mvd_fail("op_folded_group_norm: K % 8 == 0 and N % 4 == 0 expected");
-  // what ctx_fold_ok asks of a context level
-  if (rps % 256 || (cpg != 8 && cpg != 16 && cpg != 32) || (long)B * rps < 512)
-    return mvd_fail("op_folded_group_norm: rps % 256 == 0, 8 / 16 / 32 channels per group and at least 512 rows expected");
-  if (N % cpg || N / cpg > 32) return mvd_fail("op_folded_group_norm: at most 32 whole groups expected");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  const int rows = B * rps, G = N / cpg, ntile = rps / 256;
-  half_t* wp = ws_alloc<half_t>(c, (size_t)N * K);
-  half_t* xh = ws_alloc<half_t>(c, (size_t)rows * K);
-  WS_CHECK(wp && xh);
-  RET_IF(launch_pack_weight(w, N, K, 1, 0, 0, wp, s, K, 0));
-  RET_IF(launch_f32_to_f16(x, xh, (size_t)rows * K, s));
-  ConvW cw;
-  cw.w = wp; cw.N = N; cw.Cin = K; cw.taps = 1;
-  if (poison) RET_IF(ex_poison(c, s));
-  GemmArgs g;
-  g.a = xh; g.lda = K; g.w = &cw; g.use_bias = false; g.gn_partial = partials; g.gn_cpg = cpg; g.force_splitk = 1;
-  int rc = run_linear(c, g, B, rows, s);
-  if (!rc) rc = launch_gn_finalize(partials, B, ntile, rps, N, G, gamma, beta, eps, scale, shift, N, s);
-  if (!rc) {
-    g = GemmArgs();
-    g.a = xh; g.lda = K; g.w = &cw; g.use_bias = false; g.out = out; g.out_f32 = 0; g.ldc = N;
-    g.rowscale = scale; g.rs_ld = N; g.rowbias = shift; g.rb_ld = N; g.act = ACT_RELU; g.force_splitk = 1;
-    rc = run_linear(c, g, B, rows, s);
-  }
-  return op_sync("op_folded_group_norm", s, rc);
-}
-
-// softmax_rows_kernel (out_f32 == 0: fp16 probabilities) / softmax_rows_f32_kernel on [rows][cols] fp32 scores; out [rows + 1][cols]
-int mvd_op_softmax_rows(mvd_ctx* c, const float* scores, int rows, int cols, int out_f32, void* out, void* stream) {
-  RET_IF(ex_begin(c));
-  if (!scores || !out || rows <= 0 || cols <= 0) return mvd_fail("op_softmax_rows: bad argument");
-  hipStream_t s = S(stream);
-  return op_sync("op_softmax_rows", s,
-                 out_f32 ? launch_softmax_rows_f32(scores, rows, cols, (float*)out, s) : launch_softmax_rows(scores, rows, cols, (half_t*)out, s));
-}
-
-// launch_rows_f32_to_f16_split: fp32 rows `lda` floats apart -> [hi | lo | hi] rows of 3 C halfs; out [rows + 1][3 C]
-int mvd_op_rows_split(mvd_ctx* c, const float* x, int lda, int rows, int C, void* out, void* stream) {
-  RET_IF(ex_begin(c));
-  if (!x || !out || rows <= 0 || C <= 0 || lda < C) return mvd_fail("op_rows_split: bad argument");
-  hipStream_t s = S(stream);
-  return op_sync("op_rows_split", s, launch_rows_f32_to_f16_split(x, lda, rows, C, (half_t*)out, s));
-}
-
-
-// tests/test_gpu_attention.py: attn_kernel and the two backward kernels on the engine's images, with everything the launches may touch
-// beside their operands and results poisoned first (0xFFFF is NaN in fp16 and in bfloat16)
-namespace {
-int attn_ex_check(const char* who, const void* q, const void* k, const void* v, int B, int T, int heads, int d) {
-  const std::string w(who);
-  if (!q || !k || !v) return mvd_fail((w + ": null operand").c_str());
-  if (B < 1 || T < 1 || heads < 1) return mvd_fail((w + ": B, T, heads >= 1 expected").c_str());
-  if (d != 8 && d != 16 && d != 32 && d != 40 && d != 64 && d != 80 && d != 160) return mvd_fail((w + ": unsupported head dim").c_str());
-  return 0;
-}
-}  // namespace
-
-int mvd_op_attention_ex(mvd_ctx* c, const float* q, const float* k, const float* v, int B, int T, int heads, int d, int Tstride,
-                        int ld_pad, int xcd, float* out, void* stream) {
-  RET_IF(ex_begin(c));
-  RET_IF(attn_ex_check("op_attention_ex", q, k, v, B, T, heads, d));
-  if (!out) return mvd_fail("op_attention_ex: null operand");
-  if (Tstride < 0 || (Tstride != 0 && Tstride < T)) return mvd_fail("op_attention_ex: Tstride >= T (or 0) expected");
-  if (ld_pad < 0 || ld_pad % 8) return mvd_fail("op_attention_ex: ld_pad must be a multiple of 8");
-  if (xcd < -1 || xcd > 1) return mvd_fail("op_attention_ex: xcd is -1, 0 or 1");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  const int C = heads * d, ld = 3 * C + ld_pad, Ts = Tstride ? Tstride : T;
-  const size_t rows = (size_t)B * Ts + 1;
-  half_t* qkv = ws_alloc<half_t>(c, rows * ld);
-  half_t* o = ws_alloc<half_t>(c, rows * C);
-  WS_CHECK(qkv && o);
-  HIP_CHECK_RET(hipMemsetAsync(qkv, 0xFF, rows * ld * sizeof(half_t), s));
-  HIP_CHECK_RET(hipMemsetAsync(o, 0xFF, rows * C * sizeof(half_t), s));
-  hipLaunchKernelGGL(pack_qkv_image_kernel, dim3(nblk((size_t)B * T * C)), dim3(256), 0, s, q, k, v, B, T, C, Ts, ld, qkv);
-  int rc = launch_attention(qkv, ld, qkv + 2 * C, ld, o, C, B, T, heads, d, s, Ts, xcd);
-  if (!rc) {
-    hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk(rows * C)), dim3(256), 0, s, o, out, rows * C);
-    if (hipGetLastError() != hipSuccess) rc = mvd_fail("op_attention_ex: launch failed");
-  }
-  return op_sync("op_attention_ex", s, rc);
-}
-
-int mvd_op_attention_bwd_ex(mvd_ctx* c, const float* q, const float* k, const float* v, const float* d_out, int B, int T, int heads,
-                            int d, float* dq, float* dk, float* dv, float* lse, float* delta, float* o_out, void* stream) {
-  RET_IF(ex_begin(c));
-  RET_IF(attn_ex_check("op_attention_bwd_ex", q, k, v, B, T, heads, d));
-  if (!d_out || !dq || !dk || !dv || !lse || !delta || !o_out) return mvd_fail("op_attention_bwd_ex: null operand");
-  hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  const int C = heads * d;
-  const size_t rows = (size_t)B * T, nstat = (size_t)B * heads * T + 1;
-  half_t* qkv = ws_alloc<half_t>(c, (rows + 1) * 3 * C);
-  half_t* o = ws_alloc<half_t>(c, (rows + 1) * C);
-  half_t* do16 = ws_alloc<half_t>(c, (rows + 1) * C);
-  half_t* dqkv = ws_alloc<half_t>(c, (rows + 1) * 3 * C);
-  float* lse_d = ws_alloc<float>(c, nstat);
-  float* delta_d = ws_alloc<float>(c, nstat);
-  float* tmp = ws_alloc<float>(c, (rows + 1) * 3 * C);
-  WS_CHECK(qkv && o && do16 && dqkv && lse_d && delta_d && tmp);
-  HIP_CHECK_RET(hipMemsetAsync(qkv, 0xFF, (rows + 1) * 3 * C * sizeof(half_t), s));
-  HIP_CHECK_RET(hipMemsetAsync(o, 0xFF, (rows + 1) * C * sizeof(half_t), s));
-  HIP_CHECK_RET(hipMemsetAsync(do16, 0xFF, (rows + 1) * C * sizeof(half_t), s));
-  HIP_CHECK_RET(hipMemsetAsync(dqkv, 0xFF, (rows + 1) * 3 * C * sizeof(half_t), s));
-  HIP_CHECK_RET(hipMemsetAsync(lse_d, 0xFF, nstat * sizeof(float), s));
-  HIP_CHECK_RET(hipMemsetAsync(delta_d, 0xFF, nstat * sizeof(float), s));
-  hipLaunchKernelGGL(pack_qkv_image_kernel, dim3(nblk(rows * C)), dim3(256), 0, s, q, k, v, B, T, C, T, 3 * C, qkv);
-  int rc = launch_attention(qkv, 3 * C, qkv + 2 * C, 3 * C, o, C, B, T, heads, d, s);
-  if (!rc) rc = bwd_cast_rows(d_out, C, (long)rows, C, C, do16, s);
-  if (!rc) rc = bwd_attention(qkv, 3 * C, o, do16, C, dqkv, 3 * C, lse_d, delta_d, B, T, heads, d, s);
-  if (!rc) {
-    hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk((rows + 1) * 3 * C)), dim3(256), 0, s, dqkv, tmp, (rows + 1) * 3 * C);
-    hipLaunchKernelGGL(f16_to_f32_kernel, dim3(nblk((rows + 1) * C)), dim3(256), 0, s, o, o_out, (rows + 1) * C);
-    if (hipGetLastError() != hipSuccess) rc = mvd_fail("op_attention_bwd_ex: launch failed");
-    float* outs[3] = {dq, dk, dv};
-    for (int i = 0; i < 3 && !rc; ++i)
-      if (hipMemcpy2DAsync(outs[i], (size_t)C * 4, tmp + (size_t)i * C, (size_t)3 * C * 4, (size_t)C * 4, rows + 1, hipMemcpyDeviceToDevice, s) != hipSuccess)
-        rc = mvd_fail("op_attention_bwd_ex: copy failed");
-    if (!rc && (hipMemcpyAsync(lse, lse_d, nstat * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-                hipMemcpyAsync(delta, delta_d, nstat * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess))
-      rc = mvd_fail("op_attention_bwd_ex: copy failed");
-  }
-  return op_sync("op_attention_bwd_ex", s, rc);
-}
-
-// the DepthTransformer's fp32 training kernels (csrc/k_train.hip) on the caller's device buffers; no context
-int mvd_op_train_depth_attn(const float* q, const float* k, const float* v, int R, int HW, int D, int hn, int hd, float* attn, float* z,
-                            void* stream) {
-  if (!q || !k || !v || !attn || !z) return mvd_fail("mvd_op_train_depth_attn: null argument");
-  if (R <= 0 || HW <= 0 || R % HW || D <= 0 || hn <= 0 || hd <= 0) return mvd_fail("mvd_op_train_depth_attn: R a positive multiple of HW, D, hn, hd >= 1 expected");
-  hipStream_t s = S(stream);
-  return op_sync("mvd_op_train_depth_attn", s, train_depth_fwd(q, k, v, R, HW, D, hn, hd, 1.0f / sqrtf((float)hd), attn, z, s));
-}
-
-int mvd_op_train_depth_attn_bwd(const float* q, const float* k, const float* v, const float* attn, const float* dz, int R, int HW, int D,
-                                int hn, int hd, float* dq, float* dk, float* dv, void* stream) {
-  if (!q || !k || !v || !attn || !dz || !dq || !dk || !dv) return mvd_fail("mvd_op_train_depth_attn_bwd: null argument");
-  if (R <= 0 || HW <= 0 || R % HW || D <= 0 || hn <= 0 || hd <= 0) return mvd_fail("mvd_op_train_depth_attn_bwd: R a positive multiple of HW, D, hn, hd >= 1 expected");
-  hipStream_t s = S(stream);
-  return op_sync("mvd_op_train_depth_attn_bwd", s,
-                 train_depth_bwd(q, k, v, attn, dz, R, HW, D, hn, hd, 1.0f / sqrtf((float)hd), dq, dk, dv, s));
-}
-
-int mvd_op_train_im2col3(const float* x, int B, int H, int W, int C, float* col, void* stream) {
-  if (!x || !col || B <= 0 || H <= 0 || W <= 0 || C <= 0) return mvd_fail("mvd_op_train_im2col3: bad argument");
-  hipStream_t s = S(stream);
-  return op_sync("mvd_op_train_im2col3", s, train_im2col3(x, B, H, W, C, col, s));
-}
-
-int mvd_op_train_col2im3(const float* dcol, int B, int H, int W, int C, float* dx, void* stream) {
-  if (!dcol || !dx || B <= 0 || H <= 0 || W <= 0 || C <= 0) return mvd_fail("mvd_op_train_col2im3: bad argument");
-  hipStream_t s = S(stream);
-  return op_sync("mvd_op_train_col2im3", s, train_col2im3(dcol, B, H, W, C, dx, s));
-}
-
-int mvd_op_train_perm_w3(const float* src, int N, int C, int to_mat, float* dst, void* stream) {
-  if (!src || !dst || N <= 0 || C <= 0) return mvd_fail("mvd_op_train_perm_w3: bad argument");
-  hipStream_t s = S(stream);
-  return op_sync("mvd_op_train_perm_w3", s, train_perm_w3(src, N, C, to_mat, dst, s));
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 #include <chrono>
 
 #include "engine.h"
+#include "hooks.h"
 
 // ---------------------------------------------------------------------------------------------------------------------
 // arenas
@@ -1551,50 +1552,15 @@ struct GradOverride {  // the override table is empty again on every exit path
   GradOverride& operator=(const GradOverride&) = delete;
 };
 
-int hook_begin(mvd_ctx* c) {
-  if (!c) return mvd_fail("null context");
-  if (hipSetDevice(c->device) != hipSuccess) return mvd_fail("hipSetDevice failed");
-  return 0;
-}
-
-// the free part of the workspace -> 0xFF bytes (NaN as fp16, bf16 and fp32): a read of anything the op did not write shows
-// in its result
-int ws_poison(mvd_ctx* c, hipStream_t s) {
-  const size_t o = (c->ws.off + 255) & ~(size_t)255;
-  if (o < c->ws.size) HIP_CHECK_RET(hipMemsetAsync(c->ws.base + o, 0xFF, c->ws.size - o, s));
-  return 0;
-}
-
-// w fp32 in the reference layout ([N][cin][taps], transposed: [cin][N][taps]) -> the forward pack (Cl = up8(cin) columns, or
-// 3 Cl with xp) and its adjoint pack [taps][Cl][Np]
+// hook_pack_fwd (hooks.h) plus the layer's adjoint pack [taps][Cl][Np] and the keys its gradients are booked under
 int hook_pack(mvd_ctx* c, const float* w, int N, int cin, int taps, int transposed, int geglu, int xp, int flip, ConvW* o, hipStream_t s) {
-  const int Cl = up8(cin);
-  o->N = N;
-  o->taps = taps;
-  o->xp = xp ? 1 : 0;
-  o->cin_l = xp ? Cl : 0;
-  o->Cin = xp ? 3 * Cl : Cl;
+  RET_IF(hook_pack_fwd(c, w, N, cin, taps, transposed, geglu, xp, o, s));
   o->Np = up8(N);
-  o->w = ws_alloc<half_t>(c, (size_t)taps * N * o->Cin);
-  o->wT = ws_alloc<half_t>(c, (size_t)taps * Cl * o->Np);
-  WS_CHECK(o->w && o->wT);
+  o->wT = ws_alloc<half_t>(c, (size_t)taps * o->cin_l * o->Np);
+  WS_CHECK(o->wT);
   o->key = kHookW;
   o->bkey = kHookB;
-  RET_IF(launch_pack_weight(w, N, o->Cin, taps, transposed, geglu, o->w, s, cin, o->xp));
-  return bwd_pack_dgrad(o->w, taps, N, o->Cin, Cl, o->Np, o->wT, s, flip);
-}
-
-// an fp32 operand the caller supplies as the fp16 image the production path reads
-int hook_f16(mvd_ctx* c, const float* src, size_t n, const half_t** out, hipStream_t s) {
-  half_t* d = ws_alloc<half_t>(c, n);
-  WS_CHECK(d);
-  RET_IF(launch_f32_to_f16(src, d, n, s));
-  *out = d;
-  return 0;
-}
-
-__global__ void hook_f16_to_f32_kernel(const half_t* in, float* out, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) out[i] = (float)in[i];
+  return bwd_pack_dgrad(o->w, taps, N, o->Cin, o->cin_l, o->Np, o->wT, s, flip);
 }
 }  // namespace
 
@@ -1618,7 +1584,7 @@ int mvd_op_conv_bwd(mvd_ctx* c, int kind, int ksize, int B, int Cin, int H, int 
   const half_t* x16 = nullptr;
   if (x_f16) RET_IF(hook_f16(c, x, (size_t)rows * cp, &x16, s));
   const void* xs = x_f16 ? (const void*)x16 : (const void*)x;
-  if (poison) RET_IF(ws_poison(c, s));
+  if (poison) RET_IF(hook_poison(c, s));
   GradOverride go(c, dw, db);
   Bwd b{c, s, B, nullptr, nullptr};
   if (whole) {
@@ -1672,7 +1638,7 @@ int mvd_op_linear_bwd(mvd_ctx* c, int B, int rows, int K, int N, const float* x,
     RET_IF(launch_permute_geglu_bias(bias, N, bp, s));
     cw.bias = bp;
   }
-  if (poison) RET_IF(ws_poison(c, s));
+  if (poison) RET_IF(hook_poison(c, s));
   GradOverride go(c, dw, db);
   Bwd b{c, s, B, nullptr, nullptr};
   if (geglu) return bwd_ff1_geglu(b, cw, x16, K, dy, rows, pre16, dpre16, dx, accum != 0, tmpW, part);
@@ -1682,7 +1648,7 @@ int mvd_op_linear_bwd(mvd_ctx* c, int B, int rows, int K, int N, const float* x,
   RET_IF(dgrad_linear(b, cw, dy16, up8(N), dx_f16 ? (void*)dx16 : (void*)dx, kp, dx_f16 ? 0 : 1, rows, accum != 0));
   RET_IF(wgrad_linear(b, cw, dy, N, xs, x_f16 ? 0 : 1, kp, rows, K, dyT));
   if (dx_f16) {
-    hipLaunchKernelGGL(hook_f16_to_f32_kernel, dim3(256), dim3(256), 0, s, dx16, dx, (size_t)rows * kp);
+    hook_f16_to_f32(dx16, dx, (size_t)rows * kp, s);
     HIP_CHECK_RET(hipGetLastError());
   }
   return 0;
@@ -1705,7 +1671,7 @@ int mvd_op_conv3d_bwd(mvd_ctx* c, int kind, int B, int Cin, int D, int H, int W,
   const half_t* x16 = nullptr;
   if (x_f16) RET_IF(hook_f16(c, x, (size_t)rows * Cin, &x16, s));
   const void* xs = x_f16 ? (const void*)x16 : (const void*)x;
-  if (poison) RET_IF(ws_poison(c, s));
+  if (poison) RET_IF(hook_poison(c, s));
   GradOverride go(c, dw, db);
   Bwd b{c, s, B, nullptr, nullptr};
   half_t* dy16;
@@ -1741,7 +1707,7 @@ int mvd_op_tgemm(mvd_ctx* c, int M, int N, int K, const float* a, int a_f16, int
     RET_IF(hook_f16(c, bm, (size_t)(b_trans ? N : K) * ldb, &h, s));
     Bm = F16(h, ldb, b_trans);
   }
-  if (poison) RET_IF(ws_poison(c, s));
+  if (poison) RET_IF(hook_poison(c, s));
   return tgemm(c, A, Bm, out, ldc, M, N, K, accum != 0, s, xp != 0);
 }
 
@@ -1847,7 +1813,7 @@ int mvd_op_frustum_gather(mvd_ctx* c, const float* vol, const int32_t* view_idx,
   WS_CHECK(gath);
   RET_IF(launch_frustum_gather(vol, c->cams, vidx, TN, D, S, c->v.spatial_volume_size, c->v.spatial_volume_length,
                                c->v.projection == 0, gath, s));
-  hipLaunchKernelGGL(hook_f16_to_f32_kernel, dim3(256), dim3(256), 0, s, gath, out, n);
+  hook_f16_to_f32(gath, out, n, s);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }

@@ -407,15 +407,28 @@ def op_bn_rows_relu_bwd(xraw, dy, stats, gamma, beta, accum=None, poison=False, 
     return d, dg, db
 
 
-def _nan_guarded(rows, width, dev):
-    """[rows + 1][width] fp32 of NaN bit patterns (0xFF bytes): a result buffer with one guard row behind it."""
-    t = torch.empty(rows + 1, width, device=dev, dtype=torch.float32)
-    t.view(torch.int32).fill_(-1)
+def _nan_guarded(rows, width, dev, dtype=torch.float32):
+    """[rows + 1][width] of 0xFF bytes (NaN in fp32 and in both 16-bit types): a result buffer with one guard row behind it."""
+    t = torch.empty(rows + 1, width, device=dev, dtype=dtype)
+    t.view(torch.int32 if dtype == torch.float32 else torch.int16).fill_(-1)
     return t
 
 
-def _nan_guard_intact(t, rows, what):
-    assert bool((t.view(torch.int32)[rows:] == -1).all()), f"{what}: the launch wrote behind its result (guard row changed)"
+def _guard_ok(t, rows, width=None, exact=True):
+    """Everything behind row `rows` (and, with width, right of column `width`) is as a hook must leave it.  exact: still the 0xFF
+    bytes the buffer was preset with.  Not exact: NaN -- for a result the hook converts from its own poisoned 16-bit image, guard
+    included; such a buffer is preset to zero, so that a guard the hook did not write shows too."""
+    if exact:
+        t = t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
+    held = (lambda x: x == -1) if exact else torch.isnan
+    return bool(held(t[rows:]).all()) and (width is None or bool(held(t[:rows, width:]).all()))
+
+
+def _nan_guard_intact(t, rows, what, width=None):
+    if width is None:
+        assert _guard_ok(t, rows), f"{what}: the launch wrote behind its result (guard row changed)"
+    else:
+        assert _guard_ok(t, rows, width), f"{what}: the launch wrote outside its result (guard row / pad columns changed)"
 
 
 def op_train_depth_attn(q, k, v, HW, D, hn, device=None, lib=None):
@@ -1477,16 +1490,11 @@ class Engine:
     # (and pad columns where ld > width), preset to 0xFF bytes -- NaN in every type the kernels write; each wrapper asserts that
     # the guard came back unchanged
     def _guarded(self, rows, ld, f32=True):
-        dt = torch.float32 if f32 else (torch.float16 if L.DTYPE == "f16" else torch.bfloat16)
-        t = torch.empty(rows + 1, ld, device=self.device, dtype=dt)
-        t.view(torch.int32 if f32 else torch.int16).fill_(-1)
-        return t
+        return _nan_guarded(rows, ld, self.device, torch.float32 if f32 else (torch.float16 if L.DTYPE == "f16" else torch.bfloat16))
 
     @staticmethod
     def _guard_intact(t, rows, width, what):
-        bits = t.view(torch.int32 if t.dtype == torch.float32 else torch.int16)
-        ok = bool((bits[rows:] == -1).all()) and bool((bits[:rows, width:] == -1).all())
-        assert ok, f"{what}: the launch wrote outside its result (guard row / pad columns changed)"
+        _nan_guard_intact(t, rows, what, width)
 
     def _epi_args(self, rows, N, B, bias, rowbias, rb_ld, resid, ldr, out_f16, out_split, ldc, defer_cap):
         """Stages the epilogue operands shared by op_linear_ex / op_conv_ex; rows: output rows."""
@@ -1705,13 +1713,8 @@ class Engine:
         return out
 
     def op_layer_norm(self, x, gamma, beta):
-        dev = self.device
-        x = _f32(x, dev)
-        out = torch.empty_like(x)
-        g, b = _f32(gamma, dev), _f32(beta, dev)  # keep alive across the call
-        L.check(self.lib.mvd_op_layer_norm(self._ctx, L.ptr(x), x.shape[0], x.shape[1], L.ptr(g), L.ptr(b), L.ptr(out),
-                                           _stream()))
-        return out
+        """launch_layernorm with eps = 1e-5 on x [rows, C]: the plain form of op_layer_norm_slabs (16-bit result, returned as fp32)."""
+        return self.op_layer_norm_slabs(x, gamma, beta, eps=1e-5, plain=True)[0]
 
     def op_st_tail(self, xin, ln_g, ln_b, w1, b1, w2, b2, ao=None, w_ao=None, b_ao=None, rowbias=None, T=None, w_po=None, b_po=None,
                    resid=None, split=False, iters=0, xp_out=False):
@@ -1744,13 +1747,7 @@ class Engine:
         return (t0, qkv, ms.value) if iters > 0 else (t0, qkv)
 
     def op_attention(self, q, k, v, heads):
-        dev = self.device
-        q, k, v = _f32(q, dev), _f32(k, dev), _f32(v, dev)
-        B, T, Cc = q.shape
-        out = torch.empty_like(q)
-        L.check(self.lib.mvd_op_attention(self._ctx, L.ptr(q), L.ptr(k), L.ptr(v), B, T, heads, Cc // heads, L.ptr(out),
-                                          _stream()))
-        return out
+        return self.op_attention_ex(q, k, v, heads)
 
     def op_attention_ex(self, q, k, v, heads, Tstride=0, ld_pad=0, xcd=-1):
         """mvd_op_attention_ex: attn_kernel on the fused 16-bit image with samples ``Tstride`` rows apart (0 = T) and ``ld_pad`` pad
@@ -1764,7 +1761,7 @@ class Engine:
         L.check(self.lib.mvd_op_attention_ex(self._ctx, L.ptr(q), L.ptr(k), L.ptr(v), B, T, heads, Cc // heads, Tstride, ld_pad, xcd,
                                              L.ptr(out), _stream()))
         body = out[:B * Ts].reshape(B, Ts, Cc)
-        assert bool(torch.isnan(out[B * Ts:]).all()) and bool(torch.isnan(body[:, T:]).all()), \
+        assert _guard_ok(out, B * Ts, exact=False) and bool(torch.isnan(body[:, T:]).all()), \
             "op_attention_ex: the launch wrote outside its result (a pad row or the guard row changed)"
         return body[:, :T].clone()
 
@@ -1780,7 +1777,7 @@ class Engine:
         L.check(self.lib.mvd_op_attention_bwd_ex(self._ctx, L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(d_out), B, T, heads, Cc // heads,
                                                  L.ptr(dq), L.ptr(dk), L.ptr(dv), L.ptr(lse), L.ptr(delta), L.ptr(o), _stream()))
         for t, n, name in ((dq, rows, "dq"), (dk, rows, "dk"), (dv, rows, "dv"), (o, rows, "o"), (lse, nstat, "lse"), (delta, nstat, "delta")):
-            assert bool(torch.isnan(t[n:]).all()), f"op_attention_bwd_ex: the launch wrote behind {name} (guard changed)"
+            assert _guard_ok(t, n, exact=False), f"op_attention_bwd_ex: the launch wrote behind {name} (guard changed)"
             assert not bool(torch.isnan(t[:n]).any()), f"op_attention_bwd_ex: elements of {name} were never written (still NaN)"
         return (dq[:rows].reshape(B, T, Cc), dk[:rows].reshape(B, T, Cc), dv[:rows].reshape(B, T, Cc),
                 lse[:nstat].reshape(B, heads, T), delta[:nstat].reshape(B, heads, T), o[:rows].reshape(B, T, Cc))
@@ -1811,13 +1808,7 @@ class Engine:
         return None if rc == 0 else self.lib.mvd_last_error().decode()
 
     def op_attention_bwd(self, q, k, v, d_out, heads):
-        dev = self.device
-        q, k, v, d_out = _f32(q, dev), _f32(k, dev), _f32(v, dev), _f32(d_out, dev)
-        B, T, Cc = q.shape
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
-        L.check(self.lib.mvd_op_attention_bwd(self._ctx, L.ptr(q), L.ptr(k), L.ptr(v), L.ptr(d_out), B, T, heads, Cc // heads,
-                                              L.ptr(dq), L.ptr(dk), L.ptr(dv), _stream()))
-        return dq, dk, dv
+        return self.op_attention_bwd_ex(q, k, v, d_out, heads)[:3]
 
     def op_group_norm_bwd(self, x, dy, groups, gamma, beta, eps, act=0):
         """x, dy [B, rows, C] channels-last -> (dx, dgamma, dbeta)"""

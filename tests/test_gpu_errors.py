@@ -170,3 +170,33 @@ def test_unsupported_arguments_keep_the_reference_exceptions():
     with pytest.raises(KeyError):             # source_dict[res] lookup, attention.py:127-135
         e.unet_forward(x.cuda(), t.cuda(), ctx.cuda(), {k: v.cuda() for k, v in sd.items()})
     e.close()
+
+
+@pytest.mark.parametrize("name,args", [
+    # (everything after the context) the smallest shapes each hook takes; the data pointers are never reached
+    ("mvd_op_conv", (None, 1, 8, 4, 4, None, None, 8, 3, 1, 0, None, None, 0, None)),
+    ("mvd_op_linear", (None, 8, 8, None, None, 8, 0, None, 0, 0, None, None)),
+    ("mvd_op_group_norm", (None, 1, 32, 4, 8, None, None, 1e-5, 0, None, None)),
+    ("mvd_bench_conv", (1, 64, 8, 8, 64, 1, "ms", None)),
+])
+def test_hooks_refuse_a_null_context(name, args):
+    """The asynchronous per-op hooks and the bench hooks return an error for a NULL context before they size or launch anything
+    (they used to dereference it)."""
+    import ctypes as C
+    lib = L.load()
+    ms = C.c_float(-1.0)
+    rc = getattr(lib, name)(None, *[C.byref(ms) if a == "ms" else a for a in args])
+    assert rc == -1 and lib.mvd_last_error() == b"null context"
+    assert ms.value == -1.0
+
+
+def test_bench_hook_refuses_a_null_result_and_the_context_stays_usable():
+    import ctypes as C
+    from morphablediffusion_amd.engine import Engine
+    e = Engine(gi.SMALL_UNET, VolumeConfig(), workspace_gb=0.5)
+    rc = e.lib.mvd_bench_conv(e._ctx, 1, 64, 8, 8, 64, 1, None, None)
+    assert rc == -1 and b"mvd_bench_conv: null ms_out" in e.lib.mvd_last_error()
+    ms = C.c_float(-1.0)
+    L.check(e.lib.mvd_bench_conv(e._ctx, 1, 64, 8, 8, 64, 1, C.byref(ms), None))
+    assert ms.value > 0.0
+    e.close()
