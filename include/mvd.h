@@ -787,6 +787,14 @@ int mvd_op_conv_ex(mvd_ctx* ctx, const float* x, int B, int H, int W, int Cin, c
                    int use_bias, int out_f16, int out_split, int ldc, const float* resid, int resid_f16, int ldr, int a_half,
                    int force_splitk, int xp, int conv3x_stream, float* slabs, size_t slabs_cap, int defer_epilogue, int* sk_used,
                    int poison, void* out, void* stream);
+/* mvd_op_conv3d_ex (run_conv3d / run_convT3d; tests/test_gpu_conv3d_forms.py): the GemmArgs fields the two 3-D U-nets set.
+ * x [B][D][H][W][Cin] (Cin % 8 == 0); w [Cout][Cin][27], or [Cin][Cout][27] with transposed (ConvTranspose3d k3 s2 p1 op1, stride
+ * must be 1 then); stride 1 / 2; out = acc + bias + resid on [B][Do][Ho][Wo] rows of ldc columns, fp32 or 16-bit (out_f16);
+ * resid [rows][ldr] fp32; in_place: the residual image is first copied into the result buffer (rounded to 16 bits with out_f16)
+ * and read from there by the launch, as the networks' up path does.  a_half, force_splitk, poison: as above. */
+int mvd_op_conv3d_ex(mvd_ctx* ctx, const float* x, int B, int D, int H, int W, int Cin, const float* w, const float* bias, int Cout,
+                     int stride, int transposed, int use_bias, const float* resid, int ldr, int in_place, int out_f16, int ldc,
+                     int a_half, int force_splitk, int poison, void* out, void* stream);
 /* GroupNorm(+act) of sum(slabs) + bias2 + preadd[sample] + resid.  x: nslab slabs of [B][rows][ld] fp32, slab_stride floats apart.
  * form 0: run_group_norm's own choice of kernel; form 1: the two-pass pair called directly (one slab, no bias2 / resid / mat).
  * split 0: out [B*rows + 1][ldo] 16-bit; 1: [hi | lo | hi] blocks of C columns; 2: fp32 rows of ldo / 2 floats.  mat (may be NULL):

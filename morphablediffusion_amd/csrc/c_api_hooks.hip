@@ -24,6 +24,11 @@ __global__ void rows_f32_to_f16_ld_kernel(const float* in, size_t rows, int C, h
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * C; i += (size_t)gridDim.x * blockDim.x)
     out[(i / C) * ldo + i % C] = (half_t)in[i];
 }
+// fp32 rows ldi floats apart -> 16-bit rows ldo apart (the pad columns of both are left as they are)
+__global__ void rows_f32_ld_to_f16_ld_kernel(const float* in, int ldi, size_t rows, int C, half_t* out, int ldo) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * C; i += (size_t)gridDim.x * blockDim.x)
+    out[(i / C) * ldo + i % C] = (half_t)in[(i / C) * ldi + i % C];
+}
 __global__ void rows_f16_ld_to_f32_kernel(const half_t* in, size_t rows, int C, int ldi, float* out) {
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < rows * C; i += (size_t)gridDim.x * blockDim.x)
     out[i] = (float)in[(i / C) * ldi + i % C];
@@ -689,6 +694,60 @@ int mvd_op_conv_ex(mvd_ctx* c, const float* x, int B, int H, int W, int Cin, con
   if (sk_used) *sk_used = 1;
   if (poison) RET_IF(hook_poison(c, s));
   return hook_sync("op_conv_ex", s, up_fold ? run_upconv2d(c, g, B, H, W, s) : run_conv2d(c, g, B, H, W, stride, upsample, s));
+}
+
+// tests/test_gpu_conv3d_forms.py: run_conv3d / run_convT3d in the forms the two 3-D U-nets launch them in.  x [B][D][H][W][Cin],
+// resid [rows][ldr] on the output grid, out [rows + 1][ldc] (fp32, or 16-bit with out_f16); w [Cout][Cin][27], transposed:
+// [Cin][Cout][27].  in_place: the residual image is copied into the result buffer (rounded to 16 bits with out_f16) and the launch
+// reads it from there, as the up path does where xf_l == xd_l.
+int mvd_op_conv3d_ex(mvd_ctx* c, const float* x, int B, int D, int H, int W, int Cin, const float* w, const float* bias, int Cout,
+                     int stride, int transposed, int use_bias, const float* resid, int ldr, int in_place, int out_f16, int ldc,
+                     int a_half, int force_splitk, int poison, void* out, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!x || !w || !out) return mvd_fail("op_conv3d_ex: null operand");
+  if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || (Cin & 7)) return mvd_fail("op_conv3d_ex: Cin % 8 == 0 expected");
+  if (Cout <= 0 || (Cout & 3)) return mvd_fail("op_conv3d_ex: Cout must be a positive multiple of 4");
+  if ((transposed != 0 && transposed != 1) || (stride != 1 && stride != 2) || (transposed && stride != 1))
+    return mvd_fail("op_conv3d_ex: stride 1 or 2, or transposed (with stride 1)");
+  if (use_bias && !bias) return mvd_fail("op_conv3d_ex: use_bias without a bias");
+  if (resid && (ldr < Cout || (ldr & 3))) return mvd_fail("op_conv3d_ex: ldr must be a multiple of 4, >= Cout");
+  if (in_place && !resid) return mvd_fail("op_conv3d_ex: in_place needs a residual");
+  if ((ldc & 3) || ldc < Cout) return mvd_fail("op_conv3d_ex: ldc must be a multiple of 4, >= Cout");
+  if (force_splitk < 0) return mvd_fail("op_conv3d_ex: force_splitk >= 0");
+  if ((uintptr_t)out & 15) return mvd_fail("op_conv3d_ex: the result must be 16-byte aligned");
+  const int Do = transposed ? 2 * D : (D - 1) / stride + 1, Ho = transposed ? 2 * H : (H - 1) / stride + 1,
+            Wo = transposed ? 2 * W : (W - 1) / stride + 1;
+  const size_t rows_in = (size_t)B * D * H * W, rows_out = (size_t)B * Do * Ho * Wo;
+  if (rows_out > (size_t)1 << 24 || rows_out * (size_t)ldc > (size_t)1 << 30 || rows_in * (size_t)Cin > (size_t)1 << 30)
+    return mvd_fail("op_conv3d_ex: at most 2^24 output rows and 2^30 elements per image");
+  hipStream_t s = S(stream);
+  WsScope ws_scope(c);
+  ConvW cw;
+  RET_IF(hook_pack_fwd(c, w, Cout, Cin, 27, transposed, 0, 0, &cw, s));
+  cw.bias = const_cast<float*>(bias);
+  GemmArgs g;
+  g.a = x; g.a_f32 = 1; g.lda = Cin; g.w = &cw; g.out = out; g.out_f32 = out_f16 ? 0 : 1; g.ldc = ldc;
+  g.use_bias = use_bias != 0; g.force_splitk = force_splitk;
+  if (a_half) {
+    const half_t* xh;
+    RET_IF(hook_f16(c, x, rows_in * Cin, &xh, s));
+    g.a = xh; g.a_f32 = 0;
+  }
+  if (resid) {
+    g.resid = resid; g.resid_f32 = 1; g.ldr = ldr;
+    if (in_place) {
+      if (out_f16) {
+        hipLaunchKernelGGL(rows_f32_ld_to_f16_ld_kernel, dim3(hook_blocks(rows_out * Cout)), dim3(256), 0, s, resid, ldr, rows_out, Cout,
+                           (half_t*)out, ldc);
+        HIP_CHECK_RET(hipGetLastError());
+      } else {
+        HIP_CHECK_RET(hipMemcpy2DAsync(out, (size_t)ldc * 4, resid, (size_t)ldr * 4, (size_t)Cout * 4, rows_out, hipMemcpyDeviceToDevice, s));
+      }
+      g.resid = out; g.resid_f32 = out_f16 ? 0 : 1; g.ldr = ldc;
+    }
+  }
+  if (poison) RET_IF(hook_poison(c, s));
+  return hook_sync("op_conv3d_ex", s, transposed ? run_convT3d(c, g, B, D, H, W, s) : run_conv3d(c, g, B, D, H, W, stride, s));
 }
 
 // x: nslab slabs of channels-last [B][rows][ld] fp32, slab_stride floats apart.  form 0: run_group_norm's own choice; form 1: the

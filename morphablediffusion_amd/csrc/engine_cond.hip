@@ -685,10 +685,24 @@ FrustumGeom frustum_geom(const mvd_ctx* c) {
   return g;
 }
 
+// The up path writes 2 D[l+1] x 2 S[l+1] x 2 S[l+1] voxels into level l (run_convT3d), while the levels are sized by
+// (n - 1) / 2 + 1: FrustumTV3DNet needs every level to halve exactly, i.e. frustum_volume_depth and input_image_size / 8
+// multiples of 8 (the reference raises a shape error at conv4 + conv7(x) otherwise).  The gathers alone take any geometry.
+static int frustum_geom_check(const FrustumGeom& geo) {
+  for (int l = 0; l < 3; ++l) {
+    if (2 * geo.D[l + 1] != geo.D[l])
+      return mvd_fail("FrustumTV3DNet: frustum_volume_depth must be a multiple of 8 (every level halves exactly)");
+    if (2 * geo.S[l + 1] != geo.S[l])
+      return mvd_fail("FrustumTV3DNet: input_image_size / 8 must be a multiple of 8 (every level halves exactly)");
+  }
+  return 0;
+}
+
 // FrustumTV3DNet (network.py:313-347) on TN gathered frustum volumes
 int engine_frustum_layers(mvd_ctx* c, int TN, const half_t* gath, const float* pre, const FrustumBufs& b, hipStream_t s,
                           const std::function<int()>* film) {
   const FrustumGeom geo = frustum_geom(c);
+  RET_IF(frustum_geom_check(geo));
   const int *fd = c->v.frustum_dims, *D = geo.D, *S = geo.S, FT = c->film_total;
   GemmArgs g;
   g.a = gath; g.lda = 64; g.w = &c->fr_conv0; g.out = b.xd[0]; g.ldc = fd[0];
@@ -726,8 +740,9 @@ int engine_frustum_layers(mvd_ctx* c, int TN, const half_t* gath, const float* p
 template <typename Gather, typename Film>
 static int frustum_net(mvd_ctx* c, int TN, FrustumOut* out, hipStream_t s, bool half0, Gather&& gather, Film&& film) {
   const FrustumGeom geo = frustum_geom(c);
+  RET_IF(frustum_geom_check(geo));  // before the gather: a refused geometry launches nothing
   const int* fd = c->v.frustum_dims;
-  auto vox = [&](int l) { return (size_t)TN * geo.vox[l]; };
+  auto vox =[&](int l) { return (size_t)TN * geo.vox[l]; };
   // outputs (persist for the caller)
   float* x[4];
   for (int l = 0; l < 4; ++l) {

@@ -1583,6 +1583,34 @@ class Engine:
         res.nchw = res.out.reshape(B, Ho, Wo, Cout).permute(0, 3, 1, 2).contiguous()
         return res
 
+    def op_conv3d_ex(self, x, w, bias=None, stride=1, transposed=False, use_bias=True, resid=None, ldr=0, in_place=False,
+                     out_f16=False, ldc=0, a_half=True, force_splitk=0, poison=True):
+        """mvd_op_conv3d_ex: x [B,Cin,D,H,W], w [Cout,Cin,3,3,3] ([Cin,Cout,3,3,3] transposed), resid [B,Cout,Do,Ho,Wo] (reference
+        layouts; the hook's channels-last images are made here) -> a namespace with .out (fp32 [B,Cout,Do,Ho,Wo]) and .raw (the
+        result rows [rows][Cout] as written, fp32 or the library's 16-bit type).  The guard row and the pad columns of the result
+        buffer are asserted unchanged."""
+        dev = self.device
+        x, w = _f32(x, dev), _f32(w, dev)
+        B, Cin, D, H, W = x.shape
+        Cout = w.shape[1] if transposed else w.shape[0]
+        od = (2 * D, 2 * H, 2 * W) if transposed else tuple((n - 1) // stride + 1 for n in (D, H, W))
+        rows = B * od[0] * od[1] * od[2]
+        xl = x.permute(0, 2, 3, 4, 1).contiguous()
+        b = None if bias is None else _f32(bias, dev)
+        r = None
+        if resid is not None:
+            ldr = ldr or Cout
+            r = torch.full((rows, ldr), float("nan"), device=dev)
+            r[:, :Cout] = _f32(resid, dev).permute(0, 2, 3, 4, 1).reshape(rows, Cout)
+        ldc = ldc or Cout
+        out = self._guarded(rows, ldc, f32=not out_f16)
+        L.check(self.lib.mvd_op_conv3d_ex(self._ctx, L.ptr(xl), B, D, H, W, Cin, L.ptr(w), L.ptr(b), Cout, stride, bool(transposed),
+                                          bool(use_bias and b is not None), L.ptr(r), ldr or 0, bool(in_place), bool(out_f16), ldc,
+                                          bool(a_half), force_splitk, bool(poison), L.ptr(out), _stream()))
+        self._guard_intact(out, rows, Cout, "op_conv3d_ex")
+        raw = out[:rows, :Cout]
+        return types.SimpleNamespace(raw=raw, out=raw.float().reshape(B, *od, Cout).permute(0, 4, 1, 2, 3).contiguous())
+
     def op_group_norm_ex(self, x, groups, gamma, beta, eps=1e-5, act=0, form=0, ld=0, preadd=None, pld=0, split=0, bias2=None,
                          resid=None, ldr=0, mat=False, ldm=0, ldo=0, poison=True):
         """mvd_op_group_norm_ex: x [nslab, B, rows, C] channels-last slabs (or [B, rows, C]); preadd [B, C], bias2 [C], resid

@@ -213,6 +213,10 @@ class VolumeConfig:
     ``num_views`` is SMPLFeatureExtractor.num_views, hard-coded to 16 in the reference
     (morphable_diffusion.py:165-167, SURVEY gotcha G3); ``input_image_size`` is not forwarded from the
     model config in the reference either (gotcha G4).  Both are explicit here.
+
+    FrustumTV3DNet needs every level to halve exactly: ``frustum_volume_depth`` and ``input_image_size / 8`` must be
+    multiples of 8, or the call that runs the network is refused before its first launch (the reference raises a shape error
+    at ``conv4 + conv7(x)``).  The gathers alone take any geometry.
     """
     time_dim: int = 256
     view_dim: int = 4

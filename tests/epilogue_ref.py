@@ -1,8 +1,10 @@
 """fp64 references of the forward kernels' epilogue, split-precision and slab forms, written from the reference model's definition
 (not from the kernels), the torch-fp32 emulation of the split arithmetic, and the case tables of tests/test_gpu_epilogue_forms.py
-with the conditions each case is built to meet (tests/test_epilogue_forms_cpu.py checks both without a GPU).
+with the conditions each case is built to meet (tests/test_epilogue_forms_cpu.py checks both without a GPU).  At the end: the same
+for the 3-D convolutions of tests/test_gpu_conv3d_forms.py (checked by tests/test_conv3d_forms_cpu.py).
 
 Order of a GEMM / conv epilogue:  out = act(alpha * acc + bias + rowbias[sample] + resid),  sample = row // rows_per_sample."""
+import collections
 import functools
 import math
 import re
@@ -340,3 +342,195 @@ def softmax_scores(cols):
     s[1, (7 * cols) // 11] = 30.0
     s[2] = 3.25
     return s
+
+
+# -------------------------------------------------------------------------------------- 3-D convolutions (tests/test_gpu_conv3d_forms.py)
+# run_conv3d / run_convT3d (csrc/engine_unet.hip) as the two 3-D U-nets launch them: out = acc + bias + resid on the output grid.
+
+CONV3D_DMA_MAX_M = 16384  # igemm_go: a multi-tap launch with more rows stays on the 128-row gather kernel
+CONVT3D_BATCH_MIN_ROWS = 512  # run_convT3d: fewer input rows launch one GEMM per output-parity class
+
+
+def conv3d(x, w, stride=1, transposed=False, bias=None, resid=None):
+    """x [B, Cin, D, H, W]; w [Cout, Cin, 3, 3, 3] (Conv3d k3 p1) or, transposed, [Cin, Cout, 3, 3, 3] (ConvTranspose3d k3 s2 p1 op1);
+    bias [Cout], resid on the output grid -> fp64 [B, Cout, Do, Ho, Wo]"""
+    x, w = x.double(), w.double()
+    if transposed:
+        v = F.conv_transpose3d(x, w, stride=2, padding=1, output_padding=1)
+    else:
+        v = F.conv3d(x, w, stride=stride, padding=1)
+    if bias is not None:
+        v = v + bias.double()[None, :, None, None, None]
+    if resid is not None:
+        v = v + resid.double()
+    return v
+
+
+def conv3d_out_dims(kind, dims):
+    if kind == "T":
+        return tuple(2 * n for n in dims)
+    s = 2 if kind == "s2" else 1
+    return tuple((n - 1) // s + 1 for n in dims)
+
+
+def conv3d_rows(kind, B, dims):
+    """the GEMM rows of a launch, which the routing goes by: output voxels, or for the transposed conv (whose classes each
+    produce one output voxel per INPUT voxel) input voxels"""
+    return B * math.prod(dims if kind == "T" else conv3d_out_dims(kind, dims))
+
+
+def _conv3d_route(M, ntaps, Cin, Cout, a_half, ldc, ldr):
+    """igemm_go for one launch of M rows and ntaps taps (k_gemm.hip gemm_dma_eligible; no 3-D launch is halo- or conv3x-eligible)"""
+    if not a_half:
+        return "gather_f32"
+    dense = (DENSE_MIN_M <= M and (ntaps == 1 or M <= CONV3D_DMA_MAX_M) and Cin % 8 == 0 and Cout % 4 == 0 and ldc % 4 == 0
+             and ldr % 4 == 0)
+    return "dense" if dense else "gather_f16"
+
+
+def convT3d_launches(B, Cin, Cout, dims, a_half, force_splitk=0, ldc=0, ldr=0):
+    """run_convT3d restated: [(family, taps)] per launch -- one parity-batched launch of the LDS-DMA kernel, or the eight classes
+    (pz, py, px) with (1 + pz)(1 + py)(1 + px) taps, each routed like a convolution of its own over the input rows"""
+    M = B * math.prod(dims)
+    ldc = ldc or Cout
+    eligible = a_half and Cin % 8 == 0 and Cout % 4 == 0 and ldc % 4 == 0 and ldr % 4 == 0
+    if eligible and force_splitk <= 1 and M >= CONVT3D_BATCH_MIN_ROWS:
+        return [("dense", 8)]
+    out = []
+    for par in range(8):
+        taps = (1 + (par >> 2)) * (1 + ((par >> 1) & 1)) * (1 + (par & 1))
+        out.append((_conv3d_route(M, taps, Cin, Cout, a_half, ldc, ldr), taps))
+    return out
+
+
+def conv3d_launches(kind, B, Cin, Cout, dims, a_half, force_splitk=0, ldc=0, ldr=0):
+    if kind == "T":
+        return convT3d_launches(B, Cin, Cout, dims, a_half, force_splitk, ldc, ldr)
+    return [(_conv3d_route(conv3d_rows(kind, B, dims), 27, Cin, Cout, a_half, ldc or Cout, ldr), 27)]
+
+
+def conv3d_family_ok(family, kind, B, Cin, Cout, dims, a_half, force_splitk=0, ldc=0, ldr=0):
+    """every launch of the layer runs on `family`"""
+    return all(f == family for f, _ in conv3d_launches(kind, B, Cin, Cout, dims, a_half, force_splitk, ldc, ldr))
+
+
+def conv3d_reduce_launches(kind, B, Cin, Cout, dims, a_half, force_splitk=0, ldc=0, ldr=0):
+    """splitk_reduce_kernel launches of a FORCED split (plan_dense / plan_gather: sk = min(force_splitk, k-steps), a k-step being one
+    tap of up to 64 channels): one per launch with at least two k-steps; the parity-batched launch never splits"""
+    launches = conv3d_launches(kind, B, Cin, Cout, dims, a_half, force_splitk, ldc, ldr)
+    if kind == "T" and len(launches) == 1:
+        return 0
+    return sum(1 for _, taps in launches if min(force_splitk, taps * ((Cin + 63) // 64)) > 1)
+
+
+def igemm_pick_bn(N):
+    """k_igemm.hip: the column-tile width of a launch that is not a plain GEMM"""
+    if N <= 64:
+        return 64
+    return 160 if -(-N // 160) * 160 < -(-N // 128) * 128 else 128
+
+
+def parity_batch_nch(M, Cin, Cout, npar=8, kmax=8):
+    """go_parity_batch -> gemm_dma_plan (k_gemm.hip), restated: the column tiles one workgroup walks.  Cost in k-steps per round of
+    256 workgroups: nch * ksteps + 4 + 2 nch."""
+    bn, ksteps = igemm_pick_bn(Cout), kmax * ((Cin + 63) // 64)
+    tiles_m, tiles_n = -(-M * npar // 256), -(-Cout // bn)
+    best, best_nch = None, 1
+    for nch in range(1, tiles_n + 1):
+        cost = -(-tiles_m * -(-tiles_n // nch) // 256) * (nch * ksteps + 4 + 2 * nch)
+        if best is None or cost < best:
+            best, best_nch = cost, nch
+    return best_nch
+
+
+def conv3d_cell(case):
+    """the routing cell a case is in: (stride 1 | stride 2 | transposed batched | transposed unbatched, family)"""
+    if case.kind != "T":
+        return case.kind, case.family
+    return ("T batched" if case.launches == 1 else "T unbatched"), case.family
+
+
+# the cells igemm_go / run_convT3d allow: the parity-batched launch is always the LDS-DMA kernel's
+CONV3D_CELLS = {(k, f) for k in ("s1", "s2", "T unbatched") for f in ("dense", "gather_f16", "gather_f32")} | {("T batched", "dense")}
+
+Conv3dCase = collections.namedtuple(
+    "Conv3dCase", "name kind B Cin Cout dims a_half force_splitk in_place out_f16 ldc_pad family launches reduces density span")
+
+
+def _c3(name, kind, B, Cin, Cout, dims, a_half, family, launches=1, reduces=0, force_splitk=0, in_place=False, out_f16=False, ldc_pad=0,
+        density=0.15, span=61):
+    return Conv3dCase(name, kind, B, Cin, Cout, dims, a_half, force_splitk, in_place, out_f16, ldc_pad, family, launches, reduces, density,
+                      span)
+
+
+# Exact-arithmetic cases.  force_splitk = 0 in the table is passed as 1 (the kernel's own epilogue; the planner's split of a small
+# launch is its own choice and is left to the random-operand cases); 2 forces the reduce pass.  A 16-bit result lowers the density
+# and the span until the reference is representable in fp16 AND bfloat16 (tests/test_conv3d_forms_cpu.py).
+CONV3D_CASES = [
+    # ---- stride 1
+    _c3("s1 gather_f16 17x32x32 72->40 above 16384 rows", "s1", 1, 72, 40, (17, 32, 32), True, "gather_f16"),
+    _c3("s1 dense 16x32x32 16->8 exactly 16384 rows", "s1", 1, 16, 8, (16, 32, 32), True, "dense"),
+    _c3("s1 gather_f16 3x4x4 64->40 48 rows", "s1", 1, 64, 40, (3, 4, 4), True, "gather_f16"),
+    _c3("s1 dense 4x4x4 64->40 exactly 64 rows", "s1", 1, 64, 40, (4, 4, 4), True, "dense"),
+    _c3("s1 dense B=3 5x7x9 16->40", "s1", 3, 16, 40, (5, 7, 9), True, "dense"),
+    _c3("s1 dense B=3 5x7x9 48->200 ldc", "s1", 3, 48, 200, (5, 7, 9), True, "dense", ldc_pad=12),
+    _c3("s1 dense B=3 5x7x9 72->320", "s1", 3, 72, 320, (5, 7, 9), True, "dense"),
+    _c3("s1 dense B=5 1x3x5 64->40 extent 1", "s1", 5, 64, 40, (1, 3, 5), True, "dense"),
+    _c3("s1 dense B=3 5x7x9 128->40 split-K", "s1", 3, 128, 40, (5, 7, 9), True, "dense", reduces=1, force_splitk=2),
+    _c3("s1 dense B=3 5x7x9 48->40 in place f16 out", "s1", 3, 48, 40, (5, 7, 9), True, "dense", in_place=True, out_f16=True, ldc_pad=8,
+        density=0.02, span=5),
+    _c3("s1 gather_f32 B=3 5x7x9 24->40", "s1", 3, 24, 40, (5, 7, 9), False, "gather_f32"),
+    _c3("s1 gather_f32 B=3 5x7x9 128->200 split-K ldc", "s1", 3, 128, 200, (5, 7, 9), False, "gather_f32", reduces=1, force_splitk=2,
+        ldc_pad=4),
+    # ---- stride 2: odd extents ((n - 1) / 2 + 1 outputs), extent 1, one output voxel
+    _c3("s2 gather_f16 51x53x51 16->8 above 16384 rows", "s2", 1, 16, 8, (51, 53, 51), True, "gather_f16"),
+    _c3("s2 dense B=3 5x7x9 16->40", "s2", 3, 16, 40, (5, 7, 9), True, "dense"),
+    _c3("s2 dense B=3 5x7x9 48->200", "s2", 3, 48, 200, (5, 7, 9), True, "dense"),
+    _c3("s2 dense B=3 5x7x9 72->320 ldc", "s2", 3, 72, 320, (5, 7, 9), True, "dense", ldc_pad=4),
+    _c3("s2 dense B=11 1x3x5 64->40 extent 1", "s2", 11, 64, 40, (1, 3, 5), True, "dense"),
+    _c3("s2 gather_f16 B=2 1x3x5 64->40 extent 1", "s2", 2, 64, 40, (1, 3, 5), True, "gather_f16"),
+    _c3("s2 gather_f16 B=2 2x2x2 72->40 one voxel", "s2", 2, 72, 40, (2, 2, 2), True, "gather_f16"),
+    _c3("s2 gather_f32 B=3 5x7x9 24->40", "s2", 3, 24, 40, (5, 7, 9), False, "gather_f32"),
+    _c3("s2 gather_f32 B=2 2x2x2 24->40 one voxel", "s2", 2, 24, 40, (2, 2, 2), False, "gather_f32"),
+    # ---- transposed, all eight parity classes in one launch
+    _c3("T batched B=2 4x8x8 64->200 exactly 512 rows", "T", 2, 64, 200, (4, 8, 8), True, "dense"),
+    _c3("T batched B=2 4x8x8 64->320", "T", 2, 64, 320, (4, 8, 8), True, "dense"),
+    _c3("T batched B=2 6x16x24 64->200 column walk", "T", 2, 64, 200, (6, 16, 24), True, "dense"),
+    _c3("T batched B=1 5x7x15 48->40 in place", "T", 1, 48, 40, (5, 7, 15), True, "dense", in_place=True),
+    _c3("T batched B=2 4x8x8 64->40 in place f16 out ldc (level-0 form)", "T", 2, 64, 40, (4, 8, 8), True, "dense", in_place=True,
+        out_f16=True, ldc_pad=8, density=0.02, span=5),
+    _c3("T batched B=2 4x8x8 72->200 f16 out", "T", 2, 72, 200, (4, 8, 8), True, "dense", out_f16=True, density=0.02, span=5),
+    # ---- transposed, one launch per parity class
+    _c3("T unbatched 6x7x12 64->40 504 rows", "T", 1, 64, 40, (6, 7, 12), True, "dense", launches=8),
+    _c3("T unbatched 6x7x12 64->40 fp32 source", "T", 1, 64, 40, (6, 7, 12), False, "gather_f32", launches=8),
+    _c3("T unbatched B=2 4x8x8 128->40 split-K", "T", 2, 128, 40, (4, 8, 8), True, "dense", launches=8, reduces=8, force_splitk=2),
+    _c3("T unbatched B=2 4x8x8 64->200 split-K fp32 source", "T", 2, 64, 200, (4, 8, 8), False, "gather_f32", launches=8, reduces=7,
+        force_splitk=2),
+    _c3("T unbatched B=2 2x3x4 72->40 48 rows", "T", 2, 72, 40, (2, 3, 4), True, "gather_f16", launches=8),
+    _c3("T unbatched 6x7x12 48->40 fp32 source in place f16 out ldc", "T", 1, 48, 40, (6, 7, 12), False, "gather_f32", launches=8,
+        in_place=True, out_f16=True, ldc_pad=8, density=0.02, span=5),
+]
+CONV3D_BY_NAME = {c.name: c for c in CONV3D_CASES}
+
+
+def conv3d_ld(case):
+    """(ldc, ldr) of a case: the residual rows are padded whenever the result rows are"""
+    return case.Cout + case.ldc_pad, case.Cout + (4 if case.ldc_pad else 0)
+
+
+def conv3d_operands(case):
+    """(x, w, bias, resid) with every product and every partial sum exact in 16-bit x 16-bit -> fp32"""
+    T = case.kind == "T"
+    seed = CONV3D_CASES.index(case) % 5
+    small = case.out_f16
+    x = binary(case.B, case.Cin, *case.dims, seed=seed, density=case.density)
+    w = ints64(*((case.Cin, case.Cout) if T else (case.Cout, case.Cin)), 3, 3, 3, seed=1, span=case.span)
+    od = conv3d_out_dims(case.kind, case.dims)
+    return x, w, ints64(case.Cout, seed=2, span=7 if small else 47), ints64(case.B, case.Cout, *od, seed=4, span=9 if small else 59)
+
+
+@functools.lru_cache(maxsize=None)
+def conv3d_reference(name):
+    case = CONV3D_BY_NAME[name]
+    x, w, bias, resid = conv3d_operands(case)
+    return conv3d(x, w, stride=2 if case.kind == "s2" else 1, transposed=case.kind == "T", bias=bias, resid=resid)
