@@ -795,6 +795,19 @@ int mvd_op_conv_ex(mvd_ctx* ctx, const float* x, int B, int H, int W, int Cin, c
 int mvd_op_conv3d_ex(mvd_ctx* ctx, const float* x, int B, int D, int H, int W, int Cin, const float* w, const float* bias, int Cout,
                      int stride, int transposed, int use_bias, const float* resid, int ldr, int in_place, int out_f16, int ldc,
                      int a_half, int force_splitk, int poison, void* out, void* stream);
+/* mvd_op_conv3d_form (tests/test_gpu_conv3d_halo.py): mvd_op_conv3d_ex with the kernel form chosen by the caller.  form 0: the
+ * engine's own routing; form 1: conv3z, the plane-halo kernel of the 3x3x3 stride-1 layers (k_conv3x.hip), whatever the row count --
+ * an error, never another kernel, where the layer is outside its limits (fp16 source, Cin % 64 == 0, Cout 64 or 128, H and W
+ * multiples of 16; force_splitk is not used: the kernel does not split). */
+int mvd_op_conv3d_form(mvd_ctx* ctx, const float* x, int B, int D, int H, int W, int Cin, const float* w, const float* bias, int Cout,
+                       int stride, int transposed, int use_bias, const float* resid, int ldr, int in_place, int out_f16, int ldc,
+                       int a_half, int force_splitk, int form, int poison, void* out, void* stream);
+/* The form the engine's routing gives a 3x3x3 layer of this shape (0: the kernels mvd_op_conv3d_ex documents, 1: conv3z), assuming
+ * the weights carry every stream the engine packs for them and a context with its default switches: the gate igemm_go puts in front
+ * of the predicate (MVD_NO_CONV3X / MVD_NO_HALO unset, inference context) is not evaluated here -- with either switch set, or in a
+ * training context, no layer has a stream and every layer keeps form 0.  Needs no context and no device; -1 = bad arguments. */
+int mvd_conv3d_routed_form(int B, int D, int H, int W, int Cin, int Cout, int stride, int transposed, int a_half, int out_f16, int ldc,
+                           int has_resid, int resid_f16, int ldr, int force_splitk);
 /* GroupNorm(+act) of sum(slabs) + bias2 + preadd[sample] + resid.  x: nslab slabs of [B][rows][ld] fp32, slab_stride floats apart.
  * form 0: run_group_norm's own choice of kernel; form 1: the two-pass pair called directly (one slab, no bias2 / resid / mat).
  * split 0: out [B*rows + 1][ldo] 16-bit; 1: [hi | lo | hi] blocks of C columns; 2: fp32 rows of ldo / 2 floats.  mat (may be NULL):

@@ -700,10 +700,13 @@ int mvd_op_conv_ex(mvd_ctx* c, const float* x, int B, int H, int W, int Cin, con
 // resid [rows][ldr] on the output grid, out [rows + 1][ldc] (fp32, or 16-bit with out_f16); w [Cout][Cin][27], transposed:
 // [Cin][Cout][27].  in_place: the residual image is copied into the result buffer (rounded to 16 bits with out_f16) and the launch
 // reads it from there, as the up path does where xf_l == xd_l.
-int mvd_op_conv3d_ex(mvd_ctx* c, const float* x, int B, int D, int H, int W, int Cin, const float* w, const float* bias, int Cout,
-                     int stride, int transposed, int use_bias, const float* resid, int ldr, int in_place, int out_f16, int ldc,
-                     int a_half, int force_splitk, int poison, void* out, void* stream) {
+// form (tests/test_gpu_conv3d_halo.py): 0 = the kernel igemm_go picks, 1 = conv3z (k_conv3x.hip) whatever the row count.
+static int conv3d_hook(const char* who, mvd_ctx* c, const float* x, int B, int D, int H, int W, int Cin, const float* w, const float* bias,
+                       int Cout, int stride, int transposed, int use_bias, const float* resid, int ldr, int in_place, int out_f16, int ldc,
+                       int a_half, int force_splitk, int form, int poison, void* out, void* stream) {
   RET_IF(hook_begin(c));
+  if (form != 0 && form != 1) return mvd_fail("op_conv3d_form: form must be 0 or 1");
+  if (form == 1 && (transposed || stride != 1)) return mvd_fail("op_conv3d_form: form 1 (conv3z) is a stride-1 convolution");
   if (!x || !w || !out) return mvd_fail("op_conv3d_ex: null operand");
   if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || (Cin & 7)) return mvd_fail("op_conv3d_ex: Cin % 8 == 0 expected");
   if (Cout <= 0 || (Cout & 3)) return mvd_fail("op_conv3d_ex: Cout must be a positive multiple of 4");
@@ -725,6 +728,13 @@ int mvd_op_conv3d_ex(mvd_ctx* c, const float* x, int B, int D, int H, int W, int
   ConvW cw;
   RET_IF(hook_pack_fwd(c, w, Cout, Cin, 27, transposed, 0, 0, &cw, s));
   cw.bias = const_cast<float*>(bias);
+  const int bnz = transposed || stride != 1 ? 0 : conv3z_stream_bn(27, Cout, Cin);
+  if (bnz && mvd_env_call::conv3x()) {  // ... and the conv3z form of the weights, as pack_conv3z_stream does
+    cw.wx = ws_alloc<half_t>(c, conv3z_stream_halfs(Cout, Cin, bnz));
+    WS_CHECK(cw.wx);
+    RET_IF(conv3z_pack(cw.w, Cout, Cin, bnz, cw.wx, s));
+    cw.wx_bn = bnz;
+  }
   GemmArgs g;
   g.a = x; g.a_f32 = 1; g.lda = Cin; g.w = &cw; g.out = out; g.out_f32 = out_f16 ? 0 : 1; g.ldc = ldc;
   g.use_bias = use_bias != 0; g.force_splitk = force_splitk;
@@ -747,7 +757,37 @@ int mvd_op_conv3d_ex(mvd_ctx* c, const float* x, int B, int D, int H, int W, int
     }
   }
   if (poison) RET_IF(hook_poison(c, s));
-  return hook_sync("op_conv3d_ex", s, transposed ? run_convT3d(c, g, B, D, H, W, s) : run_conv3d(c, g, B, D, H, W, stride, s));
+  return hook_sync(who, s, transposed ? run_convT3d(c, g, B, D, H, W, s) : run_conv3d(c, g, B, D, H, W, stride, s, form));
+}
+int mvd_op_conv3d_ex(mvd_ctx* c, const float* x, int B, int D, int H, int W, int Cin, const float* w, const float* bias, int Cout,
+                     int stride, int transposed, int use_bias, const float* resid, int ldr, int in_place, int out_f16, int ldc,
+                     int a_half, int force_splitk, int poison, void* out, void* stream) {
+  return conv3d_hook("op_conv3d_ex", c, x, B, D, H, W, Cin, w, bias, Cout, stride, transposed, use_bias, resid, ldr, in_place, out_f16, ldc,
+                     a_half, force_splitk, 0, poison, out, stream);
+}
+int mvd_op_conv3d_form(mvd_ctx* c, const float* x, int B, int D, int H, int W, int Cin, const float* w, const float* bias, int Cout,
+                       int stride, int transposed, int use_bias, const float* resid, int ldr, int in_place, int out_f16, int ldc,
+                       int a_half, int force_splitk, int form, int poison, void* out, void* stream) {
+  return conv3d_hook("op_conv3d_form", c, x, B, D, H, W, Cin, w, bias, Cout, stride, transposed, use_bias, resid, ldr, in_place, out_f16,
+                     ldc, a_half, force_splitk, form, poison, out, stream);
+}
+// The form igemm_go gives a stride-1 / stride-2 3x3x3 layer whose weights carry every stream the engine packs for them: 0 = the
+// kernels of before, 1 = conv3z; transposed layers: 0.  Evaluates the routing predicate (conv3z_routed) alone: no context, no device --
+// and so not the gate igemm_go puts in front of it (env.conv3x && c->use_halo; training contexts pack no stream): the answer is
+// that of an inference context with its default switches.
+int mvd_conv3d_routed_form(int B, int D, int H, int W, int Cin, int Cout, int stride, int transposed, int a_half, int out_f16, int ldc,
+                           int has_resid, int resid_f16, int ldr, int force_splitk) {
+  if (B <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (stride != 1 && stride != 2)) return mvd_fail("conv3d_routed_form: bad shape");
+  if (transposed) return 0;
+  static const half_t some = (half_t)0.f;  // never read: only "there is a stream" is asked
+  ConvW cw;
+  cw.N = Cout; cw.Cin = Cin; cw.taps = 27;
+  cw.wx_bn = stride == 1 ? conv3z_stream_bn(27, Cout, Cin) : 0;
+  cw.wx = cw.wx_bn ? const_cast<half_t*>(&some) : nullptr;
+  GemmArgs g;
+  g.a = &some; g.a_f32 = a_half ? 0 : 1; g.lda = Cin; g.w = &cw; g.out_f32 = out_f16 ? 0 : 1; g.ldc = ldc; g.force_splitk = force_splitk;
+  if (has_resid) { g.resid = &some; g.resid_f32 = resid_f16 ? 0 : 1; g.ldr = ldr; }
+  return conv3d_routed_form(g, B, D, H, W, stride);
 }
 
 // x: nslab slabs of channels-last [B][rows][ld] fp32, slab_stride floats apart.  form 0: run_group_norm's own choice; form 1: the

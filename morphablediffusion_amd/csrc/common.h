@@ -110,6 +110,7 @@ struct IGemm {
   int par_oz[8], par_oy[8], par_ox[8];
   int par_walk;         // LDS-DMA kernel: one workgroup walks the npar classes of its tile (grid.z = 1) instead of one per class
   const half_t* wx;     // the same weights as a conv3x fragment stream (k_conv3x.hip) packed for column tiles of wx_bn, or null
+                        // (27 taps: the conv3z stream, wx_bn 64 or 128)
   int wx_bn;
   int bn;               // column-tile width (64 / 96 / 128 / 160); 0 = pick from N
   int bm;               // LDS-DMA GEMM only: row-tile height, 256 (0 = 256: eight waves) or 128 (four waves; plain GEMMs)
@@ -151,6 +152,13 @@ bool conv3x_eligible(const IGemm& g, int bn);
 size_t conv3x_stream_halfs(int N, int Cin, int bn);
 int conv3x_pack(const half_t* w, int N, int Cin, int bn, half_t* stream, hipStream_t s);
 int launch_conv3x(const IGemm& g, const half_t* stream, int bn, hipStream_t s);
+// the 3 x 3 x 3 stride-1 form of the same kernel (k_conv3x.hip, conv3z): hard limits, stream size / pack (bn 64 or 128), launch
+constexpr int CONV3D_DMA_MAX_M = 16384;  // rows up to which igemm_go sends a 27-tap layer to the LDS-DMA tap gather
+int conv3z_stream_bn(int taps, int N, int Cin);  // the column tile a layer's conv3z stream is packed for, 0: the layer gets none
+bool conv3z_eligible(const IGemm& g, int bn);
+size_t conv3z_stream_halfs(int N, int Cin, int bn);
+int conv3z_pack(const half_t* w, int N, int Cin, int bn, half_t* stream, hipStream_t s);
+int launch_conv3z(const IGemm& g, const half_t* stream, int bn, hipStream_t s);
 bool gemm_dma_eligible(const IGemm& g);
 bool gemm_dma_is_plain(const IGemm& g);
 void gemm_dma_plan(int M, int N, int ksteps, int bn, int geglu, int* nch_out, int* splitk_out);

@@ -702,7 +702,8 @@ int run_conv2d(mvd_ctx* c, const GemmArgs& ga, int B, int H, int W, int stride, 
 // nearest x2 upsample + 3x3 conv as four parity-folded 2x2 convs on the [B,H,W] input (needs ConvW::w_up)
 int run_upconv2d(mvd_ctx* c, const GemmArgs& ga, int B, int H, int W, hipStream_t s);
 // 3x3x3 conv stride 1/2 on [B,D,H,W,*]
-int run_conv3d(mvd_ctx* c, const GemmArgs& ga, int B, int D, int H, int W, int stride, hipStream_t s);
+int run_conv3d(mvd_ctx* c, const GemmArgs& ga, int B, int D, int H, int W, int stride, hipStream_t s, int form = 0);
+int conv3d_routed_form(const GemmArgs& ga, int B, int D, int H, int W, int stride);
 // ConvTranspose3d(k3,s2,p1,op1): 8 output-parity classes
 int run_convT3d(mvd_ctx* c, const GemmArgs& ga, int B, int D, int H, int W, hipStream_t s);
 // GroupNorm(+act) -> fp16

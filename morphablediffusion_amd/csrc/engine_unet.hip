@@ -120,6 +120,23 @@ int go_conv3x(mvd_ctx* c, IGemm& g, int M, int force_splitk, hipStream_t s, cons
   return r;
 }
 
+// conv3z (k_conv3x.hip): the 3 x 3 x 3 stride-1 convolutions of the two 3-D U-nets' wide levels, one workgroup per 16 x 16 block of
+// a depth plane x wx_bn columns, the plane halos in LDS instead of 27 register-staged gathers of every voxel; no split-K
+int go_conv3z(mvd_ctx* c, IGemm& g, int M, hipStream_t s) {
+  g.bn = g.wx_bn;
+  g.splitk = 1;
+  g.partial = nullptr;
+  const double kalg = (double)(g.cin_alg ? g.cin_alg : g.Cin);
+  double bytes = (double)M * kalg * 2 + 27.0 * g.N * kalg * 2 + (double)M * g.N * (g.out_f32 ? 4 : 2);
+  if (g.resid) bytes += (double)M * g.N * 4;
+  ProbeScope ps(c, s, g.wx_bn == 64 ? "conv3z_kernel<2>" : "conv3z_kernel<4>", 2.0 * M * g.N * kalg * 27.0, bytes);
+  return launch_conv3z(g, g.wx, g.wx_bn, s);
+}
+// ... taken above the row count up to which igemm_go sends a 27-tap layer to the LDS-DMA tap gather, unless the caller forces a split
+bool conv3z_routed(const IGemm& g, int M, int force_splitk) {
+  return g.wx && g.ntaps == 27 && force_splitk <= 1 && M > CONV3D_DMA_MAX_M && conv3z_eligible(g, g.wx_bn);
+}
+
 // parity-batched launch (run_convT3d / run_upconv2d): LDS-DMA kernel, no split-K
 int go_parity_batch(mvd_ctx* c, IGemm& g, int M, hipStream_t s) {
   if (!gemm_dma_eligible(g)) return mvd_fail("igemm_go: parity batch needs the LDS-DMA kernel");
@@ -287,12 +304,13 @@ int igemm_go(mvd_ctx* c, IGemm& g, int force_splitk, hipStream_t s, const GemmAr
   //  a half rounds, A read three times -- and 37 us as 2 x 160; MVD_IGEMM_F32_BN128=1 restores the old choice)
   if (g.a_f32 && g.bn == 160 && env.igemm_f32_bn128) g.bn = 128;
   if (env.conv3x && c->use_halo && g.wx && conv3x_eligible(g, g.wx_bn)) return go_conv3x(c, g, M, force_splitk, s, defer);
+  if (env.conv3x && c->use_halo && conv3z_routed(g, M, force_splitk)) return go_conv3z(c, g, M, s);
   if (g.npar > 0) return go_parity_batch(c, g, M, s);
   const bool halo = c->use_halo && conv3_halo_eligible(g);
   // one 256-row workgroup per CU: wins for the Linear layers and wherever weights stream (small M, long K), down to one
   // quarter-filled row tile (2-views-per-rank step: 7.08 ms with a 512-row threshold, 6.97 ms with 64);
   // the big shallow 3-D convs keep the 128-row gather kernel (finer tiles, 2 workgroups per CU)
-  const bool dense = env.gemm_dma && !halo && M >= env.dense_min_m && (g.ntaps == 1 || M <= 16384) && gemm_dma_eligible(g);
+  const bool dense = env.gemm_dma && !halo && M >= env.dense_min_m && (g.ntaps == 1 || M <= CONV3D_DMA_MAX_M) && gemm_dma_eligible(g);
   if (g.gn_partial && !dense) return mvd_fail("igemm_go: the statistics-only pass needs the LDS-DMA kernel");
   if (halo) return launch_planned(c, g, M, plan_halo(g, M, force_splitk), K_HALO, s, defer);
   if (dense) return launch_planned(c, g, M, plan_dense(g, M, force_splitk), K_DENSE, s, defer);
@@ -396,8 +414,10 @@ int run_upconv2d(mvd_ctx* c, const GemmArgs& ga_in, int B, int H, int W, hipStre
   return 0;
 }
 
-int run_conv3d(mvd_ctx* c, const GemmArgs& ga, int B, int D, int H, int W, int stride, hipStream_t s) {
-  IGemm g;
+namespace {
+
+// the descriptor of a 3-D convolution of stride 1 / 2 (1 or 27 taps): what run_conv3d launches and conv3d_routed_form asks about
+int conv3d_desc(IGemm& g, const GemmArgs& ga, int B, int D, int H, int W, int stride) {
   igemm_init(g);
   igemm_fill(g, ga);
   g.B = B;
@@ -416,7 +436,29 @@ int run_conv3d(mvd_ctx* c, const GemmArgs& ga, int B, int D, int H, int W, int s
   } else {
     return mvd_fail("run_conv3d: kernel must be 1 or 27 taps");
   }
+  return 0;
+}
+
+}  // namespace
+
+// form 0: igemm_go's choice of kernel; form 1: conv3z whatever the row count, an error where the kernel does not take the layer
+int run_conv3d(mvd_ctx* c, const GemmArgs& ga, int B, int D, int H, int W, int stride, hipStream_t s, int form) {
+  IGemm g;
+  RET_IF(conv3d_desc(g, ga, B, D, H, W, stride));
+  if (form == 1) {
+    if (!g.wx || !conv3z_eligible(g, g.wx_bn))
+      return mvd_fail("run_conv3d: form 1 (conv3z) takes 3x3x3 stride-1 layers of an fp16 source with Cin % 64 == 0, 64 or 128 output channels, H and W multiples of 16");
+    return go_conv3z(c, g, B * g.Z * g.Y * g.X, s);
+  }
+  if (form != 0) return mvd_fail("run_conv3d: form must be 0 or 1");
   return igemm_go(c, g, ga.force_splitk, s);
+}
+
+// the form igemm_go gives this layer (0: none of the forms above, 1: conv3z), from the descriptor alone: no device, no launch
+int conv3d_routed_form(const GemmArgs& ga, int B, int D, int H, int W, int stride) {
+  IGemm g;
+  if (conv3d_desc(g, ga, B, D, H, W, stride)) return -1;
+  return conv3z_routed(g, B * g.Z * g.Y * g.X, ga.force_splitk) ? 1 : 0;
 }
 
 // out[o] += in[i] * W[k] with o = 2 i - 1 + k  (ConvTranspose3d k3 s2 p1 op1).  For output parity p:

@@ -252,6 +252,20 @@ int build_sparse_layer(mvd_ctx* c, const std::string& p, const std::string& blk,
   return 0;
 }
 
+// A 3x3x3 stride-1 convolution of the two 3-D U-nets that conv3z takes (k_conv3x.hip: 64 or 128 output channels, Cin % 64 == 0)
+// also gets its weights as that kernel's fragment stream; igemm_go decides per launch (row count) whether it runs there.  Called
+// right behind the layer's pack_conv: the same build stream.  Inference contexts only: a training context re-packs every step, and
+// its forward stays on the kernels its gradient bounds were measured with (another summation order flips ReLU masks of the
+// DepthTransformers: tests/test_gpu_train.py).
+int pack_conv3z_stream(mvd_ctx* c, ConvW* w) {
+  const int bn = conv3z_stream_bn(w->taps, w->N, w->Cin);
+  if (!mvd_env().conv3x || !bn || w->xp || c->train_mode) return 0;
+  RET_IF(dmalloc(c, (void**)&w->wx, conv3z_stream_halfs(w->N, w->Cin, bn) * sizeof(half_t)));
+  RET_IF(conv3z_pack(w->w, w->N, w->Cin, bn, w->wx, c->bs));
+  w->wx_bn = bn;
+  return 0;
+}
+
 int build_frustum_block(mvd_ctx* c, const std::string& p, const char* norm_name, bool transposed, int stride,
                         FrustumBlockW* f) {
   RET_IF(pack_lin(c, p + "t_conv.weight", p + "t_conv.bias", &f->t_conv));
@@ -261,6 +275,7 @@ int build_frustum_block(mvd_ctx* c, const std::string& p, const char* norm_name,
   f->cin = f->conv.Cin;
   f->cout = f->conv.N;
   f->stride = stride;
+  if (!transposed && stride == 1) RET_IF(pack_conv3z_stream(c, &f->conv));
   return 0;
 }
 
@@ -951,6 +966,7 @@ int build_condnet_section(mvd_ctx* c) {
   }
   const std::string F = S + "frustum_volume_feats.";
   RET_IF(pack_conv(c, F + "conv0.weight", F + "conv0.bias", false, false, &c->fr_conv0));
+  RET_IF(pack_conv3z_stream(c, &c->fr_conv0));
   for (int i = 0; i < 6; ++i)
     RET_IF(build_frustum_block(c, F + "conv" + std::to_string(i + 1) + ".", "bn", false, (i % 2 == 0) ? 2 : 1,
                                &c->fr_blocks[i]));
@@ -1010,6 +1026,7 @@ int build_condnet_section(mvd_ctx* c) {
         SpatialBlockW& b = i < 10 ? c->sp_blocks[i] : c->sp_up[i - 10];
         RET_IF(load_norm(c, p + (i < 10 ? "bn" : "norm"), &b.gn));
         RET_IF(pack_conv(c, p + "conv.weight", p + "conv.bias", i >= 10, false, &b.conv));
+        if (i < 10 && i % 3 != 1) RET_IF(pack_conv3z_stream(c, &b.conv));  // the stride-1 blocks (blocks 1, 4 and 7 -- conv1, conv3, conv5 -- have stride 2)
         b.cin = b.conv.Cin;
         b.cout = b.conv.N;
         if (b.conv.taps != 27 || b.gn.C != b.cin) return mvd_fail("spatial_volume_feats: a block's conv / norm has an unexpected shape");

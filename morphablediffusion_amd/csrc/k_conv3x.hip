@@ -17,7 +17,9 @@
 //     four ds_write_b128 and stores full 128-byte row segments (bias, per-sample bias, fp32 residual as 16-byte loads).
 // Scope: fp16 channels-last input, 3x3 / stride 1 / pad 1, images of side % 16 == 0, Cin % 64 == 0, N % (32 NF) == 0, fp32 output
 // (or split-K partial slabs), no activation: the UNet's ResBlock convolutions at 32 x 32 and 16 x 16 (reference
-// ldm/modules/diffusionmodules/openaimodel.py:202-233).  Everything else stays on k_conv3.hip / k_gemm.hip.
+// ldm/modules/diffusionmodules/openaimodel.py:202-233).  The ZT instantiations ("conv3z", below) are the 3 x 3 x 3 stride-1 form of
+// the same kernel: 64 or 128 output channels, H and W multiples of 16, fp32 or 16-bit result, no split-K -- the wide levels of the
+// two 3-D U-nets.  Everything else stays on k_conv3.hip / k_gemm.hip / k_igemm.hip.
 #include "common.h"
 #include "igemm_epilogue.h"
 
@@ -47,7 +49,12 @@ __device__ __forceinline__ int halo_key(int hy, int hx) {
   else return ((hx >> 1) + 4 * (hy & 1)) & 7;
 }
 
-template <int NF, int IW>
+// ZT ("conv3z"): the 3 x 3 x 3 stride-1 convolution of a [B][Z][Y][X] volume as this 2-D kernel over the planes.  Output plane z is the
+// 3 x 3 convolution of [in[z - 1] | in[z] | in[z + 1]]: the depth taps are three times as many 64-channel chunks, chunk (kz, cc)
+// takes its halo from plane z + kz - 1 of the same sample (a plane outside the volume: every offset out of range -> zeros, the
+// padding) and the stream is packed [kz][cc] (conv3x_pack, nz = 3).  A tile is one 16 x 16 block of one plane; its 16-bit result
+// is written by the epilogue too.  No split-K, no per-sample bias.
+template <int NF, int IW, bool ZT = false>
 __global__ __launch_bounds__(256) void conv3x_kernel(const IGemm g, const half_t* __restrict__ wstream) {
 #if defined(__HIP_DEVICE_COMPILE__)
   using Geo = CxGeo<IW>;
@@ -68,7 +75,7 @@ __global__ __launch_bounds__(256) void conv3x_kernel(const IGemm g, const half_t
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int H = g.Y, W = g.X, N = g.N, Cin = g.Cin;
   const int bx_per = W / IW, by_per = H / IW, bpi = bx_per * by_per;  // image blocks per sample
-  const int nblocks = g.B * bpi;
+  const int nblocks = (ZT ? g.B * g.Z : g.B) * bpi;  // ZT: every plane is an image
   const int tiles_m = (nblocks + NI - 1) / NI, tiles_n = N / (32 * NF);
   int bid = blockIdx.x;
   {  // XCD-aware bijective remap: the column tiles of one pixel tile share an L2
@@ -89,7 +96,7 @@ __global__ __launch_bounds__(256) void conv3x_kernel(const IGemm g, const half_t
     y0 = by * IW;
     x0 = (brem - by * bx_per) * IW;
   };
-  const int ncc = Cin / 64;
+  const int ncc_in = Cin / 64, ncc = ZT ? 3 * ncc_in : ncc_in;
   int cc_beg = 0, cc_end = ncc;
   if (g.splitk > 1) {
     const int per = (ncc + g.splitk - 1) / g.splitk;
@@ -121,8 +128,20 @@ __global__ __launch_bounds__(256) void conv3x_kernel(const IGemm g, const half_t
     const unsigned pix = (unsigned)((b * H + y) * W + x);
     h_off[i] = ok ? (pix * (unsigned)g.lda + chunk * 8) * 2 : 0xFFFFFFFFu;
   }
-  auto dma_halo_piece = [&](int i, int cc, int buf) {
-    const unsigned off = h_off[i] == 0xFFFFFFFFu ? 0xFFFFFFFFu : h_off[i] + cc * 128;
+  // byte offset of chunk cc against the tile's own plane (a multiple of 16), or 0xFFFFFFFF: the chunk's plane is outside the volume
+  int zpl = 0;
+  if constexpr (ZT) zpl = (tm / bpi) % g.Z;
+  auto chunk_off = [&](int cc) -> unsigned {
+    if constexpr (ZT) {
+      const int kz = cc / ncc_in, ci = cc - kz * ncc_in;
+      if ((unsigned)(zpl + kz - 1) >= (unsigned)g.Z) return 0xFFFFFFFFu;
+      return (unsigned)(kz - 1) * (unsigned)(H * W * g.lda * 2) + (unsigned)ci * 128u;
+    } else {
+      return (unsigned)cc * 128u;
+    }
+  };
+  auto dma_halo_piece = [&](int i, unsigned coff, int buf) {
+    const unsigned off = (h_off[i] == 0xFFFFFFFFu || (ZT && coff == 0xFFFFFFFFu)) ? 0xFFFFFFFFu : h_off[i] + coff;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrcA, (lds_ptr)(sHalo + buf * CX_HALO_BYTES + h_grp[i] * 1024), 16, off, 0, 0, 0);
   };
   // weight pieces: quarter jq (global index from the first chunk of this workgroup) -> ring quarter jq & 3; piece i of this wave
@@ -155,7 +174,7 @@ __global__ __launch_bounds__(256) void conv3x_kernel(const IGemm g, const half_t
   if (nchunks > 0) {
     // start: halo of the first chunk, weight quarters 0..2 (quarter j + 3 is issued while quarter j is consumed)
 #pragma unroll
-    for (int i = 0; i < CX_HP; ++i) dma_halo_piece(i, cc_beg, 0);
+    for (int i = 0; i < CX_HP; ++i) dma_halo_piece(i, chunk_off(cc_beg), 0);
 #pragma unroll
     for (int jq = 0; jq < 3; ++jq)
 #pragma unroll
@@ -181,7 +200,7 @@ __global__ __launch_bounds__(256) void conv3x_kernel(const IGemm g, const half_t
     for (int c = 0; c < nchunks; ++c) {
       const int hbuf = c & 1;
       // the halo of the next chunk; behind the last chunk the same chunk is loaded again (unused): no branch, one wait count
-      const int cc_next = min(cc_beg + c + 1, ncc - 1);
+      const unsigned coff_next = chunk_off(min(cc_beg + c + 1, ncc - 1));
 #pragma unroll
       for (int s = 0; s < NSTEP; ++s) {
         const int qd = s / 3;  // quarter of this chunk
@@ -222,7 +241,7 @@ __global__ __launch_bounds__(256) void conv3x_kernel(const IGemm g, const half_t
 #endif
           if (qd >= 2 && qd < 2 + (CX_HP + 3) / 4 && pos >= PW && pos < PW + 4) {
             const int hi = (qd - 2) * 4 + (pos - PW);
-            if (hi < CX_HP) dma_halo_piece(hi, cc_next, hbuf ^ 1);
+            if (hi < CX_HP) dma_halo_piece(hi, coff_next, hbuf ^ 1);
           }
           const h8 a = wq[i & 3];
 #ifdef CX_EXP_NOLDSW
@@ -314,6 +333,14 @@ __global__ __launch_bounds__(256) void conv3x_kernel(const IGemm g, const half_t
 #endif
           v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
         }
+        if constexpr (ZT) {
+          if (!g.out_f32) {
+            h4 o;
+            o[0] = (half_t)v.x; o[1] = (half_t)v.y; o[2] = (half_t)v.z; o[3] = (half_t)v.w;
+            *(h4*)((half_t*)g.out + row4[p][i] * g.ldc + n) = o;
+            continue;
+          }
+        }
         *(float4*)((float*)g.out + row4[p][i] * g.ldc + n) = v;
       }
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the scratch is rewritten by the next block
@@ -322,19 +349,20 @@ __global__ __launch_bounds__(256) void conv3x_kernel(const IGemm g, const half_t
 #endif
 }
 
-// packed fp16 weights [9][N][Cin] (ConvW::w) -> per column tile [chunk][tap][k step][row block] fragments, fragment-major
-__global__ void conv3x_pack_kernel(const half_t* __restrict__ w, int N, int Cin, int NF, half_t* __restrict__ out, long nfrag) {
+// packed fp16 weights [9 nz][N][Cin] (ConvW::w) -> per column tile [chunk][tap][k step][row block] fragments, fragment-major;
+// nz = 3 (conv3z): chunk = (depth tap kz, 64-channel chunk), taps kz * 9 + tap of the 27
+__global__ void conv3x_pack_kernel(const half_t* __restrict__ w, int N, int Cin, int NF, int nz, half_t* __restrict__ out, long nfrag) {
   const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (gid >= nfrag * 64) return;
   const long q = gid >> 6;
   const int l = (int)(gid & 63), h = l >> 5, r32 = l & 31;
-  const int ncc = Cin / 64, per_tile = ncc * 36 * NF;
+  const int ncc = Cin / 64, per_tile = nz * ncc * 36 * NF;
   const int tn = (int)(q / per_tile);
   int r = (int)(q - (long)tn * per_tile);
-  const int cc = r / (36 * NF);
-  r -= cc * 36 * NF;
+  const int vc = r / (36 * NF), kz = vc / ncc, cc = vc - kz * ncc;
+  r -= vc * 36 * NF;
   const int step = r / NF, f = r - step * NF;
-  const int tap = step >> 2, kk = step & 3;
+  const int tap = kz * 9 + (step >> 2), kk = step & 3;
   const int n = tn * 32 * NF + 32 * f + r32;
   h8 o = *(const h8*)(w + ((long)tap * N + n) * Cin + 64 * cc + 16 * kk + 8 * h);
   *(h8*)(out + gid * 8) = o;
@@ -356,6 +384,24 @@ int launch_cx(const IGemm& g, const half_t* stream, hipStream_t s) {
   const int tiles_m = cdiv(g.B * (g.Y / IW) * (g.X / IW), NI);
   gl.xcd_cols = mvd_env().xcd_cols && xcd_prefers_cols(tiles_m, g.N / (32 * NF), (double)tiles_m * CxGeo<IW>::ROWS * g.Cin * 2, 9.0 * g.N * g.Cin * 2);
   hipLaunchKernelGGL((conv3x_kernel<NF, IW>), grid, dim3(256), LDS, s, gl, stream);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+
+template <int NF>
+int launch_cz(const IGemm& g, const half_t* stream, hipStream_t s) {
+  constexpr int LDS = 2 * CxGeo<16>::BYTES + 4 * 3 * NF * 1024;
+  static_assert(LDS <= 160 * 1024 && 4 * EPI_WAVE_BYTES <= LDS, "LDS budget");
+  static bool attr_done[MVD_MAX_DEVICES] = {false};
+  bool& attr_set = attr_done[mvd_current_device()];
+  if (!attr_set) {
+    HIP_CHECK_RET(hipFuncSetAttribute((const void*)conv3x_kernel<NF, 16, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+    attr_set = true;
+  }
+  IGemm gl = g;
+  gl.xcd_cols = 0;  // the whole stream is a few hundred KB: every L2 holds it beside the planes of its tiles
+  gl.splitk = 1;
+  hipLaunchKernelGGL((conv3x_kernel<NF, 16, true>), dim3(g.B * g.Z * (g.Y / 16) * (g.X / 16) * (g.N / (32 * NF))), dim3(256), LDS, s, gl, stream);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }
@@ -384,7 +430,7 @@ int conv3x_pack(const half_t* w, int N, int Cin, int bn, half_t* stream, hipStre
   const int nf = bn / 32;
   const long nfrag = (long)(N / bn) * (Cin / 64) * 36 * nf;
   HIP_CHECK_RET(hipMemsetAsync(stream + nfrag * 512, 0, (size_t)4 * 3 * nf * 1024, s));
-  hipLaunchKernelGGL(conv3x_pack_kernel, dim3((unsigned)((nfrag * 64 + 255) / 256)), dim3(256), 0, s, w, N, Cin, nf, stream, nfrag);
+  hipLaunchKernelGGL(conv3x_pack_kernel, dim3((unsigned)((nfrag * 64 + 255) / 256)), dim3(256), 0, s, w, N, Cin, nf, 1, stream, nfrag);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }
@@ -394,4 +440,38 @@ int launch_conv3x(const IGemm& g, const half_t* stream, int bn, hipStream_t s) {
   if ((long)(g.N / bn) * (g.Cin / 64) * 36 * (bn / 32) * 1024 >= 0xFFFFFF00L) return mvd_fail("conv3x: weight stream exceeds 4 GiB");
   if (g.X == 8) return bn == 160 ? launch_cx<5, 8>(g, stream, s) : launch_cx<4, 8>(g, stream, s);
   return bn == 160 ? launch_cx<5, 16>(g, stream, s) : launch_cx<4, 16>(g, stream, s);
+}
+
+// conv3z: the 3 x 3 x 3 stride-1 form (see conv3x_kernel, ZT).  Hard limits only: what a launch needs to be correct; igemm_go adds the row
+// floor below which the LDS-DMA tap gather stays the faster kernel.  bn: 64 or 128, the column tile the stream was packed for.
+bool conv3z_eligible(const IGemm& g, int bn) {
+  if (g.a_f32 || g.ntaps != 27 || g.sz != 1 || g.sy != 1 || g.sx != 1 || g.ups || g.geglu || !g.out_linear || g.npar > 0) return false;
+  for (int t = 0; t < 27; ++t)
+    if (g.tap[t] != igemm_tap(t / 9 - 1, (t / 3) % 3 - 1, t % 3 - 1, t)) return false;
+  if (g.Cin % 64 || (bn != 64 && bn != 128) || (g.N != 64 && g.N != 128) || g.N % bn) return false;
+  if (g.Z != g.IZ || g.Y != g.IY || g.X != g.IX || g.Z != g.PZ || g.Y != g.PY || g.X != g.PX) return false;
+  if (g.Y % 16 || g.X % 16) return false;
+  if (g.act != ACT_NONE || g.alpha != 1.0f || g.out_split || g.rowscale || g.rowbias || g.gn_partial) return false;
+  if ((g.lda & 7) || (g.ldc & 3) || (g.resid && (!g.resid_f32 || (g.ldr & 3)))) return false;
+  if ((long)g.B * g.Z * g.Y * g.X * g.lda * 2 >= 0xFFFFFF00L) return false;  // 32-bit buffer offsets
+  return true;
+}
+int conv3z_stream_bn(int taps, int N, int Cin) { return taps == 27 && Cin > 0 && Cin % 64 == 0 && (N == 64 || N == 128) ? N : 0; }
+size_t conv3z_stream_halfs(int N, int Cin, int bn) {
+  const size_t nf = bn / 32;  // as conv3x_stream_halfs, three times the chunks
+  return ((size_t)(N / bn) * 3 * (Cin / 64) * 36 * nf + 4 * 3 * nf) * 512;
+}
+int conv3z_pack(const half_t* w, int N, int Cin, int bn, half_t* stream, hipStream_t s) {
+  if (Cin % 64 || (bn != 64 && bn != 128) || N % bn) return mvd_fail("conv3z_pack: unsupported shape");
+  const int nf = bn / 32;
+  const long nfrag = (long)(N / bn) * 3 * (Cin / 64) * 36 * nf;
+  HIP_CHECK_RET(hipMemsetAsync(stream + nfrag * 512, 0, (size_t)4 * 3 * nf * 1024, s));
+  hipLaunchKernelGGL(conv3x_pack_kernel, dim3((unsigned)((nfrag * 64 + 255) / 256)), dim3(256), 0, s, w, N, Cin, nf, 3, stream, nfrag);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+int launch_conv3z(const IGemm& g, const half_t* stream, int bn, hipStream_t s) {
+  if (!conv3z_eligible(g, bn)) return mvd_fail("conv3z: shape not supported");
+  if ((long)(g.N / bn) * 3 * (g.Cin / 64) * 36 * (bn / 32) * 1024 >= 0xFFFFFF00L) return mvd_fail("conv3z: weight stream exceeds 4 GiB");
+  return bn == 64 ? launch_cz<2>(g, stream, s) : launch_cz<4>(g, stream, s);
 }

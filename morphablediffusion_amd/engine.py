@@ -1584,8 +1584,8 @@ class Engine:
         return res
 
     def op_conv3d_ex(self, x, w, bias=None, stride=1, transposed=False, use_bias=True, resid=None, ldr=0, in_place=False,
-                     out_f16=False, ldc=0, a_half=True, force_splitk=0, poison=True):
-        """mvd_op_conv3d_ex: x [B,Cin,D,H,W], w [Cout,Cin,3,3,3] ([Cin,Cout,3,3,3] transposed), resid [B,Cout,Do,Ho,Wo] (reference
+                     out_f16=False, ldc=0, a_half=True, force_splitk=0, poison=True, form=None):
+        """mvd_op_conv3d_ex (form None) / mvd_op_conv3d_form: x [B,Cin,D,H,W], w [Cout,Cin,3,3,3] ([Cin,Cout,3,3,3] transposed), resid [B,Cout,Do,Ho,Wo] (reference
         layouts; the hook's channels-last images are made here) -> a namespace with .out (fp32 [B,Cout,Do,Ho,Wo]) and .raw (the
         result rows [rows][Cout] as written, fp32 or the library's 16-bit type).  The guard row and the pad columns of the result
         buffer are asserted unchanged."""
@@ -1604,12 +1604,21 @@ class Engine:
             r[:, :Cout] = _f32(resid, dev).permute(0, 2, 3, 4, 1).reshape(rows, Cout)
         ldc = ldc or Cout
         out = self._guarded(rows, ldc, f32=not out_f16)
-        L.check(self.lib.mvd_op_conv3d_ex(self._ctx, L.ptr(xl), B, D, H, W, Cin, L.ptr(w), L.ptr(b), Cout, stride, bool(transposed),
-                                          bool(use_bias and b is not None), L.ptr(r), ldr or 0, bool(in_place), bool(out_f16), ldc,
-                                          bool(a_half), force_splitk, bool(poison), L.ptr(out), _stream()))
+        head = (self._ctx, L.ptr(xl), B, D, H, W, Cin, L.ptr(w), L.ptr(b), Cout, stride, bool(transposed),
+                bool(use_bias and b is not None), L.ptr(r), ldr or 0, bool(in_place), bool(out_f16), ldc, bool(a_half), force_splitk)
+        tail = (bool(poison), L.ptr(out), _stream())
+        if form is None:
+            L.check(self.lib.mvd_op_conv3d_ex(*head, *tail))
+        else:
+            L.check(self.lib.mvd_op_conv3d_form(*head, int(form), *tail))
         self._guard_intact(out, rows, Cout, "op_conv3d_ex")
         raw = out[:rows, :Cout]
         return types.SimpleNamespace(raw=raw, out=raw.float().reshape(B, *od, Cout).permute(0, 4, 1, 2, 3).contiguous())
+
+    def op_conv3d_form(self, x, w, form, **kw):
+        """mvd_op_conv3d_form: op_conv3d_ex on the kernel form the caller names (0: the engine's routing, 1: conv3z, the plane-halo
+        kernel of the 3x3x3 stride-1 layers); a layer outside the form's limits raises MvdError"""
+        return self.op_conv3d_ex(x, w, form=form, **kw)
 
     def op_group_norm_ex(self, x, groups, gamma, beta, eps=1e-5, act=0, form=0, ld=0, preadd=None, pld=0, split=0, bias2=None,
                          resid=None, ldr=0, mat=False, ldm=0, ldo=0, poison=True):

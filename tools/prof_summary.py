@@ -44,6 +44,9 @@ def family(name):
                 return f"gemm_dma_kernel<128x{a[1]}>" if a[0] == "128" else f"gemm_dma_kernel<{a[1]},{a[2]}>"
             a = a[:2]
         return f"{m.group(1)}<{','.join(a)}>"
+    m = re.search(r"conv3x_kernelILi(\d+)ELi16ELb1E", name) or re.search(r"conv3x_kernel<\s*(\d+)\s*,\s*16\s*,\s*true", name)
+    if m:  # the depth-tap instantiation (ZT) of the kernel: the engine books it as conv3z_kernel<NF>
+        return f"conv3z_kernel<{m.group(1)}>"
     m = re.search(r"conv3x_kernelILi(\d+)E", name) or re.search(r"conv3x_kernel<\s*(\d+)", name)
     if m:  # mangled or demangled; the engine books conv3x_kernel<NF> for both tile geometries
         return f"conv3x_kernel<{m.group(1)}>"
@@ -95,7 +98,7 @@ if json_out:
     import os
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from morphablediffusion_amd.lib import csrc_sha16
-    json.dump({"source": "rocprofv3 --kernel-trace --stats over bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-extras: TotalDurationNs / Calls "
+    json.dump({"source": f"rocprofv3 --kernel-trace --stats over bench.py --steps {bench['steps']} --warmup {bench['warmup']} --full --no-cpu-baseline --no-extras: TotalDurationNs / Calls "
                          "per kernel family (kernel begin to end, no launch path)",
                "config": bench.get("config", {}).get("name"), "csrc_sha16": csrc_sha16(),
                "us_per_launch": {f: fam_t[f] / fam_n[f] / 1e3 for f in fam_t}, "launches_per_step": {f: fam_n[f] / steps for f in fam_t},
