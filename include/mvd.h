@@ -617,13 +617,15 @@ int mvd_denoise_views_ms(mvd_ctx* ctx, int B, const int* slots, const float* x_n
  * the section is a test or bench hook: csrc/c_api_hooks.hip, and for the backward, adjoint and gather hooks (which call the
  * training step's file-local functions) the end of csrc/engine_train.hip, both on the scaffold of csrc/hooks.h.  Every hook
  * that takes a context refuses a NULL one ("null context") before it touches anything.  The hooks come in two kinds:
- *   asynchronous   mvd_op_conv, mvd_op_conv3d, mvd_op_linear, mvd_op_group_norm, mvd_op_depth_attn, mvd_op_group_norm_bwd,
- *                  mvd_op_layer_norm_bwd, mvd_op_conv_bwd, mvd_op_linear_bwd, mvd_op_conv3d_bwd, mvd_op_tgemm and the adjoint /
- *                  gather hooks (mvd_op_*_adjoint, mvd_op_*_gather): they enqueue on `stream` and return without synchronising
- *                  it, so they can run beside work on another stream (tests/test_gpu_determinism.py, tools/race_micro.py);
- *                  their scratch is the context's workspace, which the stream's order protects.
- *   synchronous    every *_ex hook, mvd_op_layer_norm_slabs, mvd_op_folded_group_norm, mvd_op_softmax_rows, mvd_op_rows_split,
- *                  the context-free sparse-CNN and mvd_op_train_* hooks, and the timing hooks (mvd_bench_*, mvd_op_st_tail /
+ *   asynchronous   mvd_op_conv, mvd_op_conv3d, mvd_op_linear, mvd_op_group_norm, mvd_op_depth_attn, mvd_op_conv_bwd,
+ *                  mvd_op_linear_bwd, mvd_op_conv3d_bwd, mvd_op_tgemm and the adjoint / gather hooks (mvd_op_*_adjoint,
+ *                  mvd_op_*_gather): they enqueue on `stream` and return without synchronising it, so they can run beside work
+ *                  on another stream (tests/test_gpu_determinism.py, tools/race_micro.py); their scratch is the context's
+ *                  workspace, which the stream's order protects.
+ *   synchronous    every *_ex hook (and mvd_op_group_norm_bwd / mvd_op_layer_norm_bwd, which are calls of theirs),
+ *                  mvd_op_group_norm_fwd32, mvd_op_layer_norm_slabs, mvd_op_folded_group_norm, mvd_op_softmax_rows,
+ *                  mvd_op_rows_split, the context-free sparse-CNN hooks, the mvd_op_train_* hooks (context-free but for
+ *                  mvd_op_train_colsum / _sum_rows / _outer_add), and the timing hooks (mvd_bench_*, mvd_op_st_tail /
  *                  mvd_op_st_head with iters > 0): the stream is synchronised before the call returns.  The *_ex kind also checks
  *                  its arguments before anything is launched and writes into caller buffers that carry guard rows. */
 /* The update kernel of mvd_denoise_views_ms on its own, over n device floats: eps = eps_u + scale (eps_c - eps_u) (eps_u NULL:
@@ -708,12 +710,49 @@ int mvd_op_depth_attn(mvd_ctx* ctx, const float* qk, const float* context, const
 int mvd_op_conv3d(mvd_ctx* ctx, const float* x_ncdhw, int B, int Cin, int D, int H, int W, const float* w,
                   const float* bias, int Cout, int stride, int transposed, const float* resid, float* out, void* stream);
 /* backward-kernel hooks used by tests/test_gpu_train_ops.py (each is compared with torch.autograd of the same op): GroupNorm
- * (+ SiLU / ReLU) backward and LayerNorm backward on channels-last fp32 ([B,rows,C] / [rows,C]).  (The self-attention backward
- * is mvd_op_attention_bwd_ex below.) */
+ * (+ SiLU / ReLU) backward and LayerNorm backward on channels-last fp32 ([B,rows,C] / [rows,C]): mvd_op_group_norm_bwd_ex /
+ * mvd_op_layer_norm_bwd_ex below with dense rows, eps 1e-5 (LayerNorm), no pre-add, and dx / dgamma / dbeta WRITTEN.
+ * MVD_GN_BWD_ONE_BLOCK picks form 1.  (The self-attention backward is mvd_op_attention_bwd_ex below.) */
 int mvd_op_group_norm_bwd(mvd_ctx* ctx, const float* x, const float* dy, int B, int rows, int C, int groups, const float* gamma,
                           const float* beta, float eps, int act, float* dx, float* dgamma, float* dbeta, void* stream);
 int mvd_op_layer_norm_bwd(mvd_ctx* ctx, const float* x, const float* dy, int rows, int C, const float* gamma, float* dx,
                           float* dgamma, float* dbeta, void* stream);
+/* The training backward's norms and row reductions (csrc/k_bwd.hip) in every form the training step launches them in
+ * (tests/test_gpu_norm_bwd_ops.py), through the step's own gn_backward / ln_backward / gn_forward32 (csrc/engine_train.hip).  All
+ * operands are fp32 device buffers; a bad argument, or a shape the launcher refuses, returns non-zero before anything is
+ * launched.  The caller presets every result buffer to 0xFF bytes with one guard row behind it (and pad columns where a stride
+ * exceeds the width) -- or, where the result is added to, its body to the values to start from; the production launch writes into
+ * them directly.  poison != 0 fills the free workspace (slab partials, per-slab channel sums) with 0xFF bytes first.
+ *
+ * mvd_op_group_norm_bwd_ex: x [B][rows][ld] the norm's input, pre [B][pld] (may be NULL) the per-sample pre-add of the forward
+ * (FiLM), dy [B][rows][ldy] the gradient of act(gamma xhat + beta), act 0 none / 1 SiLU / 2 ReLU.  form 0: the slabbed kernels with
+ * S_force (1..64) row slabs per (sample, group), 0 = the plan of bwd_gn_slabs; form 1: one workgroup per (sample, group).
+ * dx [B][rows][lddx] is written, or added to with accum != 0; dgamma / dbeta [C] are always ADDED to, as the gradient arena is
+ * (two-job bwd_sum_rows_multi over the B * S partial rows); dpre [B][ldp] (may be NULL) receives the per-sample column sums of dx
+ * (bwd_colsum_samples over the S slab rows), columns C .. ldp - 1 are not touched.  *S_used (may be NULL): the slab count.
+ * mvd_op_group_norm_fwd32: the fp32 forward of the DepthTransformer's re-computation, y [B][rows][ldy] = act(GroupNorm(x)).
+ * mvd_op_layer_norm_bwd_ex: x [rows][ld], dy [rows][ldy], C <= 1280; dx [rows][lddx] written or added to, dgamma / dbeta ADDED to
+ * (partials of [nblk][2][C], two-job sum with a row stride of 2 C); *nblk_used (may be NULL): the partial rows. */
+int mvd_op_group_norm_bwd_ex(mvd_ctx* ctx, const float* x, int ld, const float* pre, int pld, const float* dy, int ldy, int B, int rows,
+                             int C, int groups, const float* gamma, const float* beta, float eps, int act, int form, int S_force,
+                             float* dx, int lddx, int accum, float* dgamma, float* dbeta, float* dpre, int ldp, int poison,
+                             int* S_used, void* stream);
+int mvd_op_group_norm_fwd32(mvd_ctx* ctx, const float* x, int ld, int B, int rows, int C, int groups, const float* gamma,
+                            const float* beta, float eps, int act, int S_force, float* y, int ldy, int poison, int* S_used,
+                            void* stream);
+int mvd_op_layer_norm_bwd_ex(mvd_ctx* ctx, const float* x, int ld, const float* dy, int ldy, int rows, int C, const float* gamma,
+                             float eps, float* dx, int lddx, int accum, float* dgamma, float* dbeta, int poison, int* nblk_used,
+                             void* stream);
+/* The reductions, one launch each.  mvd_op_train_colsum (bwd_colsum_samples): out[b][c] = sum over the rows of sample b of
+ * v [B][rows][ld], c < C, out rows ldo apart; src_f16: v is rounded to the library's 16-bit type first and the 16-bit kernel runs.
+ * mvd_op_train_sum_rows (bwd_sum_rows_multi): n = 1..4 jobs in one launch, out[k][c] (+)= sum_{r < R[k]} part[k][r * ldp[k] + c]
+ * for c < C[k]; the arrays are host arrays, their pointers device pointers.  mvd_op_train_outer_add (bwd_outer_add):
+ * out [M][N] += sum_{k < K} a[k][m] b[k][n], a [K][lda], b [K][ldb]. */
+int mvd_op_train_colsum(mvd_ctx* ctx, const float* v, int src_f16, int ld, int B, int rows, int C, float* out, int ldo, void* stream);
+int mvd_op_train_sum_rows(mvd_ctx* ctx, int n, const float* const* part, const int* R, const int* C, const long* ldp, float* const* out,
+                          const int* accum, void* stream);
+int mvd_op_train_outer_add(mvd_ctx* ctx, const float* a, int lda, const float* b, int ldb, float* out, int M, int N, int K,
+                           void* stream);
 /* Adjoints of the training step's convolutions, Linears and GEMMs (csrc/engine_train.hip), one layer at a time on the production
  * code: the engine's forward pack of w (xp != 0: the extended-precision [w_hi | w_hi | w_lo] layout), the adjoint pack built as at
  * finalize, then the backward functions the training step calls.  Activations are channels-last fp32 device buffers; an input

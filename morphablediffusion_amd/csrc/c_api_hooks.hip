@@ -335,40 +335,37 @@ int mvd_op_depth_attn(mvd_ctx* c, const float* qk, const float* context, const f
   return 0;
 }
 
-// backward-kernel hooks of the two norms (tests/test_gpu_train_ops.py): each against torch.autograd of the same op
-// x, dy, dx: [B, rows, C] channels-last
-int mvd_op_group_norm_bwd(mvd_ctx* c, const float* x, const float* dy, int B, int rows, int C, int groups, const float* gamma,
-                          const float* beta, float eps, int act, float* dx, float* dgamma, float* dbeta, void* stream) {
+// The training backward's reductions one launch at a time (tests/test_gpu_norm_bwd_ops.py); the norm hooks themselves are at the end
+// of engine_train.hip.  Result buffers are the caller's (0xFF presets, guard rows), arguments are checked before any launch.
+int mvd_op_train_colsum(mvd_ctx* c, const float* v, int src_f16, int ld, int B, int rows, int C, float* out, int ldo, void* stream) {
   RET_IF(hook_begin(c));
+  if (!v || !out || B <= 0 || rows <= 0 || C <= 0 || ld < C || ldo < C) return mvd_fail("op_train_colsum: bad argument");
   hipStream_t s = S(stream);
   WsScope ws_scope(c);
-  // the slabbed form the training step uses; MVD_GN_BWD_ONE_BLOCK=1: the one-workgroup-per-(sample, group) kernel
-  const bool one_block = mvd_env().gn_bwd_one_block;
-  const int S = one_block ? 1 : bwd_gn_slabs(B, groups, rows);
-  float* dg = ws_alloc<float>(c, (size_t)B * S * C);
-  float* db = ws_alloc<float>(c, (size_t)B * S * C);
-  float* part = ws_alloc<float>(c, (size_t)B * groups * S * 4);
-  WS_CHECK(dg && db && part);
-  if (one_block)
-    RET_IF(bwd_group_norm(x, C, nullptr, 0, dy, C, B, rows, C, groups, gamma, beta, eps, act, dx, C, 0, dg, db, nullptr, s));
-  else
-    RET_IF(bwd_group_norm_slab(x, C, nullptr, 0, dy, C, B, rows, C, groups, gamma, beta, eps, act, dx, C, 0, part,
-                               part + (size_t)B * groups * S * 2, dg, db, nullptr, S, s));
-  RET_IF(bwd_sum_rows_add(dg, B * S, C, C, dgamma, 0, s));
-  return bwd_sum_rows_add(db, B * S, C, C, dbeta, 0, s);
+  const void* src = v;
+  if (src_f16) {
+    const half_t* h;
+    RET_IF(hook_f16(c, v, (size_t)B * rows * ld, &h, s));
+    src = h;
+  }
+  return hook_sync("op_train_colsum", s, bwd_colsum_samples(src, src_f16 ? 0 : 1, ld, B, rows, C, out, ldo, s));
 }
 
-int mvd_op_layer_norm_bwd(mvd_ctx* c, const float* x, const float* dy, int rows, int C, const float* gamma, float* dx, float* dgamma,
-                          float* dbeta, void* stream) {
+int mvd_op_train_sum_rows(mvd_ctx* c, int n, const float* const* part, const int* R, const int* C, const long* ldp, float* const* out,
+                          const int* accum, void* stream) {
   RET_IF(hook_begin(c));
+  if (!part || !R || !C || !ldp || !out || !accum) return mvd_fail("op_train_sum_rows: bad argument");
+  for (int k = 0; k < n && k < 4; ++k)
+    if (!part[k] || !out[k] || R[k] <= 0 || C[k] <= 0 || ldp[k] < C[k]) return mvd_fail("op_train_sum_rows: bad argument");
   hipStream_t s = S(stream);
-  WsScope ws_scope(c);
-  float* part = ws_alloc<float>(c, (size_t)bwd_ln_max_blocks() * 2 * C);
-  WS_CHECK(part);
-  int nb = 0;
-  RET_IF(bwd_layer_norm(x, C, dy, C, rows, C, gamma, 1e-5f, dx, C, 0, part, &nb, s));
-  RET_IF(bwd_sum_rows_add(part, nb, C, 2 * C, dgamma, 0, s));
-  return bwd_sum_rows_add(part + C, nb, C, 2 * C, dbeta, 0, s);
+  return hook_sync("op_train_sum_rows", s, bwd_sum_rows_multi(n, part, R, C, ldp, out, accum, s));
+}
+
+int mvd_op_train_outer_add(mvd_ctx* c, const float* a, int lda, const float* b, int ldb, float* out, int M, int N, int K, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!a || !b || !out || M <= 0 || N <= 0 || K <= 0 || lda < M || ldb < N) return mvd_fail("op_train_outer_add: bad argument");
+  hipStream_t s = S(stream);
+  return hook_sync("op_train_outer_add", s, bwd_outer_add(a, lda, b, ldb, out, M, N, K, s));
 }
 
 int mvd_bench_conv(mvd_ctx* c, int B, int C, int H, int W, int Cout, int iters, float* ms_out, void* stream) {

@@ -336,38 +336,49 @@ int sum_pair(Bwd& b, const float* pw, const float* pb, int R, int C, long ldp, f
 }
 // GroupNorm backward incl. its gain / bias gradients (slabbed: B * G * S workgroups)
 // pre / pld: the per-sample pre-add of the forward norm (FiLM); dpre [B][ldp] (may be null) receives its gradient
+// S_force (0: the plan of bwd_gn_slabs), one_block (gn_bwd_kernel: one workgroup per (sample, group), S = 1), S_used: the per-op
+// hook's handles on the launch (mvd_op_group_norm_bwd_ex); the training step leaves them at their defaults
 int gn_backward(Bwd& b, const NormW& n, int groups, float eps, int act, const float* x, long ld, const float* dy, long ldy, int rows_ps,
-                float* dx, long lddx, bool accum, const float* pre = nullptr, int pld = 0, float* dpre = nullptr, long ldp = 0) {
+                float* dx, long lddx, bool accum, const float* pre = nullptr, int pld = 0, float* dpre = nullptr, long ldp = 0,
+                int S_force = 0, bool one_block = false, int* S_used = nullptr) {
   mvd_ctx* c = b.c;
   WsScope scope(c, WS_TEMP);
-  const int S = bwd_gn_slabs(b.B, groups, rows_ps);
+  const int S = one_block ? 1 : (S_force > 0 ? S_force : bwd_gn_slabs(b.B, groups, rows_ps));
+  if (S_used) *S_used = S;
   float* dg = ws_alloc<float>(c, (size_t)b.B * S * n.C);
   float* db = ws_alloc<float>(c, (size_t)b.B * S * n.C);
   float* dp = dpre ? ws_alloc<float>(c, (size_t)b.B * S * n.C) : nullptr;
   float* part = ws_alloc<float>(c, (size_t)b.B * groups * S * 4);
   WS_CHECK(dg && db && part && (dp || !dpre));
-  RET_IF(bwd_group_norm_slab(x, ld, pre, pld, dy, ldy, b.B, rows_ps, n.C, groups, n.g, n.b, eps, act, dx, lddx, accum ? 1 : 0, part,
-                             part + (size_t)b.B * groups * S * 2, dg, db, dp, S, b.s));
+  if (one_block)
+    RET_IF(bwd_group_norm(x, ld, pre, pld, dy, ldy, b.B, rows_ps, n.C, groups, n.g, n.b, eps, act, dx, lddx, accum ? 1 : 0, dg, db, dp, b.s));
+  else
+    RET_IF(bwd_group_norm_slab(x, ld, pre, pld, dy, ldy, b.B, rows_ps, n.C, groups, n.g, n.b, eps, act, dx, lddx, accum ? 1 : 0, part,
+                               part + (size_t)b.B * groups * S * 2, dg, db, dp, S, b.s));
   RET_IF(sum_pair(b, dg, db, b.B * S, n.C, n.C, engine_grad(c, n.key + ".weight"), engine_grad(c, n.key + ".bias")));
   if (dpre) RET_IF(bwd_colsum_samples(dp, 1, n.C, b.B, S, n.C, dpre, ldp, b.s));  // per sample: its S slab rows
   return 0;
 }
-// GroupNorm forward in fp32 for the DepthTransformer re-computation
-int gn_forward32(Bwd& b, const float* x, int rows_ps, int C, int G, const float* gamma, const float* beta, int act, float* y) {
+// GroupNorm forward in fp32 for the DepthTransformer re-computation (the arguments after y: the per-op hook's, as above)
+int gn_forward32(Bwd& b, const float* x, int rows_ps, int C, int G, const float* gamma, const float* beta, int act, float* y, long ld = 0,
+                 long ldy = 0, float eps = 1e-5f, int S_force = 0, int* S_used = nullptr) {
   mvd_ctx* c = b.c;
   WsScope scope(c, WS_TEMP);
-  const int S = bwd_gn_slabs(b.B, G, rows_ps);
+  const int S = S_force > 0 ? S_force : bwd_gn_slabs(b.B, G, rows_ps);
+  if (S_used) *S_used = S;
   float* part = ws_alloc<float>(c, (size_t)b.B * G * S * 2);
   WS_CHECK(part);
-  return bwd_group_norm_fwd(x, C, b.B, rows_ps, C, G, gamma, beta, 1e-5f, act, y, C, part, S, b.s);
+  return bwd_group_norm_fwd(x, ld ? ld : C, b.B, rows_ps, C, G, gamma, beta, eps, act, y, ldy ? ldy : C, part, S, b.s);
 }
-int ln_backward(Bwd& b, const NormW& n, const float* x, long ld, const float* dy, long ldy, int rows, float* dx, long lddx, bool accum) {
+int ln_backward(Bwd& b, const NormW& n, const float* x, long ld, const float* dy, long ldy, int rows, float* dx, long lddx, bool accum,
+                float eps = 1e-5f, int* nblk_used = nullptr) {
   mvd_ctx* c = b.c;
   WsScope scope(c, WS_TEMP);
   float* part = ws_alloc<float>(c, (size_t)bwd_ln_max_blocks() * 2 * n.C);
   WS_CHECK(part);
   int nblk = 0;
-  RET_IF(bwd_layer_norm(x, ld, dy, ldy, rows, n.C, n.g, 1e-5f, dx, lddx, accum ? 1 : 0, part, &nblk, b.s));
+  RET_IF(bwd_layer_norm(x, ld, dy, ldy, rows, n.C, n.g, eps, dx, lddx, accum ? 1 : 0, part, &nblk, b.s));
+  if (nblk_used) *nblk_used = nblk;
   return sum_pair(b, part, part + n.C, nblk, n.C, 2 * n.C, engine_grad(c, n.key + ".weight"), engine_grad(c, n.key + ".bias"));
 }
 
@@ -1709,6 +1720,85 @@ int mvd_op_tgemm(mvd_ctx* c, int M, int N, int K, const float* a, int a_f16, int
   }
   if (poison) RET_IF(hook_poison(c, s));
   return tgemm(c, A, Bm, out, ldc, M, N, K, accum != 0, s, xp != 0);
+}
+
+// The two norms' backward and the fp32 GroupNorm forward in every form the training step launches them in
+// (tests/test_gpu_norm_bwd_ops.py): gn_backward / ln_backward / gn_forward32 themselves, their gain / bias gradients booked
+// under the hook keys.  Result buffers are the caller's (0xFF presets, guard rows); arguments are checked before any launch.
+namespace {
+const char* const kHookNorm = "hook";  // kHookNorm + ".weight" / ".bias" are kHookW / kHookB
+bool gn_args_bad(const float* x, int ld, int B, int rows, int C, int groups, const float* gamma, const float* beta, int act, int S_force) {
+  return !x || !gamma || !beta || B <= 0 || rows <= 0 || C <= 0 || groups <= 0 || ld < C || act < 0 || act > 2 || S_force < 0 || S_force > 64;
+}
+}  // namespace
+
+int mvd_op_group_norm_bwd_ex(mvd_ctx* c, const float* x, int ld, const float* pre, int pld, const float* dy, int ldy, int B, int rows, int C,
+                             int groups, const float* gamma, const float* beta, float eps, int act, int form, int S_force, float* dx,
+                             int lddx, int accum, float* dgamma, float* dbeta, float* dpre, int ldp, int poison, int* S_used,
+                             void* stream) {
+  RET_IF(hook_begin(c));
+  if (gn_args_bad(x, ld, B, rows, C, groups, gamma, beta, act, S_force) || !dy || !dx || !dgamma || !dbeta || ldy < C || lddx < C ||
+      form < 0 || form > 1 || (pre && pld < C) || (dpre && ldp < C) || !(eps > 0.f))
+    return mvd_fail("op_group_norm_bwd_ex: bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  WsScope ws_scope(c);
+  if (poison) RET_IF(hook_poison(c, s));
+  GradOverride go(c, dgamma, dbeta);
+  Bwd b{c, s, B, nullptr, nullptr};
+  NormW n;
+  n.g = const_cast<float*>(gamma); n.b = const_cast<float*>(beta); n.C = C; n.key = kHookNorm;
+  return hook_sync("op_group_norm_bwd_ex", s,
+                   gn_backward(b, n, groups, eps, act, x, ld, dy, ldy, rows, dx, lddx, accum != 0, pre, pld, dpre, ldp, S_force, form == 1, S_used));
+}
+
+int mvd_op_group_norm_fwd32(mvd_ctx* c, const float* x, int ld, int B, int rows, int C, int groups, const float* gamma, const float* beta,
+                            float eps, int act, int S_force, float* y, int ldy, int poison, int* S_used, void* stream) {
+  RET_IF(hook_begin(c));
+  if (gn_args_bad(x, ld, B, rows, C, groups, gamma, beta, act, S_force) || !y || ldy < C || !(eps > 0.f))
+    return mvd_fail("op_group_norm_fwd32: bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  WsScope ws_scope(c);
+  if (poison) RET_IF(hook_poison(c, s));
+  Bwd b{c, s, B, nullptr, nullptr};
+  return hook_sync("op_group_norm_fwd32", s, gn_forward32(b, x, rows, C, groups, gamma, beta, act, y, ld, ldy, eps, S_force, S_used));
+}
+
+int mvd_op_layer_norm_bwd_ex(mvd_ctx* c, const float* x, int ld, const float* dy, int ldy, int rows, int C, const float* gamma, float eps,
+                             float* dx, int lddx, int accum, float* dgamma, float* dbeta, int poison, int* nblk_used, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!x || !dy || !gamma || !dx || !dgamma || !dbeta || rows <= 0 || C <= 0 || ld < C || ldy < C || lddx < C || !(eps > 0.f))
+    return mvd_fail("op_layer_norm_bwd_ex: bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  WsScope ws_scope(c);
+  if (poison) RET_IF(hook_poison(c, s));
+  GradOverride go(c, dgamma, dbeta);
+  Bwd b{c, s, 1, nullptr, nullptr};
+  NormW n;
+  n.g = const_cast<float*>(gamma); n.C = C; n.key = kHookNorm;
+  return hook_sync("op_layer_norm_bwd_ex", s, ln_backward(b, n, x, ld, dy, ldy, rows, dx, lddx, accum != 0, eps, nblk_used));
+}
+
+// the two hooks of tests/test_gpu_train_ops.py: the dense, written (not accumulated) form of the two above
+int mvd_op_group_norm_bwd(mvd_ctx* c, const float* x, const float* dy, int B, int rows, int C, int groups, const float* gamma,
+                          const float* beta, float eps, int act, float* dx, float* dgamma, float* dbeta, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!dgamma || !dbeta || C <= 0) return mvd_fail("op_group_norm_bwd: bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  HIP_CHECK_RET(hipMemsetAsync(dgamma, 0, (size_t)C * sizeof(float), s));
+  HIP_CHECK_RET(hipMemsetAsync(dbeta, 0, (size_t)C * sizeof(float), s));
+  // the slabbed form the training step uses; MVD_GN_BWD_ONE_BLOCK=1: the one-workgroup-per-(sample, group) kernel
+  return mvd_op_group_norm_bwd_ex(c, x, C, nullptr, 0, dy, C, B, rows, C, groups, gamma, beta, eps, act, mvd_env().gn_bwd_one_block ? 1 : 0,
+                                  0, dx, C, 0, dgamma, dbeta, nullptr, 0, 0, nullptr, stream);
+}
+
+int mvd_op_layer_norm_bwd(mvd_ctx* c, const float* x, const float* dy, int rows, int C, const float* gamma, float* dx, float* dgamma,
+                          float* dbeta, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!dgamma || !dbeta || C <= 0) return mvd_fail("op_layer_norm_bwd: bad argument");
+  hipStream_t s = (hipStream_t)stream;
+  HIP_CHECK_RET(hipMemsetAsync(dgamma, 0, (size_t)C * sizeof(float), s));
+  HIP_CHECK_RET(hipMemsetAsync(dbeta, 0, (size_t)C * sizeof(float), s));
+  return mvd_op_layer_norm_bwd_ex(c, x, C, dy, C, rows, C, gamma, 1e-5f, dx, C, 0, dgamma, dbeta, 0, nullptr, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -379,12 +379,21 @@ __global__ __launch_bounds__(256) void gn_bwd_kernel(const float* __restrict__ x
 
 // ---- slabbed GroupNorm forward / backward: one workgroup per (sample, group, row slab), so that the few (sample, group)
 // pairs of a small batch still fill the chip (B * G * S workgroups instead of B * G).  Three passes over the data:
-//   gn_slab_stats:  per-slab (sum, sumsq) of x (+ pre)                     -> part [B*G][S][2]
+//   gn_slab_stats:  per-slab (sum, sumsq) of x (+ pre) - pivot              -> part [B*G][S][2]
 //   gn_slab_sums:   mean / rstd from the S partials (fp64), then per-slab (sum dxhat, sum dxhat xhat) -> part2 [B*G][S][2]
 //                   and per-(sample, slab) channel sums of du xhat / du   -> dg_part / db_part [B*S][C]
 //   gn_slab_apply:  m1 / m2 from the S partials, dx for the slab's rows
 // The forward (fp32 out) is gn_slab_stats + gn_slab_fwd.  Same thread mapping as gn_bwd_kernel (fixed summation orders).
-__device__ __forceinline__ void gn_slab_meanrstd(const float* __restrict__ part, int S, float n, float eps, float* mean, float* rstd) {
+// The one-pass sums are taken about a pivot, the (sample, group)'s first element (+ its pre): E[d^2] - E[d]^2 of d = v - pivot
+// cancels by 1 + ((mean - pivot) / std)^2, a few units for a pivot drawn from the data, where the raw sums cancel by
+// 1 + (mean / std)^2 -- 65 for a group a FiLM pre-add moved 8 std off zero.  Every kernel of the pass reads the same pivot.
+__device__ __forceinline__ float gn_slab_pivot(const float* __restrict__ x, long ld, const float* __restrict__ pre, int pld, int rows, int b,
+                                               int ch0) {
+  const float p = x[(long)b * rows * ld + ch0];
+  return pre ? p + pre[(long)b * pld + ch0] : p;
+}
+__device__ __forceinline__ void gn_slab_meanrstd(const float* __restrict__ part, int S, float n, float eps, float pivot, float* mean,
+                                                 float* rstd) {
   double sx = 0.0, sq = 0.0;
   for (int k = 0; k < S; ++k) {
     sx += (double)part[2 * k];
@@ -393,7 +402,7 @@ __device__ __forceinline__ void gn_slab_meanrstd(const float* __restrict__ part,
   const double m = sx / (double)n;
   double var = sq / (double)n - m * m;
   if (var < 0.0) var = 0.0;
-  *mean = (float)m;
+  *mean = (float)((double)pivot + m);
   *rstd = (float)(1.0 / sqrt(var + (double)eps));
 }
 
@@ -407,12 +416,13 @@ __global__ __launch_bounds__(256) void gn_slab_stats_kernel(const float* __restr
   const int rbeg = sl * rps, rend = min(rows, rbeg + rps);
   const float* xb = x + (long)b * rows * ld + ch;
   const float pv = (pre && active) ? pre[(long)b * pld + ch] : 0.f;
+  const float pivot = gn_slab_pivot(x, ld, pre, pld, rows, b, g * cpg);
   float a = 0.f, q = 0.f;
   if (active)
     for (int r = rbeg + r0; r < rend; r += rpi) {
-      const float v = xb[(long)r * ld] + pv;
-      a += v;
-      q += v * v;
+      const float d = xb[(long)r * ld] + pv - pivot;
+      a += d;
+      q += d * d;
     }
   const float sa = block_sum256(a, s_red), sq = block_sum256(q, s_red);
   if (t == 0) {
@@ -430,12 +440,13 @@ __global__ __launch_bounds__(256) void gn_slab_fwd_kernel(const float* __restric
   if (t >= rpi * cpg) return;
   const int c = t % cpg, r0 = t / cpg, ch = g * cpg + c;
   float mean, rstd;
-  gn_slab_meanrstd(part + (long)bg * S * 2, S, (float)rows * (float)cpg, eps, &mean, &rstd);
-  const float gm = gamma[ch] * rstd, bt = beta[ch] - mean * rstd * gamma[ch];
+  gn_slab_meanrstd(part + (long)bg * S * 2, S, (float)rows * (float)cpg, eps, gn_slab_pivot(x, ld, nullptr, 0, rows, b, g * cpg), &mean,
+                   &rstd);
+  const float gm = gamma[ch] * rstd, bt = beta[ch];
   const int rbeg = sl * rps, rend = min(rows, rbeg + rps);
   for (int r = rbeg + r0; r < rend; r += rpi) {
     const long o = ((long)b * rows + r);
-    y[o * ldy + ch] = act_f(x[o * ld + ch] * gm + bt, act);
+    y[o * ldy + ch] = act_f((x[o * ld + ch] - mean) * gm + bt, act);  // centred first: x gm - mean gm would cancel
   }
 }
 
@@ -450,7 +461,8 @@ __global__ __launch_bounds__(256) void gn_slab_sums_kernel(const float* __restri
   const bool active = t < rpi * cpg;
   const int c = t % cpg, r0 = t / cpg, ch = g * cpg + c;
   float mean, rstd;
-  gn_slab_meanrstd(part + (long)bg * S * 2, S, (float)rows * (float)cpg, eps, &mean, &rstd);
+  gn_slab_meanrstd(part + (long)bg * S * 2, S, (float)rows * (float)cpg, eps, gn_slab_pivot(x, ld, pre, pld, rows, b, g * cpg), &mean,
+                   &rstd);
   const int rbeg = sl * rps, rend = min(rows, rbeg + rps);
   const float* xb = x + (long)b * rows * ld + ch;
   const float* dyb = dy + (long)b * rows * ldy + ch;
@@ -500,7 +512,7 @@ __global__ __launch_bounds__(256) void gn_slab_apply_kernel(const float* __restr
   const int c = t % cpg, r0 = t / cpg, ch = g * cpg + c;
   const float n = (float)rows * (float)cpg;
   float mean, rstd;
-  gn_slab_meanrstd(part + (long)bg * S * 2, S, n, eps, &mean, &rstd);
+  gn_slab_meanrstd(part + (long)bg * S * 2, S, n, eps, gn_slab_pivot(x, ld, pre, pld, rows, b, g * cpg), &mean, &rstd);
   double a1 = 0.0, a2 = 0.0;
   for (int k = 0; k < S; ++k) {
     a1 += (double)part2[((long)bg * S + k) * 2];

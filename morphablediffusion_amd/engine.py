@@ -1865,6 +1865,133 @@ class Engine:
                                                L.ptr(db), _stream()))
         return dx, dg, db
 
+    # ---- the training backward's norms and reductions in their production forms (tests/test_gpu_norm_bwd_ops.py).  Operands go in
+    # as rows `ld` floats apart inside NaN-filled buffers (ld = 0: dense); results come back compact from guarded buffers, after the
+    # guard row and the pad columns were found bit-exact.  accum: the values a result that is added to starts from.
+    def _rows_in(self, t, ld=0, off=0):
+        """t [rows, C] -> (buffer [rows, ld] of NaN with t at columns off .. off + C, device pointer of t[0][0] in it, ld)"""
+        t = _f32(t, self.device)
+        rows, Cc = t.shape
+        ld = ld or Cc
+        if off + Cc > ld:
+            raise ValueError("the operand does not fit its rows")
+        buf = torch.full((rows, ld), float("nan"), device=self.device)
+        buf[:, off:off + Cc] = t
+        return buf, buf.data_ptr() + 4 * off, ld
+
+    def _rows_out(self, rows, Cc, ld=0, start=None, off=0):
+        """A guarded result: [rows + 1][ld] of 0xFF bytes, columns off .. off + C of the body preset to `start` where given."""
+        ld = ld or Cc
+        buf = _nan_guarded(rows, ld, self.device)
+        if start is not None:
+            buf[:rows, off:off + Cc] = _f32(start, self.device).reshape(rows, Cc)
+        return buf, buf.data_ptr() + 4 * off, ld
+
+    @staticmethod
+    def _rows_result(buf, rows, Cc, what, off=0):
+        _nan_guard_intact(buf, rows, what, off + Cc)
+        assert bool((buf.view(torch.int32)[:rows, :off] == -1).all()), f"{what}: the launch wrote left of its columns"
+        return buf[:rows, off:off + Cc].clone()
+
+    def _refused(self, rc, bufs, before):
+        """rc != 0: raises MvdError with the library's text; its results_untouched says whether every result buffer still holds its
+        preset, bit for bit (what a refusal must leave)."""
+        if rc == 0:
+            return
+        torch.cuda.synchronize(self.device)
+        err = L.MvdError(self.lib.mvd_last_error().decode())
+        err.results_untouched = all(torch.equal(t.view(torch.int32), u.view(torch.int32)) for t, u in zip(bufs, before))
+        raise err
+
+    def op_group_norm_bwd_ex(self, x, dy, groups, gamma, beta, eps, act=0, pre=None, pld=0, pre_off=0, form=0, S_force=0, ld=0, x_off=0,
+                             ldy=0, lddx=0, accum=None, want_dpre=False, ldp=0, dpre_off=0, poison=False):
+        """mvd_op_group_norm_bwd_ex: gn_backward on x, dy [B, rows, C]; pre [B, C] (optional) at column pre_off of rows of pld floats;
+        accum = (dx0, dgamma0, dbeta0).  Returns a namespace: dx [B, rows, C], dgamma, dbeta [C], dpre [B, C] or None, S_used."""
+        B, rows, Cc = x.shape
+        xb, xp, ld = self._rows_in(x.reshape(B * rows, Cc), ld, x_off)
+        yb, yp, ldy = self._rows_in(dy.reshape(B * rows, Cc), ldy)
+        g, b = _f32(gamma, self.device), _f32(beta, self.device)
+        pb, pp, pld = (None, None, 0) if pre is None else self._rows_in(pre.reshape(B, Cc), pld, pre_off)
+        a = accum or (None, torch.zeros(Cc), torch.zeros(Cc))
+        dxb, dxp, lddx = self._rows_out(B * rows, Cc, lddx, a[0])
+        dgb, dgp, _ = self._rows_out(1, Cc, 0, a[1])
+        dbb, dbp, _ = self._rows_out(1, Cc, 0, a[2])
+        dpb, dpp, ldp = self._rows_out(B, Cc, ldp, None, dpre_off) if want_dpre else (None, None, 0)
+        S_used = C.c_int(-1)
+        bufs = [t for t in (dxb, dgb, dbb, dpb) if t is not None]
+        before = [t.clone() for t in bufs]
+        self._refused(self.lib.mvd_op_group_norm_bwd_ex(self._ctx, xp, ld, pp, pld, yp, ldy, B, rows, Cc, groups, L.ptr(g), L.ptr(b), eps, act,
+                                                        form, S_force, dxp, lddx, accum is not None, dgp, dbp, dpp, ldp, bool(poison),
+                                                        C.byref(S_used), _stream()), bufs, before)
+        what = "op_group_norm_bwd_ex"
+        return types.SimpleNamespace(dx=self._rows_result(dxb, B * rows, Cc, what + " (dx)").reshape(B, rows, Cc),
+                                     dgamma=self._rows_result(dgb, 1, Cc, what + " (dgamma)")[0],
+                                     dbeta=self._rows_result(dbb, 1, Cc, what + " (dbeta)")[0],
+                                     dpre=self._rows_result(dpb, B, Cc, what + " (dpre)", dpre_off) if want_dpre else None,
+                                     S_used=S_used.value)
+
+    def op_group_norm_fwd32(self, x, groups, gamma, beta, eps, act=0, S_force=0, ld=0, x_off=0, ldy=0, poison=False):
+        """mvd_op_group_norm_fwd32: gn_forward32 on x [B, rows, C] -> (y [B, rows, C], S_used)."""
+        B, rows, Cc = x.shape
+        xb, xp, ld = self._rows_in(x.reshape(B * rows, Cc), ld, x_off)
+        g, b = _f32(gamma, self.device), _f32(beta, self.device)
+        yb, yp, ldy = self._rows_out(B * rows, Cc, ldy)
+        S_used = C.c_int(-1)
+        L.check(self.lib.mvd_op_group_norm_fwd32(self._ctx, xp, ld, B, rows, Cc, groups, L.ptr(g), L.ptr(b), eps, act, S_force, yp, ldy,
+                                                 bool(poison), C.byref(S_used), _stream()))
+        return self._rows_result(yb, B * rows, Cc, "op_group_norm_fwd32").reshape(B, rows, Cc), S_used.value
+
+    def op_layer_norm_bwd_ex(self, x, dy, gamma, eps, ld=0, x_off=0, ldy=0, lddx=0, accum=None, poison=False):
+        """mvd_op_layer_norm_bwd_ex: ln_backward on x, dy [rows, C]; accum = (dx0, dgamma0, dbeta0).  Returns a namespace: dx,
+        dgamma, dbeta, nblk_used."""
+        rows, Cc = x.shape
+        xb, xp, ld = self._rows_in(x, ld, x_off)
+        yb, yp, ldy = self._rows_in(dy, ldy)
+        g = _f32(gamma, self.device)
+        a = accum or (None, torch.zeros(Cc), torch.zeros(Cc))
+        dxb, dxp, lddx = self._rows_out(rows, Cc, lddx, a[0])
+        dgb, dgp, _ = self._rows_out(1, Cc, 0, a[1])
+        dbb, dbp, _ = self._rows_out(1, Cc, 0, a[2])
+        before = [t.clone() for t in (dxb, dgb, dbb)]
+        nblk = C.c_int(-1)
+        rc = self.lib.mvd_op_layer_norm_bwd_ex(self._ctx, xp, ld, yp, ldy, rows, Cc, L.ptr(g), eps, dxp, lddx, accum is not None, dgp, dbp,
+                                               bool(poison), C.byref(nblk), _stream())
+        self._refused(rc, (dxb, dgb, dbb), before)
+        what = "op_layer_norm_bwd_ex"
+        return types.SimpleNamespace(dx=self._rows_result(dxb, rows, Cc, what + " (dx)"),
+                                     dgamma=self._rows_result(dgb, 1, Cc, what + " (dgamma)")[0],
+                                     dbeta=self._rows_result(dbb, 1, Cc, what + " (dbeta)")[0], nblk_used=nblk.value)
+
+    def op_train_colsum(self, v, B, src_half=False, ld=0, ldo=0, out_off=0):
+        """mvd_op_train_colsum: v [B * rows, C] -> [B, C] per-sample column sums, written at column out_off of rows of ldo floats."""
+        R, Cc = v.shape
+        vb, vp, ld = self._rows_in(v, ld)
+        ob, op, ldo = self._rows_out(B, Cc, ldo, None, out_off)
+        L.check(self.lib.mvd_op_train_colsum(self._ctx, vp, bool(src_half), ld, B, R // B, Cc, op, ldo, _stream()))
+        return self._rows_result(ob, B, Cc, "op_train_colsum", out_off)
+
+    def op_train_sum_rows(self, jobs):
+        """mvd_op_train_sum_rows: jobs = [(part [R, C], ldp, out0 [C] or None)], 1..4 of them in ONE launch; out0: the job adds to
+        these values (accum = 1), None: it writes.  Returns the [C] results."""
+        n = len(jobs)
+        parts = [self._rows_in(p, ldp) for p, ldp, _ in jobs]
+        outs = [self._rows_out(1, p.shape[1], 0, o) for p, _, o in jobs]
+        arr = lambda ty, vals: (ty * n)(*vals)  # noqa: E731
+        L.check(self.lib.mvd_op_train_sum_rows(self._ctx, n, arr(C.c_void_p, [p[1] for p in parts]), arr(C.c_int, [j[0].shape[0] for j in jobs]),
+                                               arr(C.c_int, [j[0].shape[1] for j in jobs]), arr(C.c_long, [p[2] for p in parts]),
+                                               arr(C.c_void_p, [o[1] for o in outs]), arr(C.c_int, [j[2] is not None for j in jobs]),
+                                               _stream()))
+        return [self._rows_result(o[0], 1, j[0].shape[1], f"op_train_sum_rows (job {k})")[0] for k, (o, j) in enumerate(zip(outs, jobs))]
+
+    def op_train_outer_add(self, a, b, out0, lda=0, ldb=0):
+        """mvd_op_train_outer_add: out0 [M, N] + sum_k a[k][:, None] * b[k][None, :] with a [K, M], b [K, N]."""
+        ab, ap, lda = self._rows_in(a, lda)
+        bb, bp, ldb = self._rows_in(b, ldb)
+        (K, M), N = a.shape, b.shape[1]
+        ob, op, _ = self._rows_out(M, N, 0, out0)
+        L.check(self.lib.mvd_op_train_outer_add(self._ctx, ap, lda, bp, ldb, op, M, N, K, _stream()))
+        return self._rows_result(ob, M, N, "op_train_outer_add")
+
     # ---- training-backward adjoints of one layer (mvd_op_*_bwd, mvd_op_tgemm): reference layouts in, reference layouts out.
     # accum = (dx0, dW0, db0): the gradients start from these values (otherwise from zero: dx written, dW / db added to zero).
     def _pad_last(self, t, n):
