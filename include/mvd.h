@@ -420,13 +420,88 @@ int mvd_op_mesh_vertex_colors(const void* images, int dtype, int layout, const i
  *                 vertex index out of range is never dereferenced: that landmark is NaN.
  * Errors, which return before the first HIP call: a null pointer (but post, and pose_feature when J == 1); F, V, L, NB, M or
  * Nf < 1; J < 1 or J > 64; L != NB + 9 (J-1); a bad parents; F V 3 >= 2^31 (and F M 3, F J 12, NB J 3 likewise).
- * Not computed: the pose-dependent contour landmarks, vertex normals, any backward pass. */
+ * Not computed: the pose-dependent contour landmarks, vertex normals. */
 int mvd_op_morph_pose(const float* betas, const float* pose, const float* j_template, const float* j_dirs, const int32_t* parents, int F,
                       int NB, int J, float* j_rest, float* rot, float* pose_feature, float* joints, float* A, void* stream);
 int mvd_op_morph_skin(const float* basis, const float* v_template, const float* coef, const float* weights, const float* A,
                       const float* post, int F, int V, int L, int NB, int J, float* verts, void* stream);
 int mvd_op_morph_landmarks(const float* verts, const int32_t* faces, const int32_t* lmk_face, const float* lmk_bary, int F, int V, int Nf,
                            int M, float* out, void* stream);
+/* The morphable-model backward and the fitter (csrc/k_morph_bwd.hip, entries in csrc/c_api_morph.hip): the vector-Jacobian product
+ * of the forward above, a data term and an Adam step, all fp32 with every sum in an order fixed by indices alone and no atomics:
+ * two calls agree bit for bit and frame f of a batch equals the frame computed alone.  With b = t + B^T c, T = sum_j w_vj A_j,
+ * o = T[:, :3] b + T[:, 3] (+ transl_f), y = P[:, :3] o + P[:, 3]:
+ *   mvd_op_morph_skin_ex    mvd_op_morph_skin with an optional transl [F,3] added to o (NULL is a branch, not "+ 0": the bits of
+ *                 mvd_op_morph_skin, which calls the same kernel with both NULL) and an optional output blend [F,V,3] = b.
+ *   mvd_op_morph_skin_bwd   g_y [F,V,3], post [12] or NULL, weights, A, blend, basis as above.  Vertex phase, a thread per (vertex,
+ *                 frame): g_o_k = fma(P_2k, g_y2, fma(P_1k, g_y1, P_0k g_y0)) (g_y without post); T as the forward chains it;
+ *                 g_b [F,V,3]: g_b_k = fma(T_2k, g_o2, fma(T_1k, g_o1, T_0k g_o0)); g_T_ik = g_o_i b_k, g_T_i3 = g_o_i; the
+ *                 products w_vj g_T are summed over a chunk of 256 consecutive vertices: a butterfly over each wave's 64 lanes
+ *                 (partners at distance 32, 16, ... 1), then ((s0 + s1) + s2) + s3 over the chunk's 4 waves.  part_a
+ *                 [mvd_morph_bwd_chunks(V), F, J 12 + 3]: g_A of the chunk, then the chunk's sum of g_o (the adjoint of transl).
+ *                 Basis phase: the 3V basis columns in slabs of 256; part_c [mvd_morph_bwd_slabs(V), F, L], part_c[s,f,l] = fma
+ *                 chain of basis[l,k] g_b[f,k] over the slab's columns k ascending, starting from 0.  Both counts depend on V
+ *                 alone.  The consumer sums part_a over chunks and part_c over slabs, ascending, starting from chunk / slab 0.
+ *   mvd_op_morph_pose_bwd   one workgroup per frame.  pose [F,J,3], j_rest [F,J,3] and A [F,J,12] as mvd_op_morph_pose wrote them,
+ *                 j_dirs, parents (HOST), the two partial buffers with their counts, g_joints [F,J,3] or NULL (the adjoint of the
+ *                 posed joints).  Sums the partials as above (g_pose_feature = the summed part_c[:, NB:]), then goes back through
+ *                 the chain in the forward's own form, joints descending with p = parents[j]: g_R_j = G_p^T g_G_j, g_G_p +=
+ *                 g_G_j R_j^T - g_a_j u_j^T + g_t_j (j_rest_j - j_rest_p)^T, g_a_p += g_a_j, g_t_p += g_t_j, g_u_j = -G_p^T g_a_j,
+ *                 g_D_j = g_pose_feature_j + g_R_j + g_u_j j_rest_j^T, g_j_rest_j += D_j^T g_u_j + G_p^T g_t_j, g_j_rest_p -=
+ *                 G_p^T g_t_j (root: g_R_0 = g_G_0, g_u_0 = -g_a_0, g_j_rest_0 += g_t_0); then through Rodrigues as the forward
+ *                 writes it, q = r + 1e-8, angle = |q|, k = r / angle differentiated as written: the reference's autograd, finite
+ *                 at a zero pose (the rotation generators).  g_pose [F,J,3]; g_betas [F,NB] = summed part_c[:, n] + (an fma
+ *                 chain of j_dirs[n,c] g_j_rest[c] from 0, c ascending); g_transl [F,3] = the summed last three columns of part_a.
+ *   mvd_op_morph_landmarks_bwd   g_lmk [F,M,3], g_in [F,V,3] or NULL, the vertex -> (landmark, corner) table csr_ptr [V+1], csr_ent
+ *                 [n_ent] (entry = landmark * 3 + corner, ascending within a vertex), lmk_bary [M,3]: g_verts [F,V,3] = fma chain
+ *                 of lmk_bary[entry] g_lmk[f, entry / 3] over the vertex's entries in table order, starting from g_in or 0.  A gather:
+ *                 landmarks that share a vertex are summed in a fixed order.  Entries and offsets out of range are skipped.
+ *   mvd_op_morph_fit_data   E_f = inv_vw_sum sum_v w_v |y - t|^2 + lmk_scale sum_m w'_m |l - l'|^2 (inv_vw_sum = 1 / sum_v w_v,
+ *                 lmk_scale = lambda / sum_m w'_m, computed by the caller; weights NULL = ones).  verts [F,V,3]; target
+ *                 [target_frames,V,3] with target_frames 1 or F, or NULL; lmk / target_lmk likewise with M, or NULL (not both
+ *                 targets NULL).  g_y [F,V,3] = 2 w_v inv_vw_sum (y - t), then per table entry fma(lmk_bary[entry] (2 lmk_scale
+ *                 w'_m), l - l', g_y).  E [F]: squares summed per block of 256 vertices in the vertex phase's shape into e_part
+ *                 [mvd_morph_bwd_chunks(V), F], then per frame a lane-strided ascending sum over blocks (and over landmarks) and one
+ *                 butterfly.  Each frame's loss is its own: no mean over F.
+ *   mvd_op_morph_fit_update   p, g, m, v [F,P]; lr, lam, p0 [P].  g' = fma(2 lam, p - p0, g); torch.optim.Adam's step `step` (>= 1):
+ *                 m = fma(1 - beta1, g' - m, m), v = fma((1 - beta2) g', g', v beta2), p = fma(-(lr / bias1), m / (sqrt(v) /
+ *                 sqrt(bias2) + eps), p) with bias_i = 1 - beta_i^step in double on the host.  lr[c] == 0: p, m and v of that
+ *                 column keep their bits.
+ *   mvd_morph_fit_run   `iters` iterations of pose, skin_ex, landmarks, fit_data, skin_bwd, pose_bwd, fit_update enqueued on the
+ *                 stream as plain launches with no host synchronisation between them and one at the end.  p [F,P] = betas |
+ *                 pose | transl, P = NB + 3 J + 3, is read and written in place by the stages through row strides; m, v
+ *                 likewise; Adam steps step0 + 1 .. step0 + iters.  workspace: as many floats of the caller as
+ *                 mvd_morph_fit_workspace(F, V, NB, J, M, &floats) stores in the HOST integer (M = 0 without a landmark target).  loss_history [iters,F]: E before each update.  Each
+ *                 iteration's bits are those of the seven per-op entries called in turn.
+ * Errors, which return before the first HIP call: those of the forward's list for the same arguments; a null pointer (but post,
+ * transl, blend, g_joints, g_in, the weights, and one of the two targets); counts < 1; a target with neither 1 nor F frames; more
+ * than 65535 frames in fit_data / fit_run; step < 1, beta outside [0, 1), eps <= 0; a workspace that is too small. */
+int mvd_morph_bwd_chunks(int V);
+int mvd_morph_bwd_slabs(int V);
+int mvd_morph_fit_workspace(int F, int V, int NB, int J, int M, int64_t* floats);
+int mvd_op_morph_skin_ex(const float* basis, const float* v_template, const float* coef, const float* weights, const float* A,
+                         const float* post, const float* transl, int F, int V, int L, int NB, int J, float* verts, float* blend,
+                         void* stream);
+int mvd_op_morph_skin_bwd(const float* g_y, const float* post, const float* weights, const float* A, const float* blend,
+                          const float* basis, int F, int V, int L, int NB, int J, float* g_b, float* part_a, float* part_c, void* stream);
+int mvd_op_morph_pose_bwd(const float* pose, const float* j_rest, const float* A, const float* j_dirs, const int32_t* parents,
+                          const float* part_a, int nchunk, const float* part_c, int nslab, const float* g_joints, int F, int NB, int J,
+                          float* g_betas, float* g_pose, float* g_transl, void* stream);
+int mvd_op_morph_landmarks_bwd(const float* g_lmk, const float* g_in, const int32_t* csr_ptr, const int32_t* csr_ent, const float* lmk_bary,
+                               int F, int V, int M, int n_ent, float* g_verts, void* stream);
+int mvd_op_morph_fit_data(const float* verts, const float* target, int target_frames, const float* vertex_weight, float inv_vw_sum,
+                          const float* lmk, const float* target_lmk, int target_lmk_frames, const float* lmk_weight, float lmk_scale,
+                          const int32_t* csr_ptr, const int32_t* csr_ent, const float* lmk_bary, int F, int V, int M, int n_ent,
+                          float* g_y, float* e_part, float* E, void* stream);
+int mvd_op_morph_fit_update(float* p, const float* g, float* m, float* v, const float* lr, const float* lam, const float* p0, int F, int P,
+                            int step, float beta1, float beta2, float eps, void* stream);
+int mvd_morph_fit_run(const float* basis, const float* v_template, const float* weights, const float* j_template, const float* j_dirs,
+                      const int32_t* parents, const float* post, const int32_t* faces, const int32_t* lmk_face, const float* lmk_bary,
+                      const int32_t* csr_ptr, const int32_t* csr_ent, int F, int V, int NB, int J, int Nf, int M, int n_ent,
+                      const float* target, int target_frames, const float* vertex_weight, float inv_vw_sum, const float* target_lmk,
+                      int target_lmk_frames, const float* lmk_weight, float lmk_scale, float* p, float* m, float* v, const float* lr,
+                      const float* lam, const float* p0, int iters, int step0, float beta1, float beta2, float eps, float* workspace,
+                      size_t workspace_floats, float* loss_history, void* stream);
 /* The conditioner's backward for ONE sample (its mesh / cameras active: mvd_select_sample): re-runs construct_spatial_volume and
  * construct_view_frustum_volume (morphable_diffusion.py:203-320: step embedding, 2-D encoder on the N noisy views, vertex gather,
  * view fusion, sparse voxel CNN in train mode, lattice gather, frustum gather and FrustumTV3DNet for the target view) with every
@@ -613,7 +688,8 @@ int mvd_denoise_views_ms(mvd_ctx* ctx, int B, const int* slots, const float* x_n
 
 /* ---- per-op hooks: one kernel, or one layer's launch sequence, on the caller's data ----
  * The stateless product ops (mvd_op_cfg_ms, mvd_op_adamw_ex, mvd_op_lora_*, and above mvd_op_train_loss, mvd_op_image_metrics,
- * mvd_op_mesh_*, mvd_op_morph_*) are defined with the product API in csrc/c_api.hip.  Everything else from here to the end of
+ * mvd_op_mesh_*, mvd_op_morph_*) are defined with the product API in csrc/c_api.hip (the morphable-model backward and fitter
+ * in csrc/c_api_morph.hip).  Everything else from here to the end of
  * the section is a test or bench hook: csrc/c_api_hooks.hip, and for the backward, adjoint and gather hooks (which call the
  * training step's file-local functions) the end of csrc/engine_train.hip, both on the scaffold of csrc/hooks.h.  Every hook
  * that takes a context refuses a NULL one ("null context") before it touches anything.  The hooks come in two kinds:

@@ -1,0 +1,146 @@
+// The morphable-model backward and fitter of the C ABI (include/mvd.h: mvd_op_morph_skin_ex, the mvd_op_morph_*_bwd and
+// mvd_op_morph_fit_* entries, mvd_morph_fit_run) over k_morph.hip and k_morph_bwd.hip.  No context, the caller's device buffers;
+// parents is a host array.  The per-op entries end in hooks.h's hook_sync; the loop of mvd_morph_fit_run synchronises once.
+#include "hooks.h"
+#include "morph.h"
+
+namespace {
+
+inline hipStream_t S(void* s) { return (hipStream_t)s; }
+
+// the float offsets of mvd_morph_fit_run's workspace, every buffer on a 256-byte boundary
+struct FitLayout {
+  size_t j_rest, rot, joints, A, coef, verts, blend, lmk, g_y, g_b, part_a, part_c, e_part, g, total;
+  FitLayout(int F, int V, int NB, int J, int M) {
+    const size_t f = (size_t)F, L = (size_t)NB + 9 * (size_t)(J - 1), P = (size_t)NB + 3 * (size_t)J + 3;
+    size_t o = 0;
+    auto take = [&](size_t n) {
+      const size_t at = o;
+      o += (n + 63) & ~(size_t)63;
+      return at;
+    };
+    j_rest = take(f * J * 3), rot = take(f * J * 9), joints = take(f * J * 3), A = take(f * J * 12), coef = take(f * L);
+    verts = take(f * V * 3), blend = take(f * V * 3), lmk = take(f * (size_t)M * 3), g_y = take(f * V * 3), g_b = take(f * V * 3);
+    part_a = take((size_t)morph_bwd_chunks(V) * f * ((size_t)J * 12 + 3)), part_c = take((size_t)morph_bwd_slabs(V) * f * L);
+    e_part = take((size_t)morph_bwd_chunks(V) * f), g = take(f * P);
+    total = o;
+  }
+};
+
+}  // namespace
+
+int mvd_morph_bwd_chunks(int V) { return V < 1 ? 0 : morph_bwd_chunks(V); }
+int mvd_morph_bwd_slabs(int V) { return V < 1 ? 0 : morph_bwd_slabs(V); }
+
+int mvd_op_morph_skin_ex(const float* basis, const float* v_template, const float* coef, const float* weights, const float* A,
+                         const float* post, const float* transl, int F, int V, int L, int NB, int J, float* verts, float* blend,
+                         void* stream) {
+  RET_IF(morph_skin_check("mvd_op_morph_skin_ex", basis, v_template, coef, weights, A, F, V, L, NB, J, verts));
+  hipStream_t s = S(stream);
+  return hook_sync("mvd_op_morph_skin_ex", s,
+                   launch_morph_skin_ex(basis, v_template, coef, weights, A, post, transl, 3, F, V, L, J, verts, blend, s));
+}
+
+int mvd_op_morph_skin_bwd(const float* g_y, const float* post, const float* weights, const float* A, const float* blend,
+                          const float* basis, int F, int V, int L, int NB, int J, float* g_b, float* part_a, float* part_c, void* stream) {
+  RET_IF(morph_skin_bwd_check("mvd_op_morph_skin_bwd", g_y, weights, A, blend, basis, F, V, L, NB, J, g_b, part_a, part_c));
+  hipStream_t s = S(stream);
+  return hook_sync("mvd_op_morph_skin_bwd", s, launch_morph_skin_bwd(g_y, post, weights, A, blend, basis, F, V, L, J, g_b, part_a, part_c, s));
+}
+
+int mvd_op_morph_pose_bwd(const float* pose, const float* j_rest, const float* A, const float* j_dirs, const int32_t* parents,
+                          const float* part_a, int nchunk, const float* part_c, int nslab, const float* g_joints, int F, int NB, int J,
+                          float* g_betas, float* g_pose, float* g_transl, void* stream) {
+  RET_IF(morph_pose_bwd_check("mvd_op_morph_pose_bwd", pose, j_rest, A, j_dirs, parents, part_a, nchunk, part_c, nslab, F, NB, J, g_betas,
+                              g_pose, g_transl));
+  hipStream_t s = S(stream);
+  return hook_sync("mvd_op_morph_pose_bwd", s,
+                   launch_morph_pose_bwd(pose, 3 * J, j_rest, A, j_dirs, parents, part_a, nchunk, part_c, nslab, g_joints, F, NB, J, g_betas,
+                                         NB, g_pose, 3 * J, g_transl, 3, s));
+}
+
+int mvd_op_morph_landmarks_bwd(const float* g_lmk, const float* g_in, const int32_t* csr_ptr, const int32_t* csr_ent, const float* lmk_bary,
+                               int F, int V, int M, int n_ent, float* g_verts, void* stream) {
+  RET_IF(morph_landmarks_bwd_check("mvd_op_morph_landmarks_bwd", g_lmk, csr_ptr, csr_ent, lmk_bary, F, V, M, n_ent, g_verts));
+  hipStream_t s = S(stream);
+  return hook_sync("mvd_op_morph_landmarks_bwd", s,
+                   launch_morph_landmarks_bwd(g_lmk, g_in, csr_ptr, csr_ent, lmk_bary, F, V, M, n_ent, g_verts, s));
+}
+
+int mvd_op_morph_fit_data(const float* verts, const float* target, int target_frames, const float* vertex_weight, float inv_vw_sum,
+                          const float* lmk, const float* target_lmk, int target_lmk_frames, const float* lmk_weight, float lmk_scale,
+                          const int32_t* csr_ptr, const int32_t* csr_ent, const float* lmk_bary, int F, int V, int M, int n_ent,
+                          float* g_y, float* e_part, float* E, void* stream) {
+  RET_IF(morph_fit_data_check("mvd_op_morph_fit_data", verts, target, target_frames, lmk, target_lmk, target_lmk_frames, csr_ptr, csr_ent,
+                              lmk_bary, F, V, M, n_ent, g_y, e_part, E));
+  hipStream_t s = S(stream);
+  return hook_sync("mvd_op_morph_fit_data", s,
+                   launch_morph_fit_data(verts, target, target_frames, vertex_weight, inv_vw_sum, lmk, target_lmk, target_lmk_frames,
+                                         lmk_weight, lmk_scale, csr_ptr, csr_ent, lmk_bary, F, V, M, n_ent, g_y, e_part, E, s));
+}
+
+int mvd_op_morph_fit_update(float* p, const float* g, float* m, float* v, const float* lr, const float* lam, const float* p0, int F, int P,
+                            int step, float beta1, float beta2, float eps, void* stream) {
+  RET_IF(morph_fit_update_check("mvd_op_morph_fit_update", p, g, m, v, lr, lam, p0, F, P, step, beta1, beta2, eps));
+  hipStream_t s = S(stream);
+  return hook_sync("mvd_op_morph_fit_update", s, launch_morph_fit_update(p, g, m, v, lr, lam, p0, F, P, step, beta1, beta2, eps, s));
+}
+
+int mvd_morph_fit_workspace(int F, int V, int NB, int J, int M, int64_t* floats) {
+  if (!floats) return morph_fail("mvd_morph_fit_workspace", ": null argument");
+  if (F < 1 || V < 1 || NB < 1 || J < 1 || J > MORPH_MAX_JOINTS || M < 0)
+    return morph_fail("mvd_morph_fit_workspace", ": F, V and NB must be at least 1, J in 1..64, M at least 0");
+  *floats = (int64_t)FitLayout(F, V, NB, J, M).total;
+  return 0;
+}
+
+int mvd_morph_fit_run(const float* basis, const float* v_template, const float* weights, const float* j_template, const float* j_dirs,
+                      const int32_t* parents, const float* post, const int32_t* faces, const int32_t* lmk_face, const float* lmk_bary,
+                      const int32_t* csr_ptr, const int32_t* csr_ent, int F, int V, int NB, int J, int Nf, int M, int n_ent,
+                      const float* target, int target_frames, const float* vertex_weight, float inv_vw_sum, const float* target_lmk,
+                      int target_lmk_frames, const float* lmk_weight, float lmk_scale, float* p, float* m, float* v, const float* lr,
+                      const float* lam, const float* p0, int iters, int step0, float beta1, float beta2, float eps, float* workspace,
+                      size_t workspace_floats, float* loss_history, void* stream) {
+  const char* who = "mvd_morph_fit_run";
+  if (!workspace || !loss_history) return morph_fail(who, ": null argument");
+  if (iters < 1 || step0 < 0 || step0 > 0x7fffffff - iters) return morph_fail(who, ": iters must be at least 1 and step0 at least 0");
+  if (F < 1 || V < 1 || NB < 1 || J < 1 || J > MORPH_MAX_JOINTS || M < 0)
+    return morph_fail(who, ": F, V and NB must be at least 1, J in 1..64, M at least 0");
+  if (morph_too_big(iters, F, 1)) return morph_fail(who, ": iters F must be below 2^31");
+  const bool use_lmk = target_lmk != nullptr;
+  if (use_lmk && (!faces || !lmk_face || M < 1 || Nf < 1)) return morph_fail(who, ": a landmark target needs the landmark embedding");
+  const FitLayout lay(F, V, NB, J, use_lmk ? M : 0);
+  if (workspace_floats < lay.total) return morph_fail(who, ": the workspace is smaller than mvd_morph_fit_workspace says");
+  const int L = NB + 9 * (J - 1), P = NB + 3 * J + 3, nchunk = morph_bwd_chunks(V), nslab = morph_bwd_slabs(V);
+  float* w = workspace;
+  float *j_rest = w + lay.j_rest, *rot = w + lay.rot, *joints = w + lay.joints, *A = w + lay.A, *coef = w + lay.coef;
+  float *verts = w + lay.verts, *blend = w + lay.blend, *lmk = use_lmk ? w + lay.lmk : nullptr, *g_y = w + lay.g_y, *g_b = w + lay.g_b;
+  float *part_a = w + lay.part_a, *part_c = w + lay.part_c, *e_part = w + lay.e_part, *g = w + lay.g;
+  // every argument error of every stage, before the first HIP call
+  RET_IF(morph_pose_check(who, p, p, j_template, j_dirs, parents, F, NB, J, j_rest, rot, coef, joints, A));
+  RET_IF(morph_skin_check(who, basis, v_template, coef, weights, A, F, V, L, NB, J, verts));
+  if (use_lmk) RET_IF(morph_landmarks_check(who, verts, faces, lmk_face, lmk_bary, F, V, Nf, M, lmk));
+  RET_IF(morph_fit_data_check(who, verts, target, target_frames, lmk, target_lmk, target_lmk_frames, csr_ptr, csr_ent, lmk_bary, F, V, M,
+                              n_ent, g_y, e_part, loss_history));
+  RET_IF(morph_skin_bwd_check(who, g_y, weights, A, blend, basis, F, V, L, NB, J, g_b, part_a, part_c));
+  RET_IF(morph_pose_bwd_check(who, p, j_rest, A, j_dirs, parents, part_a, nchunk, part_c, nslab, F, NB, J, g, g, g));
+  RET_IF(morph_fit_update_check(who, p, g, m, v, lr, lam, p0, F, P, step0 + 1, beta1, beta2, eps));
+  hipStream_t s = S(stream);
+  int rc = 0;
+  // p [F][P] = betas | pose | translation: the stages read and write it in place through row strides
+  const float *betas = p, *pose = p + NB, *transl = p + NB + 3 * J;
+  for (int it = 0; it < iters && !rc; ++it) {
+    rc = launch_morph_pose_ex(betas, P, pose, P, j_template, j_dirs, parents, F, NB, J, j_rest, rot, nullptr, joints, A, coef, s);
+    if (!rc) rc = launch_morph_skin_ex(basis, v_template, coef, weights, A, post, transl, P, F, V, L, J, verts, blend, s);
+    if (!rc && use_lmk) rc = launch_morph_landmarks(verts, faces, lmk_face, lmk_bary, F, V, Nf, M, lmk, s);
+    if (!rc)
+      rc = launch_morph_fit_data(verts, target, target_frames, vertex_weight, inv_vw_sum, lmk, target_lmk, target_lmk_frames, lmk_weight,
+                                 lmk_scale, csr_ptr, csr_ent, lmk_bary, F, V, M, n_ent, g_y, e_part, loss_history + (size_t)it * F, s);
+    if (!rc) rc = launch_morph_skin_bwd(g_y, post, weights, A, blend, basis, F, V, L, J, g_b, part_a, part_c, s);
+    if (!rc)
+      rc = launch_morph_pose_bwd(pose, P, j_rest, A, j_dirs, parents, part_a, nchunk, part_c, nslab, nullptr, F, NB, J, g, P, g + NB, P,
+                                 g + NB + 3 * J, P, s);
+    if (!rc) rc = launch_morph_fit_update(p, g, m, v, lr, lam, p0, F, P, step0 + it + 1, beta1, beta2, eps, s);
+  }
+  return hook_sync(who, s, rc);
+}

@@ -23,7 +23,7 @@
 //                           only parallel axis (the order over l is fixed): FLAME's 5023 vertices give 314 workgroups for 256
 //                           CUs.  The blended template goes through LDS to a (vertex, frame) thread layout for the skinning.
 //   morph_landmarks_kernel  one thread per (frame, landmark); an index out of range is never dereferenced (NaN).
-#include "common.h"
+#include "morph.h"
 
 #include <string>
 
@@ -42,8 +42,8 @@ static_assert(SKIN_NLD * MORPH_T == SKIN_LC * SKIN_CB && SKIN_CB <= 64 && SKIN_V
 
 struct MorphPoseArgs {
   const float *betas, *pose, *j_template, *j_dirs;
-  float *j_rest, *rot, *pose_feature, *joints, *A;
-  int F, NB, J;
+  float *j_rest, *rot, *pose_feature, *joints, *A, *coef;  // coef [F][NB + 9 (J-1)] = betas | pose feature, or null
+  int F, NB, J, ldb, ldp;                                   // ldb, ldp: floats between two frames' betas and poses
   signed char parents[MORPH_MAX_JOINTS];
 };
 
@@ -54,7 +54,11 @@ __global__ __launch_bounds__(64) void morph_pose_kernel(MorphPoseArgs a) {
   __shared__ float s_jr[MORPH_MAX_JOINTS * 3], s_D[MORPH_MAX_JOINTS * 9], s_A[MORPH_MAX_JOINTS * 12], s_t[MORPH_MAX_JOINTS * 3];
   const int f = blockIdx.x, lane = threadIdx.x;
   const int J = a.J, NB = a.NB;
-  const float* beta = a.betas + (size_t)f * NB;
+  const float* beta = a.betas + (size_t)f * a.ldb;
+  const float* posef = a.pose + (size_t)f * a.ldp;
+  float* coef = a.coef ? a.coef + (size_t)f * (NB + 9 * (J - 1)) : nullptr;
+  if (coef)
+    for (int n = lane; n < NB; n += 64) coef[n] = beta[n];
   for (int c = lane; c < J * 3; c += 64) {
     float s = a.j_template[c];
 #pragma unroll 8
@@ -65,7 +69,7 @@ __global__ __launch_bounds__(64) void morph_pose_kernel(MorphPoseArgs a) {
   if (lane < J) {
     const int j = lane;
     const size_t fj = (size_t)f * J + j;
-    const float rx = a.pose[fj * 3], ry = a.pose[fj * 3 + 1], rz = a.pose[fj * 3 + 2];
+    const float rx = posef[j * 3], ry = posef[j * 3 + 1], rz = posef[j * 3 + 2];
     const float qx = rx + 1e-8f, qy = ry + 1e-8f, qz = rz + 1e-8f;
     const float angle = sqrtf(fmaf(qz, qz, fmaf(qy, qy, qx * qx)));
     const float x = rx / angle, y = ry / angle, z = rz / angle;
@@ -85,7 +89,8 @@ __global__ __launch_bounds__(64) void morph_pose_kernel(MorphPoseArgs a) {
     for (int e = 0; e < 9; ++e) {
       s_D[j * 9 + e] = D[e];
       a.rot[fj * 9 + e] = (e % 4 == 0 ? 1.0f : 0.0f) + D[e];
-      if (j >= 1) a.pose_feature[((size_t)f * (J - 1) + (j - 1)) * 9 + e] = D[e];
+      if (j >= 1 && a.pose_feature) a.pose_feature[((size_t)f * (J - 1) + (j - 1)) * 9 + e] = D[e];
+      if (j >= 1 && coef) coef[NB + (j - 1) * 9 + e] = D[e];
     }
   }
   __syncthreads();
@@ -149,8 +154,9 @@ __device__ inline void skin_rows(const float* tile, const float* crow, int nrow,
 
 __global__ __launch_bounds__(MORPH_T) void morph_skin_kernel(const float* __restrict__ basis, const float* __restrict__ v_template,
                                                              const float* __restrict__ coef, const float* __restrict__ weights,
-                                                             const float* __restrict__ A, const float* __restrict__ post, int F, int V,
-                                                             int L, int J, int nvb, float* __restrict__ verts) {
+                                                             const float* __restrict__ A, const float* __restrict__ post,
+                                                             const float* __restrict__ transl, int ldt, int F, int V, int L, int J,
+                                                             int nvb, float* __restrict__ verts, float* __restrict__ blend) {
   __shared__ float s_tile[2][SKIN_LC * SKIN_CB];
   __shared__ __align__(16) float s_coef[2][SKIN_LC * SKIN_CLD];
   __shared__ float s_b[SKIN_FT][SKIN_CB];
@@ -231,6 +237,14 @@ __global__ __launch_bounds__(MORPH_T) void morph_skin_kernel(const float* __rest
     float o[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) o[i] = fmaf(T[i * 4], b0, fmaf(T[i * 4 + 1], b1, fmaf(T[i * 4 + 2], b2, T[i * 4 + 3])));
+    if (transl) {  // a branch, not "+ 0": without a translation -0 stays -0
+#pragma unroll
+      for (int i = 0; i < 3; ++i) o[i] += transl[(size_t)f * ldt + i];
+    }
+    if (blend) {
+      float* bd = blend + ((size_t)f * V + gv) * 3;
+      bd[0] = b0, bd[1] = b1, bd[2] = b2;
+    }
     float* dst = verts + ((size_t)f * V + gv) * 3;
     if (post) {
 #pragma unroll
@@ -264,11 +278,11 @@ __global__ __launch_bounds__(MORPH_T) void morph_landmarks_kernel(const float* _
   for (int k = 0; k < 3; ++k) out[(size_t)i * 3 + k] = o[k];
 }
 
+}  // namespace
+
 int morph_fail(const char* who, const char* what) { return mvd_fail((std::string(who) + what).c_str()); }
 
 bool morph_too_big(long long a, long long b, long long c) { return a * b > 0x7fffffffLL / c; }  // a b c >= 2^31, without overflow
-
-}  // namespace
 
 int morph_pose_check(const char* who, const float* betas, const float* pose, const float* j_template, const float* j_dirs,
                      const int* parents, int F, int NB, int J, const float* j_rest, const float* rot, const float* pose_feature,
@@ -286,10 +300,16 @@ int morph_pose_check(const char* who, const float* betas, const float* pose, con
 
 int launch_morph_pose(const float* betas, const float* pose, const float* j_template, const float* j_dirs, const int* parents, int F,
                       int NB, int J, float* j_rest, float* rot, float* pose_feature, float* joints, float* A, hipStream_t s) {
+  return launch_morph_pose_ex(betas, NB, pose, 3 * J, j_template, j_dirs, parents, F, NB, J, j_rest, rot, pose_feature, joints, A, nullptr, s);
+}
+
+int launch_morph_pose_ex(const float* betas, int ldb, const float* pose, int ldp, const float* j_template, const float* j_dirs,
+                         const int* parents, int F, int NB, int J, float* j_rest, float* rot, float* pose_feature, float* joints, float* A,
+                         float* coef, hipStream_t s) {
   MorphPoseArgs a;
   a.betas = betas, a.pose = pose, a.j_template = j_template, a.j_dirs = j_dirs;
-  a.j_rest = j_rest, a.rot = rot, a.pose_feature = pose_feature, a.joints = joints, a.A = A;
-  a.F = F, a.NB = NB, a.J = J;
+  a.j_rest = j_rest, a.rot = rot, a.pose_feature = pose_feature, a.joints = joints, a.A = A, a.coef = coef;
+  a.F = F, a.NB = NB, a.J = J, a.ldb = ldb, a.ldp = ldp;
   for (int j = 0; j < MORPH_MAX_JOINTS; ++j) a.parents[j] = (signed char)(j < J ? parents[j] : -1);
   hipLaunchKernelGGL(morph_pose_kernel, dim3(F), dim3(64), 0, s, a);
   HIP_CHECK_RET(hipGetLastError());
@@ -308,9 +328,15 @@ int morph_skin_check(const char* who, const float* basis, const float* v_templat
 
 int launch_morph_skin(const float* basis, const float* v_template, const float* coef, const float* weights, const float* A,
                       const float* post, int F, int V, int L, int J, float* verts, hipStream_t s) {
+  return launch_morph_skin_ex(basis, v_template, coef, weights, A, post, nullptr, 0, F, V, L, J, verts, nullptr, s);
+}
+
+int launch_morph_skin_ex(const float* basis, const float* v_template, const float* coef, const float* weights, const float* A,
+                         const float* post, const float* transl, int ldt, int F, int V, int L, int J, float* verts, float* blend,
+                         hipStream_t s) {
   const int nvb = (V + SKIN_VB - 1) / SKIN_VB, nft = (F + SKIN_FT - 1) / SKIN_FT;  // nvb nft <= F V / 512 + F + V + 1 < 2^31
   hipLaunchKernelGGL(morph_skin_kernel, dim3((unsigned)nvb * (unsigned)nft), dim3(MORPH_T), 0, s, basis, v_template, coef, weights, A, post,
-                     F, V, L, J, nvb, verts);
+                     transl, ldt, F, V, L, J, nvb, verts, blend);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }

@@ -1,0 +1,50 @@
+// The morphable-model launchers beyond the three of common.h: the extended forward (k_morph.hip) and the backward, data term and
+// optimiser of the fitter (k_morph_bwd.hip; include/mvd.h: mvd_op_morph_*_bwd, mvd_op_morph_fit_*, mvd_morph_fit_run).  The *_check
+// functions are the argument errors (0 = fine) and touch no device; the launchers enqueue on `s` and never synchronise.
+#pragma once
+#include "common.h"
+
+int morph_fail(const char* who, const char* what);
+bool morph_too_big(long long a, long long b, long long c);  // a b c >= 2^31
+
+// the forward with row strides (ldb, ldp, ldt: floats between two frames' betas, poses and translations), an optional coef
+// [F][NB + 9 (J-1)] = betas | pose feature written by the pose kernel, an optional translation and the blended template as output
+int launch_morph_pose_ex(const float* betas, int ldb, const float* pose, int ldp, const float* j_template, const float* j_dirs,
+                         const int* parents, int F, int NB, int J, float* j_rest, float* rot, float* pose_feature, float* joints, float* A,
+                         float* coef, hipStream_t s);
+int launch_morph_skin_ex(const float* basis, const float* v_template, const float* coef, const float* weights, const float* A,
+                         const float* post, const float* transl, int ldt, int F, int V, int L, int J, float* verts, float* blend,
+                         hipStream_t s);
+
+// vertices of a chunk of the vertex phase (and of a block of the data term), basis columns of a slab of the basis phase: the
+// partial buffers are [chunks][F][J 12 + 3] and [slabs][F][L], and both counts follow from V alone
+constexpr int MORPH_BWD_CHUNK = 256, MORPH_BWD_SLAB = 256;
+inline int morph_bwd_chunks(int V) { return (V + MORPH_BWD_CHUNK - 1) / MORPH_BWD_CHUNK; }
+inline int morph_bwd_slabs(int V) { return (int)((3LL * V + MORPH_BWD_SLAB - 1) / MORPH_BWD_SLAB); }
+
+int morph_skin_bwd_check(const char* who, const float* g_y, const float* weights, const float* A, const float* blend, const float* basis,
+                         int F, int V, int L, int NB, int J, const float* g_b, const float* part_a, const float* part_c);
+int launch_morph_skin_bwd(const float* g_y, const float* post, const float* weights, const float* A, const float* blend,
+                          const float* basis, int F, int V, int L, int J, float* g_b, float* part_a, float* part_c, hipStream_t s);
+// g_betas / g_pose / g_transl with their row strides; g_joints may be null
+int morph_pose_bwd_check(const char* who, const float* pose, const float* j_rest, const float* A, const float* j_dirs, const int* parents,
+                         const float* part_a, int nchunk, const float* part_c, int nslab, int F, int NB, int J, const float* g_betas,
+                         const float* g_pose, const float* g_transl);
+int launch_morph_pose_bwd(const float* pose, int ldp, const float* j_rest, const float* A, const float* j_dirs, const int* parents,
+                          const float* part_a, int nchunk, const float* part_c, int nslab, const float* g_joints, int F, int NB, int J,
+                          float* g_betas, int ldgb, float* g_pose, int ldgp, float* g_transl, int ldgt, hipStream_t s);
+int morph_landmarks_bwd_check(const char* who, const float* g_lmk, const int* csr_ptr, const int* csr_ent, const float* lmk_bary, int F,
+                              int V, int M, int n_ent, const float* g_verts);
+int launch_morph_landmarks_bwd(const float* g_lmk, const float* g_in, const int* csr_ptr, const int* csr_ent, const float* lmk_bary, int F,
+                               int V, int M, int n_ent, float* g_verts, hipStream_t s);
+int morph_fit_data_check(const char* who, const float* verts, const float* target, int target_frames, const float* lmk,
+                         const float* target_lmk, int target_lmk_frames, const int* csr_ptr, const int* csr_ent, const float* lmk_bary,
+                         int F, int V, int M, int n_ent, const float* g_y, const float* e_part, const float* E);
+int launch_morph_fit_data(const float* verts, const float* target, int target_frames, const float* vertex_weight, float inv_vw_sum,
+                          const float* lmk, const float* target_lmk, int target_lmk_frames, const float* lmk_weight, float lmk_scale,
+                          const int* csr_ptr, const int* csr_ent, const float* lmk_bary, int F, int V, int M, int n_ent, float* g_y,
+                          float* e_part, float* E, hipStream_t s);
+int morph_fit_update_check(const char* who, const float* p, const float* g, const float* m, const float* v, const float* lr,
+                           const float* lam, const float* p0, int F, int P, int step, float beta1, float beta2, float eps);
+int launch_morph_fit_update(float* p, const float* g, float* m, float* v, const float* lr, const float* lam, const float* p0, int F, int P,
+                            int step, float beta1, float beta2, float eps, hipStream_t s);

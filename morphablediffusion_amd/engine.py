@@ -328,6 +328,339 @@ def op_morph_landmarks(verts, faces, lmk_face, lmk_bary, device=None, lib=None):
     return out
 
 
+# ---- the morphable-model backward and fitter (include/mvd.h: mvd_op_morph_skin_ex, mvd_op_morph_*_bwd, mvd_op_morph_fit_*,
+# mvd_morph_fit_run; csrc/k_morph_bwd.hip): context-free.  Shapes and dtypes are checked before anything is copied.
+def morph_bwd_counts(V, lib=None):
+    """(chunks, slabs) of mvd_op_morph_skin_bwd's two partial buffers for V vertices: both follow from V alone."""
+    lib = lib or L.load()
+    return int(lib.mvd_morph_bwd_chunks(int(V))), int(lib.mvd_morph_bwd_slabs(int(V)))
+
+
+def _skin_args(who, basis, v_template, coef, weights, A, post, n_betas):
+    """The shape checks op_morph_skin makes, shared by the extended forward: (F, V, L, NB, J)."""
+    _float_arg(who, "v_template", v_template, (None, 3))
+    V = v_template.shape[0]
+    _float_arg(who, "basis", basis, (None, 3 * V))
+    Lb = basis.shape[0]
+    _float_arg(who, "coef", coef, (None, Lb))
+    F = coef.shape[0]
+    _float_arg(who, "weights", weights, (V, None))
+    J = weights.shape[1]
+    if J > MORPH_MAX_JOINTS:
+        raise ValueError(f"{who}: at most {MORPH_MAX_JOINTS} joints, got {J}")
+    _float_arg(who, "A", A, (F, J, 3, 4) if torch.is_tensor(A) and A.dim() == 4 else (F, J, 12))
+    NB = Lb - 9 * (J - 1) if n_betas is None else int(n_betas)
+    if NB < 1 or Lb != NB + 9 * (J - 1):
+        raise ValueError(f"{who}: basis has L = {Lb} rows, which must be NB + 9 (J - 1) with NB >= 1 (J = {J}, NB = {NB})")
+    if post is not None:
+        _float_arg(who, "post", post, (3, 4))
+    if F * V * 3 >= 2 ** 31:
+        raise ValueError(f"{who}: F V 3 must be below 2^31, got F = {F}, V = {V}")
+    return F, V, Lb, NB, J
+
+
+def op_morph_skin_ex(basis, v_template, coef, weights, A, post=None, transl=None, n_betas=None, want_blend=False, device=None, lib=None):
+    """mvd_op_morph_skin_ex on ``device`` (default: basis'): op_morph_skin's arguments, an optional transl [F,3] added before post,
+    and with want_blend the blended template [F,V,3] that the backward needs.  Returns verts, or (verts, blend)."""
+    who = "op_morph_skin_ex"
+    F, V, Lb, NB, J = _skin_args(who, basis, v_template, coef, weights, A, post, n_betas)
+    if transl is not None:
+        _float_arg(who, "transl", transl, (F, 3))
+    dev = basis.device if device is None else device
+    bs, vt, cf, wt, a = _f32(basis, dev), _f32(v_template, dev), _f32(coef, dev), _f32(weights, dev), _f32(A, dev)
+    ps, tr = (None if t is None else _f32(t, dev) for t in (post, transl))
+    lib = lib or L.load()
+    verts = torch.full((F, V, 3), float("nan"), device=dev)
+    blend = torch.full((F, V, 3), float("nan"), device=dev) if want_blend else None
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_morph_skin_ex(L.ptr(bs), L.ptr(vt), L.ptr(cf), L.ptr(wt), L.ptr(a), L.ptr(ps), L.ptr(tr), F, V, Lb, NB, J,
+                                         L.ptr(verts), L.ptr(blend), _stream()))
+    return (verts, blend) if want_blend else verts
+
+
+def sum_partials(part):
+    """A partial buffer [n, ...] summed over its first axis in ascending order starting from part[0], in float32: the order of
+    the kernels that consume mvd_op_morph_skin_bwd's partials."""
+    s = part[0].clone()
+    for i in range(1, part.shape[0]):
+        s += part[i]
+    return s
+
+
+def op_morph_skin_bwd(g_y, weights, A, blend, basis, post=None, n_betas=None, device=None, lib=None):
+    """mvd_op_morph_skin_bwd on ``device`` (default: basis'): g_y [F,V,3], weights [V,J], A [F,J,3,4] or [F,J,12], blend [F,V,3]
+    (op_morph_skin_ex's), basis [L,3V], post [3,4] or None.  Returns a dict of float32 device tensors: g_b [F,V,3], part_a
+    [chunks,F,J*12+3], part_c [slabs,F,L], and their ascending sums g_A [F,J,3,4], g_transl [F,3], g_coef [F,L]."""
+    who = "op_morph_skin_bwd"
+    _float_arg(who, "g_y", g_y, (None, None, 3))
+    F, V = g_y.shape[:2]
+    _float_arg(who, "basis", basis, (None, 3 * V))
+    Lb = basis.shape[0]
+    _float_arg(who, "weights", weights, (V, None))
+    J = weights.shape[1]
+    if J > MORPH_MAX_JOINTS:
+        raise ValueError(f"{who}: at most {MORPH_MAX_JOINTS} joints, got {J}")
+    _float_arg(who, "A", A, (F, J, 3, 4) if torch.is_tensor(A) and A.dim() == 4 else (F, J, 12))
+    _float_arg(who, "blend", blend, (F, V, 3))
+    NB = Lb - 9 * (J - 1) if n_betas is None else int(n_betas)
+    if NB < 1 or Lb != NB + 9 * (J - 1):
+        raise ValueError(f"{who}: basis has L = {Lb} rows, which must be NB + 9 (J - 1) with NB >= 1 (J = {J}, NB = {NB})")
+    if post is not None:
+        _float_arg(who, "post", post, (3, 4))
+    lib = lib or L.load()
+    nchunk, nslab = morph_bwd_counts(V, lib)
+    if F * V * 3 >= 2 ** 31 or nslab * F * Lb >= 2 ** 31 or nchunk * F * (J * 12 + 3) >= 2 ** 31:
+        raise ValueError(f"{who}: F V 3 and the partial buffers must be below 2^31 elements, got F = {F}, V = {V}")
+    dev = basis.device if device is None else device
+    gy, wt, a, bl, bs = _f32(g_y, dev), _f32(weights, dev), _f32(A, dev), _f32(blend, dev), _f32(basis, dev)
+    ps = None if post is None else _f32(post, dev)
+    nan = float("nan")
+    out = {"g_b": torch.full((F, V, 3), nan, device=dev), "part_a": torch.full((nchunk, F, J * 12 + 3), nan, device=dev),
+           "part_c": torch.full((nslab, F, Lb), nan, device=dev)}
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_morph_skin_bwd(L.ptr(gy), L.ptr(ps), L.ptr(wt), L.ptr(a), L.ptr(bl), L.ptr(bs), F, V, Lb, NB, J,
+                                          L.ptr(out["g_b"]), L.ptr(out["part_a"]), L.ptr(out["part_c"]), _stream()))
+    sa = sum_partials(out["part_a"])
+    out["g_A"], out["g_transl"], out["g_coef"] = sa[:, :J * 12].reshape(F, J, 3, 4), sa[:, J * 12:], sum_partials(out["part_c"])
+    return out
+
+
+def op_morph_pose_bwd(pose, j_rest, A, j_dirs, parents, part_a, part_c, g_joints=None, device=None, lib=None):
+    """mvd_op_morph_pose_bwd on ``device`` (default: pose's): pose [F,J,3], j_rest [F,J,3] and A [F,J,3,4] or [F,J,12] as
+    op_morph_pose returned them, j_dirs [NB,J*3], parents, the partials of op_morph_skin_bwd (part_a [chunks,F,J*12+3], part_c
+    [slabs,F,NB+9(J-1)]; a single "chunk" holding g_A | g_transl and a single "slab" holding g_coef are the plain adjoints),
+    g_joints [F,J,3] or None.  Returns {"betas" [F,NB], "pose" [F,J,3], "transl" [F,3]}."""
+    who = "op_morph_pose_bwd"
+    _float_arg(who, "pose", pose, (None, None, 3))
+    F, J = pose.shape[:2]
+    if J > MORPH_MAX_JOINTS:
+        raise ValueError(f"{who}: at most {MORPH_MAX_JOINTS} joints, got {J}")
+    _float_arg(who, "j_rest", j_rest, (F, J, 3))
+    _float_arg(who, "A", A, (F, J, 3, 4) if torch.is_tensor(A) and A.dim() == 4 else (F, J, 12))
+    _float_arg(who, "j_dirs", j_dirs, (None, J * 3))
+    NB = j_dirs.shape[0]
+    par = morph_parents(who, parents, J)
+    _float_arg(who, "part_a", part_a, (None, F, J * 12 + 3))
+    _float_arg(who, "part_c", part_c, (None, F, NB + 9 * (J - 1)))
+    if g_joints is not None:
+        _float_arg(who, "g_joints", g_joints, (F, J, 3))
+    if max(part_a.numel(), part_c.numel()) >= 2 ** 31:
+        raise ValueError(f"{who}: the partial buffers must be below 2^31 elements")
+    dev = pose.device if device is None else device
+    p, jr, a, jd, pa, pc = (_f32(t, dev) for t in (pose, j_rest, A, j_dirs, part_a, part_c))
+    gj = None if g_joints is None else _f32(g_joints, dev)
+    lib = lib or L.load()
+    nan = float("nan")
+    out = {"betas": torch.full((F, NB), nan, device=dev), "pose": torch.full((F, J, 3), nan, device=dev),
+           "transl": torch.full((F, 3), nan, device=dev)}
+    par_c = (C.c_int32 * J)(*par)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_morph_pose_bwd(L.ptr(p), L.ptr(jr), L.ptr(a), L.ptr(jd), C.addressof(par_c), L.ptr(pa), pa.shape[0], L.ptr(pc),
+                                          pc.shape[0], L.ptr(gj), F, NB, J, L.ptr(out["betas"]), L.ptr(out["pose"]),
+                                          L.ptr(out["transl"]), _stream()))
+    return out
+
+
+def landmark_csr(faces, lmk_face, lmk_bary, V):
+    """The vertex -> (landmark, corner) table of a static embedding, built on the host: (csr_ptr [V+1], csr_ent [3M]) int32 numpy
+    arrays, the entries landmark * 3 + corner of vertex v at csr_ent[csr_ptr[v] : csr_ptr[v+1]], ascending."""
+    import numpy as np
+    faces, lmk_face = np.asarray(faces, dtype=np.int64), np.asarray(lmk_face, dtype=np.int64).reshape(-1)
+    vert = faces[lmk_face].reshape(-1)  # vertex of entry landmark * 3 + corner
+    if vert.size and (vert.min() < 0 or vert.max() >= V):
+        raise ValueError(f"landmark_csr: a landmark's face names a vertex outside 0..{V - 1}")
+    order = np.argsort(vert, kind="stable")  # stable: ascending entries within a vertex
+    ptr = np.zeros(V + 1, dtype=np.int64)
+    np.add.at(ptr, vert + 1, 1)
+    return np.cumsum(ptr).astype(np.int32), order.astype(np.int32)
+
+
+def _csr_args(who, csr_ptr, csr_ent, lmk_bary, V):
+    _i32("csr_ptr", csr_ptr, (V + 1,), who)
+    _i32("csr_ent", csr_ent, (None,), who)
+    _float_arg(who, "lmk_bary", lmk_bary, (None, 3))
+    if csr_ent.shape[0] < 1:
+        raise ValueError(f"{who}: the landmark table is empty")
+    return lmk_bary.shape[0], csr_ent.shape[0]
+
+
+def op_morph_landmarks_bwd(g_lmk, csr_ptr, csr_ent, lmk_bary, V, g_in=None, device=None, lib=None):
+    """mvd_op_morph_landmarks_bwd on ``device`` (default: g_lmk's): g_lmk [F,M,3], the table of landmark_csr as int32 tensors,
+    lmk_bary [M,3], g_in [F,V,3] or None.  Returns g_verts [F,V,3] = g_in + the gathered landmark adjoint."""
+    who = "op_morph_landmarks_bwd"
+    V = int(V)
+    M, n_ent = _csr_args(who, csr_ptr, csr_ent, lmk_bary, V)
+    _float_arg(who, "g_lmk", g_lmk, (None, M, 3))
+    F = g_lmk.shape[0]
+    if g_in is not None:
+        _float_arg(who, "g_in", g_in, (F, V, 3))
+    if F * V * 3 >= 2 ** 31 or F * M * 3 >= 2 ** 31:
+        raise ValueError(f"{who}: F V 3 and F M 3 must be below 2^31")
+    dev = g_lmk.device if device is None else device
+    gl, bc = _f32(g_lmk, dev), _f32(lmk_bary, dev)
+    gi = None if g_in is None else _f32(g_in, dev)
+    cp, ce = (t.detach().to(dev).contiguous() for t in (csr_ptr, csr_ent))
+    lib = lib or L.load()
+    out = torch.full((F, V, 3), float("nan"), device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_morph_landmarks_bwd(L.ptr(gl), L.ptr(gi), L.ptr(cp), L.ptr(ce), L.ptr(bc), F, V, M, n_ent, L.ptr(out), _stream()))
+    return out
+
+
+def _fit_data_args(who, F, V, target, vertex_weight, lmk, target_lmk, lmk_weight, lmk_lambda, csr, dev):
+    """The data term's arguments checked and on the device: (target, frames, vw, inv_vw_sum, lmk, target_lmk, frames, lw, lmk_scale,
+    csr_ptr, csr_ent, lmk_bary, M, n_ent).  The two weight sums are taken here, on the host, once."""
+    if target is None and target_lmk is None:
+        raise ValueError(f"{who}: give target vertices, target landmarks or both")
+    tg = vw = tl = lw = cp = ce = bc = None
+    tf = tlf = 1
+    inv_vw, scale, M, n_ent = 0.0, 0.0, 0, 0
+    if vertex_weight is not None and target is None:
+        raise ValueError(f"{who}: vertex_weight without target vertices")
+    if target is not None:
+        _float_arg(who, "target", target, (None, V, 3))
+        tf = target.shape[0]
+        if tf not in (1, F):
+            raise ValueError(f"{who}: target must have 1 or F = {F} frames, got {tf}")
+        tg, total = _f32(target, dev), float(V)
+        if vertex_weight is not None:
+            _float_arg(who, "vertex_weight", vertex_weight, (V,))
+            vw = _f32(vertex_weight, dev)
+            total = float(vw.double().sum())
+            if not (float(vw.min()) >= 0.0 and 0.0 < total < float("inf")):
+                raise ValueError(f"{who}: vertex_weight must be non-negative with a positive finite sum")
+        inv_vw = 1.0 / total
+    if lmk_weight is not None and target_lmk is None:
+        raise ValueError(f"{who}: landmark_weight without target landmarks")
+    if target_lmk is not None:
+        if csr is None or lmk is None:
+            raise ValueError(f"{who}: target landmarks need a model with a landmark embedding")
+        cp, ce, bc = csr
+        M, n_ent = _csr_args(who, cp, ce, bc, V)
+        _float_arg(who, "lmk", lmk, (F, M, 3))
+        _float_arg(who, "target_lmk", target_lmk, (None, M, 3))
+        tlf = target_lmk.shape[0]
+        if tlf not in (1, F):
+            raise ValueError(f"{who}: target_lmk must have 1 or F = {F} frames, got {tlf}")
+        lmk_lambda = float(lmk_lambda)
+        if not (0.0 <= lmk_lambda < float("inf")):
+            raise ValueError(f"{who}: lmk_lambda must be non-negative and finite, got {lmk_lambda}")
+        tl, total = _f32(target_lmk, dev), float(M)
+        if lmk_weight is not None:
+            _float_arg(who, "lmk_weight", lmk_weight, (M,))
+            lw = _f32(lmk_weight, dev)
+            total = float(lw.double().sum())
+            if not (float(lw.min()) >= 0.0 and 0.0 < total < float("inf")):
+                raise ValueError(f"{who}: lmk_weight must be non-negative with a positive finite sum")
+        scale = lmk_lambda / total
+        lmk, bc = _f32(lmk, dev), _f32(bc, dev)
+        cp, ce = (t.detach().to(dev).contiguous() for t in (cp, ce))
+    if F > 65535 or F * V * 3 >= 2 ** 31:
+        raise ValueError(f"{who}: at most 65535 frames and F V 3 below 2^31, got F = {F}, V = {V}")
+    return tg, tf, vw, inv_vw, (lmk if target_lmk is not None else None), tl, tlf, lw, scale, cp, ce, bc, M, n_ent
+
+
+def op_morph_fit_data(verts, target=None, vertex_weight=None, lmk=None, target_lmk=None, lmk_weight=None, lmk_lambda=1.0, csr=None,
+                      device=None, lib=None):
+    """mvd_op_morph_fit_data on ``device`` (default: verts'): verts [F,V,3]; target [F,V,3] or [1,V,3] with an optional
+    vertex_weight [V]; lmk [F,M,3] (the landmarks of verts), target_lmk [F,M,3] or [1,M,3], an optional lmk_weight [M] and
+    csr = (csr_ptr, csr_ent, lmk_bary) as int32 / float tensors.  E_f = sum_v w |y - t|^2 / sum_v w + lmk_lambda sum_m w' |l -
+    l'|^2 / sum_m w'.  Returns (E [F], g_y [F,V,3] = dE_f / dverts_f with the landmark term gathered through the table)."""
+    who = "op_morph_fit_data"
+    _float_arg(who, "verts", verts, (None, None, 3))
+    F, V = verts.shape[:2]
+    dev = verts.device if device is None else device
+    tg, tf, vw, inv_vw, lm, tl, tlf, lw, scale, cp, ce, bc, M, n_ent = _fit_data_args(who, F, V, target, vertex_weight, lmk, target_lmk,
+                                                                                      lmk_weight, lmk_lambda, csr, dev)
+    y = _f32(verts, dev)
+    lib = lib or L.load()
+    nan = float("nan")
+    g_y, E = torch.full((F, V, 3), nan, device=dev), torch.full((F,), nan, device=dev)
+    e_part = torch.full((morph_bwd_counts(V, lib)[0], F), nan, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_morph_fit_data(L.ptr(y), L.ptr(tg), tf, L.ptr(vw), inv_vw, L.ptr(lm), L.ptr(tl), tlf, L.ptr(lw), scale,
+                                          L.ptr(cp), L.ptr(ce), L.ptr(bc), F, V, M, n_ent, L.ptr(g_y), L.ptr(e_part), L.ptr(E), _stream()))
+    return E, g_y
+
+
+ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8  # torch.optim.Adam's defaults
+
+
+def _fit_update_args(who, p, m, v, lr, lam, p0):
+    for name, t in (("p", p), ("m", m), ("v", v)):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 or not t.is_contiguous() or not t.is_cuda or \
+                t.shape != p.shape or t.device != p.device:
+            raise ValueError(f"{who}: {name} must be a contiguous float32 device tensor [F,P] (updated in place), got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    F, P = p.shape
+    if F < 1 or P < 1 or F * P >= 2 ** 31:
+        raise ValueError(f"{who}: p must be [F,P] with F, P >= 1 and F P < 2^31, got {tuple(p.shape)}")
+    for name, t in (("lr", lr), ("lam", lam), ("p0", p0)):
+        _float_arg(who, name, t, (P,))
+    return F, P
+
+
+def op_morph_fit_update(p, g, m, v, lr, lam, p0, step, betas=ADAM_BETAS, eps=ADAM_EPS, lib=None):
+    """mvd_op_morph_fit_update: p, m, v [F,P] float32 device tensors, updated IN PLACE; g [F,P]; lr, lam, p0 [P]; step >= 1.
+    g' = g + 2 lam (p - p0), then torch.optim.Adam's step; a column with lr == 0 keeps the bits of p, m and v."""
+    who = "op_morph_fit_update"
+    F, P = _fit_update_args(who, p, m, v, lr, lam, p0)
+    _float_arg(who, "g", g, (F, P))
+    step, b1, b2, eps = int(step), float(betas[0]), float(betas[1]), float(eps)
+    if step < 1 or not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0 and eps > 0.0):
+        raise ValueError(f"{who}: step must be at least 1, betas in [0, 1) and eps positive, got {step}, {betas}, {eps}")
+    dev = p.device
+    gg, lrd, lamd, p0d = (_f32(t, dev) for t in (g, lr, lam, p0))
+    lib = lib or L.load()
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_morph_fit_update(L.ptr(p), L.ptr(gg), L.ptr(m), L.ptr(v), L.ptr(lrd), L.ptr(lamd), L.ptr(p0d), F, P, step,
+                                            b1, b2, eps, _stream()))
+
+
+def morph_fit_run(model, p, m, v, lr, lam, p0, iters, target=None, vertex_weight=None, target_lmk=None, lmk_weight=None, lmk_lambda=1.0,
+                  post=None, step0=0, betas=ADAM_BETAS, eps=ADAM_EPS, lib=None):
+    """mvd_morph_fit_run: ``iters`` Adam iterations enqueued without a host synchronisation between them.  model: an object with
+    the device tensors of morphable.MorphableModel (basis, v_template, weights, j_template, j_dirs, parents, faces, lmk_face,
+    lmk_bary, csr_ptr, csr_ent).  p, m, v [F,P] with P = NB + 3 J + 3 (betas | pose | transl), float32 on the model's device,
+    updated IN PLACE; lr, lam, p0 [P].  Returns loss_history [iters,F]."""
+    who = "morph_fit_run"
+    F, P = _fit_update_args(who, p, m, v, lr, lam, p0)
+    V, NB, J = model.v_template.shape[0], model.j_dirs.shape[0], model.weights.shape[1]
+    if P != NB + 3 * J + 3:
+        raise ValueError(f"{who}: p must have P = NB + 3 J + 3 = {NB + 3 * J + 3} columns, got {P}")
+    dev = p.device
+    if model.basis.device != dev:
+        raise ValueError(f"{who}: the model is on {model.basis.device}, the parameters on {dev}")
+    iters, step0, b1, b2, eps = int(iters), int(step0), float(betas[0]), float(betas[1]), float(eps)
+    if iters < 1 or step0 < 0 or iters * F >= 2 ** 31 or not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0 and eps > 0.0):
+        raise ValueError(f"{who}: iters must be at least 1 (iters F < 2^31), step0 at least 0, betas in [0, 1), eps positive")
+    if post is not None:
+        _float_arg(who, "post", post, (3, 4))
+    use_lmk = target_lmk is not None
+    csr = (model.csr_ptr, model.csr_ent, model.lmk_bary) if use_lmk and getattr(model, "csr_ptr", None) is not None else None
+    lmk_stub = torch.empty((F, model.lmk_bary.shape[0], 3), device=dev) if csr is not None else None  # shape check only
+    tg, tf, vw, inv_vw, _, tl, tlf, lw, scale, cp, ce, bc, M, n_ent = _fit_data_args(who, F, V, target, vertex_weight, lmk_stub, target_lmk,
+                                                                                     lmk_weight, lmk_lambda, csr, dev)
+    par = morph_parents(who, model.parents, J)
+    lrd, lamd, p0d = (_f32(t, dev) for t in (lr, lam, p0))
+    ps = None if post is None else _f32(post, dev)
+    lib = lib or L.load()
+    n_ws_c = C.c_int64(0)
+    L.check(lib.mvd_morph_fit_workspace(F, V, NB, J, M, C.addressof(n_ws_c)))
+    n_ws = int(n_ws_c.value)
+    ws = torch.full((n_ws,), float("nan"), device=dev)
+    hist = torch.full((iters, F), float("nan"), device=dev)
+    par_c = (C.c_int32 * J)(*par)
+    fc, lf = (model.faces, model.lmk_face) if use_lmk else (None, None)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_morph_fit_run(L.ptr(model.basis), L.ptr(model.v_template), L.ptr(model.weights), L.ptr(model.j_template),
+                                      L.ptr(model.j_dirs), C.addressof(par_c), L.ptr(ps), L.ptr(fc), L.ptr(lf), L.ptr(bc), L.ptr(cp),
+                                      L.ptr(ce), F, V, NB, J, 0 if fc is None else fc.shape[0], M, n_ent, L.ptr(tg), tf, L.ptr(vw),
+                                      inv_vw, L.ptr(tl), tlf, L.ptr(lw), scale, L.ptr(p), L.ptr(m), L.ptr(v), L.ptr(lrd), L.ptr(lamd),
+                                      L.ptr(p0d), iters, step0, b1, b2, eps, L.ptr(ws), n_ws, L.ptr(hist), _stream()))
+    return hist
+
+
 # ---- the sparse voxel CNN's kernels one at a time (include/mvd.h: mvd_op_sparse_conv ...): context-free like op_train_loss.
 # w: the 3x3x3 kernel in checkpoint layout 0 [Cout,Cin,3,3,3], 1 [Cout,3,3,3,Cin] or 2 [3,3,3,Cin,Cout]; nbr [n_out,27] int32.
 SPARSE_FORMS = ("site", "mfma")  # form of mvd_op_sparse_conv / mvd_op_sparse_conv_bwd, by index

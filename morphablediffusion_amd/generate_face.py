@@ -28,6 +28,12 @@ Differences, all outside the denoising path and stated here:
     ``<input>_<exp>.png`` as before, several write ``<input>_<exp>_fNN.png`` each (and the --export_mesh / --mesh_overlay /
     --gt_dir files with the same ``_fNN``); frames are sampled --frame_batch at a time.  With none of these flags the program
     does exactly what it did without them.
+  * --flame_model MODEL --fit_mesh MESH.{ply,obj} (not reference flags; morphable.py, csrc/k_morph_bwd.hip) fit the model's
+    parameters to a mesh of the model's topology, in the model's frame (what metrical-tracker exports), with Adam on the device
+    (--fit_iters, --fit_lr), and write ``<input>_<exp>_fit.npz`` (shape, expression, global_pose, neck, jaw, eyes, transl) and
+    ``<input>_<exp>_fit.json`` (RMS residual, iterations).  Alone, the fitted mesh conditions the views.  With --flame_params
+    the fit takes the place of --neutral_params: the --frames K frames sweep from the fit to the fitted identity, global pose
+    and translation combined with the given expression and jaw (and neck / eyes when given).
 """
 import argparse
 import json
@@ -171,6 +177,10 @@ def build_parser():
                    help="not a reference flag: an .npz like --flame_params; with --frames K the frames sweep from it to --flame_params")
     p.add_argument("--frames", type=int, default=1, help="not a reference flag: frames of the sweep (needs --neutral_params)")
     p.add_argument("--frame_batch", type=int, default=1, help="not a reference flag: frames sampled in one batch")
+    p.add_argument("--fit_mesh", type=str, default=None,
+                   help="not a reference flag: a mesh file of the model's topology; --flame_model's parameters are fitted to it")
+    p.add_argument("--fit_iters", type=int, default=300, help="not a reference flag: Adam iterations of --fit_mesh")
+    p.add_argument("--fit_lr", type=float, default=0.05, help="not a reference flag: Adam's learning rate for --fit_mesh")
     p.add_argument("--flame_n_shape", type=int, default=None,
                    help="not a reference flag: identity columns of the model's shapedirs to keep (MICA: 300; default: all)")
     p.add_argument("--flame_n_exp", type=int, default=None,
@@ -179,13 +189,27 @@ def build_parser():
 
 
 FLAME_PARAM_KEYS = ("shape", "expression", "global_pose", "neck", "jaw", "eyes")
+FLAME_FILE_KEYS = FLAME_PARAM_KEYS + ("transl",)  # what a parameter file may hold: MorphableModel.flame's arguments
 
 
 def parse_args(argv=None):
     """build_parser().parse_args plus the rules between the flags: --mesh alone as ever; --flame_model and --flame_params go
-    together and replace --mesh; --neutral_params and --frames > 1 go together and need them."""
+    together and replace --mesh; --neutral_params and --frames > 1 go together and need them; --fit_mesh needs --flame_model,
+    excludes --mesh and --neutral_params, and with --flame_params takes the place of the neutral end."""
     p = build_parser()
     flags = p.parse_args(argv)
+    if flags.fit_mesh:
+        if not flags.flame_model:
+            p.error("--fit_mesh needs --flame_model")
+        if flags.mesh or flags.neutral_params:
+            p.error("--fit_mesh excludes --mesh and --neutral_params (the fit is the neutral end)")
+        if flags.fit_iters < 1 or not flags.fit_lr > 0:
+            p.error("--fit_iters must be at least 1 and --fit_lr positive")
+        if flags.frames < 1 or flags.frame_batch < 1:
+            p.error("--frames and --frame_batch must be at least 1")
+        if flags.frames > 1 and not flags.flame_params:
+            p.error("--frames K > 1 with --fit_mesh needs --flame_params (the other end of the sweep)")
+        return flags
     flame = [flags.flame_model, flags.flame_params]
     if not any(flame) and (flags.neutral_params or flags.frames != 1 or flags.frame_batch != 1):
         p.error("--neutral_params, --frames and --frame_batch need --flame_model and --flame_params")
@@ -204,19 +228,49 @@ def parse_args(argv=None):
 
 
 def load_flame_params(path):
-    """{key: float64 array} of the FLAME_PARAM_KEYS an .npz holds; any other key is an error (a misspelt name would be zeros)."""
+    """{key: float64 array} of the FLAME_FILE_KEYS an .npz holds; any other key is an error (a misspelt name would be zeros)."""
     with np.load(path, allow_pickle=False) as z:
-        unknown = [k for k in z.files if k not in FLAME_PARAM_KEYS]
+        unknown = [k for k in z.files if k not in FLAME_FILE_KEYS]
         if unknown:
-            raise ValueError(f"{path}: unknown parameter names {unknown}; known: {list(FLAME_PARAM_KEYS)}")
+            raise ValueError(f"{path}: unknown parameter names {unknown}; known: {list(FLAME_FILE_KEYS)}")
         return {k: np.asarray(z[k], dtype=np.float64) for k in z.files}
 
 
-def flame_frames(flags, device):
-    """The conditioning meshes of --flame_model / --flame_params: (verts [F,Nv,3] on the device in the frame of
-    batch["vertices"], model-frame vertices [F,Nv,3] as a mesh file would store them, faces [Nf,3] or None)."""
+def fit_to_mesh(fm, flags, stem):
+    """--fit_mesh: the model's parameters fitted to the mesh file (same topology, the model's frame: no post).  Writes
+    <stem>_fit.npz and <stem>_fit.json; returns {key: float64 vector} over FLAME_FILE_KEYS."""
+    target = read_mesh_vertices(flags.fit_mesh)
+    if target.shape[0] != fm.V:
+        raise ValueError(f"{flags.fit_mesh}: the mesh has {target.shape[0]} vertices, the model {fm.V}: fitting needs the model's topology")
+    fit = fm.fit_flame(target_vertices=torch.from_numpy(target)[None], iters=flags.fit_iters, lr=flags.fit_lr)
+    params = {k: fit[k][0].cpu().numpy().astype(np.float64) for k in FLAME_FILE_KEYS}
+    np.savez(f"{stem}_fit.npz", **params)
+    with open(f"{stem}_fit.json", "w") as f:
+        json.dump({"mesh": str(flags.fit_mesh), "vertices": int(fm.V), "iterations": int(flags.fit_iters), "lr": float(flags.fit_lr),
+                   "rms": float(fit["rms"][0]), "loss_first": float(fit["loss_history"][0, 0]),
+                   "loss_last": float(fit["loss_history"][-1, 0])}, f, indent=2)
+    return params
+
+
+def flame_frames(flags, device, stem=None):
+    """The conditioning meshes of --flame_model with --flame_params and / or --fit_mesh: (verts [F,Nv,3] on the device in the
+    frame of batch["vertices"], model-frame vertices [F,Nv,3] as a mesh file would store them, faces [Nf,3] or None).  stem:
+    where --fit_mesh writes its files (<stem>_fit.npz / .json)."""
     from . import morphable as MM
     fm = MM.MorphableModel.load(flags.flame_model, n_shape=flags.flame_n_shape, n_exp=flags.flame_n_exp, device=device)
+    if getattr(flags, "fit_mesh", None):
+        params = fit_to_mesh(fm, flags, stem)
+        if flags.flame_params:
+            given = load_flame_params(flags.flame_params)
+            if any(v.ndim > 1 for v in given.values()):
+                raise ValueError(f"{flags.flame_params}: a sweep goes to ONE target, parameters with a frame axis cannot be swept to")
+            # the fitted identity, global pose and translation with the given expression and jaw (neck, eyes when given)
+            end = dict(params, expression=given.get("expression", np.zeros_like(params["expression"])),
+                       jaw=given.get("jaw", np.zeros(3)), **{k: given[k] for k in ("neck", "eyes") if k in given})
+            params = MM.interpolate_params(params, end, flags.frames)
+        verts = fm.flame(post=MM.flame_alignment(), **params)["vertices"]
+        stored = fm.flame(**params)["vertices"]
+        return verts, stored.cpu().numpy().astype(np.float64), None if fm.faces is None else fm.faces.cpu().numpy()
     params = load_flame_params(flags.flame_params)
     if flags.neutral_params:
         if any(v.ndim > 1 for v in params.values()):
@@ -335,7 +389,7 @@ def run_flame(flags, model, sampler, cams, input_img, img_name, exp_name, want_m
     refused for more than one frame."""
     from PIL import Image
     from . import morphable as MM
-    verts, stored, faces = flame_frames(flags, model.device)
+    verts, stored, faces = flame_frames(flags, model.device, stem=str(Path(flags.output_dir) / f"{img_name}_{exp_name}"))
     F = verts.shape[0]
     if want_mesh and faces is None:
         raise ValueError(f"{flags.flame_model}: --export_mesh / --mesh_overlay need a model file with faces ('f')")

@@ -42,7 +42,7 @@ def _ctype(decl, func, is_return=False):
 
 def parse_header(path=HEADER):
     """{name: (restype, [argtypes])} of every function include/mvd.h declares: the ONE place an entry point's signature is
-    written (c_api.hip, c_api_hooks.hip and engine_train.hip, which define them, are compiled against the same header).  The
+    written (c_api.hip, c_api_morph.hip, c_api_hooks.hip and engine_train.hip, which define them, are compiled against the same header).  The
     header keeps to one declaration style -- `RET name(ARGS);`, no macros in signatures, `(void)` for an empty list -- so this
     is a regular expression, not a C parser; a type outside the table above raises MvdError."""
     try:

@@ -11,7 +11,11 @@ vertices go straight into ``batch.build_batch`` / ``stack_batches`` / ``model.sa
     batch = frames_to_batch(input_image, out["vertices"], device="cuda:0")
 
 Units: FLAME's forward is in metres, and so are the mesh files of the reference pipeline, so ``unit_scale``
-defaults to 1.0.  Not here: the pose-dependent contour landmarks, fitting parameters to a mesh, vertex normals on the device.
+defaults to 1.0.  The inverse is here too (csrc/k_morph_bwd.hip): ``vjp`` is the vector-Jacobian product of the forward,
+``differentiable`` the same as a torch.autograd.Function, ``fit`` / ``fit_flame`` run Adam on the device against target vertices
+and 3-D landmarks.  Not here: the pose-dependent contour landmarks, vertex normals on the device.
+
+    fit = fm.fit_flame(target_vertices=mesh_vertices, free=("expression", "jaw"), prior={"shape": mica_shape})
 """
 import io
 import pickle
@@ -167,7 +171,7 @@ class MorphableModel:
         self.weights = f32(W)
         self.j_template = f32(Jr @ vt * s)
         self.j_dirs = f32(np.einsum("jv,vkn->njk", Jr, S).reshape(NB, 3 * J) * s)
-        self.faces = self.lmk_face = self.lmk_bary = None
+        self.faces = self.lmk_face = self.lmk_bary = self.csr_ptr = self.csr_ent = None
         if faces is not None:
             fc = np.asarray(_plain(faces)).astype(np.int64)
             if fc.ndim != 2 or fc.shape[1] != 3 or fc.shape[0] < 1 or fc.min() < 0 or fc.max() >= V:
@@ -182,6 +186,8 @@ class MorphableModel:
             if len(lf) < 1 or lb.shape != (len(lf), 3) or lf.min() < 0 or lf.max() >= self.faces.shape[0]:
                 raise ValueError(f"{who}: lmk_face must be [M] face indices and lmk_bary [M,3], got {lf.shape} and {lb.shape}")
             self.lmk_face, self.lmk_bary = torch.from_numpy(lf.astype(np.int32)).to(self.device), f32(lb)
+            # the backward of the landmarks is a gather through this table: entries ascending, no atomics
+            self.csr_ptr, self.csr_ent = (torch.from_numpy(a).to(self.device) for a in E.landmark_csr(fc, lf, lb, V))
         return self
 
     @classmethod
@@ -206,11 +212,8 @@ class MorphableModel:
         return cls.from_arrays(d["v_template"], S, d["posedirs"], d["J_regressor"], kt[0] if kt.ndim == 2 else kt, d["weights"],
                                faces=d.get("f"), device=device, unit_scale=unit_scale, n_shape=n_shape, **lm)
 
-    def forward(self, betas, pose, post=None) -> Dict[str, Optional[torch.Tensor]]:
-        """betas [F,NB], pose [F,J,3] or [F,3J] (axis-angle), post [3,4] or None: an affine applied to the vertices in the
-        skinning pass (flame_alignment()).  Returns device tensors: vertices [F,V,3], joints [F,J,3] (the posed joints, in the
-        model's frame: post is not applied to them), landmarks [F,M,3] (of the returned vertices) or None without an embedding."""
-        who = "MorphableModel.forward"
+    def _params(self, who, betas, pose, transl=None):
+        """(betas [F,NB], pose [F,J,3], transl [F,3] or None) as float32 tensors on the model's device, shapes checked."""
         if self.device.type != "cuda":
             raise ValueError(f"{who}: the model is on {self.device}; the forward runs on the GPU only (model.to('cuda:0'))")
         if not torch.is_tensor(betas) or not torch.is_tensor(pose):
@@ -222,18 +225,209 @@ class MorphableModel:
             pose = pose.reshape(F, self.J, 3)
         if tuple(pose.shape) != (F, self.J, 3):
             raise ValueError(f"{who}: pose must be [F,{self.J},3] or [F,{3 * self.J}] with F = {F}, got {tuple(pose.shape)}")
+        if transl is not None:
+            transl = transl if torch.is_tensor(transl) else torch.as_tensor(np.asarray(transl))
+            transl = transl.reshape(1, 3).expand(F, 3) if transl.dim() == 1 and transl.numel() == 3 else transl
+            if tuple(transl.shape) != (F, 3):
+                raise ValueError(f"{who}: transl must be [3] or [F,3] with F = {F}, got {tuple(transl.shape)}")
+        f32 = lambda t: None if t is None else t.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        return f32(betas), f32(pose), f32(transl)
+
+    def _run(self, betas, pose, post, transl, want_blend):
+        """The three forward launches on checked parameters; with want_blend what the backward needs is kept."""
         dev = self.device
-        betas = betas.detach().to(device=dev, dtype=torch.float32).contiguous()
         p = E.op_morph_pose(betas, pose, self.j_template, self.j_dirs, self.parents, device=dev)
         coef = torch.cat([betas, p["pose_feature"]], 1) if self.J > 1 else betas
-        verts = E.op_morph_skin(self.basis, self.v_template, coef, self.weights, p["A"], post=post, n_betas=self.NB, device=dev)
+        blend = None
+        if transl is None and not want_blend:  # what the forward has always launched
+            verts = E.op_morph_skin(self.basis, self.v_template, coef, self.weights, p["A"], post=post, n_betas=self.NB, device=dev)
+        else:
+            r = E.op_morph_skin_ex(self.basis, self.v_template, coef, self.weights, p["A"], post=post, transl=transl, n_betas=self.NB,
+                                   want_blend=want_blend, device=dev)
+            verts, blend = r if want_blend else (r, None)
         lmk = None if self.lmk_face is None else E.op_morph_landmarks(verts, self.faces, self.lmk_face, self.lmk_bary, device=dev)
-        return {"vertices": verts, "joints": p["joints"], "landmarks": lmk}
+        return {"vertices": verts, "joints": p["joints"], "landmarks": lmk, "pose": pose, "j_rest": p["j_rest"], "A": p["A"],
+                "blend": blend}
 
-    def flame(self, shape, expression=None, global_pose=None, neck=None, jaw=None, eyes=None, post=None):
+    def forward(self, betas, pose, post=None, transl=None) -> Dict[str, Optional[torch.Tensor]]:
+        """betas [F,NB], pose [F,J,3] or [F,3J] (axis-angle), post [3,4] or None: an affine applied to the vertices in the
+        skinning pass (flame_alignment()); transl [F,3] or [3] or None: a translation in the model's frame, added before post.
+        Returns device tensors: vertices [F,V,3], joints [F,J,3] (the posed joints, in the model's frame: neither transl nor post
+        is applied to them), landmarks [F,M,3] (of the returned vertices) or None without an embedding."""
+        betas, pose, transl = self._params("MorphableModel.forward", betas, pose, transl)
+        r = self._run(betas, pose, post, transl, False)
+        return {k: r[k] for k in ("vertices", "joints", "landmarks")}
+
+    def _backward(self, saved, post, grad_vertices, grad_joints, grad_landmarks):
+        """The backward launches on what _run(..., want_blend=True) kept: {"betas", "pose", "transl"} gradients."""
+        who, dev = "MorphableModel.vjp", self.device
+        F = saved["pose"].shape[0]
+        for name, g, shape in (("grad_vertices", grad_vertices, (F, self.V, 3)), ("grad_joints", grad_joints, (F, self.J, 3))):
+            if g is not None and (not torch.is_tensor(g) or tuple(g.shape) != shape):
+                raise ValueError(f"{who}: {name} must be a tensor {list(shape)}, got {tuple(getattr(g, 'shape', ()))}")
+        g_y = grad_vertices
+        if grad_landmarks is not None:
+            if self.csr_ptr is None:
+                raise ValueError(f"{who}: grad_landmarks given, and the model has no landmark embedding")
+            g_y = E.op_morph_landmarks_bwd(grad_landmarks, self.csr_ptr, self.csr_ent, self.lmk_bary, self.V, g_in=g_y, device=dev)
+        if g_y is None:
+            if grad_joints is None:
+                raise ValueError(f"{who}: give at least one of grad_vertices, grad_joints, grad_landmarks")
+            g_y = torch.zeros((F, self.V, 3), device=dev)
+        sb = E.op_morph_skin_bwd(g_y, self.weights, saved["A"], saved["blend"], self.basis, post=post, n_betas=self.NB, device=dev)
+        return E.op_morph_pose_bwd(saved["pose"], saved["j_rest"], saved["A"], self.j_dirs, self.parents, sb["part_a"], sb["part_c"],
+                                   g_joints=grad_joints, device=dev)
+
+    def vjp(self, betas, pose, grad_vertices=None, grad_joints=None, grad_landmarks=None, post=None, transl=None):
+        """The vector-Jacobian product of ``forward`` at (betas, pose, transl): the cotangents grad_vertices [F,V,3], grad_joints
+        [F,J,3] and grad_landmarks [F,M,3] (any of them None) pulled back to {"betas" [F,NB], "pose" [F,J,3], "transl" [F,3]}."""
+        betas, pose, transl = self._params("MorphableModel.vjp", betas, pose, transl)
+        return self._backward(self._run(betas, pose, post, transl, True), post, grad_vertices, grad_joints, grad_landmarks)
+
+    def differentiable(self, betas, pose, post=None, transl=None):
+        """``forward`` as a torch.autograd.Function over the same kernels: betas, pose and transl may require gradients, and the
+        returned vertices, joints and landmarks carry them, so a loss of one's own (a 2-D reprojection term, say) can be written
+        in torch.  Float32 on the model's device; ``.backward()`` runs the launches of ``vjp``."""
+        who = "MorphableModel.differentiable"
+        if not all(torch.is_tensor(t) for t in (betas, pose)) or (transl is not None and not torch.is_tensor(transl)):
+            raise ValueError(f"{who}: betas, pose and transl must be tensors")
+        self._params(who, betas, pose, transl)  # the shape errors, before autograd sees anything
+        F = betas.shape[0]
+        has_t = transl is not None
+        t_in = transl if has_t else torch.zeros((F, 3), device=self.device)
+        out = _MorphFunction.apply(self, post, has_t, betas, pose, t_in)
+        return {"vertices": out[0], "joints": out[1], "landmarks": out[2] if self.lmk_face is not None else None}
+
+    # ---- fitting: Adam on the device against target vertices and 3-D landmarks (engine.morph_fit_run)
+    def param_groups(self):
+        """{name: slice} of the parameter row [betas | pose | transl] (P = NB + 3 J + 3 columns); a FLAME model adds the names of
+        ``flame``'s arguments."""
+        NB, J = self.NB, self.J
+        g = {"betas": slice(0, NB), "pose": slice(NB, NB + 3 * J), "transl": slice(NB + 3 * J, NB + 3 * J + 3)}
+        if J == len(FLAME_JOINTS):
+            g.update({"shape": slice(0, self.n_shape), "expression": slice(self.n_shape, NB), "global_pose": slice(NB, NB + 3),
+                      "neck": slice(NB + 3, NB + 6), "jaw": slice(NB + 6, NB + 9), "eyes": slice(NB + 9, NB + 15)})
+        return g
+
+    def fit_vectors(self, lr=0.05, free=None, reg=None, prior=None, fit_transl=True, who="MorphableModel.fit"):
+        """The optimiser's per-parameter vectors (float64 numpy, [P] each): lr (0 = frozen), lam and p0 of the penalty
+        lam (p - p0)^2.  free: None (everything) or names of param_groups(); reg: {name: lam}; prior: {name: vector}.
+        fit_transl=False freezes the translation whatever ``free`` says."""
+        groups = self.param_groups()
+        P = self.NB + 3 * self.J + 3
+
+        def sl(kind, name):
+            if name not in groups:
+                raise ValueError(f"{who}: {kind} names {name!r}; this model has {sorted(groups)}")
+            return groups[name]
+
+        lr = float(lr)
+        if not (0.0 < lr < float("inf")):
+            raise ValueError(f"{who}: lr must be positive and finite, got {lr}")
+        lrv, lam, p0 = np.zeros(P), np.zeros(P), np.zeros(P)
+        if free is None:
+            lrv[:] = lr
+        else:
+            if isinstance(free, str):
+                raise ValueError(f"{who}: free must be a sequence of names, not the string {free!r}")
+            for name in free:
+                lrv[sl("free", name)] = lr
+        if not fit_transl:
+            lrv[groups["transl"]] = 0.0
+        if not lrv.any():
+            raise ValueError(f"{who}: nothing is free")
+        for name, val in (reg or {}).items():
+            val = float(val)
+            if not (0.0 <= val < float("inf")):
+                raise ValueError(f"{who}: reg[{name!r}] must be non-negative and finite, got {val}")
+            lam[sl("reg", name)] = val
+        for name, vec in (prior or {}).items():
+            s = sl("prior", name)
+            vec = np.asarray(vec.detach().cpu() if torch.is_tensor(vec) else vec, dtype=np.float64).reshape(-1)
+            if vec.shape[0] != s.stop - s.start:
+                raise ValueError(f"{who}: prior[{name!r}] must have {s.stop - s.start} entries, got {vec.shape[0]}")
+            p0[s] = vec
+        return lrv, lam, p0
+
+    def _fit_init(self, who, init, F, p0, lrv):
+        """The start [F,P] (float64 numpy): zeros, a frozen column at its prior, then what ``init`` names."""
+        groups = self.param_groups()
+        p = np.zeros((F, p0.shape[0]))
+        p[:, lrv == 0.0] = p0[lrv == 0.0]
+        for name, val in (init or {}).items():
+            if name not in groups:
+                raise ValueError(f"{who}: init names {name!r}; this model has {sorted(groups)}")
+            if val is not None:
+                s = groups[name]
+                p[:, s] = _rows(val.reshape(val.shape[0], -1) if np.ndim(val) == 3 else val, F, s.stop - s.start, f"init[{name!r}]")
+        return p
+
+    def fit(self, target_vertices=None, target_landmarks=None, vertex_weight=None, landmark_weight=None, lmk_lambda=1.0, iters=300,
+            lr=0.05, init=None, free=None, reg=None, prior=None, post=None, fit_transl=True, _who="MorphableModel.fit"):
+        """Adam on the device: parameters whose forward meets target_vertices [F,V,3] and / or target_landmarks [F,M,3] (3-D).
+        Per frame E_f = sum_v w_v |y - t|^2 / sum_v w_v + lmk_lambda sum_m w'_m |l - l'|^2 / sum_m w'_m + sum_p lam_p (p - p0_p)^2;
+        frames are independent.  init: {name: value} (zeros otherwise); free / reg / prior: see fit_vectors.  Returns device
+        tensors: betas [F,NB], pose [F,J,3], transl [F,3], vertices [F,V,3] (of the fitted parameters), loss_history [iters,F]
+        (the data term before each step) and rms [F]: the root mean square vertex distance to target_vertices, or to the target
+        landmarks without them."""
+        who = _who
+        lrv, lam, p0 = self.fit_vectors(lr, free, reg, prior, fit_transl, who)
+        if target_vertices is None and target_landmarks is None:
+            raise ValueError(f"{who}: give target_vertices, target_landmarks or both")
+        tv, tl = (None if t is None else (t if torch.is_tensor(t) else torch.as_tensor(np.asarray(t))) for t in
+                  (target_vertices, target_landmarks))
+        tv = tv[None] if tv is not None and tv.dim() == 2 else tv
+        tl = tl[None] if tl is not None and tl.dim() == 2 else tl
+        if tv is not None and (tv.dim() != 3 or tuple(tv.shape[1:]) != (self.V, 3) or tv.shape[0] < 1):
+            raise ValueError(f"{who}: target_vertices must be [F,{self.V},3] (the model's topology), got {tuple(tv.shape)}")
+        if tl is not None:
+            if self.lmk_face is None:
+                raise ValueError(f"{who}: target_landmarks given, and the model has no landmark embedding")
+            M = self.lmk_face.shape[0]
+            if tl.dim() != 3 or tuple(tl.shape[1:]) != (M, 3) or tl.shape[0] < 1:
+                raise ValueError(f"{who}: target_landmarks must be [F,{M},3], got {tuple(tl.shape)}")
+        F = max(t.shape[0] for t in (tv, tl) if t is not None)
+        if any(t is not None and t.shape[0] not in (1, F) for t in (tv, tl)):
+            raise ValueError(f"{who}: target_vertices and target_landmarks must have the same number of frames (or one)")
+        iters = int(iters)
+        if iters < 1:
+            raise ValueError(f"{who}: iters must be at least 1, got {iters}")
+        start = self._fit_init(who, init, F, p0, lrv)
+        if self.device.type != "cuda":
+            raise ValueError(f"{who}: the model is on {self.device}; the fitter runs on the GPU only (model.to('cuda:0'))")
+        dev = self.device
+        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+        p = f32(start)
+        m, v = torch.zeros_like(p), torch.zeros_like(p)
+        hist = E.morph_fit_run(self, p, m, v, f32(lrv), f32(lam), f32(p0), iters, target=tv, vertex_weight=vertex_weight, target_lmk=tl,
+                               lmk_weight=landmark_weight, lmk_lambda=lmk_lambda, post=post)
+        NB, J = self.NB, self.J
+        out = {"betas": p[:, :NB].contiguous(), "pose": p[:, NB:NB + 3 * J].reshape(F, J, 3).contiguous(),
+               "transl": p[:, NB + 3 * J:].contiguous(), "loss_history": hist}
+        fw = self.forward(out["betas"], out["pose"], post=post, transl=out["transl"])
+        out["vertices"] = fw["vertices"]
+        got, want = (fw["vertices"], tv) if tv is not None else (fw["landmarks"], tl)
+        out["rms"] = (got - want.to(device=dev, dtype=torch.float32)).square().sum(-1).mean(-1).sqrt()
+        return out
+
+    def fit_flame(self, target_vertices=None, target_landmarks=None, free=None, reg=None, prior=None, init=None, **kw):
+        """``fit`` in ``flame``'s names: free=("expression", "jaw"), reg={"shape": 1e-4, "expression": 1e-4, "jaw": 1e-4} (the
+        tracker's reg/shape, reg/exp, reg/jaw), prior={"shape": mica_shape} and init take shape / expression / global_pose / neck /
+        jaw / eyes / transl.  A frozen part starts, and stays, at its prior (zero without one) unless init names it.  Returns
+        fit's dict and the six FLAME parts [F,n] of the result."""
+        who = "MorphableModel.fit_flame"
+        if self.J != len(FLAME_JOINTS):
+            raise ValueError(f"{who}: a FLAME model has {len(FLAME_JOINTS)} joints, this one {self.J}")
+        out = self.fit(target_vertices, target_landmarks, free=free, reg=reg, prior=prior, init=init, _who=who, **kw)
+        flat = torch.cat([out["betas"], out["pose"].reshape(out["betas"].shape[0], -1)], 1)
+        g = self.param_groups()
+        out.update({k: flat[:, g[k]].contiguous() for k in ("shape", "expression", "global_pose", "neck", "jaw", "eyes")})
+        return out
+
+    def flame(self, shape, expression=None, global_pose=None, neck=None, jaw=None, eyes=None, post=None, transl=None):
         """The reference's FLAME.forward (flame.py:252-279): betas = [shape, expression], full_pose = [global, neck, jaw, eyes]
         (3, 3, 3 and 6 numbers); missing parts are zero.  Every argument is a vector or has a leading frame axis; single rows
-        are repeated for every frame."""
+        are repeated for every frame.  transl [3] or [F,3]: see forward."""
         if self.J != len(FLAME_JOINTS):
             raise ValueError(f"MorphableModel.flame: a FLAME model has {len(FLAME_JOINTS)} joints, this one {self.J}")
         parts = {"shape": shape, "expression": expression, "global_pose": global_pose, "neck": neck, "jaw": jaw, "eyes": eyes}
@@ -245,14 +439,37 @@ class MorphableModel:
         betas = np.concatenate([_rows(shape, F, n_sh, "shape"), _rows(expression, F, self.NB - n_sh, "expression")], 1)
         pose = np.concatenate([_rows(global_pose, F, 3, "global_pose"), _rows(neck, F, 3, "neck"), _rows(jaw, F, 3, "jaw"),
                                _rows(eyes, F, 6, "eyes")], 1)
-        return self.forward(torch.from_numpy(betas), torch.from_numpy(pose), post=post)
+        transl = None if transl is None else torch.from_numpy(np.array(_rows(transl, F, 3, "transl")))
+        return self.forward(torch.from_numpy(betas), torch.from_numpy(pose), post=post, transl=transl)
 
     def to(self, device):
         self.device = torch.device(device)
-        for k in ("v_template", "basis", "weights", "j_template", "j_dirs", "faces", "lmk_face", "lmk_bary"):
+        for k in ("v_template", "basis", "weights", "j_template", "j_dirs", "faces", "lmk_face", "lmk_bary", "csr_ptr", "csr_ent"):
             if getattr(self, k) is not None:
                 setattr(self, k, getattr(self, k).to(self.device))
         return self
+
+
+class _MorphFunction(torch.autograd.Function):
+    """MorphableModel.differentiable: the forward's launches, and in backward those of MorphableModel.vjp."""
+
+    @staticmethod
+    def forward(ctx, model, post, has_transl, betas, pose, transl):
+        b, p, t = model._params("MorphableModel.differentiable", betas, pose, transl if has_transl else None)
+        r = model._run(b, p, post, t, True)
+        ctx.model, ctx.post, ctx.saved, ctx.pose_shape = model, post, r, pose.shape
+        ctx.dtypes = (betas.dtype, pose.dtype, transl.dtype)
+        lmk = r["landmarks"] if r["landmarks"] is not None else r["vertices"].new_zeros(())
+        ctx.set_materialize_grads(False)  # an output nobody used arrives as None, as in vjp
+        ctx.mark_non_differentiable(*([lmk] if r["landmarks"] is None else []))
+        return r["vertices"], r["joints"], lmk
+
+    @staticmethod
+    def backward(ctx, g_verts, g_joints, g_lmk):
+        model = ctx.model
+        g = model._backward(ctx.saved, ctx.post, g_verts, g_joints, g_lmk if model.lmk_face is not None else None)
+        gb, gp, gt = (x.to(d) for x, d in zip((g["betas"], g["pose"].reshape(ctx.pose_shape), g["transl"]), ctx.dtypes))
+        return None, None, None, gb, gp, gt
 
 
 def flame_alignment() -> torch.Tensor:
