@@ -701,8 +701,9 @@ int mvd_denoise_views_ms(mvd_ctx* ctx, int B, const int* slots, const float* x_n
  *   synchronous    every *_ex hook (and mvd_op_group_norm_bwd / mvd_op_layer_norm_bwd, which are calls of theirs),
  *                  mvd_op_group_norm_fwd32, mvd_op_layer_norm_slabs, mvd_op_folded_group_norm, mvd_op_softmax_rows,
  *                  mvd_op_rows_split, the context-free sparse-CNN hooks, the mvd_op_train_* hooks (context-free but for
- *                  mvd_op_train_colsum / _sum_rows / _outer_add), and the timing hooks (mvd_bench_*, mvd_op_st_tail /
- *                  mvd_op_st_head with iters > 0): the stream is synchronised before the call returns.  The *_ex kind also checks
+ *                  mvd_op_train_colsum / _sum_rows / _outer_add), the small-op hooks (mvd_op_target_encoder ... mvd_op_small_mix,
+ *                  below, which check their arguments and write into guarded caller buffers like the *_ex kind), and the timing
+ *                  hooks (mvd_bench_*, mvd_op_st_tail / mvd_op_st_head with iters > 0): the stream is synchronised before the call returns.  The *_ex kind also checks
  *                  its arguments before anything is launched and writes into caller buffers that carry guard rows. */
 /* The update kernel of mvd_denoise_views_ms on its own, over n device floats: eps = eps_u + scale (eps_c - eps_u) (eps_u NULL:
  * eps = eps_c), then the update above.  No context: runs on the current device. */
@@ -983,6 +984,41 @@ int mvd_op_train_depth_attn_bwd(const float* q, const float* k, const float* v, 
 int mvd_op_train_im2col3(const float* x, int B, int H, int W, int C, float* col, void* stream);
 int mvd_op_train_col2im3(const float* dcol, int B, int H, int W, int C, float* dx, void* stream);
 int mvd_op_train_perm_w3(const float* src, int N, int C, int to_mat, float* dst, void* stream);
+/* The small-op layer one production launcher at a time (tests/test_gpu_small_ops.py; csrc/c_api_hooks.hip describes every operand):
+ * synchronous, arguments checked before anything is allocated or launched, results written by the launcher straight into the
+ * caller's buffers (0xFF presets, one guard row, pad columns where a stride exceeds the width).  16-bit operands are given in
+ * fp32 and rounded by the hook; 16-bit results are returned as written.  *form_used (may be NULL): the kernel form the launcher
+ * chose -- mvd_op_small_linear 1 vector / 0 scalar, mvd_op_layout 1 LDS-tiled / 0 element, mvd_op_pack_weight 0 element / 1 per-tap /
+ * 2 per-tap with 16-byte stores.
+ *   mvd_op_target_encoder     launch_target_encoder on w[8] ([16][4][3][3], then [16][16][3][3]), bias[8], gamma[7], beta[7]
+ *   mvd_op_small_linear       launch_small_linear; rows < 0 broadcasts the one input row to -rows result rows
+ *   mvd_op_timestep_embedding launch_timestep_embedding, t on the device
+ *   mvd_op_layout             op 0 launch_nchw_to_nhwc, 1 launch_nhwc_to_nchw
+ *   mvd_op_pack_weight        launch_pack_weight at out + dst_off halfs; Cin is the packed width
+ *   mvd_op_move               op 0 pack_upconv_weight, 1 permute_geglu_bias, 2 relu_beta_tile, 3 fill_rows_f16, 4 rows_f32_to_f16,
+ *                             5 upsample2_f16, 6 add_image_rows, 7 rows_f16_to_nchw, 8 sparse_densify
+ *   mvd_op_fold               op 0 launch_fold_qk, 1 launch_fold_ov, 2 launch_fold_mm; out fp32 (out_f32) or 16-bit
+ *   mvd_op_cfg_assemble       the samplers' UNet batch assembly (timesteps: host), mvd_op_cfg_ddim: launch_cfg_ddim
+ *   mvd_op_small_mix          op 0 launch_fuse_views, 1 launch_mse, 2 launch_accumulate_f32, 3 launch_add_rows */
+int mvd_op_target_encoder(mvd_ctx* ctx, const float* x, const float* pre, int n_views, const float* const* w, const float* const* bias,
+                          const float* const* gamma, const float* const* beta, float* feats, void* stream);
+int mvd_op_small_linear(mvd_ctx* ctx, const float* a, int lda, int rows, int K, const float* w, const float* bias, int N, int act_in,
+                        float* out, int ldo, int accumulate, int* form_used, void* stream);
+int mvd_op_timestep_embedding(mvd_ctx* ctx, const int64_t* t, int B, int dim, float* out, void* stream);
+int mvd_op_layout(mvd_ctx* ctx, int op, const float* in, int B, int C, int HW, int ld, int cpad, float* out, int* form_used,
+                  void* stream);
+int mvd_op_pack_weight(mvd_ctx* ctx, const float* src, int N, int Cin, int taps, int transposed, int geglu, int cin_src, int xp,
+                       int dst_off, void* out, int* form_used, void* stream);
+int mvd_op_move(mvd_ctx* ctx, int op, const float* a, const void* b, int i0, int i1, int i2, int i3, int i4, void* out, void* stream);
+int mvd_op_fold(mvd_ctx* ctx, int op, const float* a, const float* b, int heads, int hd, int Cc, int I, float scale, int M, int N,
+                int K, int lda, int ldb, int ldc, int out_f32, void* out, void* stream);
+int mvd_op_cfg_assemble(mvd_ctx* ctx, const float* x_noisy, const float* x_input, const float* clip, const int64_t* timesteps, int B,
+                        int TN, int HW, int dim, int copies, float* xin, float* ctx_out, int64_t* tt, void* stream);
+int mvd_op_cfg_ddim(mvd_ctx* ctx, const float* eps_c, const float* eps_u, float scale, const float* x, const float* noise, float s1m,
+                    float sqrt_at, float sqrt_aprev, float dir_coef, float sigma, float* eps_out, float* x_prev, size_t n,
+                    void* stream);
+int mvd_op_small_mix(mvd_ctx* ctx, int op, const float* a, const float* b, const float* w, int i0, int i1, int i2, int i3, size_t n,
+                     float* out, void* stream);
 /* time of the dominant kernel, for bench.py: runs the 3x3 conv implicit GEMM `iters` times on stream and
  * returns the mean kernel time in ms measured with HIP events on that stream */
 int mvd_bench_conv(mvd_ctx* ctx, int B, int C, int H, int W, int Cout, int iters, float* ms_out, void* stream);

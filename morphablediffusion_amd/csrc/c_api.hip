@@ -55,6 +55,22 @@ inline int nblk(size_t n) { size_t g = (n + 255) / 256; return (int)(g > 4096 ? 
 
 }  // namespace
 
+// The UNet batch of B samples x TN views (morphable_diffusion.py:133-147): every conditional row first -- sample by sample, view
+// by view --, then (copies == 2) the unconditional copies in the same order, half_off = B * TN rows further on.  timesteps: HOST.
+int launch_build_cfg_batch(const float* x_noisy, const float* x_input, const float* clip, const int64_t* timesteps, int B, int TN, int HW,
+                           int dim, int copies, float* xin, float* ctx, int64_t* tt, hipStream_t s) {
+  const long half_off = (long)B * TN;
+  for (int b = 0; b < B; ++b) {
+    hipLaunchKernelGGL(build_cfg_input_kernel, dim3(nblk((size_t)copies * TN * HW * 8)), dim3(256), 0, s,
+                       x_noisy + (size_t)b * TN * 4 * HW, x_input + (size_t)b * 4 * HW, TN, HW, copies, xin + (size_t)b * TN * HW * 8,
+                       half_off);
+    hipLaunchKernelGGL(build_cfg_context_kernel, dim3(nblk((size_t)copies * TN * dim)), dim3(256), 0, s, clip + (size_t)b * dim, TN, dim,
+                       copies, ctx + (size_t)b * TN * dim, tt + (size_t)b * TN, timesteps[b], half_off);
+  }
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+
 extern "C" {
 
 const char* mvd_last_error(void) { return g_err.c_str(); }
@@ -1299,18 +1315,7 @@ static int denoise_views_common(const char* name, mvd_ctx* c, int B, const int* 
   float* eps = ws_alloc<float>(c, (size_t)Bv * HW * 4);
   float* eps_nchw = ws_alloc<float>(c, (size_t)Bv * HW * 4);
   WS_CHECK(xin && ctx && tt && eps && eps_nchw);
-  // UNet batch order (morphable_diffusion.py:133-147): every conditional row first -- sample by sample, view by view --, then
-  // the unconditional copies in the same order
-  const long half_off = (long)B * TN;
-  for (int b = 0; b < B; ++b) {
-    hipLaunchKernelGGL(build_cfg_input_kernel, dim3(nblk((size_t)copies * TN * HW * 8)), dim3(256), 0, s,
-                       x_noisy + (size_t)b * TN * 4 * HW, x_input + (size_t)b * 4 * HW, TN, HW, copies, xin + (size_t)b * TN * HW * 8,
-                       half_off);
-    hipLaunchKernelGGL(build_cfg_context_kernel, dim3(nblk((size_t)copies * TN * u.context_dim)), dim3(256), 0, s,
-                       clip + (size_t)b * u.context_dim, TN, u.context_dim, copies, ctx + (size_t)b * TN * u.context_dim,
-                       tt + (size_t)b * TN, timesteps[b], half_off);
-  }
-  HIP_CHECK_RET(hipGetLastError());
+  RET_IF(launch_build_cfg_batch(x_noisy, x_input, clip, timesteps, B, TN, HW, u.context_dim, copies, xin, ctx, tt, s));
   (void)td; (void)vd;
   RET_IF(engine_unet(c, xin, 8, tt, ctx, Bv, B * TN, c->v.frustum_volume_depth, cl, eps, s, &produce));
   RET_IF(launch_nhwc_to_nchw(eps, 4, Bv, 4, HW, eps_nchw, s));

@@ -1024,4 +1024,212 @@ int mvd_op_train_perm_w3(const float* src, int N, int C, int to_mat, float* dst,
   return hook_sync("mvd_op_train_perm_w3", s, train_perm_w3(src, N, C, to_mat, dst, s));
 }
 
+// ---------------------------------------------------------------------------------------------- small-op hooks
+// tests/test_gpu_small_ops.py: the kernels of k_misc.hip and k_enc.hip, the element-wise kernels of k_cond.hip and the samplers'
+// batch assembly, one production launcher per call on the caller's buffers (0xFF presets, guard rows, pad columns).  Every
+// argument is checked before anything is allocated or launched; the stream is synchronised before the call returns.
+
+// launch_target_encoder without a context's weights: w[0] [16][4][3][3], w[1..7] [16][16][3][3] fp32, packed here as pack_conv
+// does (launch_pack_weight, the init conv with cin_src = 4 into Cin = 8); bias[8], gamma[7], beta[7] of 16 floats; x [n][4][32][32],
+// pre [n][48]; feats [n * 1024 (+ guard)][16]
+int mvd_op_target_encoder(mvd_ctx* c, const float* x, const float* pre, int n_views, const float* const* w, const float* const* bias,
+                          const float* const* gamma, const float* const* beta, float* feats, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!x || !pre || !w || !bias || !gamma || !beta || !feats) return mvd_fail("op_target_encoder: null argument");
+  if (n_views < 1 || n_views > 4096) return mvd_fail("op_target_encoder: 1 .. 4096 views expected");
+  for (int i = 0; i < 8; ++i)
+    if (!w[i] || !bias[i] || (i < 7 && (!gamma[i] || !beta[i]))) return mvd_fail("op_target_encoder: null layer parameter");
+  hipStream_t s = S(stream);
+  WsScope ws_scope(c);
+  const half_t* wp[8];
+  int cin[8];
+  for (int i = 0; i < 8; ++i) {
+    ConvW cw;
+    RET_IF(hook_pack_fwd(c, w[i], 16, i ? 16 : 4, 9, 0, 0, 0, &cw, s));
+    wp[i] = cw.w;
+    cin[i] = cw.Cin;
+  }
+  return hook_sync("op_target_encoder", s, launch_target_encoder(x, pre, n_views, wp, bias, cin, gamma, beta, feats, s));
+}
+
+// launch_small_linear on a [in rows][lda] (any float-aligned pointer), w [N][K] fp32 (rounded to 16 bits here), out rows of ldo floats;
+// rows < 0: the one input row is broadcast to -rows result rows.  *form_used: small_linear_form of the launch (1 vector, 0 scalar).
+int mvd_op_small_linear(mvd_ctx* c, const float* a, int lda, int rows, int K, const float* w, const float* bias, int N, int act_in,
+                        float* out, int ldo, int accumulate, int* form_used, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!a || !w || !out) return mvd_fail("op_small_linear: null argument");
+  if (rows == 0 || K < 1 || N < 1 || lda < K || ldo < N) return mvd_fail("op_small_linear: rows != 0, K, N >= 1, lda >= K, ldo >= N expected");
+  if (act_in != ACT_NONE && act_in != ACT_SILU) return mvd_fail("op_small_linear: act_in is none (0) or SiLU (1)");
+  hipStream_t s = S(stream);
+  WsScope ws_scope(c);
+  const half_t* wh;
+  RET_IF(hook_f16(c, w, (size_t)N * K, &wh, s));
+  if (form_used) *form_used = small_linear_form(a, lda, K, wh);
+  return hook_sync("op_small_linear", s, launch_small_linear(a, lda, rows, K, wh, bias, N, act_in, out, ldo, accumulate ? 1 : 0, s));
+}
+
+int mvd_op_timestep_embedding(mvd_ctx* c, const int64_t* t, int B, int dim, float* out, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!t || !out || B < 1 || dim < 1) return mvd_fail("op_timestep_embedding: bad argument");
+  hipStream_t s = S(stream);
+  return hook_sync("op_timestep_embedding", s, launch_timestep_embedding(t, B, dim, out, s));
+}
+
+// op 0: launch_nchw_to_nhwc, in [B][C][HW] -> out rows of ld floats, columns [0, cpad) written (zero from C on); op 1:
+// launch_nhwc_to_nchw, in rows of ld floats -> out [B][C][HW] (cpad unused).  *form_used: layout_form of the launch.
+int mvd_op_layout(mvd_ctx* c, int op, const float* in, int B, int C, int HW, int ld, int cpad, float* out, int* form_used, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!in || !out || B < 1 || C < 1 || HW < 1) return mvd_fail("op_layout: bad argument");
+  if (op != 0 && op != 1) return mvd_fail("op_layout: op is 0 (to channels-last) or 1 (to NCHW)");
+  if (op == 0 ? (cpad < C || ld < cpad) : ld < C) return mvd_fail("op_layout: bad stride");
+  hipStream_t s = S(stream);
+  if (form_used) *form_used = layout_form(B, C, HW, op == 0 ? cpad : C);
+  return hook_sync("op_layout", s, op == 0 ? launch_nchw_to_nhwc(in, B, C, HW, out, ld, cpad, s) : launch_nhwc_to_nchw(in, ld, B, C, HW, out, s));
+}
+
+// launch_pack_weight into the caller's 16-bit buffer at out + dst_off halfs: [taps][N][Cin] with Cin the PACKED width (3 Cl with xp);
+// src [N][cin_src][taps] (transposed: [cin_src][N][taps]).  *form_used: pack_weight_form of the launch.
+int mvd_op_pack_weight(mvd_ctx* c, const float* src, int N, int Cin, int taps, int transposed, int geglu, int cin_src, int xp, int dst_off,
+                       void* out, int* form_used, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!src || !out || N < 1 || Cin < 1 || taps < 1 || taps > 27 || dst_off < 0) return mvd_fail("op_pack_weight: bad argument");
+  if (xp && Cin % 3) return mvd_fail("op_pack_weight: the extended-precision layout needs Cin = 3 * Cl");
+  if (cin_src < 1 || cin_src > (xp ? Cin / 3 : Cin)) return mvd_fail("op_pack_weight: 1 <= cin_src <= Cl expected");
+  if (geglu && N % 64) return mvd_fail("op_pack_weight: geglu pairs 32-row blocks: N % 64 == 0");
+  hipStream_t s = S(stream);
+  half_t* dst = (half_t*)out + dst_off;
+  if (form_used) *form_used = pack_weight_form(N, Cin, taps, transposed, dst, xp);
+  return hook_sync("op_pack_weight", s, launch_pack_weight(src, N, Cin, taps, transposed ? 1 : 0, geglu ? 1 : 0, dst, s, cin_src, xp ? 1 : 0));
+}
+
+// The other packs, fills and moves, one launcher per op id (a / b: the operands, i0 .. i4: the launcher's integers in its own order;
+// a 16-bit operand is given in fp32 and rounded here):
+//   0 launch_pack_upconv_weight   a [N][Cin][9], i0 N, i1 Cin                                  out 16-bit [16][N][Cin]
+//   1 launch_permute_geglu_bias   a [N], i0 N (N % 64 == 0)                                    out fp32 [N]
+//   2 launch_relu_beta_tile       a [Cc], i0 Cc, i1 heads, i2 split                            out 16-bit [(split ? 3 : 1) heads Cc]
+//   3 launch_fill_rows_f16        a [n] (16-bit), i0 ld, i1 rows, i2 n                         out 16-bit rows of ld
+//   4 launch_rows_f32_to_f16      a rows of lda, i0 lda, i1 rows, i2 C                         out 16-bit [rows][C]
+//   5 launch_upsample2_f16        a [B][H][W] rows of ldi, i0 ldi, i1 B, i2 H, i3 W, i4 C      out 16-bit [B][2H][2W][C]
+//   6 launch_add_image_rows       a [nb HW] rows of ldi, b [HW][C], i0 ldi, i1 C, i2 nb, i3 HW, i4 ldo    out fp32 rows of ldo
+//   7 launch_rows_f16_to_nchw     a [rows][C] (16-bit), i0 rows, i1 C                          out fp32 [C][rows]
+//   8 launch_sparse_densify       a [nrows][C], b int32 [nvox] (-1 .. nrows - 1), i0 nvox, i1 C    out fp32 [C][nvox]
+int mvd_op_move(mvd_ctx* c, int op, const float* a, const void* b, int i0, int i1, int i2, int i3, int i4, void* out, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!a || !out) return mvd_fail("op_move: null argument");
+  hipStream_t s = S(stream);
+  WsScope ws_scope(c);
+  const half_t* h;
+  int rc;
+  switch (op) {
+    case 0:
+      if (i0 < 1 || i1 < 1) return mvd_fail("op_move: bad argument");
+      rc = launch_pack_upconv_weight(a, i0, i1, (half_t*)out, s);
+      break;
+    case 1:
+      if (i0 < 64 || i0 % 64) return mvd_fail("op_move: geglu pairs 32-row blocks: N % 64 == 0");
+      rc = launch_permute_geglu_bias(a, i0, (float*)out, s);
+      break;
+    case 2:
+      if (i0 < 1 || i1 < 1) return mvd_fail("op_move: bad argument");
+      rc = launch_relu_beta_tile(a, i0, i1, (half_t*)out, s, i2 ? 1 : 0);
+      break;
+    case 3:
+      if (i1 < 1 || i2 < 1 || i0 < i2) return mvd_fail("op_move: bad stride");
+      RET_IF(hook_f16(c, a, (size_t)i2, &h, s));
+      rc = launch_fill_rows_f16((half_t*)out, i0, i1, h, i2, s);
+      break;
+    case 4:
+      if (i1 < 1 || i2 < 1 || i0 < i2) return mvd_fail("op_move: bad stride");
+      rc = launch_rows_f32_to_f16(a, i0, (long)i1, i2, (half_t*)out, s);
+      break;
+    case 5:
+      if (i1 < 1 || i2 < 1 || i3 < 1 || i4 < 1 || i0 < i4) return mvd_fail("op_move: bad stride");
+      rc = launch_upsample2_f16(a, i0, i1, i2, i3, i4, (half_t*)out, s);
+      break;
+    case 6:
+      if (!b || i1 < 1 || i2 < 1 || i3 < 1 || i0 < i1 || i4 < i1) return mvd_fail("op_move: bad stride");
+      rc = launch_add_image_rows(a, i0, (const float*)b, i1, i2, i3, (float*)out, i4, s);
+      break;
+    case 7:
+      if (i0 < 1 || i1 < 1) return mvd_fail("op_move: bad argument");
+      RET_IF(hook_f16(c, a, (size_t)i0 * i1, &h, s));
+      rc = launch_rows_f16_to_nchw(h, (long)i0, i1, (float*)out, s);
+      break;
+    case 8:
+      if (!b || i0 < 1 || i1 < 1) return mvd_fail("op_move: bad argument");
+      rc = launch_sparse_densify(a, (const int*)b, (long)i0, i1, (float*)out, s);
+      break;
+    default:
+      return mvd_fail("op_move: unknown op");
+  }
+  return hook_sync("op_move", s, rc);
+}
+
+// The weight folds (fold_gemm_kernel), result fp32 (out_f32) or 16-bit in the caller's buffer:
+//   0 launch_fold_qk   a = Wq [heads hd][I], b = Wk [heads hd][Cc] -> [heads Cc][I], scaled
+//   1 launch_fold_ov   a = Wo [I][heads hd], b = Wv [heads hd][Cc] -> [I][heads Cc]
+//   2 launch_fold_mm   a [M] rows of lda, b [K] rows of ldb -> [M] rows of ldc, columns [0, N)
+int mvd_op_fold(mvd_ctx* c, int op, const float* a, const float* b, int heads, int hd, int Cc, int I, float scale, int M, int N, int K,
+                int lda, int ldb, int ldc, int out_f32, void* out, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!a || !b || !out) return mvd_fail("op_fold: null argument");
+  hipStream_t s = S(stream);
+  half_t* o16 = out_f32 ? nullptr : (half_t*)out;
+  float* o32 = out_f32 ? (float*)out : nullptr;
+  if (op == 0 || op == 1) {
+    if (heads < 1 || heads > 65535 || hd < 1 || Cc < 1 || I < 1) return mvd_fail("op_fold: heads, hd, Cc, I >= 1 expected");
+    return hook_sync("op_fold", s, op == 0 ? launch_fold_qk(a, b, heads, hd, Cc, I, scale, o16, s, o32) : launch_fold_ov(a, b, heads, hd, Cc, I, o16, s, o32));
+  }
+  if (op != 2) return mvd_fail("op_fold: unknown op");
+  if (M < 1 || N < 1 || K < 1 || lda < K || ldb < N || ldc < N) return mvd_fail("op_fold: M, N, K >= 1, lda >= K, ldb >= N, ldc >= N expected");
+  return hook_sync("op_fold", s, launch_fold_mm(a, lda, b, ldb, M, N, K, o16, ldc, o32, s));
+}
+
+// launch_build_cfg_batch: x_noisy [B][TN][4][HW], x_input [B][4][HW], clip [B][dim], timesteps HOST [B] -> xin [copies B TN][HW][8],
+// ctx [copies B TN][dim], tt [copies B TN]
+int mvd_op_cfg_assemble(mvd_ctx* c, const float* x_noisy, const float* x_input, const float* clip, const int64_t* timesteps, int B, int TN,
+                        int HW, int dim, int copies, float* xin, float* ctx, int64_t* tt, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!x_noisy || !x_input || !clip || !timesteps || !xin || !ctx || !tt) return mvd_fail("op_cfg_assemble: null argument");
+  if (B < 1 || TN < 1 || HW < 1 || dim < 1 || (copies != 1 && copies != 2)) return mvd_fail("op_cfg_assemble: B, TN, HW, dim >= 1 and 1 or 2 copies expected");
+  hipStream_t s = S(stream);
+  return hook_sync("op_cfg_assemble", s, launch_build_cfg_batch(x_noisy, x_input, clip, timesteps, B, TN, HW, dim, copies, xin, ctx, tt, s));
+}
+
+// launch_cfg_ddim over n device floats; eps_u, noise, eps_out and x_prev may each be NULL
+int mvd_op_cfg_ddim(mvd_ctx* c, const float* eps_c, const float* eps_u, float scale, const float* x, const float* noise, float s1m,
+                    float sqrt_at, float sqrt_aprev, float dir_coef, float sigma, float* eps_out, float* x_prev, size_t n, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!eps_c || n < 1 || (x_prev && !x)) return mvd_fail("op_cfg_ddim: eps_c, n >= 1 and x with x_prev expected");
+  hipStream_t s = S(stream);
+  return hook_sync("op_cfg_ddim", s, launch_cfg_ddim(eps_c, eps_u, scale, x, noise, s1m, sqrt_at, sqrt_aprev, dir_coef, sigma, eps_out, x_prev, n, s));
+}
+
+// The small reductions and mixes:
+//   0 launch_fuse_views      a = vf [i0 views][i1 Nv][16], w [16][16], b bias [16] or NULL, i2 total_views, i3 accumulate -> out [Nv][16]
+//   1 launch_mse             a, b [n] -> out [1]
+//   2 launch_accumulate_f32  out [n] += a [n]  (n % 4 == 0)
+//   3 launch_add_rows        out [n] = a [n] + b [n] (b may be NULL)
+int mvd_op_small_mix(mvd_ctx* c, int op, const float* a, const float* b, const float* w, int i0, int i1, int i2, int i3, size_t n,
+                     float* out, void* stream) {
+  RET_IF(hook_begin(c));
+  if (!a || !out) return mvd_fail("op_small_mix: null argument");
+  hipStream_t s = S(stream);
+  switch (op) {
+    case 0:
+      if (!w || i0 < 1 || i1 < 1 || i2 < 1) return mvd_fail("op_small_mix: bad argument");
+      return hook_sync("op_small_mix", s, launch_fuse_views(a, i0, i1, i2, w, b, out, i3 ? 1 : 0, s));
+    case 1:
+      if (!b || n < 1) return mvd_fail("op_small_mix: bad argument");
+      return hook_sync("op_small_mix", s, launch_mse(a, b, n, out, s));
+    case 2:
+      if (n < 1) return mvd_fail("op_small_mix: bad argument");
+      return hook_sync("op_small_mix", s, launch_accumulate_f32(out, a, n, s));
+    case 3:
+      if (n < 1) return mvd_fail("op_small_mix: bad argument");
+      return hook_sync("op_small_mix", s, launch_add_rows(out, a, b, n, s));
+  }
+  return mvd_fail("op_small_mix: unknown op");
+}
+
 }  // extern "C"

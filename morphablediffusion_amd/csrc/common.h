@@ -212,9 +212,12 @@ int launch_depth_attn(const float* qk, const half_t* ctxn, half_t* z, int n_cond
 int depth_attn_check(int D, int Cc, int heads, int ldx, int nfill);  // the launcher's shape check alone: 0, or mvd_fail
 int launch_small_linear(const float* a, int lda, int rows, int K, const half_t* w, const float* bias, int N,
                         int act_in, float* out, int ldo, int accumulate, hipStream_t s);
+int small_linear_form(const float* a, int lda, int K, const half_t* w);  // the path launch_small_linear takes: 1 vector, 0 scalar
 int launch_timestep_embedding(const int64_t* t, int B, int dim, float* out, hipStream_t s);
 int launch_nchw_to_nhwc(const float* in, int B, int C, int HW, float* out, int ldo, int cpad, hipStream_t s);
 int launch_nhwc_to_nchw(const float* in, int ld, int B, int C, int HW, float* out, hipStream_t s);
+int layout_form(int B, int C, int HW, int cols);  // the two launchers above: 1 LDS-tiled kernel, 0 element kernel (cols: cpad / C)
+int pack_weight_form(int N, int Cin, int taps, int transposed, const half_t* dst, int xp);  // 0 element, 1 per-tap, 2 per-tap vector
 // xp != 0: Cin is the packed width 3 * Cl and each row holds [w_hi | w_hi | w_lo] (w_hi = fp16(w), w_lo = fp16(w - w_hi))
 int launch_pack_weight(const float* src, int N, int Cin, int taps, int transposed, int geglu, half_t* dst,
                        hipStream_t s, int cin_src = -1, int xp = 0);
@@ -237,6 +240,9 @@ int launch_relu_beta_tile(const float* beta, int Cc, int heads, half_t* out, hip
 int launch_cfg_ddim(const float* eps_c, const float* eps_u, float scale, const float* x, const float* noise,
                     float sqrt_one_minus_at, float sqrt_at, float sqrt_aprev, float dir_coef, float sigma,
                     float* eps_out, float* x_prev, size_t n, hipStream_t s);
+// the samplers' UNet batch assembly (c_api.hip: build_cfg_input_kernel + build_cfg_context_kernel per sample); timesteps: host
+int launch_build_cfg_batch(const float* x_noisy, const float* x_input, const float* clip, const int64_t* timesteps, int B, int TN, int HW,
+                           int dim, int copies, float* xin, float* ctx, int64_t* tt, hipStream_t s);
 // DPM-Solver++ multistep update coefficients of one step (schedule.py DPMSolverSchedule.rows)
 struct DpmCoef {
   float s1m, sqrt_at, c_x, c_d, c_c, c_n;

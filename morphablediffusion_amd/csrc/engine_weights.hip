@@ -1083,8 +1083,8 @@ int engine_finalize(mvd_ctx* c) {
   const bool has_vae = c->raw.count("first_stage_model.decoder.conv_in.weight") > 0;
   const bool has_vae_enc = c->raw.count("first_stage_model.encoder.conv_in.weight") > 0;
   const bool has_clip = c->raw.count("clip_image_encoder.model.visual.conv1.weight") > 0;
-  if (!has_unet && !has_cond && !has_vae && !has_vae_enc && !has_clip)
-    return mvd_fail("finalize: no UNet, spatial_volume, first-stage or CLIP weights were uploaded");
+  if (!has_unet && !has_cond && !has_step && !has_vae && !has_vae_enc && !has_clip)
+    return mvd_fail("finalize: no UNet, spatial_volume, step-embedding, first-stage or CLIP weights were uploaded");
   if (has_clip) RET_IF(build_clip(c));
   if (has_vae) RET_IF(build_vae(c));
   if (has_vae_enc) RET_IF(build_vae_encoder(c));

@@ -9,7 +9,7 @@ namespace {
 __global__ __launch_bounds__(256) void small_linear_kernel(const float* __restrict__ a, int lda, int rows, int K,
                                                            const half_t* __restrict__ w, const float* __restrict__ bias,
                                                            int N, int act_in, float* __restrict__ out, int ldo,
-                                                           int accumulate) {
+                                                           int accumulate, int vec) {
   const int lane = threadIdx.x & 63;
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (n >= N) return;
@@ -21,7 +21,7 @@ __global__ __launch_bounds__(256) void small_linear_kernel(const float* __restri
     float acc[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-    if ((K & 7) == 0 && (lda & 3) == 0) {
+    if (vec) {  // small_linear_form: K % 8 == 0, lda % 4 == 0, a and w 16-byte aligned
       for (int k = lane * 8; k < K; k += 512) {
         const h8 wv = *(const h8*)(wr + k);
 #pragma unroll
@@ -478,10 +478,16 @@ inline int grid_for(size_t n, int block = 256, int cap = 4096) {
 
 }  // namespace
 
+// 1: the 16-byte path (h8 weight and float4 activation loads), 0: the scalar path.  Callers pass rows of larger tables
+// (t_embed + b * td, v_embed + tgt * vd), so the operand pointers are part of the choice, as in launch_cfg_dpm.
+int small_linear_form(const float* a, int lda, int K, const half_t* w) {
+  return (K & 7) == 0 && (lda & 3) == 0 && (((uintptr_t)a | (uintptr_t)w) & 15) == 0;
+}
+
 int launch_small_linear(const float* a, int lda, int rows, int K, const half_t* w, const float* bias, int N,
                         int act_in, float* out, int ldo, int accumulate, hipStream_t s) {
   hipLaunchKernelGGL(small_linear_kernel, dim3(cdiv(N, 4)), dim3(256), 0, s, a, lda, rows, K, w, bias, N, act_in, out,
-                     ldo, accumulate);
+                     ldo, accumulate, small_linear_form(a, lda, K, w));
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }
@@ -492,8 +498,11 @@ int launch_timestep_embedding(const int64_t* t, int B, int dim, float* out, hipS
   return 0;
 }
 
+// 1: the 32 x 32 LDS-tiled kernel, 0: the element-per-thread kernel (cols: cpad, or C for nhwc_to_nchw)
+int layout_form(int B, int C, int HW, int cols) { return C >= 16 && HW >= 32 && B <= 65535 && cdiv(cols, 32) <= 65535; }
+
 int launch_nchw_to_nhwc(const float* in, int B, int C, int HW, float* out, int ldo, int cpad, hipStream_t s) {
-  if (C >= 16 && HW >= 32 && B <= 65535 && cdiv(cpad, 32) <= 65535)
+  if (layout_form(B, C, HW, cpad))
     hipLaunchKernelGGL(nchw_to_nhwc_tiled_kernel, dim3(cdiv(HW, 32), cdiv(cpad, 32), B), dim3(256), 0, s, in, C, HW, out, ldo, cpad);
   else
     hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3(grid_for((size_t)B * HW * cpad)), dim3(256), 0, s, in, B, C, HW, out,
@@ -503,7 +512,7 @@ int launch_nchw_to_nhwc(const float* in, int B, int C, int HW, float* out, int l
 }
 
 int launch_nhwc_to_nchw(const float* in, int ld, int B, int C, int HW, float* out, hipStream_t s) {
-  if (C >= 16 && HW >= 32 && B <= 65535 && cdiv(C, 32) <= 65535)
+  if (layout_form(B, C, HW, C))
     hipLaunchKernelGGL(nhwc_to_nchw_tiled_kernel, dim3(cdiv(HW, 32), cdiv(C, 32), B), dim3(256), 0, s, in, ld, C, HW, out);
   else
     hipLaunchKernelGGL(nhwc_to_nchw_kernel, dim3(grid_for((size_t)B * HW * C)), dim3(256), 0, s, in, ld, B, C, HW, out);
@@ -511,13 +520,20 @@ int launch_nhwc_to_nchw(const float* in, int ld, int B, int C, int HW, float* ou
   return 0;
 }
 
+// 0: the element-per-thread kernel, 1: the per-tap kernel, 2: the per-tap kernel with 16-byte stores
+int pack_weight_form(int N, int Cin, int taps, int transposed, const half_t* dst, int xp) {
+  if (!(taps > 1 && taps <= 27 && !transposed && N <= 65535)) return 0;
+  const int Cl = xp ? Cin / 3 : Cin;
+  return !(Cl & 7) && !((uintptr_t)dst & 15) ? 2 : 1;
+}
+
 int launch_pack_weight(const float* src, int N, int Cin, int taps, int transposed, int geglu, half_t* dst,
                        hipStream_t s, int cin_src, int xp) {
   if (xp && Cin % 3) return mvd_fail("pack_weight: the extended-precision layout needs Cin = 3 * Cl");
   if (cin_src <= 0) cin_src = xp ? Cin / 3 : Cin;
-  if (taps > 1 && taps <= 27 && !transposed && N <= 65535) {
+  if (const int form = pack_weight_form(N, Cin, taps, transposed, dst, xp)) {
     const int Cl = xp ? Cin / 3 : Cin;
-    if (!(Cl & 7) && !((uintptr_t)dst & 15))
+    if (form == 2)
       hipLaunchKernelGGL(pack_weight_taps_vec_kernel, dim3(cdiv(Cl, 64), cdiv(N, 4)), dim3(256), 0, s, src, N, Cin, taps, geglu, cin_src,
                          dst, xp);
     else
@@ -581,7 +597,8 @@ int launch_fold_qk(const float* wq, const float* wk, int heads, int hd, int Cc, 
 int launch_fold_ov(const float* wo, const float* wv, int heads, int hd, int Cc, int I, half_t* out, hipStream_t s,
                    float* out32) {
   // W_ov[i][hn*Cc + j] = sum_c Wo[i][hn*hd + c] * Wv[hn*hd + c][j]:  per head  C[i][j] = sum_c Wo(i, hn*hd + c) Wv(hn*hd + c, j)
-  hipLaunchKernelGGL(fold_gemm_kernel, dim3(cdiv(Cc, 64), cdiv(I, 64), heads), dim3(256), 0, s, wo, (long)hd, (long)I, 1L, wv,
+  // (Wo is [I][heads * hd]: its rows are heads * hd floats apart -- I only where the inner width equals I, as in every checkpoint)
+  hipLaunchKernelGGL(fold_gemm_kernel, dim3(cdiv(Cc, 64), cdiv(I, 64), heads), dim3(256), 0, s, wo, (long)hd, (long)heads * hd, 1L, wv,
                      (long)hd * Cc, (long)Cc, 1L, I, Cc, hd, 1.0f, (long)Cc, (long)heads * Cc, 1L, out, out32);
   HIP_CHECK_RET(hipGetLastError());
   return 0;

@@ -2325,6 +2325,146 @@ class Engine:
         L.check(self.lib.mvd_op_train_outer_add(self._ctx, ap, lda, bp, ldb, op, M, N, K, _stream()))
         return self._rows_result(ob, M, N, "op_train_outer_add")
 
+    # ---- small-op hooks (tests/test_gpu_small_ops.py): one production launcher per call, written straight into guarded 0xFF
+    # buffers allocated here; a refusal raises MvdError with .results_untouched (Engine._refused).  Operands may be None where a
+    # test wants the hook's own refusal.
+    def _dev(self, t, dtype=torch.float32):
+        return None if t is None else t.detach().to(device=self.device, dtype=dtype).contiguous()
+
+    @staticmethod
+    def _bits(t):
+        """a result buffer of any element size as the int32 words Engine._refused compares"""
+        flat = t.reshape(-1)
+        return flat[:flat.numel() * t.element_size() // 4 * 4 // t.element_size()].view(torch.int32)
+
+    def _call_hook(self, fn, args, bufs, form=False):
+        """fn(ctx, *args[, &form], stream) with the result buffers watched -> form_used (or None)"""
+        before = [t.clone() for t in bufs]
+        used = C.c_int(-1)
+        tail = (C.byref(used), _stream()) if form else (_stream(),)
+        self._refused(fn(self._ctx, *args, *tail), bufs, before)
+        return used.value if form else None
+
+    def op_target_encoder(self, x, pre, w, bias, gamma, beta, n=None, out=None):
+        """mvd_op_target_encoder: x [n, 4, 32, 32], pre [n, 48], w / bias 8 fp32 tensors, gamma / beta 7 -> the guarded result buffer
+        [n * 1024 + 1, 16] (`out`: a buffer of an earlier call, written again as it is)."""
+        x, pre = self._dev(x), self._dev(pre)
+        n = x.shape[0] if n is None else n
+        lists = [[self._dev(t) for t in ts] for ts in (w, bias, gamma, beta)]
+        arr = lambda ts: (C.c_void_p * len(ts))(*[L.ptr(t) for t in ts])  # noqa: E731
+        rows = max(n, 1) * 1024
+        out = _nan_guarded(rows, 16, self.device) if out is None else out
+        self._call_hook(self.lib.mvd_op_target_encoder, (L.ptr(x), L.ptr(pre), n, *[arr(ts) for ts in lists], L.ptr(out)), [out])
+        _nan_guard_intact(out, rows, "op_target_encoder")
+        return out
+
+    def op_small_linear(self, a, w, bias, rows, act=0, lda=0, ldo=0, start=None, a_off=0):
+        """mvd_op_small_linear: a [in rows, K] placed a_off floats into a NaN buffer with rows of lda; w [N, K]; start: the result
+        is added to these values -> (out [|rows|, N], form_used)."""
+        in_rows, K = (1, 1) if a is None else a.shape
+        N = 1 if w is None else w.shape[0]
+        lda = lda or K
+        abuf = torch.full((in_rows * max(lda, K) + 8,), float("nan"), device=self.device)
+        if a is not None:
+            abuf[a_off:a_off + in_rows * lda].view(in_rows, lda)[:, :K] = self._dev(a)
+        w, b = self._dev(w), self._dev(bias)
+        ob, op, ldo_ = self._rows_out(abs(rows) or 1, N, max(ldo, N), start)
+        form = self._call_hook(self.lib.mvd_op_small_linear, (None if a is None else abuf.data_ptr() + 4 * a_off, lda, rows, K, L.ptr(w),
+                                                             L.ptr(b), N, act, op, ldo or N, start is not None), [ob], form=True)
+        return self._rows_result(ob, abs(rows), N, "op_small_linear"), form
+
+    def op_timestep_embedding(self, t, dim):
+        t = self._dev(t, torch.int64)
+        B = t.shape[0]
+        ob, op, _ = self._rows_out(B, max(dim, 1))
+        self._call_hook(self.lib.mvd_op_timestep_embedding, (L.ptr(t), B, dim, op), [ob])
+        return self._rows_result(ob, B, dim, "op_timestep_embedding")
+
+    def op_layout(self, op, x, B, Cc, HW, ld, cpad=0):
+        """mvd_op_layout.  op 0: x [B, C, HW] -> ([B * HW, cpad], form), rows of ld floats whose columns from cpad on must come back
+        untouched; op 1: x [B * HW, C] in NaN rows of ld floats -> ([B, C, HW], form)."""
+        if op == 1:
+            xb, xp, _ = self._rows_in(x, max(ld, Cc))
+            ob, optr, _ = self._rows_out(B * Cc, HW)
+        else:
+            xb = self._dev(x)
+            xp = L.ptr(xb)
+            ob, optr, _ = self._rows_out(B * HW, max(cpad, 1), max(ld, 1))
+        form = self._call_hook(self.lib.mvd_op_layout, (op, xp, B, Cc, HW, ld, cpad, optr), [ob], form=True)
+        if op == 1:
+            return self._rows_result(ob, B * Cc, HW, "op_layout").reshape(B, Cc, HW), form
+        return self._rows_result(ob, B * HW, cpad, "op_layout"), form
+
+    def op_pack_weight(self, src, N, Cin, taps, transposed=0, geglu=0, cin_src=0, xp=0, dst_off=0):
+        """mvd_op_pack_weight at dst_off halfs into a 16-bit 0xFF buffer -> ([taps, N, Cin] as written, form)."""
+        src = self._dev(src)
+        n = max(taps * N * Cin, 1)
+        buf = torch.full((max(dst_off, 0) + n + 64,), -1, dtype=torch.int16, device=self.device)
+        form = self._call_hook(self.lib.mvd_op_pack_weight, (L.ptr(src), N, Cin, taps, transposed, geglu, cin_src, xp, dst_off, L.ptr(buf)),
+                               [buf.view(torch.int32)], form=True)
+        assert bool((buf[:dst_off] == -1).all()) and bool((buf[dst_off + n:] == -1).all()), "op_pack_weight: the launch wrote outside its result"
+        return buf[dst_off:dst_off + n].view(torch.float16 if L.DTYPE == "f16" else torch.bfloat16).reshape(taps, N, Cin).clone(), form
+
+    def op_move(self, op, a, b, ints, rows, width, ld=0, f32=False):
+        """mvd_op_move: a (fp32) and b (fp32 or int32) as the op takes them, ints (i0 .. i4, padded with 0) -> [rows, width] of a
+        guarded result with rows of ld."""
+        a = self._dev(a)
+        b = None if b is None else b.detach().to(self.device).contiguous()
+        ints = tuple(ints) + (0,) * (5 - len(ints))
+        out = self._guarded(rows, ld or width, f32=f32)
+        self._call_hook(self.lib.mvd_op_move, (op, L.ptr(a), L.ptr(b), *ints, L.ptr(out)), [self._bits(out)])
+        self._guard_intact(out, rows, width, f"op_move (op {op})")
+        return out[:rows, :width].clone()
+
+    def op_fold(self, op, a, b, heads=1, hd=1, Cc=1, I=1, scale=1.0, M=0, N=0, K=0, lda=0, ldb=0, ldc=0, out_f32=True):
+        """mvd_op_fold: op 0 (Wq, Wk) -> [heads Cc, I]; 1 (Wo, Wv) -> [I, heads Cc]; 2 a [M, lda], b [K, ldb] -> [M, N] in rows of ldc."""
+        a, b = self._dev(a), self._dev(b)
+        rows, width, ld = ((heads * Cc, I, I), (I, heads * Cc, heads * Cc), (M, N, ldc or N))[min(max(op, 0), 2)]
+        out = self._guarded(max(rows, 1), max(ld, width, 1), f32=out_f32)
+        self._call_hook(self.lib.mvd_op_fold, (op, L.ptr(a), L.ptr(b), heads, hd, Cc, I, scale, M, N, K, lda, ldb, ldc, bool(out_f32), L.ptr(out)),
+                        [self._bits(out)])
+        self._guard_intact(out, rows, width, f"op_fold (op {op})")
+        return out[:rows, :width].clone()
+
+    def op_cfg_assemble(self, x_noisy, x_input, clip, timesteps, copies):
+        """mvd_op_cfg_assemble: x_noisy [B, TN, 4, HW], x_input [B, 4, HW], clip [B, dim], timesteps (host ints) -> (xin [rows, HW, 8],
+        ctx [rows, dim], tt [rows]), rows = copies B TN; results preset to NaN / -1 with a guard behind each."""
+        B, TN, _, HW = x_noisy.shape
+        dim = clip.shape[1]
+        rows = max(copies, 1) * B * TN
+        xn, xi, cl = self._dev(x_noisy), self._dev(x_input), self._dev(clip)
+        ts = None if timesteps is None else (C.c_int64 * B)(*[int(t) for t in timesteps])
+        xin, ctx = _nan_guarded(rows * HW, 8, self.device), _nan_guarded(rows, dim, self.device)
+        tt = torch.full((rows + 1,), -1, dtype=torch.int64, device=self.device)
+        self._call_hook(self.lib.mvd_op_cfg_assemble, (L.ptr(xn), L.ptr(xi), L.ptr(cl), ts, B, TN, HW, dim, copies, L.ptr(xin), L.ptr(ctx),
+                                                       L.ptr(tt)), [xin, ctx, tt.view(torch.int32)])
+        _nan_guard_intact(xin, rows * HW, "op_cfg_assemble (xin)")
+        _nan_guard_intact(ctx, rows, "op_cfg_assemble (ctx)")
+        assert int(tt[rows]) == -1, "op_cfg_assemble: the launch wrote behind the timesteps"
+        return xin[:rows * HW].reshape(rows, HW, 8).clone(), ctx[:rows].clone(), tt[:rows].clone()
+
+    def op_cfg_ddim(self, ec, eu, x, noise, k, want_eps=True, want_x=True):
+        """mvd_op_cfg_ddim over flat tensors; k: dict(scale, s1m, sqrt_at, sqrt_aprev, dir_coef, sigma) -> (eps or None, x_prev or None)"""
+        ec, eu, x, noise = self._dev(ec), self._dev(eu), self._dev(x), self._dev(noise)
+        n = 0 if ec is None else ec.numel()
+        eb = _nan_guarded(1, max(n, 1), self.device) if want_eps else None
+        xb = _nan_guarded(1, max(n, 1), self.device) if want_x else None
+        self._call_hook(self.lib.mvd_op_cfg_ddim, (L.ptr(ec), L.ptr(eu), k["scale"], L.ptr(x), L.ptr(noise), k["s1m"], k["sqrt_at"], k["sqrt_aprev"],
+                                                   k["dir_coef"], k["sigma"], L.ptr(eb), L.ptr(xb), n), [t for t in (eb, xb) if t is not None])
+        for t in (eb, xb):
+            if t is not None:
+                _nan_guard_intact(t, 1, "op_cfg_ddim")
+        return None if eb is None else eb[0].clone(), None if xb is None else xb[0].clone()
+
+    def op_small_mix(self, op, a, b=None, w=None, ints=(), n=0, rows=1, width=1, start=None):
+        """mvd_op_small_mix: op 0 fuse_views (ints: n_views, Nv, total_views, accumulate), 1 mse, 2 accumulate_f32 (start += a),
+        3 add_rows -> [rows, width]"""
+        a, b, w = self._dev(a), self._dev(b), self._dev(w)
+        ints = tuple(ints) + (0,) * (4 - len(ints))
+        ob, op_, _ = self._rows_out(rows, width, 0, start)
+        self._call_hook(self.lib.mvd_op_small_mix, (op, L.ptr(a), L.ptr(b), L.ptr(w), *ints, n, op_), [ob])
+        return self._rows_result(ob, rows, width, f"op_small_mix (op {op})")
+
     # ---- training-backward adjoints of one layer (mvd_op_*_bwd, mvd_op_tgemm): reference layouts in, reference layouts out.
     # accum = (dx0, dW0, db0): the gradients start from these values (otherwise from zero: dx written, dW / db added to zero).
     def _pad_last(self, t, n):
