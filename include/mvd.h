@@ -382,7 +382,7 @@ int mvd_op_image_metrics(const void* pred, int pred_dtype, int pred_layout, cons
  *                 a NaN spread.  fp32 in a fixed order, no floating-point atomics: two calls agree bit for bit.
  * Errors, which launch nothing: a null pointer (but visible); N < 1, Nv < 1, Nf < 1; H or W < 1 or > 4096; N H W >= 2^31;
  * z_near <= 0 or non-finite; power < 1; an unknown dtype or layout; N > 65535, N Nv >= 2^30.
- * Not computed: UV texture maps, perspective-correct attribute rendering. */
+ * UV texture atlases and perspective-correct rendering: the next block. */
 int mvd_op_mesh_project(const float* verts, const float* K, const float* RT, int N, int Nv, float z_near, int32_t* xy, int32_t* key,
                         void* stream);
 int mvd_op_mesh_raster(const int32_t* xy, const int32_t* key, const int32_t* faces, int N, int Nv, int Nf, int H, int W, int32_t* face_id,
@@ -392,6 +392,65 @@ int mvd_op_mesh_vertex_colors(const void* images, int dtype, int layout, const i
                               const float* centres, int N, int Nv, int Nf, int H, int W, float power, int bias, int two_sided,
                               float fill_r, float fill_g, float fill_b, float* color, float* weight_sum, int32_t* n_seen, float* spread,
                               unsigned char* visible, void* stream);
+/* UV texture atlases out of the same views (csrc/k_mesh_uv.hip; shared device helpers in csrc/mesh.h): vertex normals on the device, a
+ * per-texel bake with the visibility and the weights of mvd_op_mesh_vertex_colors, a dilation of the atlas into its gutters, and a
+ * render of the textured mesh with perspective-correct UVs.  No context; device pointers; each call synchronises the stream.
+ *   conventions   uv [Nt,2] float; face_uv [Nf,3] int32, indices into uv, parallel to faces [Nf,3].  OBJ convention: u to the right,
+ *                 v up, (0, 0) at the bottom-left.  The atlas is [Ht,Wt,3] with row 0 at the top (a PNG written as is): texel (i, j)
+ *                 has its centre at u = (j + 0.5) / Wt, v = 1 - (i + 0.5) / Ht.  Chart coordinates in 1/16 texel:
+ *                 xs = rint(16 (u Wt - 0.5)), ys = rint(16 ((1 - v) Ht - 0.5)), computed on the host in float64 (mesh.uv_to_atlas) and
+ *                 passed as int32 uv_xy [Nt,2].  mvd_op_mesh_raster on them (N = 1, Nv = Nt, faces = face_uv, key = 1 everywhere) IS
+ *                 the UV-space rasteriser: its face_id [1,Ht,Wt] is the texel -> face map tex_face (-1: no chart; a texel on a
+ *                 shared chart edge belongs to one face by the top-left rule, overlapping charts go to the smallest face index).  A
+ *                 chart vertex beyond the guard band is invalid here as it is there.
+ *   mvd_op_mesh_vertex_normals   verts [F,Nv,3]; the vertex -> face incidence of the topology in CSR form, built once on the host:
+ *                 inc_ptr [Nv+1], inc_face [3 Nf], the faces of a vertex in ascending order.  One thread per (frame, vertex):
+ *                 the sum of cross(v1 - v0, v2 - v0) over its incident faces in table order, fp32, then divided by its length; a
+ *                 vertex with no face or a zero sum gets the zero vector.  A row of inc_ptr outside 0 <= lo <= hi <= 3 Nf, a face
+ *                 index outside [0, Nf) or a corner outside [0, Nv) is never dereferenced and is counted (by frame 0) into
+ *                 *bad_faces (one device int).  No floating-point atomics: frame f of a batch equals the frame computed alone.
+ *   mvd_op_mesh_texel_bake   images / dtype / layout / N / H / W, face_id and pix_key [N,H,W] as mvd_op_mesh_vertex_colors takes them;
+ *                 K [N,3,3], RT [N,3,4], centres [N,3], z_near as mvd_op_mesh_project; verts, normals [Nv,3]; faces, face_uv [Nf,3];
+ *                 uv_xy [Nt,2]; tex_face [Ht,Wt].  A workgroup owns a 16 x 16 tile of texels.  Texel (i, j) with f = tex_face in
+ *                 [0, Nf), valid indices and valid chart vertices of non-zero area A: the three int64 edge functions e_k of chart
+ *                 triangle f at (16 j, 16 i), exactly as the rasteriser computes them (orientation swap included);
+ *                 b_k = (float)e_k / (float)A belongs to corner k of the face AS STORED, whichever orientation the chart has;
+ *                 p = sum b_k verts[faces[f][k]], n = sum b_k normals[...] (not normalised: the cosine normalises it).  For every
+ *                 view in index order the fp32 chain of mvd_op_mesh_project on p gives xs, ys, key; the texel is visible in the view
+ *                 iff they are valid, the nearest pixel ((xs + 8) >> 4, (ys + 8) >> 4) is inside the image and covered, and the
+ *                 winning face there IS f or key + bias >= pix_key.  Weight and colour as for the vertices (cosine between n and
+ *                 centre - p; bilinear at the snapped position).  texture [Ht,Wt,3] = sum w c / sum w; weight_sum, n_seen, spread
+ *                 [Ht,Wt] as for the vertices (spread from a second pass).  A texel without a face or with a zero weight sum: the
+ *                 fill colour, n_seen as counted, a NaN spread.  Nullable taps: visible [N,Ht,Wt] bytes, pos [Ht,Wt,3] (p; NaN
+ *                 without a face), txy [N,Ht,Wt,2] and tkey [N,Ht,Wt] (the per-view integers; 0 without a face).  fp32 in a fixed
+ *                 order, no floating-point atomics: two calls agree bit for bit.
+ *   mvd_op_mesh_texture_dilate   texture [Ht,Wt,3] fp32, valid [Ht,Wt] bytes, passes in 0..64 -> texture_out, valid_out.  In a round an
+ *                 invalid texel with at least one valid 8-neighbour (validity BEFORE the round) becomes valid and takes the mean of
+ *                 the valid neighbours: summed in fp32 in the order N, NE, E, SE, S, SW, W, NW, divided by their count.  One launch
+ *                 per round between two buffers; passes = 0 copies.  The outputs must not alias the inputs.
+ *   mvd_op_mesh_render_uv   xy [N,Nv,2], key [N,Nv], face_id [N,H,W] as the projection and the rasteriser return them; faces, face_uv,
+ *                 uv [Nt,2] fp32, texture [Ht,Wt,3] fp32 in [0, 1].  Per covered pixel: the int64 edge functions e_k of the winning
+ *                 face and g_k = e_k key_k (exact, within the 2^59 above); perspective-correct barycentrics
+ *                 b_k = (float)((double)g_k / (double)(g_0 + g_1 + g_2)) -- keys are proportional to 1 / Z, so this is the textbook
+ *                 division done on integers; (u, v) = sum b_k uv[face_uv[f][k]]; bilinear, clamp to edge, at (u Wt - 0.5,
+ *                 (1 - v) Ht - 0.5).  images: float32 in [-1, 1] (2 c - 1), layout 0 [N,3,H,W] or 1 [N,H,W,3]; uncovered pixels, and
+ *                 pixels whose face has an index out of range, take the background.
+ * Errors, which launch nothing: a null pointer (but the taps); F, N, Nv, Nf or Nt < 1; N > 65535; F Nv or N Nv >= 2^30; 3 Nf >= 2^31;
+ * H, W, Ht or Wt outside 1..4096; N H W or N Ht Wt >= 2^31; z_near <= 0 or non-finite; power < 1; passes outside 0..64; an unknown
+ * dtype or layout.  Not computed: UV unwrapping beyond mesh.triangle_atlas, mip-maps, seam-aware blending across charts. */
+int mvd_op_mesh_vertex_normals(const float* verts, const int32_t* faces, const int32_t* inc_ptr, const int32_t* inc_face, int F, int Nv,
+                               int Nf, float* normals, int32_t* bad_faces, void* stream);
+int mvd_op_mesh_texel_bake(const void* images, int dtype, int layout, const int32_t* face_id, const int32_t* pix_key, const float* K,
+                           const float* RT, const float* centres, float z_near, const float* verts, const float* normals,
+                           const int32_t* faces, const int32_t* uv_xy, const int32_t* face_uv, const int32_t* tex_face, int N, int Nv,
+                           int Nf, int Nt, int H, int W, int Ht, int Wt, float power, int bias, int two_sided, float fill_r, float fill_g,
+                           float fill_b, float* texture, float* weight_sum, int32_t* n_seen, float* spread, unsigned char* visible,
+                           float* pos, int32_t* txy, int32_t* tkey, void* stream);
+int mvd_op_mesh_texture_dilate(const float* texture, const unsigned char* valid, int Ht, int Wt, int passes, float* texture_out,
+                               unsigned char* valid_out, void* stream);
+int mvd_op_mesh_render_uv(const int32_t* xy, const int32_t* key, const int32_t* face_id, const int32_t* faces, const int32_t* face_uv,
+                          const float* uv, const float* texture, int N, int Nv, int Nf, int Nt, int H, int W, int Ht, int Wt, int layout,
+                          float bg_r, float bg_g, float bg_b, float* images, void* stream);
 /* The morphable-model forward (csrc/k_morph.hip): FLAME / SMPL-X parameters to vertices by linear blend skinning, the formulas of
  * the reference's third_party/MICA/models/lbs.py.  No context; device pointers but `parents`; each call synchronises the stream.
  * Everything is fp32 on the vector ALU with fused multiply-adds in an order fixed by indices alone, no atomics: two calls agree

@@ -651,6 +651,60 @@ int mvd_op_mesh_vertex_colors(const void* images, int dtype, int layout, const i
   return rc;
 }
 
+// ---- UV texture atlases (csrc/k_mesh_uv.hip): no context, the caller's device buffers
+int mvd_op_mesh_vertex_normals(const float* verts, const int32_t* faces, const int32_t* inc_ptr, const int32_t* inc_face, int F, int Nv,
+                               int Nf, float* normals, int32_t* bad_faces, void* stream) {
+  RET_IF(mesh_vertex_normals_check("mvd_op_mesh_vertex_normals", verts, faces, inc_ptr, inc_face, F, Nv, Nf, normals, bad_faces));
+  hipStream_t s = S(stream);
+  int rc = launch_mesh_vertex_normals(verts, faces, inc_ptr, inc_face, F, Nv, Nf, normals, bad_faces, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_mesh_vertex_normals: stream synchronisation failed");
+  return rc;
+}
+
+int mvd_op_mesh_texel_bake(const void* images, int dtype, int layout, const int32_t* face_id, const int32_t* pix_key, const float* K,
+                           const float* RT, const float* centres, float z_near, const float* verts, const float* normals,
+                           const int32_t* faces, const int32_t* uv_xy, const int32_t* face_uv, const int32_t* tex_face, int N, int Nv,
+                           int Nf, int Nt, int H, int W, int Ht, int Wt, float power, int bias, int two_sided, float fill_r, float fill_g,
+                           float fill_b, float* texture, float* weight_sum, int32_t* n_seen, float* spread, unsigned char* visible,
+                           float* pos, int32_t* txy, int32_t* tkey, void* stream) {
+  MeshBakeArgs a;
+  a.images = images, a.face_id = face_id, a.pix_key = pix_key, a.faces = faces, a.uv_xy = uv_xy, a.face_uv = face_uv, a.tex_face = tex_face;
+  a.K = K, a.RT = RT, a.centres = centres, a.verts = verts, a.normals = normals;
+  a.dtype = dtype, a.layout = layout, a.N = N, a.Nv = Nv, a.Nf = Nf, a.Nt = Nt, a.H = H, a.W = W, a.Ht = Ht, a.Wt = Wt, a.bias = bias;
+  a.two_sided = two_sided, a.z_near = z_near, a.power = power, a.fill[0] = fill_r, a.fill[1] = fill_g, a.fill[2] = fill_b;
+  a.texture = texture, a.weight_sum = weight_sum, a.spread = spread, a.pos = pos, a.n_seen = n_seen, a.txy = txy, a.tkey = tkey;
+  a.visible = visible;
+  RET_IF(mesh_texel_bake_check("mvd_op_mesh_texel_bake", a));
+  hipStream_t s = S(stream);
+  int rc = launch_mesh_texel_bake(a, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_mesh_texel_bake: stream synchronisation failed");
+  return rc;
+}
+
+int mvd_op_mesh_texture_dilate(const float* texture, const unsigned char* valid, int Ht, int Wt, int passes, float* texture_out,
+                               unsigned char* valid_out, void* stream) {
+  RET_IF(mesh_texture_dilate_check("mvd_op_mesh_texture_dilate", texture, valid, Ht, Wt, passes, texture_out, valid_out));
+  hipStream_t s = S(stream);
+  void* scratch = nullptr;  // the second buffer of the ping-pong lives for this call only
+  if (passes > 1) HIP_CHECK_RET(hipMalloc(&scratch, mesh_texture_dilate_scratch_bytes(Ht, Wt)));
+  int rc = launch_mesh_texture_dilate(texture, valid, Ht, Wt, passes, texture_out, valid_out, scratch, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_mesh_texture_dilate: stream synchronisation failed");
+  if (scratch) hipFree(scratch);
+  return rc;
+}
+
+int mvd_op_mesh_render_uv(const int32_t* xy, const int32_t* key, const int32_t* face_id, const int32_t* faces, const int32_t* face_uv,
+                          const float* uv, const float* texture, int N, int Nv, int Nf, int Nt, int H, int W, int Ht, int Wt, int layout,
+                          float bg_r, float bg_g, float bg_b, float* images, void* stream) {
+  RET_IF(mesh_render_uv_check("mvd_op_mesh_render_uv", xy, key, face_id, faces, face_uv, uv, texture, N, Nv, Nf, Nt, H, W, Ht, Wt, layout,
+                              images));
+  hipStream_t s = S(stream);
+  int rc = launch_mesh_render_uv(xy, key, face_id, faces, face_uv, uv, texture, N, Nv, Nf, Nt, H, W, Ht, Wt, layout, bg_r, bg_g, bg_b, images,
+                                 s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_mesh_render_uv: stream synchronisation failed");
+  return rc;
+}
+
 // ---- the morphable-model forward (csrc/k_morph.hip): no context, the caller's device buffers; parents is a host array
 int mvd_op_morph_pose(const float* betas, const float* pose, const float* j_template, const float* j_dirs, const int32_t* parents, int F,
                       int NB, int J, float* j_rest, float* rot, float* pose_feature, float* joints, float* A, void* stream) {

@@ -315,6 +315,36 @@ int launch_mesh_vertex_colors(const void* images, int dtype, int layout, const i
                               const int* pix_key, const float* verts, const float* normals, const float* centres, int N, int Nv, int Nf,
                               int H, int W, float power, int bias, int two_sided, float fill_r, float fill_g, float fill_b, float* color,
                               float* weight_sum, int* n_seen, float* spread, unsigned char* visible, hipStream_t s);
+// k_mesh_uv.hip: UV texture atlases (include/mvd.h: mvd_op_mesh_vertex_normals / _texel_bake / _texture_dilate / _render_uv).  The
+// *_check functions are the argument errors (0 = fine) and touch no device.  MeshBakeArgs holds the arguments of
+// mvd_op_mesh_texel_bake as the header names them; visible / pos / txy / tkey may be null.
+struct MeshBakeArgs {
+  const void* images;
+  const int *face_id, *pix_key, *faces, *uv_xy, *face_uv, *tex_face;
+  const float *K, *RT, *centres, *verts, *normals;
+  int dtype, layout, N, Nv, Nf, Nt, H, W, Ht, Wt, bias, two_sided;
+  float z_near, power, fill[3];
+  float *texture, *weight_sum, *spread, *pos;
+  int *n_seen, *txy, *tkey;
+  unsigned char* visible;
+};
+int mesh_vertex_normals_check(const char* who, const float* verts, const int* faces, const int* inc_ptr, const int* inc_face, int F, int Nv,
+                              int Nf, const float* normals, const int* bad_faces);
+int launch_mesh_vertex_normals(const float* verts, const int* faces, const int* inc_ptr, const int* inc_face, int F, int Nv, int Nf,
+                               float* normals, int* bad_faces, hipStream_t s);
+int mesh_texel_bake_check(const char* who, const MeshBakeArgs& a);
+int launch_mesh_texel_bake(const MeshBakeArgs& a, hipStream_t s);
+int mesh_texture_dilate_check(const char* who, const float* texture, const unsigned char* valid, int Ht, int Wt, int passes,
+                              const float* texture_out, const unsigned char* valid_out);
+size_t mesh_texture_dilate_scratch_bytes(int Ht, int Wt);
+int launch_mesh_texture_dilate(const float* texture, const unsigned char* valid, int Ht, int Wt, int passes, float* texture_out,
+                               unsigned char* valid_out, void* scratch, hipStream_t s);
+int mesh_render_uv_check(const char* who, const int* xy, const int* key, const int* face_id, const int* faces, const int* face_uv,
+                         const float* uv, const float* texture, int N, int Nv, int Nf, int Nt, int H, int W, int Ht, int Wt, int layout,
+                         const float* images);
+int launch_mesh_render_uv(const int* xy, const int* key, const int* face_id, const int* faces, const int* face_uv, const float* uv,
+                          const float* texture, int N, int Nv, int Nf, int Nt, int H, int W, int Ht, int Wt, int layout, float bg_r, float bg_g,
+                          float bg_b, float* images, hipStream_t s);
 // k_morph.hip: the morphable-model forward (include/mvd.h: mvd_op_morph_pose / _skin / _landmarks).  The *_check functions are the
 // argument errors (0 = fine) and touch no device; parents [J] is a HOST array, copied into the pose kernel's argument struct.
 // pose_feature [F][9 (J - 1)] may be null when J == 1, post [12] may be null; everything else is a device buffer of the caller.

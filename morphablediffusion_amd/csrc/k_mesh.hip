@@ -22,11 +22,11 @@
 //   mesh_resolve_kernel  one thread per pixel: face_id (-1 background) and pix_key (0 background) out of the packed winner.
 //   mesh_vertex_colors_kernel  one thread per vertex, views in index order, two passes (weighted mean, then the weighted spread
 //                        about it), fp32 in a fixed order and no floating-point atomics: two calls agree bit for bit.
-#include "common.h"
+// The projection chain, the vertex test, the weight and the bilinear sample are csrc/mesh.h, shared with k_mesh_uv.hip.
+#include "mesh.h"
 
 namespace {
 
-constexpr int MESH_SUB = 4, MESH_ONE = 1 << MESH_SUB, MESH_KMAX = (1 << 24) - 1, MESH_GUARD_PX = 4096, MESH_GUARD = MESH_GUARD_PX << MESH_SUB;
 constexpr int MESH_T = 256, MESH_SMALL = 32;
 
 __global__ __launch_bounds__(MESH_T) void mesh_project_kernel(const float* __restrict__ verts, const float* __restrict__ K,
@@ -37,19 +37,8 @@ __global__ __launch_bounds__(MESH_T) void mesh_project_kernel(const float* __res
   const float* r = RT + (size_t)n * 12;
   const float* k = K + (size_t)n * 9;
   const float x = verts[(size_t)v * 3], y = verts[(size_t)v * 3 + 1], z = verts[(size_t)v * 3 + 2];
-  const float X = r[0] * x + r[1] * y + r[2] * z + r[3];
-  const float Y = r[4] * x + r[5] * y + r[6] * z + r[7];
-  const float Z = r[8] * x + r[9] * y + r[10] * z + r[11];
-  const float u = (k[0] * X + k[1] * Y) / Z + k[2];
-  const float w = k[4] * Y / Z + k[5];
-  int xs = 0, ys = 0, kk = 0;
-  // a NaN fails every comparison: Z >= z_near and the guard band are written so that it lands on the invalid side
-  if (Z >= z_near && fabsf(u) <= (float)MESH_GUARD_PX && fabsf(w) <= (float)MESH_GUARD_PX) {
-    xs = (int)rintf(u * (float)MESH_ONE);
-    ys = (int)rintf(w * (float)MESH_ONE);
-    const float q = rintf(z_near / Z * (float)MESH_KMAX);
-    kk = q >= 1.0f ? (q <= (float)MESH_KMAX ? (int)q : MESH_KMAX) : 1;
-  }
+  int xs, ys, kk;
+  mesh_project_point(r, k, x, y, z, z_near, xs, ys, kk);
   const size_t o = (size_t)n * Nv + v;
   xy[o * 2] = xs;
   xy[o * 2 + 1] = ys;
@@ -61,10 +50,6 @@ struct MeshTri {
   int j0, j1, i0, i1;  // bounding box in pixels, inclusive, inside the image
   int f;
 };
-
-__device__ inline bool mesh_vertex_ok(int xs, int ys, int k) {
-  return k >= 1 && k <= MESH_KMAX && xs >= -MESH_GUARD && xs <= MESH_GUARD && ys >= -MESH_GUARD && ys <= MESH_GUARD;
-}
 
 // twice the signed area after the orientation swap (> 0), or 0 when the face draws nothing in this view; bad: an index outside [0, Nv)
 __device__ inline long long mesh_setup(const int* __restrict__ xy, const int* __restrict__ key, const int* __restrict__ faces, int n,
@@ -109,12 +94,12 @@ __device__ inline long long mesh_setup(const int* __restrict__ xy, const int* __
 __device__ inline void mesh_pixel(const MeshTri& t, long long A, int i, int j, unsigned long long* __restrict__ win, int W) {
   const long long px = (long long)j << MESH_SUB, py = (long long)i << MESH_SUB;
   long long e[3];
+  mesh_edge_functions(t.x, t.y, px, py, e);  // csrc/mesh.h: the one definition, shared with the texel bake and the UV render
   bool in = true;
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const int a = (k + 1) % 3, b = (k + 2) % 3;
     const long long dx = t.x[b] - t.x[a], dy = t.y[b] - t.y[a];
-    e[k] = dx * (py - t.y[a]) - dy * (px - t.x[a]);
     in &= e[k] > 0 || (e[k] == 0 && (dy < 0 || (dy == 0 && dx > 0)));
   }
   if (!in) return;
@@ -167,13 +152,6 @@ __global__ __launch_bounds__(MESH_T) void mesh_resolve_kernel(const unsigned lon
   pix_key[p] = (int)(v >> 32);
 }
 
-// channel c of pixel (i, j) of view n in [0, 1]
-__device__ inline float mesh_texel(const void* __restrict__ img, int dtype, int layout, int H, int W, int n, int c, int i, int j) {
-  const size_t o = layout == 0 ? (((size_t)n * 3 + c) * H + i) * W + j : (((size_t)n * H + i) * W + j) * 3 + c;
-  if (dtype == 1) return (float)((const unsigned char*)img)[o] / 255.0f;
-  return (fminf(fmaxf(((const float*)img)[o], -1.0f), 1.0f) + 1.0f) * 0.5f;
-}
-
 struct MeshColorArgs {
   const void* img;
   const int *xy, *key, *faces, *face_id, *pix_key;
@@ -199,24 +177,8 @@ __device__ inline bool mesh_view_sample(const MeshColorArgs& a, int n, int v, fl
   // weight: cos of the angle between the normal and the direction to the camera centre
   const float dx = a.centres[n * 3] - a.verts[(size_t)v * 3], dy = a.centres[n * 3 + 1] - a.verts[(size_t)v * 3 + 1],
               dz = a.centres[n * 3 + 2] - a.verts[(size_t)v * 3 + 2];
-  const float nn = nx * nx + ny * ny + nz * nz, dd = dx * dx + dy * dy + dz * dz;
-  if (nn > 0.0f && dd > 0.0f) {
-    float cs = (nx * dx + ny * dy + nz * dz) / sqrtf(nn * dd);
-    cs = a.two_sided ? fabsf(cs) : fmaxf(cs, 0.0f);
-    cs = fminf(cs, 1.0f);
-    wgt = cs > 0.0f ? powf(cs, a.power) : 0.0f;
-  }
-  // bilinear, clamp to edge, at (xs / 16, ys / 16): the fractions are exact
-  const int j0 = xs >> MESH_SUB, i0 = ys >> MESH_SUB;
-  const float fx = (float)(xs & (MESH_ONE - 1)) * (1.0f / MESH_ONE), fy = (float)(ys & (MESH_ONE - 1)) * (1.0f / MESH_ONE);
-  const int ja = min(max(j0, 0), a.W - 1), jb = min(max(j0 + 1, 0), a.W - 1);
-  const int ia = min(max(i0, 0), a.H - 1), ib = min(max(i0 + 1, 0), a.H - 1);
-  for (int ch = 0; ch < 3; ++ch) {
-    const float c00 = mesh_texel(a.img, a.dtype, a.layout, a.H, a.W, n, ch, ia, ja), c01 = mesh_texel(a.img, a.dtype, a.layout, a.H, a.W, n, ch, ia, jb);
-    const float c10 = mesh_texel(a.img, a.dtype, a.layout, a.H, a.W, n, ch, ib, ja), c11 = mesh_texel(a.img, a.dtype, a.layout, a.H, a.W, n, ch, ib, jb);
-    const float top = c00 + fx * (c01 - c00), bot = c10 + fx * (c11 - c10);
-    c[ch] = top + fy * (bot - top);
-  }
+  wgt = mesh_view_weight(nx, ny, nz, dx, dy, dz, a.power, a.two_sided);
+  mesh_view_bilinear(a.img, a.dtype, a.layout, a.H, a.W, n, xs, ys, c);
   return true;
 }
 
@@ -260,8 +222,6 @@ __global__ __launch_bounds__(MESH_T) void mesh_vertex_colors_kernel(MeshColorArg
 }
 
 int mesh_fail(const char* who, const char* what) { return mvd_fail((std::string(who) + what).c_str()); }
-
-bool mesh_bad_image(int N, int H, int W) { return H < 1 || W < 1 || H > 4096 || W > 4096 || (long long)N * H * W > 0x7fffffffLL; }
 
 }  // namespace
 

@@ -1,0 +1,79 @@
+// Device helpers shared by the mesh texturing kernels (k_mesh.hip: per-vertex fusion; k_mesh_uv.hip: per-texel bake and the
+// UV render): the constants of include/mvd.h's mesh block, the fp32 projection chain, the integer vertex test, the view texel
+// fetch, the weight and the bilinear sample at a snapped position.  One definition, so that a vertex and a texel that sit at
+// the same point get the same integers, the same weight and the same colour.
+#pragma once
+#include "common.h"
+
+constexpr int MESH_SUB = 4, MESH_ONE = 1 << MESH_SUB, MESH_KMAX = (1 << 24) - 1, MESH_GUARD_PX = 4096, MESH_GUARD = MESH_GUARD_PX << MESH_SUB;
+
+// cam = R x + t, u = (K00 X + K01 Y) / Z + K02, v = K11 Y / Z + K12 in fp32; r: 12 floats of RT, k: 9 floats of K.  xs = ys = kk = 0
+// marks an invalid point.  A NaN fails every comparison: Z >= z_near and the guard band are written so that it lands on the
+// invalid side.
+__device__ inline void mesh_project_point(const float* __restrict__ r, const float* __restrict__ k, float x, float y, float z, float z_near,
+                                          int& xs, int& ys, int& kk) {
+  const float X = r[0] * x + r[1] * y + r[2] * z + r[3];
+  const float Y = r[4] * x + r[5] * y + r[6] * z + r[7];
+  const float Z = r[8] * x + r[9] * y + r[10] * z + r[11];
+  const float u = (k[0] * X + k[1] * Y) / Z + k[2];
+  const float w = k[4] * Y / Z + k[5];
+  xs = 0, ys = 0, kk = 0;
+  if (Z >= z_near && fabsf(u) <= (float)MESH_GUARD_PX && fabsf(w) <= (float)MESH_GUARD_PX) {
+    xs = (int)rintf(u * (float)MESH_ONE);
+    ys = (int)rintf(w * (float)MESH_ONE);
+    const float q = rintf(z_near / Z * (float)MESH_KMAX);
+    kk = q >= 1.0f ? (q <= (float)MESH_KMAX ? (int)q : MESH_KMAX) : 1;
+  }
+}
+
+__device__ inline bool mesh_vertex_ok(int xs, int ys, int k) {
+  return k >= 1 && k <= MESH_KMAX && xs >= -MESH_GUARD && xs <= MESH_GUARD && ys >= -MESH_GUARD && ys <= MESH_GUARD;
+}
+
+// channel c of pixel (i, j) of view n in [0, 1]
+__device__ inline float mesh_texel(const void* __restrict__ img, int dtype, int layout, int H, int W, int n, int c, int i, int j) {
+  const size_t o = layout == 0 ? (((size_t)n * 3 + c) * H + i) * W + j : (((size_t)n * H + i) * W + j) * 3 + c;
+  if (dtype == 1) return (float)((const unsigned char*)img)[o] / 255.0f;
+  return (fminf(fmaxf(((const float*)img)[o], -1.0f), 1.0f) + 1.0f) * 0.5f;
+}
+
+// weight of a view at a surface point: cos of the angle between the normal (any length) and the direction d to the camera centre,
+// max(0, cos)^power (two_sided: |cos|^power); a zero normal or a zero direction weighs 0
+__device__ inline float mesh_view_weight(float nx, float ny, float nz, float dx, float dy, float dz, float power, int two_sided) {
+  const float nn = nx * nx + ny * ny + nz * nz, dd = dx * dx + dy * dy + dz * dz;
+  float wgt = 0.0f;
+  if (nn > 0.0f && dd > 0.0f) {
+    float cs = (nx * dx + ny * dy + nz * dz) / sqrtf(nn * dd);
+    cs = two_sided ? fabsf(cs) : fmaxf(cs, 0.0f);
+    cs = fminf(cs, 1.0f);
+    wgt = cs > 0.0f ? powf(cs, power) : 0.0f;
+  }
+  return wgt;
+}
+
+// bilinear, clamp to edge, at the snapped position (xs / 16, ys / 16) of view n: the fractions are exact
+__device__ inline void mesh_view_bilinear(const void* __restrict__ img, int dtype, int layout, int H, int W, int n, int xs, int ys, float c[3]) {
+  const int j0 = xs >> MESH_SUB, i0 = ys >> MESH_SUB;
+  const float fx = (float)(xs & (MESH_ONE - 1)) * (1.0f / MESH_ONE), fy = (float)(ys & (MESH_ONE - 1)) * (1.0f / MESH_ONE);
+  const int ja = min(max(j0, 0), W - 1), jb = min(max(j0 + 1, 0), W - 1);
+  const int ia = min(max(i0, 0), H - 1), ib = min(max(i0 + 1, 0), H - 1);
+  for (int ch = 0; ch < 3; ++ch) {
+    const float c00 = mesh_texel(img, dtype, layout, H, W, n, ch, ia, ja), c01 = mesh_texel(img, dtype, layout, H, W, n, ch, ia, jb);
+    const float c10 = mesh_texel(img, dtype, layout, H, W, n, ch, ib, ja), c11 = mesh_texel(img, dtype, layout, H, W, n, ch, ib, jb);
+    const float top = c00 + fx * (c01 - c00), bot = c10 + fx * (c11 - c10);
+    c[ch] = top + fy * (bot - top);
+  }
+}
+
+// the three int64 edge functions of a triangle (x, y in 1/16 units, AFTER the orientation swap that makes A > 0) at (px, py):
+// e[k] belongs to the vertex k of the swapped triangle (include/mvd.h: mvd_op_mesh_raster); |e[k]| < 2^35
+__device__ inline void mesh_edge_functions(const int x[3], const int y[3], long long px, long long py, long long e[3]) {
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const int a = (k + 1) % 3, b = (k + 2) % 3;
+    const long long dx = x[b] - x[a], dy = y[b] - y[a];
+    e[k] = dx * (py - y[a]) - dy * (px - x[a]);
+  }
+}
+
+inline bool mesh_bad_image(int N, int H, int W) { return H < 1 || W < 1 || H > 4096 || W > 4096 || (long long)N * H * W > 0x7fffffffLL; }

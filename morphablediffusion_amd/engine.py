@@ -214,6 +214,175 @@ def op_mesh_vertex_colors(images, xy, key, faces, face_id, pix_key, verts, norma
     return out
 
 
+# ---- UV texture atlases (include/mvd.h: mvd_op_mesh_vertex_normals / _texel_bake / _texture_dilate / _render_uv; csrc/k_mesh_uv.hip)
+def _atlas_dims(who, Ht, Wt):
+    if not (1 <= Ht <= 4096 and 1 <= Wt <= 4096):
+        raise ValueError(f"{who}: the atlas needs Ht and Wt in 1..4096, got {(Ht, Wt)}")
+
+
+def op_mesh_vertex_normals(verts, faces, inc_ptr, inc_face, device=None, lib=None):
+    """mvd_op_mesh_vertex_normals on ``device`` (default: verts'): verts [F,Nv,3] float, faces [Nf,3], inc_ptr [Nv+1] and inc_face
+    [3 Nf] int32 (the vertex -> face incidence in CSR form, mesh.face_incidence).  Returns (normals [F,Nv,3] float32, bad [1] int32:
+    table entries that were not dereferenced) on the device."""
+    who = "op_mesh_vertex_normals"
+    if not torch.is_tensor(verts) or not verts.is_floating_point() or verts.dim() != 3 or verts.shape[2] != 3 or verts.shape[0] < 1 \
+            or verts.shape[1] < 1:
+        raise ValueError(f"{who}: verts must be a float tensor [F,Nv,3], got {getattr(verts, 'dtype', type(verts))} "
+                         f"{tuple(getattr(verts, 'shape', ()))}")
+    F, Nv = verts.shape[:2]
+    _i32("faces", faces, (None, 3), who)
+    Nf = faces.shape[0]
+    if Nf < 1:
+        raise ValueError(f"{who}: at least one face is needed")
+    _i32("inc_ptr", inc_ptr, (Nv + 1,), who)
+    _i32("inc_face", inc_face, (3 * Nf,), who)
+    if F > 65535 or F * Nv >= 2 ** 30:
+        raise ValueError(f"{who}: needs F <= 65535 and F Nv < 2^30, got (F, Nv) = {(F, Nv)}")
+    dev = verts.device if device is None else device
+    v = _f32(verts, dev)
+    faces, inc_ptr, inc_face = (t.detach().to(dev).contiguous() for t in (faces, inc_ptr, inc_face))
+    lib = lib or L.load()
+    normals = torch.full((F, Nv, 3), float("nan"), device=dev)
+    bad = torch.zeros((1,), device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_mesh_vertex_normals(L.ptr(v), L.ptr(faces), L.ptr(inc_ptr), L.ptr(inc_face), F, Nv, Nf, L.ptr(normals),
+                                               L.ptr(bad), _stream()))
+    return normals, bad
+
+
+def op_mesh_texel_bake(images, face_id, pix_key, K, RT, centres, z_near, verts, normals, faces, uv_xy, face_uv, tex_face, power=2.0,
+                       bias=4096, two_sided=False, fill=(0.5, 0.5, 0.5), taps=True, device=None, lib=None):
+    """mvd_op_mesh_texel_bake on ``device`` (default: images'): images [N,3,H,W] or [N,H,W,3], float (taken as [-1, 1]) or uint8;
+    face_id / pix_key [N,H,W] int32 as op_mesh_raster returns them; K [N,3,3], RT [N,3,4], centres [N,3], verts / normals [Nv,3]
+    float; faces / face_uv [Nf,3], uv_xy [Nt,2] (mesh.uv_to_atlas), tex_face [Ht,Wt] int32.  Returns a dict of device tensors:
+    texture [Ht,Wt,3], weight_sum, spread [Ht,Wt] (float32), n_seen [Ht,Wt] (int32) and, with ``taps``, visible [N,Ht,Wt] (bool),
+    pos [Ht,Wt,3], txy [N,Ht,Wt,2], tkey [N,Ht,Wt]: the kernel's own surface point and per-view integers."""
+    who = "op_mesh_texel_bake"
+    if images.dim() != 4 or (images.shape[1] == 3) == (images.shape[3] == 3):
+        raise ValueError(f"{who}: images must be [N,3,H,W] or [N,H,W,3], got {tuple(images.shape)}")
+    if images.dtype != torch.uint8 and not images.is_floating_point():
+        raise ValueError(f"{who}: images must be a float tensor or uint8, not {images.dtype}")
+    dtype, layout = int(images.dtype == torch.uint8), 0 if images.shape[1] == 3 else 1
+    N, H, W = (images.shape[0], images.shape[2], images.shape[3]) if layout == 0 else tuple(images.shape[:3])
+    _mesh_image_dims(who, N, H, W)
+    _i32("face_id", face_id, (N, H, W), who)
+    _i32("pix_key", pix_key, (N, H, W), who)
+    _i32("faces", faces, (None, 3), who)
+    Nf = faces.shape[0]
+    _i32("face_uv", face_uv, (Nf, 3), who)
+    _i32("uv_xy", uv_xy, (None, 2), who)
+    _i32("tex_face", tex_face, (None, None), who)
+    Nt, (Ht, Wt) = uv_xy.shape[0], tex_face.shape
+    _atlas_dims(who, Ht, Wt)
+    if not torch.is_tensor(verts) or verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError(f"{who}: verts must be [Nv,3]")
+    Nv = verts.shape[0]
+    if Nv < 1 or Nf < 1 or Nt < 1 or N * Ht * Wt >= 2 ** 31:
+        raise ValueError(f"{who}: needs Nv, Nf, Nt >= 1 and N Ht Wt < 2^31, got Nv = {Nv}, Nf = {Nf}, Nt = {Nt}, atlas {(Ht, Wt)}")
+    for name, t, shape in (("verts", verts, (Nv, 3)), ("normals", normals, (Nv, 3)), ("centres", centres, (N, 3)), ("K", K, (N, 3, 3)),
+                           ("RT", RT, (N, 3, 4))):
+        if not torch.is_tensor(t) or tuple(t.shape) != shape or not t.is_floating_point():
+            raise ValueError(f"{who}: {name} must be a float tensor {list(shape)}, got {getattr(t, 'dtype', type(t))} "
+                             f"{tuple(getattr(t, 'shape', ()))}")
+    power, fill, z_near = float(power), tuple(float(c) for c in fill), float(z_near)
+    if not (power >= 1.0 and power < float("inf")):
+        raise ValueError(f"{who}: power must be at least 1 and finite, got {power}")
+    if not (z_near > 0.0 and z_near < float("inf")):
+        raise ValueError(f"{who}: z_near must be positive and finite, got {z_near}")
+    if len(fill) != 3:
+        raise ValueError(f"{who}: fill must be three numbers")
+    dev = images.device if device is None else device
+    img = images.detach().to(device=dev, dtype=torch.uint8 if dtype else torch.float32).contiguous()
+    face_id, pix_key, faces, uv_xy, face_uv, tex_face = (t.detach().to(dev).contiguous()
+                                                         for t in (face_id, pix_key, faces, uv_xy, face_uv, tex_face))
+    k, rt, cen, v, nrm = (_f32(t, dev) for t in (K, RT, centres, verts, normals))
+    lib = lib or L.load()
+    nan = float("nan")
+    out = {"texture": torch.full((Ht, Wt, 3), nan, device=dev), "weight_sum": torch.full((Ht, Wt), nan, device=dev),
+           "n_seen": torch.full((Ht, Wt), -1, device=dev, dtype=torch.int32), "spread": torch.full((Ht, Wt), nan, device=dev)}
+    tap = {}
+    if taps:
+        tap = {"visible": torch.zeros((N, Ht, Wt), device=dev, dtype=torch.uint8), "pos": torch.full((Ht, Wt, 3), nan, device=dev),
+               "txy": torch.zeros((N, Ht, Wt, 2), device=dev, dtype=torch.int32),
+               "tkey": torch.zeros((N, Ht, Wt), device=dev, dtype=torch.int32)}
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_mesh_texel_bake(L.ptr(img), dtype, layout, L.ptr(face_id), L.ptr(pix_key), L.ptr(k), L.ptr(rt), L.ptr(cen), z_near,
+                                           L.ptr(v), L.ptr(nrm), L.ptr(faces), L.ptr(uv_xy), L.ptr(face_uv), L.ptr(tex_face), N, Nv, Nf, Nt,
+                                           H, W, Ht, Wt, power, int(bias), int(bool(two_sided)), fill[0], fill[1], fill[2],
+                                           L.ptr(out["texture"]), L.ptr(out["weight_sum"]), L.ptr(out["n_seen"]), L.ptr(out["spread"]),
+                                           L.ptr(tap.get("visible")), L.ptr(tap.get("pos")), L.ptr(tap.get("txy")), L.ptr(tap.get("tkey")),
+                                           _stream()))
+    if taps:
+        tap["visible"] = tap["visible"].bool()
+    out.update(tap)
+    return out
+
+
+def op_mesh_texture_dilate(texture, valid, passes, device=None, lib=None):
+    """mvd_op_mesh_texture_dilate on ``device`` (default: texture's): texture [Ht,Wt,3] float, valid [Ht,Wt] (bool or uint8, nonzero =
+    valid), passes in 0..64.  Returns (texture [Ht,Wt,3] float32, valid [Ht,Wt] bool) after ``passes`` rounds; the inputs stay."""
+    who = "op_mesh_texture_dilate"
+    if not torch.is_tensor(texture) or not texture.is_floating_point() or texture.dim() != 3 or texture.shape[2] != 3:
+        raise ValueError(f"{who}: texture must be a float tensor [Ht,Wt,3], got {tuple(getattr(texture, 'shape', ()))}")
+    Ht, Wt = texture.shape[:2]
+    _atlas_dims(who, Ht, Wt)
+    if not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != (Ht, Wt):
+        raise ValueError(f"{who}: valid must be bool or uint8 {[Ht, Wt]}, got {getattr(valid, 'dtype', type(valid))} "
+                         f"{tuple(getattr(valid, 'shape', ()))}")
+    passes = int(passes)
+    if not 0 <= passes <= 64:
+        raise ValueError(f"{who}: passes must be in 0..64, got {passes}")
+    dev = texture.device if device is None else device
+    tex = _f32(texture, dev)
+    val = (valid.detach().to(dev) != 0).to(torch.uint8).contiguous()
+    lib = lib or L.load()
+    tex_out = torch.full((Ht, Wt, 3), float("nan"), device=dev)
+    val_out = torch.zeros((Ht, Wt), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_mesh_texture_dilate(L.ptr(tex), L.ptr(val), Ht, Wt, passes, L.ptr(tex_out), L.ptr(val_out), _stream()))
+    return tex_out, val_out.bool()
+
+
+def op_mesh_render_uv(xy, key, face_id, faces, face_uv, uv, texture, background=(1.0, 1.0, 1.0), layout="nchw", device=None, lib=None):
+    """mvd_op_mesh_render_uv on ``device`` (default: xy's): xy [N,Nv,2], key [N,Nv], face_id [N,H,W] int32 as op_mesh_project and
+    op_mesh_raster return them; faces / face_uv [Nf,3] int32; uv [Nt,2] float; texture [Ht,Wt,3] float in [0, 1].  Returns the
+    images, float32 in [-1, 1]: [N,3,H,W] (``layout`` "nchw") or [N,H,W,3] ("nhwc"); uncovered pixels take ``background``."""
+    who = "op_mesh_render_uv"
+    _i32("xy", xy, (None, None, 2), who)
+    N, Nv = xy.shape[:2]
+    _i32("key", key, (N, Nv), who)
+    _i32("face_id", face_id, (N, None, None), who)
+    H, W = face_id.shape[1:]
+    _i32("faces", faces, (None, 3), who)
+    Nf = faces.shape[0]
+    _i32("face_uv", face_uv, (Nf, 3), who)
+    if Nv < 1 or Nf < 1:
+        raise ValueError(f"{who}: at least one vertex and one face are needed, got Nv = {Nv}, Nf = {Nf}")
+    _mesh_image_dims(who, N, H, W)
+    if 3 * N * H * W >= 2 ** 31:
+        raise ValueError(f"{who}: needs 3 N H W < 2^31, got (N, H, W) = {(N, H, W)}")
+    if not torch.is_tensor(uv) or not uv.is_floating_point() or uv.dim() != 2 or uv.shape[1] != 2 or uv.shape[0] < 1:
+        raise ValueError(f"{who}: uv must be a float tensor [Nt,2], got {tuple(getattr(uv, 'shape', ()))}")
+    if not torch.is_tensor(texture) or not texture.is_floating_point() or texture.dim() != 3 or texture.shape[2] != 3:
+        raise ValueError(f"{who}: texture must be a float tensor [Ht,Wt,3], got {tuple(getattr(texture, 'shape', ()))}")
+    Nt, (Ht, Wt) = uv.shape[0], texture.shape[:2]
+    _atlas_dims(who, Ht, Wt)
+    if layout not in ("nchw", "nhwc"):
+        raise ValueError(f"{who}: layout must be 'nchw' or 'nhwc', not {layout!r}")
+    bg = tuple(float(c) for c in background)
+    if len(bg) != 3:
+        raise ValueError(f"{who}: background must be three numbers")
+    dev = xy.device if device is None else device
+    xy, key, face_id, faces, face_uv = (t.detach().to(dev).contiguous() for t in (xy, key, face_id, faces, face_uv))
+    uvd, tex = _f32(uv, dev), _f32(texture, dev)
+    lib = lib or L.load()
+    images = torch.full((N, 3, H, W) if layout == "nchw" else (N, H, W, 3), float("nan"), device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_mesh_render_uv(L.ptr(xy), L.ptr(key), L.ptr(face_id), L.ptr(faces), L.ptr(face_uv), L.ptr(uvd), L.ptr(tex), N, Nv,
+                                          Nf, Nt, H, W, Ht, Wt, int(layout == "nhwc"), bg[0], bg[1], bg[2], L.ptr(images), _stream()))
+    return images
+
+
 # ---- the morphable-model forward (include/mvd.h: mvd_op_morph_pose / _skin / _landmarks; csrc/k_morph.hip): context-free.
 MORPH_MAX_JOINTS = 64
 
@@ -1336,6 +1505,23 @@ class Engine:
         """mvd_op_mesh_vertex_colors on this engine's device: see the module-level op_mesh_vertex_colors."""
         return op_mesh_vertex_colors(images, xy, key, faces, face_id, pix_key, verts, normals, centres, device=self.device,
                                      lib=self.lib, **kw)
+
+    def op_mesh_vertex_normals(self, verts, faces, inc_ptr, inc_face):
+        """mvd_op_mesh_vertex_normals on this engine's device: see the module-level op_mesh_vertex_normals."""
+        return op_mesh_vertex_normals(verts, faces, inc_ptr, inc_face, device=self.device, lib=self.lib)
+
+    def op_mesh_texel_bake(self, images, face_id, pix_key, K, RT, centres, z_near, verts, normals, faces, uv_xy, face_uv, tex_face, **kw):
+        """mvd_op_mesh_texel_bake on this engine's device: see the module-level op_mesh_texel_bake."""
+        return op_mesh_texel_bake(images, face_id, pix_key, K, RT, centres, z_near, verts, normals, faces, uv_xy, face_uv, tex_face,
+                                  device=self.device, lib=self.lib, **kw)
+
+    def op_mesh_texture_dilate(self, texture, valid, passes):
+        """mvd_op_mesh_texture_dilate on this engine's device: see the module-level op_mesh_texture_dilate."""
+        return op_mesh_texture_dilate(texture, valid, passes, device=self.device, lib=self.lib)
+
+    def op_mesh_render_uv(self, xy, key, face_id, faces, face_uv, uv, texture, **kw):
+        """mvd_op_mesh_render_uv on this engine's device: see the module-level op_mesh_render_uv."""
+        return op_mesh_render_uv(xy, key, face_id, faces, face_uv, uv, texture, device=self.device, lib=self.lib, **kw)
 
     # the sparse voxel CNN's kernels one at a time: the module-level functions above on this engine's device and library
     def op_sparse_conv(self, x, nbr, w, layout, form="mfma", scale=None, shift=None):

@@ -21,6 +21,11 @@ Differences, all outside the denoising path and stated here:
   * --export_mesh / --mesh_overlay (not reference flags; mesh.py): the conditioning mesh coloured from the 16 generated views as
     ``<output_dir>/<input>_<exp>_mesh.ply`` with its statistics in ``<input>_<exp>_mesh.json``, and the mesh drawn over the views
     as ``<input>_<exp>_overlay.png`` (a check of the mesh's alignment).  Both need a mesh file with faces.
+  * --export_texture [--texture_size 1024] [--uv_mesh FILE.obj] (not reference flags; mesh.py, csrc/k_mesh_uv.hip): a UV texture
+    atlas baked from the 16 generated views, as ``<input>_<exp>_textured.obj`` / ``.mtl`` / ``<input>_<exp>_texture.png`` with
+    its coverage, consistency and reprojection PSNR / SSIM per view in ``<input>_<exp>_texture.json``.  The texture
+    coordinates are --mesh's when it is an OBJ with vt lines, else --uv_mesh's (same vertex and face counts), else one chart
+    per triangle (mesh.triangle_atlas).  Works on the --frames path as --export_mesh does.
   * --flame_model MODEL.{npz,pkl} --flame_params PARAMS.npz (not reference flags; morphable.py) replace --mesh: the conditioning
     mesh is computed from FLAME parameters (any of shape, expression, global_pose, neck, jaw, eyes; a leading frame axis gives
     several frames) on the device, the step the reference leaves to MICA's FLAME module, and aligned in the same pass.  With
@@ -167,6 +172,14 @@ def build_parser():
                         "colours fused from the generated views) and <img>_<exp>_mesh.json (coverage, consistency, visible counts)")
     p.add_argument("--mesh_overlay", action="store_true",
                    help="not a reference flag: write <output_dir>/<img>_<exp>_overlay.png, the mesh drawn over the generated views")
+    p.add_argument("--export_texture", action="store_true",
+                   help="not a reference flag: write <output_dir>/<img>_<exp>_textured.obj / .mtl, <img>_<exp>_texture.png (a UV "
+                        "texture atlas baked from the generated views) and <img>_<exp>_texture.json (coverage, consistency, "
+                        "reprojection PSNR / SSIM per view)")
+    p.add_argument("--texture_size", type=int, default=1024, help="not a reference flag: texels on a side of --export_texture's atlas")
+    p.add_argument("--uv_mesh", type=str, default=None,
+                   help="not a reference flag: an OBJ with vt lines and the mesh's vertex and face counts, whose texture coordinates "
+                        "--export_texture uses when --mesh has none (default: one chart per triangle, mesh.triangle_atlas)")
     p.add_argument("--flame_model", type=str, default=None,
                    help="not a reference flag: a FLAME model file (.npz or .pkl with the FLAME pickle's key names); with "
                         "--flame_params the mesh is computed from parameters instead of read from --mesh")
@@ -311,6 +324,51 @@ def mesh_outputs(x_sample, cams, verts, faces, file_verts, output_dir, stem, exp
     return written
 
 
+def texture_coordinates(mesh_path, uv_mesh, n_verts, faces, size):
+    """The texture coordinates of --export_texture, (uv [Nt,2], face_uv [Nf,3]): of ``mesh_path`` when it is an OBJ with vt lines,
+    else of ``uv_mesh`` (an OBJ with vt and the same vertex and face counts, or ValueError), else mesh.triangle_atlas."""
+    from . import mesh as MS
+    if mesh_path and str(mesh_path).lower().endswith(".obj"):
+        with open(mesh_path) as f:
+            if any(line.startswith("vt ") for line in f):
+                _, f2, uv, face_uv = MS.read_mesh_uv(mesh_path)
+                if len(f2) != len(faces):
+                    raise ValueError(f"{mesh_path}: {len(f2)} faces with texture coordinates, the mesh has {len(faces)}")
+                return uv, face_uv
+    if uv_mesh:
+        v2, f2, uv, face_uv = MS.read_mesh_uv(uv_mesh)
+        if len(v2) != n_verts or len(f2) != len(faces):
+            raise ValueError(f"{uv_mesh}: {len(v2)} vertices and {len(f2)} faces, the mesh has {n_verts} and {len(faces)}")
+        return uv, face_uv
+    return MS.triangle_atlas(len(faces), size, size)
+
+
+def texture_outputs(x_sample, cams, verts, faces, file_verts, uv, face_uv, output_dir, stem, export_texture=False, size=1024, **kw):
+    """The post-sampling work of --export_texture: x_sample [N,3,H,W] (or [B,N,3,H,W]: sample 0) in [-1, 1], cams, verts, faces,
+    file_verts as mesh_outputs takes them, uv [Nt,2] / face_uv [Nf,3] (texture_coordinates).  Writes <output_dir>/
+    <stem>_textured.obj and .mtl, <stem>_texture.png and <stem>_texture.json (coverage, consistency, the reprojection PSNR /
+    SSIM of the atlas rendered back into every view); nothing without the flag; kw goes to mesh.bake_texture.  Returns the
+    paths written."""
+    if not export_texture:
+        return {}
+    from . import mesh as MS
+    from . import metrics as M
+    x = x_sample[0] if x_sample.dim() == 5 else x_sample
+    K, RT = cams
+    bake = MS.bake_texture(x, verts, faces, uv, face_uv, K, RT, size=size, **kw)
+    rep = MS.reprojection_metrics(x, bake, verts, faces, uv, face_uv, K, RT)
+    out = Path(output_dir)
+    written = MS.write_obj(str(out / f"{stem}_textured.obj"), np.asarray(file_verts), faces, uv, face_uv, bake["texture"],
+                           texture_name=f"{stem}_texture.png")
+    written["json"] = str(out / f"{stem}_texture.json")
+    with open(written["json"], "w") as f:
+        json.dump(dict(M.summarise(rep, keys=("psnr", "ssim")), vertices=int(len(file_verts)), faces=int(len(faces)),
+                       texture_coordinates=int(len(uv)), size=[int(bake["texture"].shape[0]), int(bake["texture"].shape[1])],
+                       coverage=bake["coverage"], consistency=None if np.isnan(bake["consistency"]) else bake["consistency"],
+                       valid_after_dilation=float(bake["valid"].double().mean())), f, indent=2)
+    return written
+
+
 def load_model(cfg, ckpt, device="cuda:0", lora=None, lora_scale=1.0, **overrides):
     """batch.load_model: the reference's ``load_model`` plus ``lora`` / ``lora_scale`` (an adapter file merged at load time)."""
     return B.load_model(cfg, ckpt, device=device, lora=lora, lora_scale=lora_scale, **overrides)
@@ -341,14 +399,18 @@ def run(flags, model=None):
     else:
         cams = B.virtual_cameras(NUM_VIEWS, 256)
     want_mesh = getattr(flags, "export_mesh", False) or getattr(flags, "mesh_overlay", False)
+    want_tex = getattr(flags, "export_texture", False)
     if getattr(flags, "flame_model", None):
         return run_flame(flags, model, sampler, cams, input_img, img_name, exp_name, want_mesh)
     faces = None
-    if want_mesh:
+    if want_mesh or want_tex:
         from .mesh import read_mesh
         file_verts, faces = read_mesh(flags.mesh)
         if not len(faces):
-            raise ValueError(f"{flags.mesh}: --export_mesh / --mesh_overlay need a mesh with faces")
+            raise ValueError(f"{flags.mesh}: --export_mesh / --mesh_overlay / --export_texture need a mesh with faces")
+        if want_tex:
+            uv, face_uv = texture_coordinates(flags.mesh, getattr(flags, "uv_mesh", None), len(file_verts), faces,
+                                              getattr(flags, "texture_size", 1024))
     else:
         file_verts = read_mesh_vertices(flags.mesh)
     verts = B.align_flame_vertices(torch.from_numpy(file_verts).float())
@@ -373,6 +435,9 @@ def run(flags, model=None):
     if want_mesh:
         mesh_outputs(x_sample, cams, verts, faces, file_verts, flags.output_dir, f"{img_name}_{exp_name}",
                      export_mesh=getattr(flags, "export_mesh", False), mesh_overlay=getattr(flags, "mesh_overlay", False))
+    if want_tex:
+        texture_outputs(x_sample, cams, verts, faces, file_verts, uv, face_uv, flags.output_dir, f"{img_name}_{exp_name}",
+                        export_texture=True, size=getattr(flags, "texture_size", 1024))
     if neus2_root:
         # generate_face.py:255-262 slices idx*256 of the strip for idx in range(16): view 0 of the export is the INPUT view and
         # the last generated view is dropped -- reproduced as is
@@ -391,8 +456,13 @@ def run_flame(flags, model, sampler, cams, input_img, img_name, exp_name, want_m
     from . import morphable as MM
     verts, stored, faces = flame_frames(flags, model.device, stem=str(Path(flags.output_dir) / f"{img_name}_{exp_name}"))
     F = verts.shape[0]
-    if want_mesh and faces is None:
-        raise ValueError(f"{flags.flame_model}: --export_mesh / --mesh_overlay need a model file with faces ('f')")
+    want_tex = getattr(flags, "export_texture", False)
+    if (want_mesh or want_tex) and faces is None:
+        raise ValueError(f"{flags.flame_model}: --export_mesh / --mesh_overlay / --export_texture need a model file with faces ('f')")
+    if want_tex:
+        uv, face_uv = texture_coordinates(None, getattr(flags, "uv_mesh", None), verts.shape[1], faces, getattr(flags, "texture_size", 1024))
+        from .mesh import face_incidence
+        incidence = face_incidence(faces, verts.shape[1])  # one topology for every frame: the table is built once
     if flags.prepare_neus2_data and F > 1:
         raise ValueError("--prepare_neus2_data exports one mesh's views: run it with a single frame")
     strip, output_fn = None, None
@@ -415,6 +485,9 @@ def run_flame(flags, model, sampler, cams, input_img, img_name, exp_name, want_m
             if want_mesh:
                 mesh_outputs(x_sample[i], cams, chunk[i], faces, stored[f], flags.output_dir, stem,
                              export_mesh=getattr(flags, "export_mesh", False), mesh_overlay=getattr(flags, "mesh_overlay", False))
+            if want_tex:
+                texture_outputs(x_sample[i], cams, chunk[i], faces, stored[f], uv, face_uv, flags.output_dir, stem, export_texture=True,
+                                size=getattr(flags, "texture_size", 1024), incidence=incidence)
     if flags.prepare_neus2_data:
         neus2_root = os.path.join(flags.output_dir, "neus2_data", f"{img_name}_{exp_name}")
         os.makedirs(os.path.join(neus2_root, "images"), exist_ok=True)

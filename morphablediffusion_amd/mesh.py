@@ -6,9 +6,16 @@ of the view colours that see it.  Not a reference feature (its only 3-D output i
   rasterize_mesh    face_id / pix_key / depth / mask of every view       texture_mesh     per-vertex colours and their statistics
   write_ply         binary little-endian, uchar colours                  overlay_views    the mesh drawn over the views (plain torch)
 
+UV texture atlases (mvd_op_mesh_vertex_normals / _texel_bake / _texture_dilate / _render_uv, csrc/k_mesh_uv.hip):
+
+  read_mesh_uv      an OBJ with vt: verts, faces, uv, face_uv            triangle_atlas   per-triangle charts for a mesh without UVs
+  uv_to_atlas       uv -> chart coordinates in 1/16 texel (float64)      vertex_normals_device   the normals of a batch of frames
+  bake_texture      the views fused per texel, then dilated              render_textured  the textured mesh in any cameras
+  reprojection_metrics   the atlas rendered back, scored by image_metrics   write_obj     OBJ + MTL + PNG
+
 What is exact: everything after the projection (coverage, depth order, visibility, n_seen) is integer arithmetic.  What is not
-computed: UV texture maps, perspective-correct attribute rendering, the input photo as a 17th view (its camera is not in the
-batch).  The FLAME mesh ends at the head, so colour on hair and shoulders is not recovered."""
+computed: UV unwrapping beyond triangle_atlas, mip-maps, seam-aware blending across charts, the input photo as a 17th view (its
+camera is not in the batch).  The FLAME mesh ends at the head, so colour on hair and shoulders is not recovered."""
 import struct
 
 import numpy as np
@@ -291,3 +298,264 @@ def overlay_views(views, mask, face_id, alpha=0.5, tint=(0.1, 0.8, 0.3)):
     x = torch.where(edge[..., None], t.expand_as(x), x)
     strip = torch.cat(list(x), 1)  # [H, N W, 3]
     return (strip * 255.0 + 0.5).clamp(0, 255).to(torch.uint8)
+
+
+# ---- UV texture atlases (include/mvd.h: the conventions of the mvd_op_mesh_vertex_normals ... _render_uv block)
+def read_mesh_uv(path):
+    """(verts float64 [Nv,3], faces int32 [Nf,3], uv float64 [Nt,2], face_uv int32 [Nf,3]) of a Wavefront OBJ with texture
+    coordinates: ``f`` lines in the v/vt and v/vt/vn forms, negative indices in both index sets, polygons fan-triangulated in both.
+    ValueError if a face corner has no ``vt`` or an index is out of range."""
+    path = str(path)
+    if not path.lower().endswith(".obj"):
+        raise ValueError(f"{path}: expected an .obj mesh with vt lines")
+    vs, vts, tris, uvtris = [], [], [], []
+    with open(path) as f:
+        for line in f:
+            if line.startswith("v "):
+                p = line.split()
+                vs.append([float(p[1]), float(p[2]), float(p[3])])
+            elif line.startswith("vt "):
+                p = line.split()
+                vts.append([float(p[1]), float(p[2])])
+            elif line.startswith("f "):
+                poly, uvpoly = [], []
+                for tok in line.split()[1:]:
+                    part = tok.split("/")
+                    if len(part) < 2 or not part[1]:
+                        raise ValueError(f"{path}: the face corner {tok!r} has no vt index")
+                    i, t = int(part[0]), int(part[1])
+                    poly.append(i - 1 if i > 0 else len(vs) + i)
+                    uvpoly.append(t - 1 if t > 0 else len(vts) + t)
+                if len(poly) < 3:
+                    raise ValueError(f"{path}: a face with fewer than 3 vertices")
+                _fan(poly, tris)
+                _fan(uvpoly, uvtris)
+    if not vs or not tris:
+        raise ValueError(f"{path}: no vertices or no faces")
+    verts, uv = np.asarray(vs, dtype=np.float64), np.asarray(vts, dtype=np.float64).reshape(-1, 2)
+    faces, face_uv = np.asarray(tris, dtype=np.int64).reshape(-1, 3), np.asarray(uvtris, dtype=np.int64).reshape(-1, 3)
+    if faces.min() < 0 or faces.max() >= len(verts):
+        raise ValueError(f"{path}: a face index is outside the {len(verts)} vertices")
+    if face_uv.min() < 0 or face_uv.max() >= len(uv):
+        raise ValueError(f"{path}: a vt index is outside the {len(uv)} texture coordinates")
+    return verts, faces.astype(np.int32), uv, face_uv.astype(np.int32)
+
+
+def _atlas_size(size):
+    Ht, Wt = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+    if not (1 <= Ht <= 4096 and 1 <= Wt <= 4096):
+        raise ValueError(f"the atlas must be 1..4096 texels on a side, got {(Ht, Wt)}")
+    return Ht, Wt
+
+
+def uv_to_atlas(uv, Ht, Wt):
+    """Chart coordinates int32 [Nt,2] in 1/16 texel of uv [Nt,2] (OBJ convention: u right, v up, (0, 0) bottom-left) in an atlas of
+    Ht x Wt texels with row 0 at the top: xs = rint(16 (u Wt - 0.5)), ys = rint(16 ((1 - v) Ht - 0.5)), float64 on the host.
+    ValueError for a non-finite UV or one outside [0, 1]."""
+    a = (uv.detach().cpu().numpy() if torch.is_tensor(uv) else np.asarray(uv)).astype(np.float64)
+    if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] < 1:
+        raise ValueError(f"uv must be [Nt,2], got {a.shape}")
+    if not np.isfinite(a).all() or a.min() < 0.0 or a.max() > 1.0:
+        raise ValueError("uv must be finite and inside [0, 1]")
+    Ht, Wt = _atlas_size((Ht, Wt))
+    xs = np.rint(16.0 * (a[:, 0] * Wt - 0.5))
+    ys = np.rint(16.0 * ((1.0 - a[:, 1]) * Ht - 0.5))
+    return np.stack([xs, ys], -1).astype(np.int32)
+
+
+def triangle_atlas(n_faces, Ht, Wt, gutter=1):
+    """(uv float64 [3 n_faces,2], face_uv int32 [n_faces,3]) of a deterministic atlas for a mesh without UVs: square cells of s
+    texels in row-major order, two right triangles per cell (faces 2 c and 2 c + 1), every face with corners of its own.  In a
+    cell's texel indices 0..s-1, with m = s - gutter and a = s - 2 gutter - 2, face 2 c owns the texels with i + j <= a and face
+    2 c + 1 those with i, j <= m - 1 and i + j >= 2 (m - 1) - a (the chart corners sit a quarter texel outside those texel centres,
+    on the 1/16 grid), so any two charts are more than ``gutter`` texels apart (Chebyshev).  s is the largest size at which
+    the cells fit; ValueError when that leaves s < 2 gutter + 2, where a face would own no texel centre."""
+    n_faces, gutter = int(n_faces), int(gutter)
+    Ht, Wt = _atlas_size((Ht, Wt))
+    if n_faces < 1 or gutter < 0:
+        raise ValueError(f"triangle_atlas: needs n_faces >= 1 and gutter >= 0, got {n_faces}, {gutter}")
+    cells = (n_faces + 1) // 2
+    s = min(Ht, Wt)
+    while s >= 1 and (Ht // s) * (Wt // s) < cells:
+        s -= 1
+    if s < 2 * gutter + 2:
+        raise ValueError(f"triangle_atlas: {n_faces} faces in {Ht} x {Wt} texels leave cells of {s} texels; gutter {gutter} needs "
+                         f"{2 * gutter + 2}")
+    cols, m, a = Wt // s, s - gutter, s - 2 * gutter - 2
+    f = np.arange(n_faces)
+    x0, y0 = ((f // 2) % cols * s).astype(np.float64), ((f // 2) // cols * s).astype(np.float64)
+    lo, hi = -0.25, a + 0.5
+    first = np.array([[lo, lo], [hi, lo], [lo, hi]])                      # corners 0, 1, 2 of face 2 c: (x, y) in texel indices
+    second = (m - 1.0) - first                                            # face 2 c + 1: the same triangle turned half way round
+    local = np.where((f % 2 == 0)[:, None, None], first[None], second[None])
+    x, y = local[..., 0] + x0[:, None], local[..., 1] + y0[:, None]
+    uv = np.stack([(x + 0.5) / Wt, 1.0 - (y + 0.5) / Ht], -1).reshape(-1, 2)
+    return uv, np.arange(3 * n_faces, dtype=np.int32).reshape(-1, 3)
+
+
+def face_incidence(faces, Nv):
+    """The vertex -> face incidence of a topology in CSR form: (inc_ptr int32 [Nv+1], inc_face int32 [3 Nf]); the faces of vertex v
+    are inc_face[inc_ptr[v]:inc_ptr[v+1]], ascending (a face that names a vertex twice is listed twice, as the host
+    vertex_normals adds it twice)."""
+    f = (faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)).astype(np.int64).reshape(-1, 3)
+    if len(f) < 1 or f.min() < 0 or f.max() >= Nv:
+        raise ValueError(f"faces must be [Nf,3] with Nf >= 1 and indices inside [0, {Nv})")
+    flat = f.reshape(-1)
+    order = np.argsort(flat, kind="stable")
+    ptr = np.zeros(Nv + 1, dtype=np.int64)
+    np.cumsum(np.bincount(flat, minlength=Nv), out=ptr[1:])
+    return ptr.astype(np.int32), (order // 3).astype(np.int32)
+
+
+def vertex_normals_device(verts, faces, incidence=None):
+    """Unit vertex normals on the device, float32, of verts [Nv,3] or a batch of frames [F,Nv,3] over one topology
+    (mvd_op_mesh_vertex_normals): area-weighted as ``vertex_normals``, the faces of a vertex summed in ascending order without
+    atomics, so frame f of a batch equals the frame computed alone.  ``incidence``: ``face_incidence(faces, Nv)`` kept by a caller
+    that bakes many frames of one topology; by default the table is built here, on the host, at every call."""
+    v = _as_tensor(verts, torch.float32)
+    if v.dim() not in (2, 3) or v.shape[-1] != 3 or v.shape[-2] < 1:
+        raise ValueError(f"verts must be [Nv,3] or [F,Nv,3], got {tuple(v.shape)}")
+    single = v.dim() == 2
+    vb = v[None] if single else v
+    ptr, inc = face_incidence(faces, vb.shape[1]) if incidence is None else incidence
+    dev = _device_of(verts)
+    f = torch.from_numpy((faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)).astype(np.int32).reshape(-1, 3))
+    normals, bad = E.op_mesh_vertex_normals(vb, f, _as_tensor(ptr, torch.int32), _as_tensor(inc, torch.int32), device=dev)
+    if int(bad.item()):
+        raise ValueError(f"{int(bad.item())} entries of the incidence table were out of range")
+    return normals[0] if single else normals
+
+
+def _uv_args(uv, face_uv, Nf):
+    a = (uv.detach().cpu().numpy() if torch.is_tensor(uv) else np.asarray(uv)).astype(np.float64)
+    t = (face_uv.detach().cpu().numpy() if torch.is_tensor(face_uv) else np.asarray(face_uv)).astype(np.int64)
+    if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] < 1:
+        raise ValueError(f"uv must be [Nt,2], got {a.shape}")
+    if t.shape != (Nf, 3):
+        raise ValueError(f"face_uv must be [{Nf},3], parallel to faces, got {t.shape}")
+    if t.min() < 0 or t.max() >= len(a):
+        raise ValueError(f"a face_uv index is outside the {len(a)} texture coordinates")
+    return a, torch.from_numpy(t.astype(np.int32))
+
+
+def _tex_face(uv_xy, face_uv, Ht, Wt, dev):
+    tex_face, _, _ = E.op_mesh_raster(uv_xy[None], torch.ones((1, uv_xy.shape[0]), dtype=torch.int32), face_uv, Ht, Wt, device=dev)
+    return tex_face[0]
+
+
+def bake_texture(views, verts, faces, uv, face_uv, K, RT, size=1024, power=2.0, bias=4096, two_sided=False, fill=(0.5, 0.5, 0.5), pad=4,
+                 z_near=None, incidence=None):
+    """A UV texture atlas out of N views [N,3,H,W] or [N,H,W,3] (float in [-1, 1] or uint8) of the mesh (verts [Nv,3], faces
+    [Nf,3]) with texture coordinates uv [Nt,2] / face_uv [Nf,3] under cameras K, RT; ``size``: texels on a side, or (Ht, Wt).
+    Every texel centre inside a chart is lifted to its surface point, tested for visibility in every view with the integers of
+    ``texture_mesh`` (the winning face must BE the texel's face, or the point lie within ``bias`` keys of the winner) and takes
+    the mean of the view colours weighted by max(0, cos)^power.  Returns {"texture" [Ht,Wt,3] in [0, 1], row 0 at the top, after
+    ``pad`` rounds of dilation into gutters and unseen texels (what stays invalid keeps ``fill``), "valid" [Ht,Wt] bool after
+    the dilation, "tex_face" [Ht,Wt] int32 (-1: no chart), "n_seen", "weight_sum", "spread" [Ht,Wt] as texture_mesh defines them
+    per vertex, "face_id", "mask" [N,H,W] of the views} (device tensors) and the floats "coverage" (share of the chart texels
+    with a positive weight sum), "consistency" (mean spread where n_seen >= 2) and "z_near".  ``incidence``: ``face_incidence(faces, Nv)`` of the topology, for a
+    caller that bakes many frames of it (default: built at every call, an argsort over 3 Nf entries on the host)."""
+    if not torch.is_tensor(views):
+        views = torch.as_tensor(np.asarray(views))
+    if views.dim() != 4 or (views.shape[1] == 3) == (views.shape[3] == 3):
+        raise ValueError(f"views must be [N,3,H,W] or [N,H,W,3], got {tuple(views.shape)}")
+    N, H, W = (views.shape[0], views.shape[2], views.shape[3]) if views.shape[1] == 3 else tuple(views.shape[:3])
+    v, f = _mesh_args(verts, faces)
+    uv, face_uv = _uv_args(uv, face_uv, f.shape[0])
+    Ht, Wt = _atlas_size(size)
+    K3, RT = _cameras(K, RT)
+    if K3.shape[0] != N:
+        raise ValueError(f"{N} views but {K3.shape[0]} cameras")
+    if not 0 <= int(pad) <= 64:
+        raise ValueError(f"pad must be in 0..64, got {pad}")
+    uv_xy = torch.from_numpy(uv_to_atlas(uv, Ht, Wt))  # refuses bad UVs before anything is launched
+    z_near = default_z_near(v, RT) if z_near is None else float(z_near)
+    dev = _device_of(views, verts, K)
+    _, _, face_id, pix_key = _raster(v, f, K3, RT, H, W, z_near, dev)
+    tex_face = _tex_face(uv_xy, face_uv, Ht, Wt, dev)
+    normals = vertex_normals_device(v.to(dev), f, incidence=incidence)
+    centres = -torch.einsum("nji,nj->ni", RT[:, :, :3], RT[:, :, 3])  # -R^T t
+    out = E.op_mesh_texel_bake(views, face_id, pix_key, K3, RT, centres, z_near, v, normals, f, uv_xy, face_uv, tex_face, power=power,
+                               bias=bias, two_sided=two_sided, fill=fill, taps=False, device=dev)
+    seen = out["weight_sum"] > 0
+    texture, valid = E.op_mesh_texture_dilate(out["texture"], seen, int(pad), device=dev)
+    chart = tex_face >= 0
+    multi = (out["n_seen"] >= 2) & ~torch.isnan(out["spread"])
+    return {"texture": texture, "valid": valid, "tex_face": tex_face, "n_seen": out["n_seen"], "weight_sum": out["weight_sum"],
+            "spread": out["spread"], "face_id": face_id, "mask": face_id >= 0, "z_near": z_near,
+            "coverage": float((seen & chart).sum().double() / chart.sum().clamp(min=1).double()),
+            "consistency": float(out["spread"][multi].double().mean()) if bool(multi.any()) else float("nan")}
+
+
+def render_textured(texture, verts, faces, uv, face_uv, K, RT, H, W, background=(1.0, 1.0, 1.0), z_near=None):
+    """The textured mesh in the N cameras K, RT at H x W with perspective-correct texture coordinates: {"images" [N,3,H,W] float32
+    in [-1, 1] (the samplers' convention: feed it to ``image_metrics`` or ``texture_mesh``), "mask" [N,H,W] bool (covered),
+    "face_id" [N,H,W] int32}.  texture [Ht,Wt,3] in [0, 1], row 0 at the top; bilinear, clamped to the edge; uncovered pixels
+    take ``background`` (in [0, 1])."""
+    v, f = _mesh_args(verts, faces)
+    uv, face_uv = _uv_args(uv, face_uv, f.shape[0])
+    if not torch.is_tensor(texture):
+        texture = torch.as_tensor(np.asarray(texture))
+    if texture.dim() != 3 or texture.shape[2] != 3 or not texture.is_floating_point():
+        raise ValueError(f"texture must be a float tensor [Ht,Wt,3], got {texture.dtype} {tuple(texture.shape)}")
+    _atlas_size(texture.shape[:2])
+    if not np.isfinite(uv).all():
+        raise ValueError("uv must be finite")
+    K3, RT = _cameras(K, RT)
+    z_near = default_z_near(v, RT) if z_near is None else float(z_near)
+    dev = _device_of(texture, verts, K)
+    xy, key, face_id, _ = _raster(v, f, K3, RT, int(H), int(W), z_near, dev)
+    images = E.op_mesh_render_uv(xy, key, face_id, f, face_uv, torch.from_numpy(uv), texture, background=background, device=dev)
+    return {"images": images, "mask": face_id >= 0, "face_id": face_id}
+
+
+def reprojection_metrics(views, bake, verts, faces, uv, face_uv, K, RT, z_near=None):
+    """How well a baked atlas explains the views it came from, no ground truth needed: ``bake["texture"]`` rendered back into
+    the baking cameras and scored against ``views`` by ``metrics.image_metrics`` with the uncovered pixels as background
+    (``mask=~mask``).  Returns image_metrics' dict plus "images" and "mask" of the render."""
+    from .metrics import image_metrics
+    if not torch.is_tensor(views):
+        views = torch.as_tensor(np.asarray(views))
+    if views.dim() != 4 or (views.shape[1] == 3) == (views.shape[3] == 3):
+        raise ValueError(f"views must be [N,3,H,W] or [N,H,W,3], got {tuple(views.shape)}")
+    H, W = (views.shape[2], views.shape[3]) if views.shape[1] == 3 else tuple(views.shape[1:3])
+    r = render_textured(bake["texture"], verts, faces, uv, face_uv, K, RT, H, W, z_near=bake.get("z_near") if z_near is None else z_near)
+    if r["images"].shape[0] != views.shape[0]:
+        raise ValueError(f"{views.shape[0]} views but {r['images'].shape[0]} cameras")
+    out = dict(image_metrics(r["images"], views.to(r["images"].device), mask=~r["mask"]))
+    out["images"], out["mask"] = r["images"], r["mask"]
+    return out
+
+
+def write_obj(path, verts, faces, uv, face_uv, texture, texture_name=None):
+    """A textured Wavefront OBJ: ``path`` (.obj) with ``v``, ``vt`` and ``f v/vt`` lines (17 significant digits: read_mesh_uv
+    reads the same float64 back), beside it the .mtl of the same stem and the texture as a PNG, rint(255 c) of texture [Ht,Wt,3]
+    in [0, 1] written as it is (row 0 at the top) -- ``texture_name``: its file name in the same folder, default <stem>.png.
+    Returns the three paths."""
+    import os
+    from PIL import Image
+    path = str(path)
+    if not path.lower().endswith(".obj"):
+        raise ValueError(f"{path}: expected an .obj path")
+    v = (verts.detach().cpu().numpy() if torch.is_tensor(verts) else np.asarray(verts)).astype(np.float64)
+    f = (faces.detach().cpu().numpy() if torch.is_tensor(faces) else np.asarray(faces)).astype(np.int64).reshape(-1, 3)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError(f"verts must be [Nv,3], got {v.shape}")
+    a, t = _uv_args(uv, face_uv, len(f))
+    t = t.numpy()
+    tex = (texture.detach().cpu().numpy() if torch.is_tensor(texture) else np.asarray(texture)).astype(np.float64)
+    if tex.ndim != 3 or tex.shape[2] != 3:
+        raise ValueError(f"texture must be [Ht,Wt,3], got {tex.shape}")
+    stem = path[:-4]
+    folder, base = os.path.split(stem)
+    png = texture_name or base + ".png"
+    Image.fromarray(np.rint(np.clip(np.nan_to_num(tex), 0.0, 1.0) * 255.0).astype(np.uint8)).save(os.path.join(folder, png))
+    with open(stem + ".mtl", "w") as fh:
+        fh.write(f"newmtl baked\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {png}\n")
+    with open(path, "w") as fh:
+        fh.write(f"mtllib {base}.mtl\n")
+        fh.writelines(f"v {p[0]!r} {p[1]!r} {p[2]!r}\n" for p in v.tolist())
+        fh.writelines(f"vt {p[0]!r} {p[1]!r}\n" for p in a.tolist())
+        fh.write("usemtl baked\n")
+        fh.writelines(f"f {i[0] + 1}/{j[0] + 1} {i[1] + 1}/{j[1] + 1} {i[2] + 1}/{j[2] + 1}\n" for i, j in zip(f.tolist(), t.tolist()))
+    return {"obj": path, "mtl": stem + ".mtl", "png": os.path.join(folder, png)}

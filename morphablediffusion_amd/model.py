@@ -1018,6 +1018,28 @@ class SyncMultiviewDiffusion(nn.Module):
         return texture_mesh(x_sample[sample], batch["vertices"][sample], faces, batch["target_K"][sample][..., :3, :3],
                             batch["target_RT"][sample], **kw)
 
+    def bake_texture(self, batch, x_sample, faces, uv, face_uv, sample=0, **kw):
+        """A UV texture atlas out of generated views (not a reference method): ``mesh.bake_texture`` of ``x_sample[sample]``
+        ([B,N,3,H,W], what ``sample`` returns) on the mesh the sample was conditioned on -- ``batch["vertices"][sample]`` with the
+        triangles ``faces`` [Nf,3] and the texture coordinates ``uv`` [Nt,2] / ``face_uv`` [Nf,3] -- under the batch's target
+        cameras.  The argument checks of ``texture_mesh``.  ``kw``: size, power, bias, two_sided, fill, pad, z_near.  Returns
+        mesh.bake_texture's dict."""
+        from .mesh import bake_texture
+        for k in ("vertices", "target_K", "target_RT"):
+            if batch.get(k) is None:
+                raise ValueError(f"bake_texture needs batch[{k!r}]")
+        if x_sample.dim() != 5 or x_sample.shape[2] != 3:
+            raise ValueError(f"bake_texture: x_sample must be [B,N,3,H,W], got {tuple(x_sample.shape)}")
+        B, N, _, H, W = x_sample.shape
+        if H != self.image_size or W != self.image_size:
+            raise ValueError(f"bake_texture: the views are {H} x {W}, the cameras are in pixels of input_image_size = {self.image_size}")
+        if not 0 <= sample < B or batch["vertices"].shape[0] != B:
+            raise ValueError(f"bake_texture: sample {sample} of a batch of {B} (vertices: {batch['vertices'].shape[0]})")
+        if batch["target_K"].shape[1] != N or batch["target_RT"].shape[1] != N:
+            raise ValueError(f"bake_texture: {N} views but {batch['target_K'].shape[1]} cameras")
+        return bake_texture(x_sample[sample], batch["vertices"][sample], faces, uv, face_uv, batch["target_K"][sample][..., :3, :3],
+                            batch["target_RT"][sample], **kw)
+
     def log_image(self, x_sample, batch, step, output_dir):
         """morphable_diffusion.py:589-599: one row per sample -- the input view followed by the N generated views -- as
         <output_dir>/<step>.jpg."""

@@ -13,7 +13,7 @@ vertices go straight into ``batch.build_batch`` / ``stack_batches`` / ``model.sa
 Units: FLAME's forward is in metres, and so are the mesh files of the reference pipeline, so ``unit_scale``
 defaults to 1.0.  The inverse is here too (csrc/k_morph_bwd.hip): ``vjp`` is the vector-Jacobian product of the forward,
 ``differentiable`` the same as a torch.autograd.Function, ``fit`` / ``fit_flame`` run Adam on the device against target vertices
-and 3-D landmarks.  Not here: the pose-dependent contour landmarks, vertex normals on the device.
+and 3-D landmarks.  Not here: the pose-dependent contour landmarks (vertex normals of a batch of frames: mesh.vertex_normals_device).
 
     fit = fm.fit_flame(target_vertices=mesh_vertices, free=("expression", "jaw"), prior={"shape": mica_shape})
 """
