@@ -26,6 +26,9 @@ typedef half_t h4 __attribute__((ext_vector_type(4)));
 typedef half_t h2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+// one element of an fp32 or a 16-bit source as fp32 (kernels templated on their source type: k_bwd.hip, k_cond_bwd.hip)
+__device__ __forceinline__ float ldf(const float* p) { return *p; }
+__device__ __forceinline__ float ldf(const half_t* p) { return (float)*p; }
 
 #define MVD_MAX_TAPS 27
 

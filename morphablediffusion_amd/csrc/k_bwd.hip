@@ -17,9 +17,6 @@ inline int gridn(size_t n, int cap = 8192) {
   return (int)(g > (size_t)cap ? (size_t)cap : (g < 1 ? 1 : g));
 }
 
-__device__ __forceinline__ float ldf(const float* p) { return *p; }
-__device__ __forceinline__ float ldf(const half_t* p) { return (float)*p; }
-
 // ---------------------------------------------------------------------------------------------------------------------
 // dst[c][r] = fp16(src[r][c]) for c < C, r < Rp (zero for r >= R): the K-contiguous operand of a wgrad GEMM.
 // 64 x 64 tiles through LDS; reads are coalesced along c, writes along r.

@@ -7,15 +7,10 @@
 //   latent_gather   trilinear sample of the sparse CNN output at the 32^3 lattice (:232-257)
 //   frustum_gather  trilinear sample of the fused volume along each target view's frustum (:302-315)
 //   unproject_views the dense unprojection itself (use_spatial_volume=True only): the SpatialTime3DNet's input operand
-#include "common.h"
+// The coordinate maps (vertex -> cell, voxel -> map position, frustum point -> lattice, lattice -> sparse grid) are cond.h's.
+#include "cond.h"
 
 namespace {
-
-// torch.linspace(a, b, n)[i] in fp32 (symmetric evaluation, as ATen does)
-__device__ __forceinline__ float linspace_at(float a, float b, int n, int i) {
-  const float step = (b - a) / (float)(n - 1);
-  return i < n / 2 ? a + step * (float)i : b - step * (float)(n - 1 - i);
-}
 
 __global__ __launch_bounds__(256) void vertex_gather_kernel(const float* __restrict__ feats, const ViewCam* __restrict__ cams,
                                                             const int* __restrict__ view_idx, int n_views, const float* __restrict__ verts, int Nv, int V,
@@ -24,16 +19,9 @@ __global__ __launch_bounds__(256) void vertex_gather_kernel(const float* __restr
   if (idx >= n_views * Nv) return;
   const int view = idx / Nv, vi = idx - view * Nv;
   const ViewCam cam = cams[view_idx[view]];
-  float pos[3], fr[3];
+  float fr[3];
   int lo[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const float g = verts[vi * 3 + a] / vol_len;
-    pos[a] = (g + 1.0f) * 0.5f * (float)(V - 1);
-    const float f = floorf(pos[a]);
-    lo[a] = (int)f;
-    fr[a] = pos[a] - f;
-  }
+  vertex_cell(verts, vi, V, vol_len, lo, fr);
   float acc[16];
 #pragma unroll
   for (int c = 0; c < 16; ++c) acc[c] = 0.f;
@@ -42,22 +30,9 @@ __global__ __launch_bounds__(256) void vertex_gather_kernel(const float* __restr
     const int bx = corner & 1, by = (corner >> 1) & 1, bz = corner >> 2;
     const int ix = lo[0] + bx, iy = lo[1] + by, iz = lo[2] + bz;
     if (ix < 0 || ix > V - 1 || iy < 0 || iy > V - 1 || iz < 0 || iz > V - 1) continue;
-    const float w3 = (bx ? fr[0] : 1.f - fr[0]) * (by ? fr[1] : 1.f - fr[1]) * (bz ? fr[2] : 1.f - fr[2]);
-    const float X = linspace_at(-vol_len, vol_len, V, ix), Y = linspace_at(-vol_len, vol_len, V, iy),
-                Z = linspace_at(-vol_len, vol_len, V, iz);
-    const float u = cam.P[0] * X + cam.P[1] * Y + cam.P[2] * Z + cam.P[3];
-    const float v = cam.P[4] * X + cam.P[5] * Y + cam.P[6] * Z + cam.P[7];
+    const float w3 = trilinear_weight(bx, by, bz, fr[0], fr[1], fr[2]);
     float px, py;
-    if (persp) {
-      float w = cam.P[8] * X + cam.P[9] * Y + cam.P[10] * Z + cam.P[11];
-      w = w < 1e-4f ? 1e-4f : w;
-      const float hs = (float)(S - 1) * 0.5f;
-      px = ((u / w) / hs - 1.0f + 1.0f) * 0.5f * (float)(S - 1);
-      py = ((v / w) / hs - 1.0f + 1.0f) * 0.5f * (float)(S - 1);
-    } else {
-      px = (u + 1.0f) * 0.5f * (float)(S - 1);
-      py = (v + 1.0f) * 0.5f * (float)(S - 1);
-    }
+    lattice_to_map(cam.P, ix, iy, iz, V, vol_len, S, persp, px, py);
     const float fx0 = floorf(px), fy0 = floorf(py);
     const int x0 = (int)fx0, y0 = (int)fy0;
     const float tx = px - fx0, ty = py - fy0;
@@ -65,7 +40,7 @@ __global__ __launch_bounds__(256) void vertex_gather_kernel(const float* __restr
     for (int tap = 0; tap < 4; ++tap) {
       const int xx = x0 + (tap & 1), yy = y0 + (tap >> 1);
       if (xx < 0 || xx > S - 1 || yy < 0 || yy > S - 1) continue;
-      const float w2 = ((tap & 1) ? tx : 1.f - tx) * ((tap >> 1) ? ty : 1.f - ty) * w3;
+      const float w2 = bilinear_weight(tap, tx, ty) * w3;
       const float4* f4 = (const float4*)(fv + ((long)yy * S + xx) * 16);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -409,13 +384,8 @@ __global__ void latent_gather_kernel(const float* __restrict__ feats, const int*
     const int c = (int)(idx % C);
     const int pt = (int)(idx / C);
     const int ix = pt % V, iy = (pt / V) % V, iz = pt / (V * V);
-    const float X = linspace_at(-vol_len, vol_len, V, ix), Y = linspace_at(-vol_len, vol_len, V, iy),
-                Z = linspace_at(-vol_len, vol_len, V, iz);
-    const float gx = (X - minx) / voxel / shx * 2.f - 1.f;
-    const float gy = (Y - miny) / voxel / shy * 2.f - 1.f;
-    const float gz = (Z - minz) / voxel / shz * 2.f - 1.f;
-    const float px = (gx + 1.f) * 0.5f * (float)(gw - 1), py = (gy + 1.f) * 0.5f * (float)(gh - 1),
-                pz = (gz + 1.f) * 0.5f * (float)(gd - 1);
+    const float px = latent_axis_pos(minx, shx, gw, voxel, V, vol_len, ix), py = latent_axis_pos(miny, shy, gh, voxel, V, vol_len, iy),
+                pz = latent_axis_pos(minz, shz, gd, voxel, V, vol_len, iz);
     const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
     const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
     const float tx = px - fx, ty = py - fy, tz = pz - fz;
@@ -427,7 +397,7 @@ __global__ void latent_gather_kernel(const float* __restrict__ feats, const int*
       if (xx < 0 || xx > gw - 1 || yy < 0 || yy > gh - 1 || zz < 0 || zz > gd - 1) continue;
       const int row = grid[((long)zz * gh + yy) * gw + xx];
       if (row < 0) continue;
-      const float wgt = (bx ? tx : 1.f - tx) * (by ? ty : 1.f - ty) * (bz ? tz : 1.f - tz);
+      const float wgt = trilinear_weight(bx, by, bz, tx, ty, tz);
       acc += wgt * feats[(long)row * C + c];
     }
     out[idx] = acc;
@@ -458,24 +428,8 @@ __global__ __launch_bounds__(256) void frustum_gather_kernel(const float* __rest
   if (pt >= npts) return;
   const int x = (int)(pt % S), y = (int)((pt / S) % S), d = (int)((pt / ((long)S * S)) % D), tv = (int)(pt / ((long)S * S * D));
   const ViewCam cam = cams[view_idx[tv]];
-  const float depth = linspace_at(0.f, 1.f, D, d) * (cam.far_ - cam.near_) + cam.near_;
-  float wx, wy, wz;
-  if (persp) {
-    const float a = (float)x * depth, b = (float)y * depth, c = depth;
-    wx = cam.Pinv[0] * a + cam.Pinv[1] * b + cam.Pinv[2] * c + cam.Pinv[3];
-    wy = cam.Pinv[4] * a + cam.Pinv[5] * b + cam.Pinv[6] * c + cam.Pinv[7];
-    wz = cam.Pinv[8] * a + cam.Pinv[9] * b + cam.Pinv[10] * c + cam.Pinv[11];
-  } else {
-    const float gx = 2.f * (float)x / (float)(S - 1) - 1.f, gy = 2.f * (float)y / (float)(S - 1) - 1.f;
-    const float a = cam.Kinv[0] * gx + cam.Kinv[1] * gy + cam.Kinv[2];
-    const float b = cam.Kinv[3] * gx + cam.Kinv[4] * gy + cam.Kinv[5];
-    const float c = depth;
-    wx = cam.Pinv[0] * a + cam.Pinv[1] * b + cam.Pinv[2] * c + cam.Pinv[3];
-    wy = cam.Pinv[4] * a + cam.Pinv[5] * b + cam.Pinv[6] * c + cam.Pinv[7];
-    wz = cam.Pinv[8] * a + cam.Pinv[9] * b + cam.Pinv[10] * c + cam.Pinv[11];
-  }
-  const float px = (wx / vol_len + 1.f) * 0.5f * (float)(V - 1), py = (wy / vol_len + 1.f) * 0.5f * (float)(V - 1),
-              pz = (wz / vol_len + 1.f) * 0.5f * (float)(V - 1);
+  float px, py, pz;
+  frustum_to_lattice(cam, x, y, d, D, S, V, vol_len, persp, px, py, pz);
   const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
   const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
   const float tx = px - fx, ty = py - fy, tz = pz - fz;
@@ -485,7 +439,7 @@ __global__ __launch_bounds__(256) void frustum_gather_kernel(const float* __rest
     const int bx = corner & 1, by = (corner >> 1) & 1, bz = corner >> 2;
     const int xx = x0 + bx, yy = y0 + by, zz = z0 + bz;
     if (xx < 0 || xx > V - 1 || yy < 0 || yy > V - 1 || zz < 0 || zz > V - 1) continue;
-    const float wgt = (bx ? tx : 1.f - tx) * (by ? ty : 1.f - ty) * (bz ? tz : 1.f - tz);
+    const float wgt = trilinear_weight(bx, by, bz, tx, ty, tz);
     const float4 f = *(const float4*)(vol + (((long)zz * V + yy) * V + xx) * C + cq);
     acc.x += wgt * f.x;
     acc.y += wgt * f.y;
@@ -503,7 +457,6 @@ __global__ __launch_bounds__(256) void frustum_gather_kernel(const float* __rest
 // 256 / N voxels (N need not divide 256: the run then straddles workgroups) and together write one contiguous piece of the
 // channels-last fp16 operand out[V^3][16 N] -- 32 bytes per thread as two 16-byte stores.  The feature maps (64 KB per view at
 // S = 32 in fp32, 1 MB at 16 views) stay L2-resident: a tap is one 64-byte row, and neighbouring voxels of a run share taps.
-// Same projection arithmetic, in the same order, as vertex_gather_kernel above.
 __global__ __launch_bounds__(256) void unproject_views_kernel(const float* __restrict__ feats, const ViewCam* __restrict__ cams,
                                                               int N, int V, float vol_len, int S, int persp, half_t* __restrict__ out) {
   const long total = (long)V * V * V * N;
@@ -513,21 +466,8 @@ __global__ __launch_bounds__(256) void unproject_views_kernel(const float* __res
   const int pt = (int)(idx / N);
   const int ix = pt % V, iy = (pt / V) % V, iz = pt / (V * V);
   const float* P = cams[view].P;
-  const float X = linspace_at(-vol_len, vol_len, V, ix), Y = linspace_at(-vol_len, vol_len, V, iy),
-              Z = linspace_at(-vol_len, vol_len, V, iz);
-  const float u = P[0] * X + P[1] * Y + P[2] * Z + P[3];
-  const float v = P[4] * X + P[5] * Y + P[6] * Z + P[7];
   float px, py;
-  if (persp) {
-    float w = P[8] * X + P[9] * Y + P[10] * Z + P[11];
-    w = w < 1e-4f ? 1e-4f : w;
-    const float hs = (float)(S - 1) * 0.5f;
-    px = ((u / w) / hs - 1.0f + 1.0f) * 0.5f * (float)(S - 1);
-    py = ((v / w) / hs - 1.0f + 1.0f) * 0.5f * (float)(S - 1);
-  } else {
-    px = (u + 1.0f) * 0.5f * (float)(S - 1);
-    py = (v + 1.0f) * 0.5f * (float)(S - 1);
-  }
+  lattice_to_map(P, ix, iy, iz, V, vol_len, S, persp, px, py);
   float acc[16];
 #pragma unroll
   for (int c = 0; c < 16; ++c) acc[c] = 0.f;
@@ -541,7 +481,7 @@ __global__ __launch_bounds__(256) void unproject_views_kernel(const float* __res
     for (int tap = 0; tap < 4; ++tap) {
       const int xx = x0 + (tap & 1), yy = y0 + (tap >> 1);
       if (xx < 0 || xx > S - 1 || yy < 0 || yy > S - 1) continue;
-      const float w2 = ((tap & 1) ? tx : 1.f - tx) * ((tap >> 1) ? ty : 1.f - ty);
+      const float w2 = bilinear_weight(tap, tx, ty);
       const float4* f4 = (const float4*)(fv + ((long)yy * S + xx) * 16);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {

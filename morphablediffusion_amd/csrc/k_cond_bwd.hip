@@ -1,5 +1,5 @@
 // Backward kernels of the mesh conditioner (SpatialVolumeNet, morphable_diffusion.py:151-320; networks network.py): the
-// adjoints of the gathers of k_cond.hip (same index arithmetic, scatter instead of gather), the sparse voxel CNN's layers in
+// adjoints of the gathers of k_cond.hip (the same coordinate maps, cond.h; scatter instead of gather), the sparse voxel CNN's layers in
 // train mode (conv dgrad / wgrad through the neighbour tables, BatchNorm1d with batch statistics + ReLU), the view fusion, and
 // the transposing im2col for the frustum network's 3-D convolutions.
 // The three scatters use hardware fp32 atomic adds (unsafeAtomicAdd: the returning CAS loop of plain atomicAdd is 30x slower here) (unordered: the conditioner's gradients are reproducible to rounding, not bit
@@ -7,7 +7,7 @@
 // Those atomic forms are the DEFAULT.  The deterministic mode (mvd_train_set_deterministic) runs the three adjoints, and the fold
 // of duplicate vertices' rows, as gathers instead (cbwd_*_gather_adj, cbwd_lattice_to_views_adj, cbwd_sparse_fold_dups_det below):
 // no floating-point atomic to HBM or LDS, every sum in an order fixed by indices alone, every output element written.
-#include "common.h"
+#include "cond.h"
 
 namespace {
 
@@ -15,13 +15,6 @@ inline int gridn(size_t n, int cap = 8192) {
   size_t g = (n + 255) / 256;
   return (int)(g > (size_t)cap ? (size_t)cap : (g < 1 ? 1 : g));
 }
-
-__device__ __forceinline__ float linspace_at(float a, float b, int n, int i) {
-  const float step = (b - a) / (float)(n - 1);
-  return i < n / 2 ? a + step * (float)i : b - step * (float)(n - 1 - i);
-}
-__device__ __forceinline__ float ldf(const float* p) { return *p; }
-__device__ __forceinline__ float ldf(const half_t* p) { return (float)*p; }
 
 // adjoint of frustum_gather_kernel: d_vol[corner][c] += w * d_out[point][c]   (d_out fp32 [TN*D*S*S][64])
 __global__ __launch_bounds__(256) void frustum_scatter_kernel(const float* __restrict__ d_out, const ViewCam* __restrict__ cams,
@@ -35,24 +28,8 @@ __global__ __launch_bounds__(256) void frustum_scatter_kernel(const float* __res
   if (pt >= npts) return;
   const int x = (int)(pt % S), y = (int)((pt / S) % S), d = (int)((pt / ((long)S * S)) % D), tv = (int)(pt / ((long)S * S * D));
   const ViewCam cam = cams[view_idx[tv]];
-  const float depth = linspace_at(0.f, 1.f, D, d) * (cam.far_ - cam.near_) + cam.near_;
-  float wx, wy, wz;
-  if (persp) {
-    const float a = (float)x * depth, b = (float)y * depth, c = depth;
-    wx = cam.Pinv[0] * a + cam.Pinv[1] * b + cam.Pinv[2] * c + cam.Pinv[3];
-    wy = cam.Pinv[4] * a + cam.Pinv[5] * b + cam.Pinv[6] * c + cam.Pinv[7];
-    wz = cam.Pinv[8] * a + cam.Pinv[9] * b + cam.Pinv[10] * c + cam.Pinv[11];
-  } else {
-    const float gx = 2.f * (float)x / (float)(S - 1) - 1.f, gy = 2.f * (float)y / (float)(S - 1) - 1.f;
-    const float a = cam.Kinv[0] * gx + cam.Kinv[1] * gy + cam.Kinv[2];
-    const float b = cam.Kinv[3] * gx + cam.Kinv[4] * gy + cam.Kinv[5];
-    const float c = depth;
-    wx = cam.Pinv[0] * a + cam.Pinv[1] * b + cam.Pinv[2] * c + cam.Pinv[3];
-    wy = cam.Pinv[4] * a + cam.Pinv[5] * b + cam.Pinv[6] * c + cam.Pinv[7];
-    wz = cam.Pinv[8] * a + cam.Pinv[9] * b + cam.Pinv[10] * c + cam.Pinv[11];
-  }
-  const float px = (wx / vol_len + 1.f) * 0.5f * (float)(V - 1), py = (wy / vol_len + 1.f) * 0.5f * (float)(V - 1),
-              pz = (wz / vol_len + 1.f) * 0.5f * (float)(V - 1);
+  float px, py, pz;
+  frustum_to_lattice(cam, x, y, d, D, S, V, vol_len, persp, px, py, pz);
   const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
   const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
   const float tx = px - fx, ty = py - fy, tz = pz - fz;
@@ -62,7 +39,7 @@ __global__ __launch_bounds__(256) void frustum_scatter_kernel(const float* __res
     const int bx = corner & 1, by = (corner >> 1) & 1, bz = corner >> 2;
     const int xx = x0 + bx, yy = y0 + by, zz = z0 + bz;
     if (xx < 0 || xx > V - 1 || yy < 0 || yy > V - 1 || zz < 0 || zz > V - 1) continue;
-    const float wgt = (bx ? tx : 1.f - tx) * (by ? ty : 1.f - ty) * (bz ? tz : 1.f - tz);
+    const float wgt = trilinear_weight(bx, by, bz, tx, ty, tz);
     float* o = d_vol + (((long)zz * V + yy) * V + xx) * C + cq;
     unsafeAtomicAdd(o + 0, wgt * g.x);
     unsafeAtomicAdd(o + 1, wgt * g.y);
@@ -80,13 +57,8 @@ __global__ void latent_scatter_kernel(const float* __restrict__ d_vol, const int
     const int c = (int)(idx % C);
     const int pt = (int)(idx / C);
     const int ix = pt % V, iy = (pt / V) % V, iz = pt / (V * V);
-    const float X = linspace_at(-vol_len, vol_len, V, ix), Y = linspace_at(-vol_len, vol_len, V, iy),
-                Z = linspace_at(-vol_len, vol_len, V, iz);
-    const float gx = (X - minx) / voxel / shx * 2.f - 1.f;
-    const float gy = (Y - miny) / voxel / shy * 2.f - 1.f;
-    const float gz = (Z - minz) / voxel / shz * 2.f - 1.f;
-    const float px = (gx + 1.f) * 0.5f * (float)(gw - 1), py = (gy + 1.f) * 0.5f * (float)(gh - 1),
-                pz = (gz + 1.f) * 0.5f * (float)(gd - 1);
+    const float px = latent_axis_pos(minx, shx, gw, voxel, V, vol_len, ix), py = latent_axis_pos(miny, shy, gh, voxel, V, vol_len, iy),
+                pz = latent_axis_pos(minz, shz, gd, voxel, V, vol_len, iz);
     const float fx = floorf(px), fy = floorf(py), fz = floorf(pz);
     const int x0 = (int)fx, y0 = (int)fy, z0 = (int)fz;
     const float tx = px - fx, ty = py - fy, tz = pz - fz;
@@ -98,7 +70,7 @@ __global__ void latent_scatter_kernel(const float* __restrict__ d_vol, const int
       if (xx < 0 || xx > gw - 1 || yy < 0 || yy > gh - 1 || zz < 0 || zz > gd - 1) continue;
       const int row = grid[((long)zz * gh + yy) * gw + xx];
       if (row < 0) continue;
-      const float wgt = (bx ? tx : 1.f - tx) * (by ? ty : 1.f - ty) * (bz ? tz : 1.f - tz);
+      const float wgt = trilinear_weight(bx, by, bz, tx, ty, tz);
       unsafeAtomicAdd(d_rows + (long)row * C + c, wgt * g);
     }
   }
@@ -122,33 +94,13 @@ __global__ __launch_bounds__(1024) void vertex_scatter_kernel(const float* __res
     const int vi = job >> 3, corner = job & 7;
     float fr[3];
     int lo[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      const float g = verts[vi * 3 + a] / vol_len;
-      const float pos = (g + 1.0f) * 0.5f * (float)(V - 1);
-      const float f = floorf(pos);
-      lo[a] = (int)f;
-      fr[a] = pos - f;
-    }
+    vertex_cell(verts, vi, V, vol_len, lo, fr);
     const int bx = corner & 1, by = (corner >> 1) & 1, bz = corner >> 2;
     const int ix = lo[0] + bx, iy = lo[1] + by, iz = lo[2] + bz;
     if (ix < 0 || ix > V - 1 || iy < 0 || iy > V - 1 || iz < 0 || iz > V - 1) continue;
-    const float w3 = (bx ? fr[0] : 1.f - fr[0]) * (by ? fr[1] : 1.f - fr[1]) * (bz ? fr[2] : 1.f - fr[2]);
-    const float X = linspace_at(-vol_len, vol_len, V, ix), Y = linspace_at(-vol_len, vol_len, V, iy),
-                Z = linspace_at(-vol_len, vol_len, V, iz);
-    const float u = cam.P[0] * X + cam.P[1] * Y + cam.P[2] * Z + cam.P[3];
-    const float v = cam.P[4] * X + cam.P[5] * Y + cam.P[6] * Z + cam.P[7];
+    const float w3 = trilinear_weight(bx, by, bz, fr[0], fr[1], fr[2]);
     float px, py;
-    if (persp) {
-      float w = cam.P[8] * X + cam.P[9] * Y + cam.P[10] * Z + cam.P[11];
-      w = w < 1e-4f ? 1e-4f : w;
-      const float hs = (float)(S - 1) * 0.5f;
-      px = ((u / w) / hs - 1.0f + 1.0f) * 0.5f * (float)(S - 1);
-      py = ((v / w) / hs - 1.0f + 1.0f) * 0.5f * (float)(S - 1);
-    } else {
-      px = (u + 1.0f) * 0.5f * (float)(S - 1);
-      py = (v + 1.0f) * 0.5f * (float)(S - 1);
-    }
+    lattice_to_map(cam.P, ix, iy, iz, V, vol_len, S, persp, px, py);
     const float fx0 = floorf(px), fy0 = floorf(py);
     const int x0 = (int)fx0, y0 = (int)fy0;
     const float tx = px - fx0, ty = py - fy0;
@@ -160,7 +112,7 @@ __global__ __launch_bounds__(1024) void vertex_scatter_kernel(const float* __res
     for (int tap = 0; tap < 4; ++tap) {
       const int xx = x0 + (tap & 1), yy = y0 + (tap >> 1);
       if (xx < 0 || xx > S - 1 || yy < 0 || yy > S - 1) continue;
-      const float w2 = ((tap & 1) ? tx : 1.f - tx) * ((tap >> 1) ? ty : 1.f - ty) * w3;
+      const float w2 = bilinear_weight(tap, tx, ty) * w3;
       float* o = s_img + yy * S + xx;
 #pragma unroll
       for (int c = 0; c < 16; ++c) unsafeAtomicAdd(o + c * SS, w2 * g16[c]);
@@ -180,12 +132,12 @@ __global__ __launch_bounds__(1024) void vertex_scatter_kernel(const float* __res
 // every (point, corner) pair is counted exactly once whatever the box's rounding.
 constexpr float BOX_FINITE = 1e9f;  // a box bound beyond this (or NaN) means: scan everything
 
-// Lattice positions pos[point][3] of all frustum points, one thread per point: the head of frustum_scatter_kernel statement for
-// statement.  The gather below reads them instead of recomputing them per candidate: once per point, not once per (candidate,
-// channel quad), and -- a straight-line kernel of the same expressions gets the same fused multiply-adds, whereas the same code
-// inside the gather's loops is fused differently after hoisting -- the same fp32 positions as the atomic form's.  (With
-// positions recomputed in the loops the two forms' dL/d(volume) differed by 1.07e-5 relative L2 at V = 32, with positions in
-// double by 0.99e-5: fp32 rounding of x * depth against Pinv's small entries, not summation order.)
+// Lattice positions pos[point][3] of all frustum points, one thread per point, by frustum_scatter_kernel's map (cond.h).  The
+// gather below reads them instead of recomputing them per candidate: once per point, not once per (candidate, channel quad),
+// and -- a straight-line kernel of the map gets the same fused multiply-adds, whereas the same code inside the gather's loops
+// is fused differently after hoisting -- the same fp32 positions as the atomic form's.  (With positions recomputed in the loops
+// the two forms' dL/d(volume) differed by 1.07e-5 relative L2 at V = 32, with positions in double by 0.99e-5: fp32 rounding of
+// x * depth against Pinv's small entries, not summation order.)
 __global__ __launch_bounds__(256) void frustum_positions_kernel(const ViewCam* __restrict__ cams, const int* __restrict__ view_idx, int TN,
                                                                 int D, int S, int V, float vol_len, int persp, float* __restrict__ pos) {
   const long pt = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -193,24 +145,8 @@ __global__ __launch_bounds__(256) void frustum_positions_kernel(const ViewCam* _
   if (pt >= npts) return;
   const int x = (int)(pt % S), y = (int)((pt / S) % S), d = (int)((pt / ((long)S * S)) % D), tv = (int)(pt / ((long)S * S * D));
   const ViewCam cam = cams[view_idx[tv]];
-  const float depth = linspace_at(0.f, 1.f, D, d) * (cam.far_ - cam.near_) + cam.near_;
-  float wx, wy, wz;
-  if (persp) {
-    const float a = (float)x * depth, b = (float)y * depth, c = depth;
-    wx = cam.Pinv[0] * a + cam.Pinv[1] * b + cam.Pinv[2] * c + cam.Pinv[3];
-    wy = cam.Pinv[4] * a + cam.Pinv[5] * b + cam.Pinv[6] * c + cam.Pinv[7];
-    wz = cam.Pinv[8] * a + cam.Pinv[9] * b + cam.Pinv[10] * c + cam.Pinv[11];
-  } else {
-    const float gx = 2.f * (float)x / (float)(S - 1) - 1.f, gy = 2.f * (float)y / (float)(S - 1) - 1.f;
-    const float a = cam.Kinv[0] * gx + cam.Kinv[1] * gy + cam.Kinv[2];
-    const float b = cam.Kinv[3] * gx + cam.Kinv[4] * gy + cam.Kinv[5];
-    const float c = depth;
-    wx = cam.Pinv[0] * a + cam.Pinv[1] * b + cam.Pinv[2] * c + cam.Pinv[3];
-    wy = cam.Pinv[4] * a + cam.Pinv[5] * b + cam.Pinv[6] * c + cam.Pinv[7];
-    wz = cam.Pinv[8] * a + cam.Pinv[9] * b + cam.Pinv[10] * c + cam.Pinv[11];
-  }
-  const float px = (wx / vol_len + 1.f) * 0.5f * (float)(V - 1), py = (wy / vol_len + 1.f) * 0.5f * (float)(V - 1),
-              pz = (wz / vol_len + 1.f) * 0.5f * (float)(V - 1);
+  float px, py, pz;
+  frustum_to_lattice(cam, x, y, d, D, S, V, vol_len, persp, px, py, pz);
   pos[pt * 3 + 0] = px;
   pos[pt * 3 + 1] = py;
   pos[pt * 3 + 2] = pz;
@@ -338,11 +274,6 @@ __device__ __forceinline__ void latent_axis_window(float mn, float sh, int g, in
     hi = h;
   }
 }
-__device__ __forceinline__ float latent_axis_pos(float mn, float sh, int g, float voxel, int V, float vol_len, int i) {
-  const float X = linspace_at(-vol_len, vol_len, V, i);
-  const float gx = (X - mn) / voxel / sh * 2.f - 1.f;
-  return (gx + 1.f) * 0.5f * (float)(g - 1);
-}
 // d_rows[grid[cell]][c] = sum over lattice points (iz, iy, ix) ascending of w * d_vol[point][c]: one thread per (cell, channel);
 // cells without a row are skipped, every row belongs to exactly one cell, so every row is written
 __global__ __launch_bounds__(256) void latent_gather_adj_kernel(const float* __restrict__ d_vol, const int* __restrict__ grid, int gd,
@@ -388,8 +319,7 @@ __global__ void vertex_key_kernel(const float* __restrict__ verts, int Nv, int V
   int k = 0;
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const float g = verts[vi * 3 + a] / vol_len;
-    const float pos = (g + 1.0f) * 0.5f * (float)(V - 1);
+    const float pos = vertex_axis_pos(verts, vi, a, V, vol_len);
     const float f = fminf(fmaxf(floorf(pos), -2.f), (float)V);  // (outside [-1, V - 1] no corner is on the lattice)
     k |= ((int)f + 2) << (VKEY_BITS * a);
   }
@@ -417,15 +347,10 @@ __global__ __launch_bounds__(256) void vertex_bins_kernel(const int* __restrict_
     if (corner < 0) continue;
     if (FILL) {
       float fr[3];
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {  // vertex_scatter_kernel's arithmetic
-        const float g = verts[vi * 3 + a] / vol_len;
-        const float pos = (g + 1.0f) * 0.5f * (float)(V - 1);
-        fr[a] = pos - floorf(pos);
-      }
-      const int bx = corner & 1, by = (corner >> 1) & 1, bz = corner >> 2;
+      int lo[3];
+      vertex_cell(verts, vi, V, vol_len, lo, fr);
       list_v[n] = vi;
-      list_w[n] = (bx ? fr[0] : 1.f - fr[0]) * (by ? fr[1] : 1.f - fr[1]) * (bz ? fr[2] : 1.f - fr[2]);
+      list_w[n] = trilinear_weight(corner & 1, (corner >> 1) & 1, corner >> 2, fr[0], fr[1], fr[2]);
     }
     ++n;
   }
@@ -479,9 +404,8 @@ __global__ __launch_bounds__(256) void vertex_to_lattice_adj_kernel(const float*
   for (int i = b; i < e; ++i) acc += list_w[i] * src[(long)list_v[i] * 16];
   d_lat[((long)view * stride + j) * 16 + c] = acc;
 }
-// stage B, step 1: where lattice voxel vox_list[j] (NULL: voxel j) lands in every view's map -- vertex_scatter_kernel's
-// arithmetic -- as (x0, y0, tx, ty), once per (view, voxel).  Positions far outside the map are pulled to its rim + 1, where no
-// tap is inside either.
+// stage B, step 1: where lattice voxel vox_list[j] (NULL: voxel j) lands in every view's map, as (x0, y0, tx, ty), once per
+// (view, voxel).  Positions far outside the map are pulled to its rim + 1, where no tap is inside either.
 __global__ void lattice_project_kernel(const ViewCam* __restrict__ cams, const int* __restrict__ view_idx, const int* __restrict__ vox_list,
                                        const int* __restrict__ n_ptr, int n_max, int V, float vol_len, int S, int persp,
                                        float4* __restrict__ rec) {
@@ -490,21 +414,8 @@ __global__ void lattice_project_kernel(const ViewCam* __restrict__ cams, const i
   const ViewCam cam = cams[view_idx[view]];
   const int vox = vox_list ? vox_list[j] : j;
   const int ix = vox % V, iy = (vox / V) % V, iz = vox / (V * V);
-  const float X = linspace_at(-vol_len, vol_len, V, ix), Y = linspace_at(-vol_len, vol_len, V, iy),
-              Z = linspace_at(-vol_len, vol_len, V, iz);
-  const float u = cam.P[0] * X + cam.P[1] * Y + cam.P[2] * Z + cam.P[3];
-  const float v = cam.P[4] * X + cam.P[5] * Y + cam.P[6] * Z + cam.P[7];
   float px, py;
-  if (persp) {
-    float w = cam.P[8] * X + cam.P[9] * Y + cam.P[10] * Z + cam.P[11];
-    w = w < 1e-4f ? 1e-4f : w;
-    const float hs = (float)(S - 1) * 0.5f;
-    px = ((u / w) / hs - 1.0f + 1.0f) * 0.5f * (float)(S - 1);
-    py = ((v / w) / hs - 1.0f + 1.0f) * 0.5f * (float)(S - 1);
-  } else {
-    px = (u + 1.0f) * 0.5f * (float)(S - 1);
-    py = (v + 1.0f) * 0.5f * (float)(S - 1);
-  }
+  lattice_to_map(cam.P, ix, iy, iz, V, vol_len, S, persp, px, py);
   px = fminf(fmaxf(px, -2.f), (float)(S + 1));
   py = fminf(fmaxf(py, -2.f), (float)(S + 1));
   const float fx0 = floorf(px), fy0 = floorf(py);
