@@ -451,6 +451,46 @@ int mvd_op_mesh_texture_dilate(const float* texture, const unsigned char* valid,
 int mvd_op_mesh_render_uv(const int32_t* xy, const int32_t* key, const int32_t* face_id, const int32_t* faces, const int32_t* face_uv,
                           const float* uv, const float* texture, int N, int Nv, int Nf, int Nt, int H, int W, int Ht, int Wt, int layout,
                           float bg_r, float bg_g, float bg_b, float* images, void* stream);
+/* Closest point on a triangle mesh (csrc/k_closest.hip; the per-triangle function in csrc/mesh.h): for each of Q query points the
+ * closest point of the mesh by exhaustive search over its faces -- exact, no spatial structure is built.  No context; device
+ * pointers; the call synchronises the stream.  fp32 on the vector ALU, every sum written out below, no floating-point atomics:
+ * two calls agree bit for bit and the result does not depend on how the faces are spread over workgroups.
+ *   one triangle  dot(x, y) = fma(x_2, y_2, fma(x_1, y_1, x_0 y_0)).  ab = b - a, ac = c - a; d1 = dot(ab, q - a), d2 = dot(ac, q - a),
+ *                 d3 = dot(ab, q - b), d4 = dot(ac, q - b), d5 = dot(ab, q - c), d6 = dot(ac, q - c); vc = fma(d1, d4, -(d3 d2)),
+ *                 vb = fma(d5, d2, -(d1 d6)), va = fma(d3, d6, -(d5 d4)); e1 = d4 - d3, e2 = d5 - d6.  The first region that holds, in
+ *                 this order, gives the barycentrics w (all >= 0):
+ *                   corner a   d1 <= 0 and d2 <= 0                    w = (1, 0, 0)
+ *                   corner b   d3 >= 0 and d4 <= d3                   w = (0, 1, 0)
+ *                   edge ab    vc <= 0 and d1 >= 0 and d3 <= 0        t = d1 / (d1 - d3),  w = (1 - t, t, 0)
+ *                   corner c   d6 >= 0 and d5 <= d6                   w = (0, 0, 1)
+ *                   edge ac    vb <= 0 and d2 >= 0 and d6 <= 0        t = d2 / (d2 - d6),  w = (1 - t, 0, t)
+ *                   edge bc    va <= 0 and e1 >= 0 and e2 >= 0        t = e1 / (e1 + e2),  w = (0, 1 - t, t)
+ *                   interior   s = (va + vb) + vc, v = max(vb / s, 0), u = max(vc / s, 0),  w = (max((1 - v) - u, 0), v, u)
+ *                 A division whose denominator is zero gives parameter 0, so a zero-area face returns a point of itself and never
+ *                 a NaN; a point cloud is passed as faces (i, i, i), which always answer with corner a.  point_k = fma(w_2, c_k,
+ *                 fma(w_1, b_k, w_0 a_k)); dist2 = dot(q - point, q - point).  The regions are selected by predication.
+ *   selection     key [Q] = (bits(dist2) << 32) | face; the smallest key wins: the smallest distance (dist2 >= 0, so its bits order
+ *                 as the floats do), ties to the smallest face index.  A candidate needs dist2 < +inf: a face whose arithmetic
+ *                 overflows, or gives a NaN, is no candidate.  The search keeps only dist2 (a 64-bit integer atomicMin on key);
+ *                 a finalize pass recomputes bary / point / dist2 of the winner with the same function, so that the dist2 written
+ *                 equals the key's high word bit for bit and key's low word equals face.
+ *   skipped       a face with an index outside [0, Nv) or a non-finite corner is skipped and never dereferenced.
+ *   normal gate   only when query_normals [Q,3] (any length) is given: face f is a candidate for query q iff dot(n_q, N_f) >=
+ *                 cos_min (|n_q| |N_f|) with N_f = (b - a) x (c - a), N_0 = fma(ab_1, ac_2, -(ab_2 ac_1)) and cyclic, |x| =
+ *                 sqrt(dot(x, x)).  A zero-area face, and a zero query normal, therefore always pass; a NaN normal never does.
+ *   distance gate after the search: dist2 > max_dist2 is no match (+inf: no gate).
+ *   no match      face = -1, dist2 = +inf, bary and point zero, key = (bits(+inf) << 32) | 0xFFFFFFFF.  A non-finite query gives
+ *                 no match.
+ *   launch        a workgroup owns a tile of 256 queries and one slab of faces: the grid is tiles x slabs.  slabs = 0 takes
+ *                 mvd_mesh_closest_slabs(Q, Nf), a host function of Q and Nf alone that fills the chip when the query tiles do
+ *                 not (1 when they do); any other count gives the same bits.
+ * Errors, which return before the first HIP call: a null pointer (but query_normals); Q, Nv or Nf < 1; 3 Q, 3 Nv or 3 Nf >= 2^31;
+ * max_dist2 not positive or NaN; cos_min outside [-1, 1] or NaN; slabs < 0.  Not computed: point-to-plane distances, spatial
+ * acceleration structures. */
+int mvd_mesh_closest_slabs(int Q, int Nf);
+int mvd_op_mesh_closest_point(const float* queries, const float* query_normals, const float* verts, const int32_t* faces, int Q, int Nv,
+                              int Nf, float cos_min, float max_dist2, int slabs, uint64_t* key, int32_t* face, float* bary, float* point,
+                              float* dist2, void* stream);
 /* The morphable-model forward (csrc/k_morph.hip): FLAME / SMPL-X parameters to vertices by linear blend skinning, the formulas of
  * the reference's third_party/MICA/models/lbs.py.  No context; device pointers but `parents`; each call synchronises the stream.
  * Everything is fp32 on the vector ALU with fused multiply-adds in an order fixed by indices alone, no atomics: two calls agree
@@ -532,6 +572,28 @@ int mvd_op_morph_landmarks(const float* verts, const int32_t* faces, const int32
  *                 likewise; Adam steps step0 + 1 .. step0 + iters.  workspace: as many floats of the caller as
  *                 mvd_morph_fit_workspace(F, V, NB, J, M, &floats) stores in the HOST integer (M = 0 without a landmark target).  loss_history [iters,F]: E before each update.  Each
  *                 iteration's bits are those of the seven per-op entries called in turn.
+ *   mvd_op_morph_fit_data_corr   the data term against correspondences, for a target of another topology: corr_point [F,V,3] and
+ *                 corr_face [F,V] as mvd_op_mesh_closest_point returns point and face for queries = verts; m_fv = (corr_face >= 0).
+ *                 The normaliser is computed per frame on the device: W_f = sum_v w_v m_fv.  E_f = sum_v w_v m_fv |y - c|^2 / W_f +
+ *                 the landmark term of mvd_op_morph_fit_data, unchanged; g_y = (2 w_v m_fv (1 / W_f)) (y - c), then the same landmark
+ *                 gather; n_matched [F] = sum_v m_fv.  Summation shape as mvd_op_morph_fit_data: the squares and the weights per block
+ *                 of 256 vertices into e_part and w_part [mvd_morph_bwd_chunks(V) + 1, F] (its last row takes 1 / W_f), then per
+ *                 frame a lane-strided ascending sum over blocks and one butterfly.  W_f = 0 (nothing matched): the vertex term
+ *                 and its gradient are exactly zero.  An unmatched vertex's corr_point is never read: a NaN there does not leak.
+ *   mvd_morph_fit_scan_run   the loop of mvd_morph_fit_run with the target replaced by correspondences to a scan.  Iteration `it`:
+ *                 pose, skin_ex, landmarks (with a landmark target); if it % refresh == 0: mvd_op_mesh_vertex_normals of the
+ *                 current vertices (only with normal_gate != 0; inc_ptr / inc_face: the model's face incidence) and
+ *                 mvd_op_mesh_closest_point with queries = the current vertices (their normals as query_normals with the gate),
+ *                 cos_min, max_dist2 and the planned slab count; then fit_data_corr, skin_bwd, pose_bwd, fit_update.  Plain
+ *                 launches on the stream, one synchronisation at the end.  Scans: Fs = 1 (shared: one query launch with Q = F V)
+ *                 or Fs = F (one launch per frame), concatenated in scan_verts / scan_faces with HOST offset arrays scan_vptr
+ *                 [Fs+1] and scan_fptr [Fs+1] (vertices and faces, starting at 0); face indices are local to their scan.
+ *                 workspace: mvd_morph_fit_scan_workspace(F, V, NB, J, M, &floats) floats.  Outputs beyond mvd_morph_fit_run's:
+ *                 matched_history [iters,F] (n_matched of every iteration) and corr_face [F,V] (the last correspondences).  Each
+ *                 iteration's bits are those of the per-op entries called in turn.  Further errors: refresh < 1; Fs neither 1 nor
+ *                 F; offsets that do not start at 0 or leave a scan without a vertex or a face; the normal gate without faces and
+ *                 incidence; those of mvd_op_mesh_closest_point.  Not computed: point-to-plane and robust kernels, the
+ *                 scan-to-model direction as a gradient term (a scatter), non-rigid per-vertex offsets.
  * Errors, which return before the first HIP call: those of the forward's list for the same arguments; a null pointer (but post,
  * transl, blend, g_joints, g_in, the weights, and one of the two targets); counts < 1; a target with neither 1 nor F frames; more
  * than 65535 frames in fit_data / fit_run; step < 1, beta outside [0, 1), eps <= 0; a workspace that is too small. */
@@ -561,6 +623,20 @@ int mvd_morph_fit_run(const float* basis, const float* v_template, const float* 
                       int target_lmk_frames, const float* lmk_weight, float lmk_scale, float* p, float* m, float* v, const float* lr,
                       const float* lam, const float* p0, int iters, int step0, float beta1, float beta2, float eps, float* workspace,
                       size_t workspace_floats, float* loss_history, void* stream);
+int mvd_op_morph_fit_data_corr(const float* verts, const float* corr_point, const int32_t* corr_face, const float* vertex_weight,
+                               const float* lmk, const float* target_lmk, int target_lmk_frames, const float* lmk_weight, float lmk_scale,
+                               const int32_t* csr_ptr, const int32_t* csr_ent, const float* lmk_bary, int F, int V, int M, int n_ent,
+                               float* g_y, float* e_part, float* w_part, float* E, int32_t* n_matched, void* stream);
+int mvd_morph_fit_scan_workspace(int F, int V, int NB, int J, int M, int64_t* floats);
+int mvd_morph_fit_scan_run(const float* basis, const float* v_template, const float* weights, const float* j_template, const float* j_dirs,
+                           const int32_t* parents, const float* post, const int32_t* faces, const int32_t* lmk_face, const float* lmk_bary,
+                           const int32_t* csr_ptr, const int32_t* csr_ent, const int32_t* inc_ptr, const int32_t* inc_face, int F, int V,
+                           int NB, int J, int Nf, int M, int n_ent, const float* scan_verts, const int32_t* scan_faces,
+                           const int32_t* scan_vptr, const int32_t* scan_fptr, int Fs, int normal_gate, float cos_min, float max_dist2,
+                           int refresh, const float* vertex_weight, const float* target_lmk, int target_lmk_frames,
+                           const float* lmk_weight, float lmk_scale, float* p, float* m, float* v, const float* lr, const float* lam,
+                           const float* p0, int iters, int step0, float beta1, float beta2, float eps, float* workspace,
+                           size_t workspace_floats, float* loss_history, int32_t* matched_history, int32_t* corr_face, void* stream);
 /* The conditioner's backward for ONE sample (its mesh / cameras active: mvd_select_sample): re-runs construct_spatial_volume and
  * construct_view_frustum_volume (morphable_diffusion.py:203-320: step embedding, 2-D encoder on the N noisy views, vertex gather,
  * view fusion, sparse voxel CNN in train mode, lattice gather, frustum gather and FrustumTV3DNet for the target view) with every

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "mesh.h"
 #include "rowchain.h"
 
 static thread_local std::string g_err;
@@ -702,6 +703,21 @@ int mvd_op_mesh_render_uv(const int32_t* xy, const int32_t* key, const int32_t* 
   int rc = launch_mesh_render_uv(xy, key, face_id, faces, face_uv, uv, texture, N, Nv, Nf, Nt, H, W, Ht, Wt, layout, bg_r, bg_g, bg_b, images,
                                  s);
   if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_mesh_render_uv: stream synchronisation failed");
+  return rc;
+}
+
+// ---- closest point on a mesh (csrc/k_closest.hip): no context, the caller's device buffers
+int mvd_mesh_closest_slabs(int Q, int Nf) { return mesh_closest_slabs(Q, Nf); }
+
+int mvd_op_mesh_closest_point(const float* queries, const float* query_normals, const float* verts, const int32_t* faces, int Q, int Nv, int Nf,
+                              float cos_min, float max_dist2, int slabs, uint64_t* key, int32_t* face, float* bary, float* point, float* dist2,
+                              void* stream) {
+  RET_IF(mesh_closest_check("mvd_op_mesh_closest_point", queries, verts, faces, Q, Nv, Nf, cos_min, max_dist2, slabs,
+                            (const unsigned long long*)key, face, bary, point, dist2));
+  hipStream_t s = S(stream);
+  int rc = launch_mesh_closest_point(queries, query_normals, verts, faces, Q, Nv, Nf, cos_min, max_dist2, slabs, (unsigned long long*)key, face,
+                                     bary, point, dist2, s);
+  if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = mvd_fail("mvd_op_mesh_closest_point: stream synchronisation failed");
   return rc;
 }
 

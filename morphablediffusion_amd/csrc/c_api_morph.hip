@@ -1,7 +1,11 @@
 // The morphable-model backward and fitter of the C ABI (include/mvd.h: mvd_op_morph_skin_ex, the mvd_op_morph_*_bwd and
 // mvd_op_morph_fit_* entries, mvd_morph_fit_run) over k_morph.hip and k_morph_bwd.hip.  No context, the caller's device buffers;
-// parents is a host array.  The per-op entries end in hooks.h's hook_sync; the loop of mvd_morph_fit_run synchronises once.
+// parents is a host array.  The per-op entries end in hooks.h's hook_sync; the loops of mvd_morph_fit_run and mvd_morph_fit_scan_run
+// (the same loop with the target replaced by closest points of a scan, csrc/k_closest.hip) synchronise once.
+#include <algorithm>
+
 #include "hooks.h"
+#include "mesh.h"
 #include "morph.h"
 
 namespace {
@@ -23,6 +27,24 @@ struct FitLayout {
     verts = take(f * V * 3), blend = take(f * V * 3), lmk = take(f * (size_t)M * 3), g_y = take(f * V * 3), g_b = take(f * V * 3);
     part_a = take((size_t)morph_bwd_chunks(V) * f * ((size_t)J * 12 + 3)), part_c = take((size_t)morph_bwd_slabs(V) * f * L);
     e_part = take((size_t)morph_bwd_chunks(V) * f), g = take(f * P);
+    total = o;
+  }
+};
+
+// mvd_morph_fit_scan_run's workspace: the fitter's, then the correspondence buffers (key: 8 bytes a query)
+struct ScanLayout {
+  FitLayout fit;
+  size_t normals, corr_point, key, bary, dist2, w_part, bad, total;
+  ScanLayout(int F, int V, int NB, int J, int M) : fit(F, V, NB, J, M) {
+    const size_t n = (size_t)F * V;
+    size_t o = fit.total;
+    auto take = [&](size_t k) {
+      const size_t at = o;
+      o += (k + 63) & ~(size_t)63;
+      return at;
+    };
+    normals = take(n * 3), corr_point = take(n * 3), key = take(n * 2), bary = take(n * 3), dist2 = take(n);
+    w_part = take(((size_t)morph_bwd_chunks(V) + 1) * F), bad = take(1);
     total = o;
   }
 };
@@ -77,6 +99,18 @@ int mvd_op_morph_fit_data(const float* verts, const float* target, int target_fr
   return hook_sync("mvd_op_morph_fit_data", s,
                    launch_morph_fit_data(verts, target, target_frames, vertex_weight, inv_vw_sum, lmk, target_lmk, target_lmk_frames,
                                          lmk_weight, lmk_scale, csr_ptr, csr_ent, lmk_bary, F, V, M, n_ent, g_y, e_part, E, s));
+}
+
+int mvd_op_morph_fit_data_corr(const float* verts, const float* corr_point, const int32_t* corr_face, const float* vertex_weight,
+                               const float* lmk, const float* target_lmk, int target_lmk_frames, const float* lmk_weight, float lmk_scale,
+                               const int32_t* csr_ptr, const int32_t* csr_ent, const float* lmk_bary, int F, int V, int M, int n_ent,
+                               float* g_y, float* e_part, float* w_part, float* E, int32_t* n_matched, void* stream) {
+  RET_IF(morph_fit_data_corr_check("mvd_op_morph_fit_data_corr", verts, corr_point, corr_face, lmk, target_lmk, target_lmk_frames, csr_ptr,
+                                   csr_ent, lmk_bary, F, V, M, n_ent, g_y, e_part, w_part, E, n_matched));
+  hipStream_t s = S(stream);
+  return hook_sync("mvd_op_morph_fit_data_corr", s,
+                   launch_morph_fit_data_corr(verts, corr_point, corr_face, vertex_weight, lmk, target_lmk, target_lmk_frames, lmk_weight,
+                                              lmk_scale, csr_ptr, csr_ent, lmk_bary, F, V, M, n_ent, g_y, e_part, w_part, E, n_matched, s));
 }
 
 int mvd_op_morph_fit_update(float* p, const float* g, float* m, float* v, const float* lr, const float* lam, const float* p0, int F, int P,
@@ -136,6 +170,96 @@ int mvd_morph_fit_run(const float* basis, const float* v_template, const float* 
     if (!rc)
       rc = launch_morph_fit_data(verts, target, target_frames, vertex_weight, inv_vw_sum, lmk, target_lmk, target_lmk_frames, lmk_weight,
                                  lmk_scale, csr_ptr, csr_ent, lmk_bary, F, V, M, n_ent, g_y, e_part, loss_history + (size_t)it * F, s);
+    if (!rc) rc = launch_morph_skin_bwd(g_y, post, weights, A, blend, basis, F, V, L, J, g_b, part_a, part_c, s);
+    if (!rc)
+      rc = launch_morph_pose_bwd(pose, P, j_rest, A, j_dirs, parents, part_a, nchunk, part_c, nslab, nullptr, F, NB, J, g, P, g + NB, P,
+                                 g + NB + 3 * J, P, s);
+    if (!rc) rc = launch_morph_fit_update(p, g, m, v, lr, lam, p0, F, P, step0 + it + 1, beta1, beta2, eps, s);
+  }
+  return hook_sync(who, s, rc);
+}
+
+int mvd_morph_fit_scan_workspace(int F, int V, int NB, int J, int M, int64_t* floats) {
+  if (!floats) return morph_fail("mvd_morph_fit_scan_workspace", ": null argument");
+  if (F < 1 || V < 1 || NB < 1 || J < 1 || J > MORPH_MAX_JOINTS || M < 0)
+    return morph_fail("mvd_morph_fit_scan_workspace", ": F, V and NB must be at least 1, J in 1..64, M at least 0");
+  *floats = (int64_t)ScanLayout(F, V, NB, J, M).total;
+  return 0;
+}
+
+int mvd_morph_fit_scan_run(const float* basis, const float* v_template, const float* weights, const float* j_template, const float* j_dirs,
+                           const int32_t* parents, const float* post, const int32_t* faces, const int32_t* lmk_face, const float* lmk_bary,
+                           const int32_t* csr_ptr, const int32_t* csr_ent, const int32_t* inc_ptr, const int32_t* inc_face, int F, int V,
+                           int NB, int J, int Nf, int M, int n_ent, const float* scan_verts, const int32_t* scan_faces,
+                           const int32_t* scan_vptr, const int32_t* scan_fptr, int Fs, int normal_gate, float cos_min, float max_dist2,
+                           int refresh, const float* vertex_weight, const float* target_lmk, int target_lmk_frames,
+                           const float* lmk_weight, float lmk_scale, float* p, float* m, float* v, const float* lr, const float* lam,
+                           const float* p0, int iters, int step0, float beta1, float beta2, float eps, float* workspace,
+                           size_t workspace_floats, float* loss_history, int32_t* matched_history, int32_t* corr_face, void* stream) {
+  const char* who = "mvd_morph_fit_scan_run";
+  if (!workspace || !loss_history || !matched_history || !corr_face || !scan_verts || !scan_faces || !scan_vptr || !scan_fptr)
+    return morph_fail(who, ": null argument");
+  if (iters < 1 || step0 < 0 || step0 > 0x7fffffff - iters) return morph_fail(who, ": iters must be at least 1 and step0 at least 0");
+  if (refresh < 1) return morph_fail(who, ": refresh must be at least 1");
+  if (F < 1 || V < 1 || NB < 1 || J < 1 || J > MORPH_MAX_JOINTS || M < 0)
+    return morph_fail(who, ": F, V and NB must be at least 1, J in 1..64, M at least 0");
+  if (morph_too_big(iters, F, 1)) return morph_fail(who, ": iters F must be below 2^31");
+  if (Fs != 1 && Fs != F) return morph_fail(who, ": one scan or one per frame");
+  if (scan_vptr[0] != 0 || scan_fptr[0] != 0) return morph_fail(who, ": the scan offsets must start at 0");
+  for (int i = 0; i < Fs; ++i)
+    if (scan_vptr[i + 1] <= scan_vptr[i] || scan_fptr[i + 1] <= scan_fptr[i])
+      return morph_fail(who, ": every scan needs at least one vertex and one face, offsets ascending");
+  const bool use_lmk = target_lmk != nullptr, gate = normal_gate != 0;
+  if (use_lmk && (!faces || !lmk_face || M < 1 || Nf < 1)) return morph_fail(who, ": a landmark target needs the landmark embedding");
+  if (gate && (!faces || !inc_ptr || !inc_face || Nf < 1)) return morph_fail(who, ": the normal gate needs the model's faces and their incidence");
+  const ScanLayout lay(F, V, NB, J, use_lmk ? M : 0);
+  if (workspace_floats < lay.total) return morph_fail(who, ": the workspace is smaller than mvd_morph_fit_scan_workspace says");
+  const int L = NB + 9 * (J - 1), P = NB + 3 * J + 3, nchunk = morph_bwd_chunks(V), nslab = morph_bwd_slabs(V);
+  float* w = workspace;
+  float *j_rest = w + lay.fit.j_rest, *rot = w + lay.fit.rot, *joints = w + lay.fit.joints, *A = w + lay.fit.A, *coef = w + lay.fit.coef;
+  float *verts = w + lay.fit.verts, *blend = w + lay.fit.blend, *lmk = use_lmk ? w + lay.fit.lmk : nullptr, *g_y = w + lay.fit.g_y;
+  float *g_b = w + lay.fit.g_b, *part_a = w + lay.fit.part_a, *part_c = w + lay.fit.part_c, *e_part = w + lay.fit.e_part, *g = w + lay.fit.g;
+  float *normals = w + lay.normals, *corr_point = w + lay.corr_point, *bary = w + lay.bary, *dist2 = w + lay.dist2, *w_part = w + lay.w_part;
+  unsigned long long* key = (unsigned long long*)(w + lay.key);
+  int* bad = (int*)(w + lay.bad);
+  // every argument error of every stage, before the first HIP call
+  RET_IF(morph_pose_check(who, p, p, j_template, j_dirs, parents, F, NB, J, j_rest, rot, coef, joints, A));
+  RET_IF(morph_skin_check(who, basis, v_template, coef, weights, A, F, V, L, NB, J, verts));
+  if (use_lmk) RET_IF(morph_landmarks_check(who, verts, faces, lmk_face, lmk_bary, F, V, Nf, M, lmk));
+  if (gate) RET_IF(mesh_vertex_normals_check(who, verts, faces, inc_ptr, inc_face, F, V, Nf, normals, bad));
+  for (int i = 0; i < Fs; ++i)
+    RET_IF(mesh_closest_check(who, verts, scan_verts, scan_faces, Fs == 1 ? (int)std::min<long long>((long long)F * V, 0x7fffffff) : V,
+                              scan_vptr[i + 1] - scan_vptr[i], scan_fptr[i + 1] - scan_fptr[i], cos_min, max_dist2, 0, key, corr_face, bary,
+                              corr_point, dist2));
+  RET_IF(morph_fit_data_corr_check(who, verts, corr_point, corr_face, lmk, target_lmk, target_lmk_frames, csr_ptr, csr_ent, lmk_bary, F, V, M,
+                                   n_ent, g_y, e_part, w_part, loss_history, matched_history));
+  RET_IF(morph_skin_bwd_check(who, g_y, weights, A, blend, basis, F, V, L, NB, J, g_b, part_a, part_c));
+  RET_IF(morph_pose_bwd_check(who, p, j_rest, A, j_dirs, parents, part_a, nchunk, part_c, nslab, F, NB, J, g, g, g));
+  RET_IF(morph_fit_update_check(who, p, g, m, v, lr, lam, p0, F, P, step0 + 1, beta1, beta2, eps));
+  hipStream_t s = S(stream);
+  int rc = 0;
+  const float *betas = p, *pose = p + NB, *transl = p + NB + 3 * J;
+  for (int it = 0; it < iters && !rc; ++it) {
+    rc = launch_morph_pose_ex(betas, P, pose, P, j_template, j_dirs, parents, F, NB, J, j_rest, rot, nullptr, joints, A, coef, s);
+    if (!rc) rc = launch_morph_skin_ex(basis, v_template, coef, weights, A, post, transl, P, F, V, L, J, verts, blend, s);
+    if (!rc && use_lmk) rc = launch_morph_landmarks(verts, faces, lmk_face, lmk_bary, F, V, Nf, M, lmk, s);
+    if (!rc && it % refresh == 0) {
+      if (gate) rc = launch_mesh_vertex_normals(verts, faces, inc_ptr, inc_face, F, V, Nf, normals, bad, s);
+      if (!rc && Fs == 1)  // a shared scan: every frame's vertices in one launch
+        rc = launch_mesh_closest_point(verts, gate ? normals : nullptr, scan_verts, scan_faces, F * V, scan_vptr[1], scan_fptr[1], cos_min,
+                                       max_dist2, 0, key, corr_face, bary, corr_point, dist2, s);
+      for (int f = 0; f < F && !rc && Fs != 1; ++f) {
+        const size_t o = (size_t)f * V;
+        rc = launch_mesh_closest_point(verts + o * 3, gate ? normals + o * 3 : nullptr, scan_verts + (size_t)scan_vptr[f] * 3,
+                                       scan_faces + (size_t)scan_fptr[f] * 3, V, scan_vptr[f + 1] - scan_vptr[f],
+                                       scan_fptr[f + 1] - scan_fptr[f], cos_min, max_dist2, 0, key + o, corr_face + o, bary + o * 3,
+                                       corr_point + o * 3, dist2 + o, s);
+      }
+    }
+    if (!rc)
+      rc = launch_morph_fit_data_corr(verts, corr_point, corr_face, vertex_weight, lmk, target_lmk, target_lmk_frames, lmk_weight, lmk_scale,
+                                      csr_ptr, csr_ent, lmk_bary, F, V, M, n_ent, g_y, e_part, w_part, loss_history + (size_t)it * F,
+                                      matched_history + (size_t)it * F, s);
     if (!rc) rc = launch_morph_skin_bwd(g_y, post, weights, A, blend, basis, F, V, L, J, g_b, part_a, part_c, s);
     if (!rc)
       rc = launch_morph_pose_bwd(pose, P, j_rest, A, j_dirs, parents, part_a, nchunk, part_c, nslab, nullptr, F, NB, J, g, P, g + NB, P,

@@ -26,6 +26,8 @@
 //   morph_fit_data_kernel   a thread per (vertex, frame): the residual, its weighted square and g_y with the landmark adjoint gathered
 //                           through the same table; the squares are summed per block of 256 vertices in the vertex phase's shape.
 //   morph_fit_energy_kernel one wave per frame: block partials and landmark squares, a lane-strided ascending sum and a butterfly.
+//   morph_fit_corr_*_kernel the same data term against correspondences (a target point per frame and vertex, or none): block sums of
+//                           the weighted squares and of the weights, one wave per frame for W_f, E_f and the matched count, then g_y.
 //   morph_fit_update_kernel a thread per (frame, parameter): Adam as torch.optim.Adam steps it; lr == 0 leaves p, m and v alone.
 #include "morph.h"
 
@@ -415,6 +417,101 @@ __global__ __launch_bounds__(64) void morph_fit_energy_kernel(const float* __res
   if (lane == 0) E[f] = fmaf(el, lmk_scale, ev * inv_vw_sum);
 }
 
+// The data term against correspondences (include/mvd.h: mvd_op_morph_fit_data_corr): a vertex counts iff corr_face >= 0, and only
+// then is its corr_point read.  Three launches, in morph_fit_data's summation shape.  Stats: per block of 256 vertices the sums of
+// w m |y - c|^2 and of w m.
+__global__ __launch_bounds__(BWD_T) void morph_fit_corr_stats_kernel(const float* __restrict__ verts, const float* __restrict__ corr_point,
+                                                                     const int* __restrict__ corr_face,
+                                                                     const float* __restrict__ vertex_weight, int F, int V,
+                                                                     float* __restrict__ e_part, float* __restrict__ w_part) {
+  __shared__ float s_red[2][BWD_T / 64];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int blk = blockIdx.x, f = blockIdx.y;
+  const int v = blk * MORPH_BWD_CHUNK + t;
+  float e = 0.0f, ws = 0.0f;
+  if (v < V && corr_face[(size_t)f * V + v] >= 0) {
+    const float* yp = verts + ((size_t)f * V + v) * 3;
+    const float* cp = corr_point + ((size_t)f * V + v) * 3;
+    const float r0 = yp[0] - cp[0], r1 = yp[1] - cp[1], r2 = yp[2] - cp[2];
+    ws = vertex_weight ? vertex_weight[v] : 1.0f;
+    e = ws * fmaf(r2, r2, fmaf(r1, r1, r0 * r0));
+  }
+  e = wave_sum(e), ws = wave_sum(ws);
+  if (lane == 0) s_red[0][w] = e, s_red[1][w] = ws;
+  __syncthreads();
+  if (t == 0) {
+    e_part[(size_t)blk * F + f] = ((s_red[0][0] + s_red[0][1]) + s_red[0][2]) + s_red[0][3];
+    w_part[(size_t)blk * F + f] = ((s_red[1][0] + s_red[1][1]) + s_red[1][2]) + s_red[1][3];
+  }
+}
+
+// one wave per frame: W_f and the squares out of the block partials, the matched count straight from corr_face, the landmark
+// squares; row nblk of w_part takes 1 / W_f (0 when W_f is not positive), which the gradient launch reads
+__global__ __launch_bounds__(64) void morph_fit_corr_energy_kernel(const float* __restrict__ e_part, float* __restrict__ w_part, int nblk,
+                                                                   const int* __restrict__ corr_face, const float* __restrict__ lmk,
+                                                                   const float* __restrict__ target_lmk, int target_lmk_frames,
+                                                                   const float* __restrict__ lmk_weight, float lmk_scale, int F, int V, int M,
+                                                                   float* __restrict__ E, int* __restrict__ n_matched) {
+  const int f = blockIdx.x, lane = threadIdx.x;
+  float ev = 0.0f, wv = 0.0f, el = 0.0f;
+  int cnt = 0;
+  for (int b = lane; b < nblk; b += 64) ev += e_part[(size_t)b * F + f], wv += w_part[(size_t)b * F + f];
+  for (int v = lane; v < V; v += 64) cnt += corr_face[(size_t)f * V + v] >= 0;
+  if (target_lmk) {
+    for (int m = lane; m < M; m += 64) {
+      const float* lp = lmk + ((size_t)f * M + m) * 3;
+      const float* tp = target_lmk + ((size_t)(target_lmk_frames == 1 ? 0 : f) * M + m) * 3;
+      const float r0 = lp[0] - tp[0], r1 = lp[1] - tp[1], r2 = lp[2] - tp[2];
+      el = fmaf(lmk_weight ? lmk_weight[m] : 1.0f, fmaf(r2, r2, fmaf(r1, r1, r0 * r0)), el);
+    }
+  }
+  ev = wave_sum(ev), wv = wave_sum(wv), el = wave_sum(el);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+  if (lane == 0) {
+    const float inv = wv > 0.0f ? 1.0f / wv : 0.0f;
+    w_part[(size_t)nblk * F + f] = inv;
+    E[f] = fmaf(el, lmk_scale, ev * inv);
+    n_matched[f] = cnt;
+  }
+}
+
+__global__ __launch_bounds__(BWD_T) void morph_fit_corr_grad_kernel(const float* __restrict__ verts, const float* __restrict__ corr_point,
+                                                                    const int* __restrict__ corr_face,
+                                                                    const float* __restrict__ vertex_weight, const float* __restrict__ inv_w,
+                                                                    const float* __restrict__ lmk, const float* __restrict__ target_lmk,
+                                                                    int target_lmk_frames, const float* __restrict__ lmk_weight,
+                                                                    float lmk_scale, const int* __restrict__ csr_ptr,
+                                                                    const int* __restrict__ csr_ent, const float* __restrict__ lmk_bary, int F,
+                                                                    int V, int M, int n_ent, float* __restrict__ g_y) {
+  const int f = blockIdx.y, v = blockIdx.x * MORPH_BWD_CHUNK + threadIdx.x;
+  if (v >= V) return;
+  float g[3] = {0.0f, 0.0f, 0.0f};
+  const float inv = inv_w[f];
+  if (corr_face[(size_t)f * V + v] >= 0 && inv != 0.0f) {
+    const float* yp = verts + ((size_t)f * V + v) * 3;
+    const float* cp = corr_point + ((size_t)f * V + v) * 3;
+    const float sc = 2.0f * (vertex_weight ? vertex_weight[v] : 1.0f) * inv;
+    g[0] = sc * (yp[0] - cp[0]), g[1] = sc * (yp[1] - cp[1]), g[2] = sc * (yp[2] - cp[2]);
+  }
+  if (target_lmk) {
+    int q0, q1;
+    csr_range(csr_ptr, v, n_ent, &q0, &q1);
+    for (int q = q0; q < q1; ++q) {
+      const int ent = csr_ent[q];
+      if ((unsigned)ent >= (unsigned)(3 * M)) continue;
+      const int m = ent / 3;
+      const float sc = lmk_bary[ent] * (2.0f * lmk_scale * (lmk_weight ? lmk_weight[m] : 1.0f));
+      const float* lp = lmk + ((size_t)f * M + m) * 3;
+      const float* tp = target_lmk + ((size_t)(target_lmk_frames == 1 ? 0 : f) * M + m) * 3;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) g[k] = fmaf(sc, lp[k] - tp[k], g[k]);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) g_y[((size_t)f * V + v) * 3 + k] = g[k];
+}
+
 // torch.optim.Adam's single-tensor step on g' = g + 2 lam (p - p0): m = lerp(m, g', 1 - beta1), v = v beta2 + (1 - beta2) g'^2,
 // p -= (lr / bias1) m / (sqrt(v) / sqrt(bias2) + eps), the two bias corrections in double as torch computes them on the host
 __global__ __launch_bounds__(BWD_T) void morph_fit_update_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -538,6 +635,41 @@ int launch_morph_fit_data(const float* verts, const float* target, int target_fr
   HIP_CHECK_RET(hipGetLastError());
   hipLaunchKernelGGL(morph_fit_energy_kernel, dim3(F), dim3(64), 0, s, e_part, nblk, target ? inv_vw_sum : 0.0f, lmk, target_lmk,
                      target_lmk_frames, lmk_weight, lmk_scale, F, M, E);
+  HIP_CHECK_RET(hipGetLastError());
+  return 0;
+}
+
+int morph_fit_data_corr_check(const char* who, const float* verts, const float* corr_point, const int* corr_face, const float* lmk,
+                              const float* target_lmk, int target_lmk_frames, const int* csr_ptr, const int* csr_ent, const float* lmk_bary,
+                              int F, int V, int M, int n_ent, const float* g_y, const float* e_part, const float* w_part, const float* E,
+                              const int* n_matched) {
+  if (!verts || !corr_point || !corr_face || !g_y || !e_part || !w_part || !E || !n_matched) return morph_fail(who, ": null argument");
+  if (F < 1 || V < 1) return morph_fail(who, ": F and V must be at least 1");
+  if (F > 65535) return morph_fail(who, ": at most 65535 frames");
+  if (target_lmk) {
+    if (!lmk || !csr_ptr || !csr_ent || !lmk_bary) return morph_fail(who, ": a landmark target needs landmarks, their table and weights");
+    if (M < 1 || n_ent < 1) return morph_fail(who, ": M and the entry count must be at least 1 with a landmark target");
+    if (target_lmk_frames != 1 && target_lmk_frames != F) return morph_fail(who, ": the landmark target must have 1 or F frames");
+    if (morph_too_big(F, M, 3)) return morph_fail(who, ": F M 3 must be below 2^31");
+  }
+  if (morph_too_big(F, V, 3)) return morph_fail(who, ": F V 3 must be below 2^31");
+  return 0;
+}
+
+int launch_morph_fit_data_corr(const float* verts, const float* corr_point, const int* corr_face, const float* vertex_weight, const float* lmk,
+                               const float* target_lmk, int target_lmk_frames, const float* lmk_weight, float lmk_scale, const int* csr_ptr,
+                               const int* csr_ent, const float* lmk_bary, int F, int V, int M, int n_ent, float* g_y, float* e_part,
+                               float* w_part, float* E, int* n_matched, hipStream_t s) {
+  const int nblk = morph_bwd_chunks(V);
+  hipLaunchKernelGGL(morph_fit_corr_stats_kernel, dim3(nblk, F), dim3(BWD_T), 0, s, verts, corr_point, corr_face, vertex_weight, F, V, e_part,
+                     w_part);
+  HIP_CHECK_RET(hipGetLastError());
+  hipLaunchKernelGGL(morph_fit_corr_energy_kernel, dim3(F), dim3(64), 0, s, e_part, w_part, nblk, corr_face, lmk, target_lmk,
+                     target_lmk_frames, lmk_weight, lmk_scale, F, V, M, E, n_matched);
+  HIP_CHECK_RET(hipGetLastError());
+  hipLaunchKernelGGL(morph_fit_corr_grad_kernel, dim3(nblk, F), dim3(BWD_T), 0, s, verts, corr_point, corr_face, vertex_weight,
+                     w_part + (size_t)nblk * F, lmk, target_lmk, target_lmk_frames, lmk_weight, lmk_scale, csr_ptr, csr_ent, lmk_bary, F, V, M,
+                     n_ent, g_y);
   HIP_CHECK_RET(hipGetLastError());
   return 0;
 }

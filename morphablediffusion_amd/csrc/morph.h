@@ -44,6 +44,16 @@ int launch_morph_fit_data(const float* verts, const float* target, int target_fr
                           const float* lmk, const float* target_lmk, int target_lmk_frames, const float* lmk_weight, float lmk_scale,
                           const int* csr_ptr, const int* csr_ent, const float* lmk_bary, int F, int V, int M, int n_ent, float* g_y,
                           float* e_part, float* E, hipStream_t s);
+// the data term against correspondences: corr_point [F][V][3] is read only where corr_face [F][V] >= 0; w_part is [chunks + 1][F]
+// (the block sums of the weights, then 1 / W_f)
+int morph_fit_data_corr_check(const char* who, const float* verts, const float* corr_point, const int* corr_face, const float* lmk,
+                              const float* target_lmk, int target_lmk_frames, const int* csr_ptr, const int* csr_ent, const float* lmk_bary,
+                              int F, int V, int M, int n_ent, const float* g_y, const float* e_part, const float* w_part, const float* E,
+                              const int* n_matched);
+int launch_morph_fit_data_corr(const float* verts, const float* corr_point, const int* corr_face, const float* vertex_weight, const float* lmk,
+                               const float* target_lmk, int target_lmk_frames, const float* lmk_weight, float lmk_scale, const int* csr_ptr,
+                               const int* csr_ent, const float* lmk_bary, int F, int V, int M, int n_ent, float* g_y, float* e_part,
+                               float* w_part, float* E, int* n_matched, hipStream_t s);
 int morph_fit_update_check(const char* who, const float* p, const float* g, const float* m, const float* v, const float* lr,
                            const float* lam, const float* p0, int F, int P, int step, float beta1, float beta2, float eps);
 int launch_morph_fit_update(float* p, const float* g, float* m, float* v, const float* lr, const float* lam, const float* p0, int F, int P,

@@ -383,6 +383,52 @@ def op_mesh_render_uv(xy, key, face_id, faces, face_uv, uv, texture, background=
     return images
 
 
+# ---- closest point on a mesh (include/mvd.h: mvd_op_mesh_closest_point; csrc/k_closest.hip): context-free.
+def mesh_closest_slabs(Q, Nf, lib=None):
+    """mvd_mesh_closest_slabs: the slab count op_mesh_closest_point plans for Q queries against Nf faces (a host function)."""
+    return int((lib or L.load()).mvd_mesh_closest_slabs(int(Q), int(Nf)))
+
+
+def op_mesh_closest_point(queries, verts, faces, query_normals=None, cos_min=0.0, max_dist2=float("inf"), slabs=0, device=None, lib=None):
+    """mvd_op_mesh_closest_point on ``device`` (default: queries'): queries [Q,3], verts [Nv,3] float, faces [Nf,3] int32 (a point
+    cloud: faces (i, i, i)), query_normals [Q,3] float or None (no normal gate), max_dist2 = +inf for no distance gate, slabs = 0 for
+    the planned count.  Returns a dict of device tensors: key [Q] int64 (the bits of the uint64 key), face [Q] int32 (-1: no
+    match), bary [Q,3], point [Q,3], dist2 [Q] float32 (+inf: no match)."""
+    who = "op_mesh_closest_point"
+    for name, t in (("queries", queries), ("verts", verts)) + ((("query_normals", query_normals),) if query_normals is not None else ()):
+        if not torch.is_tensor(t) or not t.is_floating_point() or t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+            raise ValueError(f"{who}: {name} must be a float tensor [n,3] with n >= 1, got {getattr(t, 'dtype', type(t))} "
+                             f"{tuple(getattr(t, 'shape', ()))}")
+    _i32("faces", faces, (None, 3), who)
+    Q, Nv, Nf = queries.shape[0], verts.shape[0], faces.shape[0]
+    if Nf < 1:
+        raise ValueError(f"{who}: at least one face is needed")
+    if query_normals is not None and query_normals.shape[0] != Q:
+        raise ValueError(f"{who}: query_normals must be [{Q},3], got {tuple(query_normals.shape)}")
+    if 3 * max(Q, Nv, Nf) >= 2 ** 31:
+        raise ValueError(f"{who}: needs 3 Q, 3 Nv and 3 Nf below 2^31, got (Q, Nv, Nf) = {(Q, Nv, Nf)}")
+    cos_min, max_dist2, slabs = float(cos_min), float(max_dist2), int(slabs)
+    if not max_dist2 > 0.0:
+        raise ValueError(f"{who}: max_dist2 must be positive (inf: no gate), got {max_dist2}")
+    if not -1.0 <= cos_min <= 1.0:
+        raise ValueError(f"{who}: cos_min must be in [-1, 1], got {cos_min}")
+    if slabs < 0:
+        raise ValueError(f"{who}: slabs must be 0 (planned) or a positive count, got {slabs}")
+    dev = queries.device if device is None else device
+    q, v = _f32(queries, dev), _f32(verts, dev)
+    qn = None if query_normals is None else _f32(query_normals, dev)
+    faces = faces.detach().to(dev).contiguous()
+    lib = lib or L.load()
+    nan = float("nan")
+    out = {"key": torch.zeros((Q,), device=dev, dtype=torch.int64), "face": torch.full((Q,), -2, device=dev, dtype=torch.int32),
+           "bary": torch.full((Q, 3), nan, device=dev), "point": torch.full((Q, 3), nan, device=dev), "dist2": torch.full((Q,), nan, device=dev)}
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_mesh_closest_point(L.ptr(q), L.ptr(qn), L.ptr(v), L.ptr(faces), Q, Nv, Nf, cos_min, max_dist2, slabs,
+                                              L.ptr(out["key"]), L.ptr(out["face"]), L.ptr(out["bary"]), L.ptr(out["point"]),
+                                              L.ptr(out["dist2"]), _stream()))
+    return out
+
+
 # ---- the morphable-model forward (include/mvd.h: mvd_op_morph_pose / _skin / _landmarks; csrc/k_morph.hip): context-free.
 MORPH_MAX_JOINTS = 64
 
@@ -752,6 +798,53 @@ def op_morph_fit_data(verts, target=None, vertex_weight=None, lmk=None, target_l
     return E, g_y
 
 
+def _corr_args(who, F, V, vertex_weight, lmk, target_lmk, lmk_weight, lmk_lambda, csr, dev):
+    """The correspondence data term's arguments checked and on the device: (vw, lmk, target_lmk, frames, lw, lmk_scale, csr_ptr,
+    csr_ent, lmk_bary, M, n_ent).  The vertex normaliser is the device's (it depends on what matched); the landmarks' is taken here."""
+    vw = None
+    if vertex_weight is not None:
+        _float_arg(who, "vertex_weight", vertex_weight, (V,))
+        vw = _f32(vertex_weight, dev)
+        if not (float(vw.min()) >= 0.0 and float(vw.double().sum()) < float("inf")):
+            raise ValueError(f"{who}: vertex_weight must be non-negative and finite")
+    if target_lmk is None:
+        if lmk_weight is not None:
+            raise ValueError(f"{who}: landmark_weight without target landmarks")
+        if F > 65535 or F * V * 3 >= 2 ** 31:
+            raise ValueError(f"{who}: at most 65535 frames and F V 3 below 2^31, got F = {F}, V = {V}")
+        return vw, None, None, 1, None, 0.0, None, None, None, 0, 0
+    _, _, _, _, lm, tl, tlf, lw, scale, cp, ce, bc, M, n_ent = _fit_data_args(who, F, V, None, None, lmk, target_lmk, lmk_weight, lmk_lambda,
+                                                                             csr, dev)
+    return vw, lm, tl, tlf, lw, scale, cp, ce, bc, M, n_ent
+
+
+def op_morph_fit_data_corr(verts, corr_point, corr_face, vertex_weight=None, lmk=None, target_lmk=None, lmk_weight=None, lmk_lambda=1.0,
+                           csr=None, device=None, lib=None):
+    """mvd_op_morph_fit_data_corr on ``device`` (default: verts'): verts, corr_point [F,V,3] float, corr_face [F,V] int32 (as
+    op_mesh_closest_point returns point and face for the vertices as queries; < 0 = no match, and that corr_point is never
+    read); the landmark arguments of op_morph_fit_data.  E_f = sum_v w m |y - c|^2 / W_f + the landmark term, W_f = sum_v w m.
+    Returns (E [F], g_y [F,V,3], n_matched [F] int32)."""
+    who = "op_morph_fit_data_corr"
+    _float_arg(who, "verts", verts, (None, None, 3))
+    F, V = verts.shape[:2]
+    _float_arg(who, "corr_point", corr_point, (F, V, 3))
+    _i32("corr_face", corr_face, (F, V), who)
+    dev = verts.device if device is None else device
+    vw, lm, tl, tlf, lw, scale, cp, ce, bc, M, n_ent = _corr_args(who, F, V, vertex_weight, lmk, target_lmk, lmk_weight, lmk_lambda, csr, dev)
+    y, c, cf = _f32(verts, dev), _f32(corr_point, dev), corr_face.detach().to(dev).contiguous()
+    lib = lib or L.load()
+    nan = float("nan")
+    g_y, E = torch.full((F, V, 3), nan, device=dev), torch.full((F,), nan, device=dev)
+    nblk = morph_bwd_counts(V, lib)[0]
+    e_part, w_part = torch.full((nblk, F), nan, device=dev), torch.full((nblk + 1, F), nan, device=dev)
+    n_matched = torch.full((F,), -1, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_morph_fit_data_corr(L.ptr(y), L.ptr(c), L.ptr(cf), L.ptr(vw), L.ptr(lm), L.ptr(tl), tlf, L.ptr(lw), scale,
+                                               L.ptr(cp), L.ptr(ce), L.ptr(bc), F, V, M, n_ent, L.ptr(g_y), L.ptr(e_part), L.ptr(w_part),
+                                               L.ptr(E), L.ptr(n_matched), _stream()))
+    return E, g_y, n_matched
+
+
 ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8  # torch.optim.Adam's defaults
 
 
@@ -828,6 +921,102 @@ def morph_fit_run(model, p, m, v, lr, lam, p0, iters, target=None, vertex_weight
                                       inv_vw, L.ptr(tl), tlf, L.ptr(lw), scale, L.ptr(p), L.ptr(m), L.ptr(v), L.ptr(lrd), L.ptr(lamd),
                                       L.ptr(p0d), iters, step0, b1, b2, eps, L.ptr(ws), n_ws, L.ptr(hist), _stream()))
     return hist
+
+
+def scan_args(who, scans, F):
+    """``scans``: a list of (verts [n,3] float, faces [k,3] int32) tensors, one shared or one per frame -> (scan_verts [sum n,3],
+    scan_faces [sum k,3], vptr, fptr as host lists [Fs+1]); face indices stay local to their scan."""
+    if not isinstance(scans, (list, tuple)) or len(scans) not in (1, F):
+        raise ValueError(f"{who}: one scan, or one per frame (F = {F}), got {len(scans) if isinstance(scans, (list, tuple)) else type(scans)}")
+    vptr, fptr = [0], [0]
+    for i, sc in enumerate(scans):
+        if not isinstance(sc, (list, tuple)) or len(sc) != 2:
+            raise ValueError(f"{who}: scan {i} must be a (verts, faces) pair")
+        sv, sf = sc
+        if not torch.is_tensor(sv) or not sv.is_floating_point() or sv.dim() != 2 or sv.shape[1] != 3 or sv.shape[0] < 1:
+            raise ValueError(f"{who}: the vertices of scan {i} must be a float tensor [n,3] with n >= 1")
+        _i32(f"the faces of scan {i}", sf, (None, 3), who)
+        if sf.shape[0] < 1:
+            raise ValueError(f"{who}: scan {i} has no face (a point cloud is passed as faces (i, i, i))")
+        if 3 * max(sv.shape[0], sf.shape[0]) >= 2 ** 31:
+            raise ValueError(f"{who}: scan {i} is too large: 3 Nv and 3 Nf must be below 2^31")
+        vptr.append(vptr[-1] + sv.shape[0])
+        fptr.append(fptr[-1] + sf.shape[0])
+    if 3 * max(vptr[-1], fptr[-1]) >= 2 ** 31:
+        raise ValueError(f"{who}: the scans together are too large: 3 Nv and 3 Nf must be below 2^31")
+    return vptr, fptr
+
+
+def morph_fit_scan_run(model, p, m, v, lr, lam, p0, iters, scans, incidence=None, normal_cos=None, max_dist2=float("inf"), refresh=1,
+                       vertex_weight=None, target_lmk=None, lmk_weight=None, lmk_lambda=1.0, post=None, step0=0, betas=ADAM_BETAS,
+                       eps=ADAM_EPS, lib=None):
+    """mvd_morph_fit_scan_run: morph_fit_run's loop with the target replaced by the closest points of a scan, found again every
+    ``refresh`` iterations.  scans: a list of (verts, faces) device or host tensors, one shared or one per frame (scan_args).
+    normal_cos: None (no normal gate) or cos_min, which needs the model's faces and incidence = (inc_ptr, inc_face) of them
+    (mesh.face_incidence).  Returns (loss_history [iters,F], matched_history [iters,F] int32, corr_face [F,V] int32)."""
+    who = "morph_fit_scan_run"
+    F, P = _fit_update_args(who, p, m, v, lr, lam, p0)
+    V, NB, J = model.v_template.shape[0], model.j_dirs.shape[0], model.weights.shape[1]
+    if P != NB + 3 * J + 3:
+        raise ValueError(f"{who}: p must have P = NB + 3 J + 3 = {NB + 3 * J + 3} columns, got {P}")
+    dev = p.device
+    if model.basis.device != dev:
+        raise ValueError(f"{who}: the model is on {model.basis.device}, the parameters on {dev}")
+    iters, step0, refresh, b1, b2, eps = int(iters), int(step0), int(refresh), float(betas[0]), float(betas[1]), float(eps)
+    if iters < 1 or step0 < 0 or iters * F >= 2 ** 31 or not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0 and eps > 0.0):
+        raise ValueError(f"{who}: iters must be at least 1 (iters F < 2^31), step0 at least 0, betas in [0, 1), eps positive")
+    if refresh < 1:
+        raise ValueError(f"{who}: refresh must be at least 1, got {refresh}")
+    max_dist2 = float(max_dist2)
+    if not max_dist2 > 0.0:
+        raise ValueError(f"{who}: max_dist2 must be positive (inf: no gate), got {max_dist2}")
+    gate = normal_cos is not None
+    cos_min = float(normal_cos) if gate else 0.0
+    if not -1.0 <= cos_min <= 1.0:
+        raise ValueError(f"{who}: normal_cos must be in [-1, 1], got {cos_min}")
+    ip = ic = None
+    if gate:
+        if model.faces is None or incidence is None:
+            raise ValueError(f"{who}: the normal gate needs the model's faces and their incidence table")
+        ip, ic = incidence
+        _i32("inc_ptr", ip, (V + 1,), who)
+        _i32("inc_face", ic, (3 * model.faces.shape[0],), who)
+    if post is not None:
+        _float_arg(who, "post", post, (3, 4))
+    vptr, fptr = scan_args(who, scans, F)
+    use_lmk = target_lmk is not None
+    csr = (model.csr_ptr, model.csr_ent, model.lmk_bary) if use_lmk and getattr(model, "csr_ptr", None) is not None else None
+    lmk_stub = torch.empty((F, model.lmk_bary.shape[0], 3), device=dev) if csr is not None else None  # shape check only
+    vw, _, tl, tlf, lw, scale, cp, ce, bc, M, n_ent = _corr_args(who, F, V, vertex_weight, lmk_stub, target_lmk, lmk_weight, lmk_lambda, csr,
+                                                                dev)
+    par = morph_parents(who, model.parents, J)
+    lrd, lamd, p0d = (_f32(t, dev) for t in (lr, lam, p0))
+    ps = None if post is None else _f32(post, dev)
+    sv = torch.cat([_f32(a, dev) for a, _ in scans])
+    sf = torch.cat([b.detach().to(dev) for _, b in scans]).contiguous()
+    if gate:
+        ip, ic = (t.detach().to(dev).contiguous() for t in (ip, ic))
+    lib = lib or L.load()
+    n_ws_c = C.c_int64(0)
+    L.check(lib.mvd_morph_fit_scan_workspace(F, V, NB, J, M, C.addressof(n_ws_c)))
+    n_ws = int(n_ws_c.value)
+    ws = torch.full((n_ws,), float("nan"), device=dev)
+    hist = torch.full((iters, F), float("nan"), device=dev)
+    matched = torch.full((iters, F), -1, device=dev, dtype=torch.int32)
+    corr_face = torch.full((F, V), -2, device=dev, dtype=torch.int32)
+    par_c = (C.c_int32 * J)(*par)
+    Fs = len(scans)
+    vptr_c, fptr_c = (C.c_int32 * (Fs + 1))(*vptr), (C.c_int32 * (Fs + 1))(*fptr)
+    fc = model.faces if (use_lmk or gate) else None
+    lf = model.lmk_face if use_lmk else None
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_morph_fit_scan_run(
+            L.ptr(model.basis), L.ptr(model.v_template), L.ptr(model.weights), L.ptr(model.j_template), L.ptr(model.j_dirs),
+            C.addressof(par_c), L.ptr(ps), L.ptr(fc), L.ptr(lf), L.ptr(bc), L.ptr(cp), L.ptr(ce), L.ptr(ip), L.ptr(ic), F, V, NB, J,
+            0 if fc is None else fc.shape[0], M, n_ent, L.ptr(sv), L.ptr(sf), C.addressof(vptr_c), C.addressof(fptr_c), Fs, int(gate), cos_min,
+            max_dist2, refresh, L.ptr(vw), L.ptr(tl), tlf, L.ptr(lw), scale, L.ptr(p), L.ptr(m), L.ptr(v), L.ptr(lrd), L.ptr(lamd),
+            L.ptr(p0d), iters, step0, b1, b2, eps, L.ptr(ws), n_ws, L.ptr(hist), L.ptr(matched), L.ptr(corr_face), _stream()))
+    return hist, matched, corr_face
 
 
 # ---- the sparse voxel CNN's kernels one at a time (include/mvd.h: mvd_op_sparse_conv ...): context-free like op_train_loss.
@@ -1522,6 +1711,10 @@ class Engine:
     def op_mesh_render_uv(self, xy, key, face_id, faces, face_uv, uv, texture, **kw):
         """mvd_op_mesh_render_uv on this engine's device: see the module-level op_mesh_render_uv."""
         return op_mesh_render_uv(xy, key, face_id, faces, face_uv, uv, texture, device=self.device, lib=self.lib, **kw)
+
+    def op_mesh_closest_point(self, queries, verts, faces, **kw):
+        """mvd_op_mesh_closest_point on this engine's device: see the module-level op_mesh_closest_point."""
+        return op_mesh_closest_point(queries, verts, faces, device=self.device, lib=self.lib, **kw)
 
     # the sparse voxel CNN's kernels one at a time: the module-level functions above on this engine's device and library
     def op_sparse_conv(self, x, nbr, w, layout, form="mfma", scale=None, shift=None):

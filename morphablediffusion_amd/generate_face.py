@@ -33,6 +33,8 @@ Differences, all outside the denoising path and stated here:
     ``<input>_<exp>.png`` as before, several write ``<input>_<exp>_fNN.png`` each (and the --export_mesh / --mesh_overlay /
     --gt_dir files with the same ``_fNN``); frames are sampled --frame_batch at a time.  With none of these flags the program
     does exactly what it did without them.
+  * --flame_model MODEL --fit_scan SCAN.{ply,obj} (not reference flags; mesh.closest_point, csrc/k_closest.hip) does the same
+    against a scan of any topology, with --fit_scan_max_dist / _normal_cos / _refresh / _landmarks.
   * --flame_model MODEL --fit_mesh MESH.{ply,obj} (not reference flags; morphable.py, csrc/k_morph_bwd.hip) fit the model's
     parameters to a mesh of the model's topology, in the model's frame (what metrical-tracker exports), with Adam on the device
     (--fit_iters, --fit_lr), and write ``<input>_<exp>_fit.npz`` (shape, expression, global_pose, neck, jaw, eyes, transl) and
@@ -194,6 +196,19 @@ def build_parser():
                    help="not a reference flag: a mesh file of the model's topology; --flame_model's parameters are fitted to it")
     p.add_argument("--fit_iters", type=int, default=300, help="not a reference flag: Adam iterations of --fit_mesh")
     p.add_argument("--fit_lr", type=float, default=0.05, help="not a reference flag: Adam's learning rate for --fit_mesh")
+    p.add_argument("--fit_scan", type=str, default=None,
+                   help="not a reference flag: a scan of ANY topology (.ply / .obj; no faces: a point cloud); --flame_model's "
+                        "parameters are fitted to it through closest points (--fit_iters, --fit_lr apply)")
+    p.add_argument("--fit_scan_max_dist", type=float, default=None,
+                   help="not a reference flag: --fit_scan ignores correspondences farther than this (the scan's units)")
+    p.add_argument("--fit_scan_normal_cos", type=float, default=None,
+                   help="not a reference flag: --fit_scan admits only scan faces whose normal makes at least this cosine with the "
+                        "model vertex's")
+    p.add_argument("--fit_scan_refresh", type=int, default=1,
+                   help="not a reference flag: --fit_scan looks for closest points every this many iterations")
+    p.add_argument("--fit_scan_landmarks", type=str, default=None,
+                   help="not a reference flag: an .npz with `landmarks` [M,3], the scan's 3-D landmarks in the order of the model's "
+                        "embedding: a landmark-only fit of global pose and translation seeds --fit_scan, and the term stays on")
     p.add_argument("--flame_n_shape", type=int, default=None,
                    help="not a reference flag: identity columns of the model's shapedirs to keep (MICA: 300; default: all)")
     p.add_argument("--flame_n_exp", type=int, default=None,
@@ -208,20 +223,34 @@ FLAME_FILE_KEYS = FLAME_PARAM_KEYS + ("transl",)  # what a parameter file may ho
 def parse_args(argv=None):
     """build_parser().parse_args plus the rules between the flags: --mesh alone as ever; --flame_model and --flame_params go
     together and replace --mesh; --neutral_params and --frames > 1 go together and need them; --fit_mesh needs --flame_model,
-    excludes --mesh and --neutral_params, and with --flame_params takes the place of the neutral end."""
+    excludes --mesh and --neutral_params, and with --flame_params takes the place of the neutral end; --fit_scan follows
+    --fit_mesh's rules and excludes it."""
     p = build_parser()
     flags = p.parse_args(argv)
-    if flags.fit_mesh:
+    scan_only = [n for n in ("fit_scan_max_dist", "fit_scan_normal_cos", "fit_scan_landmarks") if getattr(flags, n) is not None]
+    if (scan_only or flags.fit_scan_refresh != 1) and not flags.fit_scan:
+        p.error("--fit_scan_max_dist, --fit_scan_normal_cos, --fit_scan_refresh and --fit_scan_landmarks need --fit_scan")
+    if flags.fit_scan and flags.fit_mesh:
+        p.error("--fit_scan excludes --fit_mesh (one target)")
+    if flags.fit_scan:
+        if flags.fit_scan_max_dist is not None and not flags.fit_scan_max_dist > 0:
+            p.error("--fit_scan_max_dist must be positive")
+        if flags.fit_scan_normal_cos is not None and not -1.0 <= flags.fit_scan_normal_cos <= 1.0:
+            p.error("--fit_scan_normal_cos must be in [-1, 1]")
+        if flags.fit_scan_refresh < 1:
+            p.error("--fit_scan_refresh must be at least 1")
+    if flags.fit_mesh or flags.fit_scan:
+        name = "--fit_mesh" if flags.fit_mesh else "--fit_scan"
         if not flags.flame_model:
-            p.error("--fit_mesh needs --flame_model")
+            p.error(f"{name} needs --flame_model")
         if flags.mesh or flags.neutral_params:
-            p.error("--fit_mesh excludes --mesh and --neutral_params (the fit is the neutral end)")
+            p.error(f"{name} excludes --mesh and --neutral_params (the fit is the neutral end)")
         if flags.fit_iters < 1 or not flags.fit_lr > 0:
             p.error("--fit_iters must be at least 1 and --fit_lr positive")
         if flags.frames < 1 or flags.frame_batch < 1:
             p.error("--frames and --frame_batch must be at least 1")
         if flags.frames > 1 and not flags.flame_params:
-            p.error("--frames K > 1 with --fit_mesh needs --flame_params (the other end of the sweep)")
+            p.error(f"--frames K > 1 with {name} needs --flame_params (the other end of the sweep)")
         return flags
     flame = [flags.flame_model, flags.flame_params]
     if not any(flame) and (flags.neutral_params or flags.frames != 1 or flags.frame_batch != 1):
@@ -265,14 +294,47 @@ def fit_to_mesh(fm, flags, stem):
     return params
 
 
+def fit_to_scan(fm, flags, stem):
+    """--fit_scan: the model's parameters fitted to a scan of any topology in the model's frame (MorphableModel.fit_flame_scan).
+    With --fit_scan_landmarks a landmark-only fit of global pose and translation comes first and seeds the start.  Writes
+    <stem>_fit.npz and <stem>_fit.json (iterations, matched share, model-to-scan rms, scan-to-mesh statistics); returns {key:
+    float64 vector} over FLAME_FILE_KEYS."""
+    from . import mesh as MS
+    sv, sf = MS.read_mesh(flags.fit_scan)
+    sf = sf if sf is not None and len(sf) else None
+    init, tl = None, None
+    if flags.fit_scan_landmarks:
+        with np.load(flags.fit_scan_landmarks, allow_pickle=False) as z:
+            if "landmarks" not in z.files:
+                raise ValueError(f"{flags.fit_scan_landmarks}: no array named 'landmarks'")
+            tl = torch.from_numpy(np.asarray(z["landmarks"], dtype=np.float32))[None]
+        rigid = fm.fit_flame(target_landmarks=tl, free=("global_pose", "transl"), iters=flags.fit_iters, lr=flags.fit_lr)
+        init = {"global_pose": rigid["global_pose"].cpu().numpy(), "transl": rigid["transl"].cpu().numpy()}
+    fit = fm.fit_flame_scan(torch.from_numpy(sv), None if sf is None else torch.from_numpy(sf), target_landmarks=tl, init=init,
+                            max_dist=flags.fit_scan_max_dist, normal_cos=flags.fit_scan_normal_cos, refresh=flags.fit_scan_refresh,
+                            iters=flags.fit_iters, lr=flags.fit_lr)
+    params = {k: fit[k][0].cpu().numpy().astype(np.float64) for k in FLAME_FILE_KEYS}
+    np.savez(f"{stem}_fit.npz", **params)
+    report = {"scan": str(flags.fit_scan), "scan_vertices": int(sv.shape[0]), "scan_faces": 0 if sf is None else int(sf.shape[0]),
+              "vertices": int(fm.V), "iterations": int(flags.fit_iters), "lr": float(flags.fit_lr), "refresh": int(flags.fit_scan_refresh),
+              "matched": float(fit["matched"][0]) / fm.V, "rms": float(fit["rms"][0]), "loss_first": float(fit["loss_history"][0, 0]),
+              "loss_last": float(fit["loss_history"][-1, 0])}
+    if fm.faces is not None:  # the standard 3-D error: every scan vertex against the fitted surface
+        s2m = MS.surface_distance(sv, fit["vertices"][0], fm.faces, max_dist=flags.fit_scan_max_dist)
+        report["scan_to_mesh"] = {k: s2m[k] for k in ("mean", "rms", "median", "p90", "max", "matched")}
+    with open(f"{stem}_fit.json", "w") as f:
+        json.dump(report, f, indent=2)
+    return params
+
+
 def flame_frames(flags, device, stem=None):
     """The conditioning meshes of --flame_model with --flame_params and / or --fit_mesh: (verts [F,Nv,3] on the device in the
     frame of batch["vertices"], model-frame vertices [F,Nv,3] as a mesh file would store them, faces [Nf,3] or None).  stem:
     where --fit_mesh writes its files (<stem>_fit.npz / .json)."""
     from . import morphable as MM
     fm = MM.MorphableModel.load(flags.flame_model, n_shape=flags.flame_n_shape, n_exp=flags.flame_n_exp, device=device)
-    if getattr(flags, "fit_mesh", None):
-        params = fit_to_mesh(fm, flags, stem)
+    if getattr(flags, "fit_mesh", None) or getattr(flags, "fit_scan", None):
+        params = fit_to_mesh(fm, flags, stem) if getattr(flags, "fit_mesh", None) else fit_to_scan(fm, flags, stem)
         if flags.flame_params:
             given = load_flame_params(flags.flame_params)
             if any(v.ndim > 1 for v in given.values()):

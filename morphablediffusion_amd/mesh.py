@@ -13,6 +13,10 @@ UV texture atlases (mvd_op_mesh_vertex_normals / _texel_bake / _texture_dilate /
   bake_texture      the views fused per texel, then dilated              render_textured  the textured mesh in any cameras
   reprojection_metrics   the atlas rendered back, scored by image_metrics   write_obj     OBJ + MTL + PNG
 
+Closest points and surface distances (mvd_op_mesh_closest_point, csrc/k_closest.hip):
+
+  closest_point     per point: face, barycentrics, point, distance        surface_distance   scan-to-mesh distance and its statistics
+
 What is exact: everything after the projection (coverage, depth order, visibility, n_seen) is integer arithmetic.  What is not
 computed: UV unwrapping beyond triangle_atlas, mip-maps, seam-aware blending across charts, the input photo as a 17th view (its
 camera is not in the batch).  The FLAME mesh ends at the head, so colour on hair and shoulders is not recovered."""
@@ -559,3 +563,85 @@ def write_obj(path, verts, faces, uv, face_uv, texture, texture_name=None):
         fh.write("usemtl baked\n")
         fh.writelines(f"f {i[0] + 1}/{j[0] + 1} {i[1] + 1}/{j[1] + 1} {i[2] + 1}/{j[2] + 1}\n" for i, j in zip(f.tolist(), t.tolist()))
     return {"obj": path, "mtl": stem + ".mtl", "png": os.path.join(folder, png)}
+
+
+# ---- closest points and surface distances (include/mvd.h: mvd_op_mesh_closest_point)
+def _cloud_faces(n):
+    """A point cloud as a mesh: faces (i, i, i), whose closest point is the vertex itself."""
+    return torch.arange(n, dtype=torch.int32)[:, None].expand(n, 3).contiguous()
+
+
+def _points_arg(name, a):
+    t = _as_tensor(a, torch.float32)
+    if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+        raise ValueError(f"{name} must be [n,3] with n >= 1, got {tuple(t.shape)}")
+    return t
+
+
+def closest_point(points, verts, faces, normals=None, cos_min=None, max_dist=None):
+    """For every point [Q,3] the closest point of the mesh verts [Nv,3] / faces [Nf,3] (``faces=None``: verts is a point cloud), by
+    exhaustive search on the device (mvd_op_mesh_closest_point: exact, smallest distance, ties to the smallest face index).
+    ``normals`` [Q,3] with ``cos_min`` (default 0) admits only faces whose normal makes a cosine >= cos_min with the point's; beyond
+    ``max_dist`` a point has no match.  Returns a dict of device tensors: face [Q] int32 (-1: no match), bary [Q,3], point [Q,3],
+    dist2 [Q], dist [Q] (+inf: no match), matched [Q] bool."""
+    pts, v = _points_arg("points", points), _points_arg("verts", verts)
+    if faces is None:
+        f = _cloud_faces(v.shape[0])
+    else:
+        _, f = _mesh_args(v, faces)
+    if cos_min is not None and normals is None:
+        raise ValueError("cos_min needs the points' normals")
+    nrm = None
+    if normals is not None:
+        nrm = _points_arg("normals", normals)
+        if nrm.shape[0] != pts.shape[0]:
+            raise ValueError(f"normals must be [{pts.shape[0]},3], got {tuple(nrm.shape)}")
+    cos_min = 0.0 if cos_min is None else float(cos_min)
+    if not -1.0 <= cos_min <= 1.0:
+        raise ValueError(f"cos_min must be in [-1, 1], got {cos_min}")
+    if max_dist is not None and not float(max_dist) > 0.0:
+        raise ValueError(f"max_dist must be positive, got {max_dist}")
+    # the gate compares float32 squares: the float32 nearest to max_dist^2
+    max_dist2 = float("inf") if max_dist is None else float(np.float32(float(max_dist) ** 2))
+    out = E.op_mesh_closest_point(pts, v, f, query_normals=nrm, cos_min=cos_min, max_dist2=max_dist2, device=_device_of(points, verts))
+    out.pop("key")
+    out["dist"] = out["dist2"].sqrt()
+    out["matched"] = out["face"] >= 0
+    return out
+
+
+def _quantile(sorted_values, q):
+    """numpy.percentile's default (linear interpolation between order statistics) of an ascending float64 tensor."""
+    pos = q * (sorted_values.numel() - 1)
+    lo = int(pos)
+    hi = min(lo + 1, sorted_values.numel() - 1)
+    return float(sorted_values[lo] + (sorted_values[hi] - sorted_values[lo]) * (pos - lo))
+
+
+def distance_statistics(dist):
+    """mean / rms / median / p90 / max of the finite entries of dist (float64 on its device) and their share ``matched``; NaN
+    statistics when no entry is finite."""
+    d = dist.double()
+    ok = torch.isfinite(d)
+    d = d[ok].sort().values
+    n = d.numel()
+    if n == 0:
+        nan = float("nan")
+        return {"mean": nan, "rms": nan, "median": nan, "p90": nan, "max": nan, "matched": 0.0}
+    return {"mean": float(d.mean()), "rms": float((d * d).mean().sqrt()), "median": _quantile(d, 0.5), "p90": _quantile(d, 0.9),
+            "max": float(d[-1]), "matched": n / dist.numel()}
+
+
+def surface_distance(points, verts, faces, normals=None, cos_min=None, max_dist=None, symmetric=False, point_faces=None):
+    """Distance of every point [Q,3] to the mesh verts / faces (``closest_point``) and its statistics over the matched points:
+    {"dist" [Q] (device, +inf: no match), "mean", "rms", "median", "p90", "max", "matched" (their share)}.  With a scan's vertices as
+    ``points`` and the posed model as the mesh this is the scan-to-mesh distance of the 3-D benchmarks.  ``symmetric``: adds
+    "back", the same dict for the mesh's vertices against the points (as a surface with ``point_faces``, else as a cloud; no
+    normal gate in that direction), and "chamfer", the mean of the two means."""
+    fwd = closest_point(points, verts, faces, normals=normals, cos_min=cos_min, max_dist=max_dist)
+    out = dict(distance_statistics(fwd["dist"]), dist=fwd["dist"])
+    if symmetric:
+        back = closest_point(verts, points, point_faces, max_dist=max_dist)
+        out["back"] = dict(distance_statistics(back["dist"]), dist=back["dist"])
+        out["chamfer"] = 0.5 * (out["mean"] + out["back"]["mean"])
+    return out

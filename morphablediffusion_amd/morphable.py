@@ -13,7 +13,8 @@ vertices go straight into ``batch.build_batch`` / ``stack_batches`` / ``model.sa
 Units: FLAME's forward is in metres, and so are the mesh files of the reference pipeline, so ``unit_scale``
 defaults to 1.0.  The inverse is here too (csrc/k_morph_bwd.hip): ``vjp`` is the vector-Jacobian product of the forward,
 ``differentiable`` the same as a torch.autograd.Function, ``fit`` / ``fit_flame`` run Adam on the device against target vertices
-and 3-D landmarks.  Not here: the pose-dependent contour landmarks (vertex normals of a batch of frames: mesh.vertex_normals_device).
+and 3-D landmarks, ``fit_scan`` / ``fit_flame_scan`` against a scan of any topology (closest points, csrc/k_closest.hip).  Not here:
+the pose-dependent contour landmarks (vertex normals of a batch of frames: mesh.vertex_normals_device).
 
     fit = fm.fit_flame(target_vertices=mesh_vertices, free=("expression", "jaw"), prior={"shape": mica_shape})
 """
@@ -419,6 +420,137 @@ class MorphableModel:
         if self.J != len(FLAME_JOINTS):
             raise ValueError(f"{who}: a FLAME model has {len(FLAME_JOINTS)} joints, this one {self.J}")
         out = self.fit(target_vertices, target_landmarks, free=free, reg=reg, prior=prior, init=init, _who=who, **kw)
+        flat = torch.cat([out["betas"], out["pose"].reshape(out["betas"].shape[0], -1)], 1)
+        g = self.param_groups()
+        out.update({k: flat[:, g[k]].contiguous() for k in ("shape", "expression", "global_pose", "neck", "jaw", "eyes")})
+        return out
+
+    # ---- fitting to an unregistered scan: correspondences by closest point (engine.morph_fit_scan_run, csrc/k_closest.hip)
+    def _scan_list(self, who, scan_vertices, scan_faces):
+        """[(verts float32 [n,3], faces int32 [k,3])] host tensors: one scan or a list of them; faces None = a point cloud (i, i, i)."""
+        many = isinstance(scan_vertices, (list, tuple))
+        vs = list(scan_vertices) if many else [scan_vertices]
+        if scan_faces is None:
+            fs = [None] * len(vs)
+        elif many:
+            fs = list(scan_faces) if isinstance(scan_faces, (list, tuple)) else None
+            if fs is None or len(fs) != len(vs):
+                raise ValueError(f"{who}: a list of scans needs a list of as many scan_faces (entries may be None)")
+        else:
+            fs = [scan_faces]
+        if not vs:
+            raise ValueError(f"{who}: no scan given")
+        out = []
+        for i, (sv, sf) in enumerate(zip(vs, fs)):
+            sv = (sv.detach().cpu() if torch.is_tensor(sv) else torch.as_tensor(np.asarray(sv))).to(torch.float32)
+            if sv.dim() != 2 or sv.shape[1] != 3 or sv.shape[0] < 1:
+                raise ValueError(f"{who}: scan {i}: vertices must be [n,3] with n >= 1, got {tuple(sv.shape)}")
+            if sf is None:
+                sf = torch.arange(sv.shape[0], dtype=torch.int32)[:, None].expand(-1, 3)
+            else:
+                sf = sf.detach().cpu() if torch.is_tensor(sf) else torch.as_tensor(np.asarray(sf))
+                if sf.dim() != 2 or sf.shape[1] != 3 or sf.shape[0] < 1 or sf.is_floating_point():
+                    raise ValueError(f"{who}: scan {i}: faces must be integers [k,3] with k >= 1, got {sf.dtype} {tuple(sf.shape)}")
+                sf = sf.to(torch.int32)
+            out.append((sv.contiguous(), sf.contiguous()))
+        return out
+
+    def scan_distance(self, vertices, scans, normal_cos=None, max_dist=None, incidence=None):
+        """The closest point of the scan(s) for vertices [F,V,3] of this model (scan f for frame f, or the one scan for all), with
+        the gates of fit_scan: dict of face [F,V] int32 (-1: no match), point [F,V,3], dist2 [F,V], matched [F] (a count) and rms
+        [F]: the root mean square distance over the matched vertices (NaN where none matched)."""
+        F = vertices.shape[0]
+        dev = vertices.device
+        nrm = None
+        if normal_cos is not None:
+            nrm, _ = E.op_mesh_vertex_normals(vertices, self.faces, incidence[0], incidence[1], device=dev)
+        max_dist2 = float("inf") if max_dist is None else float(np.float32(float(max_dist) ** 2))
+        kw = dict(cos_min=0.0 if normal_cos is None else float(normal_cos), max_dist2=max_dist2, device=dev)
+        if len(scans) == 1:
+            o = E.op_mesh_closest_point(vertices.reshape(-1, 3), scans[0][0], scans[0][1],
+                                        query_normals=None if nrm is None else nrm.reshape(-1, 3), **kw)
+            outs = {k: o[k].reshape((F, self.V) + tuple(o[k].shape[1:])) for k in ("face", "point", "dist2")}
+        else:
+            per = [E.op_mesh_closest_point(vertices[f], scans[f][0], scans[f][1], query_normals=None if nrm is None else nrm[f], **kw)
+                   for f in range(F)]
+            outs = {k: torch.stack([o[k] for o in per]) for k in ("face", "point", "dist2")}
+        hit = outs["face"] >= 0
+        outs["matched"] = hit.sum(1).to(torch.int32)
+        total = torch.where(hit, outs["dist2"], torch.zeros_like(outs["dist2"])).double().sum(1)
+        outs["rms"] = (total / outs["matched"].double()).sqrt().float()  # 0 / 0 = NaN: nothing matched
+        return outs
+
+    def fit_scan(self, scan_vertices, scan_faces=None, target_landmarks=None, max_dist=None, normal_cos=None, refresh=1, vertex_weight=None,
+                 iters=300, lr=0.05, init=None, free=None, reg=None, prior=None, post=None, landmark_weight=None, lmk_lambda=1.0,
+                 fit_transl=True, frames=None, _who="MorphableModel.fit_scan"):
+        """``fit`` against a scan of ANY topology (raw scans, registrations in another topology, point clouds): every ``refresh``
+        iterations each model vertex takes the closest point of the scan as its target (an exhaustive, exact query on the device:
+        mesh.closest_point), optionally only among faces whose normal makes a cosine >= normal_cos with the vertex normal and
+        within max_dist; unmatched vertices drop out of the data term, E_f = sum_v w_v m_fv |y - c|^2 / sum_v w_v m_fv + the
+        landmark and penalty terms of ``fit``.  scan_vertices [n,3] with scan_faces [k,3] (None: a point cloud), or lists of them,
+        one scan per frame; ``frames``: how many frames share one scan (default: those of target_landmarks or init, else 1).
+        Returns fit's dict plus matched_history [iters,F] and, from a fresh query of the returned vertices with the same gates,
+        corr_face [F,V] (-1: no match), matched [F] and rms [F]: the root mean square model-to-scan surface distance over the
+        matched vertices.  The start matters as in any ICP: give init (or target_landmarks, whose term stays on) when the scan
+        is far from the model's rest pose."""
+        who = _who
+        lrv, lam, p0 = self.fit_vectors(lr, free, reg, prior, fit_transl, who)
+        scans = self._scan_list(who, scan_vertices, scan_faces)
+        tl = None if target_landmarks is None else (target_landmarks if torch.is_tensor(target_landmarks)
+                                                    else torch.as_tensor(np.asarray(target_landmarks)))
+        tl = tl[None] if tl is not None and tl.dim() == 2 else tl
+        if tl is not None:
+            if self.lmk_face is None:
+                raise ValueError(f"{who}: target_landmarks given, and the model has no landmark embedding")
+            M = self.lmk_face.shape[0]
+            if tl.dim() != 3 or tuple(tl.shape[1:]) != (M, 3) or tl.shape[0] < 1:
+                raise ValueError(f"{who}: target_landmarks must be [F,{M},3], got {tuple(tl.shape)}")
+        counts = [len(scans), 1 if tl is None else tl.shape[0], 1 if frames is None else int(frames)]
+        counts += [int(np.shape(val)[0]) for val in (init or {}).values() if val is not None and np.ndim(val) >= 2]
+        F = max(counts)
+        if F < 1 or any(c not in (1, F) for c in counts):
+            raise ValueError(f"{who}: scans, target_landmarks, init and frames must agree on the number of frames (or be one), got {counts}")
+        iters, refresh = int(iters), int(refresh)
+        if iters < 1 or refresh < 1:
+            raise ValueError(f"{who}: iters and refresh must be at least 1, got {iters} and {refresh}")
+        if max_dist is not None and not float(max_dist) > 0.0:
+            raise ValueError(f"{who}: max_dist must be positive, got {max_dist}")
+        if normal_cos is not None:
+            if not -1.0 <= float(normal_cos) <= 1.0:
+                raise ValueError(f"{who}: normal_cos must be in [-1, 1], got {normal_cos}")
+            if self.faces is None:
+                raise ValueError(f"{who}: normal_cos needs the model's faces (vertex normals)")
+        start = self._fit_init(who, init, F, p0, lrv)
+        if self.device.type != "cuda":
+            raise ValueError(f"{who}: the model is on {self.device}; the fitter runs on the GPU only (model.to('cuda:0'))")
+        dev = self.device
+        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+        incidence = None
+        if normal_cos is not None:
+            from .mesh import face_incidence
+            incidence = tuple(torch.from_numpy(a).to(dev) for a in face_incidence(self.faces, self.V))
+        scans = [(a.to(dev), b.to(dev)) for a, b in scans]
+        p = f32(start)
+        m, v = torch.zeros_like(p), torch.zeros_like(p)
+        max_dist2 = float("inf") if max_dist is None else float(np.float32(float(max_dist) ** 2))
+        hist, matched_hist, _ = E.morph_fit_scan_run(self, p, m, v, f32(lrv), f32(lam), f32(p0), iters, scans, incidence=incidence,
+                                                     normal_cos=normal_cos, max_dist2=max_dist2, refresh=refresh,
+                                                     vertex_weight=vertex_weight, target_lmk=tl, lmk_weight=landmark_weight,
+                                                     lmk_lambda=lmk_lambda, post=post)
+        NB, J = self.NB, self.J
+        out = {"betas": p[:, :NB].contiguous(), "pose": p[:, NB:NB + 3 * J].reshape(F, J, 3).contiguous(),
+               "transl": p[:, NB + 3 * J:].contiguous(), "loss_history": hist, "matched_history": matched_hist}
+        out["vertices"] = self.forward(out["betas"], out["pose"], post=post, transl=out["transl"])["vertices"]
+        fresh = self.scan_distance(out["vertices"], scans, normal_cos, max_dist, incidence)
+        out.update(corr_face=fresh["face"], matched=fresh["matched"], rms=fresh["rms"])
+        return out
+
+    def fit_flame_scan(self, scan_vertices, scan_faces=None, target_landmarks=None, free=None, reg=None, prior=None, init=None, **kw):
+        """``fit_scan`` in ``flame``'s names, as fit_flame is to fit.  Returns fit_scan's dict and the six FLAME parts [F,n]."""
+        who = "MorphableModel.fit_flame_scan"
+        if self.J != len(FLAME_JOINTS):
+            raise ValueError(f"{who}: a FLAME model has {len(FLAME_JOINTS)} joints, this one {self.J}")
+        out = self.fit_scan(scan_vertices, scan_faces, target_landmarks, free=free, reg=reg, prior=prior, init=init, _who=who, **kw)
         flat = torch.cat([out["betas"], out["pose"].reshape(out["betas"].shape[0], -1)], 1)
         g = self.param_groups()
         out.update({k: flat[:, g[k]].contiguous() for k in ("shape", "expression", "global_pose", "neck", "jaw", "eyes")})
