@@ -519,7 +519,8 @@ int mvd_op_mesh_closest_point(const float* queries, const float* query_normals, 
  *                 vertex index out of range is never dereferenced: that landmark is NaN.
  * Errors, which return before the first HIP call: a null pointer (but post, and pose_feature when J == 1); F, V, L, NB, M or
  * Nf < 1; J < 1 or J > 64; L != NB + 9 (J-1); a bad parents; F V 3 >= 2^31 (and F M 3, F J 12, NB J 3 likewise).
- * Not computed: the pose-dependent contour landmarks, vertex normals. */
+ * Not computed here: vertex normals (mvd_op_mesh_vertex_normals); the pose-dependent contour landmarks are mvd_op_morph_contour_*
+ * further down. */
 int mvd_op_morph_pose(const float* betas, const float* pose, const float* j_template, const float* j_dirs, const int32_t* parents, int F,
                       int NB, int J, float* j_rest, float* rot, float* pose_feature, float* joints, float* A, void* stream);
 int mvd_op_morph_skin(const float* basis, const float* v_template, const float* coef, const float* weights, const float* A,
@@ -637,6 +638,91 @@ int mvd_morph_fit_scan_run(const float* basis, const float* v_template, const fl
                            const float* lmk_weight, float lmk_scale, float* p, float* m, float* v, const float* lr, const float* lam,
                            const float* p0, int iters, int step0, float beta1, float beta2, float eps, float* workspace,
                            size_t workspace_floats, float* loss_history, int32_t* matched_history, int32_t* corr_face, void* stream);
+/* The 2-D multi-view landmark term, the per-view contour landmarks and their loop (csrc/k_morph_2d.hip, entries in
+ * csrc/c_api_morph.hip): landmarks projected into C calibrated views against detected key points in pixels, the reprojection term
+ * of the reference's third_party/metrical-tracker (tracker.py:405-412, 495-508), and its per-view sliding contour (flame/FLAME.py:
+ * 126-163).  The rules of the block above: fp32, every sum in an order fixed by indices alone, no atomics, two calls agree bit for
+ * bit, frame f of a batch equals the frame alone.  Cameras: K [Fc,C,3,3], RT [Fc,C,3,4] (world -> camera) with Fc = cam_frames, 1
+ * (shared by the frames) or F.
+ *   projection    exactly mvd_op_mesh_project's fp32 chain (one device function serves both): cam = R l + t, u = (K00 X + K01 Y) / Z
+ *                 + K02, v = K11 Y / Z + K12, pixel (i, j) centred at (u, v) = (j, i).  Its adjoint for a cotangent (du, dv), the chain
+ *                 differentiated as written with iz = 1 / Z: gX = (du K00) iz, gY = fma(du, K01, dv K11) iz, gZ = -fma(du, fma(K01, Y,
+ *                 K00 X), dv (K11 Y)) (iz iz), g_l_j = fma(R_2j, gZ, fma(R_1j, gY, R_0j gX)).
+ *   mvd_op_morph_project      points [F,M,3] -> uv [F,C,M,2] (as computed, whatever the validity) and valid [F,C,M] int32 = (Z >=
+ *                 z_near and X, Y, Z, u, v finite).  A thread per (frame, view, point).
+ *   mvd_op_morph_project_bwd  g_uv [F,C,M,2] -> g_points [F,M,3] = the adjoint above summed over the valid views, c ascending,
+ *                 starting from 0, by plain additions; a thread per (frame, point).  An invalid view adds nothing and its g_uv is
+ *                 never read.
+ *   mvd_op_morph_fit_data_2d  lmk [F,M,3] as mvd_op_morph_landmarks writes it; target_uv [Ft,C,M,2] in pixels and weight [Ft,C,M]
+ *                 or NULL (ones), Ft = target_frames, 1 or F.  Optionally the contour set: dyn_lmk [F,C,Md,3] (one point per view),
+ *                 dyn_target_uv [Ft,C,Md,2], dyn_weight [Ft,C,Md] or NULL; without it dyn_lmk, dyn_target_uv, dyn_weight, dyn_uv and
+ *                 g_dyn are all NULL.  An observation (f, c, point) counts iff weight > 0, Z >= z_near and X, Y, Z, u, v are finite;
+ *                 the target of an observation that does not count is never read.  With r = px_scale (uv - target): W_f = sum of w
+ *                 over the counted observations of both sets, E2_f = lambda2 (sum w |r|^2) (1 / W_f) (+ E_add[f] if E_add is given:
+ *                 the loop's 3-D term, one rounded addition); W_f = 0: E2_f = 0 and a zero gradient, exactly.  Outputs: uv
+ *                 [F,C,M,2] and dyn_uv [F,C,Md,2] (every observation, as computed), E2 [F], n_valid [F] int32 (the counted
+ *                 observations), g_lmk [F,M,3] = sum over the counted views c ascending, from 0, of the adjoint above at (du, dv) =
+ *                 cf (uv - target), cf = (((2 lambda2) (px_scale px_scale)) w) (1 / W_f); g_dyn [F,C,Md,3] the same per view (0 where
+ *                 the observation does not count).  Summation shape, as mvd_op_morph_fit_data_corr: the points are the M static
+ *                 landmarks followed by the Md contour landmarks, a thread per (frame, point) walking the views in index order
+ *                 (e = fma(w, fma(rv, rv, ru ru), e), W += w); per block of 256 points a butterfly over each wave's 64 lanes and
+ *                 ((s0 + s1) + s2) + s3 over the 4 waves into part [3 mvd_morph_2d_blocks(M, Md) + 1, F] (the blocks' sums of
+ *                 w |r|^2, of w, their counts as int32 bits, and a last row that takes 1 / W_f); then one wave per frame: a
+ *                 lane-strided ascending sum over the blocks and one butterfly.
+ *   mvd_op_morph_contour_select   A [F,J,12] as mvd_op_morph_pose wrote it.  Per (frame, view): g = the first column of the 3x3 of
+ *                 A[f, neck_joint] (the chained global-times-neck rotation), Mx = S R_c G with S = diag(1, -1, -1) taking the
+ *                 camera's axes (x right, y down, z forward) to the model's: Mx00 = fma chain of R_c row 0 with g, Mx10 and Mx20 the
+ *                 negated chains of rows 1 and 2; yaw_deg = -atan2(-Mx20, sqrt(fma(Mx10, Mx10, Mx00 Mx00))) 180 / pi: 0 for a
+ *                 frontal camera on an unposed head.  Row of a table of R = 2 h + 1 rows (R odd): y = rint(min(yaw_deg, h)) (half
+ *                 to even); y >= 0: y; -h <= y < 0: h - y; y < -h: 2 h; a non-finite yaw: 0.  row [F,C] int32; yaw_deg [F,C] or NULL.
+ *                 Piecewise constant: no gradient, as in the reference.
+ *   mvd_op_morph_contour_landmarks   dyn_lmk_face [R,Md] int32, dyn_lmk_bary [R,Md,3]: dyn_lmk [F,C,Md,3] by mvd_op_morph_landmarks'
+ *                 fma form on row[f,c] of the table.  A row, face or vertex index out of range is never dereferenced: NaN.
+ *   mvd_op_morph_contour_bwd   a gather.  ct_vert [n_list]: the vertices that appear in the table, ascending; ct_ptr [n_list+1], ct_ent
+ *                 [n_ent]: vertex ct_vert[i] has the entries ct_ent[ct_ptr[i] .. ct_ptr[i+1]), entry = (row Md + landmark) 3 + corner,
+ *                 ascending.  g_verts [F,V,3] = g_in (NULL: zeros; g_in == g_verts: in place, what the loop does), and at every listed
+ *                 vertex, over its entries in table order and inside an entry over the views c ascending with row[f,c] == the
+ *                 entry's row, acc = fma(dyn_lmk_bary[entry], g_dyn[f,c,landmark], acc).  Entries and offsets out of range are skipped.
+ *   mvd_morph_fit_2d_run   mvd_morph_fit_run's loop with the 2-D term.  Iteration: pose, skin_ex, landmarks; contour_select and
+ *                 contour_landmarks (only with dyn_target_uv); fit_data on the vertices alone (only with a 3-D `target`: g_y0 and
+ *                 E3; without one nothing reads a target and the adjoint starts from zero); fit_data_2d (E_add = E3); landmarks_bwd
+ *                 with g_in = g_y0; contour_bwd in place; skin_bwd, pose_bwd, fit_update.  Plain launches on the stream, one
+ *                 synchronisation at the end.  loss_history [iters,F]: the sum of the terms before each update; n_valid_history
+ *                 [iters,F].  workspace: mvd_morph_fit_2d_workspace(F, V, NB, J, M, Md, C, &floats) floats (Md = 0 without a contour
+ *                 target).  Each iteration's bits are those of the per-op entries called in turn.
+ * Errors, which return before the first HIP call: those of the block above for the same arguments; a null pointer (but the weights,
+ * E_add, yaw_deg, g_in and the contour set as a whole); Fc or Ft neither 1 nor F; C < 1, M < 1, F C M 2 >= 2^31 (F C Md 3 likewise);
+ * z_near <= 0 or not finite; px_scale or lambda2 negative or not finite; part of the contour set without the rest; a contour
+ * target without the model's tables; neck_joint outside [0, J); an even R; more than 65535 frames.
+ * Not computed: focal length and camera refinement, photometric and silhouette terms, robust kernels, the landmark detector; the
+ * tracker's eyelid / iris / mouth sub-losses are weights on this term and the caller's to set. */
+int mvd_morph_2d_blocks(int M, int Md);
+int mvd_op_morph_project(const float* points, const float* K, const float* RT, int cam_frames, int F, int C, int M, float z_near, float* uv,
+                         int32_t* valid, void* stream);
+int mvd_op_morph_project_bwd(const float* points, const float* K, const float* RT, int cam_frames, const float* g_uv, int F, int C, int M,
+                             float z_near, float* g_points, void* stream);
+int mvd_op_morph_fit_data_2d(const float* lmk, const float* dyn_lmk, const float* K, const float* RT, int cam_frames, const float* target_uv,
+                             const float* weight, const float* dyn_target_uv, const float* dyn_weight, int target_frames, int F, int C, int M,
+                             int Md, float z_near, float px_scale, float lambda2, const float* E_add, float* uv, float* dyn_uv, float* part,
+                             float* E2, int32_t* n_valid, float* g_lmk, float* g_dyn, void* stream);
+int mvd_op_morph_contour_select(const float* A, const float* RT, int cam_frames, int F, int C, int J, int neck_joint, int R, int32_t* row,
+                                float* yaw_deg, void* stream);
+int mvd_op_morph_contour_landmarks(const float* verts, const int32_t* faces, const int32_t* dyn_lmk_face, const float* dyn_lmk_bary,
+                                   const int32_t* row, int F, int C, int V, int Nf, int R, int Md, float* dyn_lmk, void* stream);
+int mvd_op_morph_contour_bwd(const float* g_dyn, const float* g_in, const int32_t* row, const int32_t* ct_vert, const int32_t* ct_ptr,
+                             const int32_t* ct_ent, const float* dyn_lmk_bary, int F, int C, int V, int R, int Md, int n_list, int n_ent,
+                             float* g_verts, void* stream);
+int mvd_morph_fit_2d_workspace(int F, int V, int NB, int J, int M, int Md, int C, int64_t* floats);
+int mvd_morph_fit_2d_run(const float* basis, const float* v_template, const float* weights, const float* j_template, const float* j_dirs,
+                         const int32_t* parents, const float* post, const int32_t* faces, const int32_t* lmk_face, const float* lmk_bary,
+                         const int32_t* csr_ptr, const int32_t* csr_ent, const int32_t* dyn_lmk_face, const float* dyn_lmk_bary,
+                         const int32_t* ct_vert, const int32_t* ct_ptr, const int32_t* ct_ent, int F, int V, int NB, int J, int Nf, int M,
+                         int n_ent, int R, int Md, int n_list, int ct_n_ent, int neck_joint, const float* K, const float* RT, int cam_frames,
+                         int C, const float* target_uv, const float* weight, const float* dyn_target_uv, const float* dyn_weight,
+                         int target_frames, float z_near, float px_scale, float lambda2, const float* target, int target3_frames,
+                         const float* vertex_weight, float inv_vw_sum, float* p, float* m, float* v, const float* lr, const float* lam,
+                         const float* p0, int iters, int step0, float beta1, float beta2, float eps, float* workspace,
+                         size_t workspace_floats, float* loss_history, int32_t* n_valid_history, void* stream);
 /* The conditioner's backward for ONE sample (its mesh / cameras active: mvd_select_sample): re-runs construct_spatial_volume and
  * construct_view_frustum_volume (morphable_diffusion.py:203-320: step embedding, 2-D encoder on the N noisy views, vertex gather,
  * view fusion, sparse voxel CNN in train mode, lattice gather, frustum gather and FrustumTV3DNet for the target view) with every

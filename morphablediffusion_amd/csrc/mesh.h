@@ -11,13 +11,20 @@ constexpr int MESH_SUB = 4, MESH_ONE = 1 << MESH_SUB, MESH_KMAX = (1 << 24) - 1,
 // cam = R x + t, u = (K00 X + K01 Y) / Z + K02, v = K11 Y / Z + K12 in fp32; r: 12 floats of RT, k: 9 floats of K.  xs = ys = kk = 0
 // marks an invalid point.  A NaN fails every comparison: Z >= z_near and the guard band are written so that it lands on the
 // invalid side.
+// The chain itself, shared with the 2-D landmark term (k_morph_2d.hip), which needs the camera-space point and the unsnapped pixel.
+__device__ inline void mesh_project_uv(const float* __restrict__ r, const float* __restrict__ k, float x, float y, float z, float& X,
+                                       float& Y, float& Z, float& u, float& w) {
+  X = r[0] * x + r[1] * y + r[2] * z + r[3];
+  Y = r[4] * x + r[5] * y + r[6] * z + r[7];
+  Z = r[8] * x + r[9] * y + r[10] * z + r[11];
+  u = (k[0] * X + k[1] * Y) / Z + k[2];
+  w = k[4] * Y / Z + k[5];
+}
+
 __device__ inline void mesh_project_point(const float* __restrict__ r, const float* __restrict__ k, float x, float y, float z, float z_near,
                                           int& xs, int& ys, int& kk) {
-  const float X = r[0] * x + r[1] * y + r[2] * z + r[3];
-  const float Y = r[4] * x + r[5] * y + r[6] * z + r[7];
-  const float Z = r[8] * x + r[9] * y + r[10] * z + r[11];
-  const float u = (k[0] * X + k[1] * Y) / Z + k[2];
-  const float w = k[4] * Y / Z + k[5];
+  float X, Y, Z, u, w;
+  mesh_project_uv(r, k, x, y, z, X, Y, Z, u, w);
   xs = 0, ys = 0, kk = 0;
   if (Z >= z_near && fabsf(u) <= (float)MESH_GUARD_PX && fabsf(w) <= (float)MESH_GUARD_PX) {
     xs = (int)rintf(u * (float)MESH_ONE);

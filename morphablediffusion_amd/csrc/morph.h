@@ -58,3 +58,41 @@ int morph_fit_update_check(const char* who, const float* p, const float* g, cons
                            const float* lam, const float* p0, int F, int P, int step, float beta1, float beta2, float eps);
 int launch_morph_fit_update(float* p, const float* g, float* m, float* v, const float* lr, const float* lam, const float* p0, int F, int P,
                             int step, float beta1, float beta2, float eps, hipStream_t s);
+
+// k_morph_2d.hip: the 2-D multi-view landmark term and the per-view contour landmarks (include/mvd.h: mvd_op_morph_project,
+// mvd_op_morph_fit_data_2d, mvd_op_morph_contour_*, mvd_morph_fit_2d_run).  Points of a block of the 2-D term's reduction:
+constexpr int MORPH_2D_BLOCK = 256;
+inline int morph_2d_blocks(int M, int Md) { return (int)(((long long)M + Md + MORPH_2D_BLOCK - 1) / MORPH_2D_BLOCK); }
+// what the 2-D term reads besides the landmarks: cameras K [cam_frames][C][9], RT [cam_frames][C][12], targets in pixels
+// [target_frames][C][M][2] (and [..][Md][2] for the contour landmarks) with optional weights (null = ones)
+struct Morph2dTerm {
+  const float *K, *RT, *target_uv, *weight, *dyn_target_uv, *dyn_weight;
+  int cam_frames, target_frames, C;
+  float z_near, px_scale, lambda2;
+};
+int morph_project_check(const char* who, const float* points, const float* K, const float* RT, int cam_frames, int F, int C, int M,
+                        float z_near, const void* out_a, const void* out_b);
+int launch_morph_project(const float* points, const float* K, const float* RT, int cam_frames, int F, int C, int M, float z_near, float* uv,
+                         int* valid, hipStream_t s);
+int launch_morph_project_bwd(const float* points, const float* K, const float* RT, int cam_frames, const float* g_uv, int F, int C, int M,
+                             float z_near, float* g_points, hipStream_t s);
+// part is [3 blocks + 1][F]: the block sums of w |r|^2, of w, the block counts (int32 bits), then 1 / W_f; E_add [F] or null is
+// added to E2 (the loop's 3-D term); dyn_lmk null = no contour landmarks (dyn_uv, g_dyn and the term's dyn_* then null too)
+int morph_fit_data_2d_check(const char* who, const Morph2dTerm& t, int F, int M, int Md, const float* lmk, const float* dyn_lmk,
+                            const float* uv, const float* dyn_uv, const float* part, const float* E2, const int* n_valid, const float* g_lmk,
+                            const float* g_dyn);
+int launch_morph_fit_data_2d(const Morph2dTerm& t, int F, int M, int Md, const float* lmk, const float* dyn_lmk, const float* E_add,
+                             float* uv, float* dyn_uv, float* part, float* E2, int* n_valid, float* g_lmk, float* g_dyn, hipStream_t s);
+int morph_contour_select_check(const char* who, const float* A, const float* RT, int cam_frames, int F, int C, int J, int neck_joint, int R,
+                               const int* row);
+int launch_morph_contour_select(const float* A, const float* RT, int cam_frames, int F, int C, int J, int neck_joint, int R, int* row,
+                                float* yaw, hipStream_t s);
+int morph_contour_landmarks_check(const char* who, const float* verts, const int* faces, const int* dyn_face, const float* dyn_bary,
+                                  const int* row, int F, int C, int V, int Nf, int R, int Md, const float* out);
+int launch_morph_contour_landmarks(const float* verts, const int* faces, const int* dyn_face, const float* dyn_bary, const int* row, int F,
+                                   int C, int V, int Nf, int R, int Md, float* out, hipStream_t s);
+// g_verts is read and written in place at the listed vertices
+int morph_contour_bwd_check(const char* who, const float* g_dyn, const int* row, const int* ct_vert, const int* ct_ptr, const int* ct_ent,
+                            const float* dyn_bary, int F, int C, int V, int R, int Md, int n_list, int n_ent, const float* g_verts);
+int launch_morph_contour_bwd(const float* g_dyn, const int* row, const int* ct_vert, const int* ct_ptr, const int* ct_ent,
+                             const float* dyn_bary, int F, int C, int V, int R, int Md, int n_list, int n_ent, float* g_verts, hipStream_t s);

@@ -1019,6 +1019,307 @@ def morph_fit_scan_run(model, p, m, v, lr, lam, p0, iters, scans, incidence=None
     return hist, matched, corr_face
 
 
+# ---- the 2-D multi-view landmark term and the per-view contour landmarks (include/mvd.h: mvd_op_morph_project, _fit_data_2d,
+# mvd_op_morph_contour_*, mvd_morph_fit_2d_run; csrc/k_morph_2d.hip): context-free.
+Z_NEAR_2D = 1e-3  # metres: a landmark nearer to a camera than this does not count
+
+
+def _camera_args(who, K, RT, F):
+    """K [Fc,C,3,3] and RT [Fc,C,3,4] float tensors with Fc 1 or F (a [C,3,3] / [C,3,4] pair is shared by the frames): (K, RT, Fc, C)."""
+    if torch.is_tensor(K) and torch.is_tensor(RT) and K.dim() == 3 and RT.dim() == 3:
+        K, RT = K[None], RT[None]
+    _float_arg(who, "K", K, (None, None, 3, 3))
+    Fc, C_ = K.shape[:2]
+    _float_arg(who, "RT", RT, (Fc, C_, 3, 4))
+    if Fc not in (1, F):
+        raise ValueError(f"{who}: the cameras must have 1 or F = {F} frames, got {Fc}")
+    return K, RT, Fc, C_
+
+
+def _z_near(who, z_near):
+    z_near = float(z_near)
+    if not (0.0 < z_near < float("inf")):
+        raise ValueError(f"{who}: z_near must be positive and finite, got {z_near}")
+    return z_near
+
+
+def op_morph_project(points, K, RT, z_near=Z_NEAR_2D, device=None, lib=None):
+    """mvd_op_morph_project on ``device`` (default: points'): points [F,M,3], K [Fc,C,3,3], RT [Fc,C,3,4] (Fc 1 or F; a [C,..] pair is
+    shared).  Returns (uv [F,C,M,2] float32 in pixels, mvd_op_mesh_project's convention; valid [F,C,M] int32)."""
+    who = "op_morph_project"
+    _float_arg(who, "points", points, (None, None, 3))
+    F, M = points.shape[:2]
+    K, RT, Fc, C_ = _camera_args(who, K, RT, F)
+    z_near = _z_near(who, z_near)
+    if F * C_ * M * 3 >= 2 ** 31:
+        raise ValueError(f"{who}: F C M 2 must be below 2^31")
+    dev = points.device if device is None else device
+    pt, k, rt = _f32(points, dev), _f32(K, dev), _f32(RT, dev)
+    lib = lib or L.load()
+    uv = torch.full((F, C_, M, 2), float("nan"), device=dev)
+    valid = torch.full((F, C_, M), -1, device=dev, dtype=torch.int32)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_morph_project(L.ptr(pt), L.ptr(k), L.ptr(rt), Fc, F, C_, M, z_near, L.ptr(uv), L.ptr(valid), _stream()))
+    return uv, valid
+
+
+def op_morph_project_bwd(points, K, RT, g_uv, z_near=Z_NEAR_2D, device=None, lib=None):
+    """mvd_op_morph_project_bwd: the cotangent g_uv [F,C,M,2] of op_morph_project's uv pulled back to the points, g_points [F,M,3];
+    a view in which the point is not valid adds nothing."""
+    who = "op_morph_project_bwd"
+    _float_arg(who, "points", points, (None, None, 3))
+    F, M = points.shape[:2]
+    K, RT, Fc, C_ = _camera_args(who, K, RT, F)
+    _float_arg(who, "g_uv", g_uv, (F, C_, M, 2))
+    z_near = _z_near(who, z_near)
+    if F * C_ * M * 3 >= 2 ** 31:
+        raise ValueError(f"{who}: F C M 2 must be below 2^31")
+    dev = points.device if device is None else device
+    pt, k, rt, g = _f32(points, dev), _f32(K, dev), _f32(RT, dev), _f32(g_uv, dev)
+    lib = lib or L.load()
+    out = torch.full((F, M, 3), float("nan"), device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_morph_project_bwd(L.ptr(pt), L.ptr(k), L.ptr(rt), Fc, L.ptr(g), F, C_, M, z_near, L.ptr(out), _stream()))
+    return out
+
+
+def _term_2d_args(who, F, C_, M, Md, target_uv, weight, dyn_target_uv, dyn_weight, z_near, px_scale, lambda2, dev):
+    """The 2-D term's targets and numbers checked and on the device: (target_uv, weight, dyn_target_uv, dyn_weight, Ft, z_near,
+    px_scale, lambda2).  A [C,M,2] target is shared by the frames."""
+    def one(name, t, n, last):
+        if t is None:
+            return None, None
+        t = t[None] if torch.is_tensor(t) and t.dim() == len(last) + 2 else t
+        _float_arg(who, name, t, (None, C_, n) + last)
+        return _f32(t, dev), t.shape[0]
+    tu, ft = one("target_uv", target_uv, M, (2,))
+    if tu is None:
+        raise ValueError(f"{who}: target_uv is needed")
+    counts = [ft]
+    w, n = one("weight", weight, M, ())
+    counts += [] if n is None else [n]
+    du = dw = None
+    if dyn_target_uv is not None:
+        du, n = one("dyn_target_uv", dyn_target_uv, Md, (2,))
+        counts.append(n)
+        dw, n = one("dyn_weight", dyn_weight, Md, ())
+        counts += [] if n is None else [n]
+    elif dyn_weight is not None:
+        raise ValueError(f"{who}: dyn_weight without dyn_target_uv")
+    Ft = counts[0]
+    if Ft not in (1, F) or any(c != Ft for c in counts):
+        raise ValueError(f"{who}: the 2-D targets and their weights must all have 1 or all have F = {F} frames, got {counts}")
+    z_near, px_scale, lambda2 = _z_near(who, z_near), float(px_scale), float(lambda2)
+    if not (0.0 <= px_scale < float("inf") and 0.0 <= lambda2 < float("inf")):
+        raise ValueError(f"{who}: px_scale and lambda2 must be finite and not negative, got {px_scale} and {lambda2}")
+    if F > 65535 or F * C_ * max(M, Md, 1) * 3 >= 2 ** 31:
+        raise ValueError(f"{who}: at most 65535 frames, F C M 2 and F C Md 3 below 2^31")
+    return tu, w, du, dw, Ft, z_near, px_scale, lambda2
+
+
+def op_morph_fit_data_2d(lmk, K, RT, target_uv, weight=None, dyn_lmk=None, dyn_target_uv=None, dyn_weight=None, z_near=Z_NEAR_2D,
+                         px_scale=1.0, lambda2=1.0, E_add=None, device=None, lib=None):
+    """mvd_op_morph_fit_data_2d on ``device`` (default: lmk's): lmk [F,M,3]; cameras as op_morph_project; target_uv [Ft,C,M,2] in
+    pixels with an optional weight [Ft,C,M] (Ft 1 or F); optionally the contour set dyn_lmk [F,C,Md,3], dyn_target_uv [Ft,C,Md,2],
+    dyn_weight [Ft,C,Md].  E2_f = lambda2 sum w |px_scale (uv - target)|^2 / W_f over the observations that count (w > 0, Z >=
+    z_near, finite), W_f the sum of their weights.  Returns a dict: uv, dyn_uv (or None), E2 [F] (+ E_add), n_valid [F] int32,
+    g_lmk [F,M,3], g_dyn [F,C,Md,3] (or None), inv_w [F] = 1 / W_f (0 where nothing counts)."""
+    who = "op_morph_fit_data_2d"
+    _float_arg(who, "lmk", lmk, (None, None, 3))
+    F, M = lmk.shape[:2]
+    K, RT, Fc, C_ = _camera_args(who, K, RT, F)
+    if (dyn_lmk is None) != (dyn_target_uv is None):
+        raise ValueError(f"{who}: dyn_lmk and dyn_target_uv go together")
+    Md = 0
+    if dyn_lmk is not None:
+        _float_arg(who, "dyn_lmk", dyn_lmk, (F, C_, None, 3))
+        Md = dyn_lmk.shape[2]
+    dev = lmk.device if device is None else device
+    tu, w, du, dw, Ft, z_near, px_scale, lambda2 = _term_2d_args(who, F, C_, M, Md, target_uv, weight, dyn_target_uv, dyn_weight, z_near,
+                                                                 px_scale, lambda2, dev)
+    if E_add is not None:
+        _float_arg(who, "E_add", E_add, (F,))
+    lm, k, rt = _f32(lmk, dev), _f32(K, dev), _f32(RT, dev)
+    dl = None if dyn_lmk is None else _f32(dyn_lmk, dev)
+    ea = None if E_add is None else _f32(E_add, dev)
+    lib = lib or L.load()
+    nan = float("nan")
+    nblk = int(lib.mvd_morph_2d_blocks(M, Md))
+    out = {"uv": torch.full((F, C_, M, 2), nan, device=dev), "dyn_uv": None if dl is None else torch.full((F, C_, Md, 2), nan, device=dev),
+           "E2": torch.full((F,), nan, device=dev), "n_valid": torch.full((F,), -1, device=dev, dtype=torch.int32),
+           "g_lmk": torch.full((F, M, 3), nan, device=dev), "g_dyn": None if dl is None else torch.full((F, C_, Md, 3), nan, device=dev)}
+    part = torch.full((3 * nblk + 1, F), nan, device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_morph_fit_data_2d(L.ptr(lm), L.ptr(dl), L.ptr(k), L.ptr(rt), Fc, L.ptr(tu), L.ptr(w), L.ptr(du), L.ptr(dw), Ft, F, C_,
+                                             M, Md, z_near, px_scale, lambda2, L.ptr(ea), L.ptr(out["uv"]), L.ptr(out["dyn_uv"]), L.ptr(part),
+                                             L.ptr(out["E2"]), L.ptr(out["n_valid"]), L.ptr(out["g_lmk"]), L.ptr(out["g_dyn"]), _stream()))
+    out["inv_w"] = part[3 * nblk].clone()
+    return out
+
+
+def op_morph_contour_select(A, RT, neck_joint, R, device=None, lib=None):
+    """mvd_op_morph_contour_select on ``device`` (default: A's): A [F,J,3,4] or [F,J,12] as op_morph_pose returns it, RT [Fc,C,3,4]
+    (or [C,3,4]), neck_joint in 0..J-1, R (odd) rows of the contour table.  Returns (row [F,C] int32, yaw_deg [F,C])."""
+    who = "op_morph_contour_select"
+    if torch.is_tensor(A) and A.dim() == 4:
+        _float_arg(who, "A", A, (None, None, 3, 4))
+    else:
+        _float_arg(who, "A", A, (None, None, 12))
+    F, J = A.shape[:2]
+    RT = RT[None] if torch.is_tensor(RT) and RT.dim() == 3 else RT
+    _float_arg(who, "RT", RT, (None, None, 3, 4))
+    Fc, C_ = RT.shape[:2]
+    neck_joint, R = int(neck_joint), int(R)
+    if Fc not in (1, F) or J > MORPH_MAX_JOINTS or not 0 <= neck_joint < J or R < 1 or R % 2 == 0 or F * C_ * 12 >= 2 ** 31:
+        raise ValueError(f"{who}: needs 1 or F camera frames, J <= 64, neck_joint in 0..J-1, an odd R >= 1 and F C 12 < 2^31; got "
+                         f"Fc = {Fc}, F = {F}, J = {J}, neck_joint = {neck_joint}, R = {R}")
+    dev = A.device if device is None else device
+    a, rt = _f32(A, dev), _f32(RT, dev)
+    lib = lib or L.load()
+    row = torch.full((F, C_), -1, device=dev, dtype=torch.int32)
+    yaw = torch.full((F, C_), float("nan"), device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_morph_contour_select(L.ptr(a), L.ptr(rt), Fc, F, C_, J, neck_joint, R, L.ptr(row), L.ptr(yaw), _stream()))
+    return row, yaw
+
+
+def op_morph_contour_landmarks(verts, faces, dyn_lmk_face, dyn_lmk_bary, row, device=None, lib=None):
+    """mvd_op_morph_contour_landmarks on ``device`` (default: verts'): verts [F,V,3], faces [Nf,3] int32, the contour table
+    dyn_lmk_face [R,Md] int32 and dyn_lmk_bary [R,Md,3], row [F,C] int32.  Returns dyn_lmk [F,C,Md,3]; an index out of range: NaN."""
+    who = "op_morph_contour_landmarks"
+    _float_arg(who, "verts", verts, (None, None, 3))
+    F, V = verts.shape[:2]
+    _i32("faces", faces, (None, 3), who)
+    _i32("dyn_lmk_face", dyn_lmk_face, (None, None), who)
+    R, Md = dyn_lmk_face.shape
+    _float_arg(who, "dyn_lmk_bary", dyn_lmk_bary, (R, Md, 3))
+    _i32("row", row, (F, None), who)
+    C_, Nf = row.shape[1], faces.shape[0]
+    if Nf < 1 or R < 1 or Md < 1 or C_ < 1 or F * V * 3 >= 2 ** 31 or F * C_ * Md * 3 >= 2 ** 31 or R * Md * 3 >= 2 ** 31:
+        raise ValueError(f"{who}: needs at least one face, row, landmark and view, and F V 3, F C Md 3, R Md 3 below 2^31")
+    dev = verts.device if device is None else device
+    v, bc = _f32(verts, dev), _f32(dyn_lmk_bary, dev)
+    fc, lf, rw = (t.detach().to(dev).contiguous() for t in (faces, dyn_lmk_face, row))
+    lib = lib or L.load()
+    out = torch.full((F, C_, Md, 3), float("nan"), device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_morph_contour_landmarks(L.ptr(v), L.ptr(fc), L.ptr(lf), L.ptr(bc), L.ptr(rw), F, C_, V, Nf, R, Md, L.ptr(out),
+                                                   _stream()))
+    return out
+
+
+def contour_table(faces, dyn_lmk_face, V):
+    """The vertex -> (row, landmark, corner) table of a contour embedding, built on the host: (ct_vert [n_list], ct_ptr [n_list+1],
+    ct_ent [n_ent]) int32 numpy arrays.  ct_vert: the vertices that appear, ascending; the entries (row Md + landmark) 3 + corner of
+    ct_vert[i] are ct_ent[ct_ptr[i] : ct_ptr[i+1]], ascending.  A face index outside the mesh contributes no entry."""
+    import numpy as np
+    faces, lf = np.asarray(faces, dtype=np.int64), np.asarray(dyn_lmk_face, dtype=np.int64)
+    ok = ((lf >= 0) & (lf < len(faces))).reshape(-1)
+    vert = faces[np.where(ok, lf.reshape(-1), 0)].reshape(-1)  # vertex of entry (row Md + landmark) 3 + corner
+    ent = np.arange(vert.size)[np.repeat(ok, 3) & (vert >= 0) & (vert < V)]
+    order = ent[np.argsort(vert[ent], kind="stable")]
+    listed, counts = np.unique(vert[order], return_counts=True)
+    ptr = np.concatenate([[0], np.cumsum(counts)])
+    return listed.astype(np.int32), ptr.astype(np.int32), order.astype(np.int32)
+
+
+def op_morph_contour_bwd(g_dyn, row, table, dyn_lmk_bary, V, g_in=None, device=None, lib=None):
+    """mvd_op_morph_contour_bwd on ``device`` (default: g_dyn's): g_dyn [F,C,Md,3], row [F,C] int32, table = (ct_vert, ct_ptr,
+    ct_ent) of contour_table as int32 tensors, dyn_lmk_bary [R,Md,3], g_in [F,V,3] or None.  Returns g_verts [F,V,3] = g_in + the
+    contour landmarks' adjoint gathered per vertex."""
+    who = "op_morph_contour_bwd"
+    V = int(V)
+    _float_arg(who, "g_dyn", g_dyn, (None, None, None, 3))
+    F, C_, Md = g_dyn.shape[:3]
+    _i32("row", row, (F, C_), who)
+    cv, cp, ce = table
+    _i32("ct_vert", cv, (None,), who)
+    n_list = cv.shape[0]
+    _i32("ct_ptr", cp, (n_list + 1,), who)
+    _i32("ct_ent", ce, (None,), who)
+    _float_arg(who, "dyn_lmk_bary", dyn_lmk_bary, (None, Md, 3))
+    R, n_ent = dyn_lmk_bary.shape[0], ce.shape[0]
+    if n_list < 1 or n_ent < 1:
+        raise ValueError(f"{who}: the contour table is empty")
+    if g_in is not None:
+        _float_arg(who, "g_in", g_in, (F, V, 3))
+    if F * V * 3 >= 2 ** 31 or F * C_ * Md * 3 >= 2 ** 31 or R * Md * 3 >= 2 ** 31:
+        raise ValueError(f"{who}: F V 3, F C Md 3 and R Md 3 must be below 2^31")
+    dev = g_dyn.device if device is None else device
+    gd, bc = _f32(g_dyn, dev), _f32(dyn_lmk_bary, dev)
+    gi = None if g_in is None else _f32(g_in, dev)
+    rw, cv, cp, ce = (t.detach().to(dev).contiguous() for t in (row, cv, cp, ce))
+    lib = lib or L.load()
+    out = torch.full((F, V, 3), float("nan"), device=dev)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_op_morph_contour_bwd(L.ptr(gd), L.ptr(gi), L.ptr(rw), L.ptr(cv), L.ptr(cp), L.ptr(ce), L.ptr(bc), F, C_, V, R, Md,
+                                             n_list, n_ent, L.ptr(out), _stream()))
+    return out
+
+
+def morph_fit_2d_run(model, p, m, v, lr, lam, p0, iters, K, RT, target_uv, weight=None, dyn_target_uv=None, dyn_weight=None,
+                     z_near=Z_NEAR_2D, px_scale=1.0, lambda2=1.0, target=None, vertex_weight=None, post=None, step0=0, betas=ADAM_BETAS,
+                     eps=ADAM_EPS, lib=None):
+    """mvd_morph_fit_2d_run: morph_fit_run's loop with the 2-D multi-view landmark term.  model: morph_fit_run's, with a static
+    landmark embedding and, for a contour target, dyn_lmk_face / dyn_lmk_bary / ct_vert / ct_ptr / ct_ent / neck_joint.  K, RT,
+    target_uv, weight, dyn_target_uv, dyn_weight: op_morph_fit_data_2d's; target [F,V,3] / vertex_weight: an optional 3-D vertex
+    term added to it.  p, m, v are updated IN PLACE.  Returns (loss_history [iters,F], n_valid_history [iters,F] int32)."""
+    who = "morph_fit_2d_run"
+    F, P = _fit_update_args(who, p, m, v, lr, lam, p0)
+    V, NB, J = model.v_template.shape[0], model.j_dirs.shape[0], model.weights.shape[1]
+    if P != NB + 3 * J + 3:
+        raise ValueError(f"{who}: p must have P = NB + 3 J + 3 = {NB + 3 * J + 3} columns, got {P}")
+    dev = p.device
+    if model.basis.device != dev:
+        raise ValueError(f"{who}: the model is on {model.basis.device}, the parameters on {dev}")
+    iters, step0, b1, b2, eps = int(iters), int(step0), float(betas[0]), float(betas[1]), float(eps)
+    if iters < 1 or step0 < 0 or iters * F >= 2 ** 31 or not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0 and eps > 0.0):
+        raise ValueError(f"{who}: iters must be at least 1 (iters F < 2^31), step0 at least 0, betas in [0, 1), eps positive")
+    if post is not None:
+        _float_arg(who, "post", post, (3, 4))
+    if getattr(model, "csr_ptr", None) is None:
+        raise ValueError(f"{who}: the 2-D term needs a model with a landmark embedding")
+    M, n_ent = _csr_args(who, model.csr_ptr, model.csr_ent, model.lmk_bary, V)
+    K, RT, Fc, C_ = _camera_args(who, K, RT, F)
+    dyn = dyn_target_uv is not None
+    df = db = cv = cp = ce = None
+    R = Md = n_list = ct_n = neck = 0
+    if dyn:
+        if getattr(model, "dyn_lmk_face", None) is None:
+            raise ValueError(f"{who}: a contour target is given, and the model has no contour tables")
+        df, db, cv, cp, ce, neck = model.dyn_lmk_face, model.dyn_lmk_bary, model.ct_vert, model.ct_ptr, model.ct_ent, int(model.neck_joint)
+        (R, Md), n_list, ct_n = df.shape, cv.shape[0], ce.shape[0]
+        if not 0 <= neck < J:
+            raise ValueError(f"{who}: neck_joint must be in 0..{J - 1}, got {neck}")
+    tu, w, du, dw, Ft, z_near, px_scale, lambda2 = _term_2d_args(who, F, C_, M, Md, target_uv, weight, dyn_target_uv, dyn_weight, z_near,
+                                                                 px_scale, lambda2, dev)
+    tg, tf, vw, inv_vw = None, 1, None, 0.0
+    if target is not None:
+        tg, tf, vw, inv_vw = _fit_data_args(who, F, V, target, vertex_weight, None, None, None, 1.0, None, dev)[:4]
+    elif vertex_weight is not None:
+        raise ValueError(f"{who}: vertex_weight without target vertices")
+    par = morph_parents(who, model.parents, J)
+    lrd, lamd, p0d, k, rt = (_f32(t, dev) for t in (lr, lam, p0, K, RT))
+    ps = None if post is None else _f32(post, dev)
+    lib = lib or L.load()
+    n_ws_c = C.c_int64(0)
+    L.check(lib.mvd_morph_fit_2d_workspace(F, V, NB, J, M, Md, C_, C.addressof(n_ws_c)))
+    n_ws = int(n_ws_c.value)
+    ws = torch.full((n_ws,), float("nan"), device=dev)
+    hist = torch.full((iters, F), float("nan"), device=dev)
+    n_hist = torch.full((iters, F), -1, device=dev, dtype=torch.int32)
+    par_c = (C.c_int32 * J)(*par)
+    with torch.cuda.device(dev):
+        L.check(lib.mvd_morph_fit_2d_run(
+            L.ptr(model.basis), L.ptr(model.v_template), L.ptr(model.weights), L.ptr(model.j_template), L.ptr(model.j_dirs),
+            C.addressof(par_c), L.ptr(ps), L.ptr(model.faces), L.ptr(model.lmk_face), L.ptr(model.lmk_bary), L.ptr(model.csr_ptr),
+            L.ptr(model.csr_ent), L.ptr(df), L.ptr(db), L.ptr(cv), L.ptr(cp), L.ptr(ce), F, V, NB, J, model.faces.shape[0], M, n_ent, R, Md,
+            n_list, ct_n, neck, L.ptr(k), L.ptr(rt), Fc, C_, L.ptr(tu), L.ptr(w), L.ptr(du), L.ptr(dw), Ft, z_near, px_scale, lambda2,
+            L.ptr(tg), tf, L.ptr(vw), inv_vw, L.ptr(p), L.ptr(m), L.ptr(v), L.ptr(lrd), L.ptr(lamd), L.ptr(p0d), iters, step0, b1, b2, eps,
+            L.ptr(ws), n_ws, L.ptr(hist), L.ptr(n_hist), _stream()))
+    return hist, n_hist
+
+
 # ---- the sparse voxel CNN's kernels one at a time (include/mvd.h: mvd_op_sparse_conv ...): context-free like op_train_loss.
 # w: the 3x3x3 kernel in checkpoint layout 0 [Cout,Cin,3,3,3], 1 [Cout,3,3,3,Cin] or 2 [3,3,3,Cin,Cout]; nbr [n_out,27] int32.
 SPARSE_FORMS = ("site", "mfma")  # form of mvd_op_sparse_conv / mvd_op_sparse_conv_bwd, by index

@@ -35,6 +35,9 @@ Differences, all outside the denoising path and stated here:
     does exactly what it did without them.
   * --flame_model MODEL --fit_scan SCAN.{ply,obj} (not reference flags; mesh.closest_point, csrc/k_closest.hip) does the same
     against a scan of any topology, with --fit_scan_max_dist / _normal_cos / _refresh / _landmarks.
+  * --flame_model MODEL --fit_landmarks2d LMK.npz (not a reference flag; MorphableModel.fit_flame_2d, csrc/k_morph_2d.hip) does
+    the same against 2-D key points in calibrated views: the file holds landmarks [C,M,2] or [F,C,M,2] in pixels, K [C,3,3], RT
+    [C,3,4] and optionally weights and image_size; the .json reports reprojection_px per view.  It excludes --fit_mesh / --fit_scan.
   * --flame_model MODEL --fit_mesh MESH.{ply,obj} (not reference flags; morphable.py, csrc/k_morph_bwd.hip) fit the model's
     parameters to a mesh of the model's topology, in the model's frame (what metrical-tracker exports), with Adam on the device
     (--fit_iters, --fit_lr), and write ``<input>_<exp>_fit.npz`` (shape, expression, global_pose, neck, jaw, eyes, transl) and
@@ -209,6 +212,11 @@ def build_parser():
     p.add_argument("--fit_scan_landmarks", type=str, default=None,
                    help="not a reference flag: an .npz with `landmarks` [M,3], the scan's 3-D landmarks in the order of the model's "
                         "embedding: a landmark-only fit of global pose and translation seeds --fit_scan, and the term stays on")
+    p.add_argument("--fit_landmarks2d", type=str, default=None,
+                   help="not a reference flag: an .npz with `landmarks` [C,M,2] or [F,C,M,2] (pixels; M = the model's static landmarks, "
+                        "or 68 in iBUG order for a model with 51 + 17), `K` [C,3,3], `RT` [C,3,4] and optionally `weights` [C,M] and "
+                        "`image_size` (H, W): --flame_model's parameters are fitted to the key points in these calibrated views "
+                        "(--fit_iters, --fit_lr apply)")
     p.add_argument("--flame_n_shape", type=int, default=None,
                    help="not a reference flag: identity columns of the model's shapedirs to keep (MICA: 300; default: all)")
     p.add_argument("--flame_n_exp", type=int, default=None,
@@ -224,7 +232,7 @@ def parse_args(argv=None):
     """build_parser().parse_args plus the rules between the flags: --mesh alone as ever; --flame_model and --flame_params go
     together and replace --mesh; --neutral_params and --frames > 1 go together and need them; --fit_mesh needs --flame_model,
     excludes --mesh and --neutral_params, and with --flame_params takes the place of the neutral end; --fit_scan follows
-    --fit_mesh's rules and excludes it."""
+    --fit_mesh's rules and excludes it; --fit_landmarks2d follows them too and excludes both."""
     p = build_parser()
     flags = p.parse_args(argv)
     scan_only = [n for n in ("fit_scan_max_dist", "fit_scan_normal_cos", "fit_scan_landmarks") if getattr(flags, n) is not None]
@@ -232,6 +240,8 @@ def parse_args(argv=None):
         p.error("--fit_scan_max_dist, --fit_scan_normal_cos, --fit_scan_refresh and --fit_scan_landmarks need --fit_scan")
     if flags.fit_scan and flags.fit_mesh:
         p.error("--fit_scan excludes --fit_mesh (one target)")
+    if flags.fit_landmarks2d and (flags.fit_mesh or flags.fit_scan):
+        p.error("--fit_landmarks2d excludes --fit_mesh and --fit_scan (one target)")
     if flags.fit_scan:
         if flags.fit_scan_max_dist is not None and not flags.fit_scan_max_dist > 0:
             p.error("--fit_scan_max_dist must be positive")
@@ -239,8 +249,8 @@ def parse_args(argv=None):
             p.error("--fit_scan_normal_cos must be in [-1, 1]")
         if flags.fit_scan_refresh < 1:
             p.error("--fit_scan_refresh must be at least 1")
-    if flags.fit_mesh or flags.fit_scan:
-        name = "--fit_mesh" if flags.fit_mesh else "--fit_scan"
+    if flags.fit_mesh or flags.fit_scan or flags.fit_landmarks2d:
+        name = "--fit_mesh" if flags.fit_mesh else ("--fit_scan" if flags.fit_scan else "--fit_landmarks2d")
         if not flags.flame_model:
             p.error(f"{name} needs --flame_model")
         if flags.mesh or flags.neutral_params:
@@ -327,14 +337,43 @@ def fit_to_scan(fm, flags, stem):
     return params
 
 
+def fit_to_landmarks2d(fm, flags, stem):
+    """--fit_landmarks2d: the model's parameters fitted to 2-D key points in calibrated views (MorphableModel.fit_flame_2d; 68
+    points are taken in iBUG order).  A file with a frame axis is fitted frame by frame and frame 0 is what the run uses.  Writes
+    <stem>_fit.npz and <stem>_fit.json (iterations, counted observations, reprojection_px per view); returns {key: float64 vector}
+    over FLAME_FILE_KEYS."""
+    with np.load(flags.fit_landmarks2d, allow_pickle=False) as z:
+        missing = [k for k in ("landmarks", "K", "RT") if k not in z.files]
+        if missing:
+            raise ValueError(f"{flags.fit_landmarks2d}: missing {missing}")
+        d = {k: np.asarray(z[k]) for k in ("landmarks", "K", "RT", "weights", "image_size") if k in z.files}
+    lm = d["landmarks"]
+    if lm.ndim not in (3, 4) or lm.shape[-1] != 2:
+        raise ValueError(f"{flags.fit_landmarks2d}: landmarks must be [C,M,2] or [F,C,M,2], got {lm.shape}")
+    order = "ibug68" if lm.shape[-2] == 68 and fm.lmk_face is not None and fm.lmk_face.shape[0] != 68 else None
+    fit = fm.fit_flame_2d(lm.astype(np.float32), d["K"].astype(np.float32), d["RT"].astype(np.float32),
+                          weights=None if "weights" not in d else d["weights"].astype(np.float32), image_size=d.get("image_size"),
+                          landmark_order=order, iters=flags.fit_iters, lr=flags.fit_lr)
+    params = {k: fit[k][0].cpu().numpy().astype(np.float64) for k in FLAME_FILE_KEYS}
+    np.savez(f"{stem}_fit.npz", **params)
+    with open(f"{stem}_fit.json", "w") as f:
+        json.dump({"landmarks2d": str(flags.fit_landmarks2d), "views": int(lm.shape[-3]), "points": int(lm.shape[-2]),
+                   "frames": int(fit["betas"].shape[0]), "iterations": int(flags.fit_iters), "lr": float(flags.fit_lr),
+                   "observations": int(fit["n_valid"][0]), "reprojection_px": [float(x) for x in fit["reprojection_px"][0]],
+                   "rms": float(fit["rms"][0]), "loss_first": float(fit["loss_history"][0, 0]),
+                   "loss_last": float(fit["loss_history"][-1, 0])}, f, indent=2)
+    return params
+
+
 def flame_frames(flags, device, stem=None):
     """The conditioning meshes of --flame_model with --flame_params and / or --fit_mesh: (verts [F,Nv,3] on the device in the
     frame of batch["vertices"], model-frame vertices [F,Nv,3] as a mesh file would store them, faces [Nf,3] or None).  stem:
     where --fit_mesh writes its files (<stem>_fit.npz / .json)."""
     from . import morphable as MM
     fm = MM.MorphableModel.load(flags.flame_model, n_shape=flags.flame_n_shape, n_exp=flags.flame_n_exp, device=device)
-    if getattr(flags, "fit_mesh", None) or getattr(flags, "fit_scan", None):
-        params = fit_to_mesh(fm, flags, stem) if getattr(flags, "fit_mesh", None) else fit_to_scan(fm, flags, stem)
+    if getattr(flags, "fit_mesh", None) or getattr(flags, "fit_scan", None) or getattr(flags, "fit_landmarks2d", None):
+        params = fit_to_mesh(fm, flags, stem) if getattr(flags, "fit_mesh", None) else (
+            fit_to_scan(fm, flags, stem) if getattr(flags, "fit_scan", None) else fit_to_landmarks2d(fm, flags, stem))
         if flags.flame_params:
             given = load_flame_params(flags.flame_params)
             if any(v.ndim > 1 for v in given.values()):

@@ -13,8 +13,9 @@ vertices go straight into ``batch.build_batch`` / ``stack_batches`` / ``model.sa
 Units: FLAME's forward is in metres, and so are the mesh files of the reference pipeline, so ``unit_scale``
 defaults to 1.0.  The inverse is here too (csrc/k_morph_bwd.hip): ``vjp`` is the vector-Jacobian product of the forward,
 ``differentiable`` the same as a torch.autograd.Function, ``fit`` / ``fit_flame`` run Adam on the device against target vertices
-and 3-D landmarks, ``fit_scan`` / ``fit_flame_scan`` against a scan of any topology (closest points, csrc/k_closest.hip).  Not here:
-the pose-dependent contour landmarks (vertex normals of a batch of frames: mesh.vertex_normals_device).
+and 3-D landmarks, ``fit_scan`` / ``fit_flame_scan`` against a scan of any topology (closest points, csrc/k_closest.hip),
+``fit_2d`` / ``fit_flame_2d`` against 2-D key points in calibrated views, with the pose-dependent contour landmarks chosen per view
+(csrc/k_morph_2d.hip).  Not here: a landmark detector (vertex normals of a batch of frames: mesh.vertex_normals_device).
 
     fit = fm.fit_flame(target_vertices=mesh_vertices, free=("expression", "jaw"), prior={"shape": mica_shape})
 """
@@ -32,6 +33,8 @@ FLAME_EXPRESSION_OFFSET = 300  # FLAME's shapedirs: identity in columns 0..299, 
 FLAME_JOINTS = ("global", "neck", "jaw", "eye_left", "eye_right")
 MODEL_KEYS = ("v_template", "shapedirs", "posedirs", "J_regressor", "kintree_table", "weights", "f")
 LANDMARK_KEYS = ("static_lmk_faces_idx", "static_lmk_bary_coords")  # optional, the names of FLAME's landmark embedding
+CONTOUR_KEYS = ("dynamic_lmk_faces_idx", "dynamic_lmk_bary_coords")  # optional: the per-view contour table [R,Md] / [R,Md,3]
+FLAME_NECK_JOINT = 1
 
 
 class _ChumpyArray:
@@ -102,7 +105,7 @@ def read_model_file(path) -> Dict[str, np.ndarray]:
     missing = [k for k in MODEL_KEYS[:-1] if k not in d]
     if missing:
         raise ValueError(f"{path}: missing {missing}")
-    return {k: _plain(d[k]) for k in MODEL_KEYS + LANDMARK_KEYS if k in d}
+    return {k: _plain(d[k]) for k in MODEL_KEYS + LANDMARK_KEYS + CONTOUR_KEYS if k in d}
 
 
 def _rows(x, F, width, name):
@@ -125,12 +128,14 @@ class MorphableModel:
 
     @classmethod
     def from_arrays(cls, v_template, shapedirs, posedirs, J_regressor, parents, weights, faces=None, lmk_face=None, lmk_bary=None,
-                    device="cuda:0", unit_scale=1.0, n_shape=None):
+                    device="cuda:0", unit_scale=1.0, n_shape=None, dyn_lmk_face=None, dyn_lmk_bary=None, neck_joint=None):
         """v_template [V,3], shapedirs [V,3,NB], posedirs [V,3,9 (J-1)] (the pickle's layout) or [9 (J-1),3V] (lbs.py's),
         J_regressor [J,V] (dense or scipy sparse), parents [J] (parents[0] is taken as the root whatever it holds), weights [V,J];
         optional faces [Nf,3] and a static landmark embedding lmk_face [M], lmk_bary [M,3].  The folds run in float64:
         j_template = J_regressor v_template, j_dirs = J_regressor shapedirs, basis = [shapedirs^T; posedirs]; lengths are
-        multiplied by unit_scale; the device gets float32.  n_shape: how many leading betas ``flame`` takes as identity."""
+        multiplied by unit_scale; the device gets float32.  n_shape: how many leading betas ``flame`` takes as identity.
+        dyn_lmk_face [R,Md], dyn_lmk_bary [R,Md,3] (R odd; FLAME: 79 x 17) and neck_joint (default 1, FLAME's neck; 0 with one
+        joint): the contour landmarks, whose row is chosen per view from the head's yaw in that view (fit_2d)."""
         who = "MorphableModel.from_arrays"
         vt = _plain(v_template).astype(np.float64)
         if vt.ndim != 2 or vt.shape[1] != 3 or vt.shape[0] < 1:
@@ -189,6 +194,24 @@ class MorphableModel:
             self.lmk_face, self.lmk_bary = torch.from_numpy(lf.astype(np.int32)).to(self.device), f32(lb)
             # the backward of the landmarks is a gather through this table: entries ascending, no atomics
             self.csr_ptr, self.csr_ent = (torch.from_numpy(a).to(self.device) for a in E.landmark_csr(fc, lf, lb, V))
+        self.dyn_lmk_face = self.dyn_lmk_bary = self.ct_vert = self.ct_ptr = self.ct_ent = None
+        self.neck_joint = min(FLAME_NECK_JOINT, J - 1) if neck_joint is None else int(neck_joint)
+        if not 0 <= self.neck_joint < J:
+            raise ValueError(f"{who}: neck_joint must be in 0..{J - 1}, got {neck_joint}")
+        if (dyn_lmk_face is None) != (dyn_lmk_bary is None):
+            raise ValueError(f"{who}: dyn_lmk_face and dyn_lmk_bary go together")
+        if dyn_lmk_face is not None:
+            if self.faces is None:
+                raise ValueError(f"{who}: a contour embedding needs faces")
+            df, db = np.asarray(_plain(dyn_lmk_face)).astype(np.int64), _plain(dyn_lmk_bary).astype(np.float64)
+            if df.ndim != 2 or df.shape[0] % 2 != 1 or df.shape[1] < 1 or db.shape != df.shape + (3,):
+                raise ValueError(f"{who}: dyn_lmk_face must be [R,Md] with R odd and dyn_lmk_bary [R,Md,3], got {df.shape} and {db.shape}")
+            table = E.contour_table(fc, df, V)  # a face index outside the mesh gives NaN landmarks and no entry
+            if table[0].size == 0:
+                raise ValueError(f"{who}: no face of dyn_lmk_face is a face of the mesh")
+            self.dyn_lmk_face, self.dyn_lmk_bary = torch.from_numpy(np.ascontiguousarray(df, dtype=np.int32)).to(self.device), f32(db)
+            # the backward of the contour landmarks is a gather through this table, as the static landmarks' is
+            self.ct_vert, self.ct_ptr, self.ct_ent = (torch.from_numpy(a).to(self.device) for a in table)
         return self
 
     @classmethod
@@ -210,6 +233,8 @@ class MorphableModel:
             S, n_shape = np.concatenate([S[:, :, :ns], exp[:, :, :ne]], 2), ns
         kt = np.asarray(d["kintree_table"])
         lm = {"lmk_face": d.get(LANDMARK_KEYS[0]), "lmk_bary": d.get(LANDMARK_KEYS[1])}
+        if d.get("f") is not None and all(k in d for k in CONTOUR_KEYS):
+            lm.update(dyn_lmk_face=d[CONTOUR_KEYS[0]], dyn_lmk_bary=d[CONTOUR_KEYS[1]])
         return cls.from_arrays(d["v_template"], S, d["posedirs"], d["J_regressor"], kt[0] if kt.ndim == 2 else kt, d["weights"],
                                faces=d.get("f"), device=device, unit_scale=unit_scale, n_shape=n_shape, **lm)
 
@@ -556,6 +581,156 @@ class MorphableModel:
         out.update({k: flat[:, g[k]].contiguous() for k in ("shape", "expression", "global_pose", "neck", "jaw", "eyes")})
         return out
 
+    # ---- fitting to 2-D key points in calibrated views (engine.morph_fit_2d_run, csrc/k_morph_2d.hip)
+    def project_landmarks(self, betas, pose, K, RT, transl=None, post=None, z_near=E.Z_NEAR_2D):
+        """The forward alone: the model's landmarks in C calibrated views.  K [C,3,3] / RT [C,3,4] (world -> camera; x right, y
+        down, z forward; pixel (i, j) centred at (u, v) = (j, i): mesh.project's convention) or [F,C,...] per frame.  Returns device
+        tensors: landmarks [F,M,3], uv [F,C,M,2] in pixels, valid [F,C,M] (in front of the camera, finite) and, with a contour
+        embedding, rows [F,C] (the row of the contour table each view selects from the head's yaw in it), yaw_deg [F,C],
+        contour_landmarks [F,C,Md,3], contour_uv [F,C,Md,2], contour_valid [F,C,Md]."""
+        who = "MorphableModel.project_landmarks"
+        if self.lmk_face is None:
+            raise ValueError(f"{who}: the model has no landmark embedding")
+        betas, pose, transl = self._params(who, betas, pose, transl)
+        K, RT = (t if torch.is_tensor(t) else torch.as_tensor(np.asarray(t)) for t in (K, RT))
+        r = self._run(betas, pose, post, transl, False)
+        uv, valid = E.op_morph_project(r["landmarks"], K, RT, z_near, device=self.device)
+        out = {"landmarks": r["landmarks"], "uv": uv, "valid": valid != 0}
+        if self.dyn_lmk_face is not None:
+            F, C = uv.shape[:2]
+            R, Md = self.dyn_lmk_face.shape
+            out["rows"], out["yaw_deg"] = E.op_morph_contour_select(r["A"], RT.to(self.device), self.neck_joint, R, device=self.device)
+            dyn = E.op_morph_contour_landmarks(r["vertices"], self.faces, self.dyn_lmk_face, self.dyn_lmk_bary, out["rows"], device=self.device)
+            # every view's points through every camera, then view c's own block
+            uv_all, ok_all = E.op_morph_project(dyn.reshape(F, C * Md, 3), K, RT, z_near, device=self.device)
+            pick = torch.arange(C, device=self.device)
+            out["contour_landmarks"] = dyn
+            out["contour_uv"] = uv_all.reshape(F, C, C, Md, 2)[:, pick, pick]
+            out["contour_valid"] = ok_all.reshape(F, C, C, Md)[:, pick, pick] != 0
+        return out
+
+    def fit_2d(self, landmarks_2d, K, RT, weights=None, image_size=None, contour_2d=None, contour_weights=None, target_vertices=None,
+               vertex_weight=None, lmk2d_lambda=1.0, z_near=E.Z_NEAR_2D, iters=300, lr=0.05, init=None, free=None, reg=None, prior=None,
+               post=None, fit_transl=True, landmark_order=None, frames=None, _who="MorphableModel.fit_2d"):
+        """Adam on the device against 2-D key points in C calibrated views (the tracker's landmark reprojection term):
+        landmarks_2d [C,M,2] or [F,C,M,2] in pixels, K / RT as project_landmarks takes them, weights [C,M] or [F,C,M] (0 = not
+        detected; such a target may hold anything, NaN included).  Per frame E_f = lmk2d_lambda sum w |s (uv - target)|^2 / sum w
+        over the observations that count (w > 0, at least z_near in front of the camera, finite) + the vertex term of ``fit`` when
+        target_vertices is given + sum_p lam_p (p - p0_p)^2; s = 1 / max(H, W) of image_size = (H, W), the tracker's
+        normalisation, or 1 without one.  contour_2d [C,Md,2] or [F,C,Md,2] with contour_weights: the face contour, whose model
+        points slide with the head's yaw per view (the model needs dyn_lmk_face / dyn_lmk_bary); both sets share one sum of
+        weights.  landmark_order="ibug68": landmarks_2d (and weights) hold the 68 iBUG points, of which the first 17 (the jaw
+        line) go to the contour set and the other 51 to the static one; the model must have 51 static and 17 contour landmarks.
+        A single view with free shape and translation is scale-ambiguous: freeze or regularise the shape, or use two views.
+        Returns fit's dict (rms: the root mean square of reprojection_px's distances) plus uv [F,C,M,2], n_valid [F],
+        n_valid_history [iters,F], reprojection_px [F,C] (the mean pixel distance of the counted observations of a view, NaN where
+        none counts) and, with contours, rows [F,C] and contour_uv [F,C,Md,2]."""
+        who = _who
+        lrv, lam, p0 = self.fit_vectors(lr, free, reg, prior, fit_transl, who)
+        if self.lmk_face is None:
+            raise ValueError(f"{who}: the model has no landmark embedding")
+        M = self.lmk_face.shape[0]
+        ten = lambda t: None if t is None else (t if torch.is_tensor(t) else torch.as_tensor(np.asarray(t)))
+        lm2, w2, ct2, cw2, tv = ten(landmarks_2d), ten(weights), ten(contour_2d), ten(contour_weights), ten(target_vertices)
+        if lm2 is None or lm2.dim() not in (3, 4) or lm2.shape[-1] != 2:
+            raise ValueError(f"{who}: landmarks_2d must be [C,M,2] or [F,C,M,2], got {None if lm2 is None else tuple(lm2.shape)}")
+        if landmark_order == "ibug68":
+            if ct2 is not None or cw2 is not None:
+                raise ValueError(f"{who}: landmark_order='ibug68' takes the contour from landmarks_2d; do not pass contour_2d as well")
+            if self.dyn_lmk_face is None or self.dyn_lmk_face.shape[1] != 17 or M != 51 or lm2.shape[-2] != 68:
+                raise ValueError(f"{who}: landmark_order='ibug68' needs 68 points and a model with 51 static and 17 contour landmarks")
+            ct2, lm2 = lm2[..., :17, :], lm2[..., 17:, :]
+            if w2 is not None:
+                cw2, w2 = w2[..., :17], w2[..., 17:]
+        elif landmark_order is not None:
+            raise ValueError(f"{who}: landmark_order must be None or 'ibug68', got {landmark_order!r}")
+        lm2 = lm2[None] if lm2.dim() == 3 else lm2
+        C = lm2.shape[1]
+        if lm2.shape[2] != M:
+            raise ValueError(f"{who}: landmarks_2d has {lm2.shape[2]} points a view, the model {M} static landmarks")
+        Md = 0
+        if ct2 is not None:
+            if self.dyn_lmk_face is None:
+                raise ValueError(f"{who}: contour_2d given, and the model has no contour embedding")
+            Md = self.dyn_lmk_face.shape[1]
+            ct2 = ct2[None] if ct2.dim() == 3 else ct2
+            if ct2.dim() != 4 or tuple(ct2.shape[1:]) != (C, Md, 2):
+                raise ValueError(f"{who}: contour_2d must be [C,{Md},2] or [F,C,{Md},2] with C = {C}, got {tuple(ct2.shape)}")
+        elif cw2 is not None:
+            raise ValueError(f"{who}: contour_weights without contour_2d")
+        w2 = w2[None] if w2 is not None and w2.dim() == 2 else w2
+        cw2 = cw2[None] if cw2 is not None and cw2.dim() == 2 else cw2
+        for name, t, n in (("weights", w2, M), ("contour_weights", cw2, Md)):
+            if t is not None and (t.dim() != 3 or tuple(t.shape[1:]) != (C, n)):
+                raise ValueError(f"{who}: {name} must be [C,{n}] or [F,C,{n}] with C = {C}, got {tuple(t.shape)}")
+        tv = tv[None] if tv is not None and tv.dim() == 2 else tv
+        if tv is not None and (tv.dim() != 3 or tuple(tv.shape[1:]) != (self.V, 3)):
+            raise ValueError(f"{who}: target_vertices must be [F,{self.V},3] (the model's topology), got {tuple(tv.shape)}")
+        Kt, RTt = ten(K), ten(RT)
+        counts = [t.shape[0] for t in (lm2, w2, ct2, cw2, tv) if t is not None] + [1 if frames is None else int(frames)]
+        counts += [t.shape[0] for t in (Kt, RTt) if t.dim() == 4]
+        counts += [int(np.shape(val)[0]) for val in (init or {}).values() if val is not None and np.ndim(val) >= 2]
+        F = max(counts)
+        if F < 1 or any(c not in (1, F) for c in counts):
+            raise ValueError(f"{who}: the targets, weights, cameras, init and frames must agree on the number of frames (or be one), got {counts}")
+        grow = lambda t: None if t is None else (t if t.shape[0] == Ft else t.expand((Ft,) + tuple(t.shape[1:])))
+        Ft = max(t.shape[0] for t in (lm2, w2, ct2, cw2) if t is not None)
+        lm2, w2, ct2, cw2 = grow(lm2), grow(w2), grow(ct2), grow(cw2)
+        px_scale = 1.0
+        if image_size is not None:
+            hw = [float(x) for x in np.asarray(image_size).reshape(-1)]
+            if len(hw) not in (1, 2) or not all(0.0 < x < float("inf") for x in hw):
+                raise ValueError(f"{who}: image_size must be (H, W) or one positive number, got {image_size}")
+            px_scale = 1.0 / max(hw)
+        iters = int(iters)
+        if iters < 1:
+            raise ValueError(f"{who}: iters must be at least 1, got {iters}")
+        start = self._fit_init(who, init, F, p0, lrv)
+        if self.device.type != "cuda":
+            raise ValueError(f"{who}: the model is on {self.device}; the fitter runs on the GPU only (model.to('cuda:0'))")
+        dev = self.device
+        f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+        p = f32(start)
+        m, v = torch.zeros_like(p), torch.zeros_like(p)
+        hist, n_hist = E.morph_fit_2d_run(self, p, m, v, f32(lrv), f32(lam), f32(p0), iters, Kt, RTt, lm2, weight=w2, dyn_target_uv=ct2,
+                                          dyn_weight=cw2, z_near=z_near, px_scale=px_scale, lambda2=lmk2d_lambda, target=tv,
+                                          vertex_weight=vertex_weight, post=post)
+        NB, J = self.NB, self.J
+        out = {"betas": p[:, :NB].contiguous(), "pose": p[:, NB:NB + 3 * J].reshape(F, J, 3).contiguous(),
+               "transl": p[:, NB + 3 * J:].contiguous(), "loss_history": hist, "n_valid_history": n_hist}
+        fw = self.forward(out["betas"], out["pose"], post=post, transl=out["transl"])
+        out["vertices"] = fw["vertices"]
+        pr = self.project_landmarks(out["betas"], out["pose"], Kt, RTt, transl=out["transl"], post=post, z_near=z_near)
+        out["uv"] = pr["uv"]
+        got, want, ok, wt = [pr["uv"]], [lm2], [pr["valid"]], [w2]
+        if ct2 is not None:
+            out["rows"], out["contour_uv"] = pr["rows"], pr["contour_uv"]
+            got, want, ok, wt = got + [pr["contour_uv"]], want + [ct2], ok + [pr["contour_valid"]], wt + [cw2]
+        dist, counted = [], []
+        for g_, t_, o_, w_ in zip(got, want, ok, wt):
+            t_ = t_.to(device=dev, dtype=torch.float32)
+            c_ = o_ if w_ is None else o_ & (w_.to(dev) > 0)
+            d_ = (g_ - t_).square().sum(-1).sqrt()
+            dist.append(torch.where(c_, d_, torch.zeros_like(d_)))  # an uncounted target may be NaN
+            counted.append(c_.expand_as(d_))
+        dist, counted = torch.cat(dist, -1), torch.cat(counted, -1)
+        n = counted.sum(-1)
+        out["n_valid"] = n.sum(-1).to(torch.int32)
+        out["reprojection_px"] = dist.sum(-1) / n  # 0 / 0 = NaN: nothing counts in that view
+        out["rms"] = (dist.square().sum((-1, -2)) / n.sum(-1)).sqrt()
+        return out
+
+    def fit_flame_2d(self, landmarks_2d, K, RT, free=None, reg=None, prior=None, init=None, **kw):
+        """``fit_2d`` in ``flame``'s names, as fit_flame is to fit.  Returns fit_2d's dict and the six FLAME parts [F,n]."""
+        who = "MorphableModel.fit_flame_2d"
+        if self.J != len(FLAME_JOINTS):
+            raise ValueError(f"{who}: a FLAME model has {len(FLAME_JOINTS)} joints, this one {self.J}")
+        out = self.fit_2d(landmarks_2d, K, RT, free=free, reg=reg, prior=prior, init=init, _who=who, **kw)
+        flat = torch.cat([out["betas"], out["pose"].reshape(out["betas"].shape[0], -1)], 1)
+        g = self.param_groups()
+        out.update({k: flat[:, g[k]].contiguous() for k in ("shape", "expression", "global_pose", "neck", "jaw", "eyes")})
+        return out
+
     def flame(self, shape, expression=None, global_pose=None, neck=None, jaw=None, eyes=None, post=None, transl=None):
         """The reference's FLAME.forward (flame.py:252-279): betas = [shape, expression], full_pose = [global, neck, jaw, eyes]
         (3, 3, 3 and 6 numbers); missing parts are zero.  Every argument is a vector or has a leading frame axis; single rows
@@ -576,7 +751,8 @@ class MorphableModel:
 
     def to(self, device):
         self.device = torch.device(device)
-        for k in ("v_template", "basis", "weights", "j_template", "j_dirs", "faces", "lmk_face", "lmk_bary", "csr_ptr", "csr_ent"):
+        for k in ("v_template", "basis", "weights", "j_template", "j_dirs", "faces", "lmk_face", "lmk_bary", "csr_ptr", "csr_ent",
+                  "dyn_lmk_face", "dyn_lmk_bary", "ct_vert", "ct_ptr", "ct_ent"):
             if getattr(self, k) is not None:
                 setattr(self, k, getattr(self, k).to(self.device))
         return self
@@ -602,6 +778,61 @@ class _MorphFunction(torch.autograd.Function):
         g = model._backward(ctx.saved, ctx.post, g_verts, g_joints, g_lmk if model.lmk_face is not None else None)
         gb, gp, gt = (x.to(d) for x, d in zip((g["betas"], g["pose"].reshape(ctx.pose_shape), g["transl"]), ctx.dtypes))
         return None, None, None, gb, gp, gt
+
+
+class _ProjectFunction(torch.autograd.Function):
+    """project: mvd_op_morph_project, and in backward mvd_op_morph_project_bwd."""
+
+    @staticmethod
+    def forward(ctx, points, K, RT, z_near):
+        uv, valid = E.op_morph_project(points, K, RT, z_near)
+        ctx.save_for_backward(points, K, RT)
+        ctx.z_near = z_near
+        ctx.mark_non_differentiable(valid)
+        return uv, valid
+
+    @staticmethod
+    def backward(ctx, g_uv, _g_valid):
+        points, K, RT = ctx.saved_tensors
+        g = E.op_morph_project_bwd(points, K, RT, g_uv.contiguous(), ctx.z_near)
+        return g.to(points.dtype), None, None, None
+
+
+def project(points, K, RT, z_near=E.Z_NEAR_2D):
+    """points [F,M,3] (the landmarks, joints or vertices of ``MorphableModel.differentiable``, on the GPU) in C calibrated views, K
+    [C,3,3] / RT [C,3,4] or [F,C,...]: (uv [F,C,M,2] in pixels, valid [F,C,M] bool).  uv carries gradients to the points through
+    the library's own backward, so a 2-D objective of one's own can be written in torch; a view in which a point is not valid
+    (behind z_near, not finite) passes no gradient to it.  The cameras are constants."""
+    if not torch.is_tensor(points) or not points.is_cuda:
+        raise ValueError("project: points must be a tensor on the GPU")
+    K, RT = (t if torch.is_tensor(t) else torch.as_tensor(np.asarray(t)) for t in (K, RT))
+    uv, valid = _ProjectFunction.apply(points, K.detach().to(points.device), RT.detach().to(points.device), float(z_near))
+    return uv, valid != 0
+
+
+def reprojection_error(uv, target, weights=None, valid=None, thresholds=(2.0, 4.0, 8.0)):
+    """The read-out of a 2-D fit: uv and target [...,C,M,2] in pixels (tensors or arrays), weights [...,C,M] (0 = not detected) and
+    valid [...,C,M] (project's) or None.  Over the observations with weight > 0 that are valid, with a finite prediction and
+    target: {"mean_px" [...,C]: the mean pixel distance of a view (NaN where nothing counts), "pck" {threshold: [...,C]}: the
+    share of its points within that many pixels, "count" [...,C]}; float64 numpy."""
+    a = lambda t: np.asarray(t.detach().cpu() if torch.is_tensor(t) else t)
+    u, t = a(uv).astype(np.float64), a(target).astype(np.float64)
+    if u.shape != t.shape or u.ndim < 3 or u.shape[-1] != 2:
+        raise ValueError(f"reprojection_error: uv and target must both be [...,C,M,2], got {u.shape} and {t.shape}")
+    ok = np.isfinite(u).all(-1) & np.isfinite(t).all(-1)
+    for name, x in (("weights", weights), ("valid", valid)):
+        if x is not None:
+            x = a(x)
+            if x.shape != u.shape[:-1]:
+                raise ValueError(f"reprojection_error: {name} must be {list(u.shape[:-1])}, got {x.shape}")
+            ok &= x > 0
+    d = np.where(ok, np.sqrt(((np.where(ok[..., None], u - t, 0.0)) ** 2).sum(-1)), 0.0)
+    n = ok.sum(-1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out = {"mean_px": d.sum(-1) / n, "count": n, "pck": {}}
+        for thr in thresholds:
+            out["pck"][float(thr)] = (ok & (d <= float(thr))).sum(-1) / n
+    return out
 
 
 def flame_alignment() -> torch.Tensor:
